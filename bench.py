@@ -36,6 +36,8 @@ FLOP_PER_POINT_TRIAL = 800   # structure refine, per point per LM 
 FLOP_PER_POINT_RETRIAL = 350
 PEAK_FP64_VALU_TFLOPS = 78.6  # MI355X fp64 vector peak (256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz)
 PEAK_HBM_GBS = 8000.0
+DUMP_SEED = 20200901        # --dump-outputs: the fixed frame sample of the outputs too large to write whole
+DUMP_POSES, DUMP_FRAMES = 65536, 256  # poses written / frames whose points and associations are written (at most ~20 MB in all)
 
 
 def make_workload(B, seed0=20200901):
@@ -261,6 +263,27 @@ def stub_bench(args, ranks):
     ranks.close()
 
 
+def dump_outputs(out_dir, pose, Xw, assoc):
+    """--dump-outputs: what the caller of gl_track_frames received from the last timed step - the refined poses (B, 7), the
+    refined map points (B, M, 3) and the gated associations (B, M), -1 = none - as float64 .npy files.  Frames beyond
+    DUMP_POSES / DUMP_FRAMES are represented by a fixed, seeded sample (frame_index.npy / pose_frame_index.npy name them)."""
+    import torch
+    B = pose.shape[0]
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def pick(n):
+        return np.arange(B) if n >= B else np.sort(rng.choice(B, n, replace=False))
+    pose_rows, frame_rows = pick(DUMP_POSES), pick(DUMP_FRAMES)
+
+    def host(t, rows):
+        return t[torch.from_numpy(rows).to(t.device)].cpu().numpy().astype(np.float64)
+    arrays = {"pose": host(pose, pose_rows), "pose_frame_index": pose_rows.astype(np.float64),
+              "Xw": host(Xw, frame_rows), "assoc": host(assoc, frame_rows), "frame_index": frame_rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def refine_flop(points, trials, outer):
     """algorithmic flop of the structure refine: an outer Levenberg iteration linearises (800 flop per point); a trial
     beyond the first of an iteration only re-damps, re-solves and re-evaluates (350)"""
@@ -355,6 +378,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true",
                     help="the timed step only (what tools/profile_bench.sh profiles: the two-stream / sweep / class legs launch the same kernels)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (rank 0: refined poses, map points, associations; "
+                         "a fixed seeded frame sample where the batch is large) to DIR/<name>.npy, float64")
     ap.add_argument("--cpu-baseline-worker", nargs=2, metavar=("SEED", "BUDGET_S"), help=argparse.SUPPRESS)
     # tests of the launch plumbing: "gloo" = the whole path on CPU with a stand-in step; "nccl-dry" = the REAL backend selection
     # (Ranks("nccl"): set_device, init_process_group over RCCL, barrier / MAX / gather on device tensors) with the stand-in step -
@@ -404,10 +430,13 @@ def main():
     edges = torch.zeros((B, 2), dtype=torch.int32, device=dev)
     ctx.set_edge_stats_buffer(edges)     # ... and the level-0 reprojection edges those trials / iterations ran on
 
+    last = {}
+
     def step():
         pose.copy_(pose0)
         Xw.copy_(Xw0)
-        return gmmloc_amd.track_frames(ctx, gmm, cam, prm, pose, Xw, obs, octv, want_d2=False)
+        last["out"] = gmmloc_amd.track_frames(ctx, gmm, cam, prm, pose, Xw, obs, octv, want_d2=False)
+        return last["out"]
 
     def start_timers():
         ctx.timing(True)
@@ -417,6 +446,8 @@ def main():
 
     with torch.cuda.stream(ctx.stream):
         dt = launch.timed_steps(step, args.steps, args.warmup, ranks, before_timed=start_timers)
+        if args.dump_outputs and rank == 0:  # (before the legs below reuse pose / Xw)
+            dump_outputs(args.dump_outputs, pose, Xw, last["out"][0])
     per_rank_rate = ranks.gather(B * args.steps / ranks.last_own_dt)  # each rank's own clock around its own steps (the headline uses the MAX)
     n_trials = float(trials.sum().item())  # (of the last timed step; the legs below reuse the buffers)
     n_outer = float(outer.sum().item())

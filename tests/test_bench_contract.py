@@ -34,7 +34,7 @@ def test_cpu_baseline_leg_runs_without_gpu():
 def test_bench_cli_accepts_the_driver_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs"):
         assert flag in out.stdout
 
 
@@ -137,6 +137,38 @@ def test_bench_line_contract_live():
     assert lat["speedup_vs_cpu_same_math_brute"] >= 50.0  # north-star latency target, against the same arithmetic
     if d["cpu_baseline"]["reference_algorithm"] is not None:
         assert lat["speedup_vs_cpu_reference_algorithm"] >= 50.0  # ... and against the reference's kd-tree algorithm
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_live(tmp_path):
+    """--dump-outputs: the last timed step's results as float64 .npy files; the inputs are fixed, so two runs with other step
+    counts write the same bits, and the refined poses stay unit quaternions with every association in range or -1."""
+    import numpy as np
+    lines, dirs = [], []
+    for steps in (1, 3):
+        d = tmp_path / ("s%d" % steps)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                              "--batch", "300", "--no-extra-legs", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(json.loads([l for l in out.stdout.strip().split("\n") if l.startswith("{")][0]))
+        dirs.append(d)
+    assert [l["steps"] for l in lines] == [1, 3] and all(l["ms_per_step"] > 0 for l in lines)
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == ["Xw.npy", "assoc.npy", "frame_index.npy", "pose.npy", "pose_frame_index.npy"]
+    assert sorted(p.name for p in dirs[1].iterdir()) == names
+    a = {n[:-4]: np.load(dirs[0] / n) for n in names}
+    for n in names:
+        b = np.load(dirs[1] / n)
+        assert a[n[:-4]].dtype == np.float64 and np.array_equal(a[n[:-4]], b), n
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    B, M, S = 300, 2000, 256  # every pose; the points and associations of a seeded sample of 256 of the 300 frames
+    assert a["pose"].shape == (B, 7) and np.array_equal(a["pose_frame_index"], np.arange(B))
+    fi = a["frame_index"]
+    assert fi.shape == (S,) and (np.diff(fi) > 0).all() and fi[0] >= 0 and fi[-1] < B
+    assert a["Xw"].shape == (S, M, 3) and a["assoc"].shape == (S, M)
+    assert np.abs(np.linalg.norm(a["pose"][:, :4], axis=1) - 1).max() < 1e-6  # (qx qy qz qw tx ty tz)
+    assert ((a["assoc"] >= -1) & (a["assoc"] < 4096)).all() and (a["assoc"] >= 0).mean() > 0.5
 
 
 def test_bench_gpus_n_walks_the_nccl_path_up_to_the_first_device_call(monkeypatch):

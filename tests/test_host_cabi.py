@@ -10,9 +10,6 @@ import pytest
 
 from tests.conftest import ROOT, GOLDEN
 
-REF_MAP = "/root/reference/gmmloc_ros/data/map"
-
-
 @pytest.fixture(scope="module")
 def lib():
     from gmmloc_amd import _lib
@@ -91,12 +88,12 @@ def test_gmm_file_errors(lib, tmp_path):
     assert np.array_equal(m, [[1.0, 2.0, 3.0]]) and np.array_equal(c.reshape(3, 3), np.eye(3))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MAP), reason="reference data files not present")
 @pytest.mark.parametrize("name", ["v1", "v2"])
 def test_reader_on_the_shipped_maps(lib, name):
-    """The C++ reader on the reference's own .gmm files == the independently decoded fixture."""
+    """The C++ reader on the reference's own .gmm files (tests/golden/v{1,2}.gmm, byte-for-byte copies made by
+    tools/make_map_fixtures.py) == the independently decoded fixture."""
     from gmmloc_amd import api
-    m, c = api.read_gmm_file(os.path.join(REF_MAP, name + ".gmm"))
+    m, c = api.read_gmm_file(os.path.join(GOLDEN, name + ".gmm"))
     d = np.load(os.path.join(GOLDEN, "map_%s.npz" % name))
     assert np.array_equal(m, d["mean"]) and np.array_equal(c, d["cov"])
     assert m.shape[0] == {"v1": 3299, "v2": 5096}[name]

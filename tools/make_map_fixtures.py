@@ -6,12 +6,14 @@ Run HERE (the container that has /root/reference); the outputs are data only:
                                          (gmmloc_ros/data/map/v{1,2}.gmm)
   tests/golden/gt_sync.npz               per sequence: N x 8 (t x y z qx qy qz qw)
                                          (gmmloc_ros/data/gt_sync/*.txt)
+  tests/golden/v1.gmm, v2.gmm            the two map files themselves, byte for byte (the input of
+                                         the C++ reader's test, tests/test_host_cabi.py)
 The .gmm framing is the voxblox-style stream written by
 gmmloc/src/utils/protobuf_utils.cpp:31-40,82-100: varint32 count, then per
 component varint32 size + ComponentProto (gmmloc/proto/gmmloc/GMM.proto:5-14).
 This is an independent pure-python reader (the product's reader is C++).
 """
-import os, struct, sys
+import os, shutil, struct, sys
 import numpy as np
 
 REF = os.environ.get("GMMLOC_REF", "/root/reference")
@@ -63,7 +65,9 @@ def read_gmm(path):
 def main():
     os.makedirs(OUT, exist_ok=True)
     for name in ("v1", "v2"):
-        m, c = read_gmm(os.path.join(REF, "gmmloc_ros/data/map/%s.gmm" % name))
+        src = os.path.join(REF, "gmmloc_ros/data/map/%s.gmm" % name)
+        m, c = read_gmm(src)
+        shutil.copyfile(src, os.path.join(OUT, name + ".gmm"))
         np.savez_compressed(os.path.join(OUT, "map_%s.npz" % name), mean=m, cov=c)
         print(name, m.shape, c.shape)
     seqs = {}

@@ -60,7 +60,6 @@ struct BafKArgs {
   FixedV fxv;
   int32_t* edges_out;
   int* frame_ctr;
-  double* un_scratch;  // the two-groups-per-wave instance: 6 x 2000 doubles per workgroup of the launch (the points' hand-over slots)
 };
 __host__ __device__ inline PrepView prep_view(double* scratch, int B, int L) {
   PrepView v;
@@ -81,9 +80,6 @@ __host__ __device__ inline PrepView prep_view(double* scratch, int B, int L) {
 // point and pass).  The order is a function of the frame's data alone, so the canonical summation order built on it stays
 // independent of the launch shape and of the batch.
 constexpr int PREP_T = 256, PREP_C = 8;  // rounds of 256 consecutive points: frames up to 2 048 points
-#ifndef GL_PREP_EMPTY_LAST
-#define GL_PREP_EMPTY_LAST 1  // (0: the order of rounds 3 - 5, for A/B runs: profiles/r6_track_sparse.txt)
-#endif
 __global__ __launch_bounds__(PREP_T) void k_ba1_prep(BaK k, GmmDev gm, int B, int L, const double* __restrict__ obs_all,
                                                     const int32_t* __restrict__ oct_all, int32_t* __restrict__ assoc_all,
                                                     const double* __restrict__ d2_all, double* __restrict__ scratch,
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(PREP_T) void k_ba1_prep(BaK k, GmmDev gm, int B, in
       fl_[j] = fl;
     }
     const unsigned long long bal = __ballot((fl_[j] & 12) == 4);  // associated and not degenerate
-    const unsigned long long bal0 = __ballot(GL_PREP_EMPTY_LAST && fl_[j] == 0 && j < rounds && j * PREP_T + tid < L);  // no map point in the slot
+    const unsigned long long bal0 = __ballot(fl_[j] == 0 && j < rounds && j * PREP_T + tid < L);  // no map point in the slot
     if (lane == 0) {
       cnt[j][wave] = __popcll(bal);
       cnt0[j][wave] = __popcll(bal0);
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(PREP_T) void k_ba1_prep(BaK k, GmmDev gm, int B, in
   // non-degenerate components, the slots without a map point.  The reference's frame has one slot per FEATURE (1 200) and a few hundred
   // map points: with the empty slots LAST the chunks behind the frame's points hold nothing, every wave skips them with one test
   // (load_pt: no active edge in any lane), and since a group's chunks are interleaved (g, g + G, ...) the points still spread evenly
-  // over the waves - the refine costs what its POINTS cost, not what its slots cost.
+  // over the waves - the refine costs what its POINTS cost, not what its slots cost (profiles/r6_track_sparse.txt).
   const int n_others = L - total - total0, n_exist = L - total0;
   const double ifx = 1.0 / k.fx, ify = 1.0 / k.fy;
   int base = 0, base0 = 0;  // non-degenerate-component points / empty slots before this (round, wave)
@@ -180,7 +176,7 @@ __global__ __launch_bounds__(PREP_T) void k_ba1_prep(BaK k, GmmDev gm, int B, in
       }
     const int l = j * PREP_T + tid;
     const bool isnd = (fl_[j] & 12) == 4;
-    const bool isempty = GL_PREP_EMPTY_LAST && fl_[j] == 0 && j < rounds && l < L;
+    const bool isempty = fl_[j] == 0 && j < rounds && l < L;
     const unsigned long long bal = __ballot(isnd), bal0 = __ballot(isempty);
     const int before = base + __popcll(bal & ((1ull << lane) - 1ull));
     const int before0 = base0 + __popcll(bal0 & ((1ull << lane) - 1ull));
@@ -214,270 +210,57 @@ __global__ __launch_bounds__(PREP_T) void k_ba1_prep(BaK k, GmmDev gm, int B, in
 }
 }  // namespace
 
-// (namespace, LDS capacity in points, waves at most, SPREAD, fp32-cached step, gauge anchor of the pose)
+// The instances of gl_ba_fast_impl.hpp: per namespace, its LDS capacity in points, waves at most, SPREAD (latency shape) or DENSE,
+// fp32-cached point step (option ba_step32), gauge anchor of the pose (prior edge / fixed pose), fixed observer key-frames.
+// -DGL_BAF_QUICK builds the first two alone (tools/baf_quick.sh: register / ISA checks).
+namespace {
+struct BafCfg {
+  int mcap, nw;
+  bool spread, step32, prior, fixed;
+};
+namespace bafd2000 { constexpr BafCfg kCfg{2000, 8, false, false, false, false}; }     // DENSE, exact step: 1 frame per CU
+namespace bafs { constexpr BafCfg kCfg{256, 8, true, false, false, false}; }           // SPREAD, exact step
 #ifndef GL_BAF_QUICK
-#define GL_BAF_NS bafd496  // DENSE, exact step: 4 frames per CU
-#define GL_BAF_MCAP 496
-#define GL_BAF_NW 2
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 0
-#define GL_BAF_FIXED 0
-#include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
+namespace bafd496 { constexpr BafCfg kCfg{496, 2, false, false, false, false}; }       // 4 frames per CU
+namespace bafd1000 { constexpr BafCfg kCfg{1000, 4, false, false, false, false}; }     // 2 frames per CU
+namespace bafs32 { constexpr BafCfg kCfg{256, 8, true, true, false, false}; }          // fp32-cached step: the SPREAD kernel
+namespace bafd2000s32 { constexpr BafCfg kCfg{2000, 8, false, true, false, false}; }   // ... and the largest DENSE class
+namespace bafd496p { constexpr BafCfg kCfg{496, 2, false, false, true, false}; }       // anchored (gl_track_frames_anchored), exact step
+namespace bafd1000p { constexpr BafCfg kCfg{992, 4, false, false, true, false}; }      // (992: two frames per CU with the prior edge's records)
+namespace bafd2000p { constexpr BafCfg kCfg{2000, 8, false, false, true, false}; }
+namespace bafsp { constexpr BafCfg kCfg{256, 8, true, false, true, false}; }
+namespace bafd496f { constexpr BafCfg kCfg{496, 2, false, false, true, true}; }        // anchored with fixed observer key-frames (F = 1 .. 4),
+namespace bafd1000f { constexpr BafCfg kCfg{984, 4, false, false, true, true}; }       // batch shape (984: with the key-frames' poses too)
+namespace bafd2000f { constexpr BafCfg kCfg{2000, 8, false, false, true, true}; }
 #endif
-
+}  // namespace
+#define GL_BAF_NS bafd2000
+#include "gl_ba_fast_impl.hpp"
+#define GL_BAF_NS bafs
+#include "gl_ba_fast_impl.hpp"
 #ifndef GL_BAF_QUICK
-#define GL_BAF_NS bafd1000  // 2 frames per CU
-#define GL_BAF_MCAP 1000
-#define GL_BAF_NW 4
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 0
-#define GL_BAF_FIXED 0
+#define GL_BAF_NS bafd496
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-#define GL_BAF_NS bafd2000  // 1 frame per CU
-#if GL_BAF_W3
-#define GL_BAF_MCAP 1984
-#define GL_BAF_NW 12
-#define GL_BAF_THREADS 768
-#else
-#define GL_BAF_MCAP 2000
-#define GL_BAF_NW 8
-#endif
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 0
-#define GL_BAF_FIXED 0
+#define GL_BAF_NS bafd1000
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_THREADS
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-
-#define GL_BAF_NS bafs  // SPREAD (latency shape), exact step
-#define GL_BAF_MCAP 256
-#define GL_BAF_NW 8
-#define GL_BAF_SPREAD 1
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 0
-#define GL_BAF_FIXED 0
+#define GL_BAF_NS bafs32
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-
-// fp32-cached point step (option ba_step32): the SPREAD kernel and the largest DENSE class
-#ifndef GL_BAF_QUICK
-#define GL_BAF_NS bafs32  // 
-#define GL_BAF_MCAP 256
-#define GL_BAF_NW 8
-#define GL_BAF_SPREAD 1
-#define GL_BAF_STEP32 1
-#define GL_BAF_PRIOR 0
-#define GL_BAF_FIXED 0
+#define GL_BAF_NS bafd2000s32
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-#ifndef GL_BAF_QUICK
-#define GL_BAF_NS bafd2000s32  // 
-#define GL_BAF_MCAP 2000
-#define GL_BAF_NW 8
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 1
-#define GL_BAF_PRIOR 0
-#define GL_BAF_FIXED 0
+#define GL_BAF_NS bafd496p
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-// anchored instances (gl_track_frames_anchored: prior edge on the frame's pose, or fixed pose), exact step
-#ifndef GL_BAF_QUICK
-#define GL_BAF_NS bafd2000x  // 2 frames per CU: two groups of the canonical order per wave, the hand-over slots in global memory (GL_BAF_GPW)
-#define GL_BAF_MCAP 2000
-#define GL_BAF_NW 8
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 0
-#define GL_BAF_FIXED 0
-#undef GL_BAF_GPW
-#define GL_BAF_GPW 2
+#define GL_BAF_NS bafd1000p
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_GPW
-#define GL_BAF_GPW 1
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-#ifndef GL_BAF_QUICK
-#define GL_BAF_NS bafd496p  // 
-#define GL_BAF_MCAP 496
-#define GL_BAF_NW 2
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 1
-#define GL_BAF_FIXED 0
+#define GL_BAF_NS bafd2000p
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-#ifndef GL_BAF_QUICK
-#define GL_BAF_NS bafd1000p  // (992 points: two frames per CU with the 512 bytes of the prior edge's records)
-#define GL_BAF_MCAP 992
-#define GL_BAF_NW 4
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 1
-#define GL_BAF_FIXED 0
+#define GL_BAF_NS bafsp
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-#ifndef GL_BAF_QUICK
-#define GL_BAF_NS bafd2000p  // 
-#define GL_BAF_MCAP 2000
-#define GL_BAF_NW 8
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 1
-#define GL_BAF_FIXED 0
-#include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-#ifndef GL_BAF_QUICK
-#define GL_BAF_NS bafsp  // 
-#define GL_BAF_MCAP 256
-#define GL_BAF_NW 8
-#define GL_BAF_SPREAD 1
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 1
-#define GL_BAF_FIXED 0
-#include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-// anchored instances WITH fixed observer key-frames (F = 1 .. 4; the prior edge / fixed pose stays a per-frame flag), batch shape
-#ifndef GL_BAF_QUICK
 #define GL_BAF_NS bafd496f
-#define GL_BAF_MCAP 496
-#define GL_BAF_NW 2
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 1
-#define GL_BAF_FIXED 1
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-#ifndef GL_BAF_QUICK
-#define GL_BAF_NS bafd1000f  // (984 points: two frames per CU with the prior edge's records and the key-frames' poses)
-#define GL_BAF_MCAP 984
-#define GL_BAF_NW 4
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 1
-#define GL_BAF_FIXED 1
+#define GL_BAF_NS bafd1000f
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-#ifndef GL_BAF_QUICK
 #define GL_BAF_NS bafd2000f
-#define GL_BAF_MCAP 2000
-#define GL_BAF_NW 8
-#define GL_BAF_SPREAD 0
-#define GL_BAF_STEP32 0
-#define GL_BAF_PRIOR 1
-#define GL_BAF_FIXED 1
 #include "gl_ba_fast_impl.hpp"
-#undef GL_BAF_NS
-#undef GL_BAF_MCAP
-#undef GL_BAF_NW
-#undef GL_BAF_SPREAD
-#undef GL_BAF_STEP32
-#undef GL_BAF_PRIOR
-#undef GL_BAF_FIXED
-#endif
-
-#ifndef GL_BAF_QUICK  // (tools/baf_quick.sh: the 2 000-point batch instance and the latency shape alone, for register / ISA checks)
 namespace {
 // HW_REG_XCC_ID (hwreg 20, 4 bits): the XCD the wave runs on
 __device__ __forceinline__ int xcc_id() { return __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 15; }
@@ -516,12 +299,9 @@ bool probe_xcc_ids(Ctx* c) {
 bool ba1_fast_supported(int L) { return L <= 2000; }
 
 // the canonical summation order of a frame of stride L (gl_ba_fast_impl.hpp): G groups of S chunks of 64 points
-#ifndef GL_BAF_W3
-#define GL_BAF_W3 0  // EXPERIMENT (profiles/r5_w3_*.txt): the largest class at THREE waves per SIMD - groups of 3 chunks, 12 waves, 168 registers
-#endif
 static void canon_order(int L, int* G, int* S) {
   const int nch = (L + 63) / 64;
-  *G = (GL_BAF_W3 && L > 1000) ? (nch + 2) / 3 : (nch + 3) / 4;
+  *G = (nch + 3) / 4;
   *S = (nch + *G - 1) / *G;
 }
 
@@ -562,19 +342,12 @@ static int launch_dense(Ctx* c, BafArgs& a) {
   // (the anchored middle classes give 8 / 16 points for the prior edge's LDS records and the key-frames' poses)
   const int mid = fixed ? 984 : a.prior ? 992 : 1000;
   const int cap = s32 ? 2000 : (a.L <= 496 ? 496 : a.L <= mid ? mid : 2000);
-  const BafKernel kern0 = s32 ? bafd2000s32::k_ba1_fast
+  const BafKernel kern = s32 ? bafd2000s32::k_ba1_fast
                          : fixed ? (cap == 496 ? bafd496f::k_ba1_fast : cap == 984 ? bafd1000f::k_ba1_fast : bafd2000f::k_ba1_fast)
                          : a.prior ? (cap == 496 ? bafd496p::k_ba1_fast : cap == 992 ? bafd1000p::k_ba1_fast : bafd2000p::k_ba1_fast)
                                    : (cap == 496 ? bafd496::k_ba1_fast : cap == 1000 ? bafd1000::k_ba1_fast : bafd2000::k_ba1_fast);
-  // the largest class, plain refine: two frames per CU (bafd2000x: two groups per wave, hand-over slots in global memory; same bits)
-  const bool two = !GL_BAF_W3 && c->opt.ba_two_frames != 0 && kern0 == bafd2000::k_ba1_fast && !a.ctl;
-  const BafKernel kern = two ? bafd2000x::k_ba1_fast : kern0;
-  const int threads = two ? 64 * std::min(a.G, 4) : 64 * a.G;
-  const bool w3 = GL_BAF_W3 && kern == bafd2000::k_ba1_fast;  // (experiment: 12 groups' totals, MCAP 1984)
-  if (w3 && a.L > 1984) return GL_ERR_ARG;
-  const size_t lds = w3 ? (size_t)(10 * 1984 + 12 * 32 + 64 + 24 + 24) * sizeof(double)
-                     : two ? (size_t)(4 * cap + 8 * 32 + 64 + 40) * sizeof(double)
-                        : (size_t)(10 * cap + (cap == 496 ? 2 : cap <= 1000 ? 4 : 8) * 32 + 64 + 40 + (anch ? 64 + (cap == 496 ? 108 : 0) : 0) + (fixed ? 48 : 0)) * sizeof(double);
+  const int threads = 64 * a.G;
+  const size_t lds = (size_t)(10 * cap + (cap == 496 ? 2 : cap <= 1000 ? 4 : 8) * 32 + 64 + 40 + (anch ? 64 + (cap == 496 ? 108 : 0) : 0) + (fixed ? 48 : 0)) * sizeof(double);
   GL_HIP(ensure_dynamic_lds(c, (const void*)kern, lds));
   a.NB = 1;
   a.parts = nullptr;
@@ -594,13 +367,8 @@ static int launch_dense(Ctx* c, BafArgs& a) {
       fctr = a.fctr;
     }
   }
-  void* un = nullptr;  // (bafd2000x: 96 KB of hand-over slots per workgroup of the launch, in the context's second scratch block)
-  if (two) {
-    const int rc = gl::ctx_scratch_b(c, (size_t)grid * 6 * 2000 * sizeof(double), &un);
-    if (rc != GL_OK) return rc;
-  }
   const BafKArgs ka{a.k, a.gm, a.B, a.L, a.G, a.S, a.pose, a.pts, a.assoc, a.dropped, a.erase, a.iters, a.pn, a.stats, a.NB, a.parts, a.ctl, 0ll, 0, a.oct, a.prior,
-                    a.prior_mi, a.stage, a.nb_prev, a.counters, a.stats_iters, a.fx, a.stats_edges, fctr, (double*)un};
+                    a.prior_mi, a.stage, a.nb_prev, a.counters, a.stats_iters, a.fx, a.stats_edges, fctr};
   kern<<<grid, threads, lds, c->stream>>>(ka);
   GL_HIP(hipGetLastError());
   return GL_OK;
@@ -640,7 +408,7 @@ static int launch_spread(Ctx* c, BafArgs& a, void* scratch) {
   // (NB > 1: 64 block indices per 8 frames, the kernel's map from block to (frame, group) keeps a frame on one XCD)
   const int grid = a.NB > 1 ? 64 * ((a.B + 7) / 8) : a.B;
   const BafKArgs ka{a.k, a.gm, a.B, a.L, a.G, a.S, a.pose, a.pts, a.assoc, a.dropped, a.erase, a.iters, a.pn, a.stats, a.NB, a.parts, a.ctl, limit,
-                    (c->xcc_ids_trusted && c->opt.ba_same_xcd != 0) ? 1 : 0, a.oct, a.prior, a.prior_mi, a.stage, 0, a.counters, a.stats_iters, a.fx, a.stats_edges, nullptr, nullptr};
+                    (c->xcc_ids_trusted && c->opt.ba_same_xcd != 0) ? 1 : 0, a.oct, a.prior, a.prior_mi, a.stage, 0, a.counters, a.stats_iters, a.fx, a.stats_edges, nullptr};
   kern<<<grid, 256, lds, c->stream>>>(ka);
   GL_HIP(hipGetLastError());
   return a.NB > 1 ? 2 : GL_OK;  // 2: follow up with DENSE for the frames that did not complete

@@ -1,4 +1,5 @@
-// (included by gl_ba_fast.hip once per instance: GL_BAF_NS / GL_BAF_MCAP / GL_BAF_NW / GL_BAF_SPREAD / GL_BAF_STEP32 / GL_BAF_PRIOR / GL_BAF_FIXED)
+// (included by gl_ba_fast.hip once per instance: GL_BAF_NS names the namespace, whose kCfg - declared there - holds the
+// instance's parameters; #undefs GL_BAF_NS at the end)
 // On-chip fast path of the single-pose structure-constrained refinement (same algorithm and control flow as
 // k_ba1 in gl_ba.hip, which stays as the general / large-M path and as the A/B reference), M <= 2000 points.
 //
@@ -28,7 +29,7 @@
 // chi2 (1 fp64) and a 48-byte slot with two lifetimes: between the two passes of a Levenberg trial it holds
 // the L Delta L^T factors of the damped point block D (6 fp64) of pass A, so that pass B computes the point step
 //     eps = D^-1 (b - A (omega x q + upsilon)) = D^-1 (Jpi^T W (e - Jpi gd) + b_gmm)
-// exactly in fp64 from the re-evaluated residual (no fp32 anywhere; GL_BAF_STEP32 instead caches the fp32
+// exactly in fp64 from the re-evaluated residual (no fp32 anywhere; the kStep32 instances instead cache the fp32
 // pair {u = D^-1 b, A D^-1} of round 1: ~8 % faster, but its 1e-7 step error is amplified by badly conditioned
 // frames - off by default, gl_ctx_set_option("ba_step32", 1)); after pass B the slot holds the backup of the
 // point while the trial point sits in place (nothing to copy on acceptance).  80 B/point.
@@ -37,58 +38,16 @@
 namespace {
 namespace GL_BAF_NS {
 
-constexpr int MCAP = GL_BAF_MCAP;  // LDS capacity in points
-#if GL_BAF_SPREAD
-constexpr bool kSpread = true;
-#else
-constexpr bool kSpread = false;
-#endif
-#if GL_BAF_STEP32
-constexpr bool kStep32 = true;
-#else
-constexpr bool kStep32 = false;
-#endif
-#if GL_BAF_PRIOR
-constexpr bool kPrior = true;   // instance with the gauge anchor of the pose (prior edge / fixed pose); the plain instances
-#else                           // carry none of its code, so their register allocation is that of the unanchored refine
-constexpr bool kPrior = false;
-#endif
-#if GL_BAF_FIXED
-constexpr bool kFixed = true;   // instance with fixed observer key-frames (gl_track_frames_anchored, F = 1 .. 4): further reprojection
-#else                           // edges of the frame's points with FIXED pose vertices (localization_opt.cpp:491-516, 706-760)
-constexpr bool kFixed = false;
-#endif
-#ifndef GL_BAF_DYNB
-#define GL_BAF_DYNB 0  // measured (profiles/r5_ab_dynb.txt): same bits, the waves end pass B together - and the refine takes 10 % LONGER
-#endif
-#ifndef GL_BAF_DYNB_PRIO
-#define GL_BAF_DYNB_PRIO 1
-#endif
-// DENSE, exact step: the chunks of pass B are dealt DYNAMICALLY (optimize_fast); not with the fp32 cache, whose words fill the slot
-constexpr bool kDynB = !kSpread && !kStep32 && GL_BAF_DYNB != 0;
-#ifndef GL_BAF_ASYM
-#define GL_BAF_ASYM 0
-#endif
-constexpr bool kAsym = GL_BAF_ASYM != 0 && GL_BAF_NW == 8;  // uneven deal of the chunks over the two waves of a SIMD (slot_off)
-#ifndef GL_BAF_ALLSOLVE
-#define GL_BAF_ALLSOLVE 0  // measured (profiles/r5_ab_allsolve.txt): same bits, refine 10.80 -> 11.09 ms per 4 096 frames - seven more waves issuing the ~350 dependent instructions cost more than the hand-over they save
-#endif
-constexpr bool kAllSolve = !kSpread && GL_BAF_ALLSOLVE != 0;  // DENSE: every wave solves the reduced system itself (optimize_fast)
-constexpr int NWC = GL_BAF_NW;             // DENSE: GROUPS of the canonical order a frame of this LDS class has at most (= its waves, but see GPW)
-#ifndef GL_BAF_GPW
-#define GL_BAF_GPW 1
-#endif
-// GPW = 2 (the `x` instance of the largest class): a wave owns TWO groups of the canonical order - g and g + 4, four slots each, a
-// reduce-scatter after each group's slots, so every sum is added exactly as by eight waves - and the 48-byte hand-over slot of a
-// point (factors of pass A / backup of pass B) lives in GLOBAL memory, written and read back by the thread that owns the point.
-// The frame then needs 4 waves and 32 B of LDS per point: TWO frames per CU like the 1 000-point class, one wave of each per SIMD
-// (no older / younger wave of the same frame, one frame's solve behind the other's passes).
-constexpr int GPW = GL_BAF_GPW;
-constexpr bool kTwo = GPW == 2;
-constexpr int NWV = NWC / GPW;             // waves of a frame at most
-static_assert(GPW == 1 || (GPW == 2 && NWC == 8 && !kSpread && !kStep32), "two groups per wave: the plain batch instance of the 2 000-point class");
-constexpr int NRED = kSpread ? 1 : NWC;    // group totals kept in LDS (a SPREAD workgroup is ONE group)
-constexpr int TSP = 256;                   // SPREAD: threads of a workgroup = the <= 4 slot waves of its group
+constexpr int MCAP = kCfg.mcap;        // LDS capacity in points
+constexpr bool kSpread = kCfg.spread;  // SPREAD kernel (latency shape), else DENSE
+constexpr bool kStep32 = kCfg.step32;  // fp32-cached point step (option ba_step32)
+constexpr bool kPrior = kCfg.prior;    // instance with the gauge anchor of the pose (prior edge / fixed pose); the plain instances
+                                       // carry none of its code, so their register allocation is that of the unanchored refine
+constexpr bool kFixed = kCfg.fixed;    // instance with fixed observer key-frames (gl_track_frames_anchored, F = 1 .. 4): further reprojection
+                                       // edges of the frame's points with FIXED pose vertices (localization_opt.cpp:491-516, 706-760)
+constexpr int NWC = kCfg.nw;           // DENSE: GROUPS of the canonical order a frame of this LDS class has at most (= its waves)
+constexpr int NRED = kSpread ? 1 : NWC;  // group totals kept in LDS (a SPREAD workgroup is ONE group)
+constexpr int TSP = 256;                 // SPREAD: threads of a workgroup = the <= 4 slot waves of its group
 
 #ifdef GL_BA_TRACE  // debug build: (currentChi, tempChi, lambda, rho) of every Levenberg trial of frame 0 -> its points
 __device__ double g_trace[10 * 128];
@@ -267,7 +226,7 @@ struct Lds {      // per-frame state, SoA over MCAP points (index = local point 
   double* sp;     // 3 x MCAP  current point (world)
   double* chir;   // MCAP      stale chi2 of the reprojection edge (e->chi2())
   // 6 x MCAP doubles, two lifetimes sharing one slot per point:
-  //   pass A -> pass B : the factors of D (ldl3_factor_fast, 6 fp64)   [GL_BAF_STEP32: 12 fp32 words {u = D^-1 b (3), A D^-1 (3x3)}]
+  //   pass A -> pass B : the factors of D (ldl3_factor_fast, 6 fp64)   [kStep32: 12 fp32 words {u = D^-1 b (3), A D^-1 (3x3)}]
   //   pass B -> accept : backup of the point (3 fp64) while the trial point sits in `sp`; restored only
   //                      when the trial is rejected.
   double* un;
@@ -284,25 +243,15 @@ struct Lds {      // per-frame state, SoA over MCAP points (index = local point 
   int F, Lf;
 };
 // per-point flag bits + octave (bits 8..10) live in REGISTERS: 16 bits per point slot of the thread
-template <bool TWO>
-struct FwHi {
-  typedef unsigned type;
-};
-template <>
-struct FwHi<true> {
-  typedef unsigned long long type;
-};
-struct FlagW {  // slots 0..3 in `lo`, slot 4 (the fifth chunk of a big group, GL_BAF_ASYM) in `hi`; GPW = 2: the second group's slots 4..7 in `hi`
+struct FlagW {  // slots 0..3 in `lo`; `hi` for a slot 4, which no frame has (S <= 4) but the slot loops cannot prove it
   unsigned long long lo;
-  FwHi<kTwo>::type hi;
+  unsigned hi;
 };
 GL_DEV int fw_get(const FlagW& fw, int i) {
-  if (kTwo) return (int)(((i < 4 ? fw.lo : (unsigned long long)fw.hi) >> (16 * (i & 3))) & 0xffffull);
   return i < 4 ? (int)((fw.lo >> (16 * i)) & 0xffffull) : (int)(fw.hi & 0xffffu);
 }
 GL_DEV void fw_or(FlagW& fw, int i, int bits) {
   if (i < 4) fw.lo |= (unsigned long long)bits << (16 * i);
-  else if (kTwo) fw.hi |= (FwHi<kTwo>::type)((unsigned long long)bits << (16 * (i & 3)));
   else fw.hi |= (unsigned)bits;
 }
 GL_DEV void fw_activity(FlagW& fw, int i) {
@@ -312,26 +261,9 @@ GL_DEV void fw_activity(FlagW& fw, int i) {
   if ((fl & F_EXISTS) && (fl & F_ASSOC) && !(fl & F_LEVG)) act |= F_AG;
   if (kFixed && (fl & F_EXISTS) && ((fl / F_OFFF) & 15) != 15) act |= F_AF;
   if (i < 4) fw.lo = (fw.lo & ~((unsigned long long)(F_AR | F_AG | F_AF) << (16 * i))) | ((unsigned long long)act << (16 * i));
-  else if (kTwo) fw.hi = (FwHi<kTwo>::type)(((unsigned long long)fw.hi & ~((unsigned long long)(F_AR | F_AG | F_AF) << (16 * (i & 3)))) | ((unsigned long long)act << (16 * (i & 3))));
   else fw.hi = (fw.hi & ~(unsigned)(F_AR | F_AG | F_AF)) | (unsigned)act;
 }
 
-// the hand-over slot of a point (Lds::un).  GPW = 2: global memory, streamed (-DGL_BAF_UN_NT: non-temporal accesses)
-GL_DEV void un_st(double* p, double v) {
-#ifdef GL_BAF_UN_NT
-  if (kTwo) {
-    __builtin_nontemporal_store(v, p);
-    return;
-  }
-#endif
-  *p = v;
-}
-GL_DEV double un_ld(const double* p) {
-#ifdef GL_BAF_UN_NT
-  if (kTwo) return __builtin_nontemporal_load(p);
-#endif
-  return *p;
-}
 // the canonical order of a frame of stride L and this thread's place in it
 struct Map {
   int S;      // point slots of this thread (DENSE: chunks of its group; SPREAD: 1)
@@ -339,22 +271,9 @@ struct Map {
   int lbase;  // LDS index of the first point (DENSE: = base; SPREAD: threadIdx.x)
   int step;   // 64 G: the chunks of a group are G apart
   int L;      // points of the frame
-  bool asym;  // GL_BAF_ASYM, frames of 8 groups: the groups 0..3 take five chunks, the groups 4..7 three (slot_off)
-  bool g2;    // GPW = 2: the wave's second group (wave + 4) exists in this frame (G > wave + 4): its slots 4..7 are points of the frame
 };
-// Offset of slot i from the thread's first point.  Frames of 8 groups (29 .. 32 chunks: the 2 000-point class), GL_BAF_ASYM: the two
-// waves of a SIMD do not run at the same speed - the arbiter serves the older one first, the younger one fills the gaps, and once
-// the older one is through its chunks the younger runs ALONE at half the issue rate (its dependent chains have nobody to hide
-// behind): a third of every pass.  The chunks are therefore dealt unevenly: rounds 0..2 one chunk to each of the 8 groups (chunk
-// 8 r + g), rounds 3 and 4 only to the groups 0..3 (chunk 24 + 4 (r - 3) + g): the older wave of every SIMD has five chunks,
-// the younger three, and they end their passes together (profiles/r5_prof_ba_slots.txt).  Still a function of L alone.
-GL_DEV int slot_off(const Map& mp, int i) {
-  if (kTwo) return mp.step * (i & 3) + 64 * NWV * (i >> 2);  // slots 4..7: the chunks of group wave + 4
-  return !mp.asym ? mp.step * i : (i < 3 ? 512 * i : 1536 + 256 * (i - 3));
-}
-// (GPW = 2) slot i belongs to a group this frame does not have: its chunk index would alias another group's
-GL_DEV bool slot_absent(const Map& mp, int i) { return kTwo && i >= 4 && !mp.g2; }
-
+// offset of slot i from the thread's first point
+GL_DEV int slot_off(const Map& mp, int i) { return mp.step * i; }
 struct Lin {
   double q[3];
   double A[6];   // reprojection block sum_r w_r j_r^T j_r (camera frame, sym6; A[1] == 0)
@@ -870,29 +789,13 @@ GL_DEV void prior_record_wave(const cdouble_k* mi, const Pose& P, double* rec, d
 
 // The terms of a point enter the sums through a sink: DENSE adds them to the thread's registers (level 1 of the
 // canonical order), SPREAD just keeps them (they go to the LDS transpose).  Each index is written once per point.
-#ifndef GL_BAF_FEWACC
-#define GL_BAF_FEWACC 0
-#endif
-// (GL_BAF_FEWACC: TIMING EXPERIMENT ONLY, results are garbage - the 27 Schur terms of a point are folded into four accumulators, so that
-// the passes keep their arithmetic but not the 29 live sums: what a kernel with 50 fewer registers would cost per pass, profiles/r6_w3_fewacc.txt)
 struct SinkAcc {
   double* a;
-  GL_DEV void put(int i, double v) const {
-    if (GL_BAF_FEWACC && i < 27) a[i & 3] = add_nc(a[i & 3], v);
-    else a[i] = add_nc(a[i], v);
-  }
+  GL_DEV void put(int i, double v) const { a[i] = add_nc(a[i], v); }
 };
 struct SinkSet {
   double* a;
   GL_DEV void put(int i, double v) const { a[i] = v; }
-};
-
-// pass B with the chunks dealt dynamically: a point's two terms wait in the free half of its slot (doubles 3 and 4: the factors have
-// been read, the backup takes 0..2) for the thread that OWNS the point in the canonical order
-struct SinkSlot {
-  double* un;
-  int ll;
-  GL_DEV void put(int i, double v) const { un[(3 + i) * MCAP + ll] = v; }
 };
 
 // terms 0..20 <- upper(G^T C G), 21..26 <- G^T c,  G = [-[q]x | I], C symmetric (sym6)
@@ -980,11 +883,7 @@ GL_DEV void reduce_to_tot(double* v, const Red& R, Coop& C) {
     const double r = wave_reduce_scatter32(v);
     // no barrier needed before writing `red`: its last readers (threads < 32) finished before the
     // closing barrier of the previous reduction, which every thread has passed
-    if (wave_slot_owner(lane)) {
-      R.red[wave * 32 + wave_slot(lane)] = r;
-      // (GPW = 2: both groups of the wave in one row - only exact sums go this way: counts, XCC ids -, the second group's row reads 0.0)
-      if (kTwo) R.red[(wave + NWV) * 32 + wave_slot(lane)] = 0.0;
-    }
+    if (wave_slot_owner(lane)) R.red[wave * 32 + wave_slot(lane)] = r;
     __syncthreads();
     if (threadIdx.x < 32) {  // absent groups hold zeros (never written after the initial clear); a class
       // with fewer groups than 8 just has no further (all-zero) blocks to add
@@ -1170,26 +1069,15 @@ GL_DEV void spread_reduce2_all(double* v, const Red& R, Coop& C) {
 // pass A (29 values, read by the solving wave only): group totals to red[], ONE barrier, then wave 0 adds the blocks
 // itself and hands the totals round its lanes with v_readlane - no `tot` round trip, no second barrier.  The next
 // writer of red[] is the next trial's pass A, two barriers later.
-// (all_waves: every wave adds the blocks and takes the totals - GL_BAF_ALLSOLVE, the serial section without a hand-over)
-// (GPW = 2) the totals of the group whose slots the wave has just finished -> row `row` of red[]; the accumulators start again at zero
-GL_DEV void group_flush29(double* v, const Red& R, int row) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 29; i < 32; ++i) v[i] = 0.0;
-  const double r = wave_reduce_scatter32(v);
-  if (wave_slot_owner(lane)) R.red[row * 32 + wave_slot(lane)] = r;
-#pragma unroll
-  for (int i = 0; i < 32; ++i) v[i] = 0.0;
-}
-GL_DEV void reduce29_w0_dense(double* v, const Red& R, bool all_waves = false) {
+// (every wave adding the blocks and solving itself was measured slower: profiles/history/r5_ab_allsolve.txt)
+GL_DEV void reduce29_w0_dense(double* v, const Red& R) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int row = kTwo ? wave + NWV : wave;  // (GPW = 2: v[] holds the wave's SECOND group; the first went to its row at slot 4)
 #pragma unroll
   for (int i = 29; i < 32; ++i) v[i] = 0.0;
   const double r = wave_reduce_scatter32(v);
-  if (wave_slot_owner(lane)) R.red[row * 32 + wave_slot(lane)] = r;
+  if (wave_slot_owner(lane)) R.red[wave * 32 + wave_slot(lane)] = r;
   __syncthreads();
-  if (wave == 0 || all_waves) {
+  if (wave == 0) {
     const int t = lane & 31;
     double s = NWC > 1 ? add_nc(R.red[t], R.red[32 + t]) : R.red[t];
 #pragma unroll
@@ -1238,16 +1126,8 @@ GL_DEV double wave_allreduce_canon(double x) {
 }
 // pass B (2 values, needed by every thread): wave totals to the small buffer red2, ONE barrier, every thread
 // adds the blocks itself.  The buffer is rewritten one trial later, with the barriers of pass A in between.
-GL_DEV void group_flush2(double* v, const Red& R, int row) {  // (GPW = 2: like group_flush29, for pass B's two sums)
-  const double s0 = wave_allreduce_canon(v[0]), s1 = wave_allreduce_canon(v[1]);
-  if ((threadIdx.x & 63) == 0) {
-    R.red2[row * 2] = s0;
-    R.red2[row * 2 + 1] = s1;
-  }
-  v[0] = v[1] = 0.0;
-}
 GL_DEV void reduce2_dense(double* v, const Red& R) {
-  const int lane = threadIdx.x & 63, wave = kTwo ? (int)(threadIdx.x >> 6) + NWV : (int)(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const double s0 = wave_allreduce_canon(v[0]), s1 = wave_allreduce_canon(v[1]);
   if (lane == 0) {
     R.red2[wave * 2] = s0;
@@ -1283,59 +1163,12 @@ GL_DEV double reduce_max(double v, const Red& R, Coop& C) {
   return m;
 }
 
-// 6x6 LDL^T in place on the packed upper triangle (21 values, row-major i <= j as produced by the
-// reduction), reciprocal pivots; SimplicialLDLT semantics: fail on a zero pivot.
-// Packed index of (i, j), i <= j.
-#ifndef GL_U
-#define GL_U(i, j) ((i) * 6 - (i) * ((i)-1) / 2 + ((j) - (i)))
-#endif
-GL_DEV bool ldlt6_packed(double* a, const double* b, double lambda, double* x) {
-  // a(i,j), i<=j holds H(j,i) = H(i,j).  Column-oriented: l_ij (i > j) stored at a(j,i).
-  double iD[6];
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = a[GL_U(j, j)] + lambda;
-#pragma unroll
-    for (int kk = 0; kk < j; ++kk) d -= a[GL_U(kk, j)] * a[GL_U(kk, j)] * a[GL_U(kk, kk)];
-    if (d == 0.0 || !isfinite(d)) ok = false;
-    a[GL_U(j, j)] = d;
-    iD[j] = rcp_nr(d);
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double s = a[GL_U(j, i)];
-#pragma unroll
-      for (int kk = 0; kk < j; ++kk) s -= a[GL_U(kk, i)] * a[GL_U(kk, j)] * a[GL_U(kk, kk)];
-      a[GL_U(j, i)] = s * iD[j];
-    }
-  }
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double s = b[i];
-#pragma unroll
-    for (int kk = 0; kk < i; ++kk) s -= a[GL_U(kk, i)] * y[kk];
-    y[i] = s;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) y[i] *= iD[i];
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double s = y[i];
-#pragma unroll
-    for (int kk = i + 1; kk < 6; ++kk) s -= a[GL_U(i, kk)] * x[kk];
-    x[i] = s;
-  }
-  return ok;
-}
-
-#ifndef GL_BAF_SOLVE_BLOCKED
-#define GL_BAF_SOLVE_BLOCKED 1  // (0: the sequential LDL^T of rounds 1 - 5; profiles/r6_solve_blocked.txt)
-#endif
-// The same 6 x 6 system by BLOCKS (round 6): H + lambda I = [[A, B], [B^T, C]] with the rotation block A and the translation block C,
+// The 6 x 6 reduced system (packed upper triangle, 21 values, row-major i <= j as produced by the reduction; SimplicialLDLT
+// semantics: fail on a zero pivot) by BLOCKS (round 6, profiles/r6_solve_blocked.txt): H + lambda I = [[A, B], [B^T, C]] with the
+// rotation block A and the translation block C,
 //     A = L_a D_a L_a^T,   Y = A^-1 [B | b_r],   S = C - B^T Y_B,   s = b_t - B^T y,   S = L_s D_s L_s^T,   x_t = S^-1 s,   x_r = y - Y_B x_t.
-// The pivots are those of the unpivoted LDL^T of the whole matrix (D_a, then D_s): the same failure test.  What changes is the SHAPE of
-// the work: the serial section of a trial - one wave, every other wave of the frame waiting - was a chain of ~190 dependent fp64
+// The pivots are those of the unpivoted LDL^T of the whole matrix (D_a, then D_s): the same failure test.  What the blocks change is the
+// SHAPE of the work: the serial section of a trial - one wave, every other wave of the frame waiting - was a chain of ~190 dependent fp64
 // instructions (six reciprocals one after the other, each behind the eliminations of the column before); here four right-hand sides
 // go through the factors of A side by side and the two 3 x 3 factorisations have their first two reciprocals independent
 // (ldl3_factor_fast): about 50 instructions deep for the same count.  Other rounding, same system: held to the oracle like everything else.
@@ -1389,7 +1222,7 @@ GL_DEV bool ldlt6_blocked(const double* a, const double* b, double lambda, doubl
 }
 
 // backup of the current point in the slot (pass B) / restore on a rejected trial.  The fp32 cache of
-// GL_BAF_STEP32 is read by its owner just before, but planes of OTHER points alias a double-indexed slot,
+// kStep32 is read by its owner just before, but planes of OTHER points alias a double-indexed slot,
 // so that variant keeps the {lo, hi} words in the owner's own 32-bit entries.
 GL_DEV void backup_point(const Lds& D, int ll, const double* p) {
   if (kStep32) {
@@ -1401,7 +1234,7 @@ GL_DEV void backup_point(const Lds& D, int ll, const double* p) {
     }
   } else {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) un_st(D.un + (unsigned)(j * MCAP + ll), p[j]);
+    for (int j = 0; j < 3; ++j) D.un[(unsigned)(j * MCAP + ll)] = p[j];
   }
 }
 GL_DEV void restore_point(const Lds& D, int ll) {
@@ -1411,7 +1244,7 @@ GL_DEV void restore_point(const Lds& D, int ll) {
     for (int j = 0; j < 3; ++j) D.sp[j * MCAP + ll] = __hiloint2double(un[(2 * j + 1) * MCAP + ll], un[(2 * j) * MCAP + ll]);
   } else {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) D.sp[j * MCAP + ll] = un_ld(D.un + (unsigned)(j * MCAP + ll));
+    for (int j = 0; j < 3; ++j) D.sp[j * MCAP + ll] = D.un[(unsigned)(j * MCAP + ll)];
   }
 }
 
@@ -1432,31 +1265,6 @@ GL_DEV bool load_pt(const Lds& D, const Map& mp, FlagW fw, const double* __restr
   const int ap = a > 0 ? a : 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) c.nd[j] = gnd[(size_t)ap * 4 + j];  // plane normal n and n . mean: the map's table, by component
-  c.ar = c.fl & F_AR;
-  c.ag = c.fl & F_AG;
-  c.af = kFixed && (c.fl & F_AF);
-  const int oc = (c.fl >> 8) & 7;
-  c.sx = D.stab[oc];
-  c.sy = D.stab[8 + oc];
-  c.asc = (c.fl & F_ASSOC) && !(c.fl & F_DEG) ? a : -1;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) c.p[j] = D.sp[j * MCAP + c.ll];
-  return true;
-}
-
-// the same for point l with its flag word from memory (pass B, chunks dealt dynamically)
-GL_DEV bool load_pt_at(const Lds& D, int l, int fl, const double* __restrict__ gobn, const double* __restrict__ gnd,
-                       const int32_t* __restrict__ gassoc, PtCtx& c) {
-  c.fl = fl;
-  if (!(c.fl & (F_AR | F_AG | F_AF))) return false;
-  c.l = l;
-  c.ll = l;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) c.ob[j] = gobn[(size_t)c.l * 3 + j];
-  const int a = gassoc[c.l];
-  const int ap = a > 0 ? a : 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) c.nd[j] = gnd[(size_t)ap * 4 + j];
   c.ar = c.fl & F_AR;
   c.ag = c.fl & F_AG;
   c.af = kFixed && (c.fl & F_AF);
@@ -1605,7 +1413,7 @@ GL_DEV void pt_pass_a(const Uni& U, const GmmDev& gm, const Lds& D, const Pose& 
     for (int j = 0; j < 3; ++j) un[j * MCAP + c.ll] = __float_as_int((float)u[j]);
   } else {
 #pragma unroll
-    for (int j = 0; j < 6; ++j) un_st(D.un + (unsigned)(j * MCAP + c.ll), Df[j]);
+    for (int j = 0; j < 6; ++j) D.un[(unsigned)(j * MCAP + c.ll)] = Df[j];
   }
   if (c.ar) {
     if (!kStep32) D.chir[c.ll] = o.rho1;
@@ -1705,7 +1513,7 @@ GL_DEV void pt_pass_b_step(const Uni& U, const GmmDev& gm, const Lds& D, const P
     }
     double Df[6];
 #pragma unroll
-    for (int j = 0; j < 6; ++j) Df[j] = un_ld(D.un + (unsigned)(j * MCAP + c.ll));
+    for (int j = 0; j < 6; ++j) Df[j] = D.un[(unsigned)(j * MCAP + c.ll)];
     ldl3_solve_fast(Df, rhs, eps);
   }
   sk.put(0, eps[0] * eps[0] + eps[1] * eps[1] + eps[2] * eps[2]);
@@ -1740,27 +1548,10 @@ GL_DEV void pt_pass_b_eval(const Uni& U, const GmmDev& gm, const Lds& D, const P
 // arbiter favours the older one, which then finishes its 4 slots a third of the pass early and leaves the younger
 // one alone on the SIMD at single-wave speed (measured: 11.6 k vs 18.3 k cycles).  Waves 4..7 sit at priority 1; waves
 // 0..3 start a pass at 2 and drop to 0 for their last slot, so that the pair ends the pass together.
-#if defined(GL_BAF_NO_PRIO)
-#define GL_BAF_PRIO_PASS_BEGIN()
-#define GL_BAF_PRIO_SLOT(i)
-#else
 #define GL_BAF_PRIO_PASS_BEGIN() \
-  if (NWC == 8 && !kTwo && (threadIdx.x >> 6) < 4) __builtin_amdgcn_s_setprio(2)
+  if (NWC == 8 && (threadIdx.x >> 6) < 4) __builtin_amdgcn_s_setprio(2)
 #define GL_BAF_PRIO_SLOT(i) \
-  if (NWC == 8 && !kTwo && (threadIdx.x >> 6) < 4 && (i) == (mp.asym ? GL_BAF_PRIO_DROP_ASYM : GL_BAF_PRIO_DROP)) __builtin_amdgcn_s_setprio(0)
-#endif
-#if defined(GL_BAF_NO_PRIO)
-#define GL_BAF_PRIO_PASS_END()
-#else
-#define GL_BAF_PRIO_PASS_END() \
-  if (NWC == 8 && !kTwo && (threadIdx.x >> 6) < 4) __builtin_amdgcn_s_setprio(1)  /* a dynamically dealt pass: every wave at the same priority */
-#endif
-#ifndef GL_BAF_PRIO_DROP_ASYM
-#define GL_BAF_PRIO_DROP_ASYM 4
-#endif
-#ifndef GL_BAF_PRIO_DROP
-#define GL_BAF_PRIO_DROP 3
-#endif
+  if (NWC == 8 && (threadIdx.x >> 6) < 4 && (i) == 3) __builtin_amdgcn_s_setprio(0)
 
 #if defined(GL_BA_PROF) && defined(GL_BA_PROF_LOADS)  // (diagnosis only: the wait changes the schedule of the slot's head)
 #define GL_BAF_PROF_LOADS(i)          \
@@ -1771,9 +1562,7 @@ GL_DEV void pt_pass_b_eval(const Uni& U, const GmmDev& gm, const Lds& D, const P
 #endif
 // one pass over the thread's points: DENSE accumulates the terms in acc[] (level 1), SPREAD leaves the single
 // point's terms there (zeros when the thread has no active point)
-#define GL_BAF_PASS(BODY) GL_BAF_PASS2(BODY, )
-// (MID: GPW = 2, what happens between the slots of the wave's first and second group - the first group's totals leave the accumulators)
-#define GL_BAF_PASS2(BODY, MID)                                               \
+#define GL_BAF_PASS(BODY)                                                     \
   {                                                                           \
     _Pragma("unroll") for (int i_ = 0; i_ < 32; ++i_) acc[i_] = 0.0;          \
     if (kSpread) {                                                            \
@@ -1786,7 +1575,6 @@ GL_DEV void pt_pass_b_eval(const Uni& U, const GmmDev& gm, const Lds& D, const P
       const SinkAcc sk{acc};                                                  \
       GL_BAF_PRIO_PASS_BEGIN();                                               \
       _Pragma("unroll 1") for (int i = 0; i < mp.S; ++i) {                    \
-        if (kTwo && i == 4) { MID; }                                          \
         GL_BAF_PRIO_SLOT(i);                                                  \
         PROF_S(trials, prof_pass, i);                                         \
         PtCtx c;                                                              \
@@ -1801,7 +1589,7 @@ GL_DEV void pt_pass_b_eval(const Uni& U, const GmmDev& gm, const Lds& D, const P
 // SparseOptimizer::optimize(iters), Levenberg
 GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map& mp, FlagW fw, Pose& P,
                          const double* __restrict__ gobn, const int32_t* __restrict__ gassoc, const double* __restrict__ gnd,
-                         const PtConst& pc, bool robust, int iters, const Red& R, int& trials, Coop& C, Anchor& An, const int32_t* gpfl) {
+                         const PtConst& pc, bool robust, int iters, const Red& R, int& trials, Coop& C, Anchor& An) {
   double acc[32];
 #pragma unroll
   for (int i = 0; i < 32; ++i) acc[i] = 0.0;
@@ -1839,23 +1627,8 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
       if (!kSpread) {
         // DENSE: only the six diagonal sums, in the canonical order (level 2 = the butterfly of wave_allreduce_canon, level 3 = the blocks
         // of two groups), and the maximum of the point blocks beside them through the same LDS row: one barrier instead of five
-        // (GPW = 2: the first group's six sums and the maximum so far go to the wave's first row between the two groups' slots - behind
-        // the same barrier, which every wave reaches: the hook sits in front of the slot's activity test)
-        GL_BAF_PASS2(pt_lambda_init_diag(U, gm, D, P, c, robust, md, sk), {
-          double sd0[6];
-          _Pragma("unroll") for (int i_ = 0; i_ < 6; ++i_) sd0[i_] = wave_allreduce_canon(acc[i_]);
-          double m0 = md;
-          _Pragma("unroll") for (int o_ = 1; o_ < 64; o_ <<= 1) m0 = fmax(m0, shfl_xor_f64(m0, o_));
-          __syncthreads();
-          const int l0_ = threadIdx.x & 63;
-          if (l0_ < 7) {
-            double v0 = m0;
-            _Pragma("unroll") for (int i_ = 0; i_ < 6; ++i_) v0 = l0_ == i_ ? sd0[i_] : v0;
-            R.red[(threadIdx.x >> 6) * 32 + l0_] = v0;
-          }
-          _Pragma("unroll") for (int i_ = 0; i_ < 6; ++i_) acc[i_] = 0.0;
-        });
-        const int lane_ = threadIdx.x & 63, wave_ = kTwo ? (int)(threadIdx.x >> 6) + NWV : (int)(threadIdx.x >> 6);
+        GL_BAF_PASS(pt_lambda_init_diag(U, gm, D, P, c, robust, md, sk));
+        const int lane_ = threadIdx.x & 63, wave_ = threadIdx.x >> 6;
         double sd[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) sd[i] = wave_allreduce_canon(acc[i]);
@@ -1908,12 +1681,12 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
       PROF_T(tA0);
       // ---- pass A ---------------------------------------------------------------------------
       prof_pass = 0;
-      GL_BAF_PASS2(pt_pass_a(U, gm, D, P, c, robust, lambda, sk), group_flush29(acc, R, (int)(threadIdx.x >> 6)));
+      GL_BAF_PASS(pt_pass_a(U, gm, D, P, c, robust, lambda, sk));
       PROF_S(trials, 0, 4);
       PROF_T(tA1);
       PROF_W(trials, 0);
       if (kSpread) spread_reduce29_w0(acc, R, C);
-      else reduce29_w0_dense(acc, R, kAllSolve);
+      else reduce29_w0_dense(acc, R);
       PROF_W(trials, 1);
       PROF_T(tA2);
       double* bc = R.tot + 32;  // 28 doubles: dx[6] R[9] t[3] ok g[6] sum u.b chi2, chi2 of the prior edge at the trial pose
@@ -1923,28 +1696,6 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
       bool ok2;
       Pose Pn = P;
       bool have_pn = false;
-      if (kAllSolve) {
-        // DENSE: EVERY wave solves the 6 x 6 system from the totals it has just added up itself, and builds the trial pose: the
-        // serial section has no hand-over - no second barrier, no broadcast through LDS, no wait for the trial pose (the
-        // ~350 dependent instructions run on all eight waves at once, two per SIMD, in each other's latencies)
-        double dxs[6] = {0, 0, 0, 0, 0, 0};
-        bool ok = true;
-        if (prior_on) {  // the prior edge at the current pose: H_pp, b_p and chi2 from its record
-          const double* rc = An.rec + An.cur * 32;
-#pragma unroll
-          for (int i = 0; i < 28; ++i) acc[i] += rc[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 6; ++i) gsc[i] = acc[21 + i];
-        gsc[6] = acc[28];
-        if (qmax == 0) currentChi = acc[27];
-        if (pose_active) ok = GL_BAF_SOLVE_BLOCKED ? ldlt6_blocked(acc, acc + 21, lambda, dxs) : ldlt6_packed(acc, acc + 21, lambda, dxs);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) dx[i] = dxs[i];
-        ok2 = ok;
-        if (pose_active && ok2) Pn = pose_uni(pose_update(P, dx));
-        have_pn = true;
-      } else {
       // 6x6 solve by wave 0; the step and the status are broadcast through LDS behind a barrier.  The trial pose
       // exp(dx) P is computed by wave 0 AFTER that barrier, while the other waves are already in pass B (its first use
       // is the evaluation of their first point, ~200 instructions in), and handed over through LDS + a sequence word.
@@ -1956,7 +1707,7 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
 #pragma unroll
           for (int i = 0; i < 28; ++i) acc[i] += rc[i];
         }
-        if (pose_active) ok = GL_BAF_SOLVE_BLOCKED ? ldlt6_blocked(acc, acc + 21, lambda, dxs) : ldlt6_packed(acc, acc + 21, lambda, dxs);
+        if (pose_active) ok = ldlt6_blocked(acc, acc + 21, lambda, dxs);
         if (threadIdx.x == 0) {
 #pragma unroll
           for (int i = 0; i < 6; ++i) bc[i] = dxs[i];
@@ -1965,7 +1716,6 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
           for (int i = 0; i < 6; ++i) bc[19 + i] = acc[21 + i];  // reduced rhs g and sum u.b, for computeScale
           bc[25] = acc[28];
           bc[26] = acc[27];  // robust chi2 at the linearisation point
-          if (kDynB) *(int*)(D.stab + 20) = 0;  // pass B's chunk queue
         }
       }
       __syncthreads();
@@ -1989,7 +1739,6 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
         Pn = pose_uni(Pw);
         have_pn = true;
       }
-      }
       PROF_T(tS);
       PROF_W(trials, 2);
       // ---- pass B ---------------------------------------------------------------------------
@@ -2003,56 +1752,15 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
     have_pn = true;                                                                              \
   }
       prof_pass = 1;
-      if (kDynB) {
-        // The chunks of pass B are dealt DYNAMICALLY: a wave that is through a chunk takes the next one from a counter in LDS.  The
-        // two waves of a SIMD do not run at the same speed (the arbiter serves the older one first), and with four fixed chunks each
-        // the older one is done a third of the pass before the younger, which then runs alone at half the issue rate
-        // (profiles/r5_prof_ba_slots.txt).  Which wave evaluates a point does not show in the result: the point's two terms wait in
-        // its slot, and the thread that OWNS the point in the canonical order adds them - in the same order as ever - behind a barrier.
-        // The flag word of a point it does not own comes from the launch scratch (bits 16..31 of pfl, kept current by the owners).
-        const int nch = (mp.L + 63) >> 6;
-        volatile int* qc = (volatile int*)(D.stab + 20);
-#if GL_BAF_DYNB_PRIO == 0
-        GL_BAF_PRIO_PASS_END();
-#else
-        GL_BAF_PRIO_PASS_BEGIN();  // the older wave of a SIMD keeps the higher priority: it just takes more of the chunks
-#endif
-#pragma unroll 1
-        for (;;) {
-          int cq = 0;
-          if ((threadIdx.x & 63) == 0) cq = atomicAdd((int*)qc, 1);
-          cq = __builtin_amdgcn_readfirstlane(cq);
-          if (cq >= nch) break;
-          const int l = cq * 64 + (int)(threadIdx.x & 63);
-          const int fl = l < mp.L ? (int)((unsigned)__hip_atomic_load(gpfl + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 16) : 0;
-          PtCtx c;
-          if (!load_pt_at(D, l, fl, gobn, gnd, gassoc, c)) continue;
-          const SinkSlot sk{D.un, c.ll};
-          double pn[3];
-          pt_pass_b_step(U, gm, D, P, dx, c, pn, sk);
-          GL_BAF_GET_PN();
-          pt_pass_b_eval(U, gm, D, Pn, c, pn, robust, sk);
-        }
-        GL_BAF_GET_PN();
-        __syncthreads();
-        acc[0] = acc[1] = 0.0;
-#pragma unroll 1
-        for (int i = 0; i < mp.S; ++i) {  // level 1 of the canonical order: the owner adds its points' terms in slot order
-          if (!(fw_get(fw, i) & (F_AR | F_AG | F_AF))) continue;
-          const int ll = mp.lbase + slot_off(mp, i);
-          acc[0] = add_nc(acc[0], D.un[3 * MCAP + ll]);
-          acc[1] = add_nc(acc[1], D.un[4 * MCAP + ll]);
-        }
-      } else {
-      GL_BAF_PASS2({
+      // (pass B's chunks dealt dynamically to whichever wave is free were measured slower: profiles/history/r5_ab_dynb.txt)
+      GL_BAF_PASS({
         double pn[3];
         pt_pass_b_step(U, gm, D, P, dx, c, pn, sk);
         PROF_Q(trials, 1, i, 1);
         GL_BAF_GET_PN();
         pt_pass_b_eval(U, gm, D, Pn, c, pn, robust, sk);
-      }, group_flush2(acc, R, (int)(threadIdx.x >> 6)));
+      });
       GL_BAF_GET_PN();  // (a wave without an active point still takes the pose: P = Pn on acceptance)
-      }
       PROF_S(trials, 1, 4);
 #undef GL_BAF_GET_PN
       if (prior_on && (int)(threadIdx.x >> 6) == An.wave) prior_record_wave(An.mi, Pn, An.rec + (An.cur ^ 1) * 32, An.work, An.rezero);
@@ -2126,6 +1834,11 @@ GL_DEV T ld_karg(const T __attribute__((address_space(4)))* p) {
   return u.v;
 }
 
+// An always-false test the front end cannot fold: its `continue` at the head of the set-up loop of ba1_fast_frame gives that
+// loop the exit shape every instance's code was measured with (without it the register allocation of every instance changes,
+// bafd2000f by 55 more instructions).
+GL_DEV bool false_once_inlined() { return false; }
+
 typedef const BafKArgs __attribute__((address_space(4))) kargs_t;
 GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   // the arguments the set-up and the passes use; the caller's OUTPUT arrays are read from the argument segment again where the
@@ -2149,10 +1862,9 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   Lds D;
   D.sp = smem;                      // 3 * MCAP
   D.chir = D.sp + 3 * MCAP;         // MCAP
-  // (GPW = 2: the hand-over slots of this workgroup's frame in global memory - one region per workgroup of the launch)
-  D.un = kTwo ? ka->un_scratch + (size_t)blockIdx.x * 6 * MCAP : D.chir + MCAP;  // 6 * MCAP
+  D.un = D.chir + MCAP;             // 6 * MCAP
   Red R;
-  R.red = D.chir + (kTwo ? 1 : 7) * MCAP;  // NRED * 32
+  R.red = D.un + 6 * MCAP;          // NRED * 32
   R.tot = R.red + NRED * 32;        // 32 (+ 32 broadcast slots)
   D.stab = R.tot + 64;              // 24
   R.red2 = D.stab + 24;             // 16
@@ -2225,15 +1937,11 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   mp.L = L;
   if (kSpread) {  // workgroup pb = group pb; wave = slot; idle waves beyond S
     mp.S = 1;
-    mp.asym = false;
-    mp.g2 = false;
     mp.base = wave < S && C.pb < G ? (C.pb + G * wave) * 64 + lane : L;  // chunk g + G slot of group g
     mp.lbase = tid;
     mp.step = 0;
   } else {
-    mp.asym = kAsym && G == 8;
-    mp.S = kTwo ? 8 : mp.asym ? (wave < 4 ? 5 : 3) : S;  // (GPW = 2: four slots per group; a slot beyond the frame's S chunks per group lies behind L)
-    mp.g2 = kTwo && wave + NWV < G;
+    mp.S = S;
     mp.base = wave * 64 + lane;  // group = wave: chunks wave, wave + G, ... (slot_off)
     mp.lbase = mp.base;
     mp.step = 64 * G;
@@ -2266,24 +1974,19 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
 #pragma unroll 1
     for (int i = 0; i < ns; ++i) {
       const int l = mp.base + slot_off(mp, i), ll = mp.lbase + slot_off(mp, i);
-      if (slot_absent(mp, i)) continue;
-      if (l >= L) {
-        if (kTwo) continue;  // (the second group's slots follow)
-        break;
-      }
+      if (false_once_inlined()) continue;  // (see there)
+      if (l >= L) break;
       const size_t g = gbase + gperm[l];
 #pragma unroll
       for (int j = 0; j < 3; ++j) D.sp[j * MCAP + ll] = pts_io[g * 3 + j];
       D.chir[ll] = 0.0;
-      const int pfl0 = pv.pfl[gbase + l] & 0xffff;  // (bits 16..31: the current flag word of an earlier launch on this scratch)
-      fw_or(fw, i, pfl0);
+      fw_or(fw, i, pv.pfl[gbase + l] & 0xffff);  // (the slot's 16 bits of fw)
       if (kFixed) {  // edges the point does not have (not observed by that key-frame / no such key-frame) count as inactive
 #pragma unroll
         for (int kf = 0; kf < kMaxFixed; ++kf)
           if (kf >= D.F || D.gfoct[(size_t)kf * L + l] < 0) fw_or(fw, i, F_OFFF << kf);
       }
       fw_activity(fw, i);
-      if (kDynB) pv.pfl[gbase + l] = pfl0 | (fw_get(fw, i) << 16);  // the current flag word, for whichever wave takes the point in pass B
     }
   }
   PtConst pc;
@@ -2305,9 +2008,7 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   Anchor An{prior_flag && k.first_as_prior != 0, prior_flag && k.first_as_prior == 0,
             (const cdouble_k*)(prior_mi + (size_t)f * 12), prec, 0, pwork, !kSpread && NWC >= 4,
             kSpread ? (int)(blockDim.x >> 6) - 1 : min(1, (int)(blockDim.x >> 6) - 1)};
-#ifndef GL_BAF_NO_PRIO
   if (!kSpread && NWC == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   __syncthreads();
   if (kPrior && An.has_prior) {  // the record of the input pose (its work area may be the freshly zeroed group totals)
     if (wave == An.wave) prior_record_wave(An.mi, P, prec, pwork, An.rezero);
@@ -2331,18 +2032,14 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   PROF_K(1);
 #pragma unroll 1
   for (int phase = 0; phase < 3; ++phase) {
-    it3 = optimize_fast(U, gm, D, mp, fw, P, gobn, gassoc, gnd, pc, phase < 2, phase < 2 ? 5 : 40, R, trials, C, An, pv.pfl + gbase);
+    it3 = optimize_fast(U, gm, D, mp, fw, P, gobn, gassoc, gnd, pc, phase < 2, phase < 2 ? 5 : 40, R, trials, C, An);
     outer += it3 > 0 ? it3 : 0;
     PROF_K(2 + 2 * phase);
     if (phase == 2) break;
 #pragma unroll 1
     for (int i = 0; i < ns; ++i) {
       const int l = mp.base + slot_off(mp, i), ll = mp.lbase + slot_off(mp, i);
-      if (slot_absent(mp, i)) continue;
-      if (l >= L) {
-        if (kTwo) continue;  // (the second group's slots follow)
-        break;
-      }
+      if (l >= L) break;
       const int fl = fw_get(fw, i);
       if (phase == 0) {  // fresh error of the degenerate GMM edges (:773-786)
         if ((fl & (F_ASSOC | F_DEG)) == (F_ASSOC | F_DEG)) {
@@ -2367,7 +2064,6 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
         }
       }
       fw_activity(fw, i);
-      if (kDynB) pv.pfl[gbase + l] = (pv.pfl[gbase + l] & 0xffff) | (fw_get(fw, i) << 16);
     }
     __syncthreads();
     PROF_K(3 + 2 * phase);
@@ -2400,11 +2096,7 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
 #pragma unroll 1
   for (int i = 0; i < ns; ++i) {  // outputs (:837-879, :898-922)
     const int l = mp.base + slot_off(mp, i), ll = mp.lbase + slot_off(mp, i);
-    if (slot_absent(mp, i)) continue;
-    if (l >= L) {
-      if (kTwo) continue;
-      break;
-    }
+    if (l >= L) break;
     const size_t g = gbase + gperm[l];  // back to the caller's order
     const int fl = fw_get(fw, i);
     uint8_t dr = 0, er = 0;
@@ -2503,13 +2195,7 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
 // zeroed by k_ba1_prep): a workgroup of the largest class owns a whole CU, and between two workgroups of a plain launch that CU sat
 // idle for 16 us (median; 48 us mean: workgroup timelines of profiles/r5_prof_ba_stations.txt) - 6 % of the launch.  Which workgroup
 // takes a frame shows nowhere in its result.  SPREAD (and frame_ctr == nullptr): the plain launch, one block per (frame, group).
-#ifdef GL_BAF_THREADS
-__global__ __launch_bounds__(GL_BAF_THREADS, GL_BAF_THREADS / 256) void k_ba1_fast(BafKArgs A) {
-#elif GL_BAF_GPW == 2
-__global__ __launch_bounds__(64 * NWV, 2) void k_ba1_fast(BafKArgs A) {
-#else
 __global__ __launch_bounds__(kSpread ? TSP : 512, 2) void k_ba1_fast(BafKArgs A) {
-#endif
   extern __shared__ __attribute__((aligned(16))) double smem[];
   __shared__ int s_frame;
   const bool persistent = !kSpread && A.frame_ctr != nullptr;
@@ -2538,3 +2224,4 @@ __global__ __launch_bounds__(kSpread ? TSP : 512, 2) void k_ba1_fast(BafKArgs A)
 
 }  // namespace GL_BAF_NS
 }  // namespace
+#undef GL_BAF_NS

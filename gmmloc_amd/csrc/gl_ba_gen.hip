@@ -738,12 +738,8 @@ GL_DEV void pass_blocks(const GenP& G, bool schur, double* p2part) {
     double R1[9], t1[3], R2[9], t2[3];
     load_Rt(G.Rt + (size_t)j1 * 12, R1, t1);
     load_Rt(G.Rt + (size_t)j2 * 12, R2, t2);
-    // Software-pipelined variant (-DGL_BAGEN_PIPE, round 3: the indices and the three records of entry e + step are
-    // requested while entry e is worked on) measured against this loop on one box (tools/ab_gen.sh, profiles/history/r3_bagen_ab.txt):
-    // 20 + 8 key-frames 6.51 -> 6.41 ms, 256-problem batches 0.113 -> 0.107 ms per problem, but 8 + 4 key-frames
-    // 2.89 -> 3.53 ms and 12 + 4 4.70 -> 5.57 ms - there 2 waves share a block, a lane has 8 entries, and the 33 live
-    // prefetch registers take the kernel from 337 to 536 spilled VGPRs.  Not the default.
-#ifndef GL_BAGEN_PIPE
+    // (a software-pipelined form of this loop was measured: faster at 20 + 8 key-frames, slower at 8 + 4 and 12 + 4 - its prefetch
+    // registers spill; profiles/history/r3_bagen_ab.txt)
     for (int e = G.pl_ptr[j1] + sub * 64 + lane; act && e < G.pl_ptr[j1 + 1]; e += 64 * W) {
       // (partner, observation and point come from position-indexed tables in one round of loads; the level flags
       // are folded into the partner table when they change)
@@ -754,52 +750,6 @@ GL_DEV void pass_blocks(const GenP& G, bool schur, double* p2part) {
       const double* l1 = G.lin + (size_t)o1 * 12;
       const double* l2 = G.lin + (size_t)o2 * 12;
       const double* pw = G.ptw + (size_t)l * 12;
-  #else
-    // Software pipeline (round 3): the indices of entry e + step {partner, observation, point} and then its three records
-    // are requested while entry e is being worked on - an entry cost two DEPENDENT L2 round trips (index -> record) in front
-    // of ~500 instructions, 33 times in sequence per lane at 20 poses, on a workgroup with one wave per SIMD.
-    const int e_end = act ? G.pl_ptr[j1 + 1] : 0, e_step = 64 * W;
-    int e = G.pl_ptr[j1] + sub * 64 + lane;
-    int n_o2 = -1, n_o1 = 0, n_l = 0;
-    if (e < e_end) {
-      n_o2 = G.plm[(size_t)e * P + j2];
-      n_o1 = G.pl_obs[e];
-      n_l = G.pl_pt[e];
-    }
-    double nl1[12], nl2[12], npw[9];
-    {
-      const int o2c = max(n_o2, 0);
-#pragma unroll
-      for (int i = 0; i < 12; ++i) nl1[i] = G.lin[(size_t)n_o1 * 12 + i];
-#pragma unroll
-      for (int i = 0; i < 12; ++i) nl2[i] = G.lin[(size_t)o2c * 12 + i];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) npw[i] = G.ptw[(size_t)n_l * 12 + i];
-    }
-    for (; e < e_end; e += e_step) {
-      const int o2 = n_o2;
-      double l1[12], l2[12], pw[9];
-#pragma unroll
-      for (int i = 0; i < 12; ++i) l1[i] = nl1[i];
-#pragma unroll
-      for (int i = 0; i < 12; ++i) l2[i] = nl2[i];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) pw[i] = npw[i];
-      {  // next entry: indices now, records as soon as they are there (both rounds overlap this entry's arithmetic)
-        const int en = min(e + e_step, e_end - 1);  // (one past the end: re-reads a valid entry)
-        n_o2 = (e + e_step < e_end) ? G.plm[(size_t)en * P + j2] : -1;
-        n_o1 = G.pl_obs[en];
-        n_l = G.pl_pt[en];
-        const int o2c = max(n_o2, 0);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) nl1[i] = G.lin[(size_t)n_o1 * 12 + i];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) nl2[i] = G.lin[(size_t)o2c * 12 + i];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) npw[i] = G.ptw[(size_t)n_l * 12 + i];
-      }
-      if (o2 < 0) continue;
-#endif
       schur_entry(l1, l2, pw, R1, R2, schur, j1 == j2, v1, v2);
     }
     double r1 = wave_reduce_scatter32(v1);
@@ -862,42 +812,6 @@ GL_DEV double diag_terms(const GenP& G, const BaK& k, double lambda, int r, int 
   return v;
 }
 
-// diagonal block of a pose (one thread, registers), with the block's part of the forward substitution L y = g: row r
-// receives y_r -= l_rk y_k in ascending k from the thread that has just formed l_rk
-template <class SP>
-GL_DEV void ldlt_diag_block(SP S, int ld, int base, double* idg, double* yv, int* s_flag) {
-  double a[6][6], yb[6];
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    yb[r] = yv[base + r];
-#pragma unroll
-    for (int c = 0; c <= r; ++c) a[r][c] = S[(size_t)(base + r) * ld + base + c];
-  }
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    const double d = a[c][c];
-    if (d == 0.0 || !isfinite(d)) *s_flag = 0;
-    const double id = 1.0 / d;
-    idg[base + c] = id;
-#pragma unroll
-    for (int r = c + 1; r < 6; ++r) {
-      const double ci = a[r][c] * id;
-#pragma unroll
-      for (int j = c + 1; j <= r; ++j) a[r][j] -= ci * a[j][c];
-      yb[r] = __builtin_fma(-ci, yb[c], yb[r]);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    yv[base + r] = yb[r];
-#pragma unroll
-    for (int c = 0; c <= r; ++c) S[(size_t)(base + r) * ld + base + c] = a[r][c];
-  }
-}
-// The same on a WAVE (round 3): lane r < 6 holds row r of the block; per pivot the pivot, the pivot row's y and the
-// column's elements of the rows below travel as v_readlane broadcasts and every row updates its own elements - 6 x
-// (a division + a handful of dependent operations) on the critical path instead of the ~350 sequential double-precision
-// instructions of the one-thread version (2.8 k cycles per pose block, a third of the factorisation at 20 poses).
 GL_DEV double readlane_f64(double v, int lane) {
   union {
     double d;
@@ -908,6 +822,10 @@ GL_DEV double readlane_f64(double v, int lane) {
   w.i[1] = __builtin_amdgcn_readlane(u.i[1], lane);
   return w.d;
 }
+// diagonal block of a pose on a WAVE, with the block's part of the forward substitution L y = g: lane r < 6 holds row r of the
+// block; per pivot the pivot, the pivot row's y and the column's elements of the rows below travel as v_readlane broadcasts and
+// every row updates its own elements - 6 x (a division + a handful of dependent operations) on the critical path instead of the
+// ~350 sequential double-precision instructions of a one-thread version (2.8 k cycles per pose block, round 3).
 template <class SP>
 GL_DEV void ldlt_diag_block_wave(SP S, int ld, int base, double* idg, double* yv, int* s_flag) {
   const int lane = threadIdx.x & 63, rr = min(lane, 5);
@@ -1026,9 +944,6 @@ GL_DEV void ldlt_diag_panel_wave(SP S, int ld, int base, int n, double* idg, dou
   for (int c = 0; c < 6; ++c) {
     const double d = readlane_f64(a[c], c);
     bad = bad || d == 0.0 || !isfinite(d);
-#ifdef GL_PIPE_IEEE_DIV
-    id[c] = 1.0 / d;
-#else
     {  // reciprocal pivot by v_rcp_f64 + two Newton steps (<= 1 ulp from 1 / d): the correctly rounded division is 12 dependent
        // instructions on the one chain a pose step cannot shorten - pivot -> multiplier -> next pivot, six times per pose
       double x = __builtin_amdgcn_rcp(d);
@@ -1036,7 +951,6 @@ GL_DEV void ldlt_diag_panel_wave(SP S, int ld, int base, int n, double* idg, dou
       x = __builtin_fma(__builtin_fma(-d, x, 1.0), x, x);
       id[c] = x;
     }
-#endif
     const double yc = readlane_f64(y, c);
     const double ci = a[c] * id[c];
 #pragma unroll
@@ -1141,11 +1055,7 @@ GL_DEV bool ldlt_solve_tiles(const GenP& G, const BaK& k, double lambda, const d
       }
     }
     __syncthreads();
-#ifdef GL_BAGEN_NO_WAVEDIAG
-    if (tid == 0) ldlt_diag_block(S, ld, base, idg, yv, s_flag);
-#else
     if (tid < 64) ldlt_diag_block_wave(S, ld, base, idg, yv, s_flag);
-#endif
     __syncthreads();
     GP_T(q1);
     if (m0 + tid < n) ldlt_panel_row(S, ld, base, m0 + tid, idg, yv);
@@ -1314,75 +1224,9 @@ GL_DEV bool ldlt_solve_teams(const GenP& G, const BaK& k, double lambda, const d
   __syncthreads();
   return *s_flag != 0;
 }
-// n <= NMAX <= 48 (up to 8 free poses), round 3: the whole factorisation on ONE WAVE, lane r = row r held in registers
-// (NMAX doubles), no barrier and no LDS inside: per pivot k the pivot and the column's elements of the rows below travel as
-// v_readlane broadcasts (A[j][k] is register k of lane j - static indices in the unrolled code) and every lane updates its own
-// row, S[r][j] -= l_rk S[j][k] in ascending k like the scalar loop; the forward substitution rides along, z = D^-1 y by
-// division, L^T x = z as 48 wave sums.  ~4 300 instructions on one wave against the blocked algorithm's 8 x (3 barriers +
-// a one-wave diagonal block + panel + register-tile update).  MEASURED (profiles/history/r3_bagen_shapes.txt), NOT ENABLED (-DGL_BAGEN_WAVE_LDLT): in
-// the pipelined shape's solve kernel a window of 8 + 4 key-frames goes 2.96 -> 2.90 ms; inlined into the persistent kernel the
-// 48-register rows take it from 272 to 809 spilled VGPRs and the same window from 2.87 to 3.65 ms.
-// Rows n .. NMAX-1 are identity padding (they cost their share of the unrolled code: two instances, 24 and 48).
-template <int NMAX>
-GL_DEV bool ldlt_solve_wave(const GenP& G, const BaK& k, double lambda, const double* src, int lsrc, bool fuse, double* g, int n,
-                            int* s_flag, const double* yv) {
-  if (threadIdx.x < 64) {
-    const int r = threadIdx.x & 63, rr = min(r, n - 1);
-    double a[NMAX], y = r < n ? yv[rr] : 0.0;
-#pragma unroll
-    for (int c = 0; c < NMAX; ++c) {
-      double v = (c == r) ? 1.0 : 0.0;  // identity padding beyond the system
-      if (r < n && c <= r) {
-        v = src[(size_t)r * lsrc + c];
-        if (fuse && c >= 6 * (r / 6)) v = diag_terms(G, k, lambda, r, c, v);
-      }
-      a[c] = v;
-    }
-    bool bad = false;
-#pragma unroll
-    for (int kk = 0; kk < NMAX; ++kk) {
-      const double d = readlane_f64(a[kk], kk);
-      bad = bad || d == 0.0 || !isfinite(d);
-      const double yk = readlane_f64(y, kk);
-      const double l = a[kk] * (1.0 / d);  // l_rk of this lane's row (meaningful for r > k)
-#pragma unroll
-      for (int j = kk + 1; j < NMAX; ++j) a[j] = __builtin_fma(-l, readlane_f64(a[kk], j), a[j]);  // (entries right of the diagonal: never read)
-      if (r > kk) {
-        y = __builtin_fma(-l, yk, y);
-        a[kk] = l;
-      }
-    }
-    // z = D^-1 y (division, like the reference LDL^T); a[r] of lane r is d_r
-    double dr = 1.0;
-#pragma unroll
-    for (int c = 0; c < NMAX; ++c)
-      if (c == r) dr = a[c];
-    double x = y / dr;
-    // L^T x = z: x_k = z_k - sum_{r > k} l_rk x_r, k descending; lane r holds l_rk (register k) and x_r
-#pragma unroll
-    for (int kk = NMAX - 2; kk >= 0; --kk) {
-      double t = r > kk ? a[kk] * x : 0.0;
-      t += dpp_f64<0xB1>(t);   // lane ^ 1
-      t += dpp_f64<0x4E>(t);   // lane ^ 2
-      t += dpp_f64<0x141>(t);  // lane ^ 7  (row_half_mirror)
-      t += dpp_f64<0x140>(t);  // lane ^ 15 (row_mirror): every lane of a row of 16 holds the row's sum
-      const double tot = (readlane_f64(t, 0) + readlane_f64(t, 16)) + (readlane_f64(t, 32) + readlane_f64(t, 48));
-      if (r == kk) x -= tot;
-    }
-    if (r < n) g[r] = x;
-    if (r == 0) *s_flag = bad ? 0 : 1;
-  }
-  __syncthreads();
-  return *s_flag != 0;
-}
-
 template <class SP>
 GL_DEV bool ldlt_solve_small(const GenP& G, const BaK& k, double lambda, const double* src, int lsrc, bool fuse, SP S, int ld,
                              double* g, int n, int* s_flag, double* idg) {
-#ifdef GL_BAGEN_WAVE_LDLT  // (measured, not the default: see ldlt_solve_wave)
-  if (n <= 24) return ldlt_solve_wave<24>(G, k, lambda, src, lsrc, fuse, g, n, s_flag, idg + 128);
-  if (n <= 48) return ldlt_solve_wave<48>(G, k, lambda, src, lsrc, fuse, g, n, s_flag, idg + 128);
-#endif
   if (n <= 32) return ldlt_solve_tiles<2>(G, k, lambda, src, lsrc, fuse, S, ld, g, n, s_flag, idg);
   if (n <= 48) return ldlt_solve_tiles<3>(G, k, lambda, src, lsrc, fuse, S, ld, g, n, s_flag, idg);
   if (n <= 80) return ldlt_solve_tiles<5>(G, k, lambda, src, lsrc, fuse, S, ld, g, n, s_flag, idg);
@@ -1704,10 +1548,7 @@ __global__ __launch_bounds__(T_BA) void k_ba_gen_t(BaK k, GmmDev gm, int B, int 
   G.lin = takeD((size_t)NOBS * 12);
   G.ptw = takeD((size_t)L * 12);
   G.chi_o = takeD((size_t)NOBS);
-#ifndef GL_LD_PAD
-#define GL_LD_PAD 1  // odd row stride: the column reads of the solve spread over the LDS banks
-#endif
-  G.ld = n + GL_LD_PAD;  // row stride of S
+  G.ld = n + 1;  // row stride of S, odd: the column reads of the solve spread over the LDS banks
   G.S = takeD((size_t)n * G.ld);
   G.part = takeD((size_t)2 * 64 * 4);
   G.toggle = 0;
@@ -2017,7 +1858,7 @@ GL_DEV void genp_init(GenP& G, const PipeA& a, int f, int NB, int pb) {
   G.lin = takeD((size_t)NOBS * 12);
   G.ptw = takeD((size_t)L * 12);
   G.chi_o = takeD((size_t)NOBS);
-  G.ld = n + GL_LD_PAD;
+  G.ld = n + 1;
   G.S = takeD((size_t)n * G.ld);
   G.part = takeD((size_t)2 * 64 * 4);
   G.toggle = 0;
@@ -2705,7 +2546,7 @@ __global__ __launch_bounds__(T_BA, 2) void kp_schur(PipeA a) {
 // behind device-scope fences made the Schur pass 3.5 x slower) ------------------------------------------------------------
 // one sum of one block of window f: its chunks added in chunk order, the total to its place in the assembled system
 GL_DEV void assemble_sum(const PipeA& a, const GenP& G, int f, int b, int sidx) {
-  const int P = a.P, ld = 6 * P + GL_LD_PAD;
+  const int P = a.P, ld = 6 * P + 1;
   int j1 = 0, rem = b;
   while (rem >= P - j1) {
     rem -= P - j1;
@@ -2935,7 +2776,7 @@ int launch_ba_gen(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* p
   const size_t per = ((gen_scratch_bytes(P, F, L, NOBS) + 255) / 256) * 256;
   GmmDev gm{g->rec12, g->axis, g->sqrt_info, g->hgw, g->flags, g->plane4};
   const size_t n = 6 * (size_t)P;
-  const size_t s_bytes = n * (n + GL_LD_PAD) * sizeof(double);
+  const size_t s_bytes = n * (n + 1) * sizeof(double);
   int s_in_lds = s_bytes <= 136 * 1024 ? 1 : 0;  // 6 P <= 126: every system the register-tile solve takes
   const size_t lds = s_in_lds ? s_bytes : 0;
   if (s_in_lds)
@@ -3107,7 +2948,7 @@ static int pipe_lane_setup(Ctx* c, PipeLane& ln, int stats_off, bool stats_ok, c
   a.ext_judge = c->opt.pipe_judge >= 0 ? (c->opt.pipe_judge != 0 ? 1 : 0) : (B >= 32 ? 1 : 0);
   a.unfinished = (int*)s;  // [0] problems not finished, [1] cycles the slowest of them needed
   const size_t n = 6 * (size_t)P;
-  ln.s_bytes = n <= 128 ? n * (n + GL_LD_PAD) * sizeof(double) : 0;
+  ln.s_bytes = n <= 128 ? n * (n + 1) * sizeof(double) : 0;
   if (ln.s_bytes) GL_HIP(ensure_dynamic_lds(c, (const void*)kp_solve, ln.s_bytes));
   // (ln.hw: page-locked words of this lane - [0..1] the device's count of unfinished problems and the cycles of the slowest as copied
   // back between chunks of cycles, [2..3] their initial values)

@@ -201,56 +201,13 @@ GL_DEV PoseRt rt_update(const PoseRt& P, const double* u) {
   return rt_uni(N);
 }
 
-// 6x6 LDL^T on the packed upper triangle (row-major i <= j, as accumulated), (H + lambda I) x = b;
-// fails on a non-positive / non-finite pivot like ldlt_solve<6>(..., require_positive = true)
-#define GL_PU(i, j) ((i) * 6 - (i) * ((i)-1) / 2 + ((j) - (i)))
-GL_DEV bool ldlt6_packed_pos(const double* H, const double* b, double lambda, double* x) {
-  double a[21], iD[6], y[6];
-#pragma unroll
-  for (int i = 0; i < 21; ++i) a[i] = H[i];
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = a[GL_PU(j, j)] + lambda;
-#pragma unroll
-    for (int kk = 0; kk < j; ++kk) d -= a[GL_PU(kk, j)] * a[GL_PU(kk, j)] * a[GL_PU(kk, kk)];
-    if (!(d > 0.0) || !isfinite(d)) ok = false;
-    a[GL_PU(j, j)] = d;
-    iD[j] = rcp_nr(d);
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double s = a[GL_PU(j, i)];
-#pragma unroll
-      for (int kk = 0; kk < j; ++kk) s -= a[GL_PU(kk, i)] * a[GL_PU(kk, j)] * a[GL_PU(kk, kk)];
-      a[GL_PU(j, i)] = s * iD[j];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double s = b[i];
-#pragma unroll
-    for (int kk = 0; kk < i; ++kk) s -= a[GL_PU(kk, i)] * y[kk];
-    y[i] = s;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) y[i] *= iD[i];
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double s = y[i];
-#pragma unroll
-    for (int kk = i + 1; kk < 6; ++kk) s -= a[GL_PU(i, kk)] * x[kk];
-    x[i] = s;
-  }
-  return ok;
-}
+#define GL_PU(i, j) ((i) * 6 - (i) * ((i)-1) / 2 + ((j) - (i)))  // packed upper triangle of a 6x6, i <= j
 
-// The same system by 3 x 3 BLOCKS (round 6; see ldlt6_blocked in gl_ba_fast_impl.hpp): [[A, B], [B^T, C]] - A = L_a D_a L_a^T, Y = A^-1 [B | b_r],
-// S = C - B^T Y_B, x_t = S^-1 (b_t - B^T y), x_r = y - Y_B x_t - the pivots (and the failure test) of the unpivoted LDL^T of the whole matrix,
-// about 50 instructions deep where the column-by-column factorisation is a chain of ~190: every wave of the frame-at-a-time shapes runs
-// this solve on a SIMD of its own, once per pass.
-#ifndef GL_POSE_SOLVE_BLOCKED
-#define GL_POSE_SOLVE_BLOCKED 1
-#endif
+// (H + lambda I) x = b, 6 x 6, on the packed upper triangle (row-major i <= j, as accumulated), by 3 x 3 BLOCKS (see ldlt6_blocked in
+// gl_ba_fast_impl.hpp): [[A, B], [B^T, C]] - A = L_a D_a L_a^T, Y = A^-1 [B | b_r], S = C - B^T Y_B, x_t = S^-1 (b_t - B^T y),
+// x_r = y - Y_B x_t - the pivots of the unpivoted LDL^T of the whole matrix; fails on a non-positive / non-finite pivot like
+// ldlt_solve<6>(..., require_positive = true).  About 50 instructions deep where the column-by-column factorisation is a chain of
+// ~190 (profiles/r6_pose_solve_blocked.txt): every wave of the frame-at-a-time shapes runs this solve on a SIMD of its own, once per pass.
 GL_DEV bool pose_ldl3_factor(const double* D, double* f) {  // f = {l10, l20, l21, 1/d0, 1/d1, 1/d2}; false on a non-positive / non-finite pivot
   const double i0 = rcp_nr(D[0]);
   const double m2 = fma(D[0], D[3], -(D[1] * D[1]));  // d0 d1
@@ -714,7 +671,7 @@ __device__ __forceinline__ void pose_frame(const PoseKParams& kp, const int f, c
           // (eight-wave instances: letting only the waves 0..3 solve and handing step + trial pose to the others through LDS was built and
           //  measured - the first barrier's wait halves, but the extra barrier and 28 - 81 spilled registers cost more: 14.0 k against
           //  13.3 k ticks per pass at 1 200 edges)
-          const bool ok2 = GL_POSE_SOLVE_BLOCKED ? ldlt6_blocked_pos(H, H + 21, lambda, dx) : ldlt6_packed_pos(H, H + 21, lambda, dx);
+          const bool ok2 = ldlt6_blocked_pos(H, H + 21, lambda, dx);
           POSE_PT(ts1);
           POSE_PADD(4, ts0, ts1);  // 6 x 6 solve
           PoseRt Pn = P;

@@ -9,8 +9,13 @@ gated at chi2 <= 9) + the structure-constrained refinement (single free pose,
 Schur-marginalised points, 5/5/40 LM schedule).  The in-place state (poses, points) is
 restored from pristine device copies inside the timed region.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: the headline and what the
+timed steps' own kernel timers give (`roofline` of the refine, `kernel_ms_per_step`).  --full adds everything that takes
+runs of its own: the other legs (exhaustive sweep, two streams, 1 000-point class, anchored step), the sweep's roofline and
+the cell index's pair count, the single-frame latencies and the CPU baselines.
 
 Frames are independent units: with N > 1 every rank owns its own batch (weak scaling, GMM
 replicated, no data-path collective); the timed region is bracketed by barrier +
@@ -375,9 +380,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=16384, help="frames per step per GPU (4 096 until round 4: the tail of a launch - CUs idle while the last frames finish - is a quarter as long at 16 384)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what takes runs of its own: the other legs, the sweep's roofline, "
+                         "the latencies and the CPU baselines (off: the timed steps and the line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="the timed step only (what tools/profile_bench.sh profiles: the two-stream / sweep / class legs launch the same kernels)")
+                    help="with --full: leave out the legs beside the headline (the two-stream / sweep / class legs launch the same kernels)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the last of them computed (rank 0: refined poses, map points, associations; "
                          "a fixed seeded frame sample where the batch is large) to DIR/<name>.npy, float64")
@@ -457,7 +465,8 @@ def main():
     prep_ms, prep_n = ctx.timing_read(api.TIMER_BA_PREP)
     ctx.timing(False)
 
-    extra = not args.no_extra_legs
+    full = args.full
+    extra = full and not args.no_extra_legs
     dt_sweep = dt_two = None
     two_same = None
     sweep_steps = two_steps = 0
@@ -466,11 +475,11 @@ def main():
         dt_sweep, sweep_steps, dt_two, two_steps, two_same, leg_1000, leg_prior = extra_legs(
             args, ranks, ctx, gmm, cam, prm, mean, cov, pose0, Xw0, obs, octv, pose, Xw, step, start_timers, trials, outer, B, world, local, dev)
 
-    # the plain N x K sweep on the same points (its roofline record), and
+    # --full: the plain N x K sweep on the same points (its roofline record), and
     # the number of chi2 evaluations the cell index needed for them
     sweep_ms = None
     idx_pairs = None
-    if rank == 0:
+    if full and rank == 0:
         flat = Xw0.reshape(-1, 3)
         with torch.cuda.stream(ctx.stream):
             gmm.associate3d(flat, api.ASSOC_EXHAUSTIVE)
@@ -526,13 +535,6 @@ def main():
 
     if rank == 0:
         frames_total = B * args.steps * world
-        pairs = float(B) * N_PTS * K_GAUSS
-        assoc_s = assoc_ms / 1e3 / max(assoc_n, 1)
-        sweep_s = sweep_ms / 1e3
-        ach_tflops = FLOP_PER_PAIR * pairs / sweep_s / 1e12
-        # algorithmic HBM bytes of one association launch: points in, records in, idx+d2 out
-        alg_bytes = B * N_PTS * 24 + K_GAUSS * 96 + B * N_PTS * 12
-        info = gmm.index_info()
         ba_s = ba_ms / 1e3 / max(ba_n, 1)
         ba_flop_all_points = refine_flop(N_PTS, n_trials, n_outer)    # rounds 1-4: every point priced in every trial
         ba_flop = refine_flop_active(n_edge_trials, n_edge_outer)      # round 5: the level-0 edges only
@@ -540,7 +542,6 @@ def main():
         ba_tflops = ba_flop / ba_s / 1e12 if ba_n else None
         ba_bytes = B * (N_PTS * (24 + 24 + 4 + 4 + 8 + 24 + 4) + 2 * 56)  # Xw, obs, octave, assoc, d2 in; points, final assoc out; pose in/out
         ba_traffic, ba_traffic_src, ba_traffic_stale = measured_traffic("k_ba1_fast", B)
-        sw_traffic, sw_traffic_src, _ = measured_traffic("k_assoc_brute", B)
         ba_insts, ba_insts_frames = measured_counter("k_ba1_fast", "SQ_INSTS_VALU")
         insts_pt = (ba_insts * 64.0 / (ba_insts_frames * N_PTS * (n_trials / B))) if ba_insts else None
         if ba_traffic_stale:
@@ -603,8 +604,18 @@ def main():
                 "hbm": {"achieved_GBs": ba_bytes / ba_s / 1e9, "peak_GBs": PEAK_HBM_GBS,
                         "algorithmic_bytes_per_launch": ba_bytes},
             },
+        }
+        if full:
+            pairs = float(B) * N_PTS * K_GAUSS
+            assoc_s = assoc_ms / 1e3 / max(assoc_n, 1)
+            sweep_s = sweep_ms / 1e3
+            ach_tflops = FLOP_PER_PAIR * pairs / sweep_s / 1e12
+            # algorithmic HBM bytes of one association launch: points in, records in, idx+d2 out
+            alg_bytes = B * N_PTS * 24 + K_GAUSS * 96 + B * N_PTS * 12
+            sw_traffic, sw_traffic_src, _ = measured_traffic("k_assoc_brute", B)
+            info = gmm.index_info()
             # the association inside the step: exact argmin through the cell index (gather bound)
-            "assoc_index": {
+            out["assoc_index"] = {
                 "kernel": "k_assoc_cells_coop (exact cell index, wave-cooperative record gather; chi2 <= 9 resolved, the rest gated out)",
                 "avg_launch_ms": 1e3 * assoc_s,
                 "pairs_evaluated": idx_pairs,
@@ -613,9 +624,9 @@ def main():
                 "gather_bytes": idx_pairs * 96 + B * N_PTS * 36,
                 "gather_GBs": (idx_pairs * 96 + B * N_PTS * 36) / assoc_s / 1e9 if assoc_n else None,
                 "index": info,
-            },
+            }
             # the plain N x K sweep (GL_ASSOC_EXHAUSTIVE) on the same points, timed outside the step
-            "roofline_assoc": {
+            out["roofline_assoc"] = {
                 "kernel": "k_assoc_brute (fp64 Mahalanobis argmin, all pairs)",
                 "bound": "valu_fp64",
                 "achieved": ach_tflops,
@@ -628,10 +639,9 @@ def main():
                 "flop_per_launch": FLOP_PER_PAIR * pairs,
                 "hbm": {"achieved_GBs": alg_bytes / sweep_s / 1e9, "peak_GBs": PEAK_HBM_GBS,
                         "algorithmic_bytes_per_launch": alg_bytes},
-            },
-            "kernel_ms_per_step": {"associate": assoc_ms / max(args.steps, 1), "refine_setup": prep_ms / max(args.steps, 1),
-                                   "refine": ba_ms / max(args.steps, 1)},
-        }
+            }
+        out["kernel_ms_per_step"] = {"associate": assoc_ms / max(args.steps, 1), "refine_setup": prep_ms / max(args.steps, 1),
+                                     "refine": ba_ms / max(args.steps, 1)}
         if not extra:
             print(json.dumps(out))
             ranks.close()

@@ -34,7 +34,7 @@ def test_cpu_baseline_leg_runs_without_gpu():
 def test_bench_cli_accepts_the_driver_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs"):
+    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs", "--full"):
         assert flag in out.stdout
 
 
@@ -106,9 +106,39 @@ def test_bench_gpus_n_refuses_a_node_with_fewer_gpus():
     assert out.returncode != 0 and "GPU(s) visible" in out.stderr and not out.stdout.strip()
 
 
+FULL_ONLY = ("cpu_baseline", "latency", "speedup_batched", "assoc_index", "roofline_assoc", "step_with_exhaustive_sweep",
+             "step_two_streams", "step_anchored_prior")
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_live():
+    """A plain run times the steps and prints the headline with what the timed steps' own timers give; whatever takes runs of
+    its own (the other legs, the sweep, the latencies, the CPU baselines) is left to --full."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "512"],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.strip().split("\n") if l.startswith("{")]
+    assert len(lines) == 1  # ONE JSON line
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "kernel_ms_per_step"):
+        assert k in d, k
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+    frames = d["config"]["frames_per_step_per_gpu"] * d["steps"] * d["n_gpus"]
+    assert abs(d["value"] - frames / (d["ms_per_step"] * d["steps"] / 1e3)) / d["value"] < 1e-6
+    r = d["roofline"]
+    assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9 and 0 < r["frac"] < 1
+    assert r["avg_launch_ms"] * d["steps"] <= d["ms_per_step"] * d["steps"] * 1.001  # the kernel fits inside the step
+    assert "class_1000" not in r
+    for k in FULL_ONLY:
+        assert k not in d, k
+
+
 @pytest.mark.gpu
 def test_bench_line_contract_live():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "512"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "512",
+                          "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().split("\n") if l.startswith("{")]
@@ -121,6 +151,8 @@ def test_bench_line_contract_live():
     assert d["dtype"] == "f64" and d["data"] == "synthetic" and d["vs_baseline"] is None  # the exact fp64 step is what is timed
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
     assert "workload" in d["config"] and "model" not in d["config"]
+    for k in FULL_ONLY:
+        assert k in d, k
     frames = d["config"]["frames_per_step_per_gpu"] * d["steps"] * d["n_gpus"]
     assert abs(d["value"] - frames / (d["ms_per_step"] * d["steps"] / 1e3)) / d["value"] < 1e-6
     r = d["roofline"]

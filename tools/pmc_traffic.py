@@ -55,7 +55,7 @@ def main(root):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
     out["kernel_source_sha"] = bench.kernel_source_fingerprint()  # bench.py flags a summary made from other sources as stale
-    out["how"] = ("rocprofv3 --kernel-trace --pmc <counters> -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline, one run per "
+    out["how"] = ("rocprofv3 --kernel-trace --pmc <counters> -- python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline, one run per "
                   "counter group (tools/profile_bench.sh); averages over the bench launches")
     print(json.dumps(out, indent=1))
 

@@ -16,10 +16,12 @@ from . import _lib
 ASSOC_BRUTE = 0
 ASSOC_KNN5_EUCLID = 1
 ASSOC_EXHAUSTIVE = 2
+ASSOC_SCREENED = 3  # the same output as ASSOC_EXHAUSTIVE, bit for bit: fp32 screen + fp64 verify of the survivors
 
 F_MEAN, F_COV, F_COV_INV, F_DET, F_SCALE, F_AXIS, F_SQRT_INFO, F_FLAGS, F_NBS_PTR, F_NBS_IDX, F_NBS_DIST = range(11)
 TIMER_ASSOC, TIMER_REFINE_POSE, TIMER_BA, TIMER_BA_PREP = 0, 1, 2, 3
 COUNTER_BA_REDONE, COUNTER_MATCH_ROUNDS, COUNTER_MATCH_UNITS = 0, 1, 2
+COUNTER_ASSOC_SCREEN_VERIFIED, COUNTER_ASSOC_SCREEN_FALLBACK = 4, 5
 
 
 class GLError(RuntimeError):
@@ -125,7 +127,9 @@ class Context:
 
     def counter_read(self, counter=0, reset=True):
         """gl_ctx_counter_read: 0 = GL_COUNTER_BA_REDONE (frames of latency-shape launches redone by the follow-up kernel),
-        1 / 2 = GL_COUNTER_MATCH_ROUNDS / _UNITS (rounds of the matchers' owner fixed point, and the frames / pairs they ran on)."""
+        1 / 2 = GL_COUNTER_MATCH_ROUNDS / _UNITS (rounds of the matchers' owner fixed point, and the frames / pairs they ran on),
+        4 / 5 = GL_COUNTER_ASSOC_SCREEN_VERIFIED / _FALLBACK (pairs the screened sweep re-evaluated in fp64, and points it sent
+        through the full fp64 sweep)."""
         v = C.c_int64(0)
         _check(self.lib.gl_ctx_counter_read(self.h, counter, C.byref(v), 1 if reset else 0))
         return v.value

@@ -20,7 +20,7 @@ void set_error(const char* fmt, ...) {
 // option table: name as in gl_ctx_set_option; the environment variable is GMMLOC_<NAME IN CAPITALS>
 #define GL_OPTION_LIST(X) \
   X(ba_shape) X(ba_step32) X(ba_persist) X(ba_slow) X(ba_fixed_pack) X(ba_rendezvous_us) X(ba_test_abort_seq) X(ba_same_xcd) X(pose_waves) X(pose_regs) X(pose_compact) X(pose_compact_cap) X(fuse_records) X(bagen_nb) X(bagen_mode) X(view_slot_lds) X(view_threads) \
-  X(assoc_index_min) X(assoc_grid) X(assoc_coop) X(assoc_rec_pad) X(assoc_coop_long) X(assoc_coop_bal) X(assoc_pack_mb) X(assoc_cell8) X(assoc_cell) X(assoc_globcells) X(match_desc_lds) X(pipe_lanes) X(pipe_judge) X(pipe_fuse_asm) X(schur_kper)
+  X(assoc_index_min) X(assoc_grid) X(assoc_coop) X(assoc_rec_pad) X(assoc_coop_long) X(assoc_coop_bal) X(assoc_pack_mb) X(assoc_cell8) X(assoc_cell) X(assoc_globcells) X(match_desc_lds) X(pipe_lanes) X(pipe_judge) X(pipe_fuse_asm) X(schur_kper) X(assoc_screen32)
 double* option_slot(Options& o, const char* name) {
 #define X(n) \
   if (strcmp(name, #n) == 0) return &o.n;
@@ -78,6 +78,27 @@ int ctx_scratch_b(Ctx* c, size_t bytes, void** out) {
     c->scratch_b_bytes = want;
   }
   *out = c->scratch_b;
+  return GL_OK;
+}
+
+// fourth block: the screened association's per-split candidate lists and its fp64 fallback (launch_assoc_screened), so that it
+// needs nothing from the block its caller sized for the fp64 sweep
+int ctx_scratch_s(Ctx* c, size_t bytes, void** out) {
+  if (bytes > c->scratch_s_bytes) {
+    if (c->scratch_s) {
+      GL_HIP(hipStreamSynchronize(c->stream));
+      GL_HIP(hipFree(c->scratch_s));
+      c->scratch_s = nullptr;
+      c->scratch_s_bytes = 0;
+    }
+    const size_t want = bytes + bytes / 2;
+    if (hipMalloc(&c->scratch_s, want) != hipSuccess) {
+      set_error("scratch hipMalloc(%zu) failed", want);
+      return GL_ERR_NOMEM;
+    }
+    c->scratch_s_bytes = want;
+  }
+  *out = c->scratch_s;
   return GL_OK;
 }
 
@@ -205,6 +226,7 @@ int gl_ctx_destroy(gl_ctx_t* ctx) {
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->scratch_b) (void)hipFree(c->scratch_b);
   if (c->scratch_c) (void)hipFree(c->scratch_c);
+  if (c->scratch_s) (void)hipFree(c->scratch_s);
   if (c->counters) (void)hipFree(c->counters);
   if (c->host_word) (void)hipHostFree(c->host_word);
   for (int k = 0; k < 3; ++k) {

@@ -337,9 +337,17 @@ int launch_assoc_brute(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* 
 }
 
 // all-pairs sweep of N points, or (list / count_dev given) of the listed subset; `scratch` (may be
-// NULL: taken from the context) must hold assoc_scratch_bytes(K, N, list != NULL)
+// NULL: taken from the context) must hold assoc_scratch_bytes(K, N, list != NULL).  Option assoc_screen32 = 1 routes every
+// caller through the fp32-screened sweep (gl_assoc32.hip), which has scratch of its own and returns the same bits.
 int launch_assoc_sweep(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,
                        const int32_t* count_dev, void* scratch) {
+  if (c->opt.assoc_screen32 == 1) return launch_assoc_screened(c, g, pts, N, idx, d2, list, count_dev);
+  return launch_assoc_sweep64(c, g, pts, N, idx, d2, list, count_dev, scratch);
+}
+
+// the fp64 sweep itself (k_assoc_brute + k_assoc_merge)
+int launch_assoc_sweep64(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,
+                         const int32_t* count_dev, void* scratch) {
   const int K = g->K;
   int ppt, ptiles, nsplit, kchunk;
   assoc_shape(K, N, list != nullptr, &ppt, &ptiles, &nsplit, &kchunk);
@@ -425,7 +433,8 @@ int gl_knn3d(gl_ctx_t* ctx, const gl_gmm_t* gmm, const double* pts_dev, int N, i
 int gl_associate3d(gl_ctx_t* ctx, const gl_gmm_t* gmm, const double* pts_dev, int N, int mode, int32_t* idx_dev,
                    double* d2_dev) {
   GL_REQUIRE(ctx && gmm, "null argument");
-  GL_REQUIRE(mode == GL_ASSOC_BRUTE || mode == GL_ASSOC_KNN5_EUCLID || mode == GL_ASSOC_EXHAUSTIVE, "unknown mode");
+  GL_REQUIRE(mode == GL_ASSOC_BRUTE || mode == GL_ASSOC_KNN5_EUCLID || mode == GL_ASSOC_EXHAUSTIVE || mode == GL_ASSOC_SCREENED,
+             "unknown mode");
   if (N == 0) return GL_OK;
   GL_REQUIRE(idx_dev, "null argument");
   GL_REQUIRE(N > 0 && pts_dev, "bad N / pts");
@@ -436,6 +445,7 @@ int gl_associate3d(gl_ctx_t* ctx, const gl_gmm_t* gmm, const double* pts_dev, in
   double min_pairs = 6.7e7;
   if (c->opt.assoc_index_min >= 0) min_pairs = c->opt.assoc_index_min;  // option (tests force the index with 0)
   const bool small = (double)N * g->K < min_pairs;
+  if (mode == GL_ASSOC_SCREENED) return gl::launch_assoc_screened(c, g, pts_dev, N, idx_dev, d2_dev, nullptr, nullptr);
   if (mode == GL_ASSOC_EXHAUSTIVE || (mode == GL_ASSOC_BRUTE && (!g->grid.enabled || c->opt.assoc_grid == 0 || small)))
     return gl::launch_assoc_brute(c, g, pts_dev, N, idx_dev, d2_dev);
   void* scratch = nullptr;

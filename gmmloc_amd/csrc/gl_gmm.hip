@@ -204,6 +204,7 @@ int gl_gmm_create(gl_ctx_t* ctx, const double* mean, const double* cov, int K, c
   alloc((void**)&g->plane4, sizeof(double) * 4 * K);
   alloc((void**)&g->flags, K);
   if (rc == GL_OK) rc = gl::launch_build_components(c, g);
+  if (rc == GL_OK) rc = gl::build_screen_records(c, g);
   if (rc == GL_OK) rc = gl::launch_build_neighbours(c, g);
   if (rc == GL_OK) rc = gl::build_cell_index(c, g);
   if (rc != GL_OK) {
@@ -235,7 +236,7 @@ int gl_gmm_destroy(gl_gmm_t* gmm) {
   if (!gmm) return GL_OK;
   gl::Gmm* g = gl::G(gmm);
   (void)hipSetDevice(g->device);
-  void* ptrs[] = {g->rec12, g->mean, g->cov, g->det, g->scale, g->axis, g->sqrt_info, g->hgw, g->plane4, g->flags, g->nbs_ptr, g->nbs_idx, g->nbs_dist};
+  void* ptrs[] = {g->rec12, g->mean, g->cov, g->det, g->scale, g->axis, g->sqrt_info, g->hgw, g->plane4, g->flags, g->nbs_ptr, g->nbs_idx, g->nbs_dist, g->rec32};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   gl::free_cell_index(g);

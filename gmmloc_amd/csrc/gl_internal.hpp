@@ -90,6 +90,13 @@ struct Gmm {
   double* nbs_dist = nullptr;
   int nnz = 0;
   CellIndex grid;
+  // fp32 screen records of GL_ASSOC_SCREENED (gl_assoc32.hip), built at gl_gmm_create: K x 12 floats
+  // {mean - scr_o (3), cov_inv 00 11 22, cov_inv 01+10, 02+20, 12+21, bound constant, pad, pad}; null when the map has
+  // values fp32 cannot hold (the screened mode is then the fp64 sweep)
+  float* rec32 = nullptr;
+  double scr_o[3] = {0, 0, 0};  // map-wide origin the means and points are shifted by
+  double scr_rmax = 0;          // max_k |mean_k - scr_o|_inf, rounded up
+  double scr_cmax = 0;          // max_k of the bound constant
   gl_params prm;
 };
 
@@ -129,6 +136,7 @@ struct Options {
   double pipe_lanes = -1;       // pipelined local BA in batches: streams a call's windows are split over (-1 auto: 2 from 16 windows; 1 .. 4; A/B)
   double pipe_judge = -1;       //   the verdict on a trial as a kernel of its own (-1 auto: from 32 windows per lane; 0 / 1; A/B)
   double schur_kper = -1;       //   chunks of a block one wave of the Schur pass takes (-1 auto; 1 / 2 / 4 / 8; A/B)
+  double assoc_screen32 = 0;    // 1: every all-pairs sweep (launch_assoc_sweep) runs as the fp32 screen + fp64 verify of GL_ASSOC_SCREENED (same bits)
 };
 // name -> member; nullptr if unknown
 double* option_slot(Options& o, const char* name);
@@ -152,6 +160,8 @@ struct Ctx {
   size_t scratch_bytes = 0;
   void* scratch_b = nullptr;  // second block (ctx_scratch_b): the matchers' candidate cache
   size_t scratch_b_bytes = 0;
+  void* scratch_s = nullptr;  // fourth block (ctx_scratch_s): the screened sweep's partial lists, whatever block its caller passed
+  size_t scratch_s_bytes = 0;
   void* scratch_c = nullptr;  // third block (ctx_scratch_c): the intermediates of gl_track_frame_chain, whose stages use the other two
   size_t scratch_c_bytes = 0;
   // staging of the frame-at-a-time host entry point (gl_track_frame_host): page-locked + device mirror, grown on demand
@@ -182,6 +192,7 @@ struct Ctx {
 int ctx_scratch(Ctx* c, size_t bytes, void** out);
 int ctx_scratch_b(Ctx* c, size_t bytes, void** out);
 int ctx_scratch_c(Ctx* c, size_t bytes, void** out);
+int ctx_scratch_s(Ctx* c, size_t bytes, void** out);
 bool probe_xcc_ids(Ctx* c);  // gl_ba_fast.hip
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE and costs a driver call: a context (one device,
 // one host thread) remembers the limit it has set for each kernel and raises it only when it grows.  The caller
@@ -247,6 +258,12 @@ int launch_assoc_brute(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* 
 int launch_assoc_sweep(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,
                        const int32_t* count_dev, void* scratch);
 size_t assoc_scratch_bytes(int K, int N, bool listed = false);
+// (gl_assoc32.hip) the fp32-screened sweep: same arguments and results as launch_assoc_sweep, own scratch (ctx_scratch_s)
+int build_screen_records(Ctx* c, Gmm* g);
+int launch_assoc_screened(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,
+                          const int32_t* count_dev);
+int launch_assoc_sweep64(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,
+                         const int32_t* count_dev, void* scratch);
 int launch_assoc_index(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, bool resolve_all,
                        void* scratch);
 size_t assoc_index_scratch_bytes(int K, int N, bool resolve_all);

@@ -85,6 +85,8 @@ void* gl_ctx_stream(gl_ctx_t* ctx);
  *     from a queue - same bits; A/B),
  *   ba_step32 (1: fp32-cached point step in gl_track_frames, faster, NOT bit-compatible with the default),
  *   assoc_grid (0: every association is the plain N x K sweep, never the cell index),
+ *   assoc_screen32 (0; 1: every all-pairs sweep - GL_ASSOC_EXHAUSTIVE, GL_ASSOC_BRUTE where it sweeps, the points the cell index
+ *     leaves unresolved, gl_track_frames* with assoc_grid = 0 - runs as GL_ASSOC_SCREENED: same bits),
  *   assoc_coop (1; 0: the indexed association gathers a record per lane instead of per six lanes - A/B),
  *   assoc_rec_pad (1; 0: the cooperative gather reads the 96-byte records instead of their one-per-128-byte-line copy - A/B),
  *   assoc_coop_long (1; 0: a point whose cell lists more than three candidates walks that list alone after the cooperative gather - A/B),
@@ -151,7 +153,11 @@ enum gl_counter {
                                       window's cooperative launch was refused (another context holds the CUs): same arithmetic, but the
                                       window's partial sums are added in another order - the one exception to "a window's bits depend on
                                       its shape and bagen_mode only" (a refused sub-batch is first halved at the same workgroup count) */
-  GL_COUNTER_COUNT = 4
+  GL_COUNTER_ASSOC_SCREEN_VERIFIED = 4, /* (point, Gaussian) pairs that the screened sweep (GL_ASSOC_SCREENED, option assoc_screen32)
+                                           re-evaluated in fp64 after its fp32 screen */
+  GL_COUNTER_ASSOC_SCREEN_FALLBACK = 5, /* points the screened sweep sent through the full fp64 sweep instead (candidate lists too long,
+                                           coordinates fp32 cannot hold, or a map whose records fp32 cannot hold) */
+  GL_COUNTER_COUNT = 6
 };
 int gl_ctx_counter_read(gl_ctx_t* ctx, int counter, int64_t* value, int reset);
 /* Optional statistics: while a device buffer of n int32 is registered, gl_track_frames (and gl_track_frames_anchored,
@@ -219,7 +225,11 @@ enum gl_assoc_mode {
                                points it cannot resolve: identical output to GL_ASSOC_EXHAUSTIVE */
   GL_ASSOC_KNN5_EUCLID = 1, /* GMM::queryPoint (gaussian_mixture.cpp:545-576): nearest mean
                                of the exact 5-NN; d2 = its chi2                          */
-  GL_ASSOC_EXHAUSTIVE = 2   /* the same argmin by the plain N x K sweep (no index)       */
+  GL_ASSOC_EXHAUSTIVE = 2,  /* the same argmin by the plain N x K sweep (no index)       */
+  GL_ASSOC_SCREENED = 3     /* the same output as GL_ASSOC_EXHAUSTIVE, bit for bit: an N x K sweep in packed fp32
+                               with a rigorous per-pair error bound, then an fp64 re-evaluation (chi2 as above) of
+                               every component the bound cannot rule out; points it cannot screen go through the
+                               fp64 sweep (GL_COUNTER_ASSOC_SCREEN_VERIFIED / _FALLBACK count both) */
 };
 /* pts_dev: N x 3; idx_dev: N int32; d2_dev: N double (may be NULL). */
 int gl_associate3d(gl_ctx_t* ctx, const gl_gmm_t* gmm, const double* pts_dev, int N, int mode, int32_t* idx_dev,

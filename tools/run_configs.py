@@ -24,6 +24,16 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 PEAK = 78.6
+PEAK32 = 157.3  # fp32 vector (v_pk_fma_f32)
+
+
+def screen_counts(ctx, fn):
+    """GL_COUNTER_ASSOC_SCREEN_VERIFIED / _FALLBACK of one call of fn."""
+    from gmmloc_amd import api
+    ctx.counter_read(api.COUNTER_ASSOC_SCREEN_VERIFIED)
+    ctx.counter_read(api.COUNTER_ASSOC_SCREEN_FALLBACK)
+    fn()
+    return ctx.counter_read(api.COUNTER_ASSOC_SCREEN_VERIFIED), ctx.counter_read(api.COUNTER_ASSOC_SCREEN_FALLBACK)
 
 
 def ev_time(torch, fn, reps, stream):
@@ -56,6 +66,17 @@ def config2(torch, ctx, out):
         tB = ev_time(torch, lambda: g.associate3d(ptsB, EX), 10, ctx.stream)
         t1i = ev_time(torch, lambda: g.associate3d(pts1), 200, ctx.stream)
         tBi = ev_time(torch, lambda: g.associate3d(ptsB), 10, ctx.stream)
+        SC = api.ASSOC_SCREENED
+        tBs, tBe = [], []
+        for _ in range(3):  # screened vs fp64 sweep, alternated in this process
+            tBe.append(ev_time(torch, lambda: g.associate3d(ptsB, EX), 10, ctx.stream))
+            tBs.append(ev_time(torch, lambda: g.associate3d(ptsB, SC), 10, ctx.stream))
+        ver, fb = screen_counts(ctx, lambda: g.associate3d(ptsB, SC))
+        res["seed%d_screened" % seed] = {"batched_ms": [1e3 * t for t in tBs], "fp64_sweep_batched_ms": [1e3 * t for t in tBe],
+                                         "speedup_median": float(np.median(tBe) / np.median(tBs)),
+                                         "batched_pairs_per_s": 2000 * 512 * 4096 / float(np.median(tBs)),
+                                         "frac_of_fp32_vector_peak_21_per_pair": 21 * 2000 * 512 * 4096 / float(np.median(tBs)) / 1e12 / PEAK32,
+                                         "verified_pairs_per_point": ver / (2000.0 * 512), "fallback_frac": fb / (2000.0 * 512)}
         res["seed%d" % seed] = {"sweep_single_frame_latency_us": 1e6 * t1, "sweep_batched_pairs_per_s": 2000 * 512 * 4096 / tB,
                                 "sweep_batched_tflops_algorithmic": 21 * 2000 * 512 * 4096 / tB / 1e12,
                                 "sweep_single_frame_tflops_algorithmic": 21 * 2000 * 4096 / t1 / 1e12,
@@ -177,6 +198,15 @@ def config5(torch, ctx, out):
     t = ev_time(torch, lambda: g.associate3d(pts, api.ASSOC_EXHAUSTIVE), 5, ctx.stream)
     ti = ev_time(torch, lambda: g.associate3d(pts), 5, ctx.stream)
     pairs = 50000.0 * 65536
+    ts, te = [], []
+    for _ in range(5):  # screened (fp32 screen + fp64 verify, same bits) vs fp64 sweep, alternated in this process
+        te.append(ev_time(torch, lambda: g.associate3d(pts, api.ASSOC_EXHAUSTIVE), 5, ctx.stream))
+        ts.append(ev_time(torch, lambda: g.associate3d(pts, api.ASSOC_SCREENED), 5, ctx.stream))
+    ver, fb = screen_counts(ctx, lambda: g.associate3d(pts, api.ASSOC_SCREENED))
+    out({"config": "5: stress 50 000 pts x 65 536 Gaussians, association, fp32 screen + fp64 verify (exact)",
+         "ms": [1e3 * x for x in ts], "fp64_sweep_ms": [1e3 * x for x in te], "speedup_median": float(np.median(te) / np.median(ts)),
+         "pairs_per_s": pairs / float(np.median(ts)), "frac_of_fp32_vector_peak_21_per_pair": 21 * pairs / float(np.median(ts)) / 1e12 / PEAK32,
+         "verified_pairs_per_point": ver / 50000.0, "fallback_frac": fb / 50000.0})
     out({"config": "5: stress 50 000 pts x 65 536 Gaussians, association (fp64, exact)", "ms": 1e3 * t,
          "index_ms": 1e3 * ti, "index": g.index_info(), "index_pairs_per_point": g.index_work(pts) / 50000.0,
          "index_unresolved_frac": float((g.associate3d(pts)[1] > 9.000009).float().mean().item()),

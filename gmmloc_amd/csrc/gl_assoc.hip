@@ -21,8 +21,6 @@
 //
 // Compiled with -ffp-contract=off; the only fused ops are the explicit fma()
 // of the canonical chi2 (gl_device.hpp) -> bit-identical to the fp64 CPU order.
-#include <cstdlib>
-
 #include "gl_device.hpp"
 #include "gl_internal.hpp"
 
@@ -30,12 +28,12 @@ using namespace gld;
 
 namespace {
 
+// The record of Gaussian k is the same for every lane, so it is fetched with SCALAR loads and used as the SGPR
+// operand of the VALU instructions (chi2_srec, gl_device.hpp): no LDS staging, no barriers, no VGPRs for the record.
 
-// The record of Gaussian k is the same for every lane, so it is fetched with SCALAR loads
-// (constant address space -> s_load_dwordx8/x16 through the scalar cache) and used as the SGPR
-// operand of the VALU instructions: no LDS staging, no barriers, no VGPRs for the record.
-typedef const double __attribute__((address_space(4))) cdouble;
-
+// Gaussians per chunk of the index recovery below.  Chunks of 16 and 8 points per thread were measured with the other launch
+// shapes: the best were within 1 % of each other (profiles/history/r1d_assoc_tuning.txt).
+constexpr int kChunk = 8;
 
 // Per (point, Gaussian) pair the loop issues the 15 canonical v_{add,mul,fma}_f64 + ONE v_min_f64.
 // The argmin index is recovered exactly afterwards: per chunk of 8 Gaussians only {chunk-min < best}
@@ -43,7 +41,7 @@ typedef const double __attribute__((address_space(4))) cdouble;
 // same operation sequence (bit-identical values) to find the first k whose chi2 equals the minimum
 // -- the same lowest-index tie rule as the sequential compare/select loop it replaces
 // (GaussianComponent::chi2 sweep, gaussian.cpp:65-70), at 16.4 instead of 20.9 issue slots per pair.
-template <int PPT, int kChunk>
+template <int PPT>
 __global__ __launch_bounds__(256) void k_assoc_brute(const double* __restrict__ rec12, int K, int kchunk,
                                                      const double* __restrict__ pts, int Nstride,
                                                      double* __restrict__ out_d2, int32_t* __restrict__ out_idx,
@@ -72,13 +70,7 @@ __global__ __launch_bounds__(256) void k_assoc_brute(const double* __restrict__ 
     bc[p] = -1;
   }
 
-  auto pair_chi2 = [&](cdouble* rec, int p) {
-    const double d0 = px[p] - rec[0], d1 = py[p] - rec[1], d2 = pz[p] - rec[2];
-    const double r0 = fma(d2, rec[9], fma(d1, rec[6], d0 * rec[3]));
-    const double r1 = fma(d2, rec[10], fma(d1, rec[7], d0 * rec[4]));
-    const double r2 = fma(d2, rec[11], fma(d1, rec[8], d0 * rec[5]));
-    return fma(r2, d2, fma(r1, d1, r0 * d0));
-  };
+  auto pair_chi2 = [&](cdouble* rec, int p) { return chi2_srec(rec, px[p], py[p], pz[p]); };
   for (int k0 = k_begin; k0 < k_end; k0 += kChunk) {
     double cmin[PPT];
     cdouble* rec = rc + (size_t)k0 * 12;
@@ -277,52 +269,35 @@ __global__ void k_nearest_chi2(const int32_t* __restrict__ knn_idx, int knn, con
 
 namespace gl {
 
-// Launch shape (tools/tune_assoc.py sweep on MI355X, profiles/history/r1_assoc_tuning.txt):
-//  * points per thread: 4 amortises the broadcast LDS reads best once there are enough points;
-//  * K splits: aim for ~4096 workgroups so the tail is short; a single 2 000-point frame still
-//    gets 8 x 64 workgroups.
-// launch-shape tuning knobs of tools/tune_assoc.py (GMMLOC_ASSOC_CHUNK / _PPT / _NSPLIT): process-wide, read from
-// the environment ONCE (first use), never on the call path
-struct AssocTune {
-  int chunk = 8, ppt = 0, nsplit = 0;
-};
-static const AssocTune& assoc_tune() {
-  static const AssocTune t = [] {
-    AssocTune a;
-    if (const char* e = getenv("GMMLOC_ASSOC_CHUNK")) a.chunk = atoi(e) == 16 ? 16 : 8;
-    if (const char* e = getenv("GMMLOC_ASSOC_PPT")) a.ppt = atoi(e);
-    if (const char* e = getenv("GMMLOC_ASSOC_NSPLIT")) a.nsplit = atoi(e);
-    return a;
-  }();
-  return t;
-}
-static int assoc_minchunk() { return assoc_tune().chunk; }
+// Launch shape of an all-pairs sweep after its points per thread (fp64: assoc_shape; fp32-screened: gl_assoc32.hip):
+//  * K splits: aim for ~4096 workgroups so the tail is short; a single 2 000-point frame still gets 8 x 64 workgroups
+//    (profiles/history/r1_assoc_tuning.txt);
+//  * whole chunks of kChunk Gaussians and >= 64 Gaussians per split.
 // `listed`: the sweep of a point LIST whose length only the device knows (the points the cell index left unresolved,
 // typically 5 - 15 % of N).  The grid must cover N, but the shape is chosen for N / 16 points so that the few point
 // tiles that have work still make ~1 000 workgroups (config 5: 2 500 of 50 000 points x 65 536 Gaussians were 252
 // workgroups of 1 024 points, one per CU: 0.40 ms for a tenth of a millisecond of arithmetic).
-static void assoc_shape(int K, int N, bool listed, int* ppt_o, int* ptiles_o, int* nsplit_o, int* kchunk_o) {
-  const int kChunk = assoc_minchunk();
-  const int Ne = listed ? std::max(N / 16, 256) : N;
-  int ppt = 1;
-  if (Ne >= 8192) ppt = 2;
-  if (Ne >= 16384) ppt = 4;
-  if (assoc_tune().ppt > 0) ppt = assoc_tune().ppt;  // tuning knob (1, 2 or 4)
-  const int ptiles = (N + 256 * ppt - 1) / (256 * ppt);
+void sweep_split(int K, int N, bool listed, int ppt, int* ptiles_o, int* nsplit_o, int* kchunk_o) {
+  const int Ne = sweep_points(N, listed);
   const int etiles = (Ne + 256 * ppt - 1) / (256 * ppt);  // tiles expected to have work
   const int target_blocks = (Ne >= 8192) ? 4096 : (listed ? 1024 : 512);
   int nsplit = (target_blocks + etiles - 1) / etiles;
   const int max_split = (K + 63) / 64;  // >= 64 Gaussians per split
   if (nsplit > max_split) nsplit = max_split;
   if (nsplit < 1) nsplit = 1;
-  if (assoc_tune().nsplit > 0) nsplit = assoc_tune().nsplit;  // tuning knob
   int kchunk = (K + nsplit - 1) / nsplit;
-  kchunk = (kchunk + kChunk - 1) / kChunk * kChunk;  // whole min-chunks per split
-  nsplit = (K + kchunk - 1) / kchunk;
-  *ppt_o = ppt;
-  *ptiles_o = ptiles;
-  *nsplit_o = nsplit;
+  kchunk = (kchunk + kChunk - 1) / kChunk * kChunk;  // whole chunks per split
+  *ptiles_o = (N + 256 * ppt - 1) / (256 * ppt);
+  *nsplit_o = (K + kchunk - 1) / kchunk;
   *kchunk_o = kchunk;
+}
+
+// more points per thread once there are enough points to fill the chip (profiles/history/r1_assoc_tuning.txt)
+static void assoc_shape(int K, int N, bool listed, int* ppt_o, int* ptiles_o, int* nsplit_o, int* kchunk_o) {
+  const int Ne = sweep_points(N, listed);
+  const int ppt = Ne >= 16384 ? 4 : Ne >= 8192 ? 2 : 1;
+  *ppt_o = ppt;
+  sweep_split(K, N, listed, ppt, ptiles_o, nsplit_o, kchunk_o);
 }
 
 size_t assoc_scratch_bytes(int K, int N, bool listed) {
@@ -368,20 +343,11 @@ int launch_assoc_sweep64(Ctx* c, const Gmm* g, const double* pts, int N, int32_t
   {
     TimerScope ts(c, GL_TIMER_ASSOC);
     const dim3 grid(ptiles, nsplit);
-    const int ch = assoc_minchunk();
-#define GL_ASSOC_LAUNCH(P, C) \
-  k_assoc_brute<P, C><<<grid, 256, 0, c->stream>>>(g->rec12, K, kchunk, pts, N, part_d2, part_idx, list, count_dev)
-    if (ch == 16) {
-      if (ppt == 1) GL_ASSOC_LAUNCH(1, 16);
-      else if (ppt == 2) GL_ASSOC_LAUNCH(2, 16);
-      else if (ppt == 8) GL_ASSOC_LAUNCH(8, 16);
-      else GL_ASSOC_LAUNCH(4, 16);
-    } else {
-      if (ppt == 1) GL_ASSOC_LAUNCH(1, 8);
-      else if (ppt == 2) GL_ASSOC_LAUNCH(2, 8);
-      else if (ppt == 8) GL_ASSOC_LAUNCH(8, 8);
-      else GL_ASSOC_LAUNCH(4, 8);
-    }
+#define GL_ASSOC_LAUNCH(P) \
+  k_assoc_brute<P><<<grid, 256, 0, c->stream>>>(g->rec12, K, kchunk, pts, N, part_d2, part_idx, list, count_dev)
+    if (ppt == 1) GL_ASSOC_LAUNCH(1);
+    else if (ppt == 2) GL_ASSOC_LAUNCH(2);
+    else GL_ASSOC_LAUNCH(4);
 #undef GL_ASSOC_LAUNCH
   }
   GL_HIP(hipGetLastError());

@@ -330,25 +330,11 @@ __global__ void k_screen_count_all(int N, const int32_t* __restrict__ count_dev,
   atomicAdd(counters + GL_COUNTER_ASSOC_SCREEN_FALLBACK, count_dev ? *count_dev : N);
 }
 
-// Launch shape: two points per lane (four from 16 384 points), 256 lanes per workgroup; K splits as in the fp64 sweep (~4 096
-// workgroups for large N, a listed sweep shaped for N / 16 points), whole chunks of 8 and >= 64 Gaussians per split.
+// Launch shape: two points per lane (four from 16 384 points), 256 lanes per workgroup; K splits as in the fp64 sweep.
 void screen_shape(int K, int N, bool listed, int* ppt_o, int* ptiles_o, int* nsplit_o, int* kchunk_o) {
-  const int Ne = listed ? std::max(N / 16, 256) : N;
-  const int ppt = Ne >= 16384 ? 4 : 2;
-  const int ptiles = (N + 256 * ppt - 1) / (256 * ppt);
-  const int etiles = (Ne + 256 * ppt - 1) / (256 * ppt);
-  const int target_blocks = (Ne >= 8192) ? 4096 : (listed ? 1024 : 512);
-  int nsplit = (target_blocks + etiles - 1) / etiles;
-  const int max_split = (K + 63) / 64;
-  if (nsplit > max_split) nsplit = max_split;
-  if (nsplit < 1) nsplit = 1;
-  int kchunk = (K + nsplit - 1) / nsplit;
-  kchunk = (kchunk + 7) / 8 * 8;
-  nsplit = (K + kchunk - 1) / kchunk;
+  const int ppt = gl::sweep_points(N, listed) >= 16384 ? 4 : 2;
   *ppt_o = ppt;
-  *ptiles_o = ptiles;
-  *nsplit_o = nsplit;
-  *kchunk_o = kchunk;
+  gl::sweep_split(K, N, listed, ppt, ptiles_o, nsplit_o, kchunk_o);
 }
 
 }  // namespace

@@ -23,6 +23,16 @@ GL_DEV double chi2_rec(const double* __restrict__ rec, double x, double y, doubl
   const double r2 = fma(d2, rec[3 + 8], fma(d1, rec[3 + 5], d0 * rec[3 + 2]));
   return fma(r2, d2, fma(r1, d1, r0 * d0));
 }
+// The same chi2 for a wave-uniform record: through the constant address space the record comes in by scalar loads
+// (s_load_dwordx8/x16 through the scalar cache) and its values are SGPR operands of the VALU instructions.
+typedef const double __attribute__((address_space(4))) cdouble;
+GL_DEV double chi2_srec(cdouble* rec, double x, double y, double z) {
+  const double d0 = x - rec[0], d1 = y - rec[1], d2 = z - rec[2];
+  const double r0 = fma(d2, rec[9], fma(d1, rec[6], d0 * rec[3]));
+  const double r1 = fma(d2, rec[10], fma(d1, rec[7], d0 * rec[4]));
+  const double r2 = fma(d2, rec[11], fma(d1, rec[8], d0 * rec[5]));
+  return fma(r2, d2, fma(r1, d1, r0 * d0));
+}
 // 2-D MDist2 (gaussian.h:123-126)
 GL_DEV double mdist2_2d(const double* mean, const double* A, double u, double v) {
   const double d0 = u - mean[0], d1 = v - mean[1];

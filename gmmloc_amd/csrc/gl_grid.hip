@@ -36,8 +36,6 @@ using namespace gld;
 
 namespace {
 
-typedef const double __attribute__((address_space(4))) cdouble;
-
 struct GridDev {
   double lo[3];
   double inv_h;
@@ -69,6 +67,34 @@ GL_DEV void upd_min(double d, int k, double& best, int& bi) {
   bi = take ? k : bi;
 }
 
+// the (chi2, index) minimum over the short global list (components without a usable bound) that every point evaluates;
+// wave-uniform: records through scalar loads
+struct ArgMin {
+  double d;
+  int k;
+};
+GL_DEV ArgMin glob_min(const double* rec12, const GridDev& G, double x, double y, double z) {
+  ArgMin m = {__builtin_inf(), 0x7fffffff};
+  for (int j = 0; j < G.nglob; ++j) {
+    const int k = G.glob[j];
+    upd_min(chi2_srec((cdouble*)rec12 + (size_t)k * 12, x, y, z), k, m.d, m.k);
+  }
+  return m;
+}
+
+// a point whose minimum is above the gate is reported as no association and, with rest_list, listed for the all-pairs sweep
+GL_DEV void store_min(const GridDev& G, int n, double best, int bi, int32_t* out_idx, double* out_d2, int32_t* rest_list,
+                      int32_t* rest_count) {
+  if (best <= G.t_resolve) {
+    out_idx[n] = bi;
+    if (out_d2) out_d2[n] = best;
+  } else {
+    out_idx[n] = -1;
+    if (out_d2) out_d2[n] = __builtin_inf();
+    if (rest_list) rest_list[atomicAdd(rest_count, 1)] = n;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_assoc_cells(const double* __restrict__ rec12, GridDev G,
                                                      const double* __restrict__ pts, int N,
                                                      int32_t* __restrict__ out_idx, double* __restrict__ out_d2,
@@ -76,18 +102,9 @@ __global__ __launch_bounds__(256) void k_assoc_cells(const double* __restrict__ 
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   const double x = pts[(size_t)n * 3], y = pts[(size_t)n * 3 + 1], z = pts[(size_t)n * 3 + 2];
-  double best = __builtin_inf();
-  int bi = 0x7fffffff;
-  cdouble* rc = (cdouble*)rec12;
-  for (int j = 0; j < G.nglob; ++j) {  // wave-uniform: records through scalar loads
-    const int k = G.glob[j];
-    cdouble* r = rc + (size_t)k * 12;
-    const double d0 = x - r[0], d1 = y - r[1], d2 = z - r[2];
-    const double r0 = fma(d2, r[9], fma(d1, r[6], d0 * r[3]));
-    const double r1 = fma(d2, r[10], fma(d1, r[7], d0 * r[4]));
-    const double r2 = fma(d2, r[11], fma(d1, r[8], d0 * r[5]));
-    upd_min(fma(r2, d2, fma(r1, d1, r0 * d0)), k, best, bi);
-  }
+  const ArgMin g0 = glob_min(rec12, G, x, y, z);
+  double best = g0.d;
+  int bi = g0.k;
   const double fx = (x - G.lo[0]) * G.inv_h, fy = (y - G.lo[1]) * G.inv_h, fz = (z - G.lo[2]) * G.inv_h;
   const bool inside = fx >= 0.0 && fx < (double)G.dim[0] && fy >= 0.0 && fy < (double)G.dim[1] && fz >= 0.0 &&
                       fz < (double)G.dim[2];  // false for NaN
@@ -113,75 +130,45 @@ __global__ __launch_bounds__(256) void k_assoc_cells(const double* __restrict__ 
       }
     }
   }
-  if (best <= G.t_resolve) {
-    out_idx[n] = bi;
-    if (out_d2) out_d2[n] = best;
-  } else {
-    out_idx[n] = -1;
-    if (out_d2) out_d2[n] = __builtin_inf();
-    if (rest_list) rest_list[atomicAdd(rest_count, 1)] = n;
-  }
+  store_min(G, n, best, bi, out_idx, out_d2, rest_list, rest_count);
 }
 
 // The same association with a WAVE-COOPERATIVE record gather.  In k_assoc_cells every lane fetches its own candidates' 96-byte
 // records: 6 loads of 16 bytes per candidate with 64 different lines per instruction.  Here the wave lists its candidates
 // (<= 3 per lane from the packed cell, compacted with a prefix sum over the lanes), six lanes fetch one record as six
-// neighbouring 16-byte pieces and the records reach their points through LDS, 60 records per round; lanes whose cell holds
-// more than three candidates walked their list alone until round 5 (LONG = false; see below).  Same arithmetic per pair, same (chi2, index) minimum.
+// neighbouring 16-byte pieces and the records reach their points through LDS, 60 records per round.  Same arithmetic per pair,
+// same (chi2, index) minimum.
 // Measured on the bench points: 0.421 -> 0.392 ms per 8.19 M points - the address cycles of the gather drop to a third, the
 // ~50 M line requests per launch to the XCDs' L2 (two lines per record, the 393 KB of records do not live in a 32 KB L1) do not.
-// STRIDE = 16 (round 5): the gather reads the copy of the records that holds one record per 128-byte line (CellIndex::rec16) - one
-// line request per record instead of 1.75 on average; the long lists and the global list stay on rec12 (the same values).
-#ifndef GL_CG_REC
-#define GL_CG_REC 60
-#endif
-#ifndef GL_CG_PIPE
-#define GL_CG_PIPE 1
-#endif
-#ifndef GL_CG_IDXB
-#define GL_CG_IDXB 1
-#endif
-#ifndef GL_CG_BAL
-#define GL_CG_BAL 1
-#endif
-#ifndef GL_CG_IDS
-#define GL_CG_IDS 304
-#endif
-constexpr int CG_REC = GL_CG_REC;  // records per round: 10 per load instruction (6 lanes each, 4 lanes idle), 6 instructions
+// The gather reads rec16, the copy of the records that holds one record per 128-byte line (CellIndex::rec16, round 5): one line
+// request per record instead of 1.75 on average; the long lists of the lone lanes and the global list stay on rec12 (the same values).
+// Each step of round 5 - rec16, long lists through the gather, the balanced evaluation, requests a round ahead - and the values of
+// CG_REC and CG_IDS were measured against the alternatives, every variant bit-equal: profiles/history/r5_assoc_gather.txt.
+constexpr int CG_REC = 60;         // records per round: 10 per load instruction (6 lanes each, 4 lanes idle), 6 instructions
 constexpr int CG_LONE_LANES = 32;  // a wave gathers its long lists cooperatively while at most half of its lanes have one
 constexpr int CG_TAG = 26, CG_KMASK = (1 << CG_TAG) - 1;  // (component indices below 2^26: launch_assoc_index)
-constexpr int CG_IDS = GL_CG_IDS;  // candidates of a wave per chunk of its table (the bench points: 201 per wave on average; 192 - a second chunk for most waves - costs 15 %)
-template <int STRIDE, bool LONG, bool BAL>
-__global__ __launch_bounds__(256) void k_assoc_cells_coop(const double* __restrict__ rec12, const double* __restrict__ recg, GridDev G,
+constexpr int CG_IDS = 304;  // candidates of a wave per chunk of its table (the bench points: 201 per wave on average; 192 - a second chunk for most waves - costs 15 %)
+__global__ __launch_bounds__(256) void k_assoc_cells_coop(const double* __restrict__ rec12, const double* __restrict__ rec16, GridDev G,
                                                           const double* __restrict__ pts, int N,
                                                           int32_t* __restrict__ out_idx, double* __restrict__ out_d2,
                                                           int32_t* __restrict__ rest_list, int32_t* __restrict__ rest_count) {
   __shared__ __attribute__((aligned(16))) double s_rec[4][CG_REC * 12];
   __shared__ int s_id[4][CG_IDS];
-  __shared__ double s_d[BAL ? 4 : 1][BAL ? CG_IDS : 1];  // BAL: chi2 of the wave's candidates, by position in its table
+  __shared__ double s_d[4][CG_IDS];  // chi2 of the wave's candidates, by position in its table
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = blockIdx.x * 256 + threadIdx.x;
   const bool live = n < N;
   const int nc = live ? n : N - 1;
   const double x = pts[(size_t)nc * 3], y = pts[(size_t)nc * 3 + 1], z = pts[(size_t)nc * 3 + 2];
-  double best = __builtin_inf();
-  int bi = 0x7fffffff;
-  cdouble* rc = (cdouble*)rec12;
-  for (int j = 0; j < G.nglob; ++j) {  // wave-uniform: records through scalar loads
-    const int k = G.glob[j];
-    cdouble* r = rc + (size_t)k * 12;
-    const double d0 = x - r[0], d1 = y - r[1], d2 = z - r[2];
-    const double r0 = fma(d2, r[9], fma(d1, r[6], d0 * r[3]));
-    const double r1 = fma(d2, r[10], fma(d1, r[7], d0 * r[4]));
-    const double r2 = fma(d2, r[11], fma(d1, r[8], d0 * r[5]));
-    upd_min(fma(r2, d2, fma(r1, d1, r0 * d0)), k, best, bi);
-  }
+  const ArgMin g0 = glob_min(rec12, G, x, y, z);
+  double best = g0.d;
+  int bi = g0.k;
   const double fx = (x - G.lo[0]) * G.inv_h, fy = (y - G.lo[1]) * G.inv_h, fz = (z - G.lo[2]) * G.inv_h;
   const bool inside = live && fx >= 0.0 && fx < (double)G.dim[0] && fy >= 0.0 && fy < (double)G.dim[1] && fz >= 0.0 &&
                       fz < (double)G.dim[2];  // false for NaN
   int4 q = make_int4(0, 0, 0, 0);
   if (inside) q = cell_load(G, ((int)fz * G.dim[1] + (int)fy) * G.dim[0] + (int)fx);
-  // EVERY list goes through the cooperative gather (round 5, LONG = true): a cell with more than three candidates keeps its list in the
+  // EVERY list goes through the cooperative gather (round 5): a cell with more than three candidates keeps its list in the
   // CSR array, and until round 5 such a lane walked it alone behind the gather - one dependent index load and six 16-byte record loads
   // per candidate while the rest of the wave waited (a third of the bench points; the time of the kernel followed THEM:
   // profiles/r5_assoc_cell_sweep.txt, the 3 cm row).  Now the lane copies its list's indices into the wave's candidate table like
@@ -189,7 +176,7 @@ __global__ __launch_bounds__(256) void k_assoc_cells_coop(const double* __restri
   // ... unless the wave's lists are long throughout (the stress map: 74 candidates per point): then every lane is busy walking its own
   // list and the gather's rounds of 60 are the slower way (measured 1.05 against 0.38 ms per 50 000 points).  Decided per wave by
   // the number of lanes with a long list.
-  const bool lone = !LONG || __popcll(__ballot(q.x > 3)) > CG_LONE_LANES;
+  const bool lone = __popcll(__ballot(q.x > 3)) > CG_LONE_LANES;
   const int cnt = lone ? (q.x <= 3 ? q.x : 0) : q.x;
   // exclusive prefix sum of the counts over the wave
   int pos = cnt;
@@ -201,7 +188,7 @@ __global__ __launch_bounds__(256) void k_assoc_cells_coop(const double* __restri
   const int total = __shfl(pos, 63);
   pos -= cnt;
   const int sub = lane / 6, part = lane - 6 * sub;  // lanes 60 .. 63 idle in the gather
-  const int otag = BAL ? lane << CG_TAG : 0;        // BAL: a candidate carries its point's lane in the bits above the component index
+  const int otag = lane << CG_TAG;                  // a candidate carries its point's lane in the bits above the component index
   for (int c0 = 0; c0 < total; c0 += CG_IDS) {
     const int jlo = max(0, c0 - pos), jhi = min(cnt, c0 + CG_IDS - pos);  // this lane's candidates of the chunk
     if (q.x <= 3) {
@@ -209,18 +196,7 @@ __global__ __launch_bounds__(256) void k_assoc_cells_coop(const double* __restri
       if (1 >= jlo && 1 < jhi) s_id[wave][pos + 1 - c0] = q.z | otag;
       if (2 >= jlo && 2 < jhi) s_id[wave][pos + 2 - c0] = q.w | otag;
     } else if (!lone) {
-#if GL_CG_IDXB > 1
-      for (int j0 = jlo; j0 < jhi; j0 += GL_CG_IDXB) {  // GL_CG_IDXB index loads in flight together (one after the other they were a list's length of round trips)
-        int v[GL_CG_IDXB];
-#pragma unroll
-        for (int u = 0; u < GL_CG_IDXB; ++u) v[u] = j0 + u < jhi ? G.idx[q.y + j0 + u] : 0;
-#pragma unroll
-        for (int u = 0; u < GL_CG_IDXB; ++u)
-          if (j0 + u < jhi) s_id[wave][pos + j0 + u - c0] = v[u] | otag;
-      }
-#else
       for (int j = jlo; j < jhi; ++j) s_id[wave][pos + j - c0] = G.idx[q.y + j] | otag;
-#endif
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -235,13 +211,12 @@ __global__ __launch_bounds__(256) void k_assoc_cells_coop(const double* __restri
         const int rr = t * 10 + sub;
         const bool ld = lane < 60 && rr < nr;
         const int id = s_id[wave][ld ? r0 + rr : 0] & CG_KMASK;
-        piece[t] = ld ? *(const double2*)(recg + (size_t)id * STRIDE + part * 2) : make_double2(0.0, 0.0);
+        piece[t] = ld ? *(const double2*)(rec16 + (size_t)id * 16 + part * 2) : make_double2(0.0, 0.0);
       }
     };
-    if (GL_CG_PIPE) request(0);
+    request(0);
     for (int r0 = 0; r0 < nch; r0 += CG_REC) {
       const int nr = min(CG_REC, nch - r0);
-      if (!GL_CG_PIPE) request(r0);
 #pragma unroll
       for (int t = 0; t < CG_REC / 10; ++t) {
         const int rr = t * 10 + sub;
@@ -249,51 +224,34 @@ __global__ __launch_bounds__(256) void k_assoc_cells_coop(const double* __restri
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      if (GL_CG_PIPE && r0 + CG_REC < nch) request(r0 + CG_REC);
-      if (BAL) {
-        // BALANCED evaluation (round 5): candidate r0 + l of the table is evaluated by LANE l against its point, whose coordinates come
-        // from the owner's registers (ds_bpermute) - one evaluation per lane and round.  Evaluated by their owners, a round cost as many
-        // passes through the ~40 instructions of a pair as its longest list is long, with most lanes masked out: 1 012 vector
-        // instructions per wave for 201 pairs, the SIMDs' vector ALUs 73 % busy (profiles/r5n_traffic.json).
-        const bool ev = lane < nr;
-        const int w = s_id[wave][ev ? r0 + lane : 0];
-        const int own = (int)((unsigned)w >> CG_TAG);
-        const double ox = __shfl(x, own), oy = __shfl(y, own), oz = __shfl(z, own);
-        double rec[12];
+      if (r0 + CG_REC < nch) request(r0 + CG_REC);
+      // BALANCED evaluation (round 5): candidate r0 + l of the table is evaluated by LANE l against its point, whose coordinates come
+      // from the owner's registers (ds_bpermute) - one evaluation per lane and round.  Evaluated by their owners, a round cost as many
+      // passes through the ~40 instructions of a pair as its longest list is long, with most lanes masked out: 1 012 vector
+      // instructions per wave for 201 pairs, the SIMDs' vector ALUs 73 % busy (profiles/r5n_traffic.json).
+      const bool ev = lane < nr;
+      const int w = s_id[wave][ev ? r0 + lane : 0];
+      const int own = (int)((unsigned)w >> CG_TAG);
+      const double ox = __shfl(x, own), oy = __shfl(y, own), oz = __shfl(z, own);
+      double rec[12];
 #pragma unroll
-        for (int e = 0; e < 6; ++e) {
-          const double2 v = *(const double2*)(&s_rec[wave][(ev ? lane : 0) * 12 + e * 2]);
-          rec[2 * e] = v.x;
-          rec[2 * e + 1] = v.y;
-        }
-        const double d = chi2_rec(rec, ox, oy, oz);
-        if (ev) s_d[wave][r0 + lane] = d;
-      } else {
-        const int ja = max(jlo, c0 + r0 - pos), jb = min(jhi, c0 + r0 + nr - pos);
-        for (int j = ja; j < jb; ++j) {
-          const int r = pos + j - c0 - r0;
-          const int k = s_id[wave][r0 + r];
-          double rec[12];
-#pragma unroll
-          for (int e = 0; e < 6; ++e) {
-            const double2 v = *(const double2*)(&s_rec[wave][r * 12 + e * 2]);
-            rec[2 * e] = v.x;
-            rec[2 * e + 1] = v.y;
-          }
-          upd_min(chi2_rec(rec, x, y, z), k, best, bi);
-        }
+      for (int e = 0; e < 6; ++e) {
+        const double2 v = *(const double2*)(&s_rec[wave][(ev ? lane : 0) * 12 + e * 2]);
+        rec[2 * e] = v.x;
+        rec[2 * e + 1] = v.y;
       }
+      const double d = chi2_rec(rec, ox, oy, oz);
+      if (ev) s_d[wave][r0 + lane] = d;
       __builtin_amdgcn_wave_barrier();
     }
-    if (BAL) {  // the owner takes the lexicographic minimum over its candidates' (chi2, index): a read and a compare per candidate
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      for (int j = jlo; j < jhi; ++j) {
-        const int i = pos + j - c0;
-        upd_min(s_d[wave][i], s_id[wave][i] & CG_KMASK, best, bi);
-      }
-      __builtin_amdgcn_wave_barrier();
+    // the owner takes the lexicographic minimum over its candidates' (chi2, index): a read and a compare per candidate
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int j = jlo; j < jhi; ++j) {
+      const int i = pos + j - c0;
+      upd_min(s_d[wave][i], s_id[wave][i] & CG_KMASK, best, bi);
     }
+    __builtin_amdgcn_wave_barrier();
   }
   if (lone && inside && q.x > 3) {  // long list: by the lane itself
     for (int e = q.y; e < q.y + q.x; ++e) {
@@ -302,14 +260,7 @@ __global__ __launch_bounds__(256) void k_assoc_cells_coop(const double* __restri
     }
   }
   if (!live) return;
-  if (best <= G.t_resolve) {
-    out_idx[n] = bi;
-    if (out_d2) out_d2[n] = best;
-  } else {
-    out_idx[n] = -1;
-    if (out_d2) out_d2[n] = __builtin_inf();
-    if (rest_list) rest_list[atomicAdd(rest_count, 1)] = n;
-  }
+  store_min(G, n, best, bi, out_idx, out_d2, rest_list, rest_count);
 }
 
 __global__ __launch_bounds__(256) void k_index_work(GridDev G, const double* __restrict__ pts, int N,
@@ -784,23 +735,12 @@ int launch_assoc_index(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* 
   int32_t* list = count + 16;
   TimerScope ts(c, GL_TIMER_ASSOC);
   if (resolve_all) GL_HIP(hipMemsetAsync(count, 0, 4, c->stream));
-  if ((G.cell4 || G.cell8) && c->opt.assoc_coop != 0 && N >= 4096) {
-    const bool pad = g->grid.rec16 && c->opt.assoc_rec_pad != 0;
-    const double* recg = pad ? g->grid.rec16 : g->rec12;
-    int32_t* rl = resolve_all ? list : nullptr;
-    const dim3 gr((N + 255) / 256);
-    if (c->opt.assoc_coop_long != 0 && GL_CG_BAL && g->K < (1 << 26) && c->opt.assoc_coop_bal != 0) {
-      if (pad) k_assoc_cells_coop<16, true, true><<<gr, 256, 0, c->stream>>>(g->rec12, recg, G, pts, N, idx, d2, rl, count);
-      else k_assoc_cells_coop<12, true, true><<<gr, 256, 0, c->stream>>>(g->rec12, recg, G, pts, N, idx, d2, rl, count);
-    } else if (c->opt.assoc_coop_long != 0) {
-      if (pad) k_assoc_cells_coop<16, true, false><<<gr, 256, 0, c->stream>>>(g->rec12, recg, G, pts, N, idx, d2, rl, count);
-      else k_assoc_cells_coop<12, true, false><<<gr, 256, 0, c->stream>>>(g->rec12, recg, G, pts, N, idx, d2, rl, count);
-    } else {
-      if (pad) k_assoc_cells_coop<16, false, false><<<gr, 256, 0, c->stream>>>(g->rec12, recg, G, pts, N, idx, d2, rl, count);
-      else k_assoc_cells_coop<12, false, false><<<gr, 256, 0, c->stream>>>(g->rec12, recg, G, pts, N, idx, d2, rl, count);
-    }
-  } else
-    k_assoc_cells<<<(N + 255) / 256, 256, 0, c->stream>>>(g->rec12, G, pts, N, idx, d2, resolve_all ? list : nullptr, count);
+  int32_t* rl = resolve_all ? list : nullptr;
+  const dim3 gr((N + 255) / 256);
+  if ((G.cell4 || G.cell8) && g->grid.rec16 && g->K < (1 << 26) && N >= 4096 && c->opt.assoc_coop != 0)
+    k_assoc_cells_coop<<<gr, 256, 0, c->stream>>>(g->rec12, g->grid.rec16, G, pts, N, idx, d2, rl, count);
+  else
+    k_assoc_cells<<<gr, 256, 0, c->stream>>>(g->rec12, G, pts, N, idx, d2, rl, count);
   GL_HIP(hipGetLastError());
   if (resolve_all)  // the unresolved points go through the all-pairs sweep (grid sized for N, empty tiles exit)
     return launch_assoc_sweep(c, g, pts, N, idx, d2, list, count, (char*)scratch + index_list_bytes(N));

@@ -120,9 +120,6 @@ struct Options {
   double view_threads = 0;      //   0 auto, 256 / 1024
   double assoc_index_min = -1;  // pairs below which GL_ASSOC_BRUTE stays on the sweep (-1 = built-in)
   double assoc_grid = -1;       // 0: never use the cell index (every association is the N x K sweep); A/B and bench
-  double assoc_coop_bal = 1;    // 1: the cooperative gather's pairs are evaluated one per lane and round (needs assoc_coop_long), 0: by the lane that owns the point (A/B; same results)
-  double assoc_coop_long = 1;   // 1: lists of more than three candidates go through the cooperative gather too, 0: the lane walks them alone (A/B; same results)
-  double assoc_rec_pad = 1;     // 1: k_assoc_cells_coop gathers from the one-line-per-record copy (CellIndex::rec16), 0: from rec12 (A/B; same results)
   double assoc_coop = 1;        // 1: wave-cooperative record gather in the indexed association (k_assoc_cells_coop), 0: a lane per record
   double pipe_fuse_asm = -1;    // pipelined local BA: the solve kernel assembles the system itself (-1: calls of a few windows, 0 never, 1 always; same bits)
   double pose_compact_cap = 1024;  // the largest stride of a compacted pose problem (tests: 512 / 256 drive frames into the full-stride problem)
@@ -258,6 +255,10 @@ int launch_assoc_brute(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* 
 int launch_assoc_sweep(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,
                        const int32_t* count_dev, void* scratch);
 size_t assoc_scratch_bytes(int K, int N, bool listed = false);
+// launch shape of either all-pairs sweep (gl_assoc.hip): the points it is shaped for, and for a given number of points per
+// thread its point tiles, K splits and Gaussians per split
+inline int sweep_points(int N, bool listed) { return listed ? (N / 16 > 256 ? N / 16 : 256) : N; }
+void sweep_split(int K, int N, bool listed, int ppt, int* ptiles, int* nsplit, int* kchunk);
 // (gl_assoc32.hip) the fp32-screened sweep: same arguments and results as launch_assoc_sweep, own scratch (ctx_scratch_s)
 int build_screen_records(Ctx* c, Gmm* g);
 int launch_assoc_screened(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,

@@ -190,26 +190,19 @@ def test_cell_index_equals_exhaustive(gpu, oracle, map_v1, map_v2, opt, which, N
     oracle.gmm_destroy(h)
 
 
-def test_cell_index_record_copy_option_same_bits(gpu, opt):
-    """assoc_rec_pad: the cooperative gather from the one-record-per-128-byte-line copy (default) and from the 96-byte records
-    give the same indices and the same chi2 bits (and both equal the all-pairs sweep)."""
+def test_cell_index_gather_and_lane_walk_same_bits(gpu, opt):
+    """The cooperative gather (default: records from their one-per-128-byte-line copy, long lists through the gather, balanced
+    evaluation) and the lane-per-record kernel (assoc_coop = 0) each give the same indices and chi2 bits as the all-pairs sweep."""
     torch, ctx = gpu
     mean, cov = synth.synth_gmm(4096, 41)
     g = api.GMM(ctx, mean, cov)
     rng = np.random.default_rng(41)
     lo, hi = mean.min(0), mean.max(0)
     pts = np.concatenate([synth.synth_points(mean, cov, 60000, 41), rng.uniform(lo - 2, hi + 2, (8000, 3))])
-    out = {}
-    for pad, lng, bal in ((1, 1, 1), (0, 1, 1), (1, 1, 0), (0, 1, 0), (1, 0, 0), (0, 0, 0)):
-        opt("assoc_rec_pad", pad)
-        opt("assoc_coop_long", lng)   # lists of more than three candidates through the cooperative gather (default) / by their lane
-        opt("assoc_coop_bal", bal)    # a pair per lane and round (default) / the pairs of a point by the lane that owns it
-        out[pad, lng, bal] = _both(torch, g, pts)
-    (i1, d1), (ie, de) = out[1, 1, 1]
-    assert np.array_equal(i1, ie) and np.array_equal(d1, de)
-    for key in ((0, 1, 1), (1, 1, 0), (0, 1, 0), (1, 0, 0), (0, 0, 0)):
-        (i0, d0), _ = out[key]
-        assert np.array_equal(i1, i0) and np.array_equal(d1, d0), key
+    for coop in (1, 0):
+        opt("assoc_coop", coop)
+        (i1, d1), (ie, de) = _both(torch, g, pts)
+        assert np.array_equal(i1, ie) and np.array_equal(d1, de), coop
 
 
 def test_cell_index_8_byte_cells_same_bits(gpu, opt):
@@ -244,7 +237,7 @@ def test_cell_index_8_byte_cells_same_bits(gpu, opt):
 
 
 def test_cell_index_long_lists_in_chunks(gpu):
-    """Many overlapping components: cells with tens of candidates, more than one chunk of the wave's candidate table (384) per wave."""
+    """Many overlapping components: cells with tens of candidates, more than one chunk of the wave's candidate table (304) per wave."""
     torch, ctx = gpu
     rng = np.random.default_rng(77)
     K = 600

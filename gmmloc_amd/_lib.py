@@ -81,6 +81,7 @@ def load():
         "gl_fuse_search": (i32, [vp, vp, C.c_float, i32, i32, i32] + [vp] * 8 + [C.c_float, vp, vp]),
         "gl_project_map_points": (i32, [vp, vp, C.c_float, i32, i32] + [vp] * 12),
         "gl_level_steps": (i32, [C.c_float, vp]),
+        "gl_update_map_points": (i32, [vp, C.c_float, i32, i32, i32, i32, i32] + [vp] * 14),
         "gl_track_frame_chain": (i32, [vp, vp, vp, C.c_float, i32, i32, i32, i32, vp, C.c_float, C.c_float, C.c_float, i32]),
         "gl_track_frame_chain_front": (i32, [vp, vp, vp, C.c_float, i32, i32, i32, i32, vp, C.c_float, i32]),
         "gl_track_frame_chain_back": (i32, [vp, vp, vp, C.c_float, i32, i32, i32, i32, vp, C.c_float, C.c_float]),

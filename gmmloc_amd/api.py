@@ -732,6 +732,41 @@ def project_map_points(ctx, cam, pose_cw, t_wc, pos, normal, max_dist, min_dist,
     return uvr, level, viewcos, dist, inview
 
 
+MP_KF_DTYPES = {"twc": "float64", "valid": "uint8", "oct": "int32", "desc": "uint8"}
+MP_DTYPES = {"pos": "float64", "valid": "uint8", "ref_kf": "int32", "obs_ptr": "int32", "obs_kf": "int32", "obs_feat": "int32"}
+MP_OUT_DTYPES = {"desc": "uint8", "normal": "float64", "max_dist": "float32", "min_dist": "float32"}
+
+
+def update_map_points(ctx, kf, mp, out, what=3, scale_factor=1.2):
+    """MapPoint::computeDistinctiveDescriptors (mappoint.cpp:126-190, what & 1) and MapPoint::updateNormalAndDepth (:211-255, what & 2)
+    for NP map points, in place (rules: gmmloc_hip.h, gl_update_map_points).  Dicts of CUDA tensors - kf: twc (NKF,3) f64, valid
+    (NKF,) u8 (optional), oct (NKF,NFK) i32, desc (NKF,NFK,32) u8 (the feat_oct / feat_desc layout of fuse_search); mp: pos (NP,3)
+    f64, valid (NP,) u8 (optional), ref_kf (NP,) i32, observations_ as CSR obs_ptr (NP+1,) i32, obs_kf / obs_feat (NOBS,) i32; out:
+    desc (NP,32) u8, normal (NP,3) f64, max_dist / min_dist (NP,) f32 - the mp_* inputs of the matchers.  Keys `what` does not
+    need may be left out."""
+    for name, d, dtypes in (("kf", kf, MP_KF_DTYPES), ("mp", mp, MP_DTYPES), ("out", out, MP_OUT_DTYPES)):
+        for k, t in d.items():
+            if t is None:
+                continue
+            assert k in dtypes, "%s[%r]: unknown key" % (name, k)
+            assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch." + dtypes[k], \
+                "%s[%r]: expected a contiguous CUDA %s tensor, got %s" % (name, k, dtypes[k], t.dtype)
+    ref = kf.get("desc") if kf.get("desc") is not None else kf.get("oct")
+    NKF, NFK = (ref.shape[0], ref.shape[1]) if ref is not None else (kf["twc"].shape[0], 0)
+    NP = mp["obs_ptr"].shape[0] - 1
+    NOBS = mp["obs_kf"].shape[0] if mp.get("obs_kf") is not None else 0
+    g = lambda d, k: _ptr(d.get(k))
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_update_map_points(ctx.h, float(scale_factor), int(what), NP, NKF, NFK, NOBS, g(kf, "twc"), g(kf, "valid"),
+                                            g(kf, "oct"), g(kf, "desc"), g(mp, "pos"), g(mp, "valid"), g(mp, "ref_kf"), g(mp, "obs_ptr"),
+                                            g(mp, "obs_kf"), g(mp, "obs_feat"), g(out, "desc"), g(out, "normal"), g(out, "max_dist"),
+                                            g(out, "min_dist")))
+    finally:
+        ctx._exit()
+    return out
+
+
 def fuse_search(ctx, cam, feat_uv, feat_ur, feat_oct, feat_desc, mp_uvr, mp_level, mp_valid, mp_desc, th=3.0, scale_factor=1.2):
     """Localization::fuseObservations (localization.cpp:226-318), the matching half, for B key-frames: CUDA tensors feat_uv (B,NF,2)
     f64, feat_ur (B,NF) f32, feat_oct (B,NF) i32, feat_desc (B,NF,32) u8; mp_uvr (B,NP,3) f64, mp_level (B,NP) i32, mp_valid (B,NP)

@@ -623,3 +623,62 @@ def synth_chain_frame(NF, NL, NP, seed, cam, scale_factor=1.2, temporal_frac=0.0
                  kf_node_idx=kidx, kf_pt=last_pt[lk].copy(), kf_to_local=f["last_to_local"][lk].astype(np.int32), feat_node_id=fid, feat_node_ptr=fptr,
                  feat_node_idx=fidx)
     return f
+
+
+def map_point_counts(NP, rng):
+    """Observation counts of a mapping-side refresh: mostly 2 - 6, a tail to 30, 2 % without observations."""
+    u = rng.uniform(size=NP)
+    n = np.where(u < 0.6, rng.integers(2, 7, NP), np.where(u < 0.9, rng.integers(7, 16, NP), rng.integers(16, 31, NP)))
+    n[rng.uniform(size=NP) < 0.02] = 0
+    return n.astype(np.int64)
+
+
+def synth_map_points(NP, seed, NKF=257, NFK=400, counts=None, kf_invalid_frac=0.1, pt_invalid_frac=0.05, ref_missing_frac=0.1,
+                     at_centre=4, max_flips=4):
+    """Inputs of MapPoint::computeDistinctiveDescriptors / updateNormalAndDepth (mappoint.cpp:126-255) for NP map points, as the numpy
+    arrays of api.update_map_points.  Key-frames: camera centres in a room, octaves 0 .. 7, random descriptors, a share invalid.  Each
+    point is seen by `counts[p]` distinct key-frames (default map_point_counts; a count above NKF is clipped to NKF), and every
+    observed feature's descriptor is the point's own "true" descriptor with 0 .. max_flips bits flipped (realistic medians, many
+    ties; two points that draw the same feature share it, the later one's descriptor stays).  A share of the points is invalid, a
+    share has a ref key-frame that does not observe it, `at_centre` points lie exactly on the centre of a key-frame that observes
+    them.  A point's observations are listed in no particular order (a stride through the key-frame table)."""
+    rng = np.random.default_rng(seed)
+    n = map_point_counts(NP, rng) if counts is None else np.asarray(counts, np.int64)
+    n = np.minimum(n, NKF)
+    twc = rng.uniform(-5.0, 5.0, (NKF, 3))
+    kf_valid = (rng.uniform(size=NKF) >= kf_invalid_frac).astype(np.uint8)
+    kf_oct = rng.integers(0, 8, (NKF, NFK)).astype(np.int32)
+    kf_desc = rng.integers(0, 256, (NKF, NFK, 32), dtype=np.uint8)
+    obs_ptr = np.zeros(NP + 1, np.int64)
+    obs_ptr[1:] = np.cumsum(n)
+    NOBS = int(obs_ptr[-1])
+    pt = np.repeat(np.arange(NP), n)
+    j = np.arange(NOBS) - obs_ptr[pt]
+    # distinct key-frames per point: a stride through the table that is coprime with NKF
+    base = rng.integers(0, NKF, NP)
+    step = rng.integers(1, NKF, NP)
+    g = np.gcd(step, NKF)
+    step = np.where(g == 1, step, 1)
+    obs_kf = ((base[pt] + j * step[pt]) % NKF).astype(np.int32)
+    obs_feat = rng.integers(0, NFK, NOBS).astype(np.int32)
+    true = rng.integers(0, 256, (NP, 32), dtype=np.uint8)
+    od = true[pt].copy()
+    for _ in range(max_flips):
+        b = rng.integers(0, 256, NOBS)
+        on = rng.uniform(size=NOBS) < 0.5
+        od[np.arange(NOBS)[on], b[on] // 8] ^= (1 << (b[on] % 8)).astype(np.uint8)
+    kf_desc[obs_kf, obs_feat] = od
+    last = max(NOBS - 1, 0)
+    first = obs_kf[np.minimum(obs_ptr[:-1], last)] if NOBS else np.zeros(NP, np.int32)  # (meaningless where n == 0)
+    pick = obs_kf[np.minimum(obs_ptr[:-1] + rng.integers(0, np.maximum(n, 1)), last)] if NOBS else np.zeros(NP, np.int32)
+    ref_kf = np.where(n > 0, pick, rng.integers(0, NKF, NP)).astype(np.int32)
+    miss = rng.uniform(size=NP) < ref_missing_frac
+    ref_kf[miss] = rng.integers(0, NKF, int(miss.sum()))  # usually a key-frame that does not observe the point
+    d = rng.standard_normal((NP, 3))
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    pos = twc[first] + d * rng.uniform(0.3, 12.0, NP)[:, None]
+    cen = np.nonzero(n > 0)[0][:at_centre]
+    pos[cen] = twc[first[cen]]
+    pt_valid = (rng.uniform(size=NP) >= pt_invalid_frac).astype(np.uint8)
+    return dict(kf=dict(twc=twc, valid=kf_valid, oct=kf_oct, desc=kf_desc),
+                mp=dict(pos=pos, valid=pt_valid, ref_kf=ref_kf, obs_ptr=obs_ptr.astype(np.int32), obs_kf=obs_kf, obs_feat=obs_feat))

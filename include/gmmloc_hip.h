@@ -351,6 +351,34 @@ int gl_search_local_points(gl_ctx_t* ctx, const gl_camera* cam, float scale_fact
                            const double* mp_normal_dev, const float* mp_max_dist_dev, const float* mp_min_dist_dev,
                            const uint8_t* mp_cand_dev, const uint8_t* mp_desc_dev, float th, float nn_ratio, int32_t* feat_match_dev,
                            int32_t* nmatches_dev, uint8_t* inview_dev);
+/* MapPoint::computeDistinctiveDescriptors (mappoint.cpp:126-190) and MapPoint::updateNormalAndDepth (:211-255) for NP points: the
+ * refresh of the matchers' per-point inputs after a point's observations change.  what: 1 = descriptor, 2 = normal + depth, 3 = both;
+ * an output `what` does not select is not written.  The key-frame table has the layout of gl_fuse_search's feat_oct / feat_desc:
+ * kf_twc NKF x 3 (getTwc().translation()), kf_valid NKF uint8 (!not_valid_; NULL: all valid), kf_oct NKF x NFK (features_[i].octave),
+ * kf_desc NKF x NFK x 32 (features_[i].desc).  Points: pos NP x 3, pt_valid NP uint8 (!not_valid_; NULL: all valid), ref_kf NP (the
+ * row of ref_kf_ in the key-frame table), observations_ as CSR: obs_ptr NP + 1, obs_kf / obs_feat NOBS (key-frame row, feature index).
+ * In / out, in the layouts of mp_desc / mp_normal / mp_max_dist / mp_min_dist: desc NP x 32, normal NP x 3, max_dist / min_dist NP.
+ * Descriptor arrays 16-byte aligned.  Asynchronous on the context's stream; no allocation.  Needed: obs_ptr (NP > 0), obs_kf / obs_feat (NOBS > 0); what & 1: kf_desc,
+ * desc; what & 2: kf_twc, kf_oct, pos, ref_kf, normal, max_dist, min_dist and a finite scale_factor > 0.  The rules (bit for bit):
+ *   ORDER       a point's CSR row lists observations_ in the host's iteration order of the unordered_map (as INTEGRATION section 6
+ *               does for the local BA); that order is the reference's order and decides the ties.
+ *   DESCRIPTOR  only observations whose key-frame is valid count; N = their number.  D[i][j] = 256-bit Hamming distance over those N
+ *               descriptors; the median of row i is element (N-1)/2 of the sorted row, D[i][i] = 0 included; the winner is the first
+ *               row whose median is strictly the smallest - so N <= 2 takes the first valid observation.  N = 0, a point without
+ *               observations or an invalid point: desc untouched.  Exact for any N (rows of more than 32 take a slower path).
+ *   NORMAL      normal = (sum over ALL observations, key-frame validity not checked, in list order, of normalized(pos - Ow_i)) / n;
+ *               norm = sqrt(x*x + y*y + z*z) (oracle/og_math.hpp), normalized divides by it, a zero vector stays zero (Eigen 3.3+:
+ *               assumed).  dist = (float)|pos - Ow_ref|.  level = the octave of the ref key-frame's own observation of the point (its
+ *               first in the row); when the ref key-frame does not observe the point, feature 0's octave (observations[pRefKF] inserts
+ *               it on the local copy, :245).  max_dist = dist * sf[level], min_dist = max_dist / sf[7], in float; sf = the float
+ *               recurrence of init_config.hpp:67-76, 8 levels.  normal, max_dist and min_dist untouched when the point is invalid,
+ *               has no observations, its level is outside 0..7, or ref_kf is outside [0, NKF).
+ *   MALFORMED   a point whose [obs_ptr[p], obs_ptr[p+1]) is not a sub-range of [0, NOBS], or with an observation whose key-frame is
+ *               outside [0, NKF) or feature outside [0, NFK), is left entirely untouched. */
+int gl_update_map_points(gl_ctx_t* ctx, float scale_factor, int what, int NP, int NKF, int NFK, int NOBS, const double* kf_twc_dev,
+                         const uint8_t* kf_valid_dev, const int32_t* kf_oct_dev, const uint8_t* kf_desc_dev, const double* pos_dev,
+                         const uint8_t* pt_valid_dev, const int32_t* ref_kf_dev, const int32_t* obs_ptr_dev, const int32_t* obs_kf_dev,
+                         const int32_t* obs_feat_dev, uint8_t* desc_dev, double* normal_dev, float* max_dist_dev, float* min_dist_dev);
 
 /* One tracked frame, device resident (round 5; round 6: the fallback, temporal points, the two halves): what Tracking::track
  * (tracking.cpp:34-118) runs per frame - trackWithMotionModel (:333-376), trackKeyFrame when that fails (:297-331),

@@ -1,0 +1,174 @@
+"""gl_update_map_points (MapPoint::computeDistinctiveDescriptors, mappoint.cpp:126-190, and MapPoint::updateNormalAndDepth, :211-255)
+against the numpy restatement tests/map_point_ref.py, every output bit for bit, the untouched ones included: the outputs start as
+sentinels."""
+import numpy as np
+import pytest
+
+from gmmloc_amd import api, synth
+from tests import map_point_ref as M
+
+pytestmark = pytest.mark.gpu
+
+NKF_BIG = 2503  # prime: every stride through the table gives distinct key-frames, up to 2 503 observations per point
+
+
+def sentinel(NP):
+    return dict(desc=np.full((NP, 32), 0xA5, np.uint8), normal=np.full((NP, 3), -7.0), max_dist=np.full(NP, -1.0, np.float32),
+                min_dist=np.full(NP, -2.0, np.float32))
+
+
+def dev(torch, d):
+    return {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()}
+
+
+def run_both(torch, ctx, m, what=3, init=None, scale_factor=1.2):
+    NP = len(m["mp"]["obs_ptr"]) - 1
+    ref = {k: v.copy() for k, v in (init or sentinel(NP)).items()}
+    out = dev(torch, ref)
+    api.update_map_points(ctx, dev(torch, m["kf"]), dev(torch, m["mp"]), out, what=what, scale_factor=scale_factor)
+    torch.cuda.synchronize()
+    M.update_map_points_ref(m["kf"], m["mp"], ref, what=what, scale_factor=scale_factor)
+    return {k: v.cpu().numpy() for k, v in out.items()}, ref
+
+
+def assert_same(got, ref):
+    for k in ref:
+        assert got[k].tobytes() == ref[k].tobytes(), (k, int((got[k] != ref[k]).reshape(len(ref[k]), -1).any(1).sum()))
+
+
+def mixed_map(seed, extra=3000):
+    rng = np.random.default_rng(seed)
+    counts = np.concatenate([[0, 1, 2, 3, 63, 64, 65, 300, 2000], synth.map_point_counts(extra, rng), [33, 32, 31, 64, 129, 128]])
+    rng.shuffle(counts)
+    return synth.synth_map_points(len(counts), seed, NKF=NKF_BIG, NFK=64, counts=counts)
+
+
+def test_mixed_observation_counts_bit_exact(gpu):
+    torch, ctx = gpu
+    m = mixed_map(11)
+    n = np.diff(m["mp"]["obs_ptr"])
+    assert {0, 1, 2, 3, 63, 64, 65, 300, 2000} <= set(n.tolist())
+    got, ref = run_both(torch, ctx, m)
+    assert_same(got, ref)
+    touched = (ref["desc"] != 0xA5).any(1)
+    assert touched.sum() > 0.8 * len(n) and (ref["max_dist"] != -1.0).sum() > 0.7 * len(n)
+    big = np.nonzero(n >= 300)[0]
+    assert touched[big[m["mp"]["valid"][big] != 0]].all()
+
+
+def test_realistic_batch_200k(gpu):
+    torch, ctx = gpu
+    m = synth.synth_map_points(200000, 12, NKF=NKF_BIG, NFK=1000)
+    got, ref = run_both(torch, ctx, m)
+    assert_same(got, ref)
+    assert (ref["desc"] != 0xA5).any(1).sum() > 180000
+
+
+@pytest.mark.parametrize("what", [1, 2, 3])
+def test_what_selects_outputs(gpu, what):
+    torch, ctx = gpu
+    m = mixed_map(13, extra=2000)
+    got, ref = run_both(torch, ctx, m, what=what)
+    assert_same(got, ref)
+    NP = len(ref["desc"])
+    s = sentinel(NP)
+    assert ((ref["desc"] == s["desc"]).all()) == (not what & 1)
+    for k in ("normal", "max_dist", "min_dist"):
+        assert (ref[k] == s[k]).all() == (not what & 2), k
+
+
+def test_invalid_and_malformed_points_untouched(gpu):
+    torch, ctx = gpu
+    m = synth.synth_map_points(3000, 14, NKF=257, NFK=300)
+    mp, kf = m["mp"], m["kf"]
+    ptr = mp["obs_ptr"]
+    n = np.diff(ptr)
+    rows = np.nonzero(n >= 3)[0]
+    q = int(rows[len(rows) // 2])
+    rng = np.random.default_rng(14)
+    pick = rng.choice(np.setdiff1d(rows, [q, q + 1, len(n) - 1]), 60, replace=False)
+    mp["obs_kf"][ptr[pick[:10]] + 1] = -1                 # key-frame out of range
+    mp["obs_kf"][ptr[pick[10:20]] + 2] = 257
+    mp["obs_feat"][ptr[pick[20:30]]] = 300                # feature out of range
+    mp["obs_feat"][ptr[pick[30:35]] + 1] = -5
+    mp["ref_kf"][pick[35:45]] = 257                       # ref key-frame out of range: normal and depth untouched
+    mp["ref_kf"][pick[45:50]] = -1
+    kf["oct"][mp["obs_kf"][ptr[pick[50:55]]], mp["obs_feat"][ptr[pick[50:55]]]] = 8  # (a level outside 0 .. 7 where it is the ref's)
+    mp["ref_kf"][pick[50:55]] = mp["obs_kf"][ptr[pick[50:55]]]
+    ptr[q + 1] = ptr[q] - 1                               # a row that runs backwards (and the next one starts early)
+    ptr[-1] = ptr[-1] + 7                                 # the last row runs past NOBS
+    mp["valid"][pick[55:]] = 0
+    got, ref = run_both(torch, ctx, m)
+    assert_same(got, ref)
+    s = sentinel(len(n))
+    for p in list(pick[:35]) + list(pick[55:]) + [q, len(n) - 1]:
+        for k in s:
+            assert (ref[k][p] == s[k][p]).all(), (p, k)
+    for p in pick[35:55]:
+        assert ref["max_dist"][p] == -1.0
+
+
+def test_no_points_and_bad_arguments(gpu):
+    torch, ctx = gpu
+    m = synth.synth_map_points(50, 15)
+    kf, mp = dev(torch, m["kf"]), dev(torch, m["mp"])
+    empty = dict(mp, obs_ptr=mp["obs_ptr"][:1].clone())
+    out = dev(torch, sentinel(50))
+    api.update_map_points(ctx, kf, empty, out)  # NP = 0
+    torch.cuda.synchronize()
+    assert all((out[k].cpu().numpy() == v).all() for k, v in sentinel(50).items())
+    with pytest.raises(api.GLError, match="what"):
+        api.update_map_points(ctx, kf, mp, out, what=0)
+    with pytest.raises(api.GLError, match="null"):
+        api.update_map_points(ctx, kf, mp, dict(out, desc=None), what=1)
+    with pytest.raises(api.GLError, match="null"):
+        api.update_map_points(ctx, dict(kf, twc=None), mp, out, what=2)
+    api.update_map_points(ctx, dict(kf, twc=None, oct=None), mp, dict(out, normal=None), what=1)  # what = 1 needs neither
+    torch.cuda.synchronize()
+
+
+def test_same_bytes_twice(gpu):
+    torch, ctx = gpu
+    m = mixed_map(16, extra=5000)
+    kf, mp = dev(torch, m["kf"]), dev(torch, m["mp"])
+    outs = []
+    for _ in range(2):
+        out = dev(torch, sentinel(len(m["mp"]["obs_ptr"]) - 1))
+        api.update_map_points(ctx, kf, mp, out)
+        torch.cuda.synchronize()
+        outs.append({k: v.cpu().numpy().tobytes() for k, v in out.items()})
+    assert outs[0] == outs[1]
+
+
+def test_outputs_feed_projection(gpu):
+    """the refreshed normal / max_dist / min_dist go to gl_project_map_points as they are: the same in-view flags and predicted
+    levels (every output, bit for bit) as the restatement's outputs uploaded from the host"""
+    torch, ctx = gpu
+    m = synth.synth_map_points(20000, 17, NKF=257, NFK=300)
+    NP = 20000
+    init = dict(desc=np.zeros((NP, 32), np.uint8), normal=np.zeros((NP, 3)), max_dist=np.zeros(NP, np.float32),
+                min_dist=np.zeros(NP, np.float32))
+    got, ref = run_both(torch, ctx, m, init=init)
+    assert_same(got, ref)
+    cam = api.Camera()
+    twc = m["kf"]["twc"]
+    poses, tw = [], []
+    for b in range(4):  # cameras on four key-frame centres, looking at the map's centre
+        eye = twc[b * 7]
+        poses.append(synth.look_at_pose(eye, [0.0, 0.0, 0.0] if np.linalg.norm(eye) > 0.5 else [1.0, 0.0, 0.0]))
+        R = synth.quat_to_R(poses[-1][:4])
+        tw.append(-R.T @ poses[-1][4:])
+    B = len(poses)
+    pose_cw = torch.from_numpy(np.array(poses)).cuda()
+    t_wc = torch.from_numpy(np.array(tw)).cuda()
+    pos = torch.from_numpy(np.tile(m["mp"]["pos"][None], (B, 1, 1))).cuda()
+    cand = torch.ones((B, NP), dtype=torch.uint8).cuda()
+
+    def project(o):
+        t = lambda x: torch.from_numpy(np.ascontiguousarray(np.tile(x[None], (B,) + (1,) * x.ndim))).cuda()
+        return [x.cpu().numpy() for x in api.project_map_points(ctx, cam, pose_cw, t_wc, pos, t(o["normal"]), t(o["max_dist"]),
+                                                                   t(o["min_dist"]), cand)]
+    a, b = project(got), project(ref)
+    for x, y, name in zip(a, b, ("uvr", "level", "viewcos", "dist", "inview")):
+        assert x.tobytes() == y.tobytes(), name
+    assert a[4].sum() > 200 and len(np.unique(a[1][a[4] != 0])) >= 4

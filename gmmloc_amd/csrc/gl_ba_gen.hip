@@ -119,6 +119,93 @@ GL_DEV void genp_fresh(GenP& G, k_genp* s) {
 }
 #define GFRESH() genp_fresh(G, sG)
 
+// A problem's scratch area: the regions below in this order - doubles, then ints, then bytes, every region rounded up to 8 bytes -
+// and k_ba_gen's address table in the last GEN_TABLE_BYTES of the area.  Points G at the regions from `s` on and returns their end;
+// the host runs it on an offset (C = size_t) for the size of the area (gen_scratch_bytes).
+template <class C>
+__host__ __device__ __forceinline__ C genp_carve(GenP& G, C s, int P, int F, int L, int NOBS) {
+  const int n = 6 * P;
+  auto takeD = [&](size_t cnt) {
+    double* p = (double*)s;
+    s += cnt * 8;
+    return p;
+  };
+  G.Rt = takeD((size_t)(P + F) * 12);
+  G.RtN = takeD((size_t)P * 12);
+  G.qN = takeD((size_t)P * 7);
+  G.pinv = takeD((size_t)P * 7);
+  G.pn = takeD((size_t)L * 3);
+  G.lin = takeD((size_t)NOBS * 12);
+  G.ptw = takeD((size_t)L * 12);
+  G.chi_o = takeD((size_t)NOBS);
+  G.ld = n + 1;  // row stride of S, odd: the column reads of the solve spread over the LDS banks
+  G.S = takeD((size_t)n * G.ld);
+  G.part = takeD((size_t)2 * 64 * 4);
+  G.gv = takeD(n);
+  G.bp = takeD(n);
+  G.dxv = takeD(n);
+  G.pchi = takeD(P);
+  G.pchi2 = takeD(P);
+  G.prH = takeD((size_t)P * 36);
+  G.prb = takeD((size_t)P * 6);
+  G.pth = takeD((size_t)L * 6);  // (the persistent kernel's; the pipelined shape keeps its own in PipeA)
+  auto takeI = [&](size_t cnt) {
+    int32_t* p = (int32_t*)s;
+    s += ((cnt * 4 + 7) / 8) * 8;
+    return p;
+  };
+  G.opoint = takeI(NOBS);
+  G.pl_ptr = takeI(P + 1);
+  G.pl_obs = takeI(NOBS);
+  G.pl_pos = takeI(NOBS);
+  G.pl_pt = takeI(NOBS);
+  G.plm = takeI((size_t)NOBS * P);
+  auto takeB = [&](size_t cnt) {
+    uint8_t* p = (uint8_t*)s;
+    s += ((cnt + 7) / 8) * 8;
+    return p;
+  };
+  G.lev_o = takeB(NOBS);
+  G.lev_g = takeB(L);
+  G.pfree = takeB(P + F);
+  G.pact = takeB(P);
+  G.lact = takeB(L);
+  return s;
+}
+// bytes of a problem's area: its regions and the address table, 256-aligned
+size_t gen_scratch_bytes(int P, int F, int L, int NOBS) {
+  GenP G;
+  const size_t end = genp_carve(G, (size_t)0, P, F, L, NOBS);
+  return ((end + GEN_TABLE_BYTES + 255) / 256) * 256;
+}
+
+// Points G at problem f's slices of the batch arrays, its header and its area, for both shapes of the local BA (what differs between
+// them - the workgroups of a problem, S in LDS, the state of the reductions - the caller sets):
+// scratch = | B x 512 B headers {64 barrier words, solve flag, stop word} (zeroed by the host) | B areas of `per` bytes |
+GL_DEV void genp_problem(GenP& G, int f, int B, int P, int F, int L, int NOBS, double* poses, const uint8_t* prior, double* pts,
+                         const int32_t* assoc, const int32_t* optr, const int32_t* opose, const double* ouvr, const int32_t* ooct,
+                         const int32_t* stop, char* scratch, size_t per) {
+  G.P = P;
+  G.F = F;
+  G.L = L;
+  G.poses = poses + (size_t)f * (P + F) * 7;
+  G.prior = prior + (size_t)f * P;
+  G.pts = pts + (size_t)f * L * 3;
+  G.assoc = assoc + (size_t)f * L;
+  G.optr = optr + (size_t)f * (L + 1);
+  G.opose = opose + (size_t)f * NOBS;
+  G.ouvr = ouvr + (size_t)f * NOBS * 3;
+  G.ooct = ooct + (size_t)f * NOBS;
+  G.nobs = G.optr[L];
+  G.bar = (unsigned*)(scratch + (size_t)f * 512);
+  G.flagg = (int*)(G.bar + 64);
+  G.stop = stop;
+  G.stop_seen = 0;
+  G.done_iters = 0;
+  G.trials = 0;
+  genp_carve(G, scratch + (size_t)B * 512 + (size_t)f * per, P, F, L, NOBS);
+}
+
 // barrier over the NB <= 64 workgroups of one problem (all co-resident: cooperative launch).  One flag word per
 // workgroup (zeroed by the host): a workgroup announces its k-th arrival by storing k into its own word and the lanes
 // of its first wave read everybody's word until all of them say k - plain stores to different words and one 256-byte
@@ -1512,78 +1599,13 @@ __global__ __launch_bounds__(T_BA) void k_ba_gen_t(BaK k, GmmDev gm, int B, int 
   GenP G;
   G.NB = NB;
   G.pb = blockIdx.x % NB;
-  G.P = P;
-  G.F = F;
-  G.L = L;
-  G.poses = poses_all + (size_t)f * (P + F) * 7;
-  G.prior = prior_all + (size_t)f * P;
-  G.pts = pts_all + (size_t)f * L * 3;
-  G.assoc = assoc_all + (size_t)f * L;
-  G.optr = optr_all + (size_t)f * (L + 1);
-  G.opose = opose_all + (size_t)f * NOBS;
-  G.ouvr = ouvr_all + (size_t)f * NOBS * 3;
-  G.ooct = ooct_all + (size_t)f * NOBS;
-  G.nobs = G.optr[L];
-  const int nobs = G.nobs, n = 6 * P;
-  // scratch = | B x 512 B headers {64 barrier words, solve flag} (zeroed by the host) | per-problem areas |
-  G.bar = (unsigned*)(scratch + (size_t)f * 512);
-  G.flagg = (int*)(G.bar + 64);
-  G.stop = stop_dev;
-  G.stop_seen = 0;
-  G.done_iters = 0;
-  G.trials = 0;
-  if (stop_dev && G.pb == 0 && tid == 0) G.flagg[1] = stop_word_load(stop_dev);  // (published by the set-up's first barrier)
-  // carve the problem's area (doubles first, then ints, then bytes)
-  char* s = scratch + (size_t)B * 512 + (size_t)f * scratch_per_problem;
-  auto takeD = [&](size_t cnt) {
-    double* p = (double*)s;
-    s += cnt * 8;
-    return p;
-  };
-  G.Rt = takeD((size_t)(P + F) * 12);
-  G.RtN = takeD((size_t)P * 12);
-  G.qN = takeD((size_t)P * 7);
-  G.pinv = takeD((size_t)P * 7);
-  G.pn = takeD((size_t)L * 3);
-  G.lin = takeD((size_t)NOBS * 12);
-  G.ptw = takeD((size_t)L * 12);
-  G.chi_o = takeD((size_t)NOBS);
-  G.ld = n + 1;  // row stride of S, odd: the column reads of the solve spread over the LDS banks
-  G.S = takeD((size_t)n * G.ld);
-  G.part = takeD((size_t)2 * 64 * 4);
+  genp_problem(G, f, B, P, F, L, NOBS, poses_all, prior_all, pts_all, assoc_all, optr_all, opose_all, ouvr_all, ooct_all, stop_dev, scratch,
+               scratch_per_problem);
+  const int nobs = G.nobs;
   G.toggle = 0;
   G.epoch = 0u;
   // one workgroup: the in-place LDL^T does ~4n barriers, keep S next to the CU (6P <= 120)
   if (s_in_lds && NB == 1) G.S = dyn_lds;
-  G.gv = takeD(n);
-  G.bp = takeD(n);
-  G.dxv = takeD(n);
-  G.pchi = takeD(P);
-  G.pchi2 = takeD(P);
-  G.prH = takeD((size_t)P * 36);
-  G.prb = takeD((size_t)P * 6);
-  G.pth = takeD((size_t)L * 6);
-  auto takeI = [&](size_t cnt) {
-    int32_t* p = (int32_t*)s;
-    s += ((cnt * 4 + 7) / 8) * 8;
-    return p;
-  };
-  G.opoint = takeI(NOBS);
-  G.pl_ptr = takeI(P + 1);
-  G.pl_obs = takeI(NOBS);
-  G.pl_pos = takeI(NOBS);
-  G.pl_pt = takeI(NOBS);
-  G.plm = takeI((size_t)NOBS * P);
-  auto takeB = [&](size_t cnt) {
-    uint8_t* p = (uint8_t*)s;
-    s += ((cnt + 7) / 8) * 8;
-    return p;
-  };
-  G.lev_o = takeB(NOBS);
-  G.lev_g = takeB(L);
-  G.pfree = takeB(P + F);
-  G.pact = takeB(P);
-  G.lact = takeB(L);
   // the address table (header comment of genp_fresh): written by the TABLE launch in front of this one, read-only here
   GenP* const tab = (GenP*)(scratch + (size_t)B * 512 + (size_t)(f + 1) * scratch_per_problem - GEN_TABLE_BYTES);
   k_genp* const sG = (k_genp*)tab;
@@ -1591,6 +1613,7 @@ __global__ __launch_bounds__(T_BA) void k_ba_gen_t(BaK k, GmmDev gm, int B, int 
     if (tid == 0 && G.pb == 0) *tab = G;
     return;
   }
+  if (stop_dev && G.pb == 0 && tid == 0) G.flagg[1] = stop_word_load(stop_dev);  // (published by the set-up's first barrier)
   GFRESH();
 
   // ---- setup --------------------------------------------------------------------------------------
@@ -1732,15 +1755,6 @@ __global__ __launch_bounds__(T_BA) void k_ba_gen_t(BaK k, GmmDev gm, int B, int 
 #endif
 }
 
-size_t gen_scratch_bytes(int P, int F, int L, int NOBS) {
-  const size_t n = 6 * (size_t)P;
-  size_t d = (size_t)(P + F) * 12 + (size_t)P * 12 + (size_t)P * 7 * 2 + (size_t)L * 3 + (size_t)NOBS * 12 +
-             (size_t)L * 12 + NOBS + n * (n + 2) + 512 + 3 * n + 2 * P + 42 * (size_t)P + (size_t)L * 6;
-  size_t i = (size_t)NOBS * 4 + (P + 1) + (size_t)NOBS * P + 32;
-  size_t b = (size_t)NOBS + 2 * (size_t)L + (P + F) + P + 64;
-  return d * 8 + i * 4 + b + 256 + 2 * GEN_TABLE_BYTES;  // (+ k_ba_gen's address table in the last 512 bytes of the 256-aligned area)
-}
-
 }  // namespace
 
 
@@ -1823,75 +1837,9 @@ GL_DEV PipeCtl pipe_ctl(const PipeSt* st) {
 GL_DEV PipeSt* st_cur(const PipeA& a, int f) { return a.st + (size_t)(a.par ^ 1) * a.B + f; }
 GL_DEV const PipeSt* st_prev(const PipeA& a, int f) { return a.st + (size_t)a.par * a.B + f; }
 GL_DEV void genp_init(GenP& G, const PipeA& a, int f, int NB, int pb) {
-  const int P = a.P, F = a.F, L = a.L, NOBS = a.NOBS, n = 6 * P;
   G.NB = NB;
   G.pb = pb;
-  G.P = P;
-  G.F = F;
-  G.L = L;
-  G.poses = a.poses + (size_t)f * (P + F) * 7;
-  G.prior = a.prior + (size_t)f * P;
-  G.pts = a.pts + (size_t)f * L * 3;
-  G.assoc = a.assoc + (size_t)f * L;
-  G.optr = a.optr + (size_t)f * (L + 1);
-  G.opose = a.opose + (size_t)f * NOBS;
-  G.ouvr = a.ouvr + (size_t)f * NOBS * 3;
-  G.ooct = a.ooct + (size_t)f * NOBS;
-  G.nobs = G.optr[L];
-  G.bar = (unsigned*)(a.scratch + (size_t)f * 512);
-  G.flagg = (int*)(G.bar + 64);
-  G.stop = a.stop;
-  G.stop_seen = 0;
-  G.done_iters = 0;
-  G.trials = 0;
-  char* s = a.scratch + (size_t)a.B * 512 + (size_t)f * a.per;
-  auto takeD = [&](size_t cnt) {
-    double* p = (double*)s;
-    s += cnt * 8;
-    return p;
-  };
-  G.Rt = takeD((size_t)(P + F) * 12);
-  G.RtN = takeD((size_t)P * 12);
-  G.qN = takeD((size_t)P * 7);
-  G.pinv = takeD((size_t)P * 7);
-  G.pn = takeD((size_t)L * 3);
-  G.lin = takeD((size_t)NOBS * 12);
-  G.ptw = takeD((size_t)L * 12);
-  G.chi_o = takeD((size_t)NOBS);
-  G.ld = n + 1;
-  G.S = takeD((size_t)n * G.ld);
-  G.part = takeD((size_t)2 * 64 * 4);
-  G.toggle = 0;
-  G.epoch = 0u;
-  G.gv = takeD(n);
-  G.bp = takeD(n);
-  G.dxv = takeD(n);
-  G.pchi = takeD(P);
-  G.pchi2 = takeD(P);
-  G.prH = takeD((size_t)P * 36);
-  G.prb = takeD((size_t)P * 6);
-  G.pth = takeD((size_t)L * 6);  // (the persistent kernel's carve; this shape keeps its own in PipeA)
-  auto takeI = [&](size_t cnt) {
-    int32_t* p = (int32_t*)s;
-    s += ((cnt * 4 + 7) / 8) * 8;
-    return p;
-  };
-  G.opoint = takeI(NOBS);
-  G.pl_ptr = takeI(P + 1);
-  G.pl_obs = takeI(NOBS);
-  G.pl_pos = takeI(NOBS);
-  G.pl_pt = takeI(NOBS);
-  G.plm = takeI((size_t)NOBS * P);
-  auto takeB = [&](size_t cnt) {
-    uint8_t* p = (uint8_t*)s;
-    s += ((cnt + 7) / 8) * 8;
-    return p;
-  };
-  G.lev_o = takeB(NOBS);
-  G.lev_g = takeB(L);
-  G.pfree = takeB(P + F);
-  G.pact = takeB(P);
-  G.lact = takeB(L);
+  genp_problem(G, f, a.B, a.P, a.F, a.L, a.NOBS, a.poses, a.prior, a.pts, a.assoc, a.optr, a.opose, a.ouvr, a.ooct, a.stop, a.scratch, a.per);
 }
 
 // prior edges at the current state (once per outer iteration: gen_optimize does the same)
@@ -2760,20 +2708,61 @@ __global__ __launch_bounds__(T_BA) void kp_trial(PipeA a) {
 }
 
 namespace gl {
+// A batch of B windows of the local BA in the caller's arrays (strides: gmmloc_hip.h)
+struct BaBatch {
+  int B, P, F, L, NOBS;
+  double* poses;
+  const uint8_t* prior;
+  double* pts;
+  const int32_t* assoc;
+  const int32_t* optr;
+  const int32_t* opose;
+  const double* ouvr;
+  const int32_t* ooct;
+  uint8_t* dropped;
+  uint8_t* erase;
+  int32_t* iters;       // optional
+  const int32_t* stop;  // optional stop word (gl_joint_optimization_stoppable)
+  // windows [first, first + count)
+  BaBatch window(int first, int count) const {
+    const size_t w = (size_t)first;
+    BaBatch b = *this;
+    b.B = count;
+    b.poses += w * (P + F) * 7;
+    b.prior += w * P;
+    b.pts += w * L * 3;
+    b.assoc += w * L;
+    b.optr += w * (L + 1);
+    b.opose += w * NOBS;
+    b.ouvr += w * NOBS * 3;
+    b.ooct += w * NOBS;
+    b.dropped += w * L;
+    b.erase += w * NOBS;
+    if (iters) b.iters += w;
+    return b;
+  }
+};
+
+// consecutive 256-aligned regions of a scratch block from `off` on
+struct Regions {
+  size_t off;
+  size_t take(size_t bytes) {  // the offset of the next region
+    const size_t at = off;
+    off += ((bytes + 255) / 256) * 256;
+    return at;
+  }
+};
+
 size_t ba_gen_scratch_bytes(int B, int P, int F, int L, int NOBS) {
-  const size_t per = ((gen_scratch_bytes(P, F, L, NOBS) + 255) / 256) * 256;
-  return (size_t)B * 512 + per * B;
+  return (size_t)B * 512 + gen_scratch_bytes(P, F, L, NOBS) * B;
 }
 
 // the launch proper; scratch: ba_gen_scratch_bytes() bytes of the context's scratch block
 // the persistent kernel proper and the launch that writes its address table (k_ba_gen_t<true>: same arguments, one wave per window)
 static const auto k_ba_gen = &k_ba_gen_t<false>;
-int launch_ba_gen(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int P, int F, int L, int NOBS,
-                  double* poses_dev, const uint8_t* prior_dev, double* points_dev, const int32_t* assoc_dev,
-                  const int32_t* obs_ptr_dev, const int32_t* obs_pose_dev, const double* obs_uvr_dev,
-                  const int32_t* obs_oct_dev, uint8_t* assoc_dropped_dev, uint8_t* obs_erase_dev, int32_t* iters_dev,
-                  const int32_t* stop_dev, void* scratch, int force_nb = 0) {
-  const size_t per = ((gen_scratch_bytes(P, F, L, NOBS) + 255) / 256) * 256;
+int launch_ba_gen(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, const BaBatch& b, void* scratch, int force_nb = 0) {
+  const int B = b.B, P = b.P, NOBS = b.NOBS;
+  size_t per = gen_scratch_bytes(P, b.F, b.L, NOBS);
   GmmDev gm{g->rec12, g->axis, g->sqrt_info, g->hgw, g->flags, g->plane4};
   const size_t n = 6 * (size_t)P;
   const size_t s_bytes = n * (n + 1) * sizeof(double);
@@ -2817,21 +2806,10 @@ int launch_ba_gen(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* p
     gl::TimerScope ts(c, GL_TIMER_BA);
     BaK kk = make_bak(cam, prm, -1.0);
     int32_t* stats_all = (c->stats && c->stats_n >= B) ? c->stats : nullptr;  // gl_ctx_set_stats_buffer: trials per problem
-    size_t per_v = per;
     for (int b0 = 0, Bs = 0; b0 < B; b0 += Bs) {
       Bs = std::min(bsub, B - b0);
-      // the sub-batch's slices of the caller's arrays (strides: gmmloc_hip.h); the scratch is re-used, launches are in stream order
-      double* poses_s = poses_dev + (size_t)b0 * (P + F) * 7;
-      const uint8_t* prior_s = prior_dev + (size_t)b0 * P;
-      double* points_s = points_dev + (size_t)b0 * L * 3;
-      const int32_t* assoc_s = assoc_dev + (size_t)b0 * L;
-      const int32_t* optr_s = obs_ptr_dev + (size_t)b0 * (L + 1);
-      const int32_t* opose_s = obs_pose_dev + (size_t)b0 * NOBS;
-      const double* ouvr_s = obs_uvr_dev + (size_t)b0 * NOBS * 3;
-      const int32_t* ooct_s = obs_oct_dev + (size_t)b0 * NOBS;
-      uint8_t* dropped_s = assoc_dropped_dev + (size_t)b0 * L;
-      uint8_t* erase_s = obs_erase_dev + (size_t)b0 * NOBS;
-      int32_t* iters_s = iters_dev ? iters_dev + b0 : nullptr;
+      // the sub-batch's windows of the caller's arrays; the scratch is re-used, launches are in stream order
+      BaBatch s = b.window(b0, Bs);
       int32_t* stats = stats_all ? stats_all + b0 : nullptr;
       char* scr = (char*)scratch;
       GL_HIP(hipMemsetAsync(scratch, 0, (size_t)Bs * 512, c->stream));
@@ -2841,14 +2819,15 @@ int launch_ba_gen(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* p
       // fits.  Only when a single window does not fit does the call fall back to one workgroup per problem (other bits, the same
       // arithmetic): GL_COUNTER_BA_COOP_FALLBACK counts those windows.
       auto write_table = [&](int bs) {  // (the table's addresses depend on the sub-batch size: again for every size that is tried)
-        k_ba_gen_t<true><<<bs, 64, 0, c->stream>>>(kk, gm, bs, 1, P, F, L, NOBS, poses_s, prior_s, points_s, assoc_s, optr_s, opose_s, ouvr_s, ooct_s,
-                                                   dropped_s, erase_s, iters_s, scr, per_v, s_in_lds, stop_dev, stats);
+        k_ba_gen_t<true><<<bs, 64, 0, c->stream>>>(kk, gm, bs, 1, s.P, s.F, s.L, s.NOBS, s.poses, s.prior, s.pts, s.assoc, s.optr, s.opose,
+                                                   s.ouvr, s.ooct, s.dropped, s.erase, s.iters, scr, per, s_in_lds, s.stop, stats);
+        return hipGetLastError();
       };
       while (NB > 1 && !launched) {
-        void* args[] = {&kk, &gm, &Bs, &NB, &P, &F, &L, &NOBS, &poses_s, &prior_s, &points_s, &assoc_s, &optr_s,
-                        &opose_s, &ouvr_s, &ooct_s, &dropped_s, &erase_s, &iters_s, &scr, &per_v,
-                        &s_in_lds, &stop_dev, &stats};
-        write_table(Bs);
+        void* args[] = {&kk, &gm, &Bs, &NB, &s.P, &s.F, &s.L, &s.NOBS, &s.poses, &s.prior, &s.pts, &s.assoc, &s.optr,
+                        &s.opose, &s.ouvr, &s.ooct, &s.dropped, &s.erase, &s.iters, &scr, &per,
+                        &s_in_lds, &s.stop, &stats};
+        GL_HIP(write_table(Bs));
         hipError_t e = hipLaunchCooperativeKernel((const void*)k_ba_gen, dim3(Bs * NB), dim3(T_BA), args, lds, c->stream);
         launched = e == hipSuccess;
         if (!launched) {
@@ -2859,10 +2838,9 @@ int launch_ba_gen(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* p
       }
       if (!launched) {
         if (NB > 1) c->coop_fallbacks += Bs;
-        write_table(Bs);
-        k_ba_gen<<<Bs, T_BA, lds, c->stream>>>(kk, gm, Bs, 1, P, F, L, NOBS, poses_s, prior_s, points_s, assoc_s, optr_s,
-                                               opose_s, ouvr_s, ooct_s, dropped_s, erase_s, iters_s,
-                                               scr, per_v, s_in_lds, stop_dev, stats);
+        GL_HIP(write_table(Bs));
+        k_ba_gen<<<Bs, T_BA, lds, c->stream>>>(kk, gm, Bs, 1, s.P, s.F, s.L, s.NOBS, s.poses, s.prior, s.pts, s.assoc, s.optr, s.opose,
+                                               s.ouvr, s.ooct, s.dropped, s.erase, s.iters, scr, per, s_in_lds, s.stop, stats);
       }
     }
   }
@@ -2879,12 +2857,25 @@ static void pipe_shape(int P, int L, int NOBS, int* nba, int* lpp, int* nblk, in
   // is 8 % faster than 16 (3 360 of 3: a second wave of workgroups behind the first)
   *nchunk = NOBS <= 1024 ? 4 : NOBS <= 40000 ? 16 : 12;
 }
-size_t ba_pipe_scratch_bytes(int B, int P, int F, int L, int NOBS) {
+// offsets of the buffers of a lane of B windows (PipeA) behind k_ba_gen's layout; end: the lane's scratch bytes
+struct PipeLayout {
+  size_t st, partA, partD, partS, pth, stJ, verd, unfinished, end;
+};
+static PipeLayout pipe_layout(int B, int P, int F, int L, int NOBS) {
   int nba, lpp, nblk, nchunk;
   pipe_shape(P, L, NOBS, &nba, &lpp, &nblk, &nchunk);
-  auto up = [](size_t v) { return ((v + 255) / 256) * 256; };
-  return ba_gen_scratch_bytes(B, P, F, L, NOBS) + up((size_t)2 * B * sizeof(PipeSt)) + 2 * up((size_t)B * nba * 16) +
-         up((size_t)B * nblk * nchunk * 48 * 8) + up((size_t)B * L * 6 * 8) + up((size_t)B * sizeof(PipeSt)) + up((size_t)B * 8) + up((size_t)B * nblk * 4) + 1024;
+  Regions r{ba_gen_scratch_bytes(B, P, F, L, NOBS)};
+  PipeLayout o;
+  o.st = r.take((size_t)2 * B * sizeof(PipeSt));
+  o.partA = r.take((size_t)B * nba * 16);
+  o.partD = r.take((size_t)B * nba * 16);
+  o.partS = r.take((size_t)B * nblk * nchunk * 48 * 8);
+  o.pth = r.take((size_t)B * L * 6 * 8);
+  o.stJ = r.take((size_t)B * sizeof(PipeSt));
+  o.verd = r.take((size_t)B * 8);
+  o.unfinished = r.take(2 * sizeof(int));
+  o.end = r.off;
+  return o;
 }
 
 // One LANE of the pipelined local BA: a sub-batch of the call's windows with its own kernel arguments, scratch area and stream.
@@ -2896,11 +2887,9 @@ struct PipeLane {
   int* hw = nullptr;
   bool done = false;
 };
-static int pipe_lane_setup(Ctx* c, PipeLane& ln, int stats_off, bool stats_ok, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int P, int F, int L, int NOBS,
-                   double* poses_dev, const uint8_t* prior_dev, double* points_dev, const int32_t* assoc_dev,
-                   const int32_t* obs_ptr_dev, const int32_t* obs_pose_dev, const double* obs_uvr_dev,
-                   const int32_t* obs_oct_dev, uint8_t* assoc_dropped_dev, uint8_t* obs_erase_dev, int32_t* iters_dev,
-                   const int32_t* stop_dev, void* scratch) {
+static int pipe_lane_setup(Ctx* c, PipeLane& ln, int stats_off, bool stats_ok, const Gmm* g, const gl_camera* cam, const gl_params* prm,
+                           const BaBatch& b, void* scratch) {
+  const int B = b.B, P = b.P, F = b.F, L = b.L, NOBS = b.NOBS;
   PipeA& a = ln.a;
   a.k = make_bak(cam, prm, -1.0);
   a.gm = GmmDev{g->rec12, g->axis, g->sqrt_info, g->hgw, g->flags, g->plane4};
@@ -2909,44 +2898,36 @@ static int pipe_lane_setup(Ctx* c, PipeLane& ln, int stats_off, bool stats_ok, c
   a.F = F;
   a.L = L;
   a.NOBS = NOBS;
-  a.poses = poses_dev;
-  a.prior = prior_dev;
-  a.pts = points_dev;
-  a.assoc = assoc_dev;
-  a.optr = obs_ptr_dev;
-  a.opose = obs_pose_dev;
-  a.ouvr = obs_uvr_dev;
-  a.ooct = obs_oct_dev;
-  a.dropped = assoc_dropped_dev;
-  a.erase = obs_erase_dev;
-  a.iters = iters_dev;
+  a.poses = b.poses;
+  a.prior = b.prior;
+  a.pts = b.pts;
+  a.assoc = b.assoc;
+  a.optr = b.optr;
+  a.opose = b.opose;
+  a.ouvr = b.ouvr;
+  a.ooct = b.ooct;
+  a.dropped = b.dropped;
+  a.erase = b.erase;
+  a.iters = b.iters;
   a.trials_out = stats_ok ? c->stats + stats_off : nullptr;  // (checked once for the whole call: all lanes or none)
-  a.stop = stop_dev;
+  a.stop = b.stop;
   a.scratch = (char*)scratch;
-  a.per = ((gen_scratch_bytes(P, F, L, NOBS) + 255) / 256) * 256;
+  a.per = gen_scratch_bytes(P, F, L, NOBS);
   pipe_shape(P, L, NOBS, &a.nba, &a.lpp, &a.nblk, &a.nchunk);
-  auto up = [](size_t v) { return ((v + 255) / 256) * 256; };
-  char* s = (char*)scratch + ba_gen_scratch_bytes(B, P, F, L, NOBS);
-  a.st = (PipeSt*)s;
-  s += up((size_t)2 * B * sizeof(PipeSt));
-  a.partA = (double*)s;
-  s += up((size_t)B * a.nba * 16);
-  a.partD = (double*)s;
-  s += up((size_t)B * a.nba * 16);
-  a.partS = (double*)s;
-  s += up((size_t)B * a.nblk * a.nchunk * 48 * 8);
-  a.pth = (double*)s;
-  s += up((size_t)B * L * 6 * 8);
-  a.stJ = (PipeSt*)s;
-  s += up((size_t)B * sizeof(PipeSt));
-  a.verd = (int*)s;
-  s += up((size_t)B * 8);
+  const PipeLayout o = pipe_layout(B, P, F, L, NOBS);
+  a.st = (PipeSt*)(a.scratch + o.st);
+  a.partA = (double*)(a.scratch + o.partA);
+  a.partD = (double*)(a.scratch + o.partD);
+  a.partS = (double*)(a.scratch + o.partS);
+  a.pth = (double*)(a.scratch + o.pth);
+  a.stJ = (PipeSt*)(a.scratch + o.stJ);
+  a.verd = (int*)(a.scratch + o.verd);
+  a.unfinished = (int*)(a.scratch + o.unfinished);  // [0] problems not finished, [1] cycles the slowest of them needed
   // The verdict on a trial as a kernel of its own behind kp_trial (one small workgroup per window) instead of in every one of the
   // window's 24 - 47 point-pass workgroups: in batches the judging head is 14 of kp_lin's 28 us (64 windows); alone it is a launch
   // more on a single window's critical path (break-even at 16 - 24 windows per lane: from 32 on; option pipe_judge = 0 / 1 overrides,
   // for A/B runs).  The same function on the same values: the same bits.  64 windows 0.122 -> 0.114 ms per window, 256 0.118 -> 0.113.
   a.ext_judge = c->opt.pipe_judge >= 0 ? (c->opt.pipe_judge != 0 ? 1 : 0) : (B >= 32 ? 1 : 0);
-  a.unfinished = (int*)s;  // [0] problems not finished, [1] cycles the slowest of them needed
   const size_t n = 6 * (size_t)P;
   ln.s_bytes = n <= 128 ? n * (n + 1) * sizeof(double) : 0;
   if (ln.s_bytes) GL_HIP(ensure_dynamic_lds(c, (const void*)kp_solve, ln.s_bytes));
@@ -3024,12 +3005,11 @@ static void pipe_lane_windows(int B, int nl, int k, int* first, int* count) {
   if (k == nl - 1) *count = B - *first;
 }
 static size_t pipe_lane_scratch_off(int B, int nl, int k, int P, int F, int L, int NOBS) {
-  auto up = [](size_t v) { return ((v + 255) / 256) * 256; };
   size_t off = 0;
   for (int i = 0; i < k; ++i) {
     int f0, cnt;
     pipe_lane_windows(B, nl, i, &f0, &cnt);
-    off += up(ba_pipe_scratch_bytes(std::max(cnt, 1), P, F, L, NOBS));
+    off += pipe_layout(std::max(cnt, 1), P, F, L, NOBS).end;
   }
   return off;
 }
@@ -3038,11 +3018,9 @@ size_t ba_pipe_scratch_total(const Ctx* c, int B, int P, int F, int L, int NOBS)
   return pipe_lane_scratch_off(B, nl, nl, P, F, L, NOBS);
 }
 
-static int launch_ba_pipe_lanes(Ctx* c, PipeLane* lane, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int P, int F, int L, int NOBS,
-                               double* poses_dev, const uint8_t* prior_dev, double* points_dev, const int32_t* assoc_dev,
-                               const int32_t* obs_ptr_dev, const int32_t* obs_pose_dev, const double* obs_uvr_dev,
-                               const int32_t* obs_oct_dev, uint8_t* assoc_dropped_dev, uint8_t* obs_erase_dev, int32_t* iters_dev,
-                               const int32_t* stop_dev, void* scratch) {
+static int launch_ba_pipe_lanes(Ctx* c, PipeLane* lane, const Gmm* g, const gl_camera* cam, const gl_params* prm, const BaBatch& b,
+                                void* scratch) {
+  const int B = b.B, NOBS = b.NOBS;
   // page-locked words the devices' counts of unfinished problems are copied to between chunks of cycles (4 per lane)
   if (!c->host_word) GL_HIP(hipHostMalloc((void**)&c->host_word, 64, hipHostMallocDefault));
   const int nl = pipe_lanes(c, B, NOBS);
@@ -3064,12 +3042,8 @@ static int launch_ba_pipe_lanes(Ctx* c, PipeLane* lane, const Gmm* g, const gl_c
     lane[k].s = k == 0 ? c->stream : c->lane_stream[k - 1];
     if (k > 0) GL_HIP(hipStreamWaitEvent(lane[k].s, c->ev_fork, 0));
     lane[k].hw = c->host_word + 4 * k;
-    char* sk = (char*)scratch + pipe_lane_scratch_off(B, nl, k, P, F, L, NOBS);
-    const size_t w = (size_t)w0;
-    const int rc = pipe_lane_setup(c, lane[k], w0, c->stats && c->stats_n >= B, g, cam, prm, Bk, P, F, L, NOBS, poses_dev + w * (P + F) * 7, prior_dev + w * P,
-                                   points_dev + w * L * 3, assoc_dev + w * L, obs_ptr_dev + w * (L + 1), obs_pose_dev + w * NOBS,
-                                   obs_uvr_dev + w * NOBS * 3, obs_oct_dev + w * NOBS, assoc_dropped_dev ? assoc_dropped_dev + w * L : nullptr,
-                                   obs_erase_dev ? obs_erase_dev + w * NOBS : nullptr, iters_dev ? iters_dev + w : nullptr, stop_dev, sk);
+    char* sk = (char*)scratch + pipe_lane_scratch_off(B, nl, k, b.P, b.F, b.L, NOBS);
+    const int rc = pipe_lane_setup(c, lane[k], w0, c->stats && c->stats_n >= B, g, cam, prm, b.window(w0, Bk), sk);
     if (rc != GL_OK) return rc;
   }
   // a run needs 3 lambda-init cycles + its Levenberg trials (28 - 35 on the windows measured; every rejected trial adds
@@ -3114,14 +3088,9 @@ static int launch_ba_pipe_lanes(Ctx* c, PipeLane* lane, const Gmm* g, const gl_c
 // The lanes run on further non-blocking streams and share the context's scratch block: whatever way the call ends, nothing of it may
 // still be in flight when it returns - the next call on the context only orders itself behind c->stream and may overwrite or free
 // that scratch.  Every error exit therefore waits for all the lanes' streams first (the regular exit has seen their counters).
-int launch_ba_pipe(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int P, int F, int L, int NOBS,
-                   double* poses_dev, const uint8_t* prior_dev, double* points_dev, const int32_t* assoc_dev,
-                   const int32_t* obs_ptr_dev, const int32_t* obs_pose_dev, const double* obs_uvr_dev,
-                   const int32_t* obs_oct_dev, uint8_t* assoc_dropped_dev, uint8_t* obs_erase_dev, int32_t* iters_dev,
-                   const int32_t* stop_dev, void* scratch) {
+int launch_ba_pipe(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, const BaBatch& b, void* scratch) {
   PipeLane lane[PIPE_LANES_MAX];
-  const int rc = launch_ba_pipe_lanes(c, lane, g, cam, prm, B, P, F, L, NOBS, poses_dev, prior_dev, points_dev, assoc_dev, obs_ptr_dev, obs_pose_dev,
-                                      obs_uvr_dev, obs_oct_dev, assoc_dropped_dev, obs_erase_dev, iters_dev, stop_dev, scratch);
+  const int rc = launch_ba_pipe_lanes(c, lane, g, cam, prm, b, scratch);
   if (rc != GL_OK) {
     for (int k = 0; k < PIPE_LANES_MAX; ++k)
       if (lane[k].s) (void)hipStreamSynchronize(lane[k].s);  // (keep the first error's message)
@@ -3130,19 +3099,12 @@ int launch_ba_pipe(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* 
 }
 }  // namespace gl
 
-static int joint_optimization_impl(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm,
-                                   int B, int P, int F, int L, int NOBS, double* poses_dev,
-                                   const uint8_t* prior_dev, double* points_dev, const int32_t* assoc_dev,
-                                   const int32_t* obs_ptr_dev, const int32_t* obs_pose_dev,
-                                   const double* obs_uvr_dev, const int32_t* obs_oct_dev,
-                                   uint8_t* assoc_dropped_dev, uint8_t* obs_erase_dev, int32_t* iters_dev,
-                                   const int32_t* stop_dev) {
+static int joint_optimization_impl(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm, const gl::BaBatch& b) {
+  const int B = b.B, P = b.P, F = b.F, L = b.L, NOBS = b.NOBS;
   GL_REQUIRE(ctx && gmm && cam && prm, "null argument");
   if (B == 0) return GL_OK;
   GL_REQUIRE(B > 0 && P >= 1 && F >= 0 && L >= 1 && NOBS >= 1, "bad problem shape");
-  GL_REQUIRE(poses_dev && prior_dev && points_dev && assoc_dev && obs_ptr_dev && obs_pose_dev && obs_uvr_dev &&
-                 obs_oct_dev && assoc_dropped_dev && obs_erase_dev,
-             "null buffer");
+  GL_REQUIRE(b.poses && b.prior && b.pts && b.assoc && b.optr && b.opose && b.ouvr && b.ooct && b.dropped && b.erase, "null buffer");
   gl::Ctx* c = gl::C(ctx);
   gl::Gmm* g = gl::G(gmm);
   GL_HIP(hipSetDevice(c->device));
@@ -3161,12 +3123,7 @@ static int joint_optimization_impl(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_
   const bool pipe = pipe_fits && (c->opt.bagen_mode == 2 || (c->opt.bagen_mode == 0 && NOBS >= 3000));
   int rc = gl::ctx_scratch(c, pipe ? gl::ba_pipe_scratch_total(c, B, P, F, L, NOBS) : gl::ba_gen_scratch_bytes(B, P, F, L, NOBS), &scratch);
   if (rc != GL_OK) return rc;
-  if (pipe) {
-    return gl::launch_ba_pipe(c, g, cam, prm, B, P, F, L, NOBS, poses_dev, prior_dev, points_dev, assoc_dev, obs_ptr_dev, obs_pose_dev,
-                              obs_uvr_dev, obs_oct_dev, assoc_dropped_dev, obs_erase_dev, iters_dev, stop_dev, scratch);
-  }
-  return gl::launch_ba_gen(c, g, cam, prm, B, P, F, L, NOBS, poses_dev, prior_dev, points_dev, assoc_dev, obs_ptr_dev, obs_pose_dev,
-                           obs_uvr_dev, obs_oct_dev, assoc_dropped_dev, obs_erase_dev, iters_dev, stop_dev, scratch);
+  return pipe ? gl::launch_ba_pipe(c, g, cam, prm, b, scratch) : gl::launch_ba_gen(c, g, cam, prm, b, scratch);
 }
 
 extern "C" int gl_joint_optimization(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm,
@@ -3175,8 +3132,8 @@ extern "C" int gl_joint_optimization(gl_ctx_t* ctx, const gl_gmm_t* gmm, const g
                                      const int32_t* obs_ptr_dev, const int32_t* obs_pose_dev,
                                      const double* obs_uvr_dev, const int32_t* obs_oct_dev,
                                      uint8_t* assoc_dropped_dev, uint8_t* obs_erase_dev, int32_t* iters_dev) {
-  return joint_optimization_impl(ctx, gmm, cam, prm, B, P, F, L, NOBS, poses_dev, prior_dev, points_dev, assoc_dev, obs_ptr_dev,
-                                 obs_pose_dev, obs_uvr_dev, obs_oct_dev, assoc_dropped_dev, obs_erase_dev, iters_dev, nullptr);
+  return gl_joint_optimization_stoppable(ctx, gmm, cam, prm, B, P, F, L, NOBS, poses_dev, prior_dev, points_dev, assoc_dev, obs_ptr_dev,
+                                         obs_pose_dev, obs_uvr_dev, obs_oct_dev, assoc_dropped_dev, obs_erase_dev, iters_dev, nullptr);
 }
 
 extern "C" int gl_joint_optimization_stoppable(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm,
@@ -3186,8 +3143,8 @@ extern "C" int gl_joint_optimization_stoppable(gl_ctx_t* ctx, const gl_gmm_t* gm
                                                const double* obs_uvr_dev, const int32_t* obs_oct_dev,
                                                uint8_t* assoc_dropped_dev, uint8_t* obs_erase_dev, int32_t* iters_dev,
                                                const int32_t* stop_flag) {
-  return joint_optimization_impl(ctx, gmm, cam, prm, B, P, F, L, NOBS, poses_dev, prior_dev, points_dev, assoc_dev, obs_ptr_dev,
-                                 obs_pose_dev, obs_uvr_dev, obs_oct_dev, assoc_dropped_dev, obs_erase_dev, iters_dev, stop_flag);
+  return joint_optimization_impl(ctx, gmm, cam, prm, {B, P, F, L, NOBS, poses_dev, prior_dev, points_dev, assoc_dev, obs_ptr_dev, obs_pose_dev,
+                                                      obs_uvr_dev, obs_oct_dev, assoc_dropped_dev, obs_erase_dev, iters_dev, stop_flag});
 }
 
 // ---- gl_track_frames_anchored with F > 0 fixed observer key-frames --------------------------------------------------
@@ -3311,21 +3268,21 @@ int track_frames_fixed(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam,
   const size_t n = (size_t)B * M, NOBS = (size_t)M * (1 + F);
   const bool use_grid = g->grid.enabled && c->opt.assoc_grid != 0;
   const size_t assoc_bytes = use_grid ? assoc_index_scratch_bytes(g->K, (int)n, d2_dev != nullptr) : assoc_scratch_bytes(g->K, (int)n);
-  auto up = [](size_t v) { return ((v + 255) / 256) * 256; };
   // | association scratch | d2 | poses | prior | optr | opose | ouvr | ooct | dropped | erase | general kernel |
-  size_t off = up(assoc_bytes);
-  const size_t o_d2 = off;      off += up(n * 8);
-  const size_t o_poses = off;   off += up((size_t)B * (1 + F) * 56);
-  const size_t o_prior = off;   off += up((size_t)B);
-  const size_t o_optr = off;    off += up((size_t)B * (M + 1) * 4);
-  const size_t o_opose = off;   off += up((size_t)B * NOBS * 4);
-  const size_t o_ouvr = off;    off += up((size_t)B * NOBS * 24);
-  const size_t o_ooct = off;    off += up((size_t)B * NOBS * 4);
-  const size_t o_drop = off;    off += up(n);
-  const size_t o_erase = off;   off += up((size_t)B * NOBS);
-  const size_t o_gen = off;     off += ba_gen_scratch_bytes(B, 1, F, M, (int)NOBS);
+  Regions r{0};
+  r.take(assoc_bytes);
+  const size_t o_d2 = r.take(n * 8);
+  const size_t o_poses = r.take((size_t)B * (1 + F) * 56);
+  const size_t o_prior = r.take(B);
+  const size_t o_optr = r.take((size_t)B * (M + 1) * 4);
+  const size_t o_opose = r.take((size_t)B * NOBS * 4);
+  const size_t o_ouvr = r.take((size_t)B * NOBS * 24);
+  const size_t o_ooct = r.take((size_t)B * NOBS * 4);
+  const size_t o_drop = r.take(n);
+  const size_t o_erase = r.take((size_t)B * NOBS);
+  const size_t o_gen = r.take(ba_gen_scratch_bytes(B, 1, F, M, (int)NOBS));
   void* scratch = nullptr;
-  int rc = ctx_scratch(c, off + 256, &scratch);
+  int rc = ctx_scratch(c, r.off + 256, &scratch);
   if (rc != GL_OK) return rc;
   char* s = (char*)scratch;
   double* d2 = d2_dev ? d2_dev : (double*)(s + o_d2);
@@ -3341,10 +3298,10 @@ int track_frames_fixed(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam,
                                             (int32_t*)(s + o_optr), (int32_t*)(s + o_opose), (double*)(s + o_ouvr), (int32_t*)(s + o_ooct));
   }
   GL_HIP(hipGetLastError());
-  rc = launch_ba_gen(c, g, cam, prm, B, 1, F, M, (int)NOBS, (double*)(s + o_poses), (const uint8_t*)(s + o_prior), Xw_dev, assoc_dev,
-                     (const int32_t*)(s + o_optr), (const int32_t*)(s + o_opose), (const double*)(s + o_ouvr), (const int32_t*)(s + o_ooct),
-                     (uint8_t*)(s + o_drop), (uint8_t*)(s + o_erase), nullptr, nullptr, s + o_gen,
-                     1);  // one workgroup per frame: per-frame batches are large, and a frame's bits must not depend on the batch
+  const BaBatch pk{B, 1, F, M, (int)NOBS, (double*)(s + o_poses), (const uint8_t*)(s + o_prior), Xw_dev, assoc_dev, (const int32_t*)(s + o_optr),
+                   (const int32_t*)(s + o_opose), (const double*)(s + o_ouvr), (const int32_t*)(s + o_ooct), (uint8_t*)(s + o_drop),
+                   (uint8_t*)(s + o_erase), nullptr, nullptr};
+  rc = launch_ba_gen(c, g, cam, prm, pk, s + o_gen, 1);  // one workgroup per frame: per-frame batches are large, and a frame's bits must not depend on the batch
   if (rc != GL_OK) return rc;
   k_track_unpack<<<B, PK_T, 0, c->stream>>>(B, M, F, (const double*)(s + o_poses), (const int32_t*)(s + o_optr), (const int32_t*)(s + o_opose),
                                             (const uint8_t*)(s + o_drop), (const uint8_t*)(s + o_erase), pose_dev, assoc_dev, an->fixed_erase_dev);

@@ -41,84 +41,23 @@ static void options_from_env(Options& o) {
 #undef X
 }
 
-int ctx_scratch(Ctx* c, size_t bytes, void** out) {
-  if (bytes > c->scratch_bytes) {
-    if (c->scratch) {
+int ctx_scratch(Ctx* c, size_t bytes, void** out, int which) {
+  ScratchBlock& b = c->scratch[which];
+  if (bytes > b.bytes) {
+    if (b.p) {
       GL_HIP(hipStreamSynchronize(c->stream));
-      GL_HIP(hipFree(c->scratch));
-      c->scratch = nullptr;
-      c->scratch_bytes = 0;
+      GL_HIP(hipFree(b.p));
+      b.p = nullptr;
+      b.bytes = 0;
     }
     const size_t want = bytes + bytes / 2;
-    if (hipMalloc(&c->scratch, want) != hipSuccess) {
+    if (hipMalloc(&b.p, want) != hipSuccess) {
       set_error("scratch hipMalloc(%zu) failed", want);
       return GL_ERR_NOMEM;
     }
-    c->scratch_bytes = want;
+    b.bytes = want;
   }
-  *out = c->scratch;
-  return GL_OK;
-}
-
-// second block, for entry points that are themselves called with their inputs in the first one (the matchers' candidate cache:
-// gl_search_local_points keeps the projection loop's outputs in `scratch` and hands them to gl_search_by_projection)
-int ctx_scratch_b(Ctx* c, size_t bytes, void** out) {
-  if (bytes > c->scratch_b_bytes) {
-    if (c->scratch_b) {
-      GL_HIP(hipStreamSynchronize(c->stream));
-      GL_HIP(hipFree(c->scratch_b));
-      c->scratch_b = nullptr;
-      c->scratch_b_bytes = 0;
-    }
-    const size_t want = bytes + bytes / 2;
-    if (hipMalloc(&c->scratch_b, want) != hipSuccess) {
-      set_error("scratch hipMalloc(%zu) failed", want);
-      return GL_ERR_NOMEM;
-    }
-    c->scratch_b_bytes = want;
-  }
-  *out = c->scratch_b;
-  return GL_OK;
-}
-
-// fourth block: the screened association's per-split candidate lists and its fp64 fallback (launch_assoc_screened), so that it
-// needs nothing from the block its caller sized for the fp64 sweep
-int ctx_scratch_s(Ctx* c, size_t bytes, void** out) {
-  if (bytes > c->scratch_s_bytes) {
-    if (c->scratch_s) {
-      GL_HIP(hipStreamSynchronize(c->stream));
-      GL_HIP(hipFree(c->scratch_s));
-      c->scratch_s = nullptr;
-      c->scratch_s_bytes = 0;
-    }
-    const size_t want = bytes + bytes / 2;
-    if (hipMalloc(&c->scratch_s, want) != hipSuccess) {
-      set_error("scratch hipMalloc(%zu) failed", want);
-      return GL_ERR_NOMEM;
-    }
-    c->scratch_s_bytes = want;
-  }
-  *out = c->scratch_s;
-  return GL_OK;
-}
-
-// third block: gl_track_frame_chain's own intermediates (its stages use the first two)
-int ctx_scratch_c(Ctx* c, size_t bytes, void** out) {
-  if (bytes > c->scratch_c_bytes) {
-    if (c->scratch_c) {
-      GL_HIP(hipStreamSynchronize(c->stream));
-      GL_HIP(hipFree(c->scratch_c));
-      c->scratch_c = nullptr;
-      c->scratch_c_bytes = 0;
-    }
-    const size_t want = bytes + bytes / 2;
-    if (hipMalloc(&c->scratch_c, want) != hipSuccess) {
-      set_error("scratch hipMalloc(%zu) failed", want);
-      return GL_ERR_NOMEM;
-    }
-    c->scratch_c_bytes = want;
-  }
-  *out = c->scratch_c;
+  *out = b.p;
   return GL_OK;
 }
 
@@ -223,10 +162,8 @@ int gl_ctx_destroy(gl_ctx_t* ctx) {
     (void)hipEventDestroy(p.first);
     (void)hipEventDestroy(p.second);
   }
-  if (c->scratch) (void)hipFree(c->scratch);
-  if (c->scratch_b) (void)hipFree(c->scratch_b);
-  if (c->scratch_c) (void)hipFree(c->scratch_c);
-  if (c->scratch_s) (void)hipFree(c->scratch_s);
+  for (const gl::ScratchBlock& b : c->scratch)
+    if (b.p) (void)hipFree(b.p);
   if (c->counters) (void)hipFree(c->counters);
   if (c->host_word) (void)hipHostFree(c->host_word);
   for (int k = 0; k < 3; ++k) {

@@ -405,7 +405,7 @@ int launch_assoc_screened(Ctx* c, const Gmm* g, const double* pts, int N, int32_
   const size_t fb_bytes = assoc_scratch_bytes(K, N, true);
   if (!g->rec32) {  // map without screen records
     void* scratch = nullptr;
-    int rc = ctx_scratch_s(c, assoc_scratch_bytes(K, N, list != nullptr), &scratch);
+    int rc = ctx_scratch(c, assoc_scratch_bytes(K, N, list != nullptr), &scratch, SCRATCH_SCREEN);
     if (rc != GL_OK) return rc;
     k_screen_count_all<<<1, 1, 0, c->stream>>>(N, count_dev, c->counters);
     GL_HIP(hipGetLastError());
@@ -420,7 +420,7 @@ int launch_assoc_screened(Ctx* c, const Gmm* g, const double* pts, int N, int32_
                o_lo = o_k0 + up(per * 4 * kOut), o_fbc = o_lo + up(per * 4 * kOut), o_fbl = o_fbc + 256,
                o_sw = o_fbl + up((size_t)N * 4);
   void* scratch = nullptr;
-  int rc = ctx_scratch_s(c, o_sw + fb_bytes, &scratch);
+  int rc = ctx_scratch(c, o_sw + fb_bytes, &scratch, SCRATCH_SCREEN);
   if (rc != GL_OK) return rc;
   char* s = (char*)scratch;
   ScreenOut so{(float*)(s + o_u), (float*)(s + o_lost), (int32_t*)(s + o_cnt), (int32_t*)(s + o_k0), (float*)(s + o_lo)};

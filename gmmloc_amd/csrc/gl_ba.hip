@@ -19,6 +19,7 @@
 // Control flow = g2o OptimizationAlgorithmLevenberg::solve / SparseOptimizer::
 // optimize + the 5 / gate GMM / 5 / gate reprojection / 40 schedule
 // (localization_opt.cpp:770-828), incl. stale e->chi2() semantics.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -458,45 +459,27 @@ namespace gl {
 bool ba1_fast_supported(int L);
 int launch_ba1_fast(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int L, double* pose,
                     double* pts, const double* obs, const int32_t* oct, int32_t* assoc, const double* d2, double gate,
-                    uint8_t* dropped, uint8_t* erase, int32_t* iters, void* scratch, const uint8_t* prior, const TrackFixed* fixed);
+                    uint8_t* dropped, uint8_t* erase, int32_t* iters, char* scratch, const Ba1Layout& lay, const uint8_t* prior,
+                    const TrackFixed* fixed);
 
 // gl_track_frames_anchored with fixed observer key-frames (gl_ba_gen.hip: the general kernel does those)
 int track_frames_fixed(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm, int B, int M,
                        double* pose_dev, double* Xw_dev, const double* obs_dev, const int32_t* octave_dev, int32_t* assoc_dev,
                        double* d2_dev, const gl_track_anchor* anchor);
 
-// Single-free-pose jointOptimization for B frames; assoc in/out; scratch from ctx.
+// Single-free-pose jointOptimization for B frames; assoc in/out; scratch laid out by ba1_layout(..., fast = false).
 int launch_ba1(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int L, double* pose,
                const uint8_t* has_prior, double* pts, const double* obs, const int32_t* oct, int32_t* assoc,
-               const double* d2, double gate, uint8_t* dropped, uint8_t* erase, int32_t* iters, void* scratch) {
+               const double* d2, double gate, uint8_t* dropped, uint8_t* erase, int32_t* iters, char* scratch, const Ba1Layout& lay) {
   BaK k = make_bak(cam, prm, gate);
   GmmDev gm{g->rec12, g->axis, g->sqrt_info, g->hgw, g->flags, g->plane4};
-  char* s = (char*)scratch;
-  double* pn = (double*)s;
-  s += (size_t)B * L * 24;
-  double* chi = (double*)s;
-  s += (size_t)B * L * 8;
-  uint8_t* lev = (uint8_t*)s;
   {
     TimerScope ts(c, GL_TIMER_BA);
-    k_ba1<<<B, T_BA, 0, c->stream>>>(k, gm, B, L, pose, has_prior, pts, obs, oct, assoc, d2, pn, chi, lev, dropped, erase,
-                                     iters);
+    k_ba1<<<B, T_BA, 0, c->stream>>>(k, gm, B, L, pose, has_prior, pts, obs, oct, assoc, d2, (double*)(scratch + lay.trial),
+                                     (double*)(scratch + lay.chi), (uint8_t*)(scratch + lay.lev), dropped, erase, iters);
   }
   GL_HIP(hipGetLastError());
   return GL_OK;
-}
-
-// fast path: plane records (32 B) + normalised observations (24 B) + permutation, flags, gated association (12 B) per
-// point; general kernel: trial points, chi2, levels (33 B); + per frame: 2 x 4 x 32 x 2 exchange words of the latency
-// shape, 12 doubles of the prior edge's inverse measurement, and for small batches the staging area of the latency shape's
-// results (points 24 B + association 4 B per point, pose 64 B per frame) (gl_ba_fast.hip)
-// F > 0 (fixed observer key-frames on the on-chip path): behind all that, per key-frame its pose {R, t} and per point and
-// key-frame the normalised observation, the octave word and the stale chi2 (96 + L x 36 bytes)
-size_t ba1_scratch_bytes(int B, int L, int F) {
-  size_t n = (size_t)B * L * 36 + (size_t)B * (8192 + 8 + 96) + 512;
-  if ((size_t)B * ((L + 255) / 256) <= 1024) n += (size_t)B * L * 28 + (size_t)B * 64 + 64;  // a batch the latency shape may take: its staging area
-  if (F > 0) n = ((n + 63) / 64) * 64 + (size_t)B * F * (96 + (size_t)L * 36) + 64;
-  return n;
 }
 
 }  // namespace gl
@@ -512,18 +495,22 @@ static int track_frames_impl(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera
   gl::Gmm* g = gl::G(gmm);
   GL_HIP(hipSetDevice(c->device));
   const size_t n = (size_t)B * M;
-  // scratch: [d2 (if the caller does not want it)] [ba1 scratch]; the association kernel's own
-  // partial buffers come from the same context scratch, so carve everything from one block.
-  // Layout: | assoc partials (used first, dead afterwards) ... reused by ba1 | d2 |
-  void* scratch = nullptr;
-  const size_t ba_bytes = gl::ba1_scratch_bytes(B, M, fixed ? fixed->F : 0);
+  // on-chip fast path (gl_ba_fast.hip) for M <= 2000; option ba_slow forces the general kernel
+  const bool fast = (c->opt.ba_slow == 0 || fixed) && gl::ba1_fast_supported(M);
+  gl::Ba1Layout lay;
+  int rc = gl::ba1_layout(c, B, M, fixed ? fixed->F : 0, prior_dev != nullptr, fast, &lay);
+  if (rc != GL_OK) return rc;
   const bool use_grid = g->grid.enabled && c->opt.assoc_grid != 0;
   const size_t assoc_bytes =
       use_grid ? gl::assoc_index_scratch_bytes(g->K, (int)n, d2_dev != nullptr) : gl::assoc_scratch_bytes(g->K, (int)n);
-  const size_t work = ba_bytes > assoc_bytes ? ba_bytes : assoc_bytes;
-  int rc = gl::ctx_scratch(c, work + n * 8 + 64, &scratch);
+  // | association scratch (used first, dead afterwards) ... reused by the refine | d2 (if the caller does not want it) |
+  gl::Regions r{0};
+  r.take(std::max(assoc_bytes, lay.end));
+  const size_t o_d2 = r.take(n * 8);
+  void* scratch = nullptr;
+  rc = gl::ctx_scratch(c, r.off, &scratch);
   if (rc != GL_OK) return rc;
-  double* d2 = d2_dev ? d2_dev : (double*)((char*)scratch + ((work + 63) / 64) * 64);
+  double* d2 = d2_dev ? d2_dev : (double*)((char*)scratch + o_d2);
   // Only chi2 <= 9 survives the gate below, so the points the cell index cannot resolve (minimum
   // above 9) need their exact argmin only when the caller asked for the chi2 values.
   if (use_grid)
@@ -531,12 +518,11 @@ static int track_frames_impl(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera
   else
     rc = gl::launch_assoc_brute(c, g, Xw_dev, (int)n, assoc_dev, d2);
   if (rc != GL_OK) return rc;
-  // on-chip fast path (gl_ba_fast.hip) for M <= 2000; option ba_slow forces the general kernel
-  if ((c->opt.ba_slow == 0 || fixed) && gl::ba1_fast_supported(M))
+  if (fast)
     return gl::launch_ba1_fast(c, g, cam, prm, B, M, pose_dev, Xw_dev, obs_dev, octave_dev, assoc_dev, d2, 9.0,
-                               nullptr, nullptr, nullptr, scratch, prior_dev, fixed);
+                               nullptr, nullptr, nullptr, (char*)scratch, lay, prior_dev, fixed);
   return gl::launch_ba1(c, g, cam, prm, B, M, pose_dev, prior_dev, Xw_dev, obs_dev, octave_dev, assoc_dev, d2, 9.0,
-                        nullptr, nullptr, nullptr, scratch);
+                        nullptr, nullptr, nullptr, (char*)scratch, lay);
 }
 
 extern "C" int gl_track_frames(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm, int B,

@@ -26,9 +26,9 @@ struct PrepView {
 // the normalised observation, octave | stereo << 4 (-1: not observed) and the edge's stale chi2; ferase: the caller's output.
 struct FixedV {
   int F;
-  const double* fRt;   // B x F x 12
-  const double* fobn;  // B x F x L x 3
-  const int32_t* foct; // B x F x L
+  double* fRt;         // B x F x 12
+  double* fobn;        // B x F x L x 3
+  int32_t* foct;       // B x F x L
   double* chif;        // B x F x L
   uint8_t* ferase;     // B x L x F (caller's order) or null
 };
@@ -52,7 +52,7 @@ struct BafKArgs {
   int xcc_trusted;
   const int32_t* oct_all;
   const uint8_t* prior_all;
-  const double* prior_mi;
+  double* prior_mi;
   double* stage;
   int nb_prev;
   int32_t* counters;
@@ -79,45 +79,46 @@ __host__ __device__ inline PrepView prep_view(double* scratch, int B, int L) {
 // a frame instead of in 96 % of its slots (one such lane was enough to make the wave issue ~100 extra instructions per
 // point and pass).  The order is a function of the frame's data alone, so the canonical summation order built on it stays
 // independent of the launch shape and of the batch.
+// A: the refine's arguments (k_ba1_prep writes the records, exchange words, inverse measurements and fixed-observer records they
+// point to); beside them the caller's observations, Mahalanobis distances and fixed-observer inputs, and the frame queue.
 constexpr int PREP_T = 256, PREP_C = 8;  // rounds of 256 consecutive points: frames up to 2 048 points
-__global__ __launch_bounds__(PREP_T) void k_ba1_prep(BaK k, GmmDev gm, int B, int L, const double* __restrict__ obs_all,
-                                                    const int32_t* __restrict__ oct_all, int32_t* __restrict__ assoc_all,
-                                                    const double* __restrict__ d2_all, double* __restrict__ scratch,
-                                                    unsigned long long* __restrict__ xwords, int* __restrict__ xctl, int nxw,
-                                                    const double* __restrict__ pose_all, const uint8_t* __restrict__ prior_all,
-                                                    double* __restrict__ prior_mi, int F, const double* __restrict__ fpose_all,
-                                                    const double* __restrict__ fobs_all, const int32_t* __restrict__ foct_all, double* __restrict__ fRt,
-                                                    double* __restrict__ fobn, int32_t* __restrict__ foct, double* __restrict__ chif, int* __restrict__ frame_ctr) {
+__global__ __launch_bounds__(PREP_T) void k_ba1_prep(BafKArgs A, const double* __restrict__ obs_all, const double* __restrict__ d2_all,
+                                                    gl::TrackFixed fin, int* __restrict__ frame_ctr) {
   __shared__ int cnt[PREP_C][PREP_T / 64];   // non-degenerate-component points per (round, wave)
   __shared__ int cnt0[PREP_C][PREP_T / 64];  // slots WITHOUT a map point per (round, wave) (round 6: they go last, see below)
+  const BaK& k = A.k;
+  const int B = A.B, L = A.L, F = A.fxv.F;
+  const int32_t* const oct_all = A.oct_all;
+  int32_t* const assoc_all = A.assoc_all;
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (f >= B) return;
-  if (frame_ctr && f == 0 && tid == 0) *frame_ctr = 0;  // the queue the refine's persistent workgroups draw their frames from
-  if (xwords) {  // latency shape next: this frame's exchange words and {abort, done} start at zero (no separate memset)
-    for (int i = tid; i < nxw; i += PREP_T) xwords[(size_t)f * nxw + i] = 0ull;
-    if (tid < 2) xctl[2 * f + tid] = 0;
+  if (f == 0 && tid == 0) *frame_ctr = 0;  // the queue the refine's persistent workgroups draw their frames from
+  if (A.parts) {  // latency shape next: this frame's exchange words and {abort, done} start at zero (no separate memset)
+    const int nxw = 2 * A.G * 64;
+    for (int i = tid; i < nxw; i += PREP_T) A.parts[(size_t)f * nxw + i] = 0ull;
+    if (tid < 2) A.ctl[2 * f + tid] = 0;
   }
-  if (prior_all && prior_all[f] && tid == 0) {  // EdgeSE3QuatPrior::_inverseMeasurement of the frame's INPUT pose, as {R, t}
-    const SE3 Ti = se3_inverse(se3_load(pose_all + (size_t)f * 7));
+  if (A.prior_all && A.prior_all[f] && tid == 0) {  // EdgeSE3QuatPrior::_inverseMeasurement of the frame's INPUT pose, as {R, t}
+    const SE3 Ti = se3_inverse(se3_load(A.pose_io + (size_t)f * 7));
     double Ri[9];
     qtoR(Ti.r, Ri);
 #pragma unroll
-    for (int i = 0; i < 9; ++i) prior_mi[(size_t)f * 12 + i] = Ri[i];
+    for (int i = 0; i < 9; ++i) A.prior_mi[(size_t)f * 12 + i] = Ri[i];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) prior_mi[(size_t)f * 12 + 9 + i] = Ti.t[i];
+    for (int i = 0; i < 3; ++i) A.prior_mi[(size_t)f * 12 + 9 + i] = Ti.t[i];
   }
   if (F > 0 && tid < F) {  // the fixed key-frames' poses T_cw as {R, t}
-    const SE3 T = se3_load(fpose_all + ((size_t)f * F + tid) * 7);
+    const SE3 T = se3_load(fin.pose + ((size_t)f * F + tid) * 7);
     double Rm[9];
     qtoR(T.r, Rm);
-    double* o = fRt + ((size_t)f * F + tid) * 12;
+    double* o = A.fxv.fRt + ((size_t)f * F + tid) * 12;
 #pragma unroll
     for (int i = 0; i < 9; ++i) o[i] = Rm[i];
 #pragma unroll
     for (int i = 0; i < 3; ++i) o[9 + i] = T.t[i];
   }
   const size_t gbase = (size_t)f * L;
-  const PrepView pv = prep_view(scratch, B, L);
+  const PrepView pv = prep_view(A.pn_all, B, L);
   const int rounds = (L + PREP_T - 1) / PREP_T;
   // round j, thread t: point j 256 + t (coalesced); index order = (round, wave, lane)
   int a_[PREP_C], fl_[PREP_C];
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(PREP_T) void k_ba1_prep(BaK k, GmmDev gm, int B, in
       if (oc >= 0) {
         fl = 1 | ((oc & 7) << 8);                              // F_EXISTS, octave
         if (!(obs_all[g * 3 + 2] < 0)) fl |= 2;                // F_STEREO
-        if (a >= 0) fl |= 4 | ((gm.flags[a] & 1) ? 8 : 0);     // F_ASSOC, F_DEG
+        if (a >= 0) fl |= 4 | ((A.gm.flags[a] & 1) ? 8 : 0);   // F_ASSOC, F_DEG
       }
       a_[j] = a;
       fl_[j] = fl;
@@ -191,13 +192,13 @@ __global__ __launch_bounds__(PREP_T) void k_ba1_prep(BaK k, GmmDev gm, int B, in
       pv.gobn[gp * 3 + 2] = (obs_all[g * 3 + 2] - k.cx) * ifx;
       for (int kf = 0; kf < F; ++kf) {  // the point's observations by the fixed key-frames, by key-frame, in the permuted order
         const size_t src = g * F + kf, dst = ((size_t)f * F + kf) * L + lp;
-        const int fo = fl_[j] ? foct_all[src] : -1;
-        const double u = fobs_all[src * 3], v = fobs_all[src * 3 + 1], ur = fobs_all[src * 3 + 2];
-        fobn[dst * 3] = (u - k.cx) * ifx;
-        fobn[dst * 3 + 1] = (v - k.cy) * ify;
-        fobn[dst * 3 + 2] = (ur - k.cx) * ifx;
-        foct[dst] = fo < 0 ? -1 : ((fo & 7) | (!(ur < 0) ? 16 : 0));
-        chif[dst] = 0.0;
+        const int fo = fl_[j] ? fin.oct[src] : -1;
+        const double u = fin.obs[src * 3], v = fin.obs[src * 3 + 1], ur = fin.obs[src * 3 + 2];
+        A.fxv.fobn[dst * 3] = (u - k.cx) * ifx;
+        A.fxv.fobn[dst * 3 + 1] = (v - k.cy) * ify;
+        A.fxv.fobn[dst * 3 + 2] = (ur - k.cx) * ifx;
+        A.fxv.foct[dst] = fo < 0 ? -1 : ((fo & 7) | (!(ur < 0) ? 16 : 0));
+        A.fxv.chif[dst] = 0.0;
       }
     }
 #pragma unroll
@@ -305,71 +306,110 @@ static void canon_order(int L, int* G, int* S) {
   *S = (nch + *G - 1) / *G;
 }
 
-typedef void (*BafKernel)(BafKArgs);
-
-struct BafArgs {
-  BaK k;
-  GmmDev gm;
-  int B, L, G, S;
-  double *pose, *pts;
-  const double* obs;
-  const int32_t* oct;
-  int32_t* assoc;
-  const double* d2;
-  uint8_t *dropped, *erase;
-  int32_t* iters;
-  double* pn;
-  int32_t* stats;
-  int32_t* stats_iters = nullptr;
-  int32_t* stats_edges = nullptr;
-  int* fctr = nullptr;  // frame queue of the persistent DENSE workgroups (in the launch scratch, zeroed by k_ba1_prep), or null: plain launch
-  int NB;
-  unsigned long long* parts;
-  int* ctl = nullptr;  // per frame {abort, done} of a latency-shape launch (the follow-up DENSE launch skips the done ones)
-  const uint8_t* prior = nullptr;  // per frame: gauge anchor of the pose (prior edge / fixed), or null
-  const double* prior_mi = nullptr;  // per frame: inverse measurement of the prior edge {R, t} (written by k_ba1_prep)
-  double* stage = nullptr;           // latency shape: staging area of the results {points | pose | association}
-  int nb_prev = 0;                   // follow-up launch: workgroups per frame of the latency-shape launch before it
-  int32_t* counters = nullptr;       // the context's device counters (gl_ctx_counter_read)
-  FixedV fx = {0, nullptr, nullptr, nullptr, nullptr, nullptr};  // fixed observer key-frames (F > 0: the kFixed instances)
+struct BafInst {
+  BafCfg cfg;
+  void (*kern)(BafKArgs);
+  size_t lds;  // dynamic LDS of a workgroup (the carve of ba1_fast_frame)
 };
+static const BafInst kBafInst[] = {
+    {bafd2000::kCfg, bafd2000::k_ba1_fast, bafd2000::kLdsBytes},
+    {bafs::kCfg, bafs::k_ba1_fast, bafs::kLdsBytes},
+    {bafd496::kCfg, bafd496::k_ba1_fast, bafd496::kLdsBytes},
+    {bafd1000::kCfg, bafd1000::k_ba1_fast, bafd1000::kLdsBytes},
+    {bafs32::kCfg, bafs32::k_ba1_fast, bafs32::kLdsBytes},
+    {bafd2000s32::kCfg, bafd2000s32::k_ba1_fast, bafd2000s32::kLdsBytes},
+    {bafd496p::kCfg, bafd496p::k_ba1_fast, bafd496p::kLdsBytes},
+    {bafd1000p::kCfg, bafd1000p::k_ba1_fast, bafd1000p::kLdsBytes},
+    {bafd2000p::kCfg, bafd2000p::k_ba1_fast, bafd2000p::kLdsBytes},
+    {bafsp::kCfg, bafsp::k_ba1_fast, bafsp::kLdsBytes},
+    {bafd496f::kCfg, bafd496f::k_ba1_fast, bafd496f::kLdsBytes},
+    {bafd1000f::kCfg, bafd1000f::k_ba1_fast, bafd1000f::kLdsBytes},
+    {bafd2000f::kCfg, bafd2000f::k_ba1_fast, bafd2000f::kLdsBytes},
+};
+// The instance a launch takes: the flags of the launch, the smallest LDS class that holds the points of a workgroup (DENSE: the
+// frame, SPREAD: one group).  The fixed-observer instances carry the anchored code (the prior is a per-frame flag); the anchored
+// instances exist with the exact step only.
+static const BafInst* baf_instance(const Ctx* c, bool spread, bool prior, int F, int points) {
+  const bool anch = prior || F > 0;
+  const bool s32 = c->opt.ba_step32 != 0 && !anch;
+  const BafInst* best = nullptr;
+  for (const BafInst& in : kBafInst)
+    if (in.cfg.spread == spread && in.cfg.step32 == s32 && in.cfg.prior == anch && in.cfg.fixed == (F > 0) && in.cfg.mcap >= points &&
+        (!best || in.cfg.mcap < best->cfg.mcap))
+      best = &in;
+  return best;
+}
 
-// one workgroup of G waves per frame; LDS class by stride (4 / 2 / 1 frames per CU)
-static int launch_dense(Ctx* c, BafArgs& a) {
-  const bool fixed = a.fx.F > 0;
-  const bool anch = a.prior || fixed;                  // (the fixed-observer instances carry the anchored code: the prior is a per-frame flag)
-  const bool s32 = c->opt.ba_step32 != 0 && !anch;     // (the anchored instances exist with the exact step only)
-  // (the anchored middle classes give 8 / 16 points for the prior edge's LDS records and the key-frames' poses)
-  const int mid = fixed ? 984 : a.prior ? 992 : 1000;
-  const int cap = s32 ? 2000 : (a.L <= 496 ? 496 : a.L <= mid ? mid : 2000);
-  const BafKernel kern = s32 ? bafd2000s32::k_ba1_fast
-                         : fixed ? (cap == 496 ? bafd496f::k_ba1_fast : cap == 984 ? bafd1000f::k_ba1_fast : bafd2000f::k_ba1_fast)
-                         : a.prior ? (cap == 496 ? bafd496p::k_ba1_fast : cap == 992 ? bafd1000p::k_ba1_fast : bafd2000p::k_ba1_fast)
-                                   : (cap == 496 ? bafd496::k_ba1_fast : cap == 1000 ? bafd1000::k_ba1_fast : bafd2000::k_ba1_fast);
-  const int threads = 64 * a.G;
-  const size_t lds = (size_t)(10 * cap + (cap == 496 ? 2 : cap <= 1000 ? 4 : 8) * 32 + 64 + 40 + (anch ? 64 + (cap == 496 ? 108 : 0) : 0) + (fixed ? 48 : 0)) * sizeof(double);
-  GL_HIP(ensure_dynamic_lds(c, (const void*)kern, lds));
-  a.NB = 1;
-  a.parts = nullptr;
-  // persistent workgroups (option ba_persist, default on): as many as the device holds at once, drawing frames from a.fctr
-  int grid = a.B;
-  int* fctr = nullptr;
-  if (c->opt.ba_persist != 0 && a.fctr) {
-    const auto key = std::make_pair((const void*)kern, lds + (size_t)threads);
-    auto hit = c->occupancy.find(key);
-    if (hit == c->occupancy.end()) {
-      int occ = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)kern, threads, lds) != hipSuccess) occ = 0;
-      hit = c->occupancy.emplace(key, occ).first;
+// Shape: SPREAD when every workgroup of the batch gets a CU of its own (B G <= 2 CUs: the frame-at-a-time caller, small
+// batches) and the device holds all of them at once, DENSE otherwise.  Both add in the same order: the choice never shows in
+// the results (option ba_shape forces one: 0 DENSE, 1 SPREAD where it fits).  Then the scratch of that shape: only SPREAD has
+// exchange words and a staging area.  !fast: the general kernel's regions alone.
+int ba1_layout(Ctx* c, int B, int L, int F, bool prior, bool fast, Ba1Layout* out) {
+  int G, S;
+  canon_order(L, &G, &S);
+  bool spread = (long)B * G <= 2 * c->ncu;  // two workgroups of 256 threads fit a CU (LDS 2 x 80 KB, 2 waves per SIMD; checked below)
+  if (c->opt.ba_shape == 0) spread = false;
+  if (c->opt.ba_shape == 1) spread = true;  // forced (tests); a shape that does not fit the device still goes DENSE
+  if (F > 0 || !fast) spread = false;       // (fixed observers: batch-shaped instances only)
+  if (spread) {
+    const BafInst* in = baf_instance(c, true, prior, 0, 64 * S);
+    GL_REQUIRE(in, "no refine instance for this launch");
+    GL_HIP(ensure_dynamic_lds(c, (const void*)in->kern, in->lds));
+    int occ = 0;
+    (void)ctx_occupancy(c, (const void*)in->kern, 256, in->lds, &occ);
+    // ... per XCD: the kernel keeps the workgroups of a frame on ONE XCD (frame f -> XCD f % 8), so what has to fit is the
+    // ceil(B / 8) frames of an XCD into that XCD's share of the slots (a frame whose siblings queue behind the resident
+    // ones would sit in the rendezvous until its time limit and be redone by the follow-up kernel: correct, but slow)
+    spread = (long)((B + 7) / 8) * G <= (long)occ * (c->ncu / 8);
+  }
+  const size_t n = (size_t)B * L;
+  Ba1Layout& o = *out;
+  o = Ba1Layout{};
+  o.spread = spread;
+  Regions r{0};
+  if (!fast) {
+    o.trial = r.take(n * 3 * sizeof(double));
+    o.chi = r.take(n * sizeof(double));
+    o.lev = r.take(n);
+  } else {
+    o.rec = r.take(n * (3 * sizeof(double) + 3 * sizeof(int32_t)));
+    o.frame_ctr = r.take(sizeof(int));
+    o.prior_mi = r.take((size_t)B * 12 * sizeof(double));
+    if (spread) {
+      o.parts = r.take((size_t)B * 2 * G * 64 * sizeof(unsigned long long));
+      o.ctl = r.take((size_t)B * 2 * sizeof(int));
+      o.stage = r.take(n * (3 * sizeof(double) + sizeof(int32_t)) + (size_t)B * 8 * sizeof(double));
     }
-    if (hit->second > 0 && (long)hit->second * c->ncu < (long)a.B) {
-      grid = hit->second * c->ncu;
-      fctr = a.fctr;
+    if (F > 0) {
+      o.frt = r.take((size_t)B * F * 12 * sizeof(double));
+      o.fobn = r.take(n * F * 3 * sizeof(double));
+      o.foct = r.take(n * F * sizeof(int32_t));
+      o.chif = r.take(n * F * sizeof(double));
     }
   }
-  const BafKArgs ka{a.k, a.gm, a.B, a.L, a.G, a.S, a.pose, a.pts, a.assoc, a.dropped, a.erase, a.iters, a.pn, a.stats, a.NB, a.parts, a.ctl, 0ll, 0, a.oct, a.prior,
-                    a.prior_mi, a.stage, a.nb_prev, a.counters, a.stats_iters, a.fx, a.stats_edges, fctr};
-  kern<<<grid, threads, lds, c->stream>>>(ka);
+  o.end = r.off;
+  return GL_OK;
+}
+
+// one workgroup of G waves per frame; LDS class by stride (4 / 2 / 1 frames per CU)
+static int launch_dense(Ctx* c, BafKArgs a, int* frame_ctr) {
+  const BafInst* in = baf_instance(c, false, a.prior_all != nullptr, a.fxv.F, a.L);
+  GL_REQUIRE(in, "no refine instance for this launch");
+  const int threads = 64 * a.G;
+  GL_HIP(ensure_dynamic_lds(c, (const void*)in->kern, in->lds));
+  a.NB = 1;
+  a.parts = nullptr;
+  // persistent workgroups (option ba_persist, default on): as many as the device holds at once, drawing frames from frame_ctr
+  int grid = a.B;
+  if (c->opt.ba_persist != 0) {
+    int occ = 0;
+    (void)ctx_occupancy(c, (const void*)in->kern, threads, in->lds, &occ);
+    if (occ > 0 && (long)occ * c->ncu < (long)a.B) {
+      grid = occ * c->ncu;
+      a.frame_ctr = frame_ctr;
+    }
+  }
+  in->kern<<<grid, threads, in->lds, c->stream>>>(a);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
@@ -381,104 +421,69 @@ static int launch_dense(Ctx* c, BafArgs& a) {
 // frame); the kernel is launched plainly instead, with the rendezvous protocol of gld::Coop: a frame whose workgroups do not
 // all show up within the time limit (another launch holds the CUs and waits for its own) gives up without writing
 // anything, and the one-workgroup kernel that follows redoes exactly those frames - same bits, so the caller never sees
-// which kernel answered.  Returns 1 when the shape does not fit the device at all (the caller goes DENSE).
-static int launch_spread(Ctx* c, BafArgs& a, void* scratch) {
-  const BafKernel kern = a.prior ? bafsp::k_ba1_fast : c->opt.ba_step32 != 0 ? bafs32::k_ba1_fast : bafs::k_ba1_fast;
-  const size_t lds = (size_t)(10 * 256 + 1 * 32 + 64 + 40 + (a.prior ? 64 : 0) + 29 * 256) * sizeof(double);
-  GL_HIP(ensure_dynamic_lds(c, (const void*)kern, lds));
+// which kernel answered.  (ba1_layout has checked that the launch fits the device.)
+static int launch_spread(Ctx* c, BafKArgs a) {
+  const BafInst* in = baf_instance(c, true, a.prior_all != nullptr, 0, 64 * a.S);
+  GL_REQUIRE(in, "no refine instance for this launch");
+  GL_HIP(ensure_dynamic_lds(c, (const void*)in->kern, in->lds));
   a.NB = a.G;
-  {  // all the workgroups of the launch must fit the device at once (the occupancy answer is cached per context)
-    const auto key = std::make_pair((const void*)kern, lds);
-    auto hit = c->occupancy.find(key);
-    if (hit == c->occupancy.end()) {
-      int occ = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)kern, 256, lds) != hipSuccess) occ = 0;
-      hit = c->occupancy.emplace(key, occ).first;
-    }
-    // ... per XCD: the kernel keeps the workgroups of a frame on ONE XCD (frame f -> XCD f % 8), so what has to fit is the
-    // ceil(B / 8) frames of an XCD into that XCD's share of the slots (a frame whose siblings queue behind the resident
-    // ones would sit in the rendezvous until its time limit and be redone by the follow-up kernel: correct, but slow)
-    if ((long)((a.B + 7) / 8) * a.NB > (long)hit->second * (c->ncu / 8)) return 1;
-  }
-  // the exchange words of the frames sit behind the per-point records, {abort, done} per frame behind them
-  a.parts = (unsigned long long*)((char*)scratch + (((size_t)a.B * a.L * 36 + 63) / 64) * 64);
-  a.ctl = (int*)(a.parts + (size_t)a.B * 2 * a.NB * 64);  // (both zeroed by k_ba1_prep)
-  long long limit = (long long)(c->opt.ba_rendezvous_us * 100.0);  // wall_clock64() ticks at 100 MHz
-  if (c->opt.ba_test_abort_seq > 0) limit = -(long long)c->opt.ba_test_abort_seq;  // tests: a give-up in the middle of the schedule
+  a.limit = (long long)(c->opt.ba_rendezvous_us * 100.0);  // wall_clock64() ticks at 100 MHz
+  if (c->opt.ba_test_abort_seq > 0) a.limit = -(long long)c->opt.ba_test_abort_seq;  // tests: a give-up in the middle of the schedule
+  a.xcc_trusted = (c->xcc_ids_trusted && c->opt.ba_same_xcd != 0) ? 1 : 0;
   // (NB > 1: 64 block indices per 8 frames, the kernel's map from block to (frame, group) keeps a frame on one XCD)
   const int grid = a.NB > 1 ? 64 * ((a.B + 7) / 8) : a.B;
-  const BafKArgs ka{a.k, a.gm, a.B, a.L, a.G, a.S, a.pose, a.pts, a.assoc, a.dropped, a.erase, a.iters, a.pn, a.stats, a.NB, a.parts, a.ctl, limit,
-                    (c->xcc_ids_trusted && c->opt.ba_same_xcd != 0) ? 1 : 0, a.oct, a.prior, a.prior_mi, a.stage, 0, a.counters, a.stats_iters, a.fx, a.stats_edges, nullptr};
-  kern<<<grid, 256, lds, c->stream>>>(ka);
+  in->kern<<<grid, 256, in->lds, c->stream>>>(a);
   GL_HIP(hipGetLastError());
-  return a.NB > 1 ? 2 : GL_OK;  // 2: follow up with DENSE for the frames that did not complete
+  return GL_OK;
 }
 
-// Shape: SPREAD when every workgroup of the batch gets a CU of its own (B NB <= CUs: the frame-at-a-time
-// caller, small batches), DENSE otherwise.  Both add in the same order: the choice never shows in the results
-// (option ba_shape forces one: 0 DENSE, 1 SPREAD).
+// scratch: laid out by ba1_layout(..., fast = true)
 int launch_ba1_fast(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int L, double* pose,
                     double* pts, const double* obs, const int32_t* oct, int32_t* assoc, const double* d2, double gate,
-                    uint8_t* dropped, uint8_t* erase, int32_t* iters, void* scratch, const uint8_t* prior, const TrackFixed* fixed) {
-  BafArgs a;
-  a.prior = prior;
-  const int F = fixed ? fixed->F : 0;
-  double *fRt = nullptr, *fobn = nullptr, *chif = nullptr;
-  int32_t* foct = nullptr;
-  if (F > 0) {  // the fixed-observer records sit behind everything else of the launch's scratch (ba1_scratch_bytes)
-    char* fs = (char*)scratch + ((ba1_scratch_bytes(B, L, 0) + 63) / 64) * 64;
-    fRt = (double*)fs;
-    fobn = fRt + (size_t)B * F * 12;
-    chif = fobn + (size_t)B * F * L * 3;
-    foct = (int32_t*)(chif + (size_t)B * F * L);
-    a.fx = FixedV{F, fRt, fobn, foct, chif, fixed->erase};
-  }
+                    uint8_t* dropped, uint8_t* erase, int32_t* iters, char* scratch, const Ba1Layout& lay, const uint8_t* prior,
+                    const TrackFixed* fixed) {
+  BafKArgs a{};
   a.k = make_bak(cam, prm, gate);
   a.gm = GmmDev{g->rec12, g->axis, g->sqrt_info, g->hgw, g->flags, g->plane4};
   a.B = B;
   a.L = L;
   canon_order(L, &a.G, &a.S);
-  a.pose = pose;
-  a.pts = pts;
-  a.obs = obs;
-  a.oct = oct;
-  a.assoc = assoc;
-  a.d2 = d2;
-  a.dropped = dropped;
-  a.erase = erase;
-  a.iters = iters;
-  a.pn = (double*)scratch;
-  a.stats = (c->stats && c->stats_n >= B) ? c->stats : nullptr;
-  a.stats_iters = a.stats ? c->stats_iters : nullptr;
-  a.stats_edges = (c->stats_edges && c->stats_edges_n >= B) ? c->stats_edges : nullptr;
+  a.pose_io = pose;
+  a.pts_io = pts;
+  a.assoc_all = assoc;
+  a.dropped_all = dropped;
+  a.erase_all = erase;
+  a.iters_out = iters;
+  a.pn_all = (double*)(scratch + lay.rec);
+  a.trials_out = (c->stats && c->stats_n >= B) ? c->stats : nullptr;
+  a.NB = 1;
+  a.oct_all = oct;
+  a.prior_all = prior;
+  a.prior_mi = (double*)(scratch + lay.prior_mi);
   a.counters = c->counters;
-  bool spread = (long)B * a.G <= 2 * c->ncu;  // two workgroups of 256 threads fit a CU (LDS 2 x 80 KB, 2 waves per SIMD; checked in launch_spread)
-  if (c->opt.ba_shape == 0) spread = false;
-  if (c->opt.ba_shape == 1) spread = true;  // forced (tests); a shape that does not fit the device still goes DENSE
-  if (F > 0) spread = false;                // (fixed observers: batch-shaped instances only)
+  a.outer_out = a.trials_out ? c->stats_iters : nullptr;
+  if (fixed)
+    a.fxv = FixedV{fixed->F, (double*)(scratch + lay.frt), (double*)(scratch + lay.fobn), (int32_t*)(scratch + lay.foct),
+                   (double*)(scratch + lay.chif), fixed->erase};
+  a.edges_out = (c->stats_edges && c->stats_edges_n >= B) ? c->stats_edges : nullptr;
+  if (lay.spread) {
+    a.parts = (unsigned long long*)(scratch + lay.parts);
+    a.ctl = (int*)(scratch + lay.ctl);
+    a.stage = (double*)(scratch + lay.stage);
+  }
+  int* const frame_ctr = (int*)(scratch + lay.frame_ctr);
   {  // set-up: gate, flags, normalised observations, the order the refine walks each frame in - and, before a latency-shape
      // launch, the zeros its exchange words start from
     TimerScope ts(c, GL_TIMER_BA_PREP);
-    unsigned long long* xw = nullptr;
-    if (spread) xw = (unsigned long long*)((char*)scratch + (((size_t)B * L * 36 + 63) / 64) * 64);
-    const int nxw = 2 * a.G * 64;
-    // inverse measurements of the prior edges: behind the records, the exchange words and {abort, done} (ba1_scratch_bytes)
-    a.prior_mi = (double*)((char*)scratch + (((size_t)B * L * 36 + 63) / 64) * 64 + (size_t)B * (8192 + 8) + 64);
-    a.fctr = (int*)((char*)scratch + (((size_t)B * L * 36 + 63) / 64) * 64 + (size_t)B * (8192 + 8));  // (first word of the 64-byte pad in front of them)
-    if (spread) a.stage = (double*)(a.prior_mi + (size_t)B * 12);  // {points B x L x 3 | pose B x 8 | association B x L}
-    k_ba1_prep<<<B, PREP_T, 0, c->stream>>>(a.k, a.gm, B, L, obs, oct, assoc, d2, (double*)scratch, xw, xw ? (int*)(xw + (size_t)B * nxw) : nullptr, nxw,
-                                            pose, prior, (double*)a.prior_mi, F, F ? fixed->pose : nullptr, F ? fixed->obs : nullptr,
-                                            F ? fixed->oct : nullptr, fRt, fobn, foct, chif, a.fctr);
+    k_ba1_prep<<<B, PREP_T, 0, c->stream>>>(a, obs, d2, fixed ? *fixed : TrackFixed{}, frame_ctr);
   }
   GL_HIP(hipGetLastError());
   TimerScope ts(c, GL_TIMER_BA);  // the refine kernel proper
-  if (spread) {
-    const int rc = launch_spread(c, a, scratch);
-    if (rc <= 0) return rc;
-    if (rc == 1) a.ctl = nullptr;  // shape does not fit: every frame goes DENSE
-    else a.nb_prev = a.NB;         // follow-up: staged results of the complete frames -> the caller's buffers, the others redone
-  }
-  return launch_dense(c, a);
+  if (!lay.spread) return launch_dense(c, a, frame_ctr);
+  const int rc = launch_spread(c, a);
+  if (rc != GL_OK || a.G == 1) return rc;  // (one workgroup per frame: nothing to follow up)
+  a.nb_prev = a.G;  // follow-up: staged results of the complete frames -> the caller's buffers, the others redone
+  return launch_dense(c, a, frame_ctr);
 }
 
 }  // namespace gl

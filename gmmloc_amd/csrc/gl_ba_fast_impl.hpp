@@ -1,5 +1,6 @@
 // (included by gl_ba_fast.hip once per instance: GL_BAF_NS names the namespace, whose kCfg - declared there - holds the
-// instance's parameters; #undefs GL_BAF_NS at the end)
+// instance's parameters; the namespace gives back its kernel k_ba1_fast and the kernel's dynamic LDS kLdsBytes; #undefs
+// GL_BAF_NS at the end)
 // On-chip fast path of the single-pose structure-constrained refinement (same algorithm and control flow as
 // k_ba1 in gl_ba.hip, which stays as the general / large-M path and as the A/B reference), M <= 2000 points.
 //
@@ -1839,6 +1840,23 @@ GL_DEV T ld_karg(const T __attribute__((address_space(4)))* p) {
 // bafd2000f by 55 more instructions).
 GL_DEV bool false_once_inlined() { return false; }
 
+// The dynamic LDS of a frame, in doubles from its start: ba1_fast_frame carves it, the launcher sizes the launch by kLdsBytes.
+// The prior edge's records are followed by the work area of prior_record_wave where this instance has no other: the group
+// totals `red` where they are large enough (4 / 8 groups) - idle during pass B and before the first reduction -, the transpose
+// rows pass B does not use on the latency shape, 108 doubles of its own in the small class (which has LDS to spare).
+constexpr int kPriorWorkOwn = (kPrior && !kSpread && NWC < 4) ? 108 : 0;
+constexpr int kLdsSp = 0;                                             // 3 x MCAP
+constexpr int kLdsChir = kLdsSp + 3 * MCAP;                           // MCAP
+constexpr int kLdsUn = kLdsChir + MCAP;                               // 6 x MCAP
+constexpr int kLdsRed = kLdsUn + 6 * MCAP;                            // NRED x 32
+constexpr int kLdsTot = kLdsRed + NRED * 32;                          // 32 (+ 32 broadcast slots)
+constexpr int kLdsStab = kLdsTot + 64;                                // 24
+constexpr int kLdsRed2 = kLdsStab + 24;                               // 16 (2 x NWC above 8 groups)
+constexpr int kLdsPrec = kLdsRed2 + (NWC > 8 ? 2 * NWC : 16);         // anchored instances: 2 x 32, the prior edge's records
+constexpr int kLdsFrt = kLdsPrec + (kPrior ? 64 : 0) + kPriorWorkOwn;  // fixed-observer instances: F x 12, the key-frames' poses {R, t}
+constexpr int kLdsTb = kLdsFrt + (kFixed ? kMaxFixed * 12 : 0);       // SPREAD: 29 x TSP
+constexpr size_t kLdsBytes = (kLdsTb + (kSpread ? 29 * TSP : 0)) * sizeof(double);
+
 typedef const BafKArgs __attribute__((address_space(4))) kargs_t;
 GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   // the arguments the set-up and the passes use; the caller's OUTPUT arrays are read from the argument segment again where the
@@ -1860,21 +1878,17 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   double* const stage = ka->stage;
   int32_t* const counters = ka->counters;
   Lds D;
-  D.sp = smem;                      // 3 * MCAP
-  D.chir = D.sp + 3 * MCAP;         // MCAP
-  D.un = D.chir + MCAP;             // 6 * MCAP
+  D.sp = smem + kLdsSp;
+  D.chir = smem + kLdsChir;
+  D.un = smem + kLdsUn;
   Red R;
-  R.red = D.un + 6 * MCAP;          // NRED * 32
-  R.tot = R.red + NRED * 32;        // 32 (+ 32 broadcast slots)
-  D.stab = R.tot + 64;              // 24
-  R.red2 = D.stab + 24;             // 16
-  double* const prec = R.red2 + (NWC > 8 ? 2 * NWC : 16); // anchored instances: 2 x 32, the prior edge's records
-  // ... and the work area of prior_record_wave: the group totals `red` where they are large enough (4 / 8 groups) - idle
-  // during pass B and before the first reduction -, the transpose rows pass B does not use on the latency shape, 108 doubles
-  // of its own in the small class (which has LDS to spare)
-  constexpr int kPriorWorkOwn = (kPrior && !kSpread && NWC < 4) ? 108 : 0;
-  D.frt = prec + (kPrior ? 64 : 0) + kPriorWorkOwn;  // fixed-observer instances: F x 12, the key-frames' poses {R, t}
-  R.tb = D.frt + (kFixed ? kMaxFixed * 12 : 0);      // SPREAD: 29 x TSP
+  R.red = smem + kLdsRed;
+  R.tot = smem + kLdsTot;
+  D.stab = smem + kLdsStab;
+  R.red2 = smem + kLdsRed2;
+  double* const prec = smem + kLdsPrec;
+  D.frt = smem + kLdsFrt;
+  R.tb = smem + kLdsTb;
   double* const pwork = kSpread ? R.tb + 2 * TSP : (NWC >= 4 ? R.red : prec + 64);
   D.F = 0;
   D.Lf = L;

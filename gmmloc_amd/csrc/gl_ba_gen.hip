@@ -2743,16 +2743,6 @@ struct BaBatch {
   }
 };
 
-// consecutive 256-aligned regions of a scratch block from `off` on
-struct Regions {
-  size_t off;
-  size_t take(size_t bytes) {  // the offset of the next region
-    const size_t at = off;
-    off += ((bytes + 255) / 256) * 256;
-    return at;
-  }
-};
-
 size_t ba_gen_scratch_bytes(int B, int P, int F, int L, int NOBS) {
   return (size_t)B * 512 + gen_scratch_bytes(P, F, L, NOBS) * B;
 }
@@ -2774,16 +2764,9 @@ int launch_ba_gen(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* p
   // cooperative launch enforces it), at most 64; large batches run one workgroup per problem
   int NB = 1, bsub = B;
   {
-    // the occupancy query is a driver call: the context (one device, one host thread) remembers it per LDS size
-    auto key = std::make_pair((const void*)k_ba_gen, lds);
-    auto hit = c->occupancy.find(key);
-    if (hit == c->occupancy.end()) {
-      int occ_val = 0;
-      GL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_val, (const void*)k_ba_gen, T_BA, lds));
-      hit = c->occupancy.emplace(key, occ_val).first;
-    }
-    const int occ = hit->second, ncu = c->ncu;
-    const long cap = (long)occ * ncu;
+    int occ = 0;
+    GL_HIP(ctx_occupancy(c, (const void*)k_ba_gen, T_BA, lds, &occ));
+    const long cap = (long)occ * c->ncu;
     // measured optimum on single problems (tools/ba_nb.py), with up to 4 lanes per point in the
     // point passes and up to 4 waves per reduced-camera block: one workgroup up to ~600 observations (no
     // cross-workgroup barrier at all), 8 up to 2 000, 16 up to 6 000, 32 up to 16 000, 64 above; NOBS (the

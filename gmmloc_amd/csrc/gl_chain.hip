@@ -275,8 +275,8 @@ int chain_scratch(gl::Ctx* c, int B, int NF, int NP, ChainScratch* S) {
   auto up = [](size_t v) { return ((v + 255) / 256) * 256; };
   const int MC = gl::pose_compact_stride((int)c->opt.pose_compact, NF, (int)c->opt.pose_compact_cap);
   void* scratch = nullptr;
-  const int rc = gl::ctx_scratch_c(c, 2 * up(nf * 24) + 3 * up(nf * 4) + 2 * up(nf) + up(np) + up((size_t)B * 24) + up((size_t)B * 56) + 4 * up((size_t)B * 4) +
-                                       (MC ? gl::pose_compacted_bytes(B, NF, MC) : 0), &scratch);
+  const int rc = gl::ctx_scratch(c, 2 * up(nf * 24) + 3 * up(nf * 4) + 2 * up(nf) + up(np) + up((size_t)B * 24) + up((size_t)B * 56) + 4 * up((size_t)B * 4) +
+                                 (MC ? gl::pose_compacted_bytes(B, NF, MC) : 0), &scratch, gl::SCRATCH_CHAIN);
   if (rc != GL_OK) return rc;
   char* s = (char*)scratch;
   auto take = [&](size_t bytes) {

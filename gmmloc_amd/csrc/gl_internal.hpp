@@ -5,6 +5,7 @@
 
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "gmmloc_hip.h"
@@ -138,6 +139,22 @@ struct Options {
 // name -> member; nullptr if unknown
 double* option_slot(Options& o, const char* name);
 
+// a device block of a context, grown on demand (ctx_scratch)
+struct ScratchBlock {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+// the context's blocks: separate because their callers hold one while they use another
+enum {
+  SCRATCH_MAIN,    // the entry points' own scratch
+  SCRATCH_CACHE,   // the matchers' candidate cache (gl_search_local_points keeps the projection loop's outputs in the main block
+                   // and hands them to gl_search_by_projection)
+  SCRATCH_CHAIN,   // the intermediates of gl_track_frame_chain, whose stages use the two blocks above
+  SCRATCH_SCREEN,  // the screened association's per-split candidate lists and its fp64 fallback (launch_assoc_screened), so
+                   // that it needs nothing from the block its caller sized for the fp64 sweep
+  SCRATCH_COUNT
+};
+
 struct Ctx {
   int device = 0;
   int ncu = 256;  // compute units of the device (shape decisions: frames vs CUs)
@@ -146,21 +163,13 @@ struct Ctx {
   // per-context (= per device, per host thread) caches of driver queries: the dynamic-LDS limit already set
   // for a kernel (hipFuncSetAttribute is per device) and occupancy answers
   std::map<const void*, size_t> lds_limit;
-  std::map<std::pair<const void*, size_t>, int> occupancy;
+  std::map<std::tuple<const void*, int, size_t>, int> occupancy;  // (kernel, threads, dynamic LDS) -> blocks per CU
   hipStream_t stream = nullptr;
   bool own_stream = false;
   // the device reports its XCC id per workgroup and places block b on XCD b % 8 (probed once at gl_ctx_create): the
   // latency-shape kernels may then use the same-XCD form of their exchange - after checking the ids again at run time
   bool xcc_ids_trusted = false;
-  // scratch (grown on demand)
-  void* scratch = nullptr;
-  size_t scratch_bytes = 0;
-  void* scratch_b = nullptr;  // second block (ctx_scratch_b): the matchers' candidate cache
-  size_t scratch_b_bytes = 0;
-  void* scratch_s = nullptr;  // fourth block (ctx_scratch_s): the screened sweep's partial lists, whatever block its caller passed
-  size_t scratch_s_bytes = 0;
-  void* scratch_c = nullptr;  // third block (ctx_scratch_c): the intermediates of gl_track_frame_chain, whose stages use the other two
-  size_t scratch_c_bytes = 0;
+  ScratchBlock scratch[SCRATCH_COUNT];
   // staging of the frame-at-a-time host entry point (gl_track_frame_host): page-locked + device mirror, grown on demand
   void* host_stage = nullptr;
   void* dev_stage = nullptr;
@@ -186,10 +195,17 @@ struct Ctx {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
 };
 
-int ctx_scratch(Ctx* c, size_t bytes, void** out);
-int ctx_scratch_b(Ctx* c, size_t bytes, void** out);
-int ctx_scratch_c(Ctx* c, size_t bytes, void** out);
-int ctx_scratch_s(Ctx* c, size_t bytes, void** out);
+// block `which` (SCRATCH_*) of at least `bytes`; growing it waits for the stream and drops the old contents
+int ctx_scratch(Ctx* c, size_t bytes, void** out, int which = SCRATCH_MAIN);
+// consecutive 256-aligned regions of a scratch block from `off` on
+struct Regions {
+  size_t off;
+  size_t take(size_t bytes) {  // the offset of the next region
+    const size_t at = off;
+    off += ((bytes + 255) / 256) * 256;
+    return at;
+  }
+};
 bool probe_xcc_ids(Ctx* c);  // gl_ba_fast.hip
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE and costs a driver call: a context (one device,
 // one host thread) remembers the limit it has set for each kernel and raises it only when it grows.  The caller
@@ -200,6 +216,22 @@ inline hipError_t ensure_dynamic_lds(Ctx* c, const void* kernel, size_t bytes) {
   const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e == hipSuccess) have = bytes;
   return e;
+}
+// blocks of `kernel` a CU holds at once with `threads` threads and `lds` bytes of dynamic LDS (0 when the query fails): a driver
+// call, remembered by the context
+inline hipError_t ctx_occupancy(Ctx* c, const void* kernel, int threads, size_t lds, int* occ) {
+  const auto key = std::make_tuple(kernel, threads, lds);
+  auto hit = c->occupancy.find(key);
+  if (hit == c->occupancy.end()) {
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, kernel, threads, lds);
+    if (e != hipSuccess) {
+      *occ = 0;
+      return e;
+    }
+    hit = c->occupancy.emplace(key, *occ).first;
+  }
+  *occ = hit->second;
+  return hipSuccess;
 }
 // bracket a launch region with events when timing is enabled
 struct TimerScope {
@@ -225,7 +257,25 @@ struct TrackFixed {
   const int32_t* oct;   // B x M x F
   uint8_t* erase;       // B x M x F out, or null
 };
-size_t ba1_scratch_bytes(int B, int L, int F);
+// The launch scratch of the per-frame refine (gl_track_frames*): the shape it runs in and the byte offset of each region.
+// ba1_layout (gl_ba_fast.hip) decides the shape first and lays out only what that shape uses.
+struct Ba1Layout {
+  bool spread;  // the on-chip path's latency shape (SPREAD, then DENSE for the frames it did not complete)
+  // general kernel (k_ba1), per point: trial point (3 doubles), chi2, level (1 byte)
+  size_t trial, chi, lev;
+  // on-chip path, from the start again (a launch runs one of the two kernels): per point the records of k_ba1_prep
+  // (prep_view: 36 B); the frame queue of the persistent DENSE workgroups (an int); per frame the prior edge's inverse
+  // measurement {R, t} (12 doubles)
+  size_t rec, frame_ctr, prior_mi;
+  // latency shape only: per frame 2 G x 64 exchange words and {abort, done}; the staging area of its results
+  // {points B x L x 3 | pose B x 8 | association B x L}, whose inner split the kernel keeps
+  size_t parts, ctl, stage;
+  // fixed observer key-frames (F > 0, FixedV): per frame and key-frame its pose {R, t}; per point and key-frame the normalised
+  // observation, octave | stereo << 4, stale chi2
+  size_t frt, fobn, foct, chif;
+  size_t end;
+};
+int ba1_layout(Ctx* c, int B, int L, int F, bool prior, bool fast, Ba1Layout* out);
 
 // launchers implemented across the .hip files
 int launch_build_components(Ctx* c, Gmm* g);
@@ -259,7 +309,7 @@ size_t assoc_scratch_bytes(int K, int N, bool listed = false);
 // thread its point tiles, K splits and Gaussians per split
 inline int sweep_points(int N, bool listed) { return listed ? (N / 16 > 256 ? N / 16 : 256) : N; }
 void sweep_split(int K, int N, bool listed, int ppt, int* ptiles, int* nsplit, int* kchunk);
-// (gl_assoc32.hip) the fp32-screened sweep: same arguments and results as launch_assoc_sweep, own scratch (ctx_scratch_s)
+// (gl_assoc32.hip) the fp32-screened sweep: same arguments and results as launch_assoc_sweep, own scratch (SCRATCH_SCREEN)
 int build_screen_records(Ctx* c, Gmm* g);
 int launch_assoc_screened(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,
                           const int32_t* count_dev);

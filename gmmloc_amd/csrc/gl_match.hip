@@ -923,7 +923,7 @@ int launch_match(int mode, gl_ctx_t* ctx, const gl_camera* cam, float scale_fact
   GL_HIP(gl::ensure_dynamic_lds(c, (const void*)kern, lds));
   void* cache = nullptr;  // 16 bytes per query: its three best candidates of round 1 (the kernel's header)
   {
-    const int rc = gl::ctx_scratch_b(c, (size_t)B * NP * sizeof(uint4), &cache);
+    const int rc = gl::ctx_scratch(c, (size_t)B * NP * sizeof(uint4), &cache, gl::SCRATCH_CACHE);
     if (rc != GL_OK) return rc;
   }
   kern<<<B, dl ? 1024 : T_M, lds, c->stream>>>(P, B, feat_uv, feat_ur, feat_oct, feat_desc, feat_taken, mp_uvr, mp_level, mp_viewcos,

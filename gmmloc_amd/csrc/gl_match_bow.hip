@@ -370,7 +370,7 @@ int gl::launch_bow_gated(gl_ctx_t* ctx, float nn_ratio, int check_orientation, i
   GL_HIP(gl::ensure_dynamic_lds(c, (const void*)k_search_by_bow, lds));
   void* cache = nullptr;  // 16 bytes per query: its three best partners of round 1
   {
-    const int rc = gl::ctx_scratch_b(c, (size_t)B * N1 * sizeof(uint4), &cache);
+    const int rc = gl::ctx_scratch(c, (size_t)B * N1 * sizeof(uint4), &cache, gl::SCRATCH_CACHE);
     if (rc != GL_OK) return rc;
   }
   k_search_by_bow<<<B, T_B, lds, c->stream>>>(B, N1, N2, NN1, NN2, nn_ratio, check_orientation, angle1_dev, desc1_dev, has_mp1_dev, nnode1_dev,

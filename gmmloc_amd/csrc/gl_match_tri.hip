@@ -553,7 +553,7 @@ extern "C" int gl_search_for_triangulation(gl_ctx_t* ctx, float scale_factor, in
   GL_HIP(gl::ensure_dynamic_lds(c, (const void*)k_search_for_triangulation, lds));
   void* cache = nullptr;  // 16 bytes per query: its three best partners of round 1 (the kernel's round loop)
   {
-    const int rc = gl::ctx_scratch_b(c, (size_t)B * N1 * sizeof(uint4), &cache);
+    const int rc = gl::ctx_scratch(c, (size_t)B * N1 * sizeof(uint4), &cache, gl::SCRATCH_CACHE);
     if (rc != GL_OK) return rc;
   }
   k_search_for_triangulation<<<B, T_T, lds, c->stream>>>(P, B, uv1_dev, ur1_dev, oct1_dev, angle1_dev, desc1_dev, has_mp1_dev, nnode1_dev,

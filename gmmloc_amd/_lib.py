@@ -23,6 +23,17 @@ class gl_track_anchor(C.Structure):
                 ("fixed_oct_dev", C.c_void_p), ("fixed_erase_dev", C.c_void_p)]
 
 
+class gl_map_view(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("NMP", "NKF", "NFK", "NOBS")] +
+                [(k, C.c_void_p) for k in ("mp_valid", "obs_ptr", "obs_kf", "kf_valid", "kf_mp", "mp_pos", "mp_normal", "mp_max_dist",
+                                           "mp_min_dist", "mp_desc")])
+
+
+class gl_local_map_io(C.Structure):
+    _fields_ = ([("last_mp", C.c_void_p), ("kf_feat_mp", C.c_void_p), ("feat_mp", C.c_void_p), ("KFcap", C.c_int32), ("reserved_", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("local_kf", "n_local_kf", "local_mp", "n_local_mp", "ref_kf", "kf_count", "status")])
+
+
 _lib = None
 
 
@@ -85,6 +96,8 @@ def load():
         "gl_track_frame_chain": (i32, [vp, vp, vp, C.c_float, i32, i32, i32, i32, vp, C.c_float, C.c_float, C.c_float, i32]),
         "gl_track_frame_chain_front": (i32, [vp, vp, vp, C.c_float, i32, i32, i32, i32, vp, C.c_float, i32]),
         "gl_track_frame_chain_back": (i32, [vp, vp, vp, C.c_float, i32, i32, i32, i32, vp, C.c_float, C.c_float]),
+        "gl_update_local_map": (i32, [vp, vp, i32, i32, i32, i32] + [vp] * 8),
+        "gl_track_frame_chain_map": (i32, [vp, vp, vp, C.c_float, i32, i32, i32, i32, vp, vp, vp, C.c_float, C.c_float, C.c_float, i32]),
         "gl_search_local_points": (i32, [vp, vp, C.c_float, i32, i32, i32] + [vp] * 13 + [C.c_float, C.c_float, vp, vp, vp]),
         "gl_gather_triangulation_matches": (i32, [vp, i32, i32, i32, i32, i32] + [vp] * 32),
         "gl_optimize_point": (i32, [vp, vp, P(gl_camera), P(gl_params), i32] + [vp] * 10),

@@ -570,10 +570,10 @@ def _chain_io(a, out):
     return io
 
 
-def _chain_out(a, front_only=False):
+def _chain_out(a, front_only=False, NP=None):
     import torch
     B, NF = a["feat_oct"].shape
-    NP = a["mp_cand"].shape[1]
+    NP = a["mp_cand"].shape[1] if NP is None else NP
     dev = a["feat_oct"].device
     i32 = lambda *sh: torch.full(sh, -1, dtype=torch.int32, device=dev)
     out = dict(pose=a["pose_cw"].clone(), pose_mm=torch.empty((B, 7), dtype=torch.float64, device=dev), match_last=i32(B, NF),
@@ -639,6 +639,165 @@ def track_frame_chain_back(ctx, cam, prm, a, out, th_local=3.0, nn_ratio=0.8, sc
     try:
         _check(ctx.lib.gl_track_frame_chain_back(ctx.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), B, NF, NL, NP, C.byref(io),
                                                  float(th_local), float(nn_ratio)))
+    finally:
+        ctx._exit()
+    return out
+
+
+# The whole map as device arrays (gl_map_view): what update_map_points reads and writes + the key-frames' mappoints_ table.
+MAP_VIEW_DTYPES = {"mp_valid": "uint8", "obs_ptr": "int32", "obs_kf": "int32", "kf_valid": "uint8", "kf_mp": "int32", "mp_pos": "float64",
+                   "mp_normal": "float64", "mp_max_dist": "float32", "mp_min_dist": "float32", "mp_desc": "uint8"}
+MAP_VIEW_POINT_KEYS = ("mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc")
+LOCAL_MAP_STATUS_KEPT, LOCAL_MAP_STATUS_MP_TRUNCATED, LOCAL_MAP_STATUS_KF_TRUNCATED = 1, 2, 4
+
+
+def _tensor(name, t, dtype, shape, device):
+    """`t` is a contiguous CUDA tensor of that dtype and shape (None in the shape: any extent) on `device` - or raise."""
+    assert t is not None, "%s: missing" % name
+    assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch." + dtype, \
+        "%s: expected a contiguous CUDA %s tensor, got %s%s" % (name, dtype, t.dtype, "" if t.is_contiguous() else " (not contiguous)")
+    assert device is None or t.device == device, "%s: on %s, expected %s" % (name, t.device, device)
+    assert t.dim() == len(shape) and all(w is None or int(w) == int(h) for w, h in zip(shape, t.shape)), \
+        "%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape))
+    return t
+
+
+def _map_view(m, need_points):
+    """dict of CUDA tensors -> (gl_map_view, device).  Keys of MAP_VIEW_DTYPES; mp_valid / kf_valid optional (all valid); the per-point
+    arrays only where `need_points`."""
+    for k in m:
+        assert k in MAP_VIEW_DTYPES, "map[%r]: unknown key" % k
+    dev = _tensor("map['obs_ptr']", m.get("obs_ptr"), "int32", (None,), None).device
+    NMP = m["obs_ptr"].shape[0] - 1
+    assert NMP >= 0, "map['obs_ptr']: needs NMP + 1 entries"
+    _tensor("map['obs_kf']", m.get("obs_kf"), "int32", (None,), dev)
+    _tensor("map['kf_mp']", m.get("kf_mp"), "int32", (None, None), dev)
+    NKF, NFK = m["kf_mp"].shape
+    if m.get("mp_valid") is not None:
+        _tensor("map['mp_valid']", m["mp_valid"], "uint8", (NMP,), dev)
+    if m.get("kf_valid") is not None:
+        _tensor("map['kf_valid']", m["kf_valid"], "uint8", (NKF,), dev)
+    shapes = {"mp_pos": (NMP, 3), "mp_normal": (NMP, 3), "mp_max_dist": (NMP,), "mp_min_dist": (NMP,), "mp_desc": (NMP, 32)}
+    for k in MAP_VIEW_POINT_KEYS:
+        if need_points or m.get(k) is not None:
+            _tensor("map[%r]" % k, m.get(k), MAP_VIEW_DTYPES[k], shapes[k], dev)
+    v = _lib.gl_map_view()
+    v.NMP, v.NKF, v.NFK, v.NOBS = NMP, NKF, NFK, m["obs_kf"].shape[0]
+    for k in MAP_VIEW_DTYPES:
+        setattr(v, k, _ptr(m[k]) if m.get(k) is not None else None)
+    return v, dev
+
+
+def local_map_lists(B, KFcap, NPcap, NKF=None, device="cuda"):
+    """The in/out lists of update_local_map / track_frame_chain_map for B frames, empty (a tracker keeps them from frame to frame):
+    dict(local_kf (B,KFcap), n_local_kf (B,), local_mp (B,NPcap), n_local_mp (B,), ref_kf (B,) = -1, status (B,)[, kf_count (B,NKF)])."""
+    import torch
+    z = lambda *sh: torch.zeros(sh, dtype=torch.int32, device=device)
+    lists = dict(local_kf=torch.full((B, KFcap), -1, dtype=torch.int32, device=device), n_local_kf=z(B),
+                 local_mp=torch.full((B, NPcap), -1, dtype=torch.int32, device=device), n_local_mp=z(B),
+                 ref_kf=torch.full((B,), -1, dtype=torch.int32, device=device), status=z(B))
+    if NKF is not None:
+        lists["kf_count"] = z(B, NKF)
+    return lists
+
+
+def _check_lists(lists, B, NKF, dev):
+    for k in lists:
+        assert k in ("local_kf", "n_local_kf", "local_mp", "n_local_mp", "ref_kf", "status", "kf_count"), "lists[%r]: unknown key" % k
+    _tensor("lists['local_kf']", lists.get("local_kf"), "int32", (B, None), dev)
+    _tensor("lists['local_mp']", lists.get("local_mp"), "int32", (B, None), dev)
+    for k in ("n_local_kf", "n_local_mp", "ref_kf", "status"):
+        _tensor("lists[%r]" % k, lists.get(k), "int32", (B,), dev)
+    if lists.get("kf_count") is not None:
+        _tensor("lists['kf_count']", lists["kf_count"], "int32", (B, NKF), dev)
+    KFcap, NPcap = lists["local_kf"].shape[1], lists["local_mp"].shape[1]
+    return KFcap, NPcap
+
+
+def update_local_map(ctx, map, feat_mp, lists):
+    """gl_update_local_map: Tracking::updateLocalMap (tracking.cpp:119-207) for B frames on the device (rules, reproduced quirks and
+    the canonical order: gmmloc_hip.h).  `map`: dict of CUDA tensors, the whole map - obs_ptr (NMP+1,) / obs_kf (NOBS,) i32 (the CSR of
+    update_map_points), kf_mp (NKF,NFK) i32 (a key-frame's mappoints_ as map-point rows, -1 null), optionally mp_valid (NMP,) /
+    kf_valid (NKF,) u8.  feat_mp (B,NF) i32: the map-point row each feature holds, -1 none - IN/OUT (an invalid point's entry becomes
+    -1).  `lists`: the dict of local_map_lists, IN/OUT (a frame with an empty counter keeps what it holds); returned."""
+    v, dev = _map_view(map, False)
+    _tensor("feat_mp", feat_mp, "int32", (None, None), dev)
+    B, NF = feat_mp.shape
+    KFcap, NPcap = _check_lists(lists, B, v.NKF, dev)
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_update_local_map(ctx.h, C.byref(v), B, NF, KFcap, NPcap, _ptr(feat_mp), _ptr(lists["local_kf"]),
+                                           _ptr(lists["n_local_kf"]), _ptr(lists["local_mp"]), _ptr(lists["n_local_mp"]),
+                                           _ptr(lists["ref_kf"]), _ptr(lists.get("kf_count")), _ptr(lists["status"])))
+    finally:
+        ctx._exit()
+    return lists
+
+
+CHAIN_MAP_IGNORED = ("mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_cand", "mp_desc", "last_to_local", "kf_to_local")
+
+
+def track_frame_chain_map(ctx, cam, prm, a, map, lm, th_mm=7.0, th_local=3.0, nn_ratio=0.8, mono=False, scale_factor=1.2):
+    """gl_track_frame_chain_map: the tracked frame in Tracking::track's own sequence as ONE call - stages 1, 2, 2b, updateLocalMap on
+    the device, stages 3, 4 on the local map it made.  `a`: the inputs of track_frame_chain WITHOUT the local map (the keys of
+    CHAIN_MAP_IGNORED are not read; absent is fine); `map`: the whole map (update_local_map's keys + mp_pos (NMP,3) f64, mp_normal
+    (NMP,3) f64, mp_max_dist / mp_min_dist (NMP,) f32, mp_desc (NMP,32) u8); `lm`: dict(last_mp (B,NL) i32, [kf_feat_mp (B,NK) i32 with
+    the fallback,] + the lists of local_map_lists, IN/OUT).  Returns the dict of track_frame_chain (match_local indexes
+    lm['local_mp']; inview is (B,NPcap)) + feat_mp (B,NF)."""
+    import torch
+    dev = _tensor("a['feat_oct']", a.get("feat_oct"), "int32", (None, None), None).device
+    B, NF = a["feat_oct"].shape
+    _tensor("a['last_oct']", a.get("last_oct"), "int32", (B, None), dev)
+    NL = a["last_oct"].shape[1]
+    fbk = a.get("kf_desc") is not None
+    NK = a["kf_desc"].shape[1] if fbk else 0
+    shapes = {"feat_uv": (B, NF, 2), "feat_ur": (B, NF), "feat_oct": (B, NF), "feat_angle": (B, NF), "feat_desc": (B, NF, 32), "feat_taken": (B, NF),
+              "pose_lw": (B, 7), "last_pt": (B, NL, 3), "last_valid": (B, NL), "last_oct": (B, NL), "last_angle": (B, NL), "last_desc": (B, NL, 32),
+              "pose_cw": (B, 7), "last_observed": (B, NL), "kf_angle": (B, NK), "kf_desc": (B, NK, 32), "kf_has_mp": (B, NK), "kf_nnode": (B,),
+              "kf_node_id": (B, None), "kf_node_ptr": (B, None), "kf_node_idx": (B, NK), "kf_pt": (B, NK, 3), "feat_nnode": (B,),
+              "feat_node_id": (B, None), "feat_node_ptr": (B, None), "feat_node_idx": (B, NF)}
+    for k, dt in CHAIN_DTYPES.items():
+        if k not in CHAIN_MAP_IGNORED:
+            _tensor("a[%r]" % k, a.get(k), dt, shapes[k], dev)
+    for k, dt in CHAIN_OPT_DTYPES.items():
+        if k in CHAIN_MAP_IGNORED:
+            continue
+        if k == "last_observed":
+            if a.get(k) is not None:
+                _tensor("a[%r]" % k, a[k], dt, shapes[k], dev)
+        elif fbk:
+            _tensor("a[%r]" % k, a.get(k), dt, shapes[k], dev)
+        else:
+            assert a.get(k) is None, "a[%r] without a['kf_desc'] (the fallback needs all of its buffers)" % k
+    if fbk:
+        assert a["kf_node_ptr"].shape[1] == a["kf_node_id"].shape[1] + 1 and a["feat_node_ptr"].shape[1] == a["feat_node_id"].shape[1] + 1, \
+            "node_ptr needs one entry more than node_id"
+    v, mdev = _map_view(map, True)
+    assert mdev == dev, "the map is on %s, the frames on %s" % (mdev, dev)
+    assert v.NMP >= 1, "empty map"
+    lists = {k: t for k, t in lm.items() if k not in ("last_mp", "kf_feat_mp")}
+    KFcap, NPcap = _check_lists(lists, B, v.NKF, dev)
+    _tensor("lm['last_mp']", lm.get("last_mp"), "int32", (B, NL), dev)
+    if fbk:
+        _tensor("lm['kf_feat_mp']", lm.get("kf_feat_mp"), "int32", (B, NK), dev)
+    out = _chain_out(a, NP=NPcap)
+    out["feat_mp"] = torch.full((B, NF), -1, dtype=torch.int32, device=dev)
+    io = _ChainIO()
+    for k in CHAIN_FIELDS + CHAIN_FIELDS2A + CHAIN_FIELDS2B:
+        if k in CHAIN_MAP_IGNORED:
+            continue
+        t = out["pose"] if k == "pose_cw" else (out[k] if k in out else a.get(k))
+        setattr(io, k, _ptr(t) if t is not None else None)
+    if fbk:
+        io.NK, io.NNK, io.NNF = NK, a["kf_node_id"].shape[1], a["feat_node_id"].shape[1]
+    l = _lib.gl_local_map_io()
+    l.last_mp, l.kf_feat_mp, l.feat_mp, l.KFcap = _ptr(lm["last_mp"]), _ptr(lm["kf_feat_mp"]) if fbk else None, _ptr(out["feat_mp"]), KFcap
+    for k in ("local_kf", "n_local_kf", "local_mp", "n_local_mp", "ref_kf", "kf_count", "status"):
+        setattr(l, k, _ptr(lists[k]) if lists.get(k) is not None else None)
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_track_frame_chain_map(ctx.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), B, NF, NL, NPcap, C.byref(io),
+                                                C.byref(v), C.byref(l), float(th_mm), float(th_local), float(nn_ratio), int(bool(mono))))
     finally:
         ctx._exit()
     return out

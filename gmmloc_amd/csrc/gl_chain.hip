@@ -492,3 +492,61 @@ extern "C" int gl_track_frame_chain_back(gl_ctx_t* ctx, const gl_camera* cam, co
   if (rc != GL_OK) return rc;
   return chain_back(ctx, cam, prm, scale_factor, B, NF, NL, NP, io, th_local, nn_ratio, S, io->drop_src, io->drop_kf, false);
 }
+
+// The chain with Tracking::updateLocalMap (tracking.cpp:119-207) between its halves, on the device (gl_localmap.hip): front as it is,
+// one launch that makes feat_mp from the front's associations and the lists from it, one that gathers the local-map arrays the back
+// reads (a copy of the caller's io with those pointers set to the context's scratch), back as it is.
+extern "C" int gl_track_frame_chain_map(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* prm, float scale_factor, int B, int NF, int NL, int NPcap,
+                                        const gl_track_chain_io* io, const gl_map_view* map, const gl_local_map_io* lm, float th_mm, float th_local,
+                                        float nn_ratio, int mono) {
+  GL_REQUIRE(ctx && cam && prm && io && map && lm, "null argument");
+  GL_REQUIRE(B >= 0 && NF >= 1 && NL >= 1 && NPcap >= 1, "bad B / NF / NL / NPcap");
+  const gl::LocalMapLists L = {lm->KFcap, NPcap, lm->feat_mp, lm->local_kf, lm->n_local_kf, lm->local_mp, lm->n_local_mp, lm->ref_kf, lm->kf_count, lm->status};
+  int rc = gl::local_map_check(map, B, NF, L, true);
+  if (rc != GL_OK || B == 0) return rc;
+  const bool fbk = chain_has_fallback(io);
+  GL_REQUIRE(lm->last_mp && (!fbk || lm->kf_feat_mp), "null last_mp / kf_feat_mp");
+  GL_REQUIRE(map->NMP >= 1, "empty map");
+  // (for the check alone: the pointers the chain ignores stand in for themselves until the scratch is there)
+  gl_track_chain_io io2 = *io;
+  io2.mp_pos = map->mp_pos;
+  io2.mp_normal = map->mp_normal;
+  io2.mp_max_dist = map->mp_max_dist;
+  io2.mp_min_dist = map->mp_min_dist;
+  io2.mp_desc = map->mp_desc;
+  io2.mp_cand = map->mp_desc;
+  io2.last_to_local = lm->last_mp;
+  io2.kf_to_local = lm->kf_feat_mp;
+  rc = chain_check(ctx, cam, prm, B, NF, NL, NPcap, &io2);
+  if (rc != GL_OK) return rc;
+  gl::Ctx* c = gl::C(ctx);
+  GL_HIP(hipSetDevice(c->device));
+  ChainScratch S;
+  rc = chain_scratch(c, B, NF, NPcap, &S);
+  if (rc != GL_OK) return rc;
+  const int NK = fbk ? io->NK : 0;
+  const size_t gbytes = gl::local_map_gathered_place(nullptr, B, NPcap, NL, NK, nullptr);
+  void* scratch = nullptr;
+  rc = gl::ctx_scratch(c, gbytes + gl::local_map_scratch_bytes(c, map, B, lm->kf_count != nullptr), &scratch, gl::SCRATCH_LOCALMAP);
+  if (rc != GL_OK) return rc;
+  gl::LocalMapGathered G;
+  gl::local_map_gathered_place(scratch, B, NPcap, NL, NK, &G);
+  io2.mp_pos = G.mp_pos;
+  io2.mp_normal = G.mp_normal;
+  io2.mp_max_dist = G.mp_max_dist;
+  io2.mp_min_dist = G.mp_min_dist;
+  io2.mp_desc = G.mp_desc;
+  io2.mp_cand = G.mp_cand;
+  io2.last_to_local = G.last_to_local;
+  io2.kf_to_local = G.kf_to_local;
+  int32_t* drop = io->drop_src ? io->drop_src : S.drop_src;
+  int32_t* dropk = io->drop_kf ? io->drop_kf : S.drop_kf;
+  rc = chain_front(ctx, cam, prm, scale_factor, B, NF, NL, NPcap, &io2, th_mm, mono, S, drop, dropk, false);
+  if (rc != GL_OK) return rc;
+  const gl::LocalMapDerive d = {io->match_last, fbk ? io->match_kf : nullptr, lm->last_mp, fbk ? lm->kf_feat_mp : nullptr, fbk ? io->counts2 : nullptr, NL, NK};
+  rc = gl::local_map_launch(c, map, B, NF, L, &d, (char*)scratch + gbytes);
+  if (rc != GL_OK) return rc;
+  rc = gl::local_map_gather_launch(c, map, B, NL, NK, L, lm->last_mp, lm->kf_feat_mp, G);
+  if (rc != GL_OK) return rc;
+  return chain_back(ctx, cam, prm, scale_factor, B, NF, NL, NPcap, &io2, th_local, nn_ratio, S, drop, dropk, false);
+}

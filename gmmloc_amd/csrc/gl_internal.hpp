@@ -152,6 +152,8 @@ enum {
   SCRATCH_CHAIN,   // the intermediates of gl_track_frame_chain, whose stages use the two blocks above
   SCRATCH_SCREEN,  // the screened association's per-split candidate lists and its fp64 fallback (launch_assoc_screened), so
                    // that it needs nothing from the block its caller sized for the fp64 sweep
+  SCRATCH_LOCALMAP,  // gl_update_local_map's global-path counters / bitmask, and the local-map arrays gl_track_frame_chain_map gathers
+                     // for its stages (which use the three blocks above)
   SCRATCH_COUNT
 };
 
@@ -300,6 +302,32 @@ int launch_match_frame_gated(gl_ctx_t* ctx, const gl_camera* cam, float scale_fa
                              const uint8_t* feat_taken, const double* last_pt, const uint8_t* last_valid, const int32_t* last_oct, const float* last_angle,
                              const uint8_t* last_desc, float th, int mono, int check_orientation, int32_t* feat_match, int32_t* nmatches,
                              const int32_t* gate_nm, int gate_min);
+// (gl_localmap.hip) Tracking::updateLocalMap on the device and the gather of the chain's local-map arrays from the whole map.
+// LocalMapDerive: feat_mp is first MADE from the chain's associations (gl_track_frame_chain_map, step 2) in the same launch.
+struct LocalMapDerive {
+  int32_t* match_last;        // B x NF in/out
+  int32_t* match_kf;          // B x NF in/out, or null
+  const int32_t* last_mp;     // B x NL
+  const int32_t* kf_feat_mp;  // B x NK, or null
+  const int32_t* counts2;     // B x 4 (mode in [3]), or null: no frame is lost
+  int NL, NK;
+};
+struct LocalMapLists {
+  int KFcap, NPcap;
+  int32_t *feat_mp, *local_kf, *n_local_kf, *local_mp, *n_local_mp, *ref_kf, *kf_count, *status;
+};
+struct LocalMapGathered {  // B x NPcap (x 3 / x 32), B x NL, B x NK
+  double *mp_pos, *mp_normal;
+  float *mp_max_dist, *mp_min_dist;
+  uint8_t *mp_cand, *mp_desc;
+  int32_t *last_to_local, *kf_to_local;
+};
+int local_map_check(const gl_map_view* map, int B, int NF, const LocalMapLists& L, bool need_point_arrays);
+size_t local_map_scratch_bytes(const Ctx* c, const gl_map_view* map, int B, bool have_kf_count);
+int local_map_launch(Ctx* c, const gl_map_view* map, int B, int NF, const LocalMapLists& L, const LocalMapDerive* derive, void* scratch);
+size_t local_map_gathered_place(void* base, int B, int NPcap, int NL, int NK, LocalMapGathered* out);  // bytes; base may be null (size only)
+int local_map_gather_launch(Ctx* c, const gl_map_view* map, int B, int NL, int NK, const LocalMapLists& L, const int32_t* last_mp,
+                            const int32_t* kf_feat_mp, const LocalMapGathered& G);
 // association launchers (gl_assoc.hip: all-pairs sweep; gl_grid.hip: cell index + sweep of the rest)
 int launch_assoc_brute(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2);
 int launch_assoc_sweep(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,

@@ -682,3 +682,115 @@ def synth_map_points(NP, seed, NKF=257, NFK=400, counts=None, kf_invalid_frac=0.
     pt_valid = (rng.uniform(size=NP) >= pt_invalid_frac).astype(np.uint8)
     return dict(kf=dict(twc=twc, valid=kf_valid, oct=kf_oct, desc=kf_desc),
                 mp=dict(pos=pos, valid=pt_valid, ref_kf=ref_kf, obs_ptr=obs_ptr.astype(np.int32), obs_kf=obs_kf, obs_feat=obs_feat))
+
+
+def synth_chain_map(frames, seed, NMP, NKF, NFK, window=16, kf_invalid_frac=0.08, pt_invalid_frac=0.04, twice_frac=0.03, prev_frac=0.9):
+    """ONE global map for gl_update_local_map / gl_track_frame_chain_map that embeds the local maps and last frames of `frames`
+    (dicts of synth_chain_frame; may be empty: a map of distractors alone).  Drawn from a generator of its own.
+    Map points: NMP rows; the local map of frame b takes len(mp_cand) rows SCATTERED over the table (a random permutation), the rest are
+    distractors with random matcher inputs.  Every point is seen by n distinct key-frames (map_point_counts: 2 - 30, 2 % none)
+    inside a window of 2 * window + 1 rows around its centre key-frame; a frame's points have their centres within 4 rows of the frame's
+    own centre (frames evenly spaced over the table), distractors anywhere - so the key-frames that see a frame's points also hold
+    distractor points, and distractor key-frames see none of them.  An observation takes a free slot of its key-frame (a random one);
+    one that finds its key-frame full is dropped, so kf_mp and the CSR stay consistent with each other.  A share of the points and of
+    the key-frames is invalid.
+    Per frame: last_mp / kf_feat_mp = the row behind last_to_local / kf_to_local (-1: none, temporal), with twice_frac of the last-frame
+    features that had no local point given the row of ANOTHER feature (a point held by two features); prev = the lists "of the previous
+    frame": prev_frac of the frame's own rows, ascending, and the key-frames around its centre.
+    -> dict(map = dict of numpy arrays with the keys of api.MAP_VIEW_DTYPES, rows [B] (NP,), centre [B], last_mp [B] (NL,),
+            kf_feat_mp [B] (NK,) or None, prev_local_mp [B], prev_local_kf [B])"""
+    rng = np.random.default_rng(seed + 90210)
+    B = len(frames)
+    nps = [len(f["mp_cand"]) for f in frames]
+    assert sum(nps) <= NMP and NKF >= 1 and 2 * window + 1 <= max(NKF, 1) or NKF < 2 * window + 1
+    W = min(window, (NKF - 1) // 2)
+    perm = rng.permutation(NMP)
+    rows, at = [], 0
+    for n in nps:
+        rows.append(perm[at:at + n].astype(np.int32))
+        at += n
+    centre_f = [int((b * NKF) // max(B, 1) + NKF // (2 * max(B, 1))) % NKF for b in range(B)]
+    centre = rng.integers(0, NKF, NMP)
+    for b in range(B):
+        centre[rows[b]] = (centre_f[b] + rng.integers(-4, 5, nps[b])) % NKF
+    # observations: n distinct key-frames of the window per point, in no particular order
+    n = np.minimum(map_point_counts(NMP, rng), 2 * W + 1)
+    order = np.argsort(rng.uniform(size=(NMP, 2 * W + 1)), axis=1)
+    pt = np.repeat(np.arange(NMP), n)
+    j = np.arange(len(pt)) - np.repeat(np.cumsum(n) - n, n)
+    okf = (centre[pt] + order[pt, j] - W) % NKF
+    # a free slot of the key-frame each: rank among the key-frame's observations through a random permutation of its slots
+    by_kf = np.argsort(okf, kind="stable")
+    start = np.searchsorted(okf[by_kf], np.arange(NKF))
+    rank = np.empty(len(pt), np.int64)
+    rank[by_kf] = np.arange(len(pt)) - start[okf[by_kf]]
+    keep = rank < NFK
+    slots = np.argsort(rng.uniform(size=(NKF, max(NFK, 1))), axis=1)
+    pt, okf, rank = pt[keep], okf[keep], rank[keep]
+    kf_mp = -np.ones((NKF, NFK), np.int32)
+    if NFK:
+        kf_mp[okf, slots[okf, rank]] = pt
+    obs_ptr = np.zeros(NMP + 1, np.int64)
+    obs_ptr[1:] = np.cumsum(np.bincount(pt, minlength=NMP))
+    m = dict(mp_valid=(rng.uniform(size=NMP) >= pt_invalid_frac).astype(np.uint8), obs_ptr=obs_ptr.astype(np.int32), obs_kf=okf.astype(np.int32),
+             kf_valid=(rng.uniform(size=NKF) >= kf_invalid_frac).astype(np.uint8), kf_mp=kf_mp)
+    # the matcher inputs of the whole map: distractors random, a frame's rows = its local map
+    d = rng.standard_normal((NMP, 3))
+    m["mp_pos"] = rng.uniform(-10.0, 10.0, (NMP, 3))
+    m["mp_normal"] = d / np.linalg.norm(d, axis=1)[:, None]
+    m["mp_max_dist"] = rng.uniform(4.0, 20.0, NMP).astype(np.float32)
+    m["mp_min_dist"] = (m["mp_max_dist"] * np.float32(0.1)).astype(np.float32)
+    m["mp_desc"] = rng.integers(0, 256, (NMP, 32), dtype=np.uint8)
+    last_mp, kf_feat_mp, prev_mp, prev_kf = [], [], [], []
+    for b, f in enumerate(frames):
+        for k in ("mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc"):
+            m[k][rows[b]] = f[k]
+        l2l = np.asarray(f["last_to_local"])
+        lm = np.where(l2l >= 0, rows[b][np.maximum(l2l, 0)], -1).astype(np.int32)
+        observed = np.asarray(f["last_observed"]) != 0 if "last_observed" in f else np.ones(len(l2l), bool)
+        free, have = np.nonzero((lm < 0) & observed)[0], np.nonzero(lm >= 0)[0]
+        if len(have):
+            again = free[rng.uniform(size=len(free)) < twice_frac]
+            lm[again] = lm[rng.choice(have, len(again))]
+        last_mp.append(lm)
+        k2l = np.asarray(f["kf_to_local"]) if "kf_to_local" in f else None
+        kf_feat_mp.append(None if k2l is None else np.where(k2l >= 0, rows[b][np.maximum(k2l, 0)], -1).astype(np.int32))
+        prev_mp.append(np.sort(rows[b][rng.uniform(size=nps[b]) < prev_frac]).astype(np.int32))
+        prev_kf.append(np.unique((centre_f[b] + np.arange(-3, 4)) % NKF).astype(np.int32))
+    return dict(map=m, rows=rows, centre=centre_f, last_mp=last_mp, kf_feat_mp=kf_feat_mp, prev_local_mp=prev_mp, prev_local_kf=prev_kf)
+
+
+def synth_held_points(m, B, NF, seed, hold_frac=0.6, twice_frac=0.05):
+    """feat_mp (B, NF) for gl_update_local_map on a map of synth_chain_map: frame b stands at a random key-frame and its features hold
+    map points of that key-frame and its two neighbours (hold_frac of the features; twice_frac of them a point ANOTHER feature holds
+    too; invalid points included, as the reference finds them).  Every eighth frame, from the second on, has an EMPTY counter (its
+    features hold nothing or points without observations), every eighth from the third on holds ONE point with at least two valid
+    observers, twice: all its key-frames tie at 2."""
+    rng = np.random.default_rng(seed + 31337)
+    NMP, NKF = len(m["obs_ptr"]) - 1, m["kf_mp"].shape[0]
+    nobs = np.diff(m["obs_ptr"])
+    none = np.nonzero(nobs == 0)[0]
+    kfv = np.asarray(m["kf_valid"]) != 0
+    nvalid = np.add.reduceat(np.concatenate([kfv[m["obs_kf"]], [False]]).astype(np.int64), np.minimum(m["obs_ptr"][:-1], len(m["obs_kf"]))) * (nobs > 0)
+    tieable = np.nonzero((nvalid >= 2) & (np.asarray(m["mp_valid"]) != 0))[0]
+    feat_mp = -np.ones((B, NF), np.int32)
+    for b in range(B):
+        if b % 8 == 1:
+            if len(none):
+                at = rng.uniform(size=NF) < 0.2
+                feat_mp[b, at] = rng.choice(none, int(at.sum()))
+            continue
+        if b % 8 == 2 and len(tieable):
+            feat_mp[b, rng.choice(NF, min(2, NF), replace=False)] = rng.choice(tieable)
+            continue
+        c = int(rng.integers(0, NKF))
+        pool = m["kf_mp"][[(c - 1) % NKF, c, (c + 1) % NKF]].ravel()
+        pool = pool[pool >= 0]
+        if not len(pool):
+            continue
+        at = np.nonzero(rng.uniform(size=NF) < hold_frac)[0]
+        feat_mp[b, at] = rng.permutation(pool)[np.arange(len(at)) % len(pool)] if len(pool) >= len(at) else rng.choice(pool, len(at))
+        tw = at[rng.uniform(size=len(at)) < twice_frac]
+        if len(at):
+            feat_mp[b, tw] = feat_mp[b, rng.choice(at, len(tw))]
+    return feat_mp

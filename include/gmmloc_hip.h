@@ -403,7 +403,9 @@ int gl_update_map_points(gl_ctx_t* ctx, float scale_factor, int what, int NP, in
  * observe the frame's CURRENT map points and their neighbours) - host code on host containers.  gl_track_frame_chain takes ONE
  * local map, fixed before stage 1: it reproduces Tracking::track only if that list is the one updateLocalMap would produce
  * (e.g. the previous frame's local map when the covisibility set did not change); stage 3's matches are order-exact for the
- * list it is given, not for a list it never saw.  A host that wants the reference's sequence exactly calls the two halves -
+ * list it is given, not for a list it never saw.  A host that wants the reference's sequence in one call hands the whole map to
+ * gl_track_frame_chain_map (below: updateLocalMap on the device, canonical order); one that must keep its own containers' order
+ * calls the two halves -
  *      gl_track_frame_chain_front (1, 2, 2b)  ->  its own updateLocalMap  ->  gl_track_frame_chain_back (3, 4)
  * - one round trip instead of three; front needs drop_src (and drop_kf with the fallback) as OUTPUT buffers, back reads match_last /
  * match_kf / drop_src / drop_kf and the to_local maps against the NEW local map.
@@ -470,6 +472,104 @@ int gl_track_frame_chain_front(gl_ctx_t* ctx, const gl_camera* cam, const gl_par
                                const gl_track_chain_io* io, float th_mm, int mono);
 int gl_track_frame_chain_back(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* prm, float scale_factor, int B, int NF, int NL, int NP,
                               const gl_track_chain_io* io, float th_local, float nn_ratio);
+
+/* Tracking::updateLocalMap (tracking.cpp:119-207) on the device, for B frames at once, over the WHOLE map as caller-owned device arrays -
+ * the arrays gl_update_map_points reads and writes, plus one key-frame table:
+ *   NMP, NKF, NFK, NOBS   map points, key-frames, feature slots per key-frame, observations
+ *   mp_valid   NMP uint8, NULL = all        !not_valid_ of a map point
+ *   obs_ptr    NMP+1 int32, obs_kf NOBS     observations_ as the CSR of gl_update_map_points (obs_feat is not needed)
+ *   kf_valid   NKF uint8, NULL = all        !not_valid_ of a key-frame
+ *   kf_mp      NKF x NFK int32              mappoints_[i] of the key-frame as a map-point row, -1 = null
+ *   mp_pos NMP x 3 f64, mp_normal NMP x 3 f64, mp_max_dist / mp_min_dist NMP float, mp_desc NMP x 32 uint8: the per-point matcher
+ *              inputs of the whole map (read by gl_track_frame_chain_map only; gl_update_local_map ignores them, NULL allowed)
+ * What the reference does, per frame (quirks reproduced, not fixed):
+ *   1 (:129-145) for every FEATURE i with a map point (feat_mp[i] >= 0): an invalid point -> feat_mp[i] = -1 (mappoints_[i] = nullptr);
+ *     else kf_count[kf] += 1 for every observation of the point.  Per feature: a point held by two features counts twice; a temporal
+ *     point (no observations) adds nothing.
+ *   2 (:147-148) no counter entry at all -> return: local_kf, n_local_kf, local_mp, n_local_mp, ref_kf keep the values passed in
+ *     (status bit 1).
+ *   3 (:150-166, :183-188) local key-frames = the counted key-frames that are valid; ref_kf = the valid one with the largest count.
+ *     An invalid key-frame is counted (kf_count shows it) but is neither local nor ref_kf; when every counted key-frame is invalid the
+ *     lists become EMPTY and ref_kf is unchanged.
+ *   4 (:167-181) the neighbour loop adds a covisible key-frame only `if (set_local_kfs.count(neigh_kf))`, i.e. only if the set already
+ *     holds it: it never adds anything, and its `> 80` break has nothing to limit.  The device version therefore takes no
+ *     covisibility input at all.
+ *   5 (:191-206) local map points = the union over the local key-frames of their mappoints_ that are non-null and valid, each once.
+ * DECLARED DEVIATION: the reference's tie among key-frames of the same maximal count and the ORDER of local_keyframes_ /
+ * local_mappoints_ follow unordered_map / unordered_set<pointer> iteration, i.e. the allocator; no second implementation can
+ * reproduce them.  Here: ties -> the LOWEST key-frame row; local_kf and local_mp in ASCENDING row order.  (The order of
+ * local_mappoints_ decides stage 3's matches where two points compete for a feature.)  A host that must keep its own container
+ * order keeps using gl_track_frame_chain_front / _back.
+ * In/out: feat_mp B x NF int32.  In/out (step 2 leaves them untouched): local_kf B x KFcap int32 + n_local_kf B, local_mp B x NPcap
+ * int32 + n_local_mp B, ref_kf B.  Out: kf_count B x NKF int32 (NULL allowed) - the counter itself, which is also the histogram
+ * KeyFrame::updateConnections builds (keyframe.cpp:243-263) when feat_mp is a key-frame's own mappoints_; status B int32 bit flags:
+ * GL_LOCAL_MAP_KEPT counter empty (lists kept), GL_LOCAL_MAP_MP_TRUNCATED / _KF_TRUNCATED: more rows than NPcap / KFcap - the LOWEST
+ * rows are kept and n_local_* still hold the TRUE counts (local_mp is always made from ALL local key-frames).
+ * MALFORMED input is skipped, never read out of bounds: a feat_mp / kf_mp entry outside [-1, NMP) (left as it is, counts nothing), a
+ * point whose [obs_ptr[p], obs_ptr[p+1]) is not a sub-range of [0, NOBS] (counts nothing), an observation whose key-frame is outside
+ * [0, NKF) (that observation alone).
+ * One workgroup per frame; integer LDS / global atomics only, so the result does not depend on scheduling.  The key-frame counters
+ * (NKF <= 4 096) and the bitmask over map-point rows (NMP <= 1 048 576) live in LDS sized to the map passed; beyond either bound that
+ * array lives in the context's scratch (slower, same result).  Stateless, asynchronous on the context's stream. */
+#define GL_LOCAL_MAP_KEPT 1
+#define GL_LOCAL_MAP_MP_TRUNCATED 2
+#define GL_LOCAL_MAP_KF_TRUNCATED 4
+typedef struct gl_map_view {
+  int32_t NMP, NKF, NFK, NOBS;
+  const uint8_t* mp_valid;
+  const int32_t* obs_ptr;
+  const int32_t* obs_kf;
+  const uint8_t* kf_valid;
+  const int32_t* kf_mp;
+  const double* mp_pos;
+  const double* mp_normal;
+  const float* mp_max_dist;
+  const float* mp_min_dist;
+  const uint8_t* mp_desc;
+} gl_map_view;
+int gl_update_local_map(gl_ctx_t* ctx, const gl_map_view* map, int B, int NF, int KFcap, int NPcap, int32_t* feat_mp_dev,
+                        int32_t* local_kf_dev, int32_t* n_local_kf_dev, int32_t* local_mp_dev, int32_t* n_local_mp_dev, int32_t* ref_kf_dev,
+                        int32_t* kf_count_dev, int32_t* status_dev);
+
+/* The tracked frame as ONE call that follows Tracking::track's own sequence: stages 1, 2, 2b, then updateLocalMap on the map points the
+ * frame holds after the first optimisation, then stages 3, 4 on THAT local map - no host round trip, nothing uploaded mid-frame.
+ * `io` is the gl_track_chain_io of gl_track_frame_chain with mp_pos / mp_normal / mp_max_dist / mp_min_dist / mp_cand / mp_desc /
+ * last_to_local / kf_to_local IGNORED (may be NULL): the chain makes them itself, in the context's scratch.  Enqueued in order:
+ *   1  stages 1, 2, 2b as gl_track_frame_chain_front
+ *   2  feat_mp[i] = match_last[i] >= 0 ? last_mp[match_last[i]] : match_kf[i] >= 0 ? kf_feat_mp[match_kf[i]] : -1; a frame whose
+ *      mode is 2 (lost: the reference returns before updateLocalMap) gets -1 throughout, so its lists are kept.  A held point that
+ *      is invalid in mp_valid is cleared in full: feat_mp[i] = -1 AND match_last[i] / match_kf[i] = -1 - in the reference
+ *      mappoints_[i] = nullptr (:138-139, again :218-219) also takes the feature out of trackLocalMap's pose problem and lets
+ *      stage 3 match it again.  mp_valid is ONE snapshot for the whole call (the reference reads a flag another thread may flip
+ *      mid-frame; that race is not reproduced).
+ *   3  gl_update_local_map on it (in the same launch as 2)
+ *   4  the chain's local-map arrays (B x NPcap) gathered from the map's arrays through local_mp: slot s < min(n_local_mp, NPcap) is
+ *      map-point row local_mp[s] with mp_cand = 1, the slots above are zeros with mp_cand = 0; last_to_local / kf_to_local by binary
+ *      search of last_mp / kf_feat_mp in the ascending list
+ *   5  stages 3, 4 as gl_track_frame_chain_back.  match_local indexes local_mp; inview is B x NPcap against it.
+ * The padding slots change nothing: every output equals, bit for bit, the two halves run with NP = n_local_mp on the unpadded list.
+ * NF and NPcap are bounded by stage 3 as in every chain call (gl_search_local_points: 3 072 features, 4 096 map points on chip); a
+ * frame whose local map is larger runs on its lowest NPcap rows and says so (GL_LOCAL_MAP_MP_TRUNCATED).
+ * lm: last_mp B x NL int32, kf_feat_mp B x NK int32 (NULL without the fallback): the map-point row behind each last-frame /
+ * reference-key-frame feature, -1 for none and for temporal points; feat_mp B x NF out; the lists, ref_kf, kf_count (NULL allowed)
+ * and status of gl_update_local_map (the lists in/out: the previous frame's values). */
+typedef struct gl_local_map_io {
+  const int32_t* last_mp;
+  const int32_t* kf_feat_mp;
+  int32_t* feat_mp;
+  int32_t KFcap;
+  int32_t reserved_;
+  int32_t* local_kf;
+  int32_t* n_local_kf;
+  int32_t* local_mp;
+  int32_t* n_local_mp;
+  int32_t* ref_kf;
+  int32_t* kf_count;
+  int32_t* status;
+} gl_local_map_io;
+int gl_track_frame_chain_map(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* prm, float scale_factor, int B, int NF, int NL, int NPcap,
+                             const gl_track_chain_io* io, const gl_map_view* map, const gl_local_map_io* lm, float th_mm, float th_local,
+                             float nn_ratio, int mono);
 
 /* Localization::fuseObservations (localization.cpp:226-318), the matching half, for B key-frames: per candidate map point the most
  * similar feature inside Frame::getFeaturesInArea(u, v, th * scale_factors[level]) (frame.cpp:121-177) with octave level - 1 or

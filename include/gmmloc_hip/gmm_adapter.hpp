@@ -279,4 +279,58 @@ class GMM {
   gl_camera cam_{};
 };
 
+// ---- the flattening a host needs for gl_update_local_map / gl_track_frame_chain_map (Tracking::updateLocalMap on the device,
+// INTEGRATION 5c third form).  The map stays the host's: these helpers only turn its containers into the flat rows of gl_map_view.
+// A "row" is the index the host gives a MapPoint* / KeyFrame* in its device arrays (e.g. the slot of gl_update_map_points' outputs).
+struct MapRows {
+  int32_t NMP = 0, NKF = 0, NFK = 0;
+  std::vector<int32_t> kf_mp;            // NKF x NFK: KeyFrame::mappoints_[i] as a map-point row, -1 = null
+  std::vector<int32_t> obs_ptr, obs_kf;  // MapPoint::observations_ as CSR over map-point rows (NMP + 1, NOBS)
+  std::vector<uint8_t> mp_valid, kf_valid;  // !not_valid_
+};
+// point_row(k, i): row of key-frame k's i-th map point, or -1 (nullptr / slot i beyond the key-frame's features).  The CSR is made
+// from the table itself (observations_[kf] = idx <=> kf->mappoints_[idx] == this, mappoint.cpp:40-60), key-frames ascending per
+// point, so the two cannot disagree.  mp_is_valid(p), kf_is_valid(k): !not_valid_.
+template <class PointRow, class MpValid, class KfValid>
+inline MapRows flattenMap(int32_t NMP, int32_t NKF, int32_t NFK, PointRow point_row, MpValid mp_is_valid, KfValid kf_is_valid) {
+  MapRows m;
+  m.NMP = NMP;
+  m.NKF = NKF;
+  m.NFK = NFK;
+  m.kf_mp.assign((size_t)NKF * NFK, -1);
+  m.obs_ptr.assign((size_t)NMP + 1, 0);
+  for (int32_t k = 0; k < NKF; ++k)
+    for (int32_t i = 0; i < NFK; ++i) {
+      const int32_t p = point_row(k, i);
+      if (p < 0 || p >= NMP) continue;
+      m.kf_mp[(size_t)k * NFK + i] = p;
+      ++m.obs_ptr[(size_t)p + 1];
+    }
+  for (int32_t p = 0; p < NMP; ++p) m.obs_ptr[(size_t)p + 1] += m.obs_ptr[p];
+  m.obs_kf.assign((size_t)m.obs_ptr[NMP], 0);
+  std::vector<int32_t> at(m.obs_ptr.begin(), m.obs_ptr.end() - 1);
+  for (int32_t k = 0; k < NKF; ++k)
+    for (int32_t i = 0; i < NFK; ++i) {
+      const int32_t p = m.kf_mp[(size_t)k * NFK + i];
+      if (p >= 0) m.obs_kf[(size_t)at[p]++] = k;
+    }
+  m.mp_valid.resize(NMP);
+  m.kf_valid.resize(NKF);
+  for (int32_t p = 0; p < NMP; ++p) m.mp_valid[p] = mp_is_valid(p) ? 1 : 0;
+  for (int32_t k = 0; k < NKF; ++k) m.kf_valid[k] = kf_is_valid(k) ? 1 : 0;
+  return m;
+}
+// last_mp / kf_feat_mp of gl_local_map_io: the map-point row behind each of a frame's (the last frame's, the reference key-frame's)
+// n features - row(i) < 0 for a feature without a map point AND for a temporal point (createTemporalPoints, tracking.cpp:44-46: it
+// has no observations and no row in the map).
+template <class Row>
+inline std::vector<int32_t> featureRows(int32_t n, Row row) {
+  std::vector<int32_t> r((size_t)n, -1);
+  for (int32_t i = 0; i < n; ++i) {
+    const int32_t p = row(i);
+    r[i] = p < 0 ? -1 : p;
+  }
+  return r;
+}
+
 }  // namespace gmmloc_hip

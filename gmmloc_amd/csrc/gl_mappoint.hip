@@ -18,8 +18,11 @@
 #include <cmath>
 
 #include "gl_internal.hpp"
+#include "gl_match_common.hpp"
 
 namespace {
+
+using gl_match::hamming256;
 
 constexpr int MP_ROWS = 128;  // descriptor rows per wave in LDS (a packed batch, a general tile)
 constexpr int MP_NMAX = 32;   // the most observations of a point on the packed path (the lane's distance column)
@@ -45,11 +48,6 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
-         __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
@@ -308,8 +306,7 @@ extern "C" int gl_update_map_points(gl_ctx_t* ctx, float scale_factor, int what,
   P.NKF = NKF;
   P.NFK = NFK;
   P.NOBS = NOBS;
-  P.sf[0] = 1.0f;  // init_config.hpp:67-76
-  for (int i = 1; i < 8; ++i) P.sf[i] = P.sf[i - 1] * scale_factor;
+  gl_match::pyramid_scales(scale_factor, P.sf, nullptr, nullptr);
   k_update_map_points<<<(unsigned)((NP + 63) / 64), 64, 0, c->stream>>>(P, kf_twc_dev, kf_valid_dev, kf_oct_dev, kf_desc_dev, pos_dev, pt_valid_dev,
                                                                        ref_kf_dev, obs_ptr_dev, obs_kf_dev, obs_feat_dev, desc_dev, normal_dev,
                                                                        max_dist_dev, min_dist_dev);

@@ -32,10 +32,12 @@
 #include <climits>
 
 #include "gl_internal.hpp"
+#include "gl_match_common.hpp"
 
 namespace {
 
-constexpr int GC = 64, GR = 48, NCELL = GC * GR;  // frame::grid_cols / grid_rows (config.h:57)
+using namespace gl_match;
+constexpr int GR = FeatureGrid::GR, NCELL = FeatureGrid::NCELL;
 constexpr int T_M = 512;
 
 struct MatchP {
@@ -48,10 +50,10 @@ struct MatchP {
   int width, height, mono, check_orientation;
 };
 
-// 32-bit words of the kernel's LDS in front of the per-entry records: cell_ptr, cursor, cell_idx, owner, owner_n, qorder (u16)
+// 32-bit words of the kernel's LDS in front of the per-entry records: the grid, owner, owner_n, qorder (u16)
 // (round 6: the per-query `choice` table - written every round, read by nobody - is gone: 4 bytes per map point that kept a frame with
 //  3 000 local map points from sharing its CU with a second one - 85.8 KB -> 73.8 KB)
-__host__ __device__ inline int lds_ints(int NF, int NP) { return (2 * NCELL + 1 + 3 * NF + (NP + 1) / 2 + 3) & ~3; }
+__host__ __device__ inline int lds_ints(int NF, int NP) { return (FeatureGrid::words(NF) + 2 * NF + (NP + 1) / 2 + 3) & ~3; }
 
 // what one query point (a projected map point) asks of the feature grid
 struct Query {
@@ -76,13 +78,6 @@ __device__ __forceinline__ void quat_rot(const double* q, const double* v, doubl
   o[2] = v[2] + qw * uv[2] + (qx * uv[1] - qy * uv[0]);
 }
 
-__device__ __forceinline__ int hamming256(const uint32_t* a, const uint32_t* __restrict__ b) {
-  int d = 0;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) d += __popc(a[w] ^ b[w]);
-  return d;
-}
-
 // MODE 0: searchByProjection(Frame&, mappts, stats, th): query points = projected local map points
 //         (mp_uvr = ProjStat::uvr, mp_level = scale_pred, mp_viewcos).
 // MODE 1: searchByProjection(CurrentFrame, LastFrame, th, bMono): query points = the last frame's map
@@ -101,10 +96,9 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
     uint4* __restrict__ cache_all, const int32_t* gate_nm, int gate_min) {
   constexpr int TM = DL ? 1024 : T_M;  // threads per frame: the latency shape doubles them
   extern __shared__ __attribute__((aligned(16))) int32_t lds[];
-  int32_t* cell_ptr = lds;                   // NCELL + 1
-  int32_t* cursor = cell_ptr + NCELL + 1;    // NCELL (grid build only)
-  int32_t* cell_idx = cursor + NCELL;        // NF
-  int32_t* owner = cell_idx + P.NF;          // NF   owner of the previous round (-1: taken on entry)
+  const FeatureGrid grid(lds, P.col_inv, P.row_inv);
+  const int32_t* cell_ptr = grid.cell_ptr;
+  int32_t* owner = lds + FeatureGrid::words(P.NF);  // NF   owner of the previous round (-1: taken on entry)
   int32_t* owner_n = owner + P.NF;           // NF   being rebuilt
   // per CSR entry, so that the window walk touches LDS only: {u, v} double, {u_right bits, octave}
   uint16_t* qorder = (uint16_t*)(owner_n + P.NF);  // NP: the queries sorted by window class (round 5: equal work per lane)
@@ -113,8 +107,9 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
   // DL (few frames: one workgroup per CU anyway): the 256-bit descriptors too, in CSR order - a candidate that
   // survives the window test otherwise costs a dependent global load of 32 bytes
   uint4* rec_desc = (uint4*)(rec_ro + ((P.NF + 1) & ~1));  // 2 x uint4 per entry, 16-byte aligned
-  __shared__ int s_changed, s_scan[32], s_hist[32], s_keep[4];
-  __shared__ int s_fast, s_cls[17], s_nrw;
+  __shared__ FeatureGrid::Shared<TM> s_grid;
+  __shared__ int s_changed, s_hist[32], s_keep[4];
+  __shared__ int s_cls[17], s_nrw;
   __shared__ double s_pose[8];
   __shared__ int s_dir;
   const int f = blockIdx.x, tid = threadIdx.x;
@@ -136,84 +131,14 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
   const uint8_t* mp_valid = mp_valid_all + (size_t)f * NP;
   const uint32_t* mp_desc = (const uint32_t*)(mp_desc_all + (size_t)f * NP * 32);
 
-  // ---- assignFeaturesToGrid: CSR by cell (ix * GR + iy), ascending feature index inside a cell ----
-  for (int c = tid; c <= NCELL; c += TM) cell_ptr[c] = 0;
-  if (tid == 0) s_fast = 1;
-  if (tid < 17) s_cls[tid] = 0;
-  __syncthreads();
-  auto cell_of = [&](int i) -> int {
-    if (feat_oct[i] < 0) return -1;  // padding slot
-    const double px = round((feat_uv[2 * i] - 0.0f) * P.col_inv), py = round((feat_uv[2 * i + 1] - 0.0f) * P.row_inv);
-    if (!(px >= 0 && px < GC && py >= 0 && py < GR)) return -1;  // also rejects NaN
-    return (int)px * GR + (int)py;
-  };
-  {
-    // the fast walk (32-bit window test, one 16-byte record per entry) is exact iff every feature coordinate is a float value - the
-    // reference's (float)(double u - (double)x) is then the correctly rounded float difference, which is what u - x in float is
-    // (a double has more than 2 x 24 + 2 bits) - and the octaves fit the level mask
-    bool fok = true;
-    for (int i = tid; i < NF; i += TM) {
-      const int c = cell_of(i);
-      if (c >= 0) {
-        atomicAdd(&cell_ptr[c + 1], 1);
-        const double u = feat_uv[2 * i], v = feat_uv[2 * i + 1];
-        fok = fok && (double)(float)u == u && (double)(float)v == v && feat_oct[i] <= 15;
-      }
-    }
-    if (!fok) s_fast = 0;
-  }
-  __syncthreads();
-  {  // exclusive scan of NCELL counts: each thread scans a contiguous chunk, then the chunk sums
-    constexpr int CH = (NCELL + TM - 1) / TM;
-    const int c0 = tid * CH, c1 = min(NCELL, c0 + CH);
-    int s = 0;
-    for (int c = c0; c < c1; ++c) s += cell_ptr[c + 1];
-    // exclusive scan of the TM chunk sums: shuffle scan inside each wave, then the wave totals
-    int inc = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(inc, o, 64);
-      if ((tid & 63) >= o) inc += up;
-    }
-    if ((tid & 63) == 63) s_scan[tid >> 6] = inc;
-    __syncthreads();
-    int run = inc - s;
-    for (int w = 0; w < (tid >> 6); ++w) run += s_scan[w];
-    __syncthreads();  // s_scan is reused below
-    for (int c = c0; c < c1; ++c) {
-      const int v = cell_ptr[c + 1];
-      cell_ptr[c + 1] = run + v;  // inclusive end; cell_ptr[c] (= end of c-1) is its start
-      run += v;
-    }
-    __syncthreads();
-  }
-  // fill through a per-cell cursor, then put every (short) cell list in ascending feature order: that
-  // is the push_back order of the reference and decides ties between equal Hamming distances
-  for (int c = tid; c < NCELL; c += TM) cursor[c] = 0;
-  __syncthreads();
-  for (int i = tid; i < NF; i += TM) {
-    const int c = cell_of(i);
-    if (c >= 0) cell_idx[cell_ptr[c] + atomicAdd(&cursor[c], 1)] = i;
-  }
-  __syncthreads();
-  for (int c = tid; c < NCELL; c += TM) {
-    const int e0 = cell_ptr[c], e1 = cell_ptr[c + 1];
-    for (int e = e0 + 1; e < e1; ++e) {  // insertion sort
-      const int v = cell_idx[e];
-      int k = e - 1;
-      while (k >= e0 && cell_idx[k] > v) {
-        cell_idx[k + 1] = cell_idx[k];
-        --k;
-      }
-      cell_idx[k + 1] = v;
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < cell_ptr[NCELL]; e += TM) {
-    const int i = cell_idx[e];
-    if (s_fast) ((float4*)rec_uv)[e] = make_float4((float)feat_uv[2 * i], (float)feat_uv[2 * i + 1], feat_ur[i], __int_as_float((feat_oct[i] & 0xff) | (i << 8)));
+  // the fast walk (32-bit window test, one 16-byte record per entry) needs float coordinates and octaves that fit its level mask
+  grid.build<TM>(tid, NF, feat_uv, feat_oct, 15, s_grid);
+  const int& s_fast = s_grid.fast;
+  for (int e = tid; e < grid.entries(); e += TM) {
+    const int i = grid.cell_idx[e];
+    if (s_fast) ((float4*)rec_uv)[e] = FeatureGrid::record(feat_uv, feat_ur, feat_oct, i);
     else rec_uv[e] = make_double2(feat_uv[2 * i], feat_uv[2 * i + 1]);
-    rec_ro[e] = make_int2(__float_as_int(feat_ur[i]), (feat_oct[i] & 0xff) | (i << 8));  // {u_right, octave | feature << 8}
+    rec_ro[e] = make_int2(__float_as_int(feat_ur[i]), FeatureGrid::pack(feat_oct[i], i));  // {u_right, octave | feature << 8}
     if (DL) {
       const uint4* src = (const uint4*)(feat_desc + (size_t)i * 8);
       rec_desc[2 * e] = src[0];
@@ -299,36 +224,21 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
 #ifdef GL_MATCH_PROF
   const long long tp1 = clock64();
 #endif
-  // queries by window class (half size of the window = a factor x the scale of the level: 16 classes), so that the lanes of a wave
-  // walk windows of like size: counting sort, stable within a class up to the order of the atomics (the order only decides
-  // which thread takes which query - never a result)
-  {
+  {  // 16 window classes: the level, and for the local map the viewing angle's factor
     auto cls_of = [&](int m) -> int {
       if (!mp_valid[m]) return 16;
       const int lvl = mp_level[m] & 7;
       return MODE == 0 ? (lvl | (((float)mp_viewcos[m] > 0.998) ? 0 : 8)) : lvl;
     };
-    for (int m = tid; m < NP; m += TM) atomicAdd(&s_cls[cls_of(m)], 1);
-    __syncthreads();
-    if (tid == 0) {  // exclusive scan, the LARGEST windows first (they set the pace of a wave), the invalid ones last
-      const int ord[17] = {15, 14, 13, 12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 0, 16};
-      int run = 0;
-      for (int k = 0; k < 17; ++k) {
-        const int n = s_cls[ord[k]];
-        s_cls[ord[k]] = run;
-        run += n;
-      }
-    }
-    __syncthreads();
-    for (int m = tid; m < NP; m += TM) qorder[atomicAdd(&s_cls[cls_of(m)], 1)] = (uint16_t)m;
-    __syncthreads();
+    constexpr int ord[17] = {15, 14, 13, 12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 0, 16};
+    sort_queries_by_class<TM>(tid, NP, ord, cls_of, s_cls, qorder);
   }
 #ifdef GL_MATCH_PROF
   const long long tp1b = clock64();
   long long tp_r0 = 0;
 #endif
   constexpr uint32_t EMPTY = 0xffffffffu;
-  uint16_t* lst = (uint16_t*)cursor;  // 4 x TM entry indices: a thread's collected candidates (the cursors are dead after the grid build)
+  uint16_t* lst = (uint16_t*)grid.cursor;  // 4 x TM entry indices: a thread's collected candidates (the cursors are dead after the grid build)
   uint4* cache = cache_all + (size_t)f * NP;
 
   // the window walk of query m (all lanes of a wave walk together: the loop and the flushes are wave-uniform): the three smallest
@@ -349,14 +259,8 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
     uint32_t seq = 0;
     PW_T(pw0);
     const float rr = q.rr, x = q.x, y = q.y;
-    int x0 = 1, x1 = 0, y0 = 0, y1 = 0;
-    if (act) {
-      x0 = max(0, (int)floorf((x - 0.0f - rr) * P.col_inv));
-      x1 = min(GC - 1, (int)ceilf((x - 0.0f + rr) * P.col_inv));
-      y0 = max(0, (int)floorf((y - 0.0f - rr) * P.row_inv));
-      y1 = min(GR - 1, (int)ceilf((y - 0.0f + rr) * P.row_inv));
-      if (!(x0 < GC && x1 >= 0 && y0 < GR && y1 >= 0) || y0 > y1) x1 = x0 - 1;  // nothing to visit
-    }
+    FeatureGrid::Window win;
+    if (act) win = grid.window(x, y, rr);
     const int minLevel = q.minLevel, maxLevel = q.maxLevel;
     const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
     uint32_t dm[8];
@@ -375,12 +279,12 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
         if (j < cnt) {
           const int ej = lst[j * TM + tid];
           roy[j] = rec_ro[ej].y;
-          own[j] = owner[roy[j] >> 8];
+          own[j] = owner[FeatureGrid::feature_of(roy[j])];
           if (DL) {
             da[j] = rec_desc[2 * ej];
             db[j] = rec_desc[2 * ej + 1];
           } else {
-            const uint4* src = (const uint4*)(feat_desc + (size_t)(roy[j] >> 8) * 8);
+            const uint4* src = (const uint4*)(feat_desc + (size_t)FeatureGrid::feature_of(roy[j]) * 8);
             da[j] = src[0];
             db[j] = src[1];
           }
@@ -389,26 +293,13 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (j < cnt && own[j] >= m) {  // not taken on entry (-1), not owned by an earlier map point
-          const int dist = __popc(dm[0] ^ da[j].x) + __popc(dm[1] ^ da[j].y) + __popc(dm[2] ^ da[j].z) + __popc(dm[3] ^ da[j].w) +
-                           __popc(dm[4] ^ db[j].x) + __popc(dm[5] ^ db[j].y) + __popc(dm[6] ^ db[j].z) + __popc(dm[7] ^ db[j].w);
-          const int oc = roy[j] & 0xff, idx = roy[j] >> 8;
+          const int dist = hamming256(dm, da[j], db[j]);
+          const int oc = FeatureGrid::octave_of(roy[j]), idx = FeatureGrid::feature_of(roy[j]);
           if (seq > 255u || oc > 15) bad = true;  // does not fit the packed record: this query walks in every round
           if (dist < 256) {  // (a distance of 256 never beats the initial best / second best of the reference's loop)
             const unsigned long long kx = ((unsigned long long)dist << 48) | ((unsigned long long)seq << 20) | ((unsigned long long)oc << 12) | (unsigned long long)idx;
             ++npass;
-            if (kx < k2) {
-              k2 = kx;
-              if (k2 < k1) {
-                const unsigned long long t = k1;
-                k1 = k2;
-                k2 = t;
-              }
-              if (k1 < k0) {
-                const unsigned long long t = k0;
-                k0 = k1;
-                k1 = t;
-              }
-            }
+            keep3(k0, k1, k2, kx);
           }
           ++seq;
         }
@@ -419,14 +310,12 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
       ++pw_nflush;
 #endif
     };
-    int ix = x0 - 1, e = 0, e1 = 0;
 #ifdef GL_MATCH_PROF
     dm[0] += __builtin_amdgcn_readfirstlane(dm[0]) & 0;  // (the descriptor's load has landed before the clock is read)
     const long long pw1 = clock64();
     pw_setup += pw1 - pw0;
     ++pw_walks;
 #endif
-    bool more = act && x0 <= x1;
     if (s_fast) {
       // level filter as a bit mask over the octaves 0..15 (getFeaturesInArea: minLevel / maxLevel, frame.cpp:121-177)
       uint32_t lm = 0xffffu;
@@ -436,19 +325,9 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
         for (int o = 0; o < 16; ++o)
           if (!(o < minLevel) && !(maxLevel >= 0 && o > maxLevel)) lm |= 1u << o;
       }
-      const float4* rec16 = (const float4*)rec_uv;
-      // Round 6: the loop is a chain of LDS round trips, not of instructions (profiles/r6_match_stations.txt: ~0.4 us per iteration with
-      // the CU to itself) - a column's range, then an entry, then its feature's owner, one after the other.  Now an iteration waits ONCE:
-      // the NEXT column's range is requested a column ahead, two entries are read per iteration, and the owner test moved into the
-      // flush, where the (<= 4) owners are requested together with the descriptors.
-      int ne = 0, ne1 = 0;  // the range of column ix + 1
-      if (more) {
-        ne = cell_ptr[x0 * GR + y0];
-        ne1 = cell_ptr[x0 * GR + y1 + 1];
-      }
+      // (the owner test is in the flush, where the owners are requested together with the descriptors)
       auto entry = [&](const float4 r, int ee) {
-        const int pk = __float_as_int(r.w);
-        bool ok = ((lm >> (pk & 0xff)) & 1u) != 0 && fabsf(r.x - x) < rr && fabsf(r.y - y) < rr;
+        bool ok = ((lm >> FeatureGrid::octave_of(__float_as_int(r.w))) & 1u) != 0 && fabsf(r.x - x) < rr && fabsf(r.y - y) < rr;
         if (ok && r.z > 0) {
           const float er = q.ur_float ? fabsf(q.ur_f - r.z) : (float)fabs(q.ur_d - (double)r.z);
           if (er > rr) ok = false;
@@ -458,34 +337,15 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
           ++cnt;
         }
       };
-      while (__any(more)) {
-        if (more && e >= e1) {  // next column: cells (ix, y0..y1) are contiguous in the CSR
-          ++ix;
-          if (ix > x1) {
-            more = false;
-          } else {
-            e = ne;
-            e1 = ne1;
-            if (ix < x1) {
-              ne = cell_ptr[(ix + 1) * GR + y0];
-              ne1 = cell_ptr[(ix + 1) * GR + y1 + 1];
-            }
-          }
-        }
-        const bool h0 = more && e < e1, h1 = more && e + 1 < e1;
-        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0;
-        if (h0) r0 = rec16[e];
-        if (h1) r1 = rec16[e + 1];
-        if (h0) entry(r0, e);
-        if (__any(cnt == 4)) flush();
-        if (h1) entry(r1, e + 1);
-        if (__any(cnt == 4)) flush();
-        e += h1 ? 2 : (h0 ? 1 : 0);
 #ifdef GL_MATCH_PROF
-        ++pw_iter;
+      walk_window_records(grid, (const float4*)rec_uv, win, act, cnt, entry, flush, [&] { ++pw_iter; });
+#else
+      walk_window_records(grid, (const float4*)rec_uv, win, act, cnt, entry, flush);
 #endif
-      }
     } else {
+      const int x1 = win.x1, y0 = win.y0, y1 = win.y1;
+      bool more = act && win.x0 <= x1;
+      int ix = win.x0 - 1, e = 0, e1 = 0;
       while (__any(more)) {
         bool have = false;
         int ecur = 0;
@@ -507,7 +367,7 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
         if (have) {
           const int2 ro = rec_ro[ecur];
           const double2 fuv = rec_uv[ecur];
-          const int oc = ro.y & 0xff;
+          const int oc = FeatureGrid::octave_of(ro.y);
           bool ok = true;
           if (bCheckLevels) {
             if (oc < minLevel) ok = false;
@@ -515,7 +375,7 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
           }
           const float distx = (float)(fuv.x - (double)x), disty = (float)(fuv.y - (double)y);
           if (!(fabsf(distx) < rr && fabsf(disty) < rr)) ok = false;
-          if (ok && owner[ro.y >> 8] < m) ok = false;  // taken on entry (-1) or by an earlier map point
+          if (ok && owner[FeatureGrid::feature_of(ro.y)] < m) ok = false;  // taken on entry (-1) or by an earlier map point
           if (ok) {
             const float ur = __int_as_float(ro.x);
             if (ur > 0) {
@@ -570,9 +430,9 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
     const Query q = make_query(m);
     if (!q.valid) return -1;
     const float rr = q.rr, x = q.x, y = q.y;
-    const int x0 = max(0, (int)floorf((x - 0.0f - rr) * P.col_inv)), x1 = min(GC - 1, (int)ceilf((x - 0.0f + rr) * P.col_inv));
-    const int y0 = max(0, (int)floorf((y - 0.0f - rr) * P.row_inv)), y1 = min(GR - 1, (int)ceilf((y - 0.0f + rr) * P.row_inv));
-    if (!(x0 < GC && x1 >= 0 && y0 < GR && y1 >= 0) || y0 > y1 || x0 > x1) return -1;
+    const FeatureGrid::Window win = grid.window(x, y, rr);
+    if (win.x0 > win.x1) return -1;
+    const int x0 = win.x0, x1 = win.x1, y0 = win.y0, y1 = win.y1;
     const int ncols = x1 - x0 + 1;
     int cs = 0, cn = 0;
     if (lane < ncols) {
@@ -601,7 +461,7 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
       }
       if (e >= 0) {
         const int2 ro = rec_ro[e];
-        const int oc = ro.y & 0xff, idx = ro.y >> 8;
+        const int oc = FeatureGrid::octave_of(ro.y), idx = FeatureGrid::feature_of(ro.y);
         bool ok = true;
         if (bCheckLevels) {
           if (oc < minLevel) ok = false;
@@ -633,8 +493,7 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
             da = src[0];
             db = src[1];
           }
-          const int dist = __popc(dm[0] ^ da.x) + __popc(dm[1] ^ da.y) + __popc(dm[2] ^ da.z) + __popc(dm[3] ^ da.w) + __popc(dm[4] ^ db.x) +
-                           __popc(dm[5] ^ db.y) + __popc(dm[6] ^ db.z) + __popc(dm[7] ^ db.w);
+          const int dist = hamming256(dm, da, db);
           if (dist < 256) {
             const unsigned long long kx = ((unsigned long long)dist << 48) | ((unsigned long long)e << 20) | ((unsigned long long)oc << 12) | (unsigned long long)idx;
             if (kx < b0) {
@@ -659,18 +518,14 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
   const int nq_rounds = ((NP + TM - 1) / TM) * TM;  // every thread makes the same number of trips (the walk is wave-uniform)
   // Round 6: the queries that must walk again in a later round (a few per cent) are LISTED and walked densely - a wave per 64 of them -
   // instead of where they sit: one such query in a wave made the whole wave walk, and round 2 cost half of round 1
-  // (profiles/r6_match_stations.txt).  The list lives behind the walk's candidate lists in the grid build's dead cursors; a query that
+  // (profiles/r6_match_walk_ab.txt).  The list lives behind the walk's candidate lists in the grid build's dead cursors; a query that
   // finds it full walks in place, as before.
   uint16_t* rw_list = lst + 4 * TM;
   constexpr int RW_CAP = 2 * NCELL - 4 * TM;
   static_assert(RW_CAP >= 1024, "the cursors hold the walk's lists and the list of queries that walk again");
   while (true) {
-    for (int i = tid; i < NF; i += TM) owner_n[i] = feat_taken[i] ? -1 : INT_MAX;
-    if (tid == 0) {
-      s_changed = 0;
-      s_nrw = 0;
-    }
-    __syncthreads();
+    if (tid == 0) s_nrw = 0;
+    owner_round_begin<TM>(tid, owner_n, NF, &s_changed, [&](int i) { return feat_taken[i] ? -1 : INT_MAX; });
     PW_T(pr0);
     for (int sq = tid; sq < nq_rounds; sq += TM) {
       const bool in = sq < NP;
@@ -747,14 +602,7 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
     }
     __syncthreads();
     PW_T(pr2);
-    int ch = 0;
-    for (int i = tid; i < NF; i += TM) {
-      const int o = owner_n[i];
-      if (o != owner[i]) ch = 1;
-      owner[i] = o;
-    }
-    if (ch) s_changed = 1;
-    __syncthreads();
+    const bool changed = owner_round_end<TM>(tid, owner, owner_n, NF, &s_changed);
     ++rounds;
 #ifdef GL_MATCH_PROF
     if (rounds == 1) tp_r0 = clock64();
@@ -764,7 +612,7 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
       pr_c += clock64() - pr2;
     }
 #endif
-    if (!s_changed || rounds > NP + 1) break;
+    if (!changed || rounds > NP + 1) break;
     __syncthreads();
   }
 
@@ -772,64 +620,13 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
   if (MODE == 1 && P.check_orientation) {
     const float* feat_angle = feat_angle_all + (size_t)f * NF;
     const float* mp_angle = mp_angle_all + (size_t)f * NP;
-    const float factor = 30 / 360.0f;
-    auto bin_of = [&](int i) -> int {  // i: matched feature, owner[i]: its last-frame feature
-      float rot = mp_angle[owner[i]] - feat_angle[i];
-      if (rot < 0.0) rot += 360.0f;
-      int bin = (int)roundf(rot * factor);
-      if (bin == 30) bin = 0;
-      return bin;
-    };
-    if (tid < 32) s_hist[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < NF; i += TM) {
-      const int o = owner[i];
-      if (o >= 0 && o != INT_MAX) {
-        const int b = bin_of(i);
-        if (b >= 0 && b < 30) atomicAdd(&s_hist[b], 1);
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-      for (int i = 0; i < 30; i++) {
-        const int sz = s_hist[i];
-        if (sz > max1) {
-          max3 = max2;
-          max2 = max1;
-          max1 = sz;
-          ind3 = ind2;
-          ind2 = ind1;
-          ind1 = i;
-        } else if (sz > max2) {
-          max3 = max2;
-          max2 = sz;
-          ind3 = ind2;
-          ind2 = i;
-        } else if (sz > max3) {
-          max3 = sz;
-          ind3 = i;
-        }
-      }
-      if (max2 < 0.1f * (float)max1) {
-        ind2 = -1;
-        ind3 = -1;
-      } else if (max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-      }
-      s_keep[0] = ind1;
-      s_keep[1] = ind2;
-      s_keep[2] = ind3;
-    }
-    __syncthreads();
-    for (int i = tid; i < NF; i += TM) {
-      const int o = owner[i];
-      if (o >= 0 && o != INT_MAX) {
-        const int b = bin_of(i);
-        if (b >= 0 && b < 30 && b != s_keep[0] && b != s_keep[1] && b != s_keep[2]) owner[i] = INT_MAX;
-      }
-    }
-    __syncthreads();
+    // i: matched feature, owner[i]: its last-frame feature
+    rotation_filter<TM>(
+        tid, NF, s_hist, s_keep, [&](int i) {
+          const int o = owner[i];
+          return o >= 0 && o != INT_MAX;
+        },
+        [&](int i) { return mp_angle[owner[i]] - feat_angle[i]; }, [&](int i) { owner[i] = INT_MAX; });
   }
 
 #ifdef GL_MATCH_PROF
@@ -844,19 +641,9 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
     feat_match[i] = matched ? o : -1;
     cnt += matched ? 1 : 0;
   }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) cnt += __shfl_xor(cnt, o, 64);
-  if ((tid & 63) == 0) s_scan[tid >> 6] = cnt;
-  __syncthreads();
-  if (tid == 0) {
-    int tot = 0;
-    for (int w = 0; w < TM / 64; ++w) tot += s_scan[w];
-    nmatches_all[f] = tot;
-    if (counters) {  // GL_COUNTER_MATCH_ROUNDS / _UNITS: rounds of the owner fixed point, frames
-      atomicAdd(&counters[1], rounds);
-      atomicAdd(&counters[2], 1);
-    }
+  count_matches<TM>(tid, cnt, s_grid.scan, &nmatches_all[f], counters, rounds);
 #ifdef GL_MATCH_PROF
+  if (tid == 0) {
     feat_match[0] = (int)((tp1 - tp0) >> 4);
     feat_match[1] = (int)((tp2 - tp1) >> 4);
     feat_match[2] = (int)((clock64() - tp2) >> 4);
@@ -874,8 +661,8 @@ __global__ __launch_bounds__(DL ? 1024 : T_M, 4) void k_search_by_projection(  /
     feat_match[14] = (int)(pr_a >> 4);           // later rounds: the queries from their records, the listed walks + barrier, the owners compared
     feat_match[15] = (int)(pr_b >> 4);
     feat_match[16] = (int)(pr_c >> 4);                      // queries listed to walk again in the last round
-#endif
   }
+#endif
 }
 
 }  // namespace
@@ -893,12 +680,10 @@ int launch_match(int mode, gl_ctx_t* ctx, const gl_camera* cam, float scale_fact
   MatchP P;
   P.NF = NF;
   P.NP = NP;
-  P.col_inv = static_cast<float>(GC) / cam->width;  // init_config.hpp:50-54
-  P.row_inv = static_cast<float>(GR) / cam->height;
+  FeatureGrid::scale(cam, &P.col_inv, &P.row_inv);
   P.th = th;
   P.nn_ratio = nn_ratio;
-  P.sf[0] = 1.0f;  // init_config.hpp:63-79
-  for (int i = 1; i < 8; ++i) P.sf[i] = P.sf[i - 1] * scale_factor;
+  pyramid_scales(scale_factor, P.sf, nullptr, nullptr);
   // camera::fx ... are float config scalars (config.h:38-48); PinholeCamera::fx() returns them as double
   const float cfx = (float)cam->fx, cfy = (float)cam->fy, ccx = (float)cam->cx, ccy = (float)cam->cy, cbf = (float)cam->bf;
   P.fx = cfx;

@@ -15,27 +15,12 @@
 #include <climits>
 
 #include "gl_internal.hpp"
+#include "gl_match_common.hpp"
 
 namespace {
 
+using namespace gl_match;
 constexpr int T_B = 512;
-
-__device__ __forceinline__ int hamming256(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b) {
-  int d = 0;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) d += __popc(a[w] ^ b[w]);
-  return d;
-}
-// largest i with ptr[i] <= a  (the node of list entry a)
-__device__ __forceinline__ int node_of(const int32_t* __restrict__ ptr, int nn, int a) {
-  int lo = 0, hi = nn;  // ptr[lo] <= a < ptr[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= a) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 __global__ __launch_bounds__(T_B) void k_search_by_bow(int B, int N1, int N2, int NN1, int NN2, float nn_ratio, int check_orientation,
                                                        const float* __restrict__ angle1_all, const uint8_t* __restrict__ desc1_all,
@@ -51,13 +36,8 @@ __global__ __launch_bounds__(T_B) void k_search_by_bow(int B, int N1, int N2, in
   int32_t* owner = lds;            // N2: lowest query that claimed the frame feature in the previous round (INT_MAX: nobody)
   int32_t* owner_n = owner + N2;   // N2: being rebuilt
   int32_t* choice = owner_n + N2;  // N1 (by query): the frame feature an ACCEPTING query takes, else -1
-  int32_t* q_idx1 = choice + N1;   // N1: the query's key-frame feature, or -1 (no valid map point, node not shared)
-  int32_t* q_lo = q_idx1 + N1;     // N1: its candidates = node_idx2[q_lo .. q_hi)
-  int32_t* q_hi = q_lo + N1;
-  // the three tables the queries are set up from (two binary searches per query: sixteen dependent GLOBAL loads each before round 5)
-  int32_t* s_nptr1 = q_hi + N1;            // NN1 + 1
-  int32_t* s_nid2 = s_nptr1 + NN1 + 1;   // NN2
-  int32_t* s_nptr2 = s_nid2 + NN2;       // NN2 + 1
+  const NodeQueries nodes(choice + N1, N1, NN1, NN2);
+  const int32_t *q_idx1 = nodes.q_idx1, *q_lo = nodes.q_lo, *q_hi = nodes.q_hi;
   __shared__ int s_changed, s_hist[32], s_keep[4], s_cnt[T_B / 64];
   const int f = blockIdx.x, tid = threadIdx.x;
   if (f >= B) return;
@@ -72,43 +52,14 @@ __global__ __launch_bounds__(T_B) void k_search_by_bow(int B, int N1, int N2, in
   const int32_t* nid2 = nid2_all + (size_t)f * NN2;
   const int32_t* nptr2 = nptr2_all + (size_t)f * (NN2 + 1);
   const int32_t* nidx2 = nidx2_all + (size_t)f * N2;
-  const int nq = nn1 > 0 ? min(nptr1[nn1], N1) : 0;  // list entries of the key-frame = queries, in the reference's visiting order
 
-  for (int i = tid; i <= nn1; i += T_B) s_nptr1[i] = nptr1[i];
-  for (int i = tid; i <= nn2; i += T_B) {
-    s_nptr2[i] = nptr2[i];
-    if (i < nn2) s_nid2[i] = nid2[i];
-  }
-  __syncthreads();
-  for (int a = tid; a < N1; a += T_B) {
-    int idx1 = -1, lo = 0, hi = 0;
-    if (a < nq) {
-      const int n1 = node_of(s_nptr1, nn1, a);
-      const int id = nid1[n1];
-      int l = 0, h = nn2;  // lower_bound of id in nid2
-      while (l < h) {
-        const int mid = (l + h) >> 1;
-        if (s_nid2[mid] < id) l = mid + 1;
-        else h = mid;
-      }
-      if (l < nn2 && s_nid2[l] == id) {
-        const int i1 = nidx1[a];
-        if (i1 >= 0 && i1 < N1 && mp1[i1]) {
-          idx1 = i1;
-          lo = s_nptr2[l];
-          hi = min(s_nptr2[l + 1], N2);
-        }
-      }
-    }
-    q_idx1[a] = idx1;
-    q_lo[a] = lo;
-    q_hi[a] = hi;
-    choice[a] = -1;
-  }
+  // ---- queries: the key-frame's features that hold a valid map point ----
+  for (int a = tid; a < N1; a += T_B) choice[a] = -1;
+  const int nq = nodes.setup<T_B>(tid, N1, N2, nn1, nn2, nid1, nptr1, nidx1, nid2, nptr2, [&](int i1) { return mp1[i1] != 0; });
   for (int i = tid; i < N2; i += T_B) owner[i] = INT_MAX;
   __syncthreads();
 
-  // Round 5 (as in gl_match.hip / gl_match_tri.hip): a query's partners and their distances do not depend on the owners, which only
+  // Round 5: a query's partners and their distances do not depend on the owners, which only
   // REMOVE partners.  best = first of the smallest distance, second best = the smallest of the rest: the two smallest keys
   //     dist << 22 | position in the partner list << 12 | feature of the frame.
   // Round 1 evaluates every partner once (descriptors requested four at a time) and leaves the three smallest keys and their number
@@ -148,8 +99,7 @@ __global__ __launch_bounds__(T_B) void k_search_by_bow(int B, int N1, int N2, in
       for (int j = 0; j < 4; ++j) {
         const int idx2 = id[j];
         if (idx2 < 0) continue;
-        const int dist = __popc(d1[0] ^ da[j].x) + __popc(d1[1] ^ da[j].y) + __popc(d1[2] ^ da[j].z) + __popc(d1[3] ^ da[j].w) +
-                         __popc(d1[4] ^ db[j].x) + __popc(d1[5] ^ db[j].y) + __popc(d1[6] ^ db[j].z) + __popc(d1[7] ^ db[j].w);
+        const int dist = hamming256(d1, da[j], db[j]);
         if (dist >= 256) continue;  // (never below the initial best / second best)
         const int ord = b0 + j - lo;
         if (ord > 1023) {  // (a node of more than 1 024 partners cannot be keyed: the sequential evaluation, in every round)
@@ -158,19 +108,7 @@ __global__ __launch_bounds__(T_B) void k_search_by_bow(int B, int N1, int N2, in
         }
         const uint32_t kx = ((uint32_t)dist << 22) | ((uint32_t)ord << 12) | (uint32_t)idx2;
         if (npass != EMPTY) ++npass;
-        if (kx < k2) {
-          k2 = kx;
-          if (k2 < k1) {
-            const uint32_t t = k1;
-            k1 = k2;
-            k2 = t;
-          }
-          if (k1 < k0) {
-            const uint32_t t = k0;
-            k0 = k1;
-            k1 = t;
-          }
-        }
+        keep3(k0, k1, k2, kx);
       }
     }
   };
@@ -196,9 +134,7 @@ __global__ __launch_bounds__(T_B) void k_search_by_bow(int B, int N1, int N2, in
   };
   int rounds = 0;
   for (;;) {
-    for (int i = tid; i < N2; i += T_B) owner_n[i] = INT_MAX;
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
+    owner_round_begin<T_B>(tid, owner_n, N2, &s_changed, [](int) { return INT_MAX; });
     for (int m = tid; m < nq; m += T_B) {
       const int idx1 = q_idx1[m];
       int take = -1;
@@ -239,78 +175,20 @@ __global__ __launch_bounds__(T_B) void k_search_by_bow(int B, int N1, int N2, in
       if (take >= 0) atomicMin(&owner_n[take], m);
     }
     __syncthreads();
-    int ch = 0;
-    for (int i = tid; i < N2; i += T_B) {
-      const int o = owner_n[i];
-      if (o != owner[i]) ch = 1;
-      owner[i] = o;
-    }
-    if (ch) s_changed = 1;
-    __syncthreads();
+    const bool changed = owner_round_end<T_B>(tid, owner, owner_n, N2, &s_changed);
     ++rounds;
-    if (!s_changed || rounds > nq + 1) break;
+    if (!changed || rounds > nq + 1) break;
     __syncthreads();
   }
 
-  // ---- rotation consistency (:362-374, :391-405, computeThreeMaxima :544-578) ------------------------------------------
+  // ---- rotation consistency (:362-374, :391-405) ------------------------------------------------------------------------
   // (in the fixed point every accepting query owns its choice)
   if (check_orientation) {
     const float* angle1 = angle1_all + (size_t)f * N1;
     const float* angle2 = angle2_all + (size_t)f * N2;
-    const float factor = 30 / 360.0f;
-    auto bin_of = [&](int m) -> int {
-      float rot = angle1[q_idx1[m]] - angle2[choice[m]];
-      if (rot < 0.0) rot += 360.0f;
-      int bin = (int)roundf(rot * factor);
-      if (bin == 30) bin = 0;
-      return bin;
-    };
-    if (tid < 32) s_hist[tid] = 0;
-    __syncthreads();
-    for (int m = tid; m < nq; m += T_B)
-      if (choice[m] >= 0) {
-        const int b = bin_of(m);
-        if (b >= 0 && b < 30) atomicAdd(&s_hist[b], 1);
-      }
-    __syncthreads();
-    if (tid == 0) {
-      int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-      for (int i = 0; i < 30; i++) {
-        const int sz = s_hist[i];
-        if (sz > max1) {
-          max3 = max2;
-          max2 = max1;
-          max1 = sz;
-          ind3 = ind2;
-          ind2 = ind1;
-          ind1 = i;
-        } else if (sz > max2) {
-          max3 = max2;
-          max2 = sz;
-          ind3 = ind2;
-          ind2 = i;
-        } else if (sz > max3) {
-          max3 = sz;
-          ind3 = i;
-        }
-      }
-      if (max2 < 0.1f * (float)max1) {
-        ind2 = -1;
-        ind3 = -1;
-      } else if (max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-      }
-      s_keep[0] = ind1;
-      s_keep[1] = ind2;
-      s_keep[2] = ind3;
-    }
-    __syncthreads();
-    for (int m = tid; m < nq; m += T_B)
-      if (choice[m] >= 0) {
-        const int b = bin_of(m);
-        if (b >= 0 && b < 30 && b != s_keep[0] && b != s_keep[1] && b != s_keep[2]) choice[m] = -1;
-      }
-    __syncthreads();
+    rotation_filter<T_B>(
+        tid, nq, s_hist, s_keep, [&](int m) { return choice[m] >= 0; }, [&](int m) { return angle1[q_idx1[m]] - angle2[choice[m]]; },
+        [&](int m) { choice[m] = -1; });
   }
 
   // ---- outputs: matches by FRAME feature (the key-frame feature whose map point it gets) ------------------------------------
@@ -323,19 +201,7 @@ __global__ __launch_bounds__(T_B) void k_search_by_bow(int B, int N1, int N2, in
       match[choice[m]] = q_idx1[m];
       ++cnt;
     }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) cnt += __shfl_xor(cnt, o, 64);
-  if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
-  __syncthreads();
-  if (tid == 0) {
-    int tot = 0;
-    for (int w = 0; w < T_B / 64; ++w) tot += s_cnt[w];
-    nmatches_all[f] = tot;
-    if (counters) {  // GL_COUNTER_MATCH_ROUNDS / _UNITS
-      atomicAdd(&counters[1], rounds);
-      atomicAdd(&counters[2], 1);
-    }
-  }
+  count_matches<T_B>(tid, cnt, s_cnt, &nmatches_all[f], counters, rounds);
 }
 
 }  // namespace
@@ -365,7 +231,7 @@ int gl::launch_bow_gated(gl_ctx_t* ctx, float nn_ratio, int check_orientation, i
              "null buffer");
   gl::Ctx* c = gl::C(ctx);
   GL_HIP(hipSetDevice(c->device));
-  const size_t lds = ((size_t)2 * N2 + 4 * (size_t)N1 + (size_t)NN1 + 2 * (size_t)NN2 + 2) * sizeof(int32_t);
+  const size_t lds = NodeQueries::matcher_lds(N1, N2, NN1, NN2);
   GL_REQUIRE_LDS(c, lds);
   GL_HIP(gl::ensure_dynamic_lds(c, (const void*)k_search_by_bow, lds));
   void* cache = nullptr;  // 16 bytes per query: its three best partners of round 1

@@ -19,33 +19,17 @@
 #include <climits>
 
 #include "gl_internal.hpp"
+#include "gl_match_common.hpp"
 
 namespace {
 
+using namespace gl_match;
 constexpr int T_T = 512;
 
 struct TriP {
   int N1, N2, NN1, NN2, only_stereo, check_orientation;
   float sf[8], sigma2[8];
 };
-
-__device__ __forceinline__ int hamming256(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b) {
-  int d = 0;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) d += __popc(a[w] ^ b[w]);
-  return d;
-}
-
-// largest i with ptr[i] <= a  (the node of list entry a)
-__device__ __forceinline__ int node_of(const int32_t* __restrict__ ptr, int nn, int a) {
-  int lo = 0, hi = nn;  // ptr[lo] <= a < ptr[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= a) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 __global__ __launch_bounds__(T_T) void k_search_for_triangulation(
     TriP P, int B, const double* __restrict__ uv1_all, const float* __restrict__ ur1_all, const int32_t* __restrict__ oct1_all,
@@ -61,13 +45,8 @@ __global__ __launch_bounds__(T_T) void k_search_for_triangulation(
   int32_t* owner = lds;             // N2: lowest query that picked the feature in the previous round (-1: not available at all)
   int32_t* owner_n = owner + N2;    // N2: being rebuilt
   int32_t* choice = owner_n + N2;   // N1 (by query)
-  int32_t* q_idx1 = choice + N1;    // N1: the query's feature of key-frame 1, or -1 (not a query: map point, mono under only-stereo, node not shared)
-  int32_t* q_lo = q_idx1 + N1;      // N1: its partners = node_idx2[q_lo .. q_hi)
-  int32_t* q_hi = q_lo + N1;
-  // the three tables the queries are set up from (two binary searches per query: sixteen dependent GLOBAL loads each before round 5)
-  int32_t* s_nptr1 = q_hi + N1;            // NN1 + 1
-  int32_t* s_nid2 = s_nptr1 + P.NN1 + 1;   // NN2
-  int32_t* s_nptr2 = s_nid2 + P.NN2;       // NN2 + 1
+  const NodeQueries nodes(choice + N1, N1, P.NN1, P.NN2);
+  const int32_t *q_idx1 = nodes.q_idx1, *q_lo = nodes.q_lo, *q_hi = nodes.q_hi;
   __shared__ int s_changed, s_hist[32], s_keep[4], s_cnt[T_T / 64];
   const int f = blockIdx.x, tid = threadIdx.x;
   if (f >= B) return;
@@ -90,40 +69,12 @@ __global__ __launch_bounds__(T_T) void k_search_for_triangulation(
   const int32_t* nidx2 = nidx2_all + (size_t)f * N2;
   const double* F = fmat_all + (size_t)f * 9;
   const float ex = epi_all[2 * f], ey = epi_all[2 * f + 1];
-  const int nq = nn1 > 0 ? min(nptr1[nn1], N1) : 0;  // list entries of key-frame 1 = queries, in the reference's visiting order
 
   // ---- queries: list entry a of key-frame 1 -> its feature and the partner list of the same node in key-frame 2 ----
-  for (int i = tid; i <= nn1; i += T_T) s_nptr1[i] = nptr1[i];
-  for (int i = tid; i <= nn2; i += T_T) {
-    s_nptr2[i] = nptr2[i];
-    if (i < nn2) s_nid2[i] = nid2[i];
-  }
-  __syncthreads();
-  for (int a = tid; a < N1; a += T_T) {
-    int idx1 = -1, lo = 0, hi = 0;
-    if (a < nq) {
-      const int n1 = node_of(s_nptr1, nn1, a);
-      const int id = nid1[n1];
-      int l = 0, h = nn2;  // lower_bound of id in nid2
-      while (l < h) {
-        const int mid = (l + h) >> 1;
-        if (s_nid2[mid] < id) l = mid + 1;
-        else h = mid;
-      }
-      if (l < nn2 && s_nid2[l] == id) {
-        const int i1 = nidx1[a];
-        if (i1 >= 0 && i1 < N1 && oct1[i1] >= 0 && !mp1[i1] && !(P.only_stereo && !(ur1[i1] >= 0))) {
-          idx1 = i1;
-          lo = s_nptr2[l];
-          hi = min(s_nptr2[l + 1], N2);
-        }
-      }
-    }
-    q_idx1[a] = idx1;
-    q_lo[a] = lo;
-    q_hi[a] = hi;
-    choice[a] = -1;
-  }
+  // (who may ask: not the features with a map point, nor the mono ones under only-stereo)
+  for (int a = tid; a < N1; a += T_T) choice[a] = -1;
+  const int nq = nodes.setup<T_T>(tid, N1, N2, nn1, nn2, nid1, nptr1, nidx1, nid2, nptr2,
+                                  [&](int i1) { return oct1[i1] >= 0 && !mp1[i1] && !(P.only_stereo && !(ur1[i1] >= 0)); });
   for (int i = tid; i < N2; i += T_T) owner[i] = (oct2[i] >= 0 && !mp2[i] && !(P.only_stereo && !(ur2[i] >= 0))) ? INT_MAX : -1;
   __syncthreads();
 
@@ -171,8 +122,7 @@ __global__ __launch_bounds__(T_T) void k_search_for_triangulation(
       for (int j = 0; j < 4; ++j) {
         const int idx2 = id[j];
         if (idx2 < 0) continue;
-        const int dist = __popc(d1[0] ^ da[j].x) + __popc(d1[1] ^ da[j].y) + __popc(d1[2] ^ da[j].z) + __popc(d1[3] ^ da[j].w) +
-                         __popc(d1[4] ^ db[j].x) + __popc(d1[5] ^ db[j].y) + __popc(d1[6] ^ db[j].z) + __popc(d1[7] ^ db[j].w);
+        const int dist = hamming256(d1, da[j], db[j]);
         if (dist > 50) continue;  // TH_LOW
         const double u2 = uv2[2 * idx2], v2 = uv2[2 * idx2 + 1];
         const int oc2 = oct2[idx2] & 7;
@@ -192,19 +142,7 @@ __global__ __launch_bounds__(T_T) void k_search_for_triangulation(
         }
         uint32_t kx = ((uint32_t)dist << 26) | ((uint32_t)(1023 - ord) << 16) | (uint32_t)idx2;
         if (npass != EMPTY) ++npass;
-        if (kx < k2) {
-          k2 = kx;
-          if (k2 < k1) {
-            const uint32_t t = k1;
-            k1 = k2;
-            k2 = t;
-          }
-          if (k1 < k0) {
-            const uint32_t t = k0;
-            k0 = k1;
-            k1 = t;
-          }
-        }
+        keep3(k0, k1, k2, kx);
       }
     }
   };
@@ -244,9 +182,7 @@ __global__ __launch_bounds__(T_T) void k_search_for_triangulation(
   };
   int rounds = 0;
   for (;;) {
-    for (int i = tid; i < N2; i += T_T) owner_n[i] = owner[i] < 0 ? -1 : INT_MAX;
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
+    owner_round_begin<T_T>(tid, owner_n, N2, &s_changed, [&](int i) { return owner[i] < 0 ? -1 : INT_MAX; });
     for (int m = tid; m < nq; m += T_T) {
       const int idx1 = q_idx1[m];
       int bestIdx2 = -1;
@@ -285,78 +221,20 @@ __global__ __launch_bounds__(T_T) void k_search_for_triangulation(
       if (bestIdx2 >= 0) atomicMin(&owner_n[bestIdx2], m);
     }
     __syncthreads();
-    int ch = 0;
-    for (int i = tid; i < N2; i += T_T) {
-      const int o = owner_n[i];
-      if (o != owner[i]) ch = 1;
-      owner[i] = o;
-    }
-    if (ch) s_changed = 1;
-    __syncthreads();
+    const bool changed = owner_round_end<T_T>(tid, owner, owner_n, N2, &s_changed);
     ++rounds;
-    if (!s_changed || rounds > nq + 1) break;
+    if (!changed || rounds > nq + 1) break;
     __syncthreads();
   }
 
-  // ---- rotation consistency (:235-246, :264-281, computeThreeMaxima :544-578) ----------------------------------------
+  // ---- rotation consistency (:235-246, :264-281) ----------------------------------------------------------------------
   // (a query keeps its choice iff it owns it: in the fixed point every choice is owned by its query)
   if (P.check_orientation) {
     const float* angle1 = angle1_all + (size_t)f * N1;
     const float* angle2 = angle2_all + (size_t)f * N2;
-    const float factor = 30 / 360.0f;
-    auto bin_of = [&](int m) -> int {
-      float rot = angle1[q_idx1[m]] - angle2[choice[m]];
-      if (rot < 0.0) rot += 360.0f;
-      int bin = (int)roundf(rot * factor);
-      if (bin == 30) bin = 0;
-      return bin;
-    };
-    if (tid < 32) s_hist[tid] = 0;
-    __syncthreads();
-    for (int m = tid; m < nq; m += T_T)
-      if (choice[m] >= 0) {
-        const int b = bin_of(m);
-        if (b >= 0 && b < 30) atomicAdd(&s_hist[b], 1);
-      }
-    __syncthreads();
-    if (tid == 0) {
-      int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-      for (int i = 0; i < 30; i++) {
-        const int sz = s_hist[i];
-        if (sz > max1) {
-          max3 = max2;
-          max2 = max1;
-          max1 = sz;
-          ind3 = ind2;
-          ind2 = ind1;
-          ind1 = i;
-        } else if (sz > max2) {
-          max3 = max2;
-          max2 = sz;
-          ind3 = ind2;
-          ind2 = i;
-        } else if (sz > max3) {
-          max3 = sz;
-          ind3 = i;
-        }
-      }
-      if (max2 < 0.1f * (float)max1) {
-        ind2 = -1;
-        ind3 = -1;
-      } else if (max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-      }
-      s_keep[0] = ind1;
-      s_keep[1] = ind2;
-      s_keep[2] = ind3;
-    }
-    __syncthreads();
-    for (int m = tid; m < nq; m += T_T)
-      if (choice[m] >= 0) {
-        const int b = bin_of(m);
-        if (b >= 0 && b < 30 && b != s_keep[0] && b != s_keep[1] && b != s_keep[2]) choice[m] = -1;
-      }
-    __syncthreads();
+    rotation_filter<T_T>(
+        tid, nq, s_hist, s_keep, [&](int m) { return choice[m] >= 0; }, [&](int m) { return angle1[q_idx1[m]] - angle2[choice[m]]; },
+        [&](int m) { choice[m] = -1; });
   }
 
   // ---- outputs: matches12 by feature of key-frame 1 ----------------------------------------------------------------
@@ -369,19 +247,7 @@ __global__ __launch_bounds__(T_T) void k_search_for_triangulation(
       match[q_idx1[m]] = choice[m];
       ++cnt;
     }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) cnt += __shfl_xor(cnt, o, 64);
-  if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
-  __syncthreads();
-  if (tid == 0) {
-    int tot = 0;
-    for (int w = 0; w < T_T / 64; ++w) tot += s_cnt[w];
-    nmatches_all[f] = tot;
-    if (counters) {  // GL_COUNTER_MATCH_ROUNDS / _UNITS
-      atomicAdd(&counters[1], rounds);
-      atomicAdd(&counters[2], 1);
-    }
-  }
+  count_matches<T_T>(tid, cnt, s_cnt, &nmatches_all[f], counters, rounds);
 }
 
 // ---- matches -> the per-match arrays of gl_create_map_points, on the device ----------------------------------------------
@@ -542,13 +408,8 @@ extern "C" int gl_search_for_triangulation(gl_ctx_t* ctx, float scale_factor, in
   P.NN2 = NN2;
   P.only_stereo = only_stereo;
   P.check_orientation = check_orientation;
-  P.sf[0] = 1.0f;  // init_config.hpp:63-79
-  P.sigma2[0] = 1.0f;
-  for (int i = 1; i < 8; ++i) {
-    P.sf[i] = P.sf[i - 1] * scale_factor;
-    P.sigma2[i] = P.sf[i] * P.sf[i];
-  }
-  const size_t lds = ((size_t)2 * N2 + 4 * (size_t)N1 + (size_t)NN1 + 2 * (size_t)NN2 + 2) * sizeof(int32_t);
+  pyramid_scales(scale_factor, P.sf, P.sigma2, nullptr);
+  const size_t lds = NodeQueries::matcher_lds(N1, N2, NN1, NN2);
   GL_REQUIRE_LDS(c, lds);
   GL_HIP(gl::ensure_dynamic_lds(c, (const void*)k_search_for_triangulation, lds));
   void* cache = nullptr;  // 16 bytes per query: its three best partners of round 1 (the kernel's round loop)

@@ -11,6 +11,7 @@
 // computeActiveErrors(), i.e. evaluated before the final update.
 #include "gl_device.hpp"
 #include "gl_internal.hpp"
+#include "gl_match_common.hpp"
 
 using namespace gld;
 
@@ -736,12 +737,7 @@ int gl_create_map_points(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* ca
   t.mbf = (float)cam->bf;
   t.mb = t.mbf / t.ffx;
   t.ratio_factor = 1.5f * scale_factor;
-  t.sf[0] = 1.0f;
-  t.sigma2[0] = 1.0f;
-  for (int i = 1; i < 8; ++i) {
-    t.sf[i] = t.sf[i - 1] * scale_factor;
-    t.sigma2[i] = t.sf[i] * t.sf[i];
-  }
+  gl_match::pyramid_scales(scale_factor, t.sf, t.sigma2, nullptr);
   t.width = cam->width;
   t.height = cam->height;
   const int grid = (N + 63) / 64;

@@ -34,6 +34,19 @@ class gl_local_map_io(C.Structure):
                 [(k, C.c_void_p) for k in ("local_kf", "n_local_kf", "local_mp", "n_local_mp", "ref_kf", "kf_count", "status")])
 
 
+class gl_map_ba_view(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("kf_pose", "kf_twc", "kf_uvr", "kf_oct", "obs_feat", "mp_assoc")] +
+                [("kf_first", C.c_int32), ("reserved_", C.c_int32)])
+
+
+BA_WINDOW_ARRAYS = ("poses", "prior", "points", "assoc", "obs_ptr", "obs_pose", "obs_uvr", "obs_oct", "win_kf", "win_mp", "win_obs", "sizes",
+                    "status")
+
+
+class gl_ba_window(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("Pcap", "Fcap", "Lcap", "Ocap")] + [(k, C.c_void_p) for k in BA_WINDOW_ARRAYS])
+
+
 _lib = None
 
 
@@ -98,6 +111,9 @@ def load():
         "gl_track_frame_chain_back": (i32, [vp, vp, vp, C.c_float, i32, i32, i32, i32, vp, C.c_float, C.c_float]),
         "gl_update_local_map": (i32, [vp, vp, i32, i32, i32, i32] + [vp] * 8),
         "gl_track_frame_chain_map": (i32, [vp, vp, vp, C.c_float, i32, i32, i32, i32, vp, vp, vp, C.c_float, C.c_float, C.c_float, i32]),
+        "gl_update_connections": (i32, [vp, vp, i32, vp, i32] + [vp] * 5),
+        "gl_ba_window_build": (i32, [vp, vp, vp, i32, vp, vp]),
+        "gl_ba_window_apply": (i32, [vp, vp, vp, vp, i32, vp] + [vp] * 5),
         "gl_search_local_points": (i32, [vp, vp, C.c_float, i32, i32, i32] + [vp] * 13 + [C.c_float, C.c_float, vp, vp, vp]),
         "gl_gather_triangulation_matches": (i32, [vp, i32, i32, i32, i32, i32] + [vp] * 32),
         "gl_optimize_point": (i32, [vp, vp, P(gl_camera), P(gl_params), i32] + [vp] * 10),

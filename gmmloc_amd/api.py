@@ -803,6 +803,189 @@ def track_frame_chain_map(ctx, cam, prm, a, map, lm, th_mm=7.0, th_local=3.0, nn
     return out
 
 
+# ---- the mapping thread on the resident map: covisibility, the local-BA window, the write-back (gmmloc_hip.h)
+MAP_BA_DTYPES = {"kf_pose": "float64", "kf_twc": "float64", "kf_uvr": "float64", "kf_oct": "int32", "obs_feat": "int32", "mp_assoc": "int32"}
+CONN_KEPT, CONN_TRUNCATED, CONN_BAD_ROW = 1, 2, 4
+BA_WINDOW_NO_CONN, BA_WINDOW_P_TRUNCATED, BA_WINDOW_F_TRUNCATED, BA_WINDOW_L_TRUNCATED, BA_WINDOW_O_TRUNCATED, BA_WINDOW_BAD_ROW = 1, 2, 4, 8, 16, 32
+BA_WINDOW_TRUNCATED, BA_WINDOW_DROPPED_SHIFT = 30, 8
+BA_WINDOW_DTYPES = {"poses": "float64", "prior": "uint8", "points": "float64", "assoc": "int32", "obs_ptr": "int32", "obs_pose": "int32",
+                    "obs_uvr": "float64", "obs_oct": "int32", "win_kf": "int32", "win_mp": "int32", "win_obs": "int32", "sizes": "int32",
+                    "status": "int32"}
+
+
+def _map_ba_view(ba, v, dev):
+    """dict of CUDA tensors (keys of MAP_BA_DTYPES; kf_twc optional) + kf_first (int, -1: none) -> gl_map_ba_view for the map view v"""
+    for k in ba:
+        assert k in MAP_BA_DTYPES or k == "kf_first", "ba[%r]: unknown key" % k
+    shapes = {"kf_pose": (v.NKF, 7), "kf_twc": (v.NKF, 3), "kf_uvr": (v.NKF, v.NFK, 3), "kf_oct": (v.NKF, v.NFK), "obs_feat": (v.NOBS,),
+              "mp_assoc": (v.NMP,)}
+    w = _lib.gl_map_ba_view()
+    for k, dt in MAP_BA_DTYPES.items():
+        if k == "kf_twc" and ba.get(k) is None:
+            continue
+        setattr(w, k, _ptr(_tensor("ba[%r]" % k, ba.get(k), dt, shapes[k], dev)))
+    w.kf_first = int(ba.get("kf_first", -1))
+    return w
+
+
+def update_connections(ctx, map, kf_row, Ccap=None, out=None, want_count=False):
+    """gl_update_connections: KeyFrame::updateConnections (keyframe.cpp:243-316) for the B key-frame rows kf_row (B,) i32 on the map
+    of update_local_map (rules and the tie rule - lowest row first: gmmloc_hip.h).  -> dict(conn_kf (B,Ccap), conn_w (B,Ccap), n_conn
+    (B,) the true lengths, status (B,)[, kf_count (B,NKF)]); `out`: the same dict to write into (a key-frame with an empty counter
+    keeps its lists)."""
+    import torch
+    v, dev = _map_view(map, False)
+    _tensor("kf_row", kf_row, "int32", (None,), dev)
+    B = kf_row.shape[0]
+    if out is None:
+        assert Ccap is not None, "Ccap or out"
+        z = lambda *sh: torch.zeros(sh, dtype=torch.int32, device=dev)
+        out = dict(conn_kf=torch.full((B, Ccap), -1, dtype=torch.int32, device=dev), conn_w=z(B, Ccap), n_conn=z(B), status=z(B))
+        if want_count:
+            out["kf_count"] = z(B, v.NKF)
+    _tensor("out['conn_kf']", out.get("conn_kf"), "int32", (B, None), dev)
+    Ccap = out["conn_kf"].shape[1]
+    _tensor("out['conn_w']", out.get("conn_w"), "int32", (B, Ccap), dev)
+    for k in ("n_conn", "status"):
+        _tensor("out[%r]" % k, out.get(k), "int32", (B,), dev)
+    if out.get("kf_count") is not None:
+        _tensor("out['kf_count']", out["kf_count"], "int32", (B, v.NKF), dev)
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_update_connections(ctx.h, C.byref(v), B, _ptr(kf_row), Ccap, _ptr(out["conn_kf"]), _ptr(out["conn_w"]),
+                                             _ptr(out["n_conn"]), _ptr(out.get("kf_count")), _ptr(out["status"])))
+    finally:
+        ctx._exit()
+    return out
+
+
+def ba_window_slab(B, Pcap, Fcap, Lcap, Ocap, device="cuda"):
+    """B empty local-BA slabs of these capacities (gl_ba_window: the arrays gl_joint_optimization takes, the back-maps win_kf / win_mp /
+    win_obs, sizes, status) + the BA's outputs of the same capacities (dropped (B,Lcap) u8, erase (B,Ocap) u8, iters (B,)) and the
+    write-back's (erase_obs (B,Ocap), n_erase (B,))."""
+    import torch
+    shapes = {"poses": (B, Pcap + Fcap, 7), "prior": (B, Pcap), "points": (B, Lcap, 3), "assoc": (B, Lcap), "obs_ptr": (B, Lcap + 1),
+              "obs_pose": (B, Ocap), "obs_uvr": (B, Ocap, 3), "obs_oct": (B, Ocap), "win_kf": (B, Pcap + Fcap), "win_mp": (B, Lcap),
+              "win_obs": (B, Ocap), "sizes": (B, 4), "status": (B,)}
+    s = {k: torch.zeros(sh, dtype=getattr(torch, BA_WINDOW_DTYPES[k]), device=device) for k, sh in shapes.items()}
+    s.update(dropped=torch.zeros((B, Lcap), dtype=torch.uint8, device=device), erase=torch.zeros((B, Ocap), dtype=torch.uint8, device=device),
+             iters=torch.zeros(B, dtype=torch.int32, device=device), erase_obs=torch.zeros((B, Ocap), dtype=torch.int32, device=device),
+             n_erase=torch.zeros(B, dtype=torch.int32, device=device))
+    return s
+
+
+def _ba_window(slab, dev):
+    B, Pcap = _tensor("slab['prior']", slab.get("prior"), "uint8", (None, None), dev).shape
+    PF = _tensor("slab['poses']", slab.get("poses"), "float64", (B, None, 7), dev).shape[1]
+    Lcap = _tensor("slab['assoc']", slab.get("assoc"), "int32", (B, None), dev).shape[1]
+    Ocap = _tensor("slab['obs_pose']", slab.get("obs_pose"), "int32", (B, None), dev).shape[1]
+    assert PF >= Pcap, "slab['poses']: fewer poses than slab['prior'] has free ones"
+    shapes = {"points": (B, Lcap, 3), "obs_ptr": (B, Lcap + 1), "obs_uvr": (B, Ocap, 3), "obs_oct": (B, Ocap), "win_kf": (B, PF), "win_mp": (B, Lcap),
+              "win_obs": (B, Ocap), "sizes": (B, 4), "status": (B,)}
+    w = _lib.gl_ba_window()
+    w.Pcap, w.Fcap, w.Lcap, w.Ocap = Pcap, PF - Pcap, Lcap, Ocap
+    for k, dt in BA_WINDOW_DTYPES.items():
+        setattr(w, k, _ptr(_tensor("slab[%r]" % k, slab.get(k), dt, shapes[k], dev) if k in shapes else slab[k]))
+    return w, B
+
+
+def ba_window_build(ctx, map, ba, kf_row, slab):
+    """gl_ba_window_build: the local-BA windows of the key-frame rows kf_row (B,) i32 from the resident map - the selection of
+    Localization::jointOptimization (localization_opt.cpp:460-516) and its flattening (:639-763), reproduced quirks in gmmloc_hip.h.
+    `map`: the dict of update_local_map + mp_pos; `ba`: dict(kf_pose (NKF,7), [kf_twc (NKF,3),] kf_uvr (NKF,NFK,3) f64, kf_oct (NKF,NFK),
+    obs_feat (NOBS,), mp_assoc (NMP,) i32, kf_first int); `slab`: ba_window_slab's dict, written in place and returned (sizes (B,4) =
+    the true P, F, L, nobs; status (B,))."""
+    v, dev = _map_view(map, False)
+    _tensor("map['mp_pos']", map.get("mp_pos"), "float64", (v.NMP, 3), dev)
+    w = _map_ba_view(ba, v, dev)
+    win, B = _ba_window(slab, dev)
+    _tensor("kf_row", kf_row, "int32", (B,), dev)
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_ba_window_build(ctx.h, C.byref(v), C.byref(w), B, _ptr(kf_row), C.byref(win)))
+    finally:
+        ctx._exit()
+    return slab
+
+
+def ba_window_apply(ctx, map, ba, slab):
+    """gl_ba_window_apply: the write-back of jointOptimization (:837-853, :898-922) from the slabs after the BA (slab['dropped'],
+    ['erase'], ['iters'] = its outputs) onto the resident rows: ba['kf_pose'], ba['kf_twc'] (when given), map['mp_pos'], ba['mp_assoc'].
+    -> (erase_obs (B,Ocap) i32: the CSR positions of the observations to remove, ascending; n_erase (B,)) = slab['erase_obs'], ['n_erase']."""
+    v, dev = _map_view(map, False)
+    _tensor("map['mp_pos']", map.get("mp_pos"), "float64", (v.NMP, 3), dev)
+    w = _map_ba_view(ba, v, dev)
+    win, B = _ba_window(slab, dev)
+    _tensor("slab['dropped']", slab.get("dropped"), "uint8", (B, win.Lcap), dev)
+    _tensor("slab['erase']", slab.get("erase"), "uint8", (B, win.Ocap), dev)
+    _tensor("slab['iters']", slab.get("iters"), "int32", (B,), dev)
+    _tensor("slab['erase_obs']", slab.get("erase_obs"), "int32", (B, win.Ocap), dev)
+    _tensor("slab['n_erase']", slab.get("n_erase"), "int32", (B,), dev)
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_ba_window_apply(ctx.h, C.byref(v), _ptr(map["mp_pos"]), C.byref(w), B, C.byref(win), _ptr(slab["dropped"]),
+                                          _ptr(slab["erase"]), _ptr(slab["iters"]), _ptr(slab["erase_obs"]), _ptr(slab["n_erase"])))
+    finally:
+        ctx._exit()
+    return slab["erase_obs"], slab["n_erase"]
+
+
+def joint_optimization_from_map(ctx, gmm, cam, prm, map, ba, kf_row, caps, stop_flag=None, slab=None):
+    """The local BA of ONE key-frame (row kf_row, an int) on the resident map, nothing flattened or uploaded by the host:
+    ba_window_build -> the 16 bytes of `sizes` to the host -> gl_joint_optimization[_stoppable](B = 1) on the slab -> ba_window_apply.
+    caps = (Pcap, Fcap, Lcap, Ocap); a window that exceeds one is built again, once, in a slab grown to its true sizes.  `slab`: a dict
+    of ba_window_slab(1, ...) to reuse (a mapping thread keeps one).  -> dict(slab, P, F, L, nobs, status, caps (the capacities used);
+    win_kf (P+F,), win_mp (L,), assoc_dropped (L,), obs_erase (nobs,), iters (1,), erase_obs (n_erase,) - views of the slab, for the
+    host's own bookkeeping: removeObservation on erase_obs, before the next build)."""
+    import torch
+    v, dev = _map_view(map, False)
+    _tensor("map['mp_pos']", map.get("mp_pos"), "float64", (v.NMP, 3), dev)
+    w = _map_ba_view(ba, v, dev)
+    caps = tuple(int(c) for c in caps)
+    if slab is None:
+        slab = ba_window_slab(1, *caps, device=dev)
+
+    def run(fn, *args):
+        ctx._enter()
+        try:
+            _check(fn(ctx.h, *args))
+        finally:
+            ctx._exit()
+    for attempt in range(2):
+        win, B = _ba_window(slab, dev)
+        assert B == 1, "slab: one window"
+        if "kf_row" not in slab:
+            slab["kf_row"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        slab["kf_row"].fill_(int(kf_row))
+        run(ctx.lib.gl_ba_window_build, C.byref(v), C.byref(w), 1, _ptr(slab["kf_row"]), C.byref(win))
+        # the one round trip: sizes and status to the host, a synchronise
+        P, F, L, nobs, status = torch.cat((slab["sizes"][0], slab["status"])).tolist()
+        if not status & BA_WINDOW_TRUNCATED:
+            break
+        assert attempt == 0, "the window still exceeds the capacities it asked for"
+        caps = (max(caps[0], P), max(caps[1], F), max(caps[2], L), max(caps[3], nobs))
+        slab = ba_window_slab(1, *caps, device=dev)
+    assert not status & BA_WINDOW_BAD_ROW, "kf_row %d is not a key-frame row" % int(kf_row)
+    s = slab
+    for k in ("iters", "dropped", "erase"):  # (a reused slab: the BA's outputs start from zeros, as in joint_optimization)
+        s[k].zero_()
+    if L > 0 and nobs > 0:
+        args = [gmm.h, C.byref(cam.c()), C.byref(prm.c()), 1, P, F, L, nobs, _ptr(s["poses"]), _ptr(s["prior"]), _ptr(s["points"]),
+                _ptr(s["assoc"]), _ptr(s["obs_ptr"]), _ptr(s["obs_pose"]), _ptr(s["obs_uvr"]), _ptr(s["obs_oct"]), _ptr(s["dropped"]),
+                _ptr(s["erase"]), _ptr(s["iters"])]
+        if stop_flag is None:
+            run(ctx.lib.gl_joint_optimization, *args)
+        else:
+            run(ctx.lib.gl_joint_optimization_stoppable, *(args + [_ptr(stop_flag)]))
+    for k, sh in (("erase_obs", (1, win.Ocap)), ("n_erase", (1,))):
+        _tensor("slab[%r]" % k, s.get(k), "int32", sh, dev)
+    run(ctx.lib.gl_ba_window_apply, C.byref(v), _ptr(map["mp_pos"]), C.byref(w), 1, C.byref(win), _ptr(s["dropped"]), _ptr(s["erase"]),
+        _ptr(s["iters"]), _ptr(s["erase_obs"]), _ptr(s["n_erase"]))
+    n_erase = int(slab["n_erase"][0])
+    return dict(slab=slab, P=P, F=F, L=L, nobs=nobs, status=status, caps=caps, win_kf=s["win_kf"][0, :P + F], win_mp=s["win_mp"][0, :L],
+                assoc_dropped=s["dropped"][0, :L], obs_erase=s["erase"][0, :nobs], iters=s["iters"], erase_obs=s["erase_obs"][0, :n_erase])
+
+
 def search_by_projection_frame(ctx, cam, pose_cw, pose_lw, feat_uv, feat_ur, feat_oct, feat_angle, feat_desc, feat_taken,
                                last_pt, last_valid, last_oct, last_angle, last_desc, th=7.0, mono=False,
                                check_orientation=True, scale_factor=1.2):

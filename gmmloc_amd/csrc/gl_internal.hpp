@@ -154,6 +154,7 @@ enum {
                    // that it needs nothing from the block its caller sized for the fp64 sweep
   SCRATCH_LOCALMAP,  // gl_update_local_map's global-path counters / bitmask, and the local-map arrays gl_track_frame_chain_map gathers
                      // for its stages (which use the three blocks above)
+  SCRATCH_BAWINDOW,  // gl_update_connections / gl_ba_window_build / _apply: per-window words over the map's rows and the window's lists
   SCRATCH_COUNT
 };
 

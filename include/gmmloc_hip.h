@@ -571,6 +571,124 @@ int gl_track_frame_chain_map(gl_ctx_t* ctx, const gl_camera* cam, const gl_param
                              const gl_track_chain_io* io, const gl_map_view* map, const gl_local_map_io* lm, float th_mm, float th_local,
                              float nn_ratio, int mono);
 
+/* ---- the mapping thread on the resident map: covisibility, the local-BA window, the write-back ----
+ * KeyFrame::updateConnections (keyframe.cpp:243-316) for B key-frames kf_row (B int32 rows of the map's key-frame tables), over the
+ * gl_map_view of gl_update_local_map:
+ *   1 (:253-272) kf_count[k] += 1 for every observation, by key-frame k != kf_row, of every non-null valid map point in kf_row's kf_mp
+ *   2 (:275-276) empty counter -> return: n_conn = 0, status GL_CONN_KEPT (the reference keeps its previous lists; conn_* untouched)
+ *   3 (:278-300) the observers with a count >= 15; if none reaches 15, the single observer with the largest count
+ *   4 (:302-315) ordered by weight, descending: conn_kf / conn_w B x Ccap int32 = ordered_keyframes_ / ordered_weights_, n_conn B the
+ *     TRUE length (more than Ccap: the first Ccap are written, status GL_CONN_TRUNCATED); kf_count B x NKF int32 (NULL allowed) =
+ *     map_frame_weights_ as a dense row.
+ * An invalid key-frame is counted and listed like any other, as in the reference (its callers filter on not_valid_).  The list is
+ * getVectorCovisibleKeyFrames(); getBestCovisibilityKeyFrames(n) is its first n entries (createMapPoints, searchInNeighbors).
+ * DECLARED DEVIATION: the reference breaks ties of weight - and the tie for the single largest - by POINTER value (sort on
+ * pair<int, KeyFrame*>; unordered_map order for nmax).  Here ties go to the LOWEST key-frame row first.
+ * What stays with the host: addConnection on the OTHER key-frames (:293, :299) - their own lists are the host's bookkeeping.
+ * Malformed input is skipped as in gl_update_local_map; a kf_row outside [0, NKF) gives n_conn = 0 and GL_CONN_BAD_ROW.
+ * One workgroup per key-frame, integer atomics only; counters in LDS up to 4 096 key-frames, in the context's scratch above. */
+#define GL_CONN_KEPT 1
+#define GL_CONN_TRUNCATED 2
+#define GL_CONN_BAD_ROW 4
+int gl_update_connections(gl_ctx_t* ctx, const gl_map_view* map, int B, const int32_t* kf_row_dev, int Ccap, int32_t* conn_kf_dev,
+                          int32_t* conn_w_dev, int32_t* n_conn_dev, int32_t* kf_count_dev, int32_t* status_dev);
+
+/* The rest of the resident map, what the local BA needs and the tracker does not: caller-owned device arrays, row-indexed like
+ * gl_map_view.
+ *   kf_pose   NKF x 7 f64          getTcw() as (qx qy qz qw tx ty tz); read by build, written by apply
+ *   kf_twc    NKF x 3 f64          the camera centres gl_update_map_points reads; written by apply; NULL allowed
+ *   kf_uvr    NKF x NFK x 3 f64    features_[i].uv.x, uv.y, u_right (u_right < 0: a monocular observation)
+ *   kf_oct    NKF x NFK int32      features_[i].octave (the table of gl_update_map_points)
+ *   obs_feat  NOBS int32           feature index of each CSR entry (the array of gl_update_map_points)
+ *   mp_assoc  NMP int32            index of asscociations_[0], or -1; read by build, written by apply
+ *   kf_first  row of the key-frame with idx_ == 0, or -1 (sets prior[j]) */
+typedef struct gl_map_ba_view {
+  double* kf_pose;
+  double* kf_twc;
+  const double* kf_uvr;
+  const int32_t* kf_oct;
+  const int32_t* obs_feat;
+  int32_t* mp_assoc;
+  int32_t kf_first;
+  int32_t reserved_;
+} gl_map_ba_view;
+/* B local-BA windows, one slab each (row b of every array), in the layout gl_joint_optimization takes for B = 1; each slab is compact
+ * inside its capacity and the entries behind its contents are never written.
+ *   poses B x (Pcap + Fcap) x 7: free poses [0, P), fixed poses [P, P + F) - contiguous, the fixed ones start at P, not at Pcap
+ *   prior B x Pcap uint8; points B x Lcap x 3; assoc B x Lcap int32; obs_ptr B x (Lcap + 1) int32;
+ *   obs_pose B x Ocap int32; obs_uvr B x Ocap x 3; obs_oct B x Ocap int32
+ *   the back-maps: win_kf B x (Pcap + Fcap) int32 (key-frame row of pose j), win_mp B x Lcap int32 (map-point row of point l),
+ *   win_obs B x Ocap int32 (the position in the map's CSR of observation g)
+ *   sizes B x 4 int32 = {P, F, L, nobs}, the TRUE counts; status B int32 (bits below; the points dropped are counted from bit 8 up) */
+typedef struct gl_ba_window {
+  int32_t Pcap, Fcap, Lcap, Ocap;
+  double* poses;
+  uint8_t* prior;
+  double* points;
+  int32_t* assoc;
+  int32_t* obs_ptr;
+  int32_t* obs_pose;
+  double* obs_uvr;
+  int32_t* obs_oct;
+  int32_t* win_kf;
+  int32_t* win_mp;
+  int32_t* win_obs;
+  int32_t* sizes;
+  int32_t* status;
+} gl_ba_window;
+#define GL_BA_WINDOW_NO_CONN 1      /* empty covisibility counter: the key-frame is the only free pose */
+#define GL_BA_WINDOW_P_TRUNCATED 2  /* P > Pcap */
+#define GL_BA_WINDOW_F_TRUNCATED 4  /* F > Fcap */
+#define GL_BA_WINDOW_L_TRUNCATED 8  /* L > Lcap */
+#define GL_BA_WINDOW_O_TRUNCATED 16 /* nobs > Ocap */
+#define GL_BA_WINDOW_BAD_ROW 32     /* kf_row outside [0, NKF): sizes = 0 */
+#define GL_BA_WINDOW_TRUNCATED 30     /* any of the four */
+#define GL_BA_WINDOW_DROPPED_SHIFT 8
+/* The window selection of Localization::jointOptimization (localization_opt.cpp:460-516) and the flattening of :639-763, for B
+ * key-frames kf_row on the resident map - what INTEGRATION section 6 has the host do by walking its pointer graph.  Quirks reproduced:
+ *   free poses   kf_row (whatever its own validity, :462), then the list of gl_update_connections in its order, each MARKED local;
+ *                an invalid one is marked but not added (:466-471), so it is neither free nor fixed
+ *   points       the free key-frames in that order, their kf_mp slots ascending: every non-null valid point at its FIRST occurrence
+ *                (:473-489)
+ *   observations each point's CSR entries in CSR order (the host's unordered_map order as uploaded, not re-sorted), those whose
+ *                key-frame is valid (:698): obs_pose = the window index of the key-frame, obs_uvr / obs_oct gathered through obs_feat
+ *                from kf_uvr / kf_oct
+ *   fixed poses  the valid key-frames not marked local, in the order of their FIRST observation in that walk (:491-516).
+ *                fixcam_obs / best_obs are dead code (flag_fixsingle is false at :585) and have no counterpart here
+ *   prior        prior[j] = (win_kf[j] == kf_first)
+ *   no edge      a point that ends with no observation by a valid key-frame and has mp_assoc < 0 has no edge in the reference's graph:
+ *                g2o leaves the vertex out of the active set and setPosition (:920) writes back what it read.  Such a point is
+ *                DROPPED from the window (the map keeps its position, which is what the reference leaves) and counted in
+ *                status >> GL_BA_WINDOW_DROPPED_SHIFT.
+ * The order is fully determined by the inputs (the tie rule of gl_update_connections apart): first occurrences by atomicMin on a key,
+ * ordered compaction by prefix sum, nothing depends on scheduling.
+ * CAPACITIES: a window larger than a capacity sets the truncation bit(s); sizes still hold the TRUE counts; nothing is written outside
+ * the slab, and what the slab then holds is not to be optimised - the host grows its buffers and calls again.
+ * MALFORMED input is skipped, never read out of bounds: kf_mp / obs_kf rows outside the tables, CSR ranges outside [0, NOBS] (the
+ * point then has no observation), an observation whose feature index is outside [0, NFK) (that observation alone).
+ * The sizes reach the host by a 16-byte copy of `sizes` and one synchronise; then gl_joint_optimization(B = 1, P, F, L, nobs, the
+ * slab's pointers).  Requires NKF x NFK < 2^31.  One workgroup per window; per-key-frame words in LDS up to 4 096 key-frames, else in
+ * the context's scratch, which always holds the per-map-point word and the window's lists (B x (3 NMP + NKF) words and a bit per
+ * key-frame slot). */
+int gl_ba_window_build(gl_ctx_t* ctx, const gl_map_view* map, const gl_map_ba_view* ba, int B, const int32_t* kf_row_dev,
+                       const gl_ba_window* win);
+/* The write-back of Localization::jointOptimization (:837-853 associations, :898-922 poses and points) onto the resident rows, from
+ * the slabs after gl_joint_optimization[_stoppable] (assoc_dropped B x Lcap, obs_erase B x Ocap, iters B: its outputs).  Per window:
+ *   kf_pose[win_kf[j]] = poses[j] for j < P;
+ *   kf_twc[row] = -(R^T t) when kf_twc is given: with n = sqrt(qx qx + qy qy + qz qz + qw qw), (x, y, z, w) = q / n and R as in
+ *     quat_to_R - R00 = 1 - 2 (y y + z z), R01 = 2 (x y - z w), R02 = 2 (x z + y w), R10 = 2 (x y + z w), R11 = 1 - 2 (x x + z z),
+ *     R12 = 2 (y z - x w), R20 = 2 (x z - y w), R21 = 2 (y z + x w), R22 = 1 - 2 (x x + y y) - component c is
+ *     -((R0c tx + R1c ty) + R2c tz), every operation rounded once (the library is built with -ffp-contract=off);
+ *   mp_pos[win_mp[l]] = points[l];  mp_assoc[win_mp[l]] = -1 where assoc_dropped[l] is set;
+ *   erase_obs B x Ocap int32 out: the CSR positions win_obs[g] of the observations with obs_erase[g] set, ASCENDING, n_erase B their
+ *   number.  Removing them edits the CSR and kf_mp: the host's removeObservation / removeMapPoint, before the next build.
+ * A window whose iters is 0 (the stop word was set on entry, nothing ran) or whose sizes exceed a capacity applies nothing
+ * (n_erase = 0).  mp_pos_dev is map->mp_pos, non-const; the map's other point arrays are not touched (gl_update_map_points(what = 2)
+ * refreshes normals and distances from the new positions and kf_twc). */
+int gl_ba_window_apply(gl_ctx_t* ctx, const gl_map_view* map, double* mp_pos_dev, const gl_map_ba_view* ba, int B, const gl_ba_window* win,
+                       const uint8_t* assoc_dropped_dev, const uint8_t* obs_erase_dev, const int32_t* iters_dev, int32_t* erase_obs_dev,
+                       int32_t* n_erase_dev);
+
 /* Localization::fuseObservations (localization.cpp:226-318), the matching half, for B key-frames: per candidate map point the most
  * similar feature inside Frame::getFeaturesInArea(u, v, th * scale_factors[level]) (frame.cpp:121-177) with octave level - 1 or
  * level and Feature::error(uvr) * sigma2_inv[octave] within 5.99 (mono) / 7.8 (stereo).  Features as in gl_search_by_projection

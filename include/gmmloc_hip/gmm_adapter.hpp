@@ -7,11 +7,13 @@
 //   GMMUtility::loadGMMModel                        (gmm_utils.cpp:9-67)
 //   GMMLoc::optimizePoint / checkMapAssociation     (gmmloc_opt.cpp:156-342)
 //   Tracking::optimizeCurrentPose                   (tracking_opt.cpp:21-217)
-//   Localization::jointOptimization                 (localization_opt.cpp:456-925)
+//   Localization::jointOptimization                 (localization_opt.cpp:456-925), flattened by the host or built on the device
+//                                                   from the resident map (jointOptimizationFromMap)
 //   north-star per-frame path: associate + structure-constrained refinement of one frame (trackFrame)
 // Host buffers in, host buffers out: each call stages through device memory owned by the
 // adapter (gl_malloc / gl_memcpy_*), so the host code never sees a HIP type.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <memory>
@@ -23,7 +25,8 @@
 
 namespace gmmloc_hip {
 
-// 3: trackFrame is the unanchored refine again, trackFrameAnchored the anchored one (2: trackFrame(..., anchored = true))
+// 3: trackFrame is the unanchored refine again, trackFrameAnchored the anchored one (2: trackFrame(..., anchored = true));
+//    MapBaRows / flattenMapBa / jointOptimizationFromMap were added without a new version: no existing call changed meaning
 constexpr int kAdapterVersion = 3;
 
 inline void check(int rc, const char* what) {
@@ -237,6 +240,70 @@ class GMM {
     w.iters = it[0];
   }
 
+  // The same local BA with the window built ON THE DEVICE from the resident map (gl_ba_window_build -> the 16 bytes of `sizes` ->
+  // gl_joint_optimization_stoppable(B = 1) on the slab -> gl_ba_window_apply): nothing is flattened, uploaded or written back by the
+  // host.  setResidentMap: the device arrays the host keeps (gl_map_view + gl_map_ba_view, e.g. uploaded from flattenMap /
+  // flattenMapBa and maintained since); kf_pose, kf_twc, mp_pos and mp_assoc are updated in place on the device.  What comes back is
+  // what the host's own bookkeeping needs: the rows of the window's key-frames (free then fixed) and points, the dropped
+  // associations (:837-853: clear asscociations_ of win_mp[l] where assoc_dropped[l]), and erase_obs, the positions in the map's
+  // CSR of the observations to remove (:855-879: removeObservation / removeMapPoint on the host, then the CSR and kf_mp rows are
+  // re-uploaded before the next build).  A window larger than the slab grows it and is built once more.
+  struct WindowResult {
+    int P = 0, F = 0, L = 0, nobs = 0, status = 0, iters = 0;
+    std::vector<int32_t> win_kf, win_mp, erase_obs;
+    std::vector<uint8_t> assoc_dropped;
+  };
+  void setResidentMap(const gl_map_view& view, const gl_map_ba_view& ba) {
+    map_ = view;
+    map_ba_ = ba;
+  }
+  WindowResult jointOptimizationFromMap(int32_t kf_row, const int32_t* stop_flag = nullptr) {
+    WindowResult r;
+    int32_t head[8];  // sizes (4) | status | iters | n_erase
+    gl_ba_window w;
+    char* base = nullptr;
+    for (int attempt = 0;; ++attempt) {
+      base = carveWindow(w);
+      check(gl_memcpy_h2d(ctx_, base + 32, &kf_row, 4), "h2d");
+      check(gl_ba_window_build(ctx_, &map_, &map_ba_, 1, reinterpret_cast<const int32_t*>(base + 32), &w), "gl_ba_window_build");
+      check(gl_ctx_synchronize(ctx_), "sync");
+      check(gl_memcpy_d2h(ctx_, head, base, 20), "d2h");
+      r.P = head[0], r.F = head[1], r.L = head[2], r.nobs = head[3], r.status = head[4];
+      if (r.status & GL_BA_WINDOW_BAD_ROW) throw std::runtime_error("jointOptimizationFromMap: kf_row is not a key-frame row");
+      if (!(r.status & GL_BA_WINDOW_TRUNCATED)) break;
+      if (attempt) throw std::runtime_error("jointOptimizationFromMap: the window still exceeds the capacities it asked for");
+      const size_t need[4] = {(size_t)r.P, (size_t)r.F, (size_t)r.L + r.L / 4, (size_t)r.nobs + r.nobs / 4};
+      for (int i = 0; i < 4; ++i) caps_[i] = need[i] > caps_[i] ? need[i] : caps_[i];
+    }
+    uint8_t* dropped = reinterpret_cast<uint8_t*>(base + win_off_[0]);
+    uint8_t* erase = reinterpret_cast<uint8_t*>(base + win_off_[1]);
+    int32_t* erase_obs = reinterpret_cast<int32_t*>(base + win_off_[2]);
+    int32_t* iters = reinterpret_cast<int32_t*>(base + 20);
+    const int32_t zero[2] = {0, 0};
+    check(gl_memcpy_h2d(ctx_, iters, zero, 8), "h2d");
+    zeros_.assign(win_off_[2] - win_off_[0], 0);  // (a BA stopped early may leave its flags unwritten: they start from zeros)
+    check(gl_memcpy_h2d(ctx_, dropped, zeros_.data(), zeros_.size()), "h2d");
+    if (r.L > 0 && r.nobs > 0)
+      check(gl_joint_optimization_stoppable(ctx_, gmm_, &cam_, &prm_, 1, r.P, r.F, r.L, r.nobs, w.poses, w.prior, w.points, w.assoc, w.obs_ptr,
+                                            w.obs_pose, w.obs_uvr, w.obs_oct, dropped, erase, iters, stop_flag),
+            "gl_joint_optimization");
+    check(gl_ba_window_apply(ctx_, &map_, const_cast<double*>(map_.mp_pos), &map_ba_, 1, &w, dropped, erase, iters, erase_obs, iters + 1),
+          "gl_ba_window_apply");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    check(gl_memcpy_d2h(ctx_, head, base, 32), "d2h");
+    r.iters = head[5];
+    const int ne = head[6];
+    r.win_kf.resize((size_t)r.P + r.F);
+    r.win_mp.resize(r.L);
+    r.assoc_dropped.assign(r.L, 0);
+    r.erase_obs.resize(ne);
+    if (r.P + r.F) check(gl_memcpy_d2h(ctx_, r.win_kf.data(), w.win_kf, ((size_t)r.P + r.F) * 4), "d2h");
+    if (r.L) check(gl_memcpy_d2h(ctx_, r.win_mp.data(), w.win_mp, (size_t)r.L * 4), "d2h");
+    if (r.L && r.iters) check(gl_memcpy_d2h(ctx_, r.assoc_dropped.data(), dropped, r.L), "d2h");
+    if (ne) check(gl_memcpy_d2h(ctx_, r.erase_obs.data(), erase_obs, (size_t)ne * 4), "d2h");
+    return r;
+  }
+
   gl_ctx_t* ctx() { return ctx_; }
   gl_gmm_t* handle() { return gmm_; }
   gl_params& params() { return prm_; }
@@ -270,6 +337,43 @@ class GMM {
     }
     return stage_;
   }
+  // the slab of jointOptimizationFromMap in pooled buffer 2: {sizes (16) | status | iters | n_erase | pad | kf_row} in its first 64
+  // bytes, then the arrays of gl_ba_window and the BA's outputs, each 64-byte aligned, at the capacities caps_
+  char* carveWindow(gl_ba_window& w) {
+    const size_t Pc = caps_[0], Fc = caps_[1], Lc = caps_[2], Oc = caps_[3];
+    size_t off = 64;
+    auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += (bytes + 63) / 64 * 64;
+      return at;
+    };
+    const size_t o_poses = take((Pc + Fc) * 56), o_prior = take(Pc), o_points = take(Lc * 24), o_assoc = take(Lc * 4), o_ptr = take((Lc + 1) * 4),
+                 o_op = take(Oc * 4), o_uvr = take(Oc * 24), o_oct = take(Oc * 4), o_wkf = take((Pc + Fc) * 4), o_wmp = take(Lc * 4), o_wobs = take(Oc * 4);
+    win_off_[0] = take(Lc);
+    win_off_[1] = take(Oc);
+    win_off_[2] = take(Oc * 4);
+    char* b = pooled(2, off).as<char>();
+    w.Pcap = (int32_t)Pc, w.Fcap = (int32_t)Fc, w.Lcap = (int32_t)Lc, w.Ocap = (int32_t)Oc;
+    w.poses = reinterpret_cast<double*>(b + o_poses);
+    w.prior = reinterpret_cast<uint8_t*>(b + o_prior);
+    w.points = reinterpret_cast<double*>(b + o_points);
+    w.assoc = reinterpret_cast<int32_t*>(b + o_assoc);
+    w.obs_ptr = reinterpret_cast<int32_t*>(b + o_ptr);
+    w.obs_pose = reinterpret_cast<int32_t*>(b + o_op);
+    w.obs_uvr = reinterpret_cast<double*>(b + o_uvr);
+    w.obs_oct = reinterpret_cast<int32_t*>(b + o_oct);
+    w.win_kf = reinterpret_cast<int32_t*>(b + o_wkf);
+    w.win_mp = reinterpret_cast<int32_t*>(b + o_wmp);
+    w.win_obs = reinterpret_cast<int32_t*>(b + o_wobs);
+    w.sizes = reinterpret_cast<int32_t*>(b);
+    w.status = reinterpret_cast<int32_t*>(b + 16);
+    return b;
+  }
+  gl_map_view map_{};
+  gl_map_ba_view map_ba_{};
+  size_t caps_[4] = {24, 24, 2048, 16384};  // Pcap, Fcap, Lcap, Ocap: grown on demand
+  size_t win_off_[3] = {0, 0, 0};           // dropped, erase, erase_obs (consecutive)
+  std::vector<uint8_t> zeros_;
   std::vector<std::unique_ptr<DevBuf>> pool_;
   char* stage_ = nullptr;
   size_t stage_bytes_ = 0;
@@ -319,6 +423,53 @@ inline MapRows flattenMap(int32_t NMP, int32_t NKF, int32_t NFK, PointRow point_
   for (int32_t p = 0; p < NMP; ++p) m.mp_valid[p] = mp_is_valid(p) ? 1 : 0;
   for (int32_t k = 0; k < NKF; ++k) m.kf_valid[k] = kf_is_valid(k) ? 1 : 0;
   return m;
+}
+// The rest of the resident map, what gl_ba_window_build / gl_ba_window_apply read and write besides MapRows (gl_map_ba_view): built
+// ONCE from the host's containers, uploaded, and from then on maintained on the device by jointOptimizationFromMap (and by the host
+// where it inserts or culls).  pose_of(k) -> Pose (getTcw()); feature(k, i, uvr, oct) fills features_[i].uv.x, uv.y, u_right
+// (u_right < 0: monocular) and .octave of key-frame k, false for a slot beyond its features; assoc_of(p) -> the index of
+// asscociations_[0] or -1; is_first(k): idx_ == 0.  obs_feat follows flattenMap's CSR (key-frames ascending per point), kf_twc is
+// -(R^T t) by the expression gl_ba_window_apply uses (gmmloc_hip.h), so rows made here and rows written there agree to the bit.
+struct MapBaRows {
+  std::vector<double> kf_pose, kf_twc, kf_uvr;  // NKF x 7, NKF x 3, NKF x NFK x 3
+  std::vector<int32_t> kf_oct, obs_feat, mp_assoc;  // NKF x NFK, NOBS, NMP
+  int32_t kf_first = -1;
+};
+template <class PoseOf, class FeatureOf, class AssocOf, class IsFirst>
+inline MapBaRows flattenMapBa(const MapRows& m, PoseOf pose_of, FeatureOf feature, AssocOf assoc_of, IsFirst is_first) {
+  MapBaRows b;
+  const size_t NKF = (size_t)m.NKF, NFK = (size_t)m.NFK;
+  b.kf_pose.assign(NKF * 7, 0.0);
+  b.kf_twc.assign(NKF * 3, 0.0);
+  b.kf_uvr.assign(NKF * NFK * 3, -1.0);
+  b.kf_oct.assign(NKF * NFK, 0);
+  b.obs_feat.assign(m.obs_kf.size(), 0);
+  b.mp_assoc.resize((size_t)m.NMP);
+  std::vector<int32_t> at(m.obs_ptr.begin(), m.obs_ptr.end() - 1);
+  for (size_t k = 0; k < NKF; ++k) {
+    const Pose T = pose_of((int32_t)k);
+    double* q = &b.kf_pose[k * 7];
+    std::memcpy(q, &T, 56);
+    const double n = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    const double x = q[0] / n, y = q[1] / n, z = q[2] / n, w = q[3] / n, tx = q[4], ty = q[5], tz = q[6];
+    const double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)},
+                            {2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)},
+                            {2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)}};
+    for (int c = 0; c < 3; ++c) b.kf_twc[k * 3 + c] = -((R[0][c] * tx + R[1][c] * ty) + R[2][c] * tz);
+    if (is_first((int32_t)k)) b.kf_first = (int32_t)k;
+    for (size_t i = 0; i < NFK; ++i) {
+      double uvr[3] = {0.0, 0.0, -1.0};
+      int32_t oct = 0;
+      if (feature((int32_t)k, (int32_t)i, uvr, oct)) {
+        std::memcpy(&b.kf_uvr[(k * NFK + i) * 3], uvr, 24);
+        b.kf_oct[k * NFK + i] = oct;
+      }
+      const int32_t p = m.kf_mp[k * NFK + i];
+      if (p >= 0) b.obs_feat[(size_t)at[p]++] = (int32_t)i;
+    }
+  }
+  for (int32_t p = 0; p < m.NMP; ++p) b.mp_assoc[p] = assoc_of(p);
+  return b;
 }
 // last_mp / kf_feat_mp of gl_local_map_io: the map-point row behind each of a frame's (the last frame's, the reference key-frame's)
 // n features - row(i) < 0 for a feature without a map point AND for a temporal point (createTemporalPoints, tracking.cpp:44-46: it

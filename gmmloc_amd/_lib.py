@@ -43,6 +43,19 @@ BA_WINDOW_ARRAYS = ("poses", "prior", "points", "assoc", "obs_ptr", "obs_pose", 
                     "status")
 
 
+class gl_map_edit(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("mp_valid", "kf_valid", "kf_mp", "obs_ptr", "obs_kf", "obs_feat", "mp_ref_kf")]
+
+
+class gl_map_remove_lists(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("rm_mp", "n_rm_mp", "erase_obs", "n_erase", "rm_kf", "n_rm_kf")] +
+                [(k, C.c_int32) for k in ("rm_mp_cap", "erase_cap", "rm_kf_cap", "reserved_")])
+
+
+class gl_map_remove_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("result", "dead_mp", "obs_new_pos")] + [("dead_cap", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class gl_ba_window(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("Pcap", "Fcap", "Lcap", "Ocap")] + [(k, C.c_void_p) for k in BA_WINDOW_ARRAYS])
 
@@ -114,6 +127,8 @@ def load():
         "gl_update_connections": (i32, [vp, vp, i32, vp, i32] + [vp] * 5),
         "gl_ba_window_build": (i32, [vp, vp, vp, i32, vp, vp]),
         "gl_ba_window_apply": (i32, [vp, vp, vp, vp, i32, vp] + [vp] * 5),
+        "gl_cull_keyframes": (i32, [vp, vp, vp, vp, C.c_float, i32, i32] + [vp] * 8),
+        "gl_map_remove": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
         "gl_search_local_points": (i32, [vp, vp, C.c_float, i32, i32, i32] + [vp] * 13 + [C.c_float, C.c_float, vp, vp, vp]),
         "gl_gather_triangulation_matches": (i32, [vp, i32, i32, i32, i32, i32] + [vp] * 32),
         "gl_optimize_point": (i32, [vp, vp, P(gl_camera), P(gl_params), i32] + [vp] * 10),

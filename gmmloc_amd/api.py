@@ -813,15 +813,16 @@ BA_WINDOW_DTYPES = {"poses": "float64", "prior": "uint8", "points": "float64", "
                     "status": "int32"}
 
 
-def _map_ba_view(ba, v, dev):
-    """dict of CUDA tensors (keys of MAP_BA_DTYPES; kf_twc optional) + kf_first (int, -1: none) -> gl_map_ba_view for the map view v"""
+def _map_ba_view(ba, v, dev, need=None):
+    """dict of CUDA tensors (keys of MAP_BA_DTYPES; kf_twc optional; `need`: the keys a call reads when it does not read them all) +
+    kf_first (int, -1: none) -> gl_map_ba_view for the map view v"""
     for k in ba:
         assert k in MAP_BA_DTYPES or k == "kf_first", "ba[%r]: unknown key" % k
     shapes = {"kf_pose": (v.NKF, 7), "kf_twc": (v.NKF, 3), "kf_uvr": (v.NKF, v.NFK, 3), "kf_oct": (v.NKF, v.NFK), "obs_feat": (v.NOBS,),
               "mp_assoc": (v.NMP,)}
     w = _lib.gl_map_ba_view()
     for k, dt in MAP_BA_DTYPES.items():
-        if k == "kf_twc" and ba.get(k) is None:
+        if ba.get(k) is None and (k == "kf_twc" or (need is not None and k not in need)):
             continue
         setattr(w, k, _ptr(_tensor("ba[%r]" % k, ba.get(k), dt, shapes[k], dev)))
     w.kf_first = int(ba.get("kf_first", -1))
@@ -984,6 +985,114 @@ def joint_optimization_from_map(ctx, gmm, cam, prm, map, ba, kf_row, caps, stop_
     n_erase = int(slab["n_erase"][0])
     return dict(slab=slab, P=P, F=F, L=L, nobs=nobs, status=status, caps=caps, win_kf=s["win_kf"][0, :P + F], win_mp=s["win_mp"][0, :L],
                 assoc_dropped=s["dropped"][0, :L], obs_erase=s["erase"][0, :nobs], iters=s["iters"], erase_obs=s["erase_obs"][0, :n_erase])
+
+
+# ---- editing the resident map: key-frame culling and removals (gmmloc_hip.h)
+CULL_JUDGED, CULL_FIRST, CULL_BAD_ROW, CULL_INVALID, CULL_DUPLICATE = 0, 1, 2, 3, 4
+CULL_MAX_KF = 524288
+MAP_REMOVE_FIRST_REFUSED, MAP_REMOVE_DEAD_TRUNCATED = 1, 2
+CULL_DTYPES = {"cull": "uint8", "num_mps": "int32", "num_redundant": "int32", "cand_status": "int32", "cull_rows": "int32"}
+
+
+def cull_keyframes(ctx, map, ba, kf_depth, th_depth, cand, n_cand, out=None):
+    """gl_cull_keyframes: Localization::removeKeyFrames (localization.cpp:334-399) for the B candidate lists cand (B,Ccap) i32 / n_cand
+    (B,) i32 - conn_kf / n_conn of update_connections as they are - on the unedited map: the verdicts of the sequential loop in list
+    order (rules, the weighted count, malformed input, the bound on NKF: gmmloc_hip.h).  kf_depth (NKF,NFK) f32; th_depth float.  The map
+    is not modified.  -> dict(cull (B,Ccap) u8, num_mps, num_redundant, cand_status (B,Ccap) i32, cull_rows (B,Ccap) i32 + n_cull (B,):
+    the culled rows in list order, what map_remove takes as rm_kf); `out`: the same dict to write into."""
+    import torch
+    v, dev = _map_view(map, False)
+    w = _map_ba_view(ba, v, dev, need=("kf_uvr", "kf_oct", "obs_feat"))
+    _tensor("kf_depth", kf_depth, "float32", (v.NKF, v.NFK), dev)
+    B, Ccap = _tensor("cand", cand, "int32", (None, None), dev).shape
+    _tensor("n_cand", n_cand, "int32", (B,), dev)
+    if out is None:
+        out = {k: torch.zeros((B, Ccap), dtype=getattr(torch, dt), device=dev) for k, dt in CULL_DTYPES.items()}
+        out["cull_rows"].fill_(-1)
+        out["n_cull"] = torch.zeros(B, dtype=torch.int32, device=dev)
+    for k, dt in CULL_DTYPES.items():
+        _tensor("out[%r]" % k, out.get(k), dt, (B, Ccap), dev)
+    _tensor("out['n_cull']", out.get("n_cull"), "int32", (B,), dev)
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_cull_keyframes(ctx.h, C.byref(v), C.byref(w), _ptr(kf_depth), float(th_depth), B, max(Ccap, 1), _ptr(cand), _ptr(n_cand),
+                                         _ptr(out["cull"]), _ptr(out["num_mps"]), _ptr(out["num_redundant"]), _ptr(out["cand_status"]),
+                                         _ptr(out["cull_rows"]), _ptr(out["n_cull"])))
+    finally:
+        ctx._exit()
+    return out
+
+
+def _row_list(name, rows, n, dev):
+    """a list of map_remove -> (pointer, count pointer, capacity)"""
+    if rows is None:
+        assert n is None, "n_%s without %s" % (name, name)
+        return None, None, 0
+    _tensor(name, rows, "int32", (None,), dev)
+    if n is not None:
+        assert n.is_cuda and n.device == dev and str(n.dtype) == "torch.int32" and n.numel() == 1, "n_%s: one int32 on the device" % name
+    return _ptr(rows), (_ptr(n) if n is not None else None), rows.shape[0]
+
+
+def map_remove(ctx, map, ba, erase_obs=None, rm_kf=None, rm_mp=None, n_erase=None, n_rm_kf=None, n_rm_mp=None, mp_ref_kf=None, dead_cap=None,
+               want_new_pos=False):
+    """gl_map_remove: removals applied IN PLACE to the resident map - map['mp_valid'], ['kf_valid'] (both required here), ['kf_mp'],
+    ['obs_ptr'], ['obs_kf'], ba['obs_feat'] and mp_ref_kf (NMP,) i32 when given: "the points of rm_mp, then the observations at the CSR
+    positions erase_obs, then the key-frames rm_kf in list order" with the reference's cascade (a point left with a weighted count <= 2
+    dies), the CSR compacted (rules: gmmloc_hip.h).  Each list: a 1-D i32 CUDA tensor, its length the tensor's or the device count n_x
+    (a 1-element i32 tensor: n_erase of ba_window_apply, n_cull of cull_keyframes - no synchronise between the calls).
+    -> dict(map, ba: the dicts with obs_kf / obs_feat cut to the new NOBS (views; everything else the same tensors), nobs, status,
+    dead_mp (n_dead,) i32 ascending[, obs_new_pos (old NOBS,) i32]).  One 12-byte copy and one synchronise."""
+    import torch
+    v, dev = _map_view(map, False)
+    _map_ba_view(ba, v, dev, need=("kf_uvr", "obs_feat"))
+    assert map.get("mp_valid") is not None and map.get("kf_valid") is not None, "map_remove: mp_valid and kf_valid are written, both are needed"
+    ed = _lib.gl_map_edit()
+    for k in ("mp_valid", "kf_valid", "kf_mp", "obs_ptr", "obs_kf"):
+        setattr(ed, k, _ptr(map[k]))
+    ed.obs_feat = _ptr(ba["obs_feat"])
+    if mp_ref_kf is not None:
+        ed.mp_ref_kf = _ptr(_tensor("mp_ref_kf", mp_ref_kf, "int32", (v.NMP,), dev))
+    ls = _lib.gl_map_remove_lists()
+    ls.rm_mp, ls.n_rm_mp, ls.rm_mp_cap = _row_list("rm_mp", rm_mp, n_rm_mp, dev)
+    ls.erase_obs, ls.n_erase, ls.erase_cap = _row_list("erase_obs", erase_obs, n_erase, dev)
+    ls.rm_kf, ls.n_rm_kf, ls.rm_kf_cap = _row_list("rm_kf", rm_kf, n_rm_kf, dev)
+    dead_cap = v.NMP if dead_cap is None else int(dead_cap)
+    result = torch.zeros(3, dtype=torch.int32, device=dev)
+    dead = torch.zeros(dead_cap, dtype=torch.int32, device=dev)
+    new_pos = torch.zeros(v.NOBS, dtype=torch.int32, device=dev) if want_new_pos else None
+    o = _lib.gl_map_remove_out()
+    o.result, o.dead_mp, o.obs_new_pos, o.dead_cap = _ptr(result), (_ptr(dead) if dead_cap else None), _ptr(new_pos), dead_cap
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_map_remove(ctx.h, v.NMP, v.NKF, v.NFK, v.NOBS, C.byref(ed), _ptr(ba["kf_uvr"]), int(ba.get("kf_first", -1)), C.byref(ls),
+                                     C.byref(o)))
+    finally:
+        ctx._exit()
+    nobs, n_dead, status = result.tolist()  # the one round trip
+    r = dict(map=dict(map, obs_kf=map["obs_kf"][:nobs]), ba=dict(ba, obs_feat=ba["obs_feat"][:nobs]), nobs=nobs, status=status,
+             dead_mp=dead[:min(n_dead, dead_cap)], n_dead=n_dead)
+    if want_new_pos:
+        r["obs_new_pos"] = new_pos
+    return r
+
+
+def mapping_pass_from_map(ctx, gmm, cam, prm, map, ba, kf_row, caps, kf_depth, th_depth, Ccap=64, mp_ref_kf=None, stop_flag=None, slab=None):
+    """What Localization::spinOnce (localization.cpp:97-107) does to the map after a key-frame's local BA, on the resident map with nothing
+    flattened or uploaded: joint_optimization_from_map -> map_remove(erase_obs) -> update_connections(kf_row) -> cull_keyframes on that
+    list -> map_remove(rm_kf).  -> dict(ba: the dict of joint_optimization_from_map; map, ba_rows: the edited dicts; conn, cull: the
+    dicts of update_connections / cull_keyframes (B = 1); the host's bookkeeping lists as int lists: erased (CSR positions of the map on
+    entry), dead_by_erase, culled (key-frame rows in list order), dead_by_cull (map-point rows); status of the two removals)."""
+    import torch
+    r = joint_optimization_from_map(ctx, gmm, cam, prm, map, ba, kf_row, caps, stop_flag=stop_flag, slab=slab)
+    e = map_remove(ctx, map, ba, erase_obs=r["slab"]["erase_obs"][0], n_erase=r["slab"]["n_erase"], mp_ref_kf=mp_ref_kf)
+    dev = map["obs_ptr"].device
+    conn = update_connections(ctx, e["map"], torch.full((1,), int(kf_row), dtype=torch.int32, device=dev), Ccap=Ccap)
+    cull = cull_keyframes(ctx, e["map"], e["ba"], kf_depth, th_depth, conn["conn_kf"], conn["n_conn"])
+    k = map_remove(ctx, e["map"], e["ba"], rm_kf=cull["cull_rows"][0], n_rm_kf=cull["n_cull"], mp_ref_kf=mp_ref_kf)
+    n_cull = int(cull["n_cull"][0])
+    return dict(ba=r, map=k["map"], ba_rows=k["ba"], conn=conn, cull=cull, erased=r["erase_obs"].tolist(), dead_by_erase=e["dead_mp"].tolist(),
+                culled=cull["cull_rows"][0, :n_cull].tolist(), dead_by_cull=k["dead_mp"].tolist(), status=(e["status"], k["status"]))
 
 
 def search_by_projection_frame(ctx, cam, pose_cw, pose_lw, feat_uv, feat_ur, feat_oct, feat_angle, feat_desc, feat_taken,

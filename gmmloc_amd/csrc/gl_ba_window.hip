@@ -18,6 +18,8 @@
 
 namespace {
 
+using namespace gl::mapdev;  // mp_ok, kf_ok, obs_range, block_excl_scan (shared with gl_map_edit.hip)
+
 constexpr int T_BW = 1024;
 constexpr int BW_KF_LDS = 4096;  // 2 x 16 KB of words
 // window index of a key-frame that has none: valid and not in the window / marked local but invalid (:466-471) / invalid
@@ -67,28 +69,6 @@ __device__ __forceinline__ void bw_sync() {
   __syncthreads();
 }
 
-// exclusive prefix sum of v over the workgroup's T_BW threads; *total = the sum.  s_w: T_BW / 64 ints of LDS, free again on return.
-__device__ __forceinline__ int block_excl_scan(int v, int* s_w, int tid, int* total) {
-  const int lane = tid & 63, w = tid >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < T_BW / 64; ++i) {
-    const int x = s_w[i];
-    base += i < w ? x : 0;
-    tot += x;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
 __device__ __forceinline__ u64 block_max(u64 v, u64* s_b, int tid) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) {
@@ -102,16 +82,6 @@ __device__ __forceinline__ u64 block_max(u64 v, u64* s_b, int tid) {
   for (int i = 0; i < T_BW / 64; ++i) r = s_b[i] > r ? s_b[i] : r;
   __syncthreads();
   return r;
-}
-
-__device__ __forceinline__ bool mp_ok(const gl_map_view& m, int p) { return p >= 0 && p < m.NMP && (!m.mp_valid || m.mp_valid[p]); }
-__device__ __forceinline__ bool kf_ok(const gl_map_view& m, int k) { return !m.kf_valid || m.kf_valid[k]; }
-// the CSR range of point p, empty when it is not a sub-range of [0, NOBS]
-__device__ __forceinline__ void obs_range(const gl_map_view& m, int p, int* o0, int* o1) {
-  const int a = m.obs_ptr[p], b = m.obs_ptr[p + 1];
-  const bool ok = a >= 0 && b >= a && b <= m.NOBS;
-  *o0 = ok ? a : 0;
-  *o1 = ok ? b : 0;
 }
 
 // (a) + (b) of the connections: on return the counters hold map_frame_weights_, n15 = the observers that reach the threshold and
@@ -144,7 +114,7 @@ __device__ __forceinline__ void conn_count(const gl_map_view& m, int kf, KfWords
     b = key > b ? key : b;
   }
   int tot;
-  block_excl_scan(n, s_w, tid, &tot);
+  block_excl_scan<T_BW>(n, s_w, tid, &tot);
   *n15 = tot;
   *best = block_max(b, s_b, tid);
 }
@@ -169,7 +139,7 @@ __device__ __forceinline__ int rank_selected(int NKF, int tid, int* s_w, RankLds
   int n = 0;
   for (int k = k0; k < k1; ++k) n += sel(k) != 0ull;
   int total;
-  int at = block_excl_scan(n, s_w, tid, &total);
+  int at = block_excl_scan<T_BW>(n, s_w, tid, &total);
   if (total <= RANK_LDS) {
     for (int k = k0; k < k1 && n > 0; ++k) {
       const u64 key = sel(k);
@@ -392,7 +362,7 @@ __global__ __launch_bounds__(T_BW) void k_ba_window_build(BwArgs a) {
   int npt = 0;
   for (int i = w0; i < w1; ++i) npt += __popcll(posmask[i]);
   int Lall;
-  int at = block_excl_scan(npt, s_w, tid, &Lall);
+  int at = block_excl_scan<T_BW>(npt, s_w, tid, &Lall);
   for (int i = w0; i < w1 && npt > 0; ++i) {
     u64 bits = posmask[i];
     while (bits) {
@@ -420,8 +390,8 @@ __global__ __launch_bounds__(T_BW) void k_ba_window_build(BwArgs a) {
     no_run += v >> 1;
   }
   int L, nobs;
-  int lw = block_excl_scan(np_run, s_w, tid, &L);
-  int g = block_excl_scan(no_run, s_w, tid, &nobs);
+  int lw = block_excl_scan<T_BW>(np_run, s_w, tid, &L);
+  int g = block_excl_scan<T_BW>(no_run, s_w, tid, &nobs);
   for (int l = l0; l < l1; ++l) {
     const int v = lcnt[l];
     mp_word[l] = v & 1 ? lw++ : -1;
@@ -542,7 +512,7 @@ __global__ __launch_bounds__(T_BW) void k_ba_window_apply(ApplyArgs a) {
   int n = 0;
   for (int g = g0; g < g1; ++g) n += a.obs_erase[so + g] != 0;
   int ne;
-  int at = block_excl_scan(n, s_w, tid, &ne);
+  int at = block_excl_scan<T_BW>(n, s_w, tid, &ne);
   int32_t* tmp = a.tmp + so;
   for (int g = g0; g < g1 && n > 0; ++g)
     if (a.obs_erase[so + g]) tmp[at++] = w.win_obs[so + g];

@@ -155,6 +155,7 @@ enum {
   SCRATCH_LOCALMAP,  // gl_update_local_map's global-path counters / bitmask, and the local-map arrays gl_track_frame_chain_map gathers
                      // for its stages (which use the three blocks above)
   SCRATCH_BAWINDOW,  // gl_update_connections / gl_ba_window_build / _apply: per-window words over the map's rows and the window's lists
+  SCRATCH_MAPEDIT,   // gl_map_remove: the marks over the map's rows, the scan words and the copy of the CSR it moves from
   SCRATCH_COUNT
 };
 
@@ -347,5 +348,43 @@ int launch_assoc_sweep64(Ctx* c, const Gmm* g, const double* pts, int N, int32_t
 int launch_assoc_index(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, bool resolve_all,
                        void* scratch);
 size_t assoc_index_scratch_bytes(int K, int N, bool resolve_all);
+
+#ifdef __HIPCC__
+// device helpers of the kernels that walk the resident map (gl_ba_window.hip, gl_map_edit.hip)
+namespace mapdev {
+__device__ __forceinline__ bool mp_ok(const gl_map_view& m, int p) { return p >= 0 && p < m.NMP && (!m.mp_valid || m.mp_valid[p]); }
+__device__ __forceinline__ bool kf_ok(const gl_map_view& m, int k) { return !m.kf_valid || m.kf_valid[k]; }
+// the CSR range of point p, empty when it is not a sub-range of [0, NOBS]
+__device__ __forceinline__ void obs_range(const gl_map_view& m, int p, int* o0, int* o1) {
+  const int a = m.obs_ptr[p], b = m.obs_ptr[p + 1];
+  const bool ok = a >= 0 && b >= a && b <= m.NOBS;
+  *o0 = ok ? a : 0;
+  *o1 = ok ? b : 0;
+}
+// exclusive prefix sum of v over the workgroup's T threads; *total = the sum.  s_w: T / 64 words of LDS, free again on return.
+template <int T, class V>
+__device__ __forceinline__ V block_excl_scan(V v, V* s_w, int tid, V* total) {
+  const int lane = tid & 63, w = tid >> 6;
+  V inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const V t = __shfl_up(inc, o);
+    if (lane >= o) inc += t;
+  }
+  if (lane == 63) s_w[w] = inc;
+  __syncthreads();
+  V base = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < T / 64; ++i) {
+    const V x = s_w[i];
+    base += i < w ? x : 0;
+    tot += x;
+  }
+  __syncthreads();
+  *total = tot;
+  return base + inc - v;
+}
+}  // namespace mapdev
+#endif
 
 }  // namespace gl

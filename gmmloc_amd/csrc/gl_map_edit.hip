@@ -1,0 +1,446 @@
+// Editing the resident map (gmmloc_hip.h): the key-frame culling of Localization::removeKeyFrames (localization.cpp:334-399) and the
+// removals - Map::removeMapPoint (map.cpp:40-58), the local BA's erase loop (localization_opt.cpp:884-894), Map::removeKeyFrame
+// (map.cpp:60-110) with the cascade of MapPoint::removeObservation (mappoint.cpp:94-118) - applied in place to the caller-owned arrays.
+// The rules, the closed form of the sequential semantics and the declared deviation are in the header.
+//   culling   one workgroup per candidate list.  The loop's state is the set C of the key-frames culled so far: a bit per key-frame
+//             row in dynamic LDS, next to the bits of the rows already seen in the list.  The candidates are walked in order; per
+//             candidate a slot per thread, each thread walks its point's CSR range against C; wave sums, two LDS integer atomics per
+//             wave, thread 0 decides.  One pass over the candidate's points' observations per candidate, like conn_count.
+//   removal   (a) k_me_mark: a flag per erased CSR position, a flag per removed point, the list RANK of every removed key-frame
+//             (atomicMin: a duplicate is harmless); (b) k_me_points: a point per thread - what it loses, its weight, the step at
+//             which it dies, the slots cleared, mp_ref_kf, its surviving count; (c) k_me_scan / k_me_scan_top: the exclusive scan of
+//             (surviving count | died << 32) over the points, 4 096 points per workgroup and one workgroup over the partial sums;
+//             (d) k_me_move: a point per thread copies its surviving entries to their new places.  The move is NOT in place: obs_kf /
+//             obs_feat are first copied to the context's scratch and (d) reads the copy; the new obs_ptr is made in the scratch and
+//             copied over the old one last, because (d) still reads the old ranges.
+// Everything is integer; the only atomics are atomicMin / atomicOr on words whose final value the inputs determine.
+#include "gl_internal.hpp"
+
+namespace {
+
+using namespace gl::mapdev;
+
+typedef unsigned long long u64;
+
+constexpr int T_CULL = 1024;
+constexpr int T_ME = 256;
+constexpr int SCAN_T = 1024, SCAN_PER = 4, SCAN_TILE = SCAN_T * SCAN_PER;
+constexpr int RANK_NONE = 0x7f7f7f7f;  // (a byte pattern: the ranks are reset by one memset); also "never dies"
+
+// ---------------------------------------------------------------------------------------------------------------- culling
+struct CullArgs {
+  gl_map_view m;
+  gl_map_ba_view ba;
+  const float* kf_depth;
+  float th_depth;
+  int B, Ccap;
+  const int32_t *cand_kf, *n_cand;
+  uint8_t* cull;
+  int32_t *num_mps, *num_red, *status, *cull_rows, *n_cull;
+};
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__global__ __launch_bounds__(T_CULL) void k_cull_keyframes(CullArgs a) {
+  extern __shared__ unsigned cull_lds[];  // [0, nw): C; [nw, 2 nw): the rows seen
+  __shared__ int s_cnt[2];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  if (b >= a.B) return;
+  const gl_map_view& m = a.m;
+  const int NKF = m.NKF, NFK = m.NFK, nw = (NKF + 31) >> 5;
+  unsigned* const inC = cull_lds;
+  unsigned* const seen = cull_lds + nw;
+  for (int i = tid; i < 2 * nw; i += T_CULL) cull_lds[i] = 0u;
+  if (tid < 2) s_cnt[tid] = 0;
+  __syncthreads();
+  const int n = min(max(a.n_cand[b], 0), a.Ccap);
+  const size_t row0 = (size_t)b * a.Ccap;
+  int nc = 0;  // (thread 0: the culled so far)
+  for (int j = 0; j < n; ++j) {
+    const int kf = a.cand_kf[row0 + j];
+    int st = GL_CULL_JUDGED;
+    if (kf < 0 || kf >= NKF) st = GL_CULL_BAD_ROW;
+    else if (seen[kf >> 5] >> (kf & 31) & 1u) st = GL_CULL_DUPLICATE;
+    else if (kf == a.ba.kf_first) st = GL_CULL_FIRST;
+    else if (!kf_ok(m, kf)) st = GL_CULL_INVALID;
+    __syncthreads();  // (every thread has read `seen`)
+    if (tid == 0 && st != GL_CULL_BAD_ROW && st != GL_CULL_DUPLICATE) seen[kf >> 5] |= 1u << (kf & 31);
+    if (st != GL_CULL_JUDGED) {  // (workgroup-uniform)
+      if (tid == 0) {
+        a.cull[row0 + j] = 0;
+        a.num_mps[row0 + j] = 0;
+        a.num_red[row0 + j] = 0;
+        a.status[row0 + j] = st;
+      }
+      __syncthreads();
+      continue;
+    }
+    int mps = 0, red = 0;
+    const size_t krow = (size_t)kf * NFK;
+    for (int i = tid; i < NFK; i += T_CULL) {
+      const int p = m.kf_mp[krow + i];
+      if (!mp_ok(m, p)) continue;
+      const float d = a.kf_depth[krow + i];
+      if (d > a.th_depth || d < 0.f) continue;  // (:358-362; a slot that is not counted needs no walk)
+      const int oct = a.ba.kf_oct[krow + i];
+      int o0, o1, w = 0, near = 0;
+      bool byC = false;
+      obs_range(m, p, &o0, &o1);
+      for (int o = o0; o < o1; o += 2) {  // two entries at a time, their loads issued together
+        int k[2], f[2], oc[2];
+        double ur[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const bool in = o + u < o1;
+          k[u] = in ? m.obs_kf[o + u] : -1;
+          f[u] = in ? a.ba.obs_feat[o + u] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const bool kin = k[u] >= 0 && k[u] < NKF;
+          const bool gone = kin && (inC[k[u] >> 5] >> (k[u] & 31) & 1u);  // removed with its key-frame
+          byC = byC || gone;
+          if (!(kin && !gone && f[u] >= 0 && f[u] < NFK)) k[u] = -1;  // (a feature outside the table: no octave, no weight)
+          const size_t ft = k[u] >= 0 ? (size_t)k[u] * NFK + f[u] : 0;
+          ur[u] = a.ba.kf_uvr[ft * 3 + 2];
+          oc[u] = a.ba.kf_oct[ft];
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          if (k[u] < 0) continue;
+          w += ur[u] >= 0.0 ? 2 : 1;
+          near += k[u] != kf && oc[u] <= oct + 1;
+        }
+      }
+      if (byC && w <= 2) continue;  // dead by the cascade
+      ++mps;
+      red += w > 3 && near >= 3;
+    }
+    mps = wave_sum(mps);
+    red = wave_sum(red);
+    if (lane == 0 && mps) {
+      atomicAdd(&s_cnt[0], mps);
+      atomicAdd(&s_cnt[1], red);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const int nm = s_cnt[0], nr = s_cnt[1];
+      const int v = (double)nr > 0.9 * (double)nm ? 1 : 0;  // (:394)
+      s_cnt[0] = s_cnt[1] = 0;
+      a.cull[row0 + j] = (uint8_t)v;
+      a.num_mps[row0 + j] = nm;
+      a.num_red[row0 + j] = nr;
+      a.status[row0 + j] = GL_CULL_JUDGED;
+      if (v) {
+        inC[kf >> 5] |= 1u << (kf & 31);
+        a.cull_rows[row0 + nc++] = kf;
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) a.n_cull[b] = nc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- removal
+struct EditArgs {
+  int NMP, NKF, NFK, NOBS;
+  gl_map_edit ed;
+  const double* kf_uvr;
+  int kf_first;
+  gl_map_remove_lists l;
+  gl_map_remove_out out;
+  // scratch
+  int32_t* rank;    // NKF: the place of a removed key-frame in rm_kf, RANK_NONE
+  uint8_t* pflag;   // NMP: 1 listed in rm_mp; 2 died in this call
+  uint8_t* oflag;   // NOBS: 1 erased (a), then 1 lost (b)
+  u64* cnt;         // NMP: surviving entries | died << 32, then its exclusive scan inside the tile
+  u64* tile;        // a word per tile: its sum, then the exclusive scan of the sums
+  int32_t* okf;     // NOBS: obs_kf / obs_feat as they were
+  int32_t* ofeat;
+  int32_t* nptr;    // NMP + 1
+};
+
+__device__ __forceinline__ int list_len(const int32_t* n, int cap) { return n ? min(max(*n, 0), cap) : cap; }
+
+__global__ __launch_bounds__(T_ME) void k_me_mark(EditArgs a) {
+  const int g = blockIdx.x * T_ME + threadIdx.x, G = gridDim.x * T_ME;
+  if (a.l.erase_obs) {
+    const int n = list_len(a.l.n_erase, a.l.erase_cap);
+    for (int i = g; i < n; i += G) {
+      const int o = a.l.erase_obs[i];
+      if (o >= 0 && o < a.NOBS) a.oflag[o] = 1;
+    }
+  }
+  if (a.l.rm_mp) {
+    const int n = list_len(a.l.n_rm_mp, a.l.rm_mp_cap);
+    for (int i = g; i < n; i += G) {
+      const int p = a.l.rm_mp[i];
+      if (p >= 0 && p < a.NMP && a.ed.mp_valid[p]) a.pflag[p] = 1;
+    }
+  }
+  if (a.l.rm_kf) {
+    const int n = list_len(a.l.n_rm_kf, a.l.rm_kf_cap);
+    for (int i = g; i < n; i += G) {
+      const int k = a.l.rm_kf[i];
+      if (k < 0 || k >= a.NKF || !a.ed.kf_valid[k]) continue;
+      if (k == a.kf_first) atomicOr(a.out.result + 2, GL_MAP_REMOVE_FIRST_REFUSED);  // (map.cpp:63)
+      else atomicMin(a.rank + k, i);
+    }
+  }
+}
+
+__global__ __launch_bounds__(T_ME) void k_me_points(EditArgs a) {
+  const int p = blockIdx.x * T_ME + threadIdx.x;
+  if (p < a.NKF && a.rank[p] != RANK_NONE) a.ed.kf_valid[p] = 0;  // (the grid covers max(NMP, NKF) threads)
+  if (p >= a.NMP) return;
+  const int NKF = a.NKF, NFK = a.NFK;
+  const int r0 = a.ed.obs_ptr[p], r1 = a.ed.obs_ptr[p + 1];
+  const bool okr = r0 >= 0 && r1 >= r0 && r1 <= a.NOBS;
+  const int o0 = okr ? r0 : 0, o1 = okr ? r1 : 0;
+  if (!a.ed.mp_valid[p]) {  // a dead point ignores removals (mappoint.cpp:99): its entries, if it has any, stay
+    a.cnt[p] = (u64)(o1 - o0);
+    for (int o = o0; o < o1; ++o) a.oflag[o] = 0;
+    return;
+  }
+  const int pf = a.pflag[p];
+  auto weight = [&](int k, int f) -> int {
+    if (k < 0 || k >= NKF || f < 0 || f >= NFK) return 0;
+    return a.kf_uvr[((size_t)k * NFK + f) * 3 + 2] >= 0.0 ? 2 : 1;
+  };
+  auto rank_of = [&](int k) -> int { return k >= 0 && k < NKF ? a.rank[k] : RANK_NONE; };
+  int wtot = 0, w_er = 0, w_rk = 0, n_er = 0, n_rk = 0;
+  for (int o = o0; o < o1; ++o) {
+    const int k = a.ed.obs_kf[o], w = weight(k, a.ed.obs_feat[o]);
+    wtot += w;
+    if (a.oflag[o]) {
+      ++n_er;
+      w_er += w;
+    } else if (rank_of(k) != RANK_NONE) {
+      ++n_rk;
+      w_rk += w;
+    }
+  }
+  if (!pf && n_er == 0 && n_rk == 0) {  // lost nothing: untouched
+    a.cnt[p] = (u64)(o1 - o0);
+    return;
+  }
+  // the step at which it dies: -1 in the point / erase phase, else the rank of the first removed observer that leaves w <= 2
+  const int w1 = wtot - w_er;
+  int t = RANK_NONE;
+  if (pf || (n_er > 0 && w1 <= 2)) t = -1;
+  else if (n_rk > 0 && w1 - w_rk <= 2) {
+    for (int o = o0; o < o1; ++o) {
+      const int re = a.oflag[o] ? RANK_NONE : rank_of(a.ed.obs_kf[o]);
+      if (re == RANK_NONE || re >= t) continue;
+      int w = w1;
+      for (int o2 = o0; o2 < o1; ++o2) {
+        const int k2 = a.ed.obs_kf[o2];
+        if (!a.oflag[o2] && rank_of(k2) <= re) w -= weight(k2, a.ed.obs_feat[o2]);
+      }
+      if (w <= 2) t = re;
+    }
+  }
+  const bool dead = t != RANK_NONE;
+  const int ref = a.ed.mp_ref_kf ? a.ed.mp_ref_kf[p] : -1;
+  int keep = 0, first_k = -1;
+  bool ref_lost = false;
+  for (int o = o0; o < o1; ++o) {
+    const int k = a.ed.obs_kf[o], f = a.ed.obs_feat[o];
+    const bool er = a.oflag[o] != 0;
+    const int rk = rank_of(k);
+    const bool lost = dead || er || rk != RANK_NONE;
+    // an erased observation clears its slot; a dying point clears its remaining observers', a removed key-frame's only if it died before
+    const bool clear = er || (dead && (rk == RANK_NONE || t < rk));
+    if (clear && k >= 0 && k < NKF && f >= 0 && f < NFK) {
+      int32_t* slot = a.ed.kf_mp + (size_t)k * NFK + f;
+      if (*slot == p) *slot = -1;
+    }
+    a.oflag[o] = lost ? 1 : 0;
+    if (!lost) {
+      if (keep++ == 0) first_k = k;
+    } else if (k == ref) {
+      ref_lost = true;
+    }
+  }
+  if (dead) {
+    a.ed.mp_valid[p] = 0;
+    a.pflag[p] = 2;
+    a.cnt[p] = 1ull << 32;
+  } else {
+    a.cnt[p] = (u64)keep;
+    if (a.ed.mp_ref_kf && ref_lost && keep > 0) a.ed.mp_ref_kf[p] = first_k;
+  }
+}
+
+// the exclusive scan of cnt inside every tile of SCAN_TILE points, the tile's sum to tile[]
+__global__ __launch_bounds__(SCAN_T) void k_me_scan(EditArgs a) {
+  __shared__ u64 s_w[SCAN_T / 64];
+  const int tid = threadIdx.x;
+  const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)tid * SCAN_PER;
+  u64 v[SCAN_PER], sum = 0;
+#pragma unroll
+  for (int u = 0; u < SCAN_PER; ++u) {
+    v[u] = base + u < (size_t)a.NMP ? a.cnt[base + u] : 0ull;
+    sum += v[u];
+  }
+  u64 total;
+  u64 at = block_excl_scan<SCAN_T, u64>(sum, s_w, tid, &total);
+#pragma unroll
+  for (int u = 0; u < SCAN_PER; ++u) {
+    if (base + u < (size_t)a.NMP) a.cnt[base + u] = at;
+    at += v[u];
+  }
+  if (tid == 0) a.tile[blockIdx.x] = total;
+}
+
+// one workgroup: the exclusive scan of the tile sums; the totals
+__global__ __launch_bounds__(SCAN_T) void k_me_scan_top(EditArgs a, int ntile) {
+  __shared__ u64 s_w[SCAN_T / 64];
+  const int tid = threadIdx.x;
+  u64 carry = 0;
+  for (int i0 = 0; i0 < ntile; i0 += SCAN_T) {
+    const int i = i0 + tid;
+    const u64 v = i < ntile ? a.tile[i] : 0ull;
+    u64 total;
+    const u64 at = block_excl_scan<SCAN_T, u64>(v, s_w, tid, &total);
+    if (i < ntile) a.tile[i] = carry + at;
+    carry += total;
+  }
+  if (tid == 0) {
+    const int nobs = (int)(unsigned)(carry & 0xffffffffull), ndead = (int)(unsigned)(carry >> 32);
+    a.nptr[a.NMP] = nobs;
+    a.out.result[0] = nobs;
+    a.out.result[1] = ndead;
+    if (ndead > a.out.dead_cap) atomicOr(a.out.result + 2, GL_MAP_REMOVE_DEAD_TRUNCATED);
+  }
+}
+
+__global__ __launch_bounds__(T_ME) void k_me_move(EditArgs a) {
+  const int p = blockIdx.x * T_ME + threadIdx.x;
+  if (p >= a.NMP) return;
+  const u64 at = a.cnt[p] + a.tile[p / SCAN_TILE];
+  int to = (int)(unsigned)(at & 0xffffffffull);
+  const int di = (int)(unsigned)(at >> 32);
+  a.nptr[p] = to;
+  if (a.pflag[p] == 2 && di < a.out.dead_cap) a.out.dead_mp[di] = p;
+  const int r0 = a.ed.obs_ptr[p], r1 = a.ed.obs_ptr[p + 1];
+  if (!(r0 >= 0 && r1 >= r0 && r1 <= a.NOBS)) return;
+  for (int o = r0; o < r1; ++o) {
+    if (a.oflag[o]) continue;  // (its obs_new_pos stays -1)
+    if (to >= a.NOBS) break;   // (overlapping ranges of a malformed CSR: never behind the arrays)
+    a.ed.obs_kf[to] = a.okf[o];
+    a.ed.obs_feat[to] = a.ofeat[o];
+    if (a.out.obs_new_pos) a.out.obs_new_pos[o] = to;
+    ++to;
+  }
+}
+
+}  // namespace
+
+extern "C" int gl_cull_keyframes(gl_ctx_t* ctx, const gl_map_view* map, const gl_map_ba_view* ba, const float* kf_depth_dev, float th_depth, int B,
+                                 int Ccap, const int32_t* cand_kf_dev, const int32_t* n_cand_dev, uint8_t* cull_dev, int32_t* num_mps_dev,
+                                 int32_t* num_redundant_dev, int32_t* cand_status_dev, int32_t* cull_rows_dev, int32_t* n_cull_dev) {
+  GL_REQUIRE(ctx && map && ba, "null argument");
+  GL_REQUIRE(B >= 0 && Ccap >= 1, "bad B / Ccap");
+  if (B == 0) return GL_OK;
+  GL_REQUIRE(map->NMP >= 0 && map->NKF >= 0 && map->NFK >= 0 && map->NOBS >= 0, "bad NMP / NKF / NFK / NOBS");
+  GL_REQUIRE((int64_t)map->NKF * map->NFK < ((int64_t)1 << 31), "NKF x NFK must be below 2^31");
+  GL_REQUIRE(map->NKF <= GL_CULL_MAX_KF, "more than GL_CULL_MAX_KF key-frames");
+  GL_REQUIRE(map->obs_ptr, "null obs_ptr");
+  GL_REQUIRE(map->NOBS == 0 || (map->obs_kf && ba->obs_feat), "null obs_kf / obs_feat");
+  GL_REQUIRE(map->NKF == 0 || map->NFK == 0 || (map->kf_mp && ba->kf_uvr && ba->kf_oct && kf_depth_dev), "null kf_mp / kf_uvr / kf_oct / kf_depth");
+  GL_REQUIRE(cand_kf_dev && n_cand_dev && cull_dev && num_mps_dev && num_redundant_dev && cand_status_dev && cull_rows_dev && n_cull_dev, "null buffer");
+  gl::Ctx* c = gl::C(ctx);
+  GL_HIP(hipSetDevice(c->device));
+  const size_t lds = (size_t)((map->NKF + 31) / 32) * 2 * 4;
+  GL_REQUIRE_LDS(c, lds + 256);
+  CullArgs a;
+  a.m = *map;
+  a.ba = *ba;
+  a.kf_depth = kf_depth_dev;
+  a.th_depth = th_depth;
+  a.B = B;
+  a.Ccap = Ccap;
+  a.cand_kf = cand_kf_dev;
+  a.n_cand = n_cand_dev;
+  a.cull = cull_dev;
+  a.num_mps = num_mps_dev;
+  a.num_red = num_redundant_dev;
+  a.status = cand_status_dev;
+  a.cull_rows = cull_rows_dev;
+  a.n_cull = n_cull_dev;
+  GL_HIP(gl::ensure_dynamic_lds(c, (const void*)k_cull_keyframes, lds));
+  k_cull_keyframes<<<B, T_CULL, lds, c->stream>>>(a);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+extern "C" int gl_map_remove(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, const gl_map_edit* ed, const double* kf_uvr_dev, int kf_first,
+                             const gl_map_remove_lists* lists, const gl_map_remove_out* out) {
+  GL_REQUIRE(ctx && ed && lists && out, "null argument");
+  GL_REQUIRE(NMP >= 0 && NKF >= 0 && NFK >= 0 && NOBS >= 0, "bad NMP / NKF / NFK / NOBS");
+  GL_REQUIRE((int64_t)NKF * NFK < ((int64_t)1 << 31), "NKF x NFK must be below 2^31");
+  GL_REQUIRE(ed->obs_ptr, "null obs_ptr");
+  GL_REQUIRE(NMP == 0 || ed->mp_valid, "null mp_valid");
+  GL_REQUIRE(NKF == 0 || ed->kf_valid, "null kf_valid");
+  GL_REQUIRE(NKF == 0 || NFK == 0 || (ed->kf_mp && kf_uvr_dev), "null kf_mp / kf_uvr");
+  GL_REQUIRE(NOBS == 0 || (ed->obs_kf && ed->obs_feat), "null obs_kf / obs_feat");
+  GL_REQUIRE(lists->rm_mp_cap >= 0 && lists->erase_cap >= 0 && lists->rm_kf_cap >= 0, "bad list capacity");
+  GL_REQUIRE(out->result, "null result");
+  GL_REQUIRE(out->dead_cap >= 0 && (out->dead_cap == 0 || out->dead_mp), "bad dead_cap / null dead_mp");
+  gl::Ctx* c = gl::C(ctx);
+  GL_HIP(hipSetDevice(c->device));
+  EditArgs a = {};
+  a.NMP = NMP;
+  a.NKF = NKF;
+  a.NFK = NFK;
+  a.NOBS = NOBS;
+  a.ed = *ed;
+  a.kf_uvr = kf_uvr_dev;
+  a.kf_first = kf_first;
+  a.l = *lists;
+  a.out = *out;
+  if (!a.l.rm_mp || a.l.rm_mp_cap == 0) a.l.rm_mp = nullptr, a.l.rm_mp_cap = 0;
+  if (!a.l.erase_obs || a.l.erase_cap == 0) a.l.erase_obs = nullptr, a.l.erase_cap = 0;
+  if (!a.l.rm_kf || a.l.rm_kf_cap == 0) a.l.rm_kf = nullptr, a.l.rm_kf_cap = 0;
+  GL_HIP(hipMemsetAsync(out->result, 0, 3 * sizeof(int32_t), c->stream));
+  const int ntile = (NMP + SCAN_TILE - 1) / SCAN_TILE;
+  gl::Regions r = {0};
+  // rank first, the flags next to each other: two memsets reset them
+  const size_t o_rank = r.take((size_t)NKF * 4), o_pflag = r.take((size_t)NMP), o_oflag = r.take((size_t)NOBS), flags_end = r.off;
+  const size_t o_cnt = r.take((size_t)NMP * 8), o_tile = r.take((size_t)ntile * 8), o_okf = r.take((size_t)NOBS * 4), o_ofeat = r.take((size_t)NOBS * 4),
+               o_nptr = r.take(((size_t)NMP + 1) * 4);
+  void* scratch = nullptr;
+  const int rs = gl::ctx_scratch(c, r.off, &scratch, gl::SCRATCH_MAPEDIT);
+  if (rs != GL_OK) return rs;
+  char* s = (char*)scratch;
+  a.rank = (int32_t*)(s + o_rank);
+  a.pflag = (uint8_t*)(s + o_pflag);
+  a.oflag = (uint8_t*)(s + o_oflag);
+  a.cnt = (u64*)(s + o_cnt);
+  a.tile = (u64*)(s + o_tile);
+  a.okf = (int32_t*)(s + o_okf);
+  a.ofeat = (int32_t*)(s + o_ofeat);
+  a.nptr = (int32_t*)(s + o_nptr);
+  if (NKF > 0) GL_HIP(hipMemsetAsync(a.rank, 0x7f, (size_t)NKF * 4, c->stream));
+  if (flags_end > o_pflag) GL_HIP(hipMemsetAsync(a.pflag, 0, flags_end - o_pflag, c->stream));
+  if (NOBS > 0) {
+    GL_HIP(hipMemcpyAsync(a.okf, ed->obs_kf, (size_t)NOBS * 4, hipMemcpyDeviceToDevice, c->stream));
+    GL_HIP(hipMemcpyAsync(a.ofeat, ed->obs_feat, (size_t)NOBS * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (out->obs_new_pos) GL_HIP(hipMemsetAsync(out->obs_new_pos, 0xff, (size_t)NOBS * 4, c->stream));
+  }
+  const int nlist = std::max(a.l.rm_mp_cap, std::max(a.l.erase_cap, a.l.rm_kf_cap));
+  if (nlist > 0) k_me_mark<<<std::min((nlist + T_ME - 1) / T_ME, 1024), T_ME, 0, c->stream>>>(a);
+  const int nrow = std::max(NMP, NKF);
+  if (nrow > 0) k_me_points<<<(nrow + T_ME - 1) / T_ME, T_ME, 0, c->stream>>>(a);
+  if (ntile > 0) k_me_scan<<<ntile, SCAN_T, 0, c->stream>>>(a);
+  k_me_scan_top<<<1, SCAN_T, 0, c->stream>>>(a, ntile);
+  if (NMP > 0) k_me_move<<<(NMP + T_ME - 1) / T_ME, T_ME, 0, c->stream>>>(a);
+  GL_HIP(hipGetLastError());
+  GL_HIP(hipMemcpyAsync(ed->obs_ptr, a.nptr, ((size_t)NMP + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
+  return GL_OK;
+}

@@ -681,13 +681,118 @@ int gl_ba_window_build(gl_ctx_t* ctx, const gl_map_view* map, const gl_map_ba_vi
  *     -((R0c tx + R1c ty) + R2c tz), every operation rounded once (the library is built with -ffp-contract=off);
  *   mp_pos[win_mp[l]] = points[l];  mp_assoc[win_mp[l]] = -1 where assoc_dropped[l] is set;
  *   erase_obs B x Ocap int32 out: the CSR positions win_obs[g] of the observations with obs_erase[g] set, ASCENDING, n_erase B their
- *   number.  Removing them edits the CSR and kf_mp: the host's removeObservation / removeMapPoint, before the next build.
+ *   number.  Removing them edits the CSR and kf_mp: gl_map_remove(erase_obs, n_erase) on the resident rows, before the next build.
  * A window whose iters is 0 (the stop word was set on entry, nothing ran) or whose sizes exceed a capacity applies nothing
  * (n_erase = 0).  mp_pos_dev is map->mp_pos, non-const; the map's other point arrays are not touched (gl_update_map_points(what = 2)
  * refreshes normals and distances from the new positions and kf_twc). */
 int gl_ba_window_apply(gl_ctx_t* ctx, const gl_map_view* map, double* mp_pos_dev, const gl_map_ba_view* ba, int B, const gl_ba_window* win,
                        const uint8_t* assoc_dropped_dev, const uint8_t* obs_erase_dev, const int32_t* iters_dev, int32_t* erase_obs_dev,
                        int32_t* n_erase_dev);
+
+/* ---- editing the resident map: key-frame culling and removals -------------
+ * Localization::removeKeyFrames (localization.cpp:334-399) for B candidate lists on ONE unedited map: the verdicts of the sequential
+ * loop in list order, each list on its own copy of the state.  The map is NOT modified (gl_map_remove applies a list).
+ *   kf_depth  NKF x NFK float   features_[i].depth (-1: none);  th_depth = frame::th_depth
+ *   cand_kf   B x Ccap int32, n_cand B int32, on the device: conn_kf / n_conn of gl_update_connections as they are (n_cand above Ccap:
+ *             the first Ccap; below 0: none)
+ * Per list, per candidate in list order:
+ *   - a row outside [0, NKF): GL_CULL_BAD_ROW; else a row that appeared earlier in the list: GL_CULL_DUPLICATE; else kf_first:
+ *     GL_CULL_FIRST (:344); else an invalid key-frame: GL_CULL_INVALID.  Nothing is decided for these: cull = 0, counts 0.
+ *   - per slot i whose kf_mp holds a valid point that is not DEAD (below): skipped when depth > th_depth || depth < 0 (float compares);
+ *     else num_mps++; when the point's weighted count is > 3: its observations by OTHER key-frames outside C with
+ *     kf_oct[obs_kf][obs_feat] <= kf_oct[kf][i] + 1 are counted, three make the slot redundant (:366-389; the early break changes nothing)
+ *   - cull = (double)num_redundant > 0.9 * (double)num_mps (:394); a culled candidate joins the set C.
+ * The state the loop carries is C alone (Map::removeKeyFrame map.cpp:60-110, MapPoint::removeObservation mappoint.cpp:94-118,
+ * Map::removeMapPoint map.cpp:40-58): an observation by a key-frame in C does not exist; a point is DEAD when some key-frame in C
+ * observes it and its weighted count over the observers outside C is <= 2.
+ * The WEIGHTED COUNT of a point is DEFINED from the CSR and kf_uvr: 2 for an observation whose u_right (kf_uvr[obs_kf][obs_feat][2])
+ * is >= 0, 1 for a monocular one (mappoint.cpp:78-81).  The reference keeps a counter, num_obs_, that equals it on a consistent map.
+ * Out (B x Ccap; entries at and behind n_cand are not written): cull uint8, num_mps / num_redundant int32 (what the loop computed),
+ * cand_status int32, cull_rows int32 + n_cull B: the culled rows in list order - the rm_kf of gl_map_remove.
+ * MALFORMED input is skipped as in gl_ba_window_build: kf_mp / obs_kf rows outside the tables (that slot / that observation), CSR
+ * ranges outside [0, NOBS] (no observation); an obs_feat outside [0, NFK): that observation alone has no octave and no weight (it
+ * still makes its key-frame an observer).
+ * BOUND: one workgroup per list; C and the rows seen are two bit sets in LDS, 2 x NKF bits: NKF <= GL_CULL_MAX_KF (128 KB of the
+ * 160 KB a workgroup has on gfx950).  A larger map is refused: GL_ERR_ARG, nothing launched. */
+#define GL_CULL_JUDGED 0
+#define GL_CULL_FIRST 1
+#define GL_CULL_BAD_ROW 2
+#define GL_CULL_INVALID 3
+#define GL_CULL_DUPLICATE 4
+#define GL_CULL_MAX_KF 524288
+int gl_cull_keyframes(gl_ctx_t* ctx, const gl_map_view* map, const gl_map_ba_view* ba, const float* kf_depth_dev, float th_depth, int B, int Ccap,
+                      const int32_t* cand_kf_dev, const int32_t* n_cand_dev, uint8_t* cull_dev, int32_t* num_mps_dev, int32_t* num_redundant_dev,
+                      int32_t* cand_status_dev, int32_t* cull_rows_dev, int32_t* n_cull_dev);
+
+/* Removals applied IN PLACE to the resident map's mutable arrays (all required but mp_ref_kf; row-indexed as in gl_map_view /
+ * gl_map_ba_view; mp_ref_kf NMP int32 = the ref_kf array of gl_update_map_points). */
+typedef struct gl_map_edit {
+  uint8_t* mp_valid;
+  uint8_t* kf_valid;
+  int32_t* kf_mp;
+  int32_t* obs_ptr;
+  int32_t* obs_kf;
+  int32_t* obs_feat;
+  int32_t* mp_ref_kf; /* NULL allowed */
+} gl_map_edit;
+/* Three lists of rows on the device, any of them NULL / empty.  The length of a list is *n_x when n_x is given (a device int32,
+ * clamped to [0, x_cap]) and x_cap otherwise.
+ *   rm_mp      map-point rows (Localization::removeMapPoints :127-152 and a host's own culling decide them)
+ *   erase_obs  CSR positions: erase_obs / n_erase of gl_ba_window_apply (row b of a batch)
+ *   rm_kf      key-frame rows IN REMOVAL ORDER: cull_rows / n_cull of gl_cull_keyframes */
+typedef struct gl_map_remove_lists {
+  const int32_t* rm_mp;
+  const int32_t* n_rm_mp;
+  const int32_t* erase_obs;
+  const int32_t* n_erase;
+  const int32_t* rm_kf;
+  const int32_t* n_rm_kf;
+  int32_t rm_mp_cap, erase_cap, rm_kf_cap;
+  int32_t reserved_;
+} gl_map_remove_lists;
+/* result  3 int32 on the device: {the new NOBS, n_dead, status bits}
+ * dead_mp dead_cap int32: the rows of the points that died in this call, ASCENDING (more than dead_cap: the first dead_cap,
+ *         GL_MAP_REMOVE_DEAD_TRUNCATED; n_dead stays true); NULL allowed with dead_cap 0
+ * obs_new_pos  old NOBS int32, NULL allowed: the new CSR position of every old entry, -1 for one that is gone */
+typedef struct gl_map_remove_out {
+  int32_t* result;
+  int32_t* dead_mp;
+  int32_t* obs_new_pos;
+  int32_t dead_cap;
+  int32_t reserved_;
+} gl_map_remove_out;
+#define GL_MAP_REMOVE_FIRST_REFUSED 1  /* rm_kf held kf_first: not removed (map.cpp:63) */
+#define GL_MAP_REMOVE_DEAD_TRUNCATED 2
+/* "The points of rm_mp (Map::removeMapPoint), then the observations of erase_obs (the erase loop of the local BA,
+ * localization_opt.cpp:884-894), then the key-frames of rm_kf in list order (Map::removeKeyFrame)", with the reference's cascade - a
+ * point whose num_obs_ falls to <= 2 by a removal dies (mappoint.cpp:112, map.cpp:72-73) - as ONE parallel edit.  With w(p) the
+ * weighted count (gl_cull_keyframes) of the observations point p keeps:
+ *   - an observation is LOST when erase_obs lists it or its key-frame is in rm_kf; a point of rm_mp loses all of them;
+ *   - a point of rm_mp, or one that lost something and keeps w <= 2, DIES: mp_valid = 0, no CSR entries, the kf_mp slot of every
+ *     remaining observer set to -1; any other point keeps exactly the entries it did not lose, in their order;
+ *   - an erased observation clears its observer's slot (keyframe.cpp:200-205);
+ *   - the rows of the REMOVED key-frames follow the order of the list (removeKeyFrame never nulls the removed key-frame's own
+ *     mappoints_, removeMapPoint nulls the slot of every key-frame that STILL observes the dying point): with rm_kf = r_0, r_1, ... and
+ *     t(p) the step at which p dies (-1: before the key-frames; walk p's removed observers in list order, subtract their weights, stop
+ *     at the first w <= 2), the slot of r_i that holds p is cleared iff p dies with t(p) < i - kept when r_i's own removal kills p,
+ *     and kept for a point that survives;
+ *   - kf_valid[rm_kf] = 0.  kf_first is refused (map.cpp:63, GL_MAP_REMOVE_FIRST_REFUSED).  An already invalid key-frame or point, a
+ *     duplicate in a list (the FIRST occurrence gives the rank), a row or position outside its table change nothing;
+ *   - the CSR is COMPACTED, stable: obs_ptr is rewritten, result[0] = the new NOBS; obs_kf / obs_feat behind it are not written;
+ *   - mp_ref_kf[p], when given: a point that SURVIVES and lost the observation by its ref_kf gets the key-frame of its first
+ *     surviving CSR entry.  DECLARED DEVIATION: the reference takes observations_.begin() of an unordered_map<pointer>
+ *     (mappoint.cpp:108-110).  The entry of a point that dies is left as it is.
+ * The map is taken as consistent (kf_mp[obs_kf[o]][obs_feat[o]] is the point of entry o).  Where it is not, the CSR decides what is
+ * lost and a slot is cleared only if it holds that point; an entry whose key-frame or feature is outside the tables has no weight and
+ * no slot; a point whose CSR range is not inside [0, NOBS] has no entries afterwards; nothing is read or written out of bounds.
+ * What stays with the host, from dead_mp / obs_new_pos and the lists it passed: mappoints_.erase, keyframes_.erase, removeConnection,
+ * best_cov_kf_, the re-parenting of frame_info_, asscociations_.
+ * The cost follows the map, not the edit: flags over NOBS / NMP and a rank per key-frame in the context's scratch (set and reset by
+ * the call), a point per thread, a device-wide scan of the surviving counts, and the move THROUGH A COPY of obs_kf / obs_feat in the
+ * scratch (an in-place parallel compaction would read what another workgroup has overwritten).  Integer stores and atomicMin only:
+ * the result does not depend on scheduling.  Asynchronous on the context's stream, stateless, no host synchronise. */
+int gl_map_remove(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, const gl_map_edit* ed, const double* kf_uvr_dev, int kf_first,
+                  const gl_map_remove_lists* lists, const gl_map_remove_out* out);
 
 /* Localization::fuseObservations (localization.cpp:226-318), the matching half, for B key-frames: per candidate map point the most
  * similar feature inside Frame::getFeaturesInArea(u, v, th * scale_factors[level]) (frame.cpp:121-177) with octave level - 1 or

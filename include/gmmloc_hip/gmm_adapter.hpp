@@ -9,6 +9,8 @@
 //   Tracking::optimizeCurrentPose                   (tracking_opt.cpp:21-217)
 //   Localization::jointOptimization                 (localization_opt.cpp:456-925), flattened by the host or built on the device
 //                                                   from the resident map (jointOptimizationFromMap)
+//   Localization::removeKeyFrames                   (localization.cpp:334-399) and the removals of Map::removeKeyFrame /
+//                                                   removeMapPoint / the BA's erase loop on the resident map (cullKeyFrames, removeFromMap)
 //   north-star per-frame path: associate + structure-constrained refinement of one frame (trackFrame)
 // Host buffers in, host buffers out: each call stages through device memory owned by the
 // adapter (gl_malloc / gl_memcpy_*), so the host code never sees a HIP type.
@@ -27,7 +29,9 @@ namespace gmmloc_hip {
 
 // 3: trackFrame is the unanchored refine again, trackFrameAnchored the anchored one (2: trackFrame(..., anchored = true));
 //    MapBaRows / flattenMapBa / jointOptimizationFromMap were added without a new version: no existing call changed meaning
-constexpr int kAdapterVersion = 3;
+// 4: cullKeyFrames / removeFromMap edit the resident map on the device; the erase_obs of jointOptimizationFromMap no longer ask for
+//    a re-upload of the CSR (pass them to removeFromMap)
+constexpr int kAdapterVersion = 4;
 
 inline void check(int rc, const char* what) {
   if (rc != GL_OK) throw std::runtime_error(std::string(what) + ": " + gl_last_error_string());
@@ -246,8 +250,8 @@ class GMM {
   // flattenMapBa and maintained since); kf_pose, kf_twc, mp_pos and mp_assoc are updated in place on the device.  What comes back is
   // what the host's own bookkeeping needs: the rows of the window's key-frames (free then fixed) and points, the dropped
   // associations (:837-853: clear asscociations_ of win_mp[l] where assoc_dropped[l]), and erase_obs, the positions in the map's
-  // CSR of the observations to remove (:855-879: removeObservation / removeMapPoint on the host, then the CSR and kf_mp rows are
-  // re-uploaded before the next build).  A window larger than the slab grows it and is built once more.
+  // CSR of the observations to remove (:855-879: removeFromMap(erase_obs, {}) applies them to the resident rows; the host's own
+  // removeObservation / removeMapPoint follow from its dead_mp).  A window larger than the slab grows it and is built once more.
   struct WindowResult {
     int P = 0, F = 0, L = 0, nobs = 0, status = 0, iters = 0;
     std::vector<int32_t> win_kf, win_mp, erase_obs;
@@ -303,6 +307,91 @@ class GMM {
     if (ne) check(gl_memcpy_d2h(ctx_, r.erase_obs.data(), erase_obs, (size_t)ne * 4), "d2h");
     return r;
   }
+
+  // Localization::removeKeyFrames for key-frame kf_row on the resident map: gl_update_connections gives its covisible list
+  // (getVectorCovisibleKeyFrames, at most Ccap entries), gl_cull_keyframes judges it in list order - no synchronise between the two.
+  // kf_depth_dev: NKF x NFK float on the device (features_[i].depth, -1: none).  The map is not modified: pass cull_rows to
+  // removeFromMap.  The arrays have one entry per candidate (cull_rows one per culled key-frame, in list order).
+  struct CullResult {
+    std::vector<int32_t> cand, num_mps, num_redundant, cand_status, cull_rows;
+    std::vector<uint8_t> cull;
+  };
+  CullResult cullKeyFrames(int32_t kf_row, const float* kf_depth_dev, float th_depth, int32_t Ccap = 64) {
+    if (Ccap < 1) throw std::runtime_error("cullKeyFrames: Ccap");
+    const size_t C = (size_t)Ccap;
+    // {kf_row | n_conn | conn_status | n_cull} then conn_kf, conn_w, num_mps, num_redundant, cand_status, cull_rows (C words each), cull (C bytes)
+    char* b = pooled(3, 64 + 6 * C * 4 + C).as<char>();
+    int32_t* hd = reinterpret_cast<int32_t*>(b);
+    int32_t* arr = reinterpret_cast<int32_t*>(b + 64);
+    uint8_t* cull = reinterpret_cast<uint8_t*>(b + 64 + 6 * C * 4);
+    const int32_t head[4] = {kf_row, 0, 0, 0};
+    check(gl_memcpy_h2d(ctx_, hd, head, 16), "h2d");
+    check(gl_update_connections(ctx_, &map_, 1, hd, Ccap, arr, arr + C, hd + 1, nullptr, hd + 2), "gl_update_connections");
+    check(gl_cull_keyframes(ctx_, &map_, &map_ba_, kf_depth_dev, th_depth, 1, Ccap, arr, hd + 1, cull, arr + 2 * C, arr + 3 * C, arr + 4 * C, arr + 5 * C,
+                            hd + 3),
+          "gl_cull_keyframes");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t got[4];
+    check(gl_memcpy_d2h(ctx_, got, hd, 16), "d2h");
+    const size_t n = (size_t)(got[1] < 0 ? 0 : got[1] > Ccap ? Ccap : got[1]), nc = (size_t)got[3];
+    CullResult r;
+    std::vector<int32_t>* dst[6] = {&r.cand, nullptr, &r.num_mps, &r.num_redundant, &r.cand_status, &r.cull_rows};
+    for (int i = 0; i < 6; ++i) {
+      if (!dst[i]) continue;
+      dst[i]->resize(i == 5 ? nc : n);
+      if (!dst[i]->empty()) check(gl_memcpy_d2h(ctx_, dst[i]->data(), arr + i * C, dst[i]->size() * 4), "d2h");
+    }
+    r.cull.resize(n);
+    if (n) check(gl_memcpy_d2h(ctx_, r.cull.data(), cull, n), "d2h");
+    return r;
+  }
+  // gl_map_remove on the resident map: "the points rm_mp, then the observations at the CSR positions erase_obs (WindowResult::erase_obs),
+  // then the key-frames rm_kf in list order (CullResult::cull_rows)", the reference's cascade included, in place on the device - mp_valid,
+  // kf_valid, kf_mp, the CSR (compacted: the view's NOBS becomes the new one) and mp_ref_kf_dev (NMP int32, may be null).  The lists are
+  // the only upload.  dead_mp: the points that died, ascending - the host erases them from its own containers, as it does the key-frames
+  // it listed (mappoints_.erase, keyframes_.erase, removeConnection, the re-parenting of frame_info_: map.cpp:56, :67-68, :89-109).
+  struct RemoveResult {
+    int32_t nobs = 0, status = 0;
+    std::vector<int32_t> dead_mp;
+  };
+  RemoveResult removeFromMap(const std::vector<int32_t>& erase_obs, const std::vector<int32_t>& rm_kf, const std::vector<int32_t>& rm_mp = {},
+                             int32_t* mp_ref_kf_dev = nullptr) {
+    const size_t ne = erase_obs.size(), nk = rm_kf.size(), np = rm_mp.size(), NMP = (size_t)map_.NMP;
+    char* b = pooled(4, 64 + (ne + nk + np + NMP) * 4).as<char>();
+    int32_t* res = reinterpret_cast<int32_t*>(b);
+    int32_t* l_er = reinterpret_cast<int32_t*>(b + 64);
+    int32_t *l_kf = l_er + ne, *l_mp = l_kf + nk, *dead = l_mp + np;
+    if (ne) check(gl_memcpy_h2d(ctx_, l_er, erase_obs.data(), ne * 4), "h2d");
+    if (nk) check(gl_memcpy_h2d(ctx_, l_kf, rm_kf.data(), nk * 4), "h2d");
+    if (np) check(gl_memcpy_h2d(ctx_, l_mp, rm_mp.data(), np * 4), "h2d");
+    gl_map_edit ed{};
+    ed.mp_valid = const_cast<uint8_t*>(map_.mp_valid);
+    ed.kf_valid = const_cast<uint8_t*>(map_.kf_valid);
+    ed.kf_mp = const_cast<int32_t*>(map_.kf_mp);
+    ed.obs_ptr = const_cast<int32_t*>(map_.obs_ptr);
+    ed.obs_kf = const_cast<int32_t*>(map_.obs_kf);
+    ed.obs_feat = const_cast<int32_t*>(map_ba_.obs_feat);
+    ed.mp_ref_kf = mp_ref_kf_dev;
+    gl_map_remove_lists ls{};
+    ls.rm_mp = np ? l_mp : nullptr, ls.rm_mp_cap = (int32_t)np;
+    ls.erase_obs = ne ? l_er : nullptr, ls.erase_cap = (int32_t)ne;
+    ls.rm_kf = nk ? l_kf : nullptr, ls.rm_kf_cap = (int32_t)nk;
+    gl_map_remove_out out{};
+    out.result = res;
+    out.dead_mp = NMP ? dead : nullptr;
+    out.dead_cap = (int32_t)NMP;
+    check(gl_map_remove(ctx_, map_.NMP, map_.NKF, map_.NFK, map_.NOBS, &ed, map_ba_.kf_uvr, map_ba_.kf_first, &ls, &out), "gl_map_remove");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t got[3];
+    check(gl_memcpy_d2h(ctx_, got, res, 12), "d2h");
+    RemoveResult r;
+    r.nobs = got[0], r.status = got[2];
+    r.dead_mp.resize((size_t)got[1]);
+    if (got[1]) check(gl_memcpy_d2h(ctx_, r.dead_mp.data(), dead, (size_t)got[1] * 4), "d2h");
+    map_.NOBS = r.nobs;
+    return r;
+  }
+  const gl_map_view& residentMap() const { return map_; }
 
   gl_ctx_t* ctx() { return ctx_; }
   gl_gmm_t* handle() { return gmm_; }

@@ -67,6 +67,47 @@ typedef struct gl_params {
 /* Fills the values of gmmloc_ros/cfg/v1.yaml and the float 1.2^(-2l) table. */
 void gl_default_params(gl_params* p);
 
+/* What each entry point reads of gl_camera, of gl_params and of its own scale_factor argument.
+ *
+ * The intrinsics (fx fy cx cy bf) are expected to be values that float represents exactly: the reference holds them as float
+ * (config.h:38) and the matchers / the projection loop cast them to float.  "K" = fx fy cx cy, "size" = width height,
+ * "sigma2_inv" = the level table (build it for another pyramid as init_config.hpp:60-79 does for 1.2, in float arithmetic),
+ * "-" = the argument is not taken.  Every function is checked on the device under non-default values of what it reads
+ * (tests/configs.py, tests/test_gpu_configs.py).
+ *
+ * entry point                      | gl_camera      | gl_params                                                           | scale_factor
+ * ---------------------------------+----------------+---------------------------------------------------------------------+-------------
+ * gl_gmm_create                    | -              | neighbor_dist_thresh (captured: the neighbour graph)                | -
+ * gl_gmm_load_file                 | -              | neighbor_dist_thresh (captured: the neighbour graph)                | -
+ * gl_search2d                      | K size         | -                                                                   | -
+ * gl_optimize_point                | K bf           | tri_lambda2 tri_str_thresh tri_check_str_chi2 sigma2_inv            | -
+ * gl_check_map_association         | K bf           | as gl_optimize_point (+ the graph the GMM captured)                 | -
+ * gl_optimize_triangulation        | K bf           | tri_lambda2 tri_str_thresh tri_check_str_chi2 sigma2_inv            | -
+ * gl_create_map_points             | K bf size      | tri_lambda2 tri_str_thresh tri_check_str_chi2 sigma2_inv            | level ratios
+ * gl_optimize_current_pose         | K bf           | sigma2_inv                                                          | -
+ * gl_joint_optimization            | K bf           | ba_lambda2 tri_str_thresh ba_first_as_prior sigma2_inv              | -
+ * gl_joint_optimization_stoppable  | K bf           | ba_lambda2 tri_str_thresh ba_first_as_prior sigma2_inv              | -
+ * gl_track_frames                  | K bf           | ba_lambda2 tri_str_thresh sigma2_inv                                | -
+ * gl_track_frames_anchored         | K bf           | ba_lambda2 tri_str_thresh ba_first_as_prior sigma2_inv              | -
+ * gl_track_frame_host              | K bf           | ba_lambda2 tri_str_thresh sigma2_inv                                | -
+ * gl_track_frame_host_anchored     | K bf           | ba_lambda2 tri_str_thresh ba_first_as_prior sigma2_inv              | -
+ * gl_search_by_projection          | size           | -                                                                   | level radii
+ * gl_search_by_projection_frame    | K bf size      | -                                                                   | level radii
+ * gl_search_for_triangulation      | -              | -                                                                   | level sigma2
+ * gl_fuse_search                   | size           | -                                                                   | level sigma2
+ * gl_project_map_points            | K bf size      | -                                                                   | level steps, band
+ * gl_search_local_points           | K bf size      | -                                                                   | both of the above
+ * gl_level_steps                   | -              | -                                                                   | level steps
+ * gl_update_map_points             | -              | -                                                                   | distance band
+ * gl_track_frame_chain             | K bf size      | sigma2_inv                                                          | radii, steps, band
+ * gl_track_frame_chain_front       | K bf size      | sigma2_inv                                                          | level radii
+ * gl_track_frame_chain_back        | K bf size      | sigma2_inv                                                          | radii, steps, band
+ * gl_track_frame_chain_map         | K bf size      | sigma2_inv                                                          | radii, steps, band
+ *
+ * tri_lambda2 weighs the structure edge of the per-point optimisations (and scales their threshold, tri_str_thresh * tri_lambda2);
+ * ba_lambda2 does both for the pose / window optimisations (threshold tri_str_thresh * ba_lambda2).  gl_search_by_bow,
+ * gl_associate3d, gl_knn3d, gl_update_local_map, the gl_ba_window_* / gl_map_* calls read none of the three. */
+
 const char* gl_last_error_string(void); /* thread-local */
 int gl_device_count(void);
 

@@ -36,19 +36,21 @@ def pose_inputs(f, m_last, m_local=None, m_kf=None):
     return Xw, obs, oc
 
 
-def oracle_stage1(o, f):
-    m, n = o.search_by_projection_frame(CamF, *[f[x] for x in S1_KEYS], th=TH_MM, mono=False, check_orientation=True)
+def oracle_stage1(o, f, cam=CamF, scale_factor=1.2):
+    m, n = o.search_by_projection_frame(cam, *[f[x] for x in S1_KEYS], th=TH_MM, mono=False, check_orientation=True, scale_factor=scale_factor)
     if n < 20:  # tracking.cpp:340-346
-        m, n = o.search_by_projection_frame(CamF, *[f[x] for x in S1_KEYS], th=2 * TH_MM, mono=False, check_orientation=True)
+        m, n = o.search_by_projection_frame(cam, *[f[x] for x in S1_KEYS], th=2 * TH_MM, mono=False, check_orientation=True,
+                                            scale_factor=scale_factor)
     return m, n
 
 
-def oracle_front(o, cam, f):
-    """trackWithMotionModel (+ trackKeyFrame when it returns less than 10 and the frame has a key-frame) -> dict"""
+def oracle_front(o, cam, f, prm=None, scale_factor=1.2):
+    """trackWithMotionModel (+ trackKeyFrame when it returns less than 10 and the frame has a key-frame) -> dict
+    (prm: the oracle's parameters, None = the defaults; cam = None-default callers pass the default camera, whose values are CamF's)"""
     NF = len(f["feat_oct"])
-    m1, n1 = oracle_stage1(o, f)
+    m1, n1 = oracle_stage1(o, f, cam, scale_factor)
     Xw, obs, oc = pose_inputs(f, m1)
-    pose2, outl2, ninl2 = o.optimize_current_pose(cam, f["pose_cw"], Xw, obs, oc)
+    pose2, outl2, ninl2 = o.optimize_current_pose(cam, f["pose_cw"], Xw, obs, oc, prm=prm)
     drop = np.where((outl2 != 0) & (m1 >= 0), m1, -1)
     kept = np.where(outl2 != 0, -1, m1)
     observed = f["last_observed"] if "last_observed" in f else np.ones(len(f["last_oct"]), np.uint8)
@@ -60,7 +62,7 @@ def oracle_front(o, cam, f):
         fr = dict(angle=f["feat_angle"], desc=f["feat_desc"], node_id=f["feat_node_id"], node_ptr=f["feat_node_ptr"], node_idx=f["feat_node_idx"])
         mk, nbow = o.search_by_bow(kf, fr, 0.7, True)
         Xw, obs, oc = pose_inputs(f, -np.ones(NF, np.int64), None, mk)
-        pose_k, outl_k, ninl_k = o.optimize_current_pose(cam, f["pose_lw"], Xw, obs, oc)
+        pose_k, outl_k, ninl_k = o.optimize_current_pose(cam, f["pose_lw"], Xw, obs, oc, prm=prm)
         kept_k = np.where(outl_k != 0, -1, mk)
         nk = int((kept_k >= 0).sum())
         r.update(pose=pose_k, ninl=ninl_k, match_last=-np.ones(NF, np.int64), match_kf=kept_k, drop_kf=np.where((outl_k != 0) & (mk >= 0), mk, -1),
@@ -68,7 +70,7 @@ def oracle_front(o, cam, f):
     return r
 
 
-def oracle_stage3(o, cam, f, pose, match_last, match_kf, drop_src, drop_kf):
+def oracle_stage3(o, cam, f, pose, match_last, match_kf, drop_src, drop_kf, scale_factor=1.2):
     """searchLocalPoints from `pose`: candidates minus the local map points the frame holds or dropped, features with an OBSERVED map
     point taken (orb_matcher.cpp:74-76)"""
     NP = len(f["mp_cand"])
@@ -81,16 +83,17 @@ def oracle_stage3(o, cam, f, pose, match_last, match_kf, drop_src, drop_kf):
     observed = f["last_observed"] if "last_observed" in f else np.ones(len(f["last_oct"]), np.uint8)
     taken = (f["feat_taken"] != 0) | ((match_last >= 0) & (observed[np.maximum(match_last, 0)] != 0)) | (match_kf >= 0)
     twc = o.pose_twc(pose)
-    uvr, lvl, vc, dd, iv, n = o.project_map_points(cam, pose, twc, f["mp_pos"], f["mp_normal"], f["mp_max_dist"], f["mp_min_dist"], cand.astype(np.uint8))
+    uvr, lvl, vc, dd, iv, n = o.project_map_points(cam, pose, twc, f["mp_pos"], f["mp_normal"], f["mp_max_dist"], f["mp_min_dist"], cand.astype(np.uint8),
+                                                    scale_factor=scale_factor)
     m, nm = o.search_by_projection(cam.width, cam.height, f["feat_uv"], f["feat_ur"], f["feat_oct"], f["feat_desc"], taken.astype(np.uint8), uvr, lvl, vc,
-                                   iv, f["mp_desc"], th=TH_LOCAL, nn_ratio=0.8)
+                                   iv, f["mp_desc"], th=TH_LOCAL, nn_ratio=0.8, scale_factor=scale_factor)
     return m, nm, iv
 
 
-def check_chain(o, cam, f, out, b, split=False):
+def check_chain(o, cam, f, out, b, split=False, prm=None, scale_factor=1.2):
     """every stage of frame b of the device's outputs `out` against the oracle; returns dict(front=..., replaced, pose4, m3) and raises
     AssertionError with the stage's name on a mismatch"""
-    r = oracle_front(o, cam, f)
+    r = oracle_front(o, cam, f, prm, scale_factor)
     assert out["counts"][b, 0] == r["n1"], "stage 1: matches"
     assert out["counts2"][b, 0] == r["ret_mm"], "stage 2: return value of trackWithMotionModel"
     assert out["counts2"][b, 3] == r["mode"], "mode"
@@ -101,14 +104,14 @@ def check_chain(o, cam, f, out, b, split=False):
         assert out["counts2"][b, 1] == r["nbow"] and out["counts2"][b, 2] == r["ret_kf"], "stage 2b: counts"
         assert np.array_equal(out["match_kf"][b], r["match_kf"]) and np.array_equal(out["drop_kf"][b], r["drop_kf"]), "stage 2b: matches"
     # stage 3 from the DEVICE's pose: bit-exact matches and in-view flags
-    m3, n3, iv = oracle_stage3(o, cam, f, out["pose_mm"][b], r["match_last"], r["match_kf"], r["drop_src"], r["drop_kf"])
+    m3, n3, iv = oracle_stage3(o, cam, f, out["pose_mm"][b], r["match_last"], r["match_kf"], r["drop_src"], r["drop_kf"], scale_factor)
     assert out["counts"][b, 2] == n3 and np.array_equal(out["match_local"][b], m3), "stage 3: matches"
     assert np.array_equal(out["inview"][b], iv), "stage 3: in-view flags"
     replaced = (m3 >= 0) & (r["match_last"] >= 0)  # a temporal point's feature took the local map point
     assert np.array_equal(out["match_last"][b], np.where(replaced, -1, r["match_last"])), "final last-frame associations"
     # stage 4 from the device's associations and pose
     Xw, obs, oc = pose_inputs(f, r["match_last"], m3, r["match_kf"])
-    pose4, outl4, ninl4 = o.optimize_current_pose(cam, out["pose_mm"][b], Xw, obs, oc)
+    pose4, outl4, ninl4 = o.optimize_current_pose(cam, out["pose_mm"][b], Xw, obs, oc, prm=prm)
     assert np.abs(out["pose"][b] - pose4).max() < 1e-6, "stage 4: pose"
     assert out["counts"][b, 3] == ninl4, "stage 4: inliers"
     assert np.array_equal(out["outlier"][b][oc >= 0], outl4[oc >= 0]), "stage 4: outliers"

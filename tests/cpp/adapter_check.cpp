@@ -23,7 +23,7 @@ static void wr(FILE* f, const T* p, size_t n) {
 }
 
 int main(int argc, char** argv) {
-  if (argc != 4) return 2;
+  if (argc != 4 && argc != 5) return 2;  // model, frame, output [, gl_params as raw bytes: a non-default configuration]
   try {
     gmmloc_hip::GMM gmm;
     if (!gmmloc_hip::GMM::loadGMMModel(argv[1], gmm)) {
@@ -39,6 +39,14 @@ int main(int argc, char** argv) {
     const int M = MN[0], N = MN[1];
     gl_camera cam{intr[0], intr[1], intr[2], intr[3], intr[4], MN[2], MN[3]};
     gmm.setCamera(cam);
+    if (argc == 5) {
+      FILE* pf = fopen(argv[4], "rb");
+      if (!pf) return 1;
+      gl_params prm;
+      rd(pf, &prm, 1);
+      fclose(pf);
+      gmm.params() = prm;
+    }
     gmmloc_hip::Pose pose0;
     std::vector<double> Xw(M * 3), obs(M * 3), uv(N * 2);
     std::vector<int32_t> oct(M);

@@ -63,8 +63,8 @@ def frame_kinds(m, feat_mp, lists):
 
 
 # ---- gl_track_frame_chain_map: name -> (frames' arguments, map seed, NKF, NFK, KFcap, NPcap)
-def _frames(name, cam):
-    F = synth.synth_chain_frame
+def _frames(name, cam, scale_factor=1.2):
+    F = lambda *a, **kw: synth.synth_chain_frame(*a, scale_factor=scale_factor, **kw)
     if name == "one":  # a frame of the size tools/chain_time.py times
         return [F(1200, 1000, 3000, 7100, cam)]
     if name == "plain":
@@ -87,10 +87,10 @@ CHAIN_SCENES = {"one": (21, 160, 1200, 64, 3328), "plain": (22, 300, 900, 64, 14
 CHAIN_MODES = {"one": [0], "plain": [0, 0, 0], "mixed": [0, 0, 1, 2], "fallback_one": [1], "all_valid": [0, 0, 1]}
 
 
-def chain_scene(name):
+def chain_scene(name, cam=None, scale_factor=1.2):
     """-> (frames, s = synth_chain_map's dict, lists in (the previous frame's), KFcap, NPcap)"""
-    cam = api.Camera()
-    frames = _frames(name, cam)
+    cam = api.Camera() if cam is None else cam
+    frames = _frames(name, cam, scale_factor)
     seed, NKF, NFK, KFcap, NPcap = CHAIN_SCENES[name]
     NMP = int(sum(len(f["mp_cand"]) for f in frames) * 1.3) + 64
     s = synth.synth_chain_map(frames, seed, NMP, NKF, NFK, pt_invalid_frac=(0.0 if name == "all_valid" else 0.04))

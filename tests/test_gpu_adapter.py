@@ -18,9 +18,15 @@ pytestmark = pytest.mark.gpu
 
 
 def test_cpp_adapter_matches_python_host(gpu, map_v1, gt_sync, tmp_path):
+    adapter_case(gpu, map_v1, gt_sync, tmp_path, api.Camera(), api.Params(), default=True)
+
+
+def adapter_case(gpu, map_v1, gt_sync, tmp_path, cam, prm, default=False):
+    """one frame and one local window through the g++-built driver and through the Python host, under `cam` / `prm` (the driver
+    gets the parameters as a file of the struct's bytes and sets them through GMM::params(), unless they are the defaults)"""
+    import ctypes
     torch, ctx = gpu
     mean, cov = map_v1
-    cam, prm = api.Camera(), api.Params()
     exe = build_adapter_check(tmp_path)
     g0 = api.GMM(ctx, mean, cov)
     g0.save(tmp_path / "m.gmm")
@@ -28,7 +34,7 @@ def test_cpp_adapter_matches_python_host(gpu, map_v1, gt_sync, tmp_path):
     M, N = 700, 400
     f = make_frames(mean, cov, gt_sync["V1_02_medium"], cam, 1, M, 900)[0]
     f["octave"][::9] = -1
-    uv = np.random.default_rng(1).uniform([0, 0], [752, 480], (N, 2))
+    uv = np.random.default_rng(1).uniform([0, 0], [cam.width, cam.height], (N, 2))
     with open(tmp_path / "frame.bin", "wb") as fh:
         np.array([M, N, cam.width, cam.height], np.int32).tofile(fh)
         np.array([cam.fx, cam.fy, cam.cx, cam.cy, cam.bf], np.float64).tofile(fh)
@@ -48,7 +54,12 @@ def test_cpp_adapter_matches_python_host(gpu, map_v1, gt_sync, tmp_path):
             np.ascontiguousarray(pb[key], dt).tofile(fh)
     env = dict(os.environ)
     env["LD_LIBRARY_PATH"] = os.path.dirname(gmmloc_amd._lib.LIB_PATH) + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([exe, str(tmp_path / "m.gmm"), str(tmp_path / "frame.bin"), str(tmp_path / "out.bin")], env=env,
+    extra = []
+    if not default:
+        with open(tmp_path / "params.bin", "wb") as fh:
+            fh.write(ctypes.string_at(ctypes.byref(prm.c()), ctypes.sizeof(prm.c())))
+        extra = [str(tmp_path / "params.bin")]
+    r = subprocess.run([exe, str(tmp_path / "m.gmm"), str(tmp_path / "frame.bin"), str(tmp_path / "out.bin")] + extra, env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     assert "components %d" % mean.shape[0] in r.stdout

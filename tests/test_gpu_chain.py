@@ -36,9 +36,9 @@ def pack(torch, frames):
     return a
 
 
-def run_chain(torch, ctx, frames):
-    cam, prm = api.Camera(), api.Params()
-    out = api.track_frame_chain(ctx, cam, prm, pack(torch, frames), th_mm=TH_MM, th_local=TH_LOCAL, nn_ratio=0.8, mono=False)
+def run_chain(torch, ctx, frames, cam=None, prm=None, scale_factor=1.2):
+    cam, prm = cam or api.Camera(), prm or api.Params()
+    out = api.track_frame_chain(ctx, cam, prm, pack(torch, frames), th_mm=TH_MM, th_local=TH_LOCAL, nn_ratio=0.8, mono=False, scale_factor=scale_factor)
     torch.cuda.synchronize()
     return {k: v.cpu().numpy() for k, v in out.items()}
 

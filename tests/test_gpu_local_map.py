@@ -165,13 +165,13 @@ def lm_dev(torch, s, lists):
     return lm
 
 
-def run_map_chain(torch, ctx, frames, s, lists, NPcap, md=None):
-    cam, prm = api.Camera(), api.Params()
+def run_map_chain(torch, ctx, frames, s, lists, NPcap, md=None, cam=None, prm=None, scale_factor=1.2):
+    cam, prm = cam or api.Camera(), prm or api.Params()
     a = pack_chain(torch, frames, NPcap)
     a = {k: v for k, v in a.items() if k not in api.CHAIN_MAP_IGNORED}  # (the call reads none of them)
     lm = lm_dev(torch, s, lists)
     md = to_dev(torch, s["map"]) if md is None else md
-    out = api.track_frame_chain_map(ctx, cam, prm, a, md, lm, th_mm=TH_MM, th_local=TH_LOCAL, nn_ratio=0.8)
+    out = api.track_frame_chain_map(ctx, cam, prm, a, md, lm, th_mm=TH_MM, th_local=TH_LOCAL, nn_ratio=0.8, scale_factor=scale_factor)
     torch.cuda.synchronize()
     return to_host(out), {k: v.cpu().numpy() for k, v in lm.items() if k in LIST_KEYS}
 

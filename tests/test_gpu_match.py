@@ -13,13 +13,13 @@ KEYS = ("feat_uv", "feat_ur", "feat_oct", "feat_desc", "feat_taken", "mp_uvr", "
         "mp_desc")
 
 
-def run_gpu(torch, ctx, frames, th, nn_ratio=0.8):
-    cam = api.Camera()
+def run_gpu(torch, ctx, frames, th, nn_ratio=0.8, scale_factor=1.2):
+    cam = api.Camera()  # (gl_search_by_projection reads the image size alone: the frames carry the one they were made for)
     cam.width, cam.height = frames[0]["width"], frames[0]["height"]
     T = lambda k: torch.from_numpy(np.ascontiguousarray(np.stack([f[k] for f in frames]))).cuda()
     a = {k: T(k) for k in KEYS}
     a["mp_level"] = a["mp_level"].to(torch.int32)
-    m, n = api.search_by_projection(ctx, cam, *[a[k] for k in KEYS], th=th, nn_ratio=nn_ratio)
+    m, n = api.search_by_projection(ctx, cam, *[a[k] for k in KEYS], th=th, nn_ratio=nn_ratio, scale_factor=scale_factor)
     torch.cuda.synchronize()
     return m.cpu().numpy(), n.cpu().numpy()
 
@@ -100,11 +100,11 @@ class CamF:  # cfg/v1.yaml intrinsics as the float config scalars (config.h:38-4
     width, height = 752, 480
 
 
-def run_gpu_frame(torch, ctx, frames, th, mono=False, chk=True):
-    cam = api.Camera()
+def run_gpu_frame(torch, ctx, frames, th, mono=False, chk=True, cam=None, scale_factor=1.2):
+    cam = cam or api.Camera()
     T = lambda k: torch.from_numpy(np.ascontiguousarray(np.stack([f[k] for f in frames]))).cuda()
     a = [T(k) for k in FKEYS]
-    m, n = api.search_by_projection_frame(ctx, cam, *a, th=th, mono=mono, check_orientation=chk)
+    m, n = api.search_by_projection_frame(ctx, cam, *a, th=th, mono=mono, check_orientation=chk, scale_factor=scale_factor)
     torch.cuda.synchronize()
     return m.cpu().numpy(), n.cpu().numpy()
 

@@ -11,7 +11,7 @@ from tests.test_gpu_pose import make_frames, pose_err
 pytestmark = pytest.mark.gpu
 
 
-def oracle_track(oracle, h, cam, f):
+def oracle_track(oracle, h, cam, f, prm=None):
     keep = np.nonzero(f["octave"] >= 0)[0]
     Xw = f["Xw"][keep]
     idx, d2 = oracle.associate3d(h, Xw)
@@ -19,7 +19,7 @@ def oracle_track(oracle, h, cam, f):
     L = len(keep)
     poses, pts, dropped, erase, it = oracle.joint_optimization(
         h, cam, 1, 0, f["pose_init"][None], np.zeros(1, np.uint8), Xw, assoc, np.arange(L + 1, dtype=np.int32),
-        np.zeros(L, np.int32), f["obs"][keep], f["octave"][keep])
+        np.zeros(L, np.int32), f["obs"][keep], f["octave"][keep], prm=prm)
     final = np.where(dropped == 1, -1, assoc)
     return keep, poses[0], pts, final, idx, d2
 

@@ -28,6 +28,19 @@ def test_every_declared_symbol_is_exported(lib):
     assert names == set(lib._gl_signatures), names ^ set(lib._gl_signatures)
 
 
+def test_config_table_names_exported_functions(lib):
+    """the table next to gl_camera / gl_params (which fields and which scale_factor each entry point reads) speaks of functions
+    the library exports, and of every exported function that takes a camera or parameters"""
+    hdr = open(os.path.join(ROOT, "include", "gmmloc_hip.h")).read()
+    rows = re.findall(r"^ \* (gl_[a-z0-9_]+) +\|([^|]*)\|([^|]*)\|", hdr, flags=re.M)
+    assert len(rows) >= 25
+    missing = [n for n, _, _ in rows if not hasattr(lib, n)]
+    assert not missing, missing
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    takes = set(re.findall(r"\b(gl_[a-z0-9_]+)\s*\([^;]*?const gl_(?:camera|params)\*", code))
+    assert takes and takes <= {n for n, _, _ in rows}, takes - {n for n, _, _ in rows}
+
+
 def test_default_params_match_reference_config(lib):
     from gmmloc_amd import api
     p = api.Params()

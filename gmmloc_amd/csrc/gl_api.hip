@@ -19,7 +19,7 @@ void set_error(const char* fmt, ...) {
 
 // option table: name as in gl_ctx_set_option; the environment variable is GMMLOC_<NAME IN CAPITALS>
 #define GL_OPTION_LIST(X) \
-  X(ba_shape) X(ba_step32) X(ba_persist) X(ba_slow) X(ba_fixed_pack) X(ba_rendezvous_us) X(ba_test_abort_seq) X(ba_same_xcd) X(pose_waves) X(pose_regs) X(pose_compact) X(pose_compact_cap) X(fuse_records) X(bagen_nb) X(bagen_mode) X(view_slot_lds) X(view_threads) \
+  X(ba_shape) X(ba_step32) X(ba_persist) X(ba_slow) X(ba_fixed_pack) X(ba_rendezvous_us) X(ba_test_abort_seq) X(test_scratch_fill) X(ba_same_xcd) X(pose_waves) X(pose_regs) X(pose_compact) X(pose_compact_cap) X(fuse_records) X(bagen_nb) X(bagen_mode) X(view_slot_lds) X(view_threads) \
   X(assoc_index_min) X(assoc_grid) X(assoc_coop) X(assoc_pack_mb) X(assoc_cell8) X(assoc_cell) X(assoc_globcells) X(match_desc_lds) X(pipe_lanes) X(pipe_judge) X(pipe_fuse_asm) X(schur_kper) X(assoc_screen32)
 double* option_slot(Options& o, const char* name) {
 #define X(n) \
@@ -56,8 +56,19 @@ int ctx_scratch(Ctx* c, size_t bytes, void** out, int which) {
       return GL_ERR_NOMEM;
     }
     b.bytes = want;
+    if (c->opt.test_scratch_fill >= 0) GL_HIP(hipMemsetAsync(b.p, (int)c->opt.test_scratch_fill, want, c->stream));  // tests only
   }
   *out = b.p;
+  return GL_OK;
+}
+
+// option test_scratch_fill, at the moment it is set: every block the context holds, and the device staging buffer, over its whole length
+int scratch_fill_now(Ctx* c) {
+  const int v = (int)c->opt.test_scratch_fill;
+  GL_HIP(hipSetDevice(c->device));
+  for (const ScratchBlock& b : c->scratch)
+    if (b.p) GL_HIP(hipMemsetAsync(b.p, v, b.bytes, c->stream));
+  if (c->dev_stage) GL_HIP(hipMemsetAsync(c->dev_stage, v, c->stage_bytes, c->stream));
   return GL_OK;
 }
 
@@ -194,7 +205,12 @@ int gl_ctx_set_option(gl_ctx_t* ctx, const char* name, double value) {
     gl::set_error("gl_ctx_set_option: unknown option '%s'", name);
     return GL_ERR_ARG;
   }
+  if (slot == &gl::C(ctx)->opt.test_scratch_fill && value > 255) {
+    gl::set_error("gl_ctx_set_option: test_scratch_fill is a byte (0 .. 255) or -1");
+    return GL_ERR_ARG;
+  }
   *slot = value;
+  if (slot == &gl::C(ctx)->opt.test_scratch_fill && value >= 0) return gl::scratch_fill_now(gl::C(ctx));
   return GL_OK;
 }
 int gl_ctx_get_option(gl_ctx_t* ctx, const char* name, double* value) {

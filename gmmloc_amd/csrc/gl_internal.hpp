@@ -114,6 +114,8 @@ struct Options {
   double ba_rendezvous_us = 200;   // time limit of EVERY exchange of the latency shape (the fallback it protects costs ~0.5 ms; 0: a workgroup
                                    // gives up at its first unsuccessful look -> follow-up kernel; tests)
   double ba_test_abort_seq = 0;    // tests: n > 0 makes the last workgroup of every frame give up at its n-th exchange
+  double test_scratch_fill = -1;   // tests: 0 .. 255 fills every scratch block and the device staging buffer with that byte when it is set, and
+                                   // every block ctx_scratch allocates while it stays >= 0 (-1: off; gmmloc_hip.h)
   double pose_regs = 1;         //   0: the frame-at-a-time shapes read their edges from global memory every trial (A/B)
   double bagen_nb = 0;          // gl_joint_optimization, persistent kernel: 0 auto, n workgroups per problem
   double bagen_mode = 0;        //   0: by WINDOW size (never by B), 1: the persistent kernel k_ba_gen, 2: the pipelined shape, 3: persistent, whole batch in one launch (gmmloc_hip.h)
@@ -201,6 +203,7 @@ struct Ctx {
 
 // block `which` (SCRATCH_*) of at least `bytes`; growing it waits for the stream and drops the old contents
 int ctx_scratch(Ctx* c, size_t bytes, void** out, int which = SCRATCH_MAIN);
+int scratch_fill_now(Ctx* c);  // gl_ctx_set_option(test_scratch_fill >= 0)
 // consecutive 256-aligned regions of a scratch block from `off` on
 struct Regions {
   size_t off;

@@ -166,6 +166,10 @@ void* gl_ctx_stream(gl_ctx_t* ctx);
  *   ba_fixed_pack (1: fixed observers of gl_track_frames_anchored always through the general kernel),
  *   pipe_lanes, pipe_judge, schur_kper (-1 automatic; A/B switches of the pipelined local BA in batches: streams a call is split over,
  *     the verdict on a trial as a kernel of its own, chunks per wave of the Schur pass - none changes a bit),
+ *   test_scratch_fill (-1 off; TEST-ONLY): setting it to v in 0 .. 255 fills every scratch block the context holds, and the device
+ *     staging buffer of gl_track_frame_host, over its whole length with byte v (a memset on the context's stream); while it stays
+ *     >= 0 every scratch block the context allocates is filled the same way right after its allocation.  Nothing else reads it - no
+ *     fill between the stages of a call - and setting it back to -1 only stores the value.  No entry point's result may depend on v,
  *   ba_slow, ba_test_abort_seq, pose_waves, pose_regs, bagen_nb, view_slot_lds, view_threads, assoc_index_min, match_desc_lds, fuse_records, pose_compact_cap. */
 int gl_ctx_set_option(gl_ctx_t* ctx, const char* name, double value);
 int gl_ctx_get_option(gl_ctx_t* ctx, const char* name, double* value);

@@ -62,7 +62,9 @@ struct ChainSrc {  // edge i of ONE frame (pointers at the frame's rows; match_*
 // their own (a dependent launch costs the device ~5 us whatever it does, profiles/r6_chain_trace.txt): the flags cleared
 // (outlier_clear), a last-frame match that stage 3 replaced cleared (`finalise`: match_last / match_local / match_kf name the
 // feature's ONE map point when the chain returns), the preceding search's count copied into counts[., nm_slot], the fallback's start
-// pose (pose_dst := pose_src).  gate: only the frames with gate[b] != 0 get edges (trackKeyFrame: the flagged frames).
+// pose (pose_dst := pose_src).  gate: only the frames with gate[b] != 0 get edges (trackKeyFrame: the flagged frames).  nm_min > 0:
+// nor does a frame whose preceding search found fewer than nm_min matches (trackWithMotionModel returns before its optimisation,
+// tracking.cpp:352) - the optimisation then returns at its own `< 3` and leaves pose and flags alone.
 constexpr int T_GATHER = 1024;  // (a frame's 1 200 features in two rounds: every pass is a chain of dependent loads)
 __global__ __launch_bounds__(T_GATHER) void k_chain_gather(int B, int NF, int NL, int NP, int NK, const double* __restrict__ feat_uv,
                                                      const float* __restrict__ feat_ur, const int32_t* __restrict__ feat_oct,
@@ -71,10 +73,12 @@ __global__ __launch_bounds__(T_GATHER) void k_chain_gather(int B, int NF, int NL
                                                      const double* __restrict__ kf_pt, const int32_t* __restrict__ gate, double* __restrict__ Xw,
                                                      double* __restrict__ obs, int32_t* __restrict__ oct, gl::PoseCompacted pc, int finalise,
                                                      uint8_t* __restrict__ outlier_clear, const int32_t* __restrict__ nm, int32_t* __restrict__ counts,
-                                                     int nm_slot, const double* __restrict__ pose_src, double* __restrict__ pose_dst) {
+                                                     int nm_slot, int nm_min, const double* __restrict__ pose_src,
+                                                     double* __restrict__ pose_dst) {
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= B) return;
-  const bool on = !gate || gate[b] != 0;
+  const int nm_b = nm ? nm[b] : 0;
+  const bool on = (!gate || gate[b] != 0) && !(nm && nm_b < nm_min);
   const size_t fb = (size_t)b * NF;
   const ChainSrc src = {feat_uv + fb * 2, feat_ur + fb, feat_oct + fb, (on && match_last) ? match_last + fb : nullptr, last_pt + (size_t)b * NL * 3,
                         (on && match_local) ? match_local + fb : nullptr, mp_pos + (size_t)b * NP * 3, (on && match_kf) ? match_kf + fb : nullptr,
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(T_GATHER) void k_chain_gather(int B, int NF, int NL
     for (int i = tid; i < NF; i += T_GATHER)
       if (match_local[fb + i] >= 0 && match_last[fb + i] >= 0) match_last[fb + i] = -1;
   }
-  if (tid == 0 && nm) counts[(size_t)b * 4 + nm_slot] = nm[b];
+  if (tid == 0 && nm) counts[(size_t)b * 4 + nm_slot] = nm_b;
   if (tid < 7 && pose_dst) pose_dst[(size_t)b * 7 + tid] = pose_src[(size_t)b * 7 + tid];
 }
 
@@ -108,7 +112,8 @@ __global__ __launch_bounds__(T_GATHER) void k_chain_gather(int B, int NF, int NL
 //  GLUE_AFTER_MM - after the first optimisation (tracking.cpp:360-374): an outlier's feature loses its map point and its flag (drop_src
 //    remembers which last-frame feature it had: that map point has been SEEN by this frame, last_visible_idx_ = idx, :367); what
 //    trackWithMotionModel returns is the number of kept matches whose map point has observations (:370) - 0 when the search found fewer
-//    than 20 (:344-345).  Tracking::track (:50-58) falls back to trackKeyFrame when that number is below 10: fb_flag.
+//    than 20 (:352: such a frame's optimisation had no edge, k_chain_gather's nm_min, so it has no outlier here and drop_src is -1
+//    throughout).  Tracking::track (:50-58) falls back to trackKeyFrame when that number is below 10: fb_flag.
 //  GLUE_AFTER_FB - what trackKeyFrame does with its optimisation's result (:313-330), for the flagged frames: the outliers lose their map
 //    point and their flag (seen: drop_kf), the pose is the optimised one, and the frame's associations are the key-frame's alone
 //    (`curr_frame_->mappoints_ = mappts` dropped every last-frame match).  mode 1: tracked through the key-frame; 2: fewer than 10 kept
@@ -318,6 +323,7 @@ struct ChainOpt {
   int32_t* ninl;               // inlier counts out, ninl[b * nin_stride]
   int nin_stride;
   int nm_slot;
+  int nm_min;                  // with nm_slot >= 0: a frame whose S.nm is below it has no edges (0: every frame has)
   const double* pose_src;      // pose := pose_src first (the fallback starts from the last frame's pose), or null
 };
 int chain_optimise(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* prm, int B, int NF, int NL, int NP, int NK, const gl_track_chain_io* io,
@@ -325,7 +331,7 @@ int chain_optimise(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* prm, in
   gl::Ctx* c = gl::C(ctx);
   k_chain_gather<<<B, T_GATHER, 0, c->stream>>>(B, NF, NL, NP, NK, io->feat_uv, io->feat_ur, io->feat_oct, o.match_last, io->last_pt, o.match_local, io->mp_pos,
                                            o.match_kf, io->kf_pt, o.gate, S.Xw, S.obs, S.oct, S.pc, o.finalise, o.clear_outlier ? o.outlier : nullptr,
-                                           o.nm_slot >= 0 ? S.nm : nullptr, io->counts, o.nm_slot, o.pose_src, o.pose_src ? o.pose : nullptr);
+                                           o.nm_slot >= 0 ? S.nm : nullptr, io->counts, o.nm_slot, o.nm_min, o.pose_src, o.pose_src ? o.pose : nullptr);
   GL_HIP(hipGetLastError());
   if (S.pc.MC > 0) return gl::pose_compacted_launch(ctx, cam, prm, B, NF, o.pose, S.Xw, S.obs, S.oct, o.outlier, o.ninl, o.nin_stride, S.pc);
   return gl::optimize_current_pose_plain(ctx, cam, prm, B, NF, o.pose, S.Xw, S.obs, S.oct, o.outlier, o.ninl, o.nin_stride);
@@ -408,8 +414,9 @@ int chain_front(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* prm, float
                                     io->feat_desc, io->feat_taken, io->last_pt, io->last_valid, io->last_oct, io->last_angle, io->last_desc, 2 * th_mm, mono, 1,
                                     io->match_last, S.nm, S.nm, 20);
   if (rc != GL_OK) return rc;
-  // ---- stage 2: optimizeCurrentPose on the matched features, outliers dropped (:348-371)
-  ChainOpt o2 = {io->pose_cw, io->match_last, nullptr, nullptr, nullptr, 0, io->outlier, true, io->counts + 1, 4, 0, nullptr};
+  // ---- stage 2: optimizeCurrentPose on the matched features, outliers dropped (:356-373) - of the frames with 20 matches or more: the
+  // reference returns before it otherwise (:352), so such a frame keeps its pose and its matches and drops nothing
+  ChainOpt o2 = {io->pose_cw, io->match_last, nullptr, nullptr, nullptr, 0, io->outlier, true, io->counts + 1, 4, 0, 20, nullptr};
   rc = chain_optimise(ctx, cam, prm, B, NF, NL, NP, NK, io, S, o2);
   if (rc != GL_OK) return rc;
   const GlueArgs ga = glue_args(B, NF, NL, NP, io, S, drop_src, drop_kf);
@@ -423,7 +430,7 @@ int chain_front(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* prm, float
                             io->kf_node_ptr, io->kf_node_idx, io->feat_angle, io->feat_desc, io->feat_nnode, io->feat_node_id, io->feat_node_ptr,
                             io->feat_node_idx, io->match_kf, S.nm_bow, S.fb_flag);
   if (rc != GL_OK) return rc;
-  ChainOpt ofb = {S.pose_fb, nullptr, nullptr, io->match_kf, S.fb_flag, 0, S.outl_fb, true, S.ninl, 1, -1, io->pose_lw};
+  ChainOpt ofb = {S.pose_fb, nullptr, nullptr, io->match_kf, S.fb_flag, 0, S.outl_fb, true, S.ninl, 1, -1, 0, io->pose_lw};
   rc = chain_optimise(ctx, cam, prm, B, NF, NL, NP, NK, io, S, ofb);
   if (rc != GL_OK) return rc;
   return through_local ? glue_launch<GLUE_AFTER_FB | GLUE_POSE_MM | GLUE_BEFORE_LOCAL>(c, ga) : glue_launch<GLUE_AFTER_FB | GLUE_POSE_MM>(c, ga);
@@ -445,7 +452,7 @@ int chain_back(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* prm, float 
                               io->mp_normal, io->mp_max_dist, io->mp_min_dist, S.cand, io->mp_desc, th_local, nn_ratio, io->match_local, S.nm, io->inview);
   if (rc != GL_OK) return rc;
   // ---- stage 4: trackLocalMap's optimizeCurrentPose on every feature with a map point (:272-299)
-  ChainOpt o4 = {io->pose_cw, io->match_last, io->match_local, fbk ? io->match_kf : nullptr, nullptr, 1, io->outlier, false, io->counts + 3, 4, 2, nullptr};
+  ChainOpt o4 = {io->pose_cw, io->match_last, io->match_local, fbk ? io->match_kf : nullptr, nullptr, 1, io->outlier, false, io->counts + 3, 4, 2, 0, nullptr};
   return chain_optimise(ctx, cam, prm, B, NF, NL, NP, NK, io, S, o4);
 }
 

@@ -431,9 +431,12 @@ int gl_update_map_points(gl_ctx_t* ctx, float scale_factor, int what, int NP, in
  * intermediate array in the context's scratch:
  *   1  gl_search_by_projection_frame(th_mm, check_orientation = 1): ORBmatcher(0.9, true).searchByProjection(curr, last, 7); a frame
  *      with fewer than 20 matches is searched again with 2 x th_mm (:340-346; the second launch skips the other frames)
- *   2  gl_optimize_current_pose on the matched features (Xw = the last frame's map point), then the outliers lose their map point
- *      and their is_outlier_ flag (:360-371; drop_src remembers the map point: it has been seen, :367).  counts2[0] = what
- *      trackWithMotionModel returns: the kept matches whose map point has observations (last_observed), 0 below 20 matches.
+ *   2  a frame with 20 matches or more: gl_optimize_current_pose on the matched features (Xw = the last frame's map point), then the
+ *      outliers lose their map point and their is_outlier_ flag (:356-373; drop_src remembers the map point: it has been seen,
+ *      :368).  counts2[0] = what trackWithMotionModel returns: the kept matches whose map point has observations (last_observed).
+ *      A frame with FEWER than 20 matches returns before the optimisation as the reference does (:352): counts2[0] = 0, its pose
+ *      (pose_mm = pose_cw as passed in, bit for bit), its stage-1 matches and its flags are left alone, counts[1] = 0, drop_src = -1
+ *      throughout - no map point of it has been seen.
  *   2b (only with the key-frame buffers, kf_desc != NULL) a frame with counts2[0] < 10 (:50-58) goes through trackKeyFrame instead:
  *      gl_search_by_bow(0.7, check_orientation = 1) against the reference key-frame, pose = the LAST frame's, gl_optimize_current_pose,
  *      outliers dropped (drop_kf); its associations are then the key-frame's alone (match_last = -1, match_kf).  The other frames'

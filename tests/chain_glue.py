@@ -49,8 +49,11 @@ def oracle_front(o, cam, f, prm=None, scale_factor=1.2):
     (prm: the oracle's parameters, None = the defaults; cam = None-default callers pass the default camera, whose values are CamF's)"""
     NF = len(f["feat_oct"])
     m1, n1 = oracle_stage1(o, f, cam, scale_factor)
-    Xw, obs, oc = pose_inputs(f, m1)
-    pose2, outl2, ninl2 = o.optimize_current_pose(cam, f["pose_cw"], Xw, obs, oc, prm=prm)
+    if n1 < 20:  # tracking.cpp:352: returns before optimizeCurrentPose (:356) and the outlier loop (:360-373)
+        pose2, outl2, ninl2 = np.array(f["pose_cw"], np.float64), np.zeros(NF, np.uint8), 0
+    else:
+        Xw, obs, oc = pose_inputs(f, m1)
+        pose2, outl2, ninl2 = o.optimize_current_pose(cam, f["pose_cw"], Xw, obs, oc, prm=prm)
     drop = np.where((outl2 != 0) & (m1 >= 0), m1, -1)
     kept = np.where(outl2 != 0, -1, m1)
     observed = f["last_observed"] if "last_observed" in f else np.ones(len(f["last_oct"]), np.uint8)

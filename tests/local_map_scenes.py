@@ -79,12 +79,17 @@ def _frames(name, cam, scale_factor=1.2):
     if name == "all_valid":  # no invalid map point: tests/chain_glue.py::check_chain (which knows no clearing) applies
         return [F(700, 600, 1400, 7500 + b, cam, NK=500, temporal_frac=(0.3 if b == 1 else 0.0), pred_rot_deg=(10.0 if b == 2 else None))
                 for b in range(3)]
+    if name == "branches":  # tests/track_cases.py: 19 matches (tracking.cpp:352; its would-be optimisation has outliers), a
+        from tests import oracle_lib, track_cases  # trackWithMotionModel that returns 9 (:53), a frame that tracks (20 matches)
+        assert scale_factor == 1.2
+        return [track_cases.frame(oracle_lib.load(), n) for n in ("n1_19_s7001", "ret_mm_9", "n1_20_s7001")]
     raise KeyError(name)
 
 
 CHAIN_SCENES = {"one": (21, 160, 1200, 64, 3328), "plain": (22, 300, 900, 64, 1408), "mixed": (23, 400, 1000, 64, 1600),
-                "fallback_one": (24, 160, 1000, 64, 1600), "all_valid": (25, 300, 1000, 64, 1728)}
-CHAIN_MODES = {"one": [0], "plain": [0, 0, 0], "mixed": [0, 0, 1, 2], "fallback_one": [1], "all_valid": [0, 0, 1]}
+                "fallback_one": (24, 160, 1000, 64, 1600), "all_valid": (25, 300, 1000, 64, 1728), "branches": (26, 200, 500, 64, 768)}
+WITHOUT_INVALID_POINTS = ("all_valid", "branches")  # (what is compared stage by stage with a checker that knows no clearing)
+CHAIN_MODES = {"one": [0], "plain": [0, 0, 0], "mixed": [0, 0, 1, 2], "fallback_one": [1], "all_valid": [0, 0, 1], "branches": [1, 1, 0]}
 
 
 def chain_scene(name, cam=None, scale_factor=1.2):
@@ -93,7 +98,7 @@ def chain_scene(name, cam=None, scale_factor=1.2):
     frames = _frames(name, cam, scale_factor)
     seed, NKF, NFK, KFcap, NPcap = CHAIN_SCENES[name]
     NMP = int(sum(len(f["mp_cand"]) for f in frames) * 1.3) + 64
-    s = synth.synth_chain_map(frames, seed, NMP, NKF, NFK, pt_invalid_frac=(0.0 if name == "all_valid" else 0.04))
+    s = synth.synth_chain_map(frames, seed, NMP, NKF, NFK, pt_invalid_frac=(0.0 if name in WITHOUT_INVALID_POINTS else 0.04))
     B = len(frames)
     lists = previous_lists(B, NKF, NMP, KFcap, NPcap)
     for b in range(B):

@@ -45,8 +45,9 @@ def run_chain(torch, ctx, frames, cam=None, prm=None, scale_factor=1.2):
 
 @pytest.mark.parametrize("NF,NL,NP", [(64, 64, 64), (30, 25, 40), (8, 6, 5), (130, 20, 300)])
 def test_track_frame_chain_tiny_frames(gpu, oracle, NF, NL, NP):
-    """Frames too small to track (fewer than 20 matches: trackWithMotionModel returns 0, optimisations of a handful of edges or of none):
-    every stage still equal to the oracle's sequence on the inputs the device gave it."""
+    """Frames too small to track (fewer than 20 matches: trackWithMotionModel returns 0 BEFORE its optimisation, tracking.cpp:352 - the
+    pose and the stage-1 matches stay, nothing is dropped; trackLocalMap's optimisation of a handful of edges or of none): every stage
+    still equal to the oracle's sequence on the inputs the device gave it."""
     torch, ctx = gpu
     cam = api.Camera()
     frames = [synth.synth_chain_frame(NF, NL, NP, 4800 + 7 * NF + b, cam) for b in range(3)]

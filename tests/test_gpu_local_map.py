@@ -208,7 +208,7 @@ def run_halves(torch, ctx, frames, s, lists, NPcap, fit=False):
     return out, ls, fs
 
 
-@pytest.mark.parametrize("name", ["one", "plain", "mixed", "fallback_one"])
+@pytest.mark.parametrize("name", ["one", "plain", "mixed", "fallback_one", "branches"])
 def test_chain_map_equals_front_host_back(gpu, name):
     """plain frames, temporal points, the key-frame fallback and a lost frame, B = 1 and mixed batches: every output of the one call
     equals, bit for bit, the two halves around the host's updateLocalMap with NP = NPcap and the same padding; twice the same bytes"""

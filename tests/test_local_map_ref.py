@@ -187,7 +187,7 @@ def test_update_scenes_hold_every_kind_of_frame(name):
 def test_chain_scenes_match_something_in_every_tracked_frame(oracle, name):
     """the reference sequence (oracle front -> restatement -> gather -> oracle stage 3) on the chain scenes: the frames take the paths
     their scene is named for, every frame that is not lost finds local map points in stage 3, every tracked frame's list is new and
-    fits NPcap with little to spare, and (but for the scene without invalid points) some held point is cleared"""
+    fits NPcap with little to spare, and (but for the scenes without invalid points) some held point is cleared"""
     cam = api.Camera()
     frames, s, lists, KFcap, NPcap = S.chain_scene(name)
     cleared = 0
@@ -204,4 +204,4 @@ def test_chain_scenes_match_something_in_every_tracked_frame(oracle, name):
         assert not np.array_equal(h["lists"]["local_mp"][0], lists["local_mp"][b])
         held_before = R.derive_feat_mp(dict(s["map"], mp_valid=None), r["match_last"], r["match_kf"], s["last_mp"][b], s["kf_feat_mp"][b], r["mode"])[0]
         cleared += int(((held_before >= 0) & (h["feat_mp"] < 0)).sum())
-    assert (cleared > 0) == (name != "all_valid")
+    assert (cleared > 0) == (name not in S.WITHOUT_INVALID_POINTS)

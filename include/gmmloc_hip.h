@@ -301,7 +301,11 @@ int gl_knn3d(gl_ctx_t* ctx, const gl_gmm_t* gmm, const double* pts_dev, int N, i
  *  cand_dev: B x N x k int32 parent indices in kNN order, gated by 2-D MDist2 < 9, -1 padded;
  *  ncand_dev: B x N int32;
  *  view_ids_dev (optional): B x view_cap int32 rendered parent ids sorted by depth
- *  descending (components2d_ order), -1 padded; nview_dev (optional): B int32. */
+ *  descending (components2d_ order), -1 padded; nview_dev (optional): B int32.
+ *  Components of bit-equal depth keep the order of the merged list (the slot a component took, not its
+ *  index): the reference's std::sort leaves them unspecified, the sort here is stable.  nview counts every
+ *  rendered component; view_ids holds the first view_cap of them when there are more (the candidate tables
+ *  are searched over all of them either way). */
 int gl_search2d(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, int B, const double* pose_dev, int N,
                 const double* uv_dev, const int32_t* nfeat_dev, int k, int32_t* cand_dev, int32_t* ncand_dev,
                 int view_cap, int32_t* view_ids_dev, int32_t* nview_dev);

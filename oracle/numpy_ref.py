@@ -291,7 +291,10 @@ def optimize_point(pt, uvr, octave, pose7, normal, mu, proj_z2, cam, prm):
         H = s * J.T @ J + lam * np.outer(normal, normal)
         b = -(s * J.T @ e + lam * normal * es)
         chi2_proj, chi2_str = s * e @ e, lam * es * es
-        x = x + np.linalg.solve(H, b)
+        try:
+            x = x + np.linalg.solve(H, b)
+        except np.linalg.LinAlgError:  # solver failure ends optimize(); the errors above stay
+            break
     res = True
     if chi2_proj > 7.815:
         res = False
@@ -301,13 +304,16 @@ def optimize_point(pt, uvr, octave, pose7, normal, mu, proj_z2, cam, prm):
 
 
 # ------------------------------------------------------------------ A8
-def check_map_association(pt, uvr, octave, pose7, cands, comps, mean, nbs, cam, prm):
+def check_map_association(pt, uvr, octave, pose7, cands, comps, mean, nbs, cam, prm, ncand=None):
     """GMMLoc::checkMapAssociation (gmmloc_opt.cpp:156-258).  cands: parent component indices of the feature
     (kf->comps_[idx]); comps: build_components() dict; nbs: list of neighbour index lists (nbs_).
+    ncand: the length of the list where cands is a row of a -1 padded table (None: the entries >= 0 are the
+    list).  Entries < 0 among the first ncand are passed over, but the list is not empty (:162-164) for them.
     Returns (component or -1, point) -- the point is moved exactly where the reference writes it."""
     pt0 = np.array(pt, float)
-    cands = [int(c) for c in cands if c >= 0]
-    if not cands:
+    listed = [int(c) for c in (cands if ncand is None else cands[:ncand])]
+    cands = [c for c in listed if c >= 0]
+    if not (cands if ncand is None else listed):
         return -1, pt0
     T = SE3.from7(pose7)
     z = min(1.0, T.map(pt0)[2])

@@ -56,6 +56,20 @@ class gl_map_remove_out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("result", "dead_mp", "obs_new_pos")] + [("dead_cap", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class gl_map_add_lists(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("new_pos", "new_assoc", "new_ref_kf", "n_new_mp", "new_kf", "n_new_kf", "att_mp", "att_kf", "att_feat",
+                                           "n_attach", "walk_kf", "n_walk")] +
+                [(k, C.c_int32) for k in ("new_mp_cap", "new_kf_cap", "attach_cap", "walk_cap")])
+
+
+class gl_map_add_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("result", "already_mp", "obs_new_pos")] + [("already_cap", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class gl_map_fuse_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("result", "repl_src", "repl_tgt", "obs_new_pos")] + [("repl_cap", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class gl_ba_window(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("Pcap", "Fcap", "Lcap", "Ocap")] + [(k, C.c_void_p) for k in BA_WINDOW_ARRAYS])
 
@@ -129,6 +143,8 @@ def load():
         "gl_ba_window_apply": (i32, [vp, vp, vp, vp, i32, vp] + [vp] * 5),
         "gl_cull_keyframes": (i32, [vp, vp, vp, vp, C.c_float, i32, i32] + [vp] * 8),
         "gl_map_remove": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+        "gl_map_add": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "gl_map_fuse": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
         "gl_search_local_points": (i32, [vp, vp, C.c_float, i32, i32, i32] + [vp] * 13 + [C.c_float, C.c_float, vp, vp, vp]),
         "gl_gather_triangulation_matches": (i32, [vp, i32, i32, i32, i32, i32] + [vp] * 32),
         "gl_optimize_point": (i32, [vp, vp, P(gl_camera), P(gl_params), i32] + [vp] * 10),

@@ -20,11 +20,8 @@ namespace {
 
 using namespace gl::mapdev;
 
-typedef unsigned long long u64;
-
 constexpr int T_CULL = 1024;
 constexpr int T_ME = 256;
-constexpr int SCAN_T = 1024, SCAN_PER = 4, SCAN_TILE = SCAN_T * SCAN_PER;
 constexpr int RANK_NONE = 0x7f7f7f7f;  // (a byte pattern: the ranks are reset by one memset); also "never dies"
 
 // ---------------------------------------------------------------------------------------------------------------- culling
@@ -279,37 +276,14 @@ __global__ __launch_bounds__(T_ME) void k_me_points(EditArgs a) {
 // the exclusive scan of cnt inside every tile of SCAN_TILE points, the tile's sum to tile[]
 __global__ __launch_bounds__(SCAN_T) void k_me_scan(EditArgs a) {
   __shared__ u64 s_w[SCAN_T / 64];
-  const int tid = threadIdx.x;
-  const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)tid * SCAN_PER;
-  u64 v[SCAN_PER], sum = 0;
-#pragma unroll
-  for (int u = 0; u < SCAN_PER; ++u) {
-    v[u] = base + u < (size_t)a.NMP ? a.cnt[base + u] : 0ull;
-    sum += v[u];
-  }
-  u64 total;
-  u64 at = block_excl_scan<SCAN_T, u64>(sum, s_w, tid, &total);
-#pragma unroll
-  for (int u = 0; u < SCAN_PER; ++u) {
-    if (base + u < (size_t)a.NMP) a.cnt[base + u] = at;
-    at += v[u];
-  }
-  if (tid == 0) a.tile[blockIdx.x] = total;
+  tile_scan(a.cnt, a.tile, (size_t)a.NMP, s_w, threadIdx.x, blockIdx.x);
 }
 
 // one workgroup: the exclusive scan of the tile sums; the totals
 __global__ __launch_bounds__(SCAN_T) void k_me_scan_top(EditArgs a, int ntile) {
   __shared__ u64 s_w[SCAN_T / 64];
   const int tid = threadIdx.x;
-  u64 carry = 0;
-  for (int i0 = 0; i0 < ntile; i0 += SCAN_T) {
-    const int i = i0 + tid;
-    const u64 v = i < ntile ? a.tile[i] : 0ull;
-    u64 total;
-    const u64 at = block_excl_scan<SCAN_T, u64>(v, s_w, tid, &total);
-    if (i < ntile) a.tile[i] = carry + at;
-    carry += total;
-  }
+  const u64 carry = tile_scan_top(a.tile, ntile, s_w, tid);
   if (tid == 0) {
     const int nobs = (int)(unsigned)(carry & 0xffffffffull), ndead = (int)(unsigned)(carry >> 32);
     a.nptr[a.NMP] = nobs;

@@ -1,0 +1,212 @@
+"""Growing the resident map on the device: gl_map_add (new rows, new key-frames, attach triples, the walk of processNewKeyFrame) and
+gl_map_fuse (the second half of fuseObservations with Map::replaceMapPoint); rules in include/gmmloc_hip.h.
+
+The arrays keep their allocation and the counts grow.  `map` / `ba` are the dicts of api.map_remove whose tensors are the CAPACITY
+buffers - the per-point arrays NMPcap rows (obs_ptr NMPcap + 1), obs_kf / obs_feat OBScap entries, the key-frame tables at least NKF
+rows - and `sizes` = (NMP, NKF, NOBS) says how much of them the map fills (None: all of it).  Every call returns the new sizes and
+`map` / `ba` cut to them (views of the same tensors): what the readers (api.update_connections, api.ba_window_build, ...) take."""
+import ctypes as C
+
+from . import _lib
+from .api import MAP_BA_DTYPES, MAP_VIEW_DTYPES, _check, _ptr, _tensor, fuse_search, project_map_points
+
+GROW_OBS_TRUNCATED, GROW_MP_TRUNCATED, FUSE_REPL_TRUNCATED, ADD_ALREADY_TRUNCATED = 1, 2, 4, 8
+_PER_POINT = ("mp_valid", "mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc", "mp_assoc")
+_PER_KF = ("kf_valid", "kf_mp", "kf_pose", "kf_twc", "kf_uvr", "kf_oct")
+_PER_OBS = ("obs_kf", "obs_feat")
+_TRAIL = {"mp_pos": (3,), "mp_normal": (3,), "mp_desc": (32,), "kf_pose": (7,), "kf_twc": (3,)}
+
+
+def map_views(map, ba, sizes):
+    """the two dicts cut to sizes = (NMP, NKF, NOBS): views of the same tensors, the dicts the readers of the resident map take"""
+    NMP, NKF, NOBS = sizes
+    def cut(k, t):
+        if t is None or not hasattr(t, "shape"):
+            return t
+        n = NMP + 1 if k == "obs_ptr" else NMP if k in _PER_POINT else NKF if k in _PER_KF else NOBS if k in _PER_OBS else None
+        return t if n is None else t[:n]
+    return {k: cut(k, t) for k, t in map.items()}, {k: cut(k, t) for k, t in ba.items()}
+
+
+def _buffers(map, ba, sizes, need_ba):
+    """check every tensor of the two dicts against the capacities and `sizes` -> (NMP, NKF, NFK, NOBS, NMPcap, OBScap, device)"""
+    for k in map:
+        assert k in MAP_VIEW_DTYPES, "map[%r]: unknown key" % k
+    for k in ba:
+        assert k in MAP_BA_DTYPES or k == "kf_first", "ba[%r]: unknown key" % k
+    dev = _tensor("map['obs_ptr']", map.get("obs_ptr"), "int32", (None,), None).device
+    NMPcap = map["obs_ptr"].shape[0] - 1
+    assert NMPcap >= 0, "map['obs_ptr']: needs NMPcap + 1 entries"
+    OBScap = _tensor("map['obs_kf']", map.get("obs_kf"), "int32", (None,), dev).shape[0]
+    KFcap, NFK = _tensor("map['kf_mp']", map.get("kf_mp"), "int32", (None, None), dev).shape
+    NMP, NKF, NOBS = (NMPcap, KFcap, OBScap) if sizes is None else (int(v) for v in sizes)
+    assert 0 <= NMP <= NMPcap and 0 <= NKF <= KFcap and 0 <= NOBS <= OBScap, \
+        "sizes %s outside the buffers (NMPcap %d, key-frame rows %d, OBScap %d)" % ((NMP, NKF, NOBS), NMPcap, KFcap, OBScap)
+    assert map.get("mp_valid") is not None and map.get("kf_valid") is not None, "mp_valid and kf_valid are written, both are needed"
+    _tensor("map['mp_valid']", map["mp_valid"], "uint8", (NMPcap,), dev)
+    _tensor("map['kf_valid']", map["kf_valid"], "uint8", (KFcap,), dev)
+    _tensor("ba['obs_feat']", ba.get("obs_feat"), "int32", (OBScap,), dev)
+    for d, name, dtypes in ((map, "map", MAP_VIEW_DTYPES), (ba, "ba", MAP_BA_DTYPES)):
+        for k, t in d.items():
+            if t is None or k == "kf_first" or k in ("obs_ptr", "obs_kf", "kf_mp", "mp_valid", "kf_valid", "obs_feat"):
+                continue
+            lead = NMPcap if k in _PER_POINT else KFcap
+            shape = (lead, NFK, 3) if k == "kf_uvr" else (lead, NFK) if k == "kf_oct" else (lead,) + _TRAIL.get(k, ())
+            _tensor("%s[%r]" % (name, k), t, dtypes[k], shape, dev)
+    for k in need_ba:
+        assert ba.get(k) is not None, "ba[%r]: missing" % k
+    return NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev
+
+
+def _edit(map, ba, mp_ref_kf, NMPcap, dev):
+    ed = _lib.gl_map_edit()
+    for k in ("mp_valid", "kf_valid", "kf_mp", "obs_ptr", "obs_kf"):
+        setattr(ed, k, _ptr(map[k]))
+    ed.obs_feat = _ptr(ba["obs_feat"])
+    if mp_ref_kf is not None:
+        ed.mp_ref_kf = _ptr(_tensor("mp_ref_kf", mp_ref_kf, "int32", (NMPcap,), dev))
+    return ed
+
+
+def _count(name, n, dev):
+    if n is None:
+        return None
+    assert n.is_cuda and n.device == dev and str(n.dtype) == "torch.int32" and n.numel() == 1, "n_%s: one int32 on the device" % name
+    return _ptr(n)
+
+
+def map_add(ctx, map, ba, sizes=None, new_mp=None, new_kf=None, attach=None, walk_kf=None, mp_ref_kf=None, n_new_mp=None, n_new_kf=None,
+            n_attach=None, n_walk=None, already_cap=None, want_new_pos=False):
+    """gl_map_add: IN PLACE on the capacity buffers (module docstring).  new_mp: dict(pos (n,3) f64, assoc (n,) i32, ref_kf (n,) i32 -
+    needed with mp_ref_kf) - the rows [NMP, NMP + n); needs map['mp_pos'] and ba['mp_assoc'].  new_kf (n,) i32: rows that become valid.
+    attach: dict(mp, kf, feat) of (n,) i32, the triples in list order.  walk_kf (n,) i32: the rows whose slots are walked as
+    processNewKeyFrame does.  n_x: the length as a 1-element i32 device tensor instead of the tensor's own.  mp_ref_kf (NMPcap,) i32.
+    -> dict(sizes (NMP, NKF, NOBS) after the call - the sizes on entry after a truncation, with `needed` = what the call asked for -
+    n_attached, n_skipped, n_already, status, already_mp (min(n_already, already_cap),) i32, map, ba: cut to sizes[, obs_new_pos (old
+    NOBS,) i32: all -1 after a truncation]).  One 24-byte copy and one synchronise."""
+    import torch
+    need = ("mp_assoc",) if new_mp is not None else ()
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _buffers(map, ba, sizes, need)
+    ed = _edit(map, ba, mp_ref_kf, NMPcap, dev)
+    ls = _lib.gl_map_add_lists()
+    if new_mp is not None:
+        for k in new_mp:
+            assert k in ("pos", "assoc", "ref_kf"), "new_mp[%r]: unknown key" % k
+        assert map.get("mp_pos") is not None, "map['mp_pos']: missing"
+        n = _tensor("new_mp['pos']", new_mp.get("pos"), "float64", (None, 3), dev).shape[0]
+        ls.new_pos, ls.new_mp_cap = _ptr(new_mp["pos"]), n
+        ls.new_assoc = _ptr(_tensor("new_mp['assoc']", new_mp.get("assoc"), "int32", (n,), dev))
+        if mp_ref_kf is not None or new_mp.get("ref_kf") is not None:
+            ls.new_ref_kf = _ptr(_tensor("new_mp['ref_kf']", new_mp.get("ref_kf"), "int32", (n,), dev))
+        ls.n_new_mp = _count("new_mp", n_new_mp, dev)
+    else:
+        assert n_new_mp is None, "n_new_mp without new_mp"
+    if new_kf is not None:
+        ls.new_kf, ls.new_kf_cap = _ptr(_tensor("new_kf", new_kf, "int32", (None,), dev)), new_kf.shape[0]
+        ls.n_new_kf = _count("new_kf", n_new_kf, dev)
+    else:
+        assert n_new_kf is None, "n_new_kf without new_kf"
+    if attach is not None:
+        for k in attach:
+            assert k in ("mp", "kf", "feat"), "attach[%r]: unknown key" % k
+        n = _tensor("attach['mp']", attach.get("mp"), "int32", (None,), dev).shape[0]
+        ls.att_mp, ls.attach_cap = _ptr(attach["mp"]), n
+        ls.att_kf = _ptr(_tensor("attach['kf']", attach.get("kf"), "int32", (n,), dev))
+        ls.att_feat = _ptr(_tensor("attach['feat']", attach.get("feat"), "int32", (n,), dev))
+        ls.n_attach = _count("attach", n_attach, dev)
+    else:
+        assert n_attach is None, "n_attach without attach"
+    if walk_kf is not None:
+        ls.walk_kf, ls.walk_cap = _ptr(_tensor("walk_kf", walk_kf, "int32", (None,), dev)), walk_kf.shape[0]
+        ls.n_walk = _count("walk", n_walk, dev)
+    else:
+        assert n_walk is None, "n_walk without walk_kf"
+    already_cap = ls.walk_cap * NFK if already_cap is None else int(already_cap)
+    result = torch.zeros(6, dtype=torch.int32, device=dev)
+    already = torch.zeros(already_cap, dtype=torch.int32, device=dev)
+    new_pos = torch.zeros(NOBS, dtype=torch.int32, device=dev) if want_new_pos else None
+    o = _lib.gl_map_add_out()
+    o.result, o.already_mp, o.obs_new_pos, o.already_cap = _ptr(result), (_ptr(already) if already_cap else None), _ptr(new_pos), already_cap
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_map_add(ctx.h, NMP, NKF, NFK, NOBS, NMPcap, OBScap, C.byref(ed), _ptr(map.get("mp_pos")), _ptr(ba.get("mp_assoc")),
+                                  C.byref(ls), C.byref(o)))
+    finally:
+        ctx._exit()
+    nmp, nobs, n_att, n_skip, n_already, status = result.tolist()  # the one round trip
+    cut = status & (GROW_OBS_TRUNCATED | GROW_MP_TRUNCATED)
+    now = (NMP, NKF, NOBS) if cut else (nmp, NKF, nobs)
+    m2, b2 = map_views(map, ba, now)
+    r = dict(sizes=now, needed=(nmp, NKF, nobs), n_attached=n_att, n_skipped=n_skip, n_already=n_already, status=status,
+             already_mp=already[:min(n_already, already_cap)], map=m2, ba=b2)
+    if want_new_pos:
+        r["obs_new_pos"] = new_pos
+    return r
+
+
+def map_fuse(ctx, map, ba, kf_row, cand_mp, best_idx, sizes=None, repl_cap=None, want_new_pos=False):
+    """gl_map_fuse: the matches of ONE key-frame row applied in list order, IN PLACE on the capacity buffers (module docstring).
+    cand_mp (n,) i32: the map-point rows given to the search, in its order; best_idx (n,) i32: fuse_search's answer for them (a row of
+    it).  Needs ba['kf_uvr'].  -> dict(sizes after the call - those on entry after a truncation, with `needed` - n_fused, n_attached,
+    n_replaced, status, repl_src / repl_tgt (min(n_replaced, repl_cap),) i32 in step order, map, ba: cut to sizes[, obs_new_pos (old
+    NOBS,) i32: -1 for an entry that is gone]).  After a truncation `needed` holds NOBS + n as its third size: the UPPER BOUND the call
+    checks before it runs (every candidate may attach), not the size the edit would produce.  One 20-byte copy and one synchronise."""
+    import torch
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _buffers(map, ba, sizes, ("kf_uvr",))
+    ed = _edit(map, ba, None, NMPcap, dev)
+    kf_row = int(kf_row)
+    assert 0 <= kf_row < NKF, "kf_row %d outside [0, %d)" % (kf_row, NKF)
+    n = _tensor("cand_mp", cand_mp, "int32", (None,), dev).shape[0]
+    _tensor("best_idx", best_idx, "int32", (n,), dev)
+    repl_cap = n if repl_cap is None else int(repl_cap)
+    result = torch.zeros(5, dtype=torch.int32, device=dev)
+    src = torch.zeros(repl_cap, dtype=torch.int32, device=dev)
+    tgt = torch.zeros(repl_cap, dtype=torch.int32, device=dev)
+    new_pos = torch.zeros(NOBS, dtype=torch.int32, device=dev) if want_new_pos else None
+    o = _lib.gl_map_fuse_out()
+    o.result, o.obs_new_pos, o.repl_cap = _ptr(result), _ptr(new_pos), repl_cap
+    o.repl_src, o.repl_tgt = (_ptr(src), _ptr(tgt)) if repl_cap else (None, None)
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_map_fuse(ctx.h, NMP, NKF, NFK, NOBS, OBScap, C.byref(ed), _ptr(ba["kf_uvr"]), kf_row, n, _ptr(cand_mp), _ptr(best_idx),
+                                   C.byref(o)))
+    finally:
+        ctx._exit()
+    nobs, n_fused, n_att, n_repl, status = result.tolist()  # the one round trip
+    now = (NMP, NKF, NOBS) if status & GROW_OBS_TRUNCATED else (NMP, NKF, nobs)
+    m2, b2 = map_views(map, ba, now)
+    k = min(n_repl, repl_cap)
+    r = dict(sizes=now, needed=(NMP, NKF, nobs), n_fused=n_fused, n_attached=n_att, n_replaced=n_repl, status=status, repl_src=src[:k], repl_tgt=tgt[:k],
+             map=m2, ba=b2)
+    if want_new_pos:
+        r["obs_new_pos"] = new_pos
+    return r
+
+
+def fuse_observations_from_map(ctx, cam, map, ba, kf_tables, kf_row, cand_mp, th=3.0, scale_factor=1.2, sizes=None, want_new_pos=False):
+    """Localization::fuseObservations (localization.cpp:226-321) for ONE key-frame row on the resident map: the candidates' rows gathered
+    from the map, project_map_points -> fuse_search -> map_fuse, nothing flattened or uploaded.  map needs the per-point arrays of the
+    matchers (mp_pos, mp_normal, mp_max_dist, mp_min_dist, mp_desc), ba kf_pose / kf_twc / kf_uvr / kf_oct; kf_tables: dict(desc
+    (key-frame rows, NFK, 32) u8).  cand_mp (n,) i32.  -> the dict of map_fuse + best_idx, best_dist (n,) i32.  A candidate that already
+    observes kf_row is matched like any other and dropped by map_fuse's own test (:237)."""
+    import torch
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct"))
+    for k in ("mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc"):
+        assert map.get(k) is not None, "map[%r]: missing" % k
+    desc = _tensor("kf_tables['desc']", kf_tables.get("desc"), "uint8", (map["kf_mp"].shape[0], NFK, 32), dev)
+    kf_row = int(kf_row)
+    assert 0 <= kf_row < NKF, "kf_row %d outside [0, %d)" % (kf_row, NKF)
+    n = _tensor("cand_mp", cand_mp, "int32", (None,), dev).shape[0]
+    c = cand_mp.long()
+    inside = (c >= 0) & (c < NMP)
+    c = torch.where(inside, c, torch.zeros_like(c))
+    flag = (inside & (map["mp_valid"][c] != 0)).to(torch.uint8)[None].contiguous()
+    g = lambda k: map[k][c][None].contiguous()
+    uvr, level, _, _, inview = project_map_points(ctx, cam, ba["kf_pose"][kf_row][None].contiguous(), ba["kf_twc"][kf_row][None].contiguous(), g("mp_pos"),
+                                                  g("mp_normal"), g("mp_max_dist"), g("mp_min_dist"), flag, scale_factor=scale_factor)
+    feat = ba["kf_uvr"][kf_row]
+    bi, bd = fuse_search(ctx, cam, feat[None, :, :2].contiguous(), feat[None, :, 2].float().contiguous(), ba["kf_oct"][kf_row][None].contiguous(),
+                         desc[kf_row][None].contiguous(), uvr, level, inview, g("mp_desc"), th=th, scale_factor=scale_factor)
+    r = map_fuse(ctx, map, ba, kf_row, cand_mp, bi[0], sizes=(NMP, NKF, NOBS), want_new_pos=want_new_pos)
+    r.update(best_idx=bi[0], best_dist=bd[0])
+    return r

@@ -846,6 +846,114 @@ typedef struct gl_map_remove_out {
 int gl_map_remove(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, const gl_map_edit* ed, const double* kf_uvr_dev, int kf_first,
                   const gl_map_remove_lists* lists, const gl_map_remove_out* out);
 
+/* ---- growing the resident map: new rows, new observations, fuse matches applied in order -------------
+ * The counterparts of gl_map_remove on the same caller-owned arrays (gl_map_edit; mp_pos of gl_map_view, mp_assoc of gl_map_ba_view).
+ * The arrays keep their allocation and the counts grow, so both calls take CAPACITIES: NMPcap = the rows of the per-point arrays
+ * (obs_ptr has NMPcap + 1 entries), OBScap = the entries of obs_kf / obs_feat.  A call first computes the sizes it would produce; if
+ * one exceeds its capacity it writes NOTHING to the map, sets GL_MAP_GROW_MP_TRUNCATED / GL_MAP_GROW_OBS_TRUNCATED in its status and
+ * `result` holds the sizes that are NEEDED (as gl_ba_window_build does): the host grows its buffers and calls again.
+ * The key-frame rows are the caller's: it has written a new key-frame's kf_uvr / kf_oct / kf_desc / kf_pose / kf_mp rows (the one
+ * upload that stays) and passes the new NKF.
+ * DECLARED CSR ORDER: an entry a point gains is appended BEHIND the entries it holds, in the order of the list (gl_map_add) or of the
+ * steps (gl_map_fuse); the reference's observations_ is an unordered_map<pointer> and has no order to follow.
+ *
+ * gl_map_add - insert and attach, one parallel edit.  Four device lists, any of them NULL / empty, lengths as in gl_map_remove_lists
+ * (*n_x when given, clamped to [0, x_cap], else x_cap):
+ *   new points  new_pos n x 3 f64, new_assoc n int32, new_ref_kf n int32 (required when mp_ref_kf is given): rows [NMP, NMP + n) get
+ *               them, mp_valid = 1 and an empty CSR range at the end.  Descriptor, normal and distances are gl_update_map_points'.
+ *   new_kf      key-frame rows whose kf_valid becomes 1; a row outside [0, NKF) changes nothing
+ *   attach      triples (att_mp, att_kf, att_feat) IN LIST ORDER, each `mappt->addObservation(kf, feat); kf->addObservation(mappt,
+ *               feat)` (mappoint.cpp:72-82, keyframe.cpp:190-193) statement for statement: the point side does nothing when the point
+ *               already has an observation by that key-frame - in the CSR or from an earlier triple - and the key-frame side sets
+ *               kf_mp[kf][feat] = mp unconditionally, so the LAST triple that names a slot owns it.  Triples may name the new rows.
+ *               SKIPPED, each counted in n_skipped: a triple whose point row or feature is outside its table, whose point is invalid,
+ *               whose key-frame row is outside the table or invalid (new_kf counts as valid).
+ *   walk_kf     per listed row the loop of processNewKeyFrame (localization.cpp:424-437), after the triples, in list order: its
+ *               kf_mp slots ascending; a non-null valid point WITHOUT an observation by the key-frame gains the entry (kf, i); one
+ *               that has one - in the CSR, from a triple, from a lower slot - is written to already_mp (candidate_mappts_), in slot
+ *               order.  A row outside the table, an invalid key-frame and a row listed before change nothing.
+ * result 6 int32 = {new NMP, new NOBS, n_attached (entries gained), n_skipped, n_already, status}; already_mp already_cap int32 (more:
+ * the first already_cap, GL_MAP_ADD_ALREADY_TRUNCATED, n_already stays true); obs_new_pos old NOBS int32, NULL allowed: the new
+ * position of every old entry (nothing is lost; a host mirror follows it as with gl_map_remove).  After a capacity truncation
+ * n_attached / n_skipped / n_already are still the true counts and already_mp is written; the map is untouched and obs_new_pos holds
+ * -1 in every entry (it is reset before the sizes are known): the host's mirror does not follow it then.
+ * "Already" and "last" are decided by LIST INDEX, never by arrival: atomicMax of the triple's index on a word per slot, atomicMin
+ * of the request's index in a table keyed by (point, key-frame); a point's gained entries are ordered by index.  The cost follows the
+ * map, not the edit, like gl_map_remove: a word per kf_mp slot and per point in the context's scratch (set and reset by the call), a
+ * device-wide scan, the CSR moved through a copy in the scratch.  The map is taken as consistent; a point whose CSR range is not inside
+ * [0, NOBS] has only its gained entries afterwards; nothing is read or written out of bounds.
+ *
+ * gl_map_fuse - what Localization::fuseObservations does with its matches (localization.cpp:299-321) and Map::replaceMapPoint
+ * (map.cpp:112-150), for ONE key-frame row kf, in list order.  cand_mp n_cand int32: the map-point rows the host passed to the
+ * search, in its order; best_idx n_cand int32: gl_fuse_search's output for that list (< 0 or >= NFK: no match).  Per candidate with a
+ * match the call re-tests :237-241 ITSELF on the state the steps before left: skipped when its row is outside the table, when it is
+ * invalid, when it has an observation by kf - so a duplicate later in the list finds its own earlier attach, or that it has been
+ * replaced, as in the reference.  Then with q = kf_mp[kf][best_idx]:
+ *   q < 0       the candidate gains (kf, best_idx), the slot becomes the candidate (:315-316)
+ *   q invalid   (or a row outside the table) nothing changes (:303);  q == candidate: nothing (map.cpp:113)
+ *   q valid     by the WEIGHTED COUNT (gl_cull_keyframes) of the entries each point holds NOW, gained ones included: w(q) > w(cand)
+ *               -> replace(src = cand, tgt = q), else replace(src = q, tgt = cand) - a tie goes to the candidate (:305-313)
+ * and each of the three counts in n_fused (:320).  replace(src, tgt): src becomes invalid and loses all entries; its entries are
+ * walked in ITS CSR ORDER, the ones it gained behind its old ones (the declared order; the reference walks an unordered_map): where
+ * tgt has no observation by that key-frame the slot becomes tgt and tgt gains the entry behind what it holds, otherwise the slot
+ * becomes -1 and the entry is gone (:138).  mp_ref_kf and mp_assoc of either point are not touched.
+ * result 5 int32 = {new NOBS, n_fused, n_attached, n_replaced, status}; repl_src / repl_tgt repl_cap int32 in step order (more: the
+ * first repl_cap, GL_MAP_FUSE_REPL_TRUNCATED; n_replaced stays true and the MAP edit is complete either way); obs_new_pos old NOBS
+ * int32, NULL allowed: -1 for an entry that is gone, the new position of one that stayed or moved to tgt.
+ * NOBS grows only by the attaches, so the capacity is checked BEFORE anything runs: OBScap >= NOBS + n_cand, else result[0] =
+ * NOBS + n_cand with GL_MAP_GROW_OBS_TRUNCATED and nothing else is written.  That figure is an UPPER BOUND, not the size the edit
+ * produces: a list of which few candidates attach, or whose replaces drop entries, is refused all the same below it.
+ * What stays with the host, from repl_src / repl_tgt: num_visible_ / num_found_ (:142-143), ptr_replaced_, mappoints_.erase, and
+ * computeDistinctiveDescriptors of tgt (:144) - gl_update_map_points on the resident arrays before the next key-frame's search.
+ * The steps depend on one another through slots, counts and gained entries, so ONE workgroup walks the list; inside a step it works in
+ * parallel over src's and tgt's entries.  The walk never edits the CSR: its state (a word per point, a chain of gained entries per
+ * point in a log of NOBS + n_cand nodes, a flag per old entry, a stamp per key-frame) lives in the context's scratch, set and reset by
+ * the call; one parallel rebuild (count, device-wide scan, stable move through a copy) writes obs_ptr / obs_kf / obs_feat.  The cost
+ * follows the map plus the steps.
+ * Both: integer stores and integer atomics only - the bytes do not depend on scheduling; asynchronous on the context's stream,
+ * stateless, no host synchronise.  obs_kf / obs_feat behind the new NOBS are not written.  Map fields read / written:
+ *   call        | reads                                                    | writes
+ *   gl_map_add  | mp_valid kf_valid kf_mp obs_ptr obs_kf obs_feat          | the same, mp_pos mp_assoc mp_ref_kf (new rows only)
+ *   gl_map_fuse | mp_valid kf_mp obs_ptr obs_kf obs_feat kf_uvr (u_right)  | mp_valid kf_mp obs_ptr obs_kf obs_feat */
+#define GL_MAP_GROW_OBS_TRUNCATED 1
+#define GL_MAP_GROW_MP_TRUNCATED 2
+#define GL_MAP_FUSE_REPL_TRUNCATED 4
+#define GL_MAP_ADD_ALREADY_TRUNCATED 8
+typedef struct gl_map_add_lists {
+  const double* new_pos;
+  const int32_t* new_assoc;
+  const int32_t* new_ref_kf;
+  const int32_t* n_new_mp;
+  const int32_t* new_kf;
+  const int32_t* n_new_kf;
+  const int32_t* att_mp;
+  const int32_t* att_kf;
+  const int32_t* att_feat;
+  const int32_t* n_attach;
+  const int32_t* walk_kf;
+  const int32_t* n_walk;
+  int32_t new_mp_cap, new_kf_cap, attach_cap, walk_cap;
+} gl_map_add_lists;
+typedef struct gl_map_add_out {
+  int32_t* result;
+  int32_t* already_mp;
+  int32_t* obs_new_pos;
+  int32_t already_cap;
+  int32_t reserved_;
+} gl_map_add_out;
+int gl_map_add(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, int NMPcap, int OBScap, const gl_map_edit* ed, double* mp_pos_dev,
+               int32_t* mp_assoc_dev, const gl_map_add_lists* lists, const gl_map_add_out* out);
+typedef struct gl_map_fuse_out {
+  int32_t* result;
+  int32_t* repl_src;
+  int32_t* repl_tgt;
+  int32_t* obs_new_pos;
+  int32_t repl_cap;
+  int32_t reserved_;
+} gl_map_fuse_out;
+int gl_map_fuse(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, int OBScap, const gl_map_edit* ed, const double* kf_uvr_dev, int kf,
+                int n_cand, const int32_t* cand_mp_dev, const int32_t* best_idx_dev, const gl_map_fuse_out* out);
+
 /* Localization::fuseObservations (localization.cpp:226-318), the matching half, for B key-frames: per candidate map point the most
  * similar feature inside Frame::getFeaturesInArea(u, v, th * scale_factors[level]) (frame.cpp:121-177) with octave level - 1 or
  * level and Feature::error(uvr) * sigma2_inv[octave] within 5.99 (mono) / 7.8 (stereo).  Features as in gl_search_by_projection
@@ -854,7 +962,8 @@ int gl_map_remove(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, const gl_m
  * host's tests of :238-254 (non-null, valid, not observed by the key-frame, project3 and checkScaleAndVisible passed), mp_desc
  * B x NP x 32.  Out: best_idx B x NP int32 (the feature, if its distance is <= TH_LOW = 50, else -1) and best_dist B x NP int32 (256:
  * no candidate).  The map points do not interact in this loop; what the reference does with a match (:296-312: addObservation, or
- * replaceMapPoint by observation count) stays with the host, in list order.  cam supplies width / height (the 64 x 48 grid). */
+ * replaceMapPoint by observation count), in list order, is gl_map_fuse on the resident map - or the host's, on its own containers.
+ * cam supplies width / height (the 64 x 48 grid). */
 int gl_fuse_search(gl_ctx_t* ctx, const gl_camera* cam, float scale_factor, int B, int NF, int NP, const double* feat_uv_dev,
                    const float* feat_ur_dev, const int32_t* feat_oct_dev, const uint8_t* feat_desc_dev, const double* mp_uvr_dev,
                    const int32_t* mp_level_dev, const uint8_t* mp_valid_dev, const uint8_t* mp_desc_dev, float th,

@@ -11,10 +11,13 @@
 //                                                   from the resident map (jointOptimizationFromMap)
 //   Localization::removeKeyFrames                   (localization.cpp:334-399) and the removals of Map::removeKeyFrame /
 //                                                   removeMapPoint / the BA's erase loop on the resident map (cullKeyFrames, removeFromMap)
+//   Localization::processNewKeyFrame / createMapPoints / fuseObservations + Map::replaceMapPoint, what they ADD to the resident map
+//                                                   (localization.cpp:412-444, :299-321, map.cpp:112-150: addToMap, fuseObservationsInMap)
 //   north-star per-frame path: associate + structure-constrained refinement of one frame (trackFrame)
 // Host buffers in, host buffers out: each call stages through device memory owned by the
 // adapter (gl_malloc / gl_memcpy_*), so the host code never sees a HIP type.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -30,7 +33,8 @@ namespace gmmloc_hip {
 // 3: trackFrame is the unanchored refine again, trackFrameAnchored the anchored one (2: trackFrame(..., anchored = true));
 //    MapBaRows / flattenMapBa / jointOptimizationFromMap were added without a new version: no existing call changed meaning
 // 4: cullKeyFrames / removeFromMap edit the resident map on the device; the erase_obs of jointOptimizationFromMap no longer ask for
-//    a re-upload of the CSR (pass them to removeFromMap)
+//    a re-upload of the CSR (pass them to removeFromMap); setResidentMapCapacity / addToMap / fuseObservationsInMap were added without
+//    a new version: no existing call changed meaning
 constexpr int kAdapterVersion = 4;
 
 inline void check(int rc, const char* what) {
@@ -260,6 +264,8 @@ class GMM {
   void setResidentMap(const gl_map_view& view, const gl_map_ba_view& ba) {
     map_ = view;
     map_ba_ = ba;
+    mp_cap_ = view.NMP;  // (no room to grow until setResidentMapCapacity says otherwise)
+    obs_cap_ = view.NOBS;
   }
   WindowResult jointOptimizationFromMap(int32_t kf_row, const int32_t* stop_flag = nullptr) {
     WindowResult r;
@@ -391,6 +397,111 @@ class GMM {
     map_.NOBS = r.nobs;
     return r;
   }
+  // What ADDS to the resident map (gl_map_add / gl_map_fuse, gmmloc_hip.h), in place on the device arrays of setResidentMap.  The
+  // arrays keep their allocation: setResidentMapCapacity says how many rows the per-point arrays (obs_ptr one more) and how many entries
+  // obs_kf / obs_feat hold; the view's NMP / NOBS follow every call.  A call that would exceed a capacity changes nothing and says so
+  // (status GL_MAP_GROW_*_TRUNCATED, nmp / nobs = the sizes NEEDED): the host allocates larger arrays, copies, calls setResidentMap and
+  // calls again.  The new key-frame's own rows (kf_uvr, kf_oct, kf_pose, kf_mp, its descriptors) are the host's upload, made before;
+  // the view's NKF already counts it.  setResidentMap RESETS both capacities to the view's sizes (it cannot know the allocation), so
+  // every setResidentMap - the one after growing the buffers included - is followed by setResidentMapCapacity.  For
+  // fuseObservationsInMap the size NEEDED is the upper bound NOBS + the number of candidates, not the size the edit produces.
+  void setResidentMapCapacity(int32_t NMPcap, int32_t OBScap) {
+    mp_cap_ = NMPcap;
+    obs_cap_ = OBScap;
+  }
+  // addToMap: the new points (rows NMP, NMP + 1, ...: new_pos x 3, new_assoc, new_ref_kf per point), the key-frames that become valid,
+  // the attach triples (att_mp, att_kf, att_feat) in list order - each mappt->addObservation(kf, feat); kf->addObservation(mappt, feat) -
+  // and the key-frames walked as processNewKeyFrame walks the new one.  already_mp = candidate_mappts_.
+  struct AddLists {
+    std::vector<double> new_pos;
+    std::vector<int32_t> new_assoc, new_ref_kf, new_kf, att_mp, att_kf, att_feat, walk_kf;
+  };
+  struct AddResult {
+    int32_t nmp = 0, nobs = 0, n_attached = 0, n_skipped = 0, status = 0;
+    std::vector<int32_t> already_mp;  // all of them (n_already = its size): the call's already_cap is a slot per walked slot, never short
+  };
+  AddResult addToMap(const AddLists& l, int32_t* mp_ref_kf_dev = nullptr) {
+    const size_t nn = l.new_assoc.size(), nk = l.new_kf.size(), na = l.att_mp.size(), nw = l.walk_kf.size(), NFK = (size_t)map_.NFK;
+    if (l.new_pos.size() != nn * 3 || (mp_ref_kf_dev && l.new_ref_kf.size() != nn) || l.att_kf.size() != na || l.att_feat.size() != na)
+      throw std::runtime_error("addToMap: lists of different lengths");
+    const size_t nr = mp_ref_kf_dev ? nn : 0, words = nn + nr + nk + 3 * na + nw + nw * NFK;
+    char* b = pooled(5, 64 + nn * 24 + words * 4).as<char>();
+    int32_t* res = reinterpret_cast<int32_t*>(b);
+    double* d_pos = reinterpret_cast<double*>(b + 64);
+    int32_t* d_assoc = reinterpret_cast<int32_t*>(b + 64 + nn * 24);
+    int32_t *d_ref = d_assoc + nn, *d_kf = d_ref + nr, *d_amp = d_kf + nk, *d_akf = d_amp + na, *d_aft = d_akf + na, *d_walk = d_aft + na,
+            *d_already = d_walk + nw;
+    auto put = [this](void* dst, const void* src, size_t bytes) {
+      if (bytes) check(gl_memcpy_h2d(ctx_, dst, src, bytes), "h2d");
+    };
+    put(d_pos, l.new_pos.data(), nn * 24);
+    put(d_assoc, l.new_assoc.data(), nn * 4);
+    put(d_ref, l.new_ref_kf.data(), nr * 4);
+    put(d_kf, l.new_kf.data(), nk * 4);
+    put(d_amp, l.att_mp.data(), na * 4);
+    put(d_akf, l.att_kf.data(), na * 4);
+    put(d_aft, l.att_feat.data(), na * 4);
+    put(d_walk, l.walk_kf.data(), nw * 4);
+    const gl_map_edit ed = residentEdit(mp_ref_kf_dev);
+    gl_map_add_lists ls{};
+    if (nn) ls.new_pos = d_pos, ls.new_assoc = d_assoc, ls.new_ref_kf = nr ? d_ref : nullptr, ls.new_mp_cap = (int32_t)nn;
+    if (nk) ls.new_kf = d_kf, ls.new_kf_cap = (int32_t)nk;
+    if (na) ls.att_mp = d_amp, ls.att_kf = d_akf, ls.att_feat = d_aft, ls.attach_cap = (int32_t)na;
+    if (nw) ls.walk_kf = d_walk, ls.walk_cap = (int32_t)nw;
+    gl_map_add_out out{};
+    out.result = res;
+    out.already_mp = (nw && NFK) ? d_already : nullptr;
+    out.already_cap = (int32_t)(nw * NFK);
+    check(gl_map_add(ctx_, map_.NMP, map_.NKF, map_.NFK, map_.NOBS, mp_cap_, obs_cap_, &ed, const_cast<double*>(map_.mp_pos), map_ba_.mp_assoc, &ls, &out),
+          "gl_map_add");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t got[6];
+    check(gl_memcpy_d2h(ctx_, got, res, 24), "d2h");
+    AddResult r;
+    r.nmp = got[0], r.nobs = got[1], r.n_attached = got[2], r.n_skipped = got[3], r.status = got[5];
+    const size_t n_already = std::min((size_t)std::max(got[4], 0), nw * NFK);
+    r.already_mp.resize(n_already);
+    if (n_already) check(gl_memcpy_d2h(ctx_, r.already_mp.data(), d_already, n_already * 4), "d2h");
+    if (!(r.status & (GL_MAP_GROW_MP_TRUNCATED | GL_MAP_GROW_OBS_TRUNCATED))) map_.NMP = r.nmp, map_.NOBS = r.nobs;
+    return r;
+  }
+  // fuseObservationsInMap: what Localization::fuseObservations does with its matches (localization.cpp:299-321, Map::replaceMapPoint)
+  // for key-frame kf_row, in list order.  cand_rows: the map-point rows the host gave to the search, in its order; best_idx_dev: the
+  // best_idx row gl_fuse_search wrote for that list, still on the device.  repl_src / repl_tgt: the replacements in step order - the
+  // host's num_visible_ / num_found_, ptr_replaced_ and mappoints_.erase follow from them; the targets' descriptors are
+  // gl_update_map_points' before the next key-frame's search.
+  struct FuseResult {
+    int32_t nobs = 0, n_fused = 0, n_attached = 0, status = 0;
+    std::vector<int32_t> repl_src, repl_tgt;
+  };
+  FuseResult fuseObservationsInMap(int32_t kf_row, const std::vector<int32_t>& cand_rows, const int32_t* best_idx_dev) {
+    const size_t n = cand_rows.size();
+    char* b = pooled(5, 64 + 3 * n * 4).as<char>();
+    int32_t* res = reinterpret_cast<int32_t*>(b);
+    int32_t* d_cand = reinterpret_cast<int32_t*>(b + 64);
+    int32_t *d_src = d_cand + n, *d_tgt = d_src + n;
+    if (n) check(gl_memcpy_h2d(ctx_, d_cand, cand_rows.data(), n * 4), "h2d");
+    const gl_map_edit ed = residentEdit(nullptr);
+    gl_map_fuse_out out{};
+    out.result = res;
+    out.repl_src = n ? d_src : nullptr;
+    out.repl_tgt = n ? d_tgt : nullptr;
+    out.repl_cap = (int32_t)n;
+    check(gl_map_fuse(ctx_, map_.NMP, map_.NKF, map_.NFK, map_.NOBS, obs_cap_, &ed, map_ba_.kf_uvr, kf_row, (int)n, d_cand, best_idx_dev, &out), "gl_map_fuse");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t got[5];
+    check(gl_memcpy_d2h(ctx_, got, res, 20), "d2h");
+    FuseResult r;
+    r.nobs = got[0], r.n_fused = got[1], r.n_attached = got[2], r.status = got[4];
+    r.repl_src.resize((size_t)got[3]);
+    r.repl_tgt.resize((size_t)got[3]);
+    if (got[3]) {
+      check(gl_memcpy_d2h(ctx_, r.repl_src.data(), d_src, (size_t)got[3] * 4), "d2h");
+      check(gl_memcpy_d2h(ctx_, r.repl_tgt.data(), d_tgt, (size_t)got[3] * 4), "d2h");
+    }
+    if (!(r.status & GL_MAP_GROW_OBS_TRUNCATED)) map_.NOBS = r.nobs;
+    return r;
+  }
   const gl_map_view& residentMap() const { return map_; }
 
   gl_ctx_t* ctx() { return ctx_; }
@@ -458,8 +569,20 @@ class GMM {
     w.status = reinterpret_cast<int32_t*>(b + 16);
     return b;
   }
+  gl_map_edit residentEdit(int32_t* mp_ref_kf_dev) const {
+    gl_map_edit ed{};
+    ed.mp_valid = const_cast<uint8_t*>(map_.mp_valid);
+    ed.kf_valid = const_cast<uint8_t*>(map_.kf_valid);
+    ed.kf_mp = const_cast<int32_t*>(map_.kf_mp);
+    ed.obs_ptr = const_cast<int32_t*>(map_.obs_ptr);
+    ed.obs_kf = const_cast<int32_t*>(map_.obs_kf);
+    ed.obs_feat = const_cast<int32_t*>(map_ba_.obs_feat);
+    ed.mp_ref_kf = mp_ref_kf_dev;
+    return ed;
+  }
   gl_map_view map_{};
   gl_map_ba_view map_ba_{};
+  int32_t mp_cap_ = 0, obs_cap_ = 0;  // the rows of the per-point arrays, the entries of obs_kf / obs_feat
   size_t caps_[4] = {24, 24, 2048, 16384};  // Pcap, Fcap, Lcap, Ocap: grown on demand
   size_t win_off_[3] = {0, 0, 0};           // dropped, erase, erase_obs (consecutive)
   std::vector<uint8_t> zeros_;

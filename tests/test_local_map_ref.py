@@ -7,15 +7,10 @@ import pytest
 from gmmloc_amd import api, synth
 from tests import local_map_ref as R
 from tests import local_map_scenes as S
+from tests import map_cases as MC
 
 
-def tiny_map(kf_rows, NMP, mp_valid=None, kf_valid=None):
-    """kf_rows: per key-frame its mappoints_ (-1 = null); the observations follow from it"""
-    kf_mp = np.array(kf_rows, np.int32)
-    obs = [[k for k in range(len(kf_mp)) if p in kf_mp[k]] for p in range(NMP)]
-    ptr = np.concatenate([[0], np.cumsum([len(o) for o in obs])]).astype(np.int32)
-    return dict(kf_mp=kf_mp, obs_ptr=ptr, obs_kf=np.array([k for o in obs for k in o], np.int32),
-                mp_valid=None if mp_valid is None else np.array(mp_valid, np.uint8), kf_valid=None if kf_valid is None else np.array(kf_valid, np.uint8))
+tiny_map, ROWS = MC.rows_map, MC.ROWS  # (the builder and the four key-frames of the hand-built cases: tests/map_cases.py)
 
 
 def run(m, feat_mp, KFcap=8, NPcap=16, prev_kf=(6, 7), prev_mp=(9,), prev_ref=5):
@@ -33,76 +28,89 @@ def run(m, feat_mp, KFcap=8, NPcap=16, prev_kf=(6, 7), prev_mp=(9,), prev_ref=5)
     return fa[0], {k: v[0] for k, v in a.items()}
 
 
-#            kf 0          kf 1          kf 2           kf 3
-ROWS = [[0, 1, -1, 2], [1, 2, 3, -1], [4, -1, 1, -1], [5, 6, -1, -1]]
+def case(name):
+    """the map and the frame of a case of tests/map_cases.py::LOCAL (which tests/test_gpu_map_cases.py runs on the device), through run()"""
+    c = MC.LOCAL[name]
+    a = c.args
+    return run(c.m, a["feat_mp"], a["KFcap"], a["NPcap"], a["prev_kf"], a["prev_mp"], a["prev_ref"])
 
 
 def test_point_held_by_two_features_counts_twice():
-    m = tiny_map(ROWS, 7)
-    fm, o = run(m, [0, 0, -1])  # point 0 (seen by kf 0 alone) held twice
+    assert MC.LOCAL["held_twice"].args["feat_mp"] == [0, 0, -1]
+    fm, o = case("held_twice")  # point 0 (seen by kf 0 alone) held twice
     assert o["kf_count"].tolist() == [2, 0, 0, 0] and o["ref_kf"] == 0 and o["status"] == 0
     assert o["local_kf"][:o["n_local_kf"]].tolist() == [0] and o["local_mp"][:o["n_local_mp"]].tolist() == [0, 1, 2]
     assert o["local_kf"][1:].tolist() == [7] + [-7] * 6 and o["local_mp"][3:].tolist() == [-7] * 13  # (what lay behind the lists stays)
 
 
 def test_invalid_held_point_is_cleared_and_counts_nothing():
-    m = tiny_map(ROWS, 7, mp_valid=[1, 0, 1, 1, 1, 1, 1])
-    fm, o = run(m, [1, 4, -1, 1])  # point 1 is invalid: both features lose it; point 4 is seen by kf 2
+    c = MC.LOCAL["invalid_held_point"]
+    assert c.m["mp_valid"].tolist() == [1, 0, 1, 1, 1, 1, 1] and c.args["feat_mp"] == [1, 4, -1, 1]
+    fm, o = case("invalid_held_point")  # point 1 is invalid: both features lose it; point 4 is seen by kf 2
     assert fm.tolist() == [-1, 4, -1, -1]
     assert o["kf_count"].tolist() == [0, 0, 1, 0] and o["ref_kf"] == 2
     assert o["local_mp"][:o["n_local_mp"]].tolist() == [4]  # kf 2 holds 4 and the invalid 1
 
 
 def test_invalid_key_frame_is_counted_but_neither_local_nor_reference():
-    m = tiny_map(ROWS, 7, kf_valid=[1, 0, 1, 1])
-    fm, o = run(m, [1, 2, 3])  # kf 1 sees all three (count 3), kf 0 sees 1 and 2, kf 2 sees 1
+    c = MC.LOCAL["invalid_key_frame"]
+    assert c.m["kf_valid"].tolist() == [1, 0, 1, 1] and c.args["feat_mp"] == [1, 2, 3]
+    fm, o = case("invalid_key_frame")  # kf 1 sees all three (count 3), kf 0 sees 1 and 2, kf 2 sees 1
     assert o["kf_count"].tolist() == [2, 3, 1, 0]
     assert o["ref_kf"] == 0 and o["local_kf"][:o["n_local_kf"]].tolist() == [0, 2]
     assert o["local_mp"][:o["n_local_mp"]].tolist() == [0, 1, 2, 4]  # point 3 is held by the invalid key-frame alone
 
 
 def test_all_counted_key_frames_invalid_empties_the_lists_and_keeps_the_reference():
-    m = tiny_map(ROWS, 7, kf_valid=[1, 1, 1, 0])
-    fm, o = run(m, [5, 6])
+    c = MC.LOCAL["all_counted_invalid"]
+    assert c.m["kf_valid"].tolist() == [1, 1, 1, 0] and c.args["feat_mp"] == [5, 6]
+    fm, o = case("all_counted_invalid")
     assert o["kf_count"].tolist() == [0, 0, 0, 2] and o["status"] == 0
     assert o["n_local_kf"] == 0 and o["n_local_mp"] == 0 and o["ref_kf"] == 5
     assert o["local_kf"].tolist() == [6, 7] + [-7] * 6 and o["local_mp"].tolist() == [9] + [-7] * 15  # (nothing written)
 
 
 def test_empty_counter_keeps_everything():
-    m = tiny_map(ROWS + [[-1, -1, -1, -1]], 9)  # points 7, 8: no observation (temporal points)
-    fm, o = run(m, [-1, 7, -1, 8])
+    c = MC.LOCAL["empty_counter"]  # points 7, 8: no observation (temporal points)
+    assert c.m["kf_mp"].tolist() == ROWS + [[-1, -1, -1, -1]] and len(c.m["obs_ptr"]) == 10 and c.args["feat_mp"] == [-1, 7, -1, 8]
+    fm, o = case("empty_counter")
     assert fm.tolist() == [-1, 7, -1, 8] and o["status"] == R.KEPT
     assert o["kf_count"].tolist() == [0] * 5
     assert o["n_local_kf"] == 2 and o["n_local_mp"] == 1 and o["ref_kf"] == 5
     assert o["local_kf"].tolist() == [6, 7] + [-7] * 6 and o["local_mp"].tolist() == [9] + [-7] * 15
-    fm, o = run(m, [-1, -1])
+    assert MC.LOCAL["holds_nothing"].args["feat_mp"] == [-1, -1]
+    fm, o = case("holds_nothing")
     assert o["status"] == R.KEPT and o["ref_kf"] == 5
 
 
 def test_tie_goes_to_the_lowest_row():
-    m = tiny_map(ROWS, 7)
-    fm, o = run(m, [1])  # point 1: kf 0, 1, 2 with one count each
+    assert MC.LOCAL["tie_lowest_row"].args["feat_mp"] == [1]
+    fm, o = case("tie_lowest_row")  # point 1: kf 0, 1, 2 with one count each
     assert o["kf_count"].tolist() == [1, 1, 1, 0] and o["ref_kf"] == 0
-    m = tiny_map(ROWS, 7, kf_valid=[0, 1, 1, 1])
-    fm, o = run(m, [1, 4, 3])  # kf 1: points 1, 3; kf 2: points 1, 4; kf 0 (invalid): point 1
+    c = MC.LOCAL["tie_lowest_valid_row"]
+    assert c.m["kf_valid"].tolist() == [0, 1, 1, 1] and c.args["feat_mp"] == [1, 4, 3]
+    fm, o = case("tie_lowest_valid_row")  # kf 1: points 1, 3; kf 2: points 1, 4; kf 0 (invalid): point 1
     assert o["kf_count"].tolist() == [1, 2, 2, 0] and o["ref_kf"] == 1
 
 
 def test_null_and_invalid_points_of_a_key_frame_are_left_out_and_a_shared_point_is_listed_once():
-    m = tiny_map(ROWS, 7, mp_valid=[1, 1, 0, 1, 1, 1, 1])
-    fm, o = run(m, [1])  # local: kf 0, 1, 2 - point 1 is in all three, point 2 (invalid) in two, nulls in each
+    c = MC.LOCAL["shared_point_once"]
+    assert c.m["mp_valid"].tolist() == [1, 1, 0, 1, 1, 1, 1] and c.args["feat_mp"] == [1]
+    fm, o = case("shared_point_once")  # local: kf 0, 1, 2 - point 1 is in all three, point 2 (invalid) in two, nulls in each
     assert o["local_kf"][:o["n_local_kf"]].tolist() == [0, 1, 2]
     assert o["local_mp"][:o["n_local_mp"]].tolist() == [0, 1, 3, 4]
 
 
 def test_truncation_keeps_the_lowest_rows_and_reports_the_true_counts():
-    m = tiny_map(ROWS, 7)
-    fm, o = run(m, [1], KFcap=2, NPcap=3, prev_kf=(6, 7), prev_mp=(9,))
+    c = MC.LOCAL["truncated_both"]
+    assert (c.args["feat_mp"], c.args["KFcap"], c.args["NPcap"]) == ([1], 2, 3)
+    fm, o = case("truncated_both")
     assert o["n_local_kf"] == 3 and o["n_local_mp"] == 5
     assert o["local_kf"].tolist() == [0, 1] and o["local_mp"].tolist() == [0, 1, 2]
     assert o["status"] == R.MP_TRUNCATED | R.KF_TRUNCATED
-    fm, o = run(m, [1], KFcap=3, NPcap=4)
+    c = MC.LOCAL["truncated_points"]
+    assert (c.args["feat_mp"], c.args["KFcap"], c.args["NPcap"]) == ([1], 3, 4)
+    fm, o = case("truncated_points")
     assert o["status"] == R.MP_TRUNCATED and o["local_kf"].tolist() == [0, 1, 2]
 
 

@@ -1,10 +1,11 @@
 """The three facts gl_cull_keyframes / gl_map_remove rest on (gmmloc_hip.h), held by the sequential object model of
-tests/map_edit_ref.py alone, hand-built cases with their expected arrays written out, and the conditions the scenes of
+tests/map_edit_ref.py alone, hand-built cases (the maps and declared outputs of tests/map_cases.py) with their expected arrays written out, and the conditions the scenes of
 tests/map_edit_scenes.py must meet so that tests/test_gpu_map_edit.py cannot pass vacuously.  No GPU."""
 import numpy as np
 import pytest
 
 from tests import ba_window_scenes as S
+from tests import map_cases as MC
 from tests import map_edit_ref as E
 from tests import map_edit_scenes as ES
 
@@ -171,32 +172,15 @@ def test_scene_conditions_unclamped(name):
     assert part.any()
 
 
-# ---- hand-built cases
-
-def tiny_map(NKF, NFK, obs, stereo=True, oct_=None, first=0):
-    """obs: per point a list of (key-frame, slot[, stereo]) in CSR order -> (m, ba)"""
-    NMP = len(obs)
-    kf_mp = -np.ones((NKF, NFK), np.int32)
-    uvr = np.zeros((NKF, NFK, 3))
-    uvr[:, :, 2] = 10.0 if stereo else -1.0
-    okf, of, ptr = [], [], [0]
-    for p, lst in enumerate(obs):
-        for e in lst:
-            kf_mp[e[0], e[1]] = p
-            okf.append(e[0])
-            of.append(e[1])
-            if len(e) > 2:
-                uvr[e[0], e[1], 2] = 10.0 if e[2] else -1.0
-        ptr.append(len(okf))
-    m = dict(mp_valid=np.ones(NMP, np.uint8), kf_valid=np.ones(NKF, np.uint8), kf_mp=kf_mp, obs_ptr=np.array(ptr, np.int32), obs_kf=np.array(okf, np.int32))
-    ba = dict(kf_uvr=uvr, kf_oct=np.zeros((NKF, NFK), np.int32) if oct_ is None else np.array(oct_, np.int32), obs_feat=np.array(of, np.int32), kf_first=first)
-    return m, ba
-
+# ---- hand-built cases: the maps, the lists and the declared outputs are in tests/map_cases.py (REMOVE, CULL), which
+# tests/test_gpu_map_cases.py runs on the device as well
 
 def test_a_stereo_point_with_w4_dies_and_one_with_w5_survives():
     # point 0: two stereo observers (w = 4); point 1: two stereo + one mono (w = 5); the observation by key-frame 1 is erased from both
-    m, ba = tiny_map(4, 2, [[(1, 0), (2, 0)], [(1, 1), (2, 1), (3, 0, False)]])
-    rows, _ = E.map_remove(m, ba, erase_obs=[0, 2], mp_ref_kf=np.array([1, 1], np.int32))
+    c = MC.REMOVE["w4_dies_w5_survives"]
+    m, ba = c.m, c.ba
+    assert c.args["erase"].tolist() == [0, 2] and c.args["mp_ref_kf"].tolist() == [1, 1]
+    rows, _ = E.map_remove(m, ba, erase_obs=c.args["erase"], mp_ref_kf=c.args["mp_ref_kf"])
     assert rows["mp_valid"].tolist() == [0, 1] and rows["dead_mp"].tolist() == [0]
     assert rows["obs_ptr"].tolist() == [0, 0, 2] and rows["obs_kf"].tolist() == [2, 3] and rows["obs_feat"].tolist() == [1, 0]
     assert rows["obs_new_pos"].tolist() == [-1, -1, -1, 0, 1]
@@ -206,12 +190,15 @@ def test_a_stereo_point_with_w4_dies_and_one_with_w5_survives():
     same_rows(rows, cf, "w4 / w5")
 
 
-@pytest.mark.parametrize("order,expect", [([1, 2, 3], [[-1], [0], [0], [-1]]), ([3, 2, 1], [[-1], [-1], [0], [0]])])
-def test_three_observers_in_both_orders(order, expect):
+@pytest.mark.parametrize("name,order,expect", [("three_observers_123", [1, 2, 3], [[-1], [0], [0], [-1]]), ("three_observers_321", [3, 2, 1], [[-1], [-1], [0], [0]])],
+                         ids=["order0-expect0", "order1-expect1"])
+def test_three_observers_in_both_orders(name, order, expect):
     """a point with the three stereo observers 1, 2, 3 (w = 6), all three removed.  The first removal leaves w = 4, the second w = 2:
     the point dies at step 1.  The key-frame removed first keeps its slot (nothing nulls a removed key-frame's own row), the second
     keeps it too (its own removal kills the point: it no longer observes it), the third still observes the dying point: CLEARED."""
-    m, ba = tiny_map(4, 1, [[(1, 0), (2, 0), (3, 0)]])
+    c = MC.REMOVE[name]
+    m, ba = c.m, c.ba
+    assert c.args["rm_kf"].tolist() == order and c.out["kf_mp"].tolist() == expect
     rows, _ = E.map_remove(m, ba, rm_kf=order)
     assert rows["mp_valid"].tolist() == [0] and rows["kf_valid"].tolist() == [1, 0, 0, 0] and rows["obs_ptr"].tolist() == [0, 0]
     assert rows["kf_mp"].tolist() == expect
@@ -224,8 +211,9 @@ def test_the_rank_decides_the_removed_rows():
     [1, 2, 3]: point 0 goes 6 -> 4 -> 2 and dies at step 1; key-frame 3 (rank 2) still observes it: its slot is cleared.
     [3, 2, 1]: 6 -> 5 -> 3 -> 1, dies at step 2: no removed row is touched.  Point 1 survives with w = 4 either way and key-frame 3
     keeps its slot; the remaining observer 4 of point 0 is cleared either way."""
-    obs = [[(1, 0), (2, 0), (3, 0, False), (4, 0, False)], [(3, 1), (4, 1), (0, 0)]]
-    m, ba = tiny_map(5, 2, obs)
+    ca, cb = MC.REMOVE["rank_123"], MC.REMOVE["rank_321"]
+    m, ba = ca.m, ca.ba
+    assert all(np.array_equal(ca.m[k], cb.m[k]) for k in ca.m) and ca.args["rm_kf"].tolist() == [1, 2, 3] and cb.args["rm_kf"].tolist() == [3, 2, 1]
     a, _ = E.map_remove(m, ba, rm_kf=[1, 2, 3])
     b, _ = E.map_remove(m, ba, rm_kf=[3, 2, 1])
     assert a["kf_mp"].tolist() == [[1, -1], [0, -1], [0, -1], [-1, 1], [-1, 1]]
@@ -238,9 +226,9 @@ def test_the_rank_decides_the_removed_rows():
 
 
 def test_kf_first_is_never_culled_and_never_removed():
-    obs = [[(0, i), (1, i), (2, i), (3, i)] for i in range(4)]
-    m, ba = tiny_map(4, 4, obs, first=0)
-    depth = np.ones((4, 4), np.float32)
+    c = MC.CULL["kf_first"]
+    m, ba, depth = c.m, c.ba, c.args["kf_depth"]
+    assert ba["kf_first"] == 0 and c.args["cand"] == [0, 1] and c.args["th_depth"] == 6.0
     for judge in (lambda: E.Model(m, ba).remove_key_frames([0, 1], depth, 6.0), lambda: E.cull_by_state(m, ba, [0, 1], depth, 6.0)):
         r = judge()
         assert r["status"].tolist() == [E.FIRST, E.JUDGED] and r["cull"].tolist() == [0, 1] and r["num_mps"].tolist() == [0, 4]
@@ -248,34 +236,30 @@ def test_kf_first_is_never_culled_and_never_removed():
     assert status == E.FIRST_REFUSED and rows["kf_valid"].tolist() == [1, 1, 1, 1] and np.array_equal(rows["obs_kf"], m["obs_kf"])
 
 
-@pytest.mark.parametrize("redundant,cull", [(9, 0), (10, 1)])
-def test_the_ninety_percent_boundary(redundant, cull):
+@pytest.mark.parametrize("name,redundant,cull", [("ninety_10_at", 9, 0), ("ninety_10_over", 10, 1)], ids=["9-0", "10-1"])
+def test_the_ninety_percent_boundary(name, redundant, cull):
     """ten counted points on key-frame 1; `redundant` of them have three other observers, the rest two: 9 of 10 is not culled
     (9 > 0.9 * 10 is false), 10 of 10 is"""
-    obs = [[(1, i), (2, i), (3, i)] + ([(4, i)] if i < redundant else []) for i in range(10)]
-    m, ba = tiny_map(5, 10, obs)
-    depth = np.ones((5, 10), np.float32)
+    c = MC.CULL[name]
+    m, ba, depth = c.m, c.ba, c.args["kf_depth"]
+    assert (np.diff(m["obs_ptr"]) == 4).sum() == redundant and len(m["mp_valid"]) == 10
     for r in (E.Model(m, ba).remove_key_frames([1], depth, 6.0), E.cull_by_state(m, ba, [1], depth, 6.0)):
         assert r["num_mps"].tolist() == [10] and r["num_redundant"].tolist() == [redundant] and r["cull"].tolist() == [cull]
 
 
 def test_depth_at_the_threshold_counts_and_above_does_not():
-    obs = [[(1, i), (2, i), (3, i), (4, i)] for i in range(4)]
-    m, ba = tiny_map(5, 4, obs)
-    depth = np.ones((5, 4), np.float32)
-    depth[1] = [6.0, np.nextafter(np.float32(6.0), np.float32(7.0)), -1.0, 0.0]
+    c = MC.CULL["depth_threshold"]
+    m, ba, depth = c.m, c.ba, c.args["kf_depth"]
+    assert depth[1].tolist() == [6.0, float(np.nextafter(np.float32(6.0), np.float32(7.0))), -1.0, 0.0]
     for r in (E.Model(m, ba).remove_key_frames([1], depth, 6.0), E.cull_by_state(m, ba, [1], depth, 6.0)):
         assert r["num_mps"].tolist() == [2] and r["num_redundant"].tolist() == [2]
 
 
 def test_octave_scale_plus_one_counts_and_plus_two_does_not():
     """key-frame 1 sees both points at octave 2; point 0's other observers sit at octave 3 (counted), point 1's at 4 (not)"""
-    obs = [[(1, 0), (2, 0), (3, 0), (4, 0)], [(1, 1), (2, 1), (3, 1), (4, 1)]]
-    oct_ = np.zeros((5, 2), np.int32)
-    oct_[1] = 2
-    oct_[2:, 0], oct_[2:, 1] = 3, 4
-    m, ba = tiny_map(5, 2, obs, oct_=oct_)
-    depth = np.ones((5, 2), np.float32)
+    c = MC.CULL["octave_plus_one"]
+    m, ba, depth = c.m, c.ba, c.args["kf_depth"]
+    assert ba["kf_oct"].tolist() == [[0, 0], [2, 2], [3, 4], [3, 4], [3, 4]]
     for r in (E.Model(m, ba).remove_key_frames([1], depth, 6.0), E.cull_by_state(m, ba, [1], depth, 6.0)):
         assert r["num_mps"].tolist() == [2] and r["num_redundant"].tolist() == [1] and r["cull"].tolist() == [0]
 

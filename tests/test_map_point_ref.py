@@ -4,38 +4,11 @@ bits set), so that two of them are |b1 - b2| apart and every median can be worke
 import numpy as np
 
 from gmmloc_amd import synth
+from tests import map_cases as MC
 from tests import map_point_ref as M
 
-NKF, NFK = 8, 4
-
-
-def prefix(b):
-    bits = np.zeros(256, np.uint8)
-    bits[:b] = 1
-    return np.packbits(bits, bitorder="little")
-
-
-def table():
-    """key-frames 0 .. 7; kf k sits at (k + 1, 0, 0) except kf 1 at (0, -3, 0), kf 2 at (0, 0, -4) and kf 7 at the origin"""
-    twc = np.array([[k + 1.0, 0.0, 0.0] for k in range(NKF)])
-    twc[1], twc[2], twc[7] = [0.0, -3.0, 0.0], [0.0, 0.0, -4.0], [0.0, 0.0, 0.0]
-    oct_ = np.tile(np.arange(NFK, dtype=np.int32), (NKF, 1))  # feature f has octave f
-    return dict(twc=twc, valid=np.ones(NKF, np.uint8), oct=oct_, desc=np.zeros((NKF, NFK, 32), np.uint8))
-
-
-def points(rows, ref=None, pos=None, valid=None):
-    """rows: per point the list of (kf, feat)"""
-    ptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
-    flat = [o for r in rows for o in r]
-    return dict(pos=np.zeros((len(rows), 3)) if pos is None else np.asarray(pos, np.float64),
-                valid=np.ones(len(rows), np.uint8) if valid is None else np.asarray(valid, np.uint8),
-                ref_kf=np.array([r[0][0] if r else 0 for r in rows] if ref is None else ref, np.int32), obs_ptr=ptr,
-                obs_kf=np.array([k for k, _ in flat], np.int32), obs_feat=np.array([f for _, f in flat], np.int32))
-
-
-def sentinel(NP):
-    return dict(desc=np.full((NP, 32), 0xA5, np.uint8), normal=np.full((NP, 3), -7.0), max_dist=np.full(NP, -1.0, np.float32),
-                min_dist=np.full(NP, -2.0, np.float32))
+NKF, NFK = MC.PT_NKF, MC.PT_NFK
+prefix, table, points, sentinel, with_descs = MC.prefix, MC.table, MC.points, MC.sentinel, MC.with_descs  # (the builders: tests/map_cases.py)
 
 
 def run(kf, mp, what=3):
@@ -50,27 +23,27 @@ def run(kf, mp, what=3):
     return a
 
 
-def with_descs(kf, kfs_bits):
-    for k, f, b in kfs_bits:
-        kf["desc"][k, f] = prefix(b)
-    return kf
+def case(name, what=3):
+    """the key-frame table and the points of a case of tests/map_cases.py::POINTS (which tests/test_gpu_map_cases.py runs on the device)"""
+    c = MC.POINTS[name]
+    return run(c.m, c.ba, what)
 
 
 def test_n1_n2_first_valid_observation():
-    kf = with_descs(table(), [(0, 0, 5), (1, 1, 50), (2, 2, 9)])
-    o = run(kf, points([[(0, 0)], [(1, 1), (2, 2)], [(2, 2), (1, 1)]]))
+    o = case("n1_n2")
     assert (o["desc"][0] == prefix(5)).all()
     assert (o["desc"][1] == prefix(50)).all()  # medians 0 and 41: element (2-1)/2 = 0 of each sorted row -> both 0, the first wins
     assert (o["desc"][2] == prefix(9)).all()
 
 
 def test_n3_and_n4_hand_medians():
-    kf = with_descs(table(), [(0, 0, 0), (1, 0, 10), (2, 0, 6), (3, 0, 0), (4, 0, 20), (5, 0, 8), (6, 0, 9)])
     # N = 3, bits 0 / 10 / 6: rows {0,10,6} {10,0,4} {6,4,0}, element 1 of the sorted rows 6 / 4 / 4 -> row 1 (the first 4)
     # N = 4, bits 0 / 20 / 8 / 9: rows sorted {0,8,9,20} {0,11,12,20} {0,1,8,12} {0,1,9,11}, element 1: 8 / 11 / 1 / 1 -> row 2
-    o = run(kf, points([[(0, 0), (1, 0), (2, 0)], [(3, 0), (4, 0), (5, 0), (6, 0)]]))
+    o = case("n3_n4")
     assert (o["desc"][0] == prefix(10)).all()
     assert (o["desc"][1] == prefix(8)).all()
+    kf = MC.POINTS["n3_n4"].m
+    assert all((kf["desc"][k, 0] == prefix(b)).all() for k, b in enumerate((0, 10, 6, 0, 20, 8, 9)))
     assert M.distinctive_index(np.array([prefix(b) for b in (0, 10, 6)])) == 1
     assert M.distinctive_index(np.array([prefix(b) for b in (0, 20, 8, 9)])) == 2
 
@@ -78,6 +51,7 @@ def test_n3_and_n4_hand_medians():
 def test_median_tie_first_row_wins():
     # bits 0 / 10 / 4: element 1 of the sorted rows {0,4,10} {0,6,10} {0,4,6} = 4 / 6 / 4: rows 0 and 2 tie, row 0 wins
     assert M.distinctive_index(np.array([prefix(b) for b in (0, 10, 4)])) == 0
+    assert (case("median_tie")["desc"][0] == prefix(0)).all() and (MC.POINTS["median_tie"].m["desc"][2, 0] == prefix(4)).all()
     # five descriptors, the first one bit away from the other four: its median is 1, rows 1 .. 4 have 0 -> row 1
     d = np.array([prefix(3)] * 5)
     d[0, 31] = 1
@@ -85,14 +59,13 @@ def test_median_tie_first_row_wins():
 
 
 def test_invalid_keyframes_skipped_in_descriptor_counted_in_normal():
-    kf = with_descs(table(), [(0, 0, 7), (1, 0, 0), (2, 0, 10), (3, 0, 6)])
-    kf["valid"][0] = 0
-    mp = points([[(0, 0), (1, 0), (2, 0), (3, 0)]], ref=[1], pos=[[0.0, 0.0, 0.0]])
-    o = run(kf, mp)
+    c = MC.POINTS["invalid_kf_skipped"]
+    assert c.m["valid"].tolist() == [0] + [1] * 7 and c.ba["ref_kf"].tolist() == [1] and c.ba["obs_kf"].tolist() == [0, 1, 2, 3]
+    o = case("invalid_kf_skipped")
     assert (o["desc"][0] == prefix(10)).all()  # the N = 3 case above on kf 1 .. 3
     # with kf 0: bits 7 / 0 / 10 / 6, element 1 of the sorted rows {0,1,3,7} {0,6,7,10} {0,3,4,10} {0,1,4,6} = 1 / 6 / 3 / 1 -> row 0
-    kf["valid"][0] = 1
-    assert (run(kf, mp)["desc"][0] == prefix(7)).all()
+    assert MC.POINTS["invalid_kf_valid"].m["valid"].all()
+    assert (case("invalid_kf_valid")["desc"][0] == prefix(7)).all()
     # normal: kf 0 (1,0,0) -> (-1,0,0); kf 1 (0,-3,0) -> (0,1,0); kf 2 (0,0,-4) -> (0,0,1); kf 3 (4,0,0) -> (-1,0,0); over n = 4
     assert o["normal"][0].tolist() == [-0.5, 0.25, 0.25]
     assert o["max_dist"][0] == np.float32(3.0)  # |pos - Ow_ref| = 3, octave of feature 0 = 0
@@ -100,41 +73,36 @@ def test_invalid_keyframes_skipped_in_descriptor_counted_in_normal():
 
 
 def test_ref_keyframe_not_observed_uses_feature_zero():
-    kf = table()
-    kf["oct"][5] = [6, 2, 2, 2]
-    mp = points([[(1, 3), (2, 1)]], ref=[5], pos=[[0.0, 0.0, 0.0]])
-    o = run(kf, mp, what=2)
+    c = MC.POINTS["ref_not_observed"]
+    assert c.m["oct"][5].tolist() == [6, 2, 2, 2] and c.ba["ref_kf"].tolist() == [5] and c.args["what"] == 2
+    o = case("ref_not_observed", what=2)
     sf = M.scale_factors()
     d = np.float32(6.0)  # kf 5 at (6, 0, 0)
     assert o["max_dist"][0] == np.float32(d * sf[6])
     assert o["min_dist"][0] == np.float32(np.float32(d * sf[6]) / sf[7])
     assert (o["desc"] == 0xA5).all()  # what = 2: the descriptor is not written
     # observed: the ref key-frame's own observation decides (feature 3 -> octave 3)
-    o = run(kf, points([[(1, 3), (2, 1)]], ref=[1], pos=[[0.0, 0.0, 0.0]]), what=2)
+    assert MC.POINTS["ref_observed"].ba["ref_kf"].tolist() == [1]
+    o = case("ref_observed", what=2)
     assert o["max_dist"][0] == np.float32(np.float32(3.0) * sf[3])
 
 
 def test_point_at_camera_centre_adds_zero():
-    kf = table()
-    mp = points([[(7, 0), (1, 0)]], ref=[1], pos=[[0.0, 0.0, 0.0]])  # kf 7 sits on the point
-    o = run(kf, mp, what=2)
+    o = case("at_camera_centre", what=2)  # kf 7 sits on the point
     assert o["normal"][0].tolist() == [0.0, 0.5, 0.0]
-    mp = points([[(7, 0)]], ref=[7], pos=[[0.0, 0.0, 0.0]])
-    o = run(kf, mp, what=2)
+    o = case("only_at_camera_centre", what=2)
     assert o["normal"][0].tolist() == [0.0, 0.0, 0.0] and o["max_dist"][0] == 0.0 and o["min_dist"][0] == 0.0
 
 
 def test_octave_7():
-    kf = table()
-    kf["oct"][2, 1] = 7
-    mp = points([[(2, 1)]], ref=[2], pos=[[0.0, 0.0, 1.0]])  # 5 from kf 2 at (0, 0, -4)
-    o = run(kf, mp, what=3)
+    assert MC.POINTS["octave_7"].m["oct"][2, 1] == 7
+    o = case("octave_7", what=3)  # 5 from kf 2 at (0, 0, -4)
     sf = M.scale_factors()
     assert o["max_dist"][0] == np.float32(np.float32(5.0) * sf[7])
     assert o["min_dist"][0] == np.float32(o["max_dist"][0] / sf[7])
     assert o["normal"][0].tolist() == [0.0, 0.0, 1.0]
-    kf["oct"][2, 1] = 8  # outside 0 .. 7: normal and depth untouched, the descriptor still written
-    o = run(kf, mp, what=3)
+    assert MC.POINTS["octave_8"].m["oct"][2, 1] == 8  # outside 0 .. 7: normal and depth untouched, the descriptor still written
+    o = case("octave_8", what=3)
     assert (o["normal"] == -7.0).all() and o["max_dist"][0] == -1.0 and (o["desc"][0] == 0).all()
 
 

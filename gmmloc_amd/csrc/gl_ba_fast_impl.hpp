@@ -49,6 +49,11 @@ constexpr bool kFixed = kCfg.fixed;    // instance with fixed observer key-frame
 constexpr int NWC = kCfg.nw;           // DENSE: GROUPS of the canonical order a frame of this LDS class has at most (= its waves)
 constexpr int NRED = kSpread ? 1 : NWC;  // group totals kept in LDS (a SPREAD workgroup is ONE group)
 constexpr int TSP = 256;                 // SPREAD: threads of a workgroup = the <= 4 slot waves of its group
+// The lean reductions and hand-over of the trial loop (same sums in the same order, less data movement: the 29 totals go round wave 0
+// through LDS, the two sums of pass B share their widest stage, a pass zeroes only the accumulators it uses, g and sum u.b are read
+// where computeScale needs them).  The anchored instances keep the earlier forms: they are at 256 registers with spills, and some of
+// them spilled more with these (profiles/r8_kernel_meta.txt).
+constexpr bool kLean = !kPrior;
 
 #ifdef GL_BA_TRACE  // debug build: (currentChi, tempChi, lambda, rho) of every Levenberg trial of frame 0 -> its points
 __device__ double g_trace[10 * 128];
@@ -1068,8 +1073,10 @@ GL_DEV void spread_reduce2_all(double* v, const Red& R, Coop& C) {
 
 // ---- DENSE shortcuts for the two reductions of every Levenberg trial (same canonical order, fewer barriers) ----
 // pass A (29 values, read by the solving wave only): group totals to red[], ONE barrier, then wave 0 adds the blocks
-// itself and hands the totals round its lanes with v_readlane - no `tot` round trip, no second barrier.  The next
-// writer of red[] is the next trial's pass A, two barriers later.
+// itself and hands the totals round its lanes through tot[0..31]: one write and 15 broadcast reads of two values (29 x 2
+// v_readlane + 29 moves out of the scalar registers before) - the LDS pipe serves a wave's requests in order, and nobody else
+// touches tot[0..31] inside the trial loop (reduce_to_tot's readers are a barrier away on either side), so there is still no
+// second barrier.  The next writer of red[] is the next trial's pass A, two barriers later.
 // (every wave adding the blocks and solving itself was measured slower: profiles/history/r5_ab_allsolve.txt)
 GL_DEV void reduce29_w0_dense(double* v, const Red& R) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1083,16 +1090,22 @@ GL_DEV void reduce29_w0_dense(double* v, const Red& R) {
     double s = NWC > 1 ? add_nc(R.red[t], R.red[32 + t]) : R.red[t];
 #pragma unroll
     for (int b = 1; b < NWC / 2; ++b) s = add_nc(s, add_nc(R.red[(2 * b) * 32 + t], R.red[(2 * b + 1) * 32 + t]));
-    union {
-      double d;
-      int i[2];
-    } u, w;
-    u.d = s;
+    if (kLean) {
+      R.tot[t] = s;  // (lanes t and t + 32 hold the same sum)
 #pragma unroll
-    for (int i = 0; i < 29; ++i) {
-      w.i[0] = __builtin_amdgcn_readlane(u.i[0], i);
-      w.i[1] = __builtin_amdgcn_readlane(u.i[1], i);
-      v[i] = w.d;
+      for (int i = 0; i < 29; ++i) v[i] = R.tot[i];
+    } else {
+      union {
+        double d;
+        int i[2];
+      } u, w;
+      u.d = s;
+#pragma unroll
+      for (int i = 0; i < 29; ++i) {
+        w.i[0] = __builtin_amdgcn_readlane(u.i[0], i);
+        w.i[1] = __builtin_amdgcn_readlane(u.i[1], i);
+        v[i] = w.d;
+      }
     }
   }
 }
@@ -1125,14 +1138,44 @@ GL_DEV double wave_allreduce_canon(double x) {
   x = x + dpp_f64<0x140>(x);  // lane ^ 15
   return x;
 }
+// two values summed over the wave in the canonical butterfly: the widest stage trades them like a reduce-scatter stage (one
+// swap per word exchanges value 1 of the low half with value 0 of the high half in place), the narrower stages are those of
+// wave_allreduce_canon on the one value a lane is left with.  out: the total of value 0 in lanes 0..31, of value 1 in lanes 32..63 -
+// every lane pair of every stage is the one wave_allreduce_canon adds for that value (a + b = b + a), so the bits are its bits.
+GL_DEV double wave_reduce_pair_canon(double x0, double x1) {
+  double v[2] = {x0, x1};
+  rs_swap_stage<1, 32>(v);
+  union {
+    double d;
+    unsigned u[2];
+  } a, b;
+  a.d = v[0];
+  const gl_v2u lo = __builtin_amdgcn_permlane16_swap(a.u[0], a.u[0], false, false);
+  const gl_v2u hi = __builtin_amdgcn_permlane16_swap(a.u[1], a.u[1], false, false);
+  a.u[0] = lo.x;
+  b.u[0] = lo.y;
+  a.u[1] = hi.x;
+  b.u[1] = hi.y;
+  double x = a.d + b.d;
+  x = x + dpp_f64<0xB1>(x);   // lane ^ 1
+  x = x + dpp_f64<0x4E>(x);   // lane ^ 2
+  x = x + dpp_f64<0x141>(x);  // lane ^ 7
+  x = x + dpp_f64<0x140>(x);  // lane ^ 15
+  return x;
+}
 // pass B (2 values, needed by every thread): wave totals to the small buffer red2, ONE barrier, every thread
 // adds the blocks itself.  The buffer is rewritten one trial later, with the barriers of pass A in between.
 GL_DEV void reduce2_dense(double* v, const Red& R) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double s0 = wave_allreduce_canon(v[0]), s1 = wave_allreduce_canon(v[1]);
-  if (lane == 0) {
-    R.red2[wave * 2] = s0;
-    R.red2[wave * 2 + 1] = s1;
+  if (kLean) {
+    const double s = wave_reduce_pair_canon(v[0], v[1]);
+    if ((lane & 31) == 0) R.red2[wave * 2 + (lane >> 5)] = s;
+  } else {
+    const double s0 = wave_allreduce_canon(v[0]), s1 = wave_allreduce_canon(v[1]);
+    if (lane == 0) {
+      R.red2[wave * 2] = s0;
+      R.red2[wave * 2 + 1] = s1;
+    }
   }
   __syncthreads();
 #pragma unroll
@@ -1562,10 +1605,11 @@ GL_DEV void pt_pass_b_eval(const Uni& U, const GmmDev& gm, const Lds& D, const P
 #define GL_BAF_PROF_LOADS(i)
 #endif
 // one pass over the thread's points: DENSE accumulates the terms in acc[] (level 1), SPREAD leaves the single
-// point's terms there (zeros when the thread has no active point)
-#define GL_BAF_PASS(BODY)                                                     \
+// point's terms there (zeros when the thread has no active point).  NACC: the terms BODY puts (acc[0 .. NACC-1] are zeroed,
+// the others are not touched and not read behind the pass)
+#define GL_BAF_PASS(NACC, BODY)                                               \
   {                                                                           \
-    _Pragma("unroll") for (int i_ = 0; i_ < 32; ++i_) acc[i_] = 0.0;          \
+    _Pragma("unroll") for (int i_ = 0; i_ < (kLean ? (NACC) : 32); ++i_) acc[i_] = 0.0; \
     if (kSpread) {                                                            \
       const SinkSet sk{acc};                                                  \
       const int i = 0;                                                        \
@@ -1628,7 +1672,7 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
       if (!kSpread) {
         // DENSE: only the six diagonal sums, in the canonical order (level 2 = the butterfly of wave_allreduce_canon, level 3 = the blocks
         // of two groups), and the maximum of the point blocks beside them through the same LDS row: one barrier instead of five
-        GL_BAF_PASS(pt_lambda_init_diag(U, gm, D, P, c, robust, md, sk));
+        GL_BAF_PASS(6, pt_lambda_init_diag(U, gm, D, P, c, robust, md, sk));
         const int lane_ = threadIdx.x & 63, wave_ = threadIdx.x >> 6;
         double sd[6];
 #pragma unroll
@@ -1661,7 +1705,7 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
         }
         __syncthreads();  // (the rows are rewritten by pass A's reduction)
       } else {
-      GL_BAF_PASS(pt_lambda_init(U, gm, D, P, c, robust, md, sk));
+      GL_BAF_PASS(21, pt_lambda_init(U, gm, D, P, c, robust, md, sk));
       reduce2<21>(acc, R, C);
       if (pose_active) {
         if (prior_on) {
@@ -1682,7 +1726,7 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
       PROF_T(tA0);
       // ---- pass A ---------------------------------------------------------------------------
       prof_pass = 0;
-      GL_BAF_PASS(pt_pass_a(U, gm, D, P, c, robust, lambda, sk));
+      GL_BAF_PASS(29, pt_pass_a(U, gm, D, P, c, robust, lambda, sk));
       PROF_S(trials, 0, 4);
       PROF_T(tA1);
       PROF_W(trials, 0);
@@ -1723,8 +1767,10 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
       if (qmax == 0) currentChi = uni(bc[26]);
 #pragma unroll
       for (int i = 0; i < 6; ++i) dx[i] = uni(bc[i]);
+      if (!kLean) {
 #pragma unroll
-      for (int i = 0; i < 7; ++i) gsc[i] = uni(bc[19 + i]);
+        for (int i = 0; i < 7; ++i) gsc[i] = uni(bc[19 + i]);
+      }
       ok2 = uni(bc[18]) != 0.0;
       if (threadIdx.x < 64) {
         Pose Pw = P;
@@ -1754,7 +1800,7 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
   }
       prof_pass = 1;
       // (pass B's chunks dealt dynamically to whichever wave is free were measured slower: profiles/history/r5_ab_dynb.txt)
-      GL_BAF_PASS({
+      GL_BAF_PASS(2, {
         double pn[3];
         pt_pass_b_step(U, gm, D, P, dx, c, pn, sk);
         PROF_Q(trials, 1, i, 1);
@@ -1772,6 +1818,12 @@ GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map
       PROF_T(tB2);
       // computeScale: sum_l eps.(lambda eps + b_l) + dx.(lambda dx + b_p).  With eps = u - D^-1 A gd the
       // b-terms collapse to  sum u.b + dx.g  (g = reduced rhs of pass A), so pass B needs no b at all.
+      // (lean: g and sum u.b are read from the broadcast row here, as ordinary uniform values - wave 0 rewrites them behind the next
+      // trial's first barrier; through scalar registers they cost 14 lane reads and 14 registers held across pass B)
+      if (kLean) {
+#pragma unroll
+        for (int i = 0; i < 7; ++i) gsc[i] = bc[19 + i];
+      }
       double scale = lambda * acc[0] + gsc[6];
       const double tempChi = ok2 ? (prior_on ? acc[1] + uni(An.rec[(An.cur ^ 1) * 32 + 27]) : acc[1]) : 1.7976931348623157e308;
       if (pose_active) {

@@ -457,8 +457,10 @@ GL_DEV double dpp_f64(double v) {
     int i[2];
   } a, b;
   a.d = v;
-  b.i[0] = __builtin_amdgcn_update_dpp(0, a.i[0], CTRL, 0xF, 0xF, false);
-  b.i[1] = __builtin_amdgcn_update_dpp(0, a.i[1], CTRL, 0xF, 0xF, false);
+  // (every lane is written and every control used here reads a lane of the same row: with bound_ctrl set there is no old value
+  // to prepare - with `0, ..., false` the compiler zeroed the destination in front of every move)
+  b.i[0] = __builtin_amdgcn_update_dpp(0, a.i[0], CTRL, 0xF, 0xF, true);
+  b.i[1] = __builtin_amdgcn_update_dpp(0, a.i[1], CTRL, 0xF, 0xF, true);
   return b.d;
 }
 GL_DEV double swz16_f64(double v) {
@@ -493,6 +495,8 @@ GL_DEV void rs_stage(double* v, bool hi) {
 // second.  With a = v[i], b = v[i+H] the swap IS the select-and-exchange of a reduce-scatter stage:
 // afterwards a + b holds value i in the low half / even rows and value i+H in the high half / odd
 // rows -- 3 instructions per pair instead of 4 selects + 2 DPP moves + 1 add.
+// The swap overwrites BOTH operands, so the stage leaves the exchanged half in v[i + H] (nobody reads it): a caller that keeps
+// its array alive behind the reduction would otherwise make the compiler copy every v[i + H] in front of its swap.
 typedef unsigned gl_v2u __attribute__((ext_vector_type(2)));
 template <int H, int WIDE>
 GL_DEV void rs_swap_stage(double* v) {
@@ -517,6 +521,7 @@ GL_DEV void rs_swap_stage(double* v) {
     a.u[1] = hi.x;
     b.u[1] = hi.y;
     v[i] = a.d + b.d;
+    v[i + H] = b.d;
   }
 }
 // wave-only reduce-scatter: 32 values per lane in; out: the wave total of value `wave_slot(lane)`,

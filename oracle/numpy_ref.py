@@ -474,11 +474,15 @@ class Problem:
     """Un-reduced dense Levenberg-Marquardt over free poses (6) and free points (3) with the
     g2o control flow (OptimizationAlgorithmLevenberg::solve).  Edges are dicts."""
 
-    def __init__(self, cam, prm):
+    def __init__(self, cam, prm, rho_stop=True, raise_lambda=True, lam_scale=1.0, keep_all=False):
         self.cam, self.prm = cam, prm
+        # altered by tests only: the stop on rho == 0 (og_graph.hpp:765), lambda *= ni after a rejected trial (:748-763), the initial
+        # lambda scaled, and every free vertex kept in the system whether or not a level-0 edge touches it
+        self.rho_stop, self.raise_lambda, self.lam_scale, self.keep_all = rho_stop, raise_lambda, lam_scale, keep_all
         self.poses, self.pose_fixed = [], []
         self.points = []
         self.edges = []
+        self.trace = None  # a list: optimize() appends a record per call (test instrumentation)
 
     def residual(self, e):
         cam = self.cam
@@ -520,6 +524,8 @@ class Problem:
         self.active = [e for e in self.edges if e["level"] == level and not self._all_fixed(e)]
         fp = sorted({e["pose"] for e in self.active if "pose" in e and not self.pose_fixed[e["pose"]]})
         fx = sorted({e["pt"] for e in self.active if "pt" in e})
+        if self.keep_all:
+            fp, fx = [i for i in range(len(self.poses)) if not self.pose_fixed[i]], list(range(len(self.points)))
         self.ip = {p: 6 * i for i, p in enumerate(fp)}
         self.ix = {x: 6 * len(fp) + 3 * i for i, x in enumerate(fx)}
         self.n = 6 * len(fp) + 3 * len(fx)
@@ -565,6 +571,11 @@ class Problem:
             self.points[x] = self.points[x] + dx[o:o + 3]
 
     def optimize(self, iters):
+        """trace (a list, or None): one dict per call - the size n of the system, the initial lambda, the trials q of every outer
+        iteration and the largest ni reached (test instrumentation; no effect on the arithmetic)."""
+        tr = dict(n=self.n, lam0=None, q=[], ni_max=2.0)
+        if self.trace is not None:
+            self.trace.append(tr)
         if self.n == 0:
             return -1
         done = 0
@@ -573,8 +584,9 @@ class Problem:
             cur = self.robust_chi2()
             H, b = self.build()
             if it == 0:
-                self.lam = 1e-5 * np.max(np.abs(np.diag(H)))
+                self.lam = self.lam_scale * 1e-5 * np.max(np.abs(np.diag(H)))
                 self.ni = 2.0
+                tr["lam0"] = self.lam
             rho, q = 0.0, 0
             while True:
                 saved = self.state()
@@ -595,29 +607,40 @@ class Problem:
                     self.ni = 2.0
                     cur = tmp
                 else:
-                    self.lam *= self.ni
-                    self.ni *= 2
+                    if self.raise_lambda:
+                        self.lam *= self.ni
+                        self.ni *= 2
+                    tr["ni_max"] = max(tr["ni_max"], self.ni)
                     self.restore(saved)
                 q += 1
                 if not (rho < 0 and q < 10):
                     break
+            tr["q"].append(q)
             done += 1
-            if q == 10 or rho == 0:
+            if q == 10 or (rho == 0 and self.rho_stop):
                 break
         return done
 
 
-def optimize_current_pose(pose7, Xw, obs, octave, cam, prm):
-    """tracking_opt.cpp:21-217 -> (pose7, is_outlier, n_inliers)."""
+def optimize_current_pose(pose7, Xw, obs, octave, cam, prm, chi2_mono=5.991, chi2_stereo=7.815, cast=F32,
+                          is_mono=lambda ur: ur < 0, readmit=True, min_active=0, trace=None, **lm):
+    """tracking_opt.cpp:21-217 -> (pose7, is_outlier, n_inliers).
+    The keyword arguments are the comparisons of the function, with the reference's as defaults, for tests that alter one at a
+    time (tests/test_optim_cases.py): the two verdict thresholds, the cast both sides of the verdict go through,
+    the mono test on u_right, whether an outlier's error is recomputed before its verdict (:523/:538), and a number of level-0 edges
+    below which a round does not optimise (the reference has none); **lm: Problem's keyword arguments.  trace: a list that
+    receives, per round, dict(chi2 = the value every edge's verdict was taken on, flag = the mask after the round, lm = the
+    optimize() records)."""
     N = Xw.shape[0]
-    pb = Problem(cam, prm)
+    pb = Problem(cam, prm, **lm)
+    pb.trace = [] if trace is not None else None
     T0 = SE3.from7(pose7)
     pb.poses, pb.pose_fixed = [T0], [False]
     idx = []
     for i in range(N):
         if octave[i] < 0:
             continue
-        mono = obs[i, 2] < 0
+        mono = bool(is_mono(obs[i, 2]))
         s = float(prm.sigma2_inv[octave[i]])
         pb.edges.append(dict(kind="pose_mono" if mono else "pose_stereo", pose=0, Xw=Xw[i], meas=obs[i],
                              info=s * np.eye(2 if mono else 3), robust=True,
@@ -630,28 +653,47 @@ def optimize_current_pose(pose7, Xw, obs, octave, cam, prm):
     for rnd in range(4):
         pb.poses = [SE3(T0.R.copy(), T0.t.copy())]
         pb.activate(0)
-        pb.optimize(10)
+        if len(pb.active) >= min_active:
+            pb.optimize(10)
         nbad = 0
         for e, i in zip(pb.edges, idx):
-            if outl[i]:
+            if outl[i] and readmit:
                 e["chi2"] = pb.chi2(e)
-            thr = F32(5.991) if e["kind"] == "pose_mono" else F32(7.815)
-            if F32(e["chi2"]) > thr:
+            thr = cast(chi2_mono) if e["kind"] == "pose_mono" else cast(chi2_stereo)
+            if cast(e["chi2"]) > thr:
                 outl[i], e["level"] = 1, 1
                 nbad += 1
             else:
                 outl[i], e["level"] = 0, 0
             if rnd == 2:
                 e["robust"] = False
+        if trace is not None:
+            chi2 = np.full(N, np.nan)
+            chi2[idx] = [e["chi2"] for e in pb.edges]
+            trace.append(dict(chi2=chi2, flag=outl.copy(), lm=pb.trace))
+            pb.trace = []
         if len(pb.edges) < 10:
             break
     return pb.poses[0].to7(), outl, len(idx) - nbad
 
 
 def joint_optimization(P, F, poses7, has_prior, points, assoc, obs_ptr, obs_pose, obs_uvr, obs_oct, comps, mean,
-                       cam, prm):
-    """localization_opt.cpp:456-925 on the flat problem (see oracle/gmmloc_oracle.cpp)."""
-    pb = Problem(cam, prm)
+                       cam, prm, chi2_mono=5.991, chi2_stereo=7.815, cast=float, depth_test=True, stale=True,
+                       str_level_scale=1.0, str_drop_scale=1.0, prior_as_edge=None, str_all=False, ignore_level_last=False,
+                       trace=None, **lm):
+    """localization_opt.cpp:456-925 on the flat problem (see oracle/gmmloc_oracle.cpp).
+    The keyword arguments are the comparisons of the function, with the reference's as defaults, for tests that alter one at a
+    time (tests/test_optim_cases.py): the observation thresholds (:799-828 and :855-879), a cast on both sides of them,
+    the isDepthPositive half, whether the final verdict reads the chi2 an excluded edge was left with (stale) or
+    recomputes it, the structure threshold at :773 and at :837 scaled, ba_first_as_prior overridden, the structure test applied to
+    every association (str_all), and the levels ignored in the last optimize().  trace: a dict that
+    receives the chi2 every verdict was taken on (str_level, obs_level, str_drop, obs_erase, the last one also recomputed at the
+    final state as obs_fresh) and the optimize() records (lm).  **lm: Problem's keyword arguments."""
+    pb = Problem(cam, prm, **lm)
+    pb.trace = [] if trace is not None else None
+    if prior_as_edge is None:
+        prior_as_edge = prm.ba_first_as_prior
+    th_of = lambda e: cast(chi2_mono) if e["kind"] == "ba_mono" else cast(chi2_stereo)
     pb.poses = [SE3.from7(p) for p in poses7]
     pb.pose_fixed = [False] * P + [True] * F
     pb.points = [np.array(x, float) for x in points]
@@ -660,7 +702,7 @@ def joint_optimization(P, F, poses7, has_prior, points, assoc, obs_ptr, obs_pose
     eobs = []
     for i in range(P):
         if has_prior[i]:
-            if prm.ba_first_as_prior:
+            if prior_as_edge:
                 sr = 1.0 / (2.0 * np.pi / 180.0) ** 2
                 info = np.diag([sr] * 3 + [1.0 / 0.01 ** 2] * 3)
                 pb.edges.append(dict(kind="prior", pose=i, inv_meas=pb.poses[i].inv(), info=info, robust=False,
@@ -677,6 +719,8 @@ def joint_optimization(P, F, poses7, has_prior, points, assoc, obs_ptr, obs_pose
             else:
                 e = dict(kind="gauss", pt=l, sqrt_info=comps["sqrt_info"][a], mean=mean[a].copy(), info=np.eye(3),
                          robust=False, delta=0.0, level=0, chi2=0.0)
+                if str_all:
+                    gmm_deg[l] = e
             pb.edges.append(e)
         for o in range(obs_ptr[l], obs_ptr[l + 1]):
             mono = obs_uvr[o, 2] < 0
@@ -693,28 +737,40 @@ def joint_optimization(P, F, poses7, has_prior, points, assoc, obs_ptr, obs_pose
         if e is None:
             continue
         e["chi2"] = pb.chi2(e)
-        if e["chi2"] > thr_str:
+        if e["chi2"] > thr_str * str_level_scale:
             e["level"] = 1
         e["robust"] = False
+    if trace is not None:
+        trace["str_level"] = np.array([np.nan if e is None else e["chi2"] for e in gmm_deg])
     pb.activate(0)
     pb.optimize(5)
     for e in eobs:
-        th = 5.991 if e["kind"] == "ba_mono" else 7.815
         pc = pb.poses[e["pose"]].map(pb.points[e["pt"]])
-        if e["chi2"] > th or not pc[2] > 0:
+        if cast(e["chi2"]) > th_of(e) or (depth_test and not pc[2] > 0):
             e["level"] = 1
         e["robust"] = False
+    if trace is not None:
+        trace["obs_level"] = np.array([e["chi2"] for e in eobs])
+        trace["state_level"] = (np.stack([T.to7() for T in pb.poses]), np.stack(pb.points))
+    if ignore_level_last:
+        for e in pb.edges:
+            e["level"] = 0
     pb.activate(0)
     iters = pb.optimize(40)
     dropped = np.zeros(L, np.uint8)
     for l, e in enumerate(gmm_deg):
-        if e is not None and pb.chi2(e) > thr_str:
+        if e is not None and pb.chi2(e) > thr_str * str_drop_scale:
             dropped[l] = 1
     erase = np.zeros(len(eobs), np.uint8)
     for o, e in enumerate(eobs):
-        th = 5.991 if e["kind"] == "ba_mono" else 7.815
         pc = pb.poses[e["pose"]].map(pb.points[e["pt"]])
-        erase[o] = 1 if (e["chi2"] > th or not pc[2] > 0) else 0
+        c = e["chi2"] if stale else pb.chi2(e)
+        erase[o] = 1 if (cast(c) > th_of(e) or (depth_test and not pc[2] > 0)) else 0
+    if trace is not None:
+        trace["str_drop"] = np.array([np.nan if e is None else pb.chi2(e) for e in gmm_deg])
+        trace["obs_erase"] = np.array([e["chi2"] for e in eobs])
+        trace["obs_fresh"] = np.array([pb.chi2(e) for e in eobs])
+        trace["lm"] = pb.trace
     return (np.stack([T.to7() for T in pb.poses[:P]]), np.stack(pb.points), dropped, erase, iters)
 
 

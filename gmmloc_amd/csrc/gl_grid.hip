@@ -19,9 +19,28 @@
 //       b in {1/2, 1, 2}, rho = half diagonal of the cell: the outer ellipsoidal bound of
 //       E(T cov) (+) Ball(rho), which contains the centre of every cell the ellipsoid touches.
 // Rounding is covered by margins: T is inflated by 4e-6 for registration and by 1e-6 for the
-// "resolved" test, cells by 1e-9; components that are not SPD / finite, have a condition number
-// above 1e8 (where the computed chi2 may differ from the exact form by more than the margin) or
-// would cover more than 2^22 cells go to a short global list every point evaluates.
+// "resolved" test, cells by 1e-9.  A point is resolved on the COMPUTED chi2 (chi2_rec on the stored
+// inverse, which inv3 makes from cofactors over the determinant), the registered set is the exact
+// ellipsoid of cov, so the argument holds while |computed / exact - 1| at the gate stays below
+//   slack = (1 + 4e-6) / (1 + 1e-6) - 1 - 2e-9  (the 1e-9 terms pay for the registration's own rounding).
+// The condition number alone does not bound that error.  To first order, with u = 2^-53 and the
+// eigenvalues w0 <= w1 <= w2 of cov:
+//   every entry of cov is at most w2, so a cofactor fl(fl(ab) - fl(cd)) is off by at most 3 u w2^2 and the
+//   computed adjugate by at most 9 u w2^2 in norm; against the exact chi2 >= |d|^2 / w2 that is 9 u w2^3 / det =
+//   9 u (w2/w0)(w2/w1), and the determinant summed from the same cofactors adds as much again;
+//   the roundings of the determinant's own sum (9 u w2/w0), of the differences p - mu (2 u w2/w0) and of the nine
+//   products of chi2_rec on entries up to 1 / w0 (about 25 u w2/w0) grow with the condition number only:
+//   err(w) = u (18 (w2/w0)(w2/w1) + 40 (w2/w0)).
+// The constants 18 and 40 and the limit 1e-3 below are estimates, not a proof: they are held empirically by
+// tests/test_assoc_cases.py::test_margin_on_every_admitted_component (every measured error is 50 - 200 times below err(w)).
+// A plane (w0 << w1 ~ w2, what the maps are made of) at condition 1e8 has err = 6e-7; a needle (w0 ~ w1 << w2)
+// reaches the slack at condition 4e4, and the bit-exact host model of tests/assoc_model.py measures 6e-6 at 8e5, 7e-6 at 1e6,
+// 1e-3 at 1e7 and 8e-2 at 9.9e7 on oblique needles (DESIGN.md section 4 has the table): a point 4 % outside the
+// registered ellipsoid with a computed chi2 below the gate.  So a component whose err exceeds the slack is
+// registered with its own gate T (1 + 4e-6) / (1 - err) (every other component exactly as before), and
+// components that are not SPD / finite, have a condition number above 1e8, an err above 1e-3 (where the
+// first-order bound itself stops being trustworthy) or would cover more than 2^22 cells go to a short
+// global list every point evaluates.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -452,6 +471,11 @@ void sym3_inv_host(const double* S, double* I) {
 namespace gl {
 
 constexpr double kT0 = 9.0;  // the association gate (gmmloc_opt.cpp:230-232)
+// admission to the grid and the bound on the relative error of the computed chi2 (head of this file)
+constexpr double kCondMax = 1e8;
+constexpr double kErrPair = 18.0;
+constexpr double kErrOne = 40.0;
+constexpr double kErrMax = 1e-3;
 
 void free_cell_index(Gmm* g) {
   if (g->grid.ptr) (void)hipFree(g->grid.ptr);
@@ -471,7 +495,8 @@ int build_cell_index(Ctx* c, Gmm* g) {
   const int K = g->K;
   const double T = kT0;
   const double t_reg = T * (1.0 + 4e-6);
-  std::vector<double> ext((size_t)K * 3), semi((size_t)K * 3);
+  const double slack = t_reg / (T * (1.0 + 1e-6)) - 1.0 - 2e-9;  // what the margins leave for the error of the computed chi2
+  std::vector<double> ext((size_t)K * 3), semi((size_t)K * 3), treg(K, t_reg);
   std::vector<uint8_t> ok(K, 0);
   std::vector<int32_t> glob;
   double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
@@ -485,14 +510,21 @@ int build_cell_index(Ctx* c, Gmm* g) {
     double w[3];
     eig3_sym(cv, w);
     const double asym = std::fabs(cv[1] - cv[3]) + std::fabs(cv[2] - cv[6]) + std::fabs(cv[5] - cv[7]);
-    if (!(w[0] > 0.0) || !(w[2] / w[0] <= 1e8) || asym > 1e-12 * w[2]) {
+    if (!(w[0] > 0.0) || !(w[2] / w[0] <= kCondMax) || asym > 1e-12 * w[2]) {
       glob.push_back(k);  // no usable bound: evaluated for every point
       continue;
     }
+    const double err = 0x1p-53 * (kErrPair * (w[2] / w[0]) * (w[2] / w[1]) + kErrOne * (w[2] / w[0]));
+    if (!(err <= kErrMax)) {
+      glob.push_back(k);  // a needle: the computed chi2 is too far from the exact form for any margin
+      continue;
+    }
     ok[k] = 1;
-    for (int a = 0; a < 3; ++a) semi[(size_t)k * 3 + a] = std::sqrt(t_reg * w[a]);  // semi-axes of the T-ellipsoid
+    if (err > slack) treg[k] = t_reg / (1.0 - err);  // its own gate: computed <= T (1 + 1e-6) still implies exact <= treg[k]
+    const double t_k = treg[k];
+    for (int a = 0; a < 3; ++a) semi[(size_t)k * 3 + a] = std::sqrt(t_k * w[a]);  // semi-axes of the T-ellipsoid
     for (int a = 0; a < 3; ++a) {
-      ext[(size_t)k * 3 + a] = std::sqrt(t_reg * cv[a * 4]) * (1.0 + 1e-9);
+      ext[(size_t)k * 3 + a] = std::sqrt(t_k * cv[a * 4]) * (1.0 + 1e-9);
       lo[a] = std::min(lo[a], mu[a] - ext[(size_t)k * 3 + a]);
       hi[a] = std::max(hi[a], mu[a] + ext[(size_t)k * 3 + a]);
     }
@@ -562,7 +594,7 @@ int build_cell_index(Ctx* c, Gmm* g) {
       continue;
     }
     for (int b = 0; b < 3; ++b) {
-      const double s1 = (1.0 + 1.0 / betas[b]) * t_reg, s2 = (1.0 + betas[b]) * rho * rho;
+      const double s1 = (1.0 + 1.0 / betas[b]) * treg[k], s2 = (1.0 + betas[b]) * rho * rho;
       const double M[6] = {s1 * cv[0] + s2, s1 * cv[1], s1 * cv[2], s1 * cv[4] + s2, s1 * cv[5], s1 * cv[8] + s2};
       sym3_inv_host(M, r.Minv + b * 6);
     }

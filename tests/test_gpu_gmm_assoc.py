@@ -173,6 +173,7 @@ def test_cell_index_equals_exhaustive(gpu, oracle, map_v1, map_v2, opt, which, N
     mean, cov = {"v1": map_v1, "v2": map_v2, "synth4096": synth.synth_gmm(4096, seed),
                  "synth300": synth.synth_gmm(300, seed), "synth65536": synth.synth_gmm(65536, seed)}[which]
     g = api.GMM(ctx, mean, cov)
+    assert g.index_info()["enabled"]
     rng = np.random.default_rng(seed)
     pts = synth.synth_points(mean, cov, N, seed)
     # + uniform points in and far around the bounding box, + points exactly on means and cell-ish lattices
@@ -196,6 +197,7 @@ def test_cell_index_gather_and_lane_walk_same_bits(gpu, opt):
     torch, ctx = gpu
     mean, cov = synth.synth_gmm(4096, 41)
     g = api.GMM(ctx, mean, cov)
+    assert g.index_info()["enabled"]
     rng = np.random.default_rng(41)
     lo, hi = mean.min(0), mean.max(0)
     pts = np.concatenate([synth.synth_points(mean, cov, 60000, 41), rng.uniform(lo - 2, hi + 2, (8000, 3))])
@@ -215,15 +217,18 @@ def test_cell_index_8_byte_cells_same_bits(gpu, opt):
     mean, cov = synth.synth_gmm(4096, 43)
     lo, hi = mean.min(0), mean.max(0)
     cases.append((mean, cov, np.concatenate([synth.synth_points(mean, cov, 60000, 43), rng.uniform(lo - 2, hi + 2, (8000, 3))])))
-    K = 600  # many overlapping components: cells with tens of candidates
-    m2 = rng.uniform(-0.5, 0.5, (K, 3))
+    # many overlapping components: cells with tens of candidates (2 400 of them over 4 m: build_cell_index keeps an index only while
+    # the mean list stays under K / 24; with 600 over 1 m every cell lists every component and GL_ASSOC_BRUTE stays on the sweep)
+    K = 2400
+    m2 = rng.uniform(-2.0, 2.0, (K, 3))
     c2 = np.tile((np.eye(3) * 0.04).reshape(1, 9), (K, 1)) * rng.uniform(0.5, 1.5, (K, 1))
-    cases.append((m2, c2, rng.uniform(-0.7, 0.7, (30000, 3))))
+    cases.append((m2, c2, rng.uniform(-2.2, 2.2, (30000, 3))))
     for case, (mean, cov, pts) in enumerate(cases):
         res, size = {}, {}
         for c8 in (1, 0):
             opt("assoc_cell8", c8)  # read when the GMM's index is built
             g = api.GMM(ctx, mean, cov)
+            assert g.index_info()["enabled"]
             size[c8] = g.index_info()["bytes"]["packed_cells"]
             for coop in (1, 0):
                 opt("assoc_coop", coop)
@@ -237,17 +242,26 @@ def test_cell_index_8_byte_cells_same_bits(gpu, opt):
 
 
 def test_cell_index_long_lists_in_chunks(gpu):
-    """Many overlapping components: cells with tens of candidates, more than one chunk of the wave's candidate table (304) per wave."""
+    """Many overlapping components: cells with tens of candidates, more than one chunk of the wave's candidate table (304) per wave.
+    (2 400 components over 4 m: with 600 over 1 m every cell lists every component, the mean list is above K / 24,
+    build_cell_index keeps no index and the test would compare the sweep with itself.)  With every lane on a long list a wave walks its lists
+    lane by lane; with every other point far outside the map half of the lanes have none and the lists go through the gather, in chunks."""
     torch, ctx = gpu
     rng = np.random.default_rng(77)
-    K = 600
-    mean = rng.uniform(-0.5, 0.5, (K, 3))
+    K = 2400
+    mean = rng.uniform(-2.0, 2.0, (K, 3))
     cov = np.tile((np.eye(3) * 0.04).reshape(1, 9), (K, 1)) * rng.uniform(0.5, 1.5, (K, 1))
     g = api.GMM(ctx, mean, cov)
-    pts = rng.uniform(-0.7, 0.7, (30000, 3))
+    assert g.index_info()["enabled"]
+    pts = rng.uniform(-2.2, 2.2, (30000, 3))
+    assert g.index_work(torch.from_numpy(pts).cuda()) > 20 * len(pts)  # tens of candidates per point
     (i1, d1), (i2, d2) = _both(torch, g, pts)
     assert np.array_equal(i1, i2) and np.array_equal(d1, d2)
     assert (i1 >= 0).sum() > 10000
+    mixed = np.stack([pts, rng.uniform(50.0, 60.0, pts.shape)], 1).reshape(-1, 3)  # 32 lanes of a wave with a long list, 32 with none
+    (i1, d1), (i2, d2) = _both(torch, g, mixed)
+    assert np.array_equal(i1, i2) and np.array_equal(d1, d2)
+    assert (d1[::2] <= 9.0).sum() > 10000 and (d1[1::2] > 9.0).all()
 
 
 def test_cell_index_adversarial_components(gpu):
@@ -268,6 +282,8 @@ def test_cell_index_adversarial_components(gpu):
     mean = np.concatenate([mean, mean[100:140]])   # duplicates (ties)
     cov = np.concatenate([cov, cov[100:140]]).reshape(-1, 9)
     g = api.GMM(ctx, mean, cov)
+    info = g.index_info()
+    assert info["enabled"] and info["always"] >= 4  # 3, 11, 13, 17 (and 7 where its box is above the limit); 19 and 23 are on no list
     rng = np.random.default_rng(5)
     pts = np.concatenate([pts0, mean[100:140], rng.uniform(-20, 20, (3000, 3))])
     with np.errstate(all="ignore"):
@@ -277,10 +293,13 @@ def test_cell_index_adversarial_components(gpu):
 
 
 def test_cell_index_single_component_and_tiny_maps(gpu):
+    """A list of one component is already above K / 24: build_cell_index keeps NO index on these maps and GL_ASSOC_BRUTE is the
+    sweep (what the index does on a handful of components: tests/test_gpu_assoc_cases.py, on maps with fillers)."""
     torch, ctx = gpu
     for K in (1, 2, 5):
         mean, cov = synth.synth_gmm(K, 40 + K)
         g = api.GMM(ctx, mean, cov)
+        assert g.index_info()["enabled"] is False
         pts = np.concatenate([synth.synth_points(mean, cov, 500, K), np.random.default_rng(K).uniform(-9, 9, (500, 3))])
         (i1, d1), (i2, d2) = _both(torch, g, pts)
         assert np.array_equal(i1, i2) and np.array_equal(d1, d2)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised exactness stress of the cell index behind GL_ASSOC_BRUTE: many maps (sizes, anisotropies up to the
 cond <= 1e8 admission limit and beyond, clustered / spread means, huge and tiny components) x point clouds
-(on-surface, uniform, far outside, exactly on means / cell boundaries); idx AND chi2 must be bit-identical to the
+(on-surface, uniform, far outside, exactly on means / cell boundaries, and scans across the chi2 = 9 surface at both tips of the
+long axis of the thinnest components: the gate.tip family of tests/assoc_cases.py); idx AND chi2 must be bit-identical to the
 plain N x K sweep.    python tools/stress_index.py [n_cases]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,6 +14,16 @@ from gmmloc_amd import api
 def haar(rng, K):
     q, r = np.linalg.qr(rng.standard_normal((K, 3, 3)))
     return q * np.sign(np.diagonal(r, axis1=1, axis2=2))[:, None, :]
+
+
+def tip_scans(cov, mean, ncomp=64, n=32):
+    """n points from 0.98 to 1.08 of the gate's semi-axis at both tips of the long axis, for the ncomp components with the largest
+    (w2/w0)(w2/w1): where the computed chi2 is farthest from the exact one and the registration of the index is tightest"""
+    w, V = np.linalg.eigh(cov)
+    thin = np.argsort(-(w[:, 2] / w[:, 0]) * (w[:, 2] / w[:, 1]))[:ncomp]
+    f = np.linspace(0.98, 1.08, n)
+    step = (f[None, :, None] * np.sqrt(9.0 * w[thin, 2])[:, None, None]) * V[thin, :, 2][:, None, :]
+    return np.concatenate([mean[thin][:, None, :] + step, mean[thin][:, None, :] - step]).reshape(-1, 3)
 
 
 def main():
@@ -39,7 +50,7 @@ def main():
         pts = mean[comp] + np.einsum("nij,nj->ni", L, rng.standard_normal((N, 3))) * rng.choice([0.5, 1.0, 3.0])
         info = g.index_info()
         extra = [rng.uniform(-ext * 1.5, ext * 1.5, (N // 4, 3)), mean[rng.integers(0, K, min(K, 500))],
-                 rng.uniform(-ext, ext, (2000, 3)).round(2)]
+                 rng.uniform(-ext, ext, (2000, 3)).round(2), tip_scans(cov, mean)]
         if info["enabled"]:  # points on cell boundaries
             h = info["cell"]
             extra.append(np.round(rng.uniform(-ext, ext, (2000, 3)) / h) * h)

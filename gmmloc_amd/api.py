@@ -18,7 +18,7 @@ ASSOC_KNN5_EUCLID = 1
 ASSOC_EXHAUSTIVE = 2
 ASSOC_SCREENED = 3  # the same output as ASSOC_EXHAUSTIVE, bit for bit: fp32 screen + fp64 verify of the survivors
 
-F_MEAN, F_COV, F_COV_INV, F_DET, F_SCALE, F_AXIS, F_SQRT_INFO, F_FLAGS, F_NBS_PTR, F_NBS_IDX, F_NBS_DIST = range(11)
+F_MEAN, F_COV, F_COV_INV, F_DET, F_SCALE, F_AXIS, F_SQRT_INFO, F_FLAGS, F_NBS_PTR, F_NBS_IDX, F_NBS_DIST, F_HGW, F_PLANE4 = range(13)
 TIMER_ASSOC, TIMER_REFINE_POSE, TIMER_BA, TIMER_BA_PREP = 0, 1, 2, 3
 COUNTER_BA_REDONE, COUNTER_MATCH_ROUNDS, COUNTER_MATCH_UNITS = 0, 1, 2
 COUNTER_ASSOC_SCREEN_VERIFIED, COUNTER_ASSOC_SCREEN_FALLBACK = 4, 5
@@ -202,7 +202,8 @@ class GMM:
             F_MEAN: ((K, 3), np.float64), F_COV: ((K, 9), np.float64), F_COV_INV: ((K, 9), np.float64),
             F_DET: ((K,), np.float64), F_SCALE: ((K, 3), np.float64), F_AXIS: ((K, 9), np.float64),
             F_SQRT_INFO: ((K, 9), np.float64), F_FLAGS: ((K,), np.uint8), F_NBS_PTR: ((K + 1,), np.int32),
-            F_NBS_IDX: ((nnz,), np.int32), F_NBS_DIST: ((nnz,), np.float64)}[field]
+            F_NBS_IDX: ((nnz,), np.int32), F_NBS_DIST: ((nnz,), np.float64), F_HGW: ((K, 6), np.float64),
+            F_PLANE4: ((K, 4), np.float64)}[field]
         out = np.zeros(shape, dtype=dt)
         _check(self.lib.gl_gmm_get(self.h, field, out.ctypes.data, out.nbytes))
         return out

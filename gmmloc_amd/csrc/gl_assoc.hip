@@ -16,8 +16,10 @@
 //
 //  k_knn3d       : exact k-NN (k <= 8) on the means, ascending squared L2,
 //                  ties by lower index (GMM::queryPoint's knnSearch,
-//                  gaussian_mixture.cpp:553-558); a thread per query, or a wave per
-//                  query (k_knn3d_wave) when the queries are few.
+//                  gaussian_mixture.cpp:553-558, whose nanoflann orders exact ties by
+//                  its tree instead: a declared deviation); a
+//                  thread per query, or a wave per query (k_knn3d_wave) when the
+//                  queries are few.  Fewer than k means: idx -1, dist +inf.
 //
 // Compiled with -ffp-contract=off; the only fused ops are the explicit fma()
 // of the canonical chi2 (gl_device.hpp) -> bit-identical to the fp64 CPU order.
@@ -165,7 +167,8 @@ __global__ __launch_bounds__(256) void k_knn3d(const double* __restrict__ mean, 
       const double d0 = qx - tile[g * 3 + 0], d1 = qy - tile[g * 3 + 1], d2 = qz - tile[g * 3 + 2];
       const double d = (d0 * d0 + d1 * d1) + d2 * d2;  // kdtree_distance, gaussian_mixture.h:33-39
       if (d < dist[KNN - 1]) {
-        // insert after every entry with dist <= d (KNNResultSet::addPoint order)
+        // insert after every entry with dist <= d: means are visited in ascending index, so equal distances come out
+        // lowest index first (nanoflann's KNNResultSet::addPoint does the same insert, but in its tree's visiting order)
         double cd = d;
         int ci = k0 + g;
 #pragma unroll
@@ -193,7 +196,8 @@ __global__ __launch_bounds__(256) void k_knn3d(const double* __restrict__ mean, 
 // Few queries (the reference asks for one point at a time): a WAVE per query.  Lane l keeps the KNN best of the
 // components l, l + 64, ... (visited in ascending index, inserted after the equal ones), then KNN rounds of a
 // lexicographic (distance, index) wave argmin pop the winners - the same ascending-distance, lower-index-first
-// order.  One thread scanning 3 299 means took 0.29 ms.
+// order as k_knn3d (not nanoflann's tree order on exact ties).  An empty slot is (+inf, 0x7fffffff): it loses every
+// argmin against a real entry and comes out as the padding (-1, +inf).  One thread scanning 3 299 means took 0.29 ms.
 template <int KNN>
 __global__ __launch_bounds__(256) void k_knn3d_wave(const double* __restrict__ mean, int K, const double* __restrict__ pts,
                                                     int N, int32_t* __restrict__ out_idx, double* __restrict__ out_dist) {

@@ -265,6 +265,8 @@ int gl_gmm_get(const gl_gmm_t* gmm, int field, void* host_out, size_t bytes) {
     case GL_F_NBS_PTR: src = g->nbs_ptr; need = (K + 1) * 4; break;
     case GL_F_NBS_IDX: src = g->nbs_idx; need = (size_t)g->nnz * 4; break;
     case GL_F_NBS_DIST: src = g->nbs_dist; need = (size_t)g->nnz * 8; break;
+    case GL_F_HGW: src = g->hgw; need = K * 48; break;
+    case GL_F_PLANE4: src = g->plane4; need = K * 32; break;
     case GL_F_COV_INV: need = K * 72; break;
     default: gl::set_error("gl_gmm_get: unknown field %d", field); return GL_ERR_ARG;
   }

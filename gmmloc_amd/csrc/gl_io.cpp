@@ -57,7 +57,7 @@ int read_gmm_file(const char* path, std::vector<double>& mean, std::vector<doubl
   cov.clear();
   for (uint64_t i = 0; i < count; ++i) {
     uint64_t size = 0;
-    if (!get_varint(buf, pos, size) || size == 0 || pos + size > buf.size())
+    if (!get_varint(buf, pos, size) || size == 0 || size > buf.size() - pos)  // never pos + size: it wraps
       return fail("failed to read component message.");  // gmm_utils.cpp:44-47
     const size_t end = pos + size;
     size_t nm = 0, nc = 0;
@@ -80,7 +80,7 @@ int read_gmm_file(const char* path, std::vector<double>& mean, std::vector<doubl
         if (!get_varint(buf, pos, v)) return fail("truncated varint");
       } else if (wt == 2) {
         uint64_t len = 0;
-        if (!get_varint(buf, pos, len) || pos + len > end) return fail("bad length-delimited field");
+        if (!get_varint(buf, pos, len) || pos > end || len > end - pos) return fail("bad length-delimited field");
         if (field == 3 || field == 4) {
           if (len % 8) return fail("bad packed double field");
           for (uint64_t o = 0; o < len; o += 8) {
@@ -91,13 +91,13 @@ int read_gmm_file(const char* path, std::vector<double>& mean, std::vector<doubl
         }
         pos += len;
       } else if (wt == 1) {  // unpacked double
-        if (pos + 8 > end) return fail("truncated double");
+        if (pos > end || end - pos < 8) return fail("truncated double");
         double v;
         memcpy(&v, &buf[pos], 8);
         pos += 8;
         take(field, v);
       } else if (wt == 5) {
-        if (pos + 4 > end) return fail("truncated fixed32");
+        if (pos > end || end - pos < 4) return fail("truncated fixed32");
         pos += 4;
       } else {
         return fail("unsupported wire type");

@@ -252,7 +252,9 @@ enum gl_gmm_field {
   GL_F_FLAGS = 7,     /* K uint8        bit0 is_degenerated, bit1 is_salient */
   GL_F_NBS_PTR = 8,   /* (K+1) int32    CSR row pointer of nbs_          */
   GL_F_NBS_IDX = 9,   /* nnz int32      neighbour component index        */
-  GL_F_NBS_DIST = 10  /* nnz double     NeighbourInfo::dist              */
+  GL_F_NBS_DIST = 10, /* nnz double     NeighbourInfo::dist              */
+  GL_F_HGW = 11,      /* K x 6 double   sqrt_info_ sqrt_info_^T, upper triangle 00 01 02 11 12 22 (EdgePt2Gaussian's J^T J) */
+  GL_F_PLANE4 = 12    /* K x 4 double   axis_.col(0), axis_.col(0) . mean (EdgePt2GaussianDeg's plane) */
 };
 /* Copies a derived array to host memory (bytes = capacity of host_out). */
 int gl_gmm_get(const gl_gmm_t* gmm, int field, void* host_out, size_t bytes);
@@ -290,7 +292,11 @@ int gl_gmm_index_bytes(const gl_gmm_t* gmm, double bytes[3]);
 int gl_assoc_index_work(gl_ctx_t* ctx, const gl_gmm_t* gmm, const double* pts_dev, int N, int64_t* pairs_dev);
 
 /* exact k-NN (k <= 8) on the 3-D means, ascending squared L2 (queryPoint's knnSearch).
- * idx_dev: N x k (-1 padded); dist_dev: N x k (may be NULL). */
+ * idx_dev: N x k; dist_dev: N x k (may be NULL).  With fewer than k means (or a NaN query, or NaN means, which are
+ * never returned) the remaining entries are padded with idx = -1, dist = +inf.
+ * Equal distances are returned lowest index first.  The reference's nanoflann returns them in the order its kd-tree
+ * visits the leaves, which is not the index order: on an exact tie the index ORDER differs, and where the tie straddles
+ * the k-th place so does the index SET; the distances are the same. */
 int gl_knn3d(gl_ctx_t* ctx, const gl_gmm_t* gmm, const double* pts_dev, int N, int k, int32_t* idx_dev,
              double* dist_dev);
 

@@ -99,6 +99,48 @@ def test_gmm_file_errors(lib, tmp_path):
     (tmp_path / "unpacked.gmm").write_bytes(b"\x01" + bytes([len(msg)]) + msg)
     m, c = api.read_gmm_file(tmp_path / "unpacked.gmm")
     assert np.array_equal(m, [[1.0, 2.0, 3.0]]) and np.array_equal(c.reshape(3, 3), np.eye(3))
+    # lengths near 2^64: `pos + len` wraps, so the reader compares `len > end - pos`.  Each file is read in a child process
+    # under a time limit, so a reader that walks out of the buffer or never ends is a failed test, not a crashed or hung suite.
+    good = b"\x1a\x18" + np.arange(3.0).tobytes() + b"\x22\x48" + np.eye(3).tobytes()
+    huge = lambda n: _varint((1 << 64) - n)
+    pad8 = b"\x08\x01" * 4  # eight bytes of field 1 in front, so that pos >= 8
+    bad = {
+        "size_2p64m1": b"\x01" + huge(1) + good,                                      # a message size of 2^64 - 1
+        "packed_2p64m8": _msgs([pad8 + b"\x1a" + huge(8) + np.arange(3.0).tobytes()]),  # packed field 3, len = 2^64 - 8
+        "unknown_back_to_tag": _msgs([pad8 + b"\x2a" + huge(11) + b"\x00" * 16]),      # field 5: tag (1) + len (10) bytes back
+        "count_over_file": b"\x05" + _msgs([good])[1:],                               # five announced, one present
+        "varint_10_continued": b"\xff" * 10 + good,                                   # continuation bit on the tenth byte
+    }
+    assert len(huge(11)) == 10
+    (tmp_path / "good.gmm").write_bytes(_msgs([good]))
+    assert _read_in_child(tmp_path / "good.gmm") == "rc=0 K=1"
+    for name, data in bad.items():
+        (tmp_path / (name + ".gmm")).write_bytes(data)
+        assert _read_in_child(tmp_path / (name + ".gmm")) == "rc=-3 K=-1", name  # GL_ERR_FORMAT
+
+
+def _varint(v):
+    out = b""
+    while v >= 0x80:
+        out += bytes([(v & 0x7F) | 0x80])
+        v >>= 7
+    return out + bytes([v])
+
+
+def _msgs(msgs):
+    return _varint(len(msgs)) + b"".join(_varint(len(m)) + m for m in msgs)
+
+
+def _read_in_child(path):
+    """gl_gmm_file_read on `path` in a fresh interpreter -> 'rc=<code> K=<count>'; a crash or a hang fails here"""
+    import subprocess
+    import sys
+    from gmmloc_amd import _lib
+    code = ("import ctypes as C, sys\nlib = C.CDLL(sys.argv[1])\nK = C.c_int32(-1)\n"  # the library alone: a light child
+            "rc = lib.gl_gmm_file_read(sys.argv[2].encode(), None, None, 0, C.byref(K))\nprint('rc=%d K=%d' % (rc, K.value))\n")
+    r = subprocess.run([sys.executable, "-c", code, _lib.LIB_PATH, str(path)], cwd=ROOT, capture_output=True, text=True, timeout=20)
+    assert r.returncode == 0, "the reader's process ended with %d: %s" % (r.returncode, r.stderr[-400:])
+    return r.stdout.strip()
 
 
 @pytest.mark.parametrize("name", ["v1", "v2"])

@@ -19,4 +19,4 @@ from .api import (  # noqa: F401
     track_frames,
     track_frames_anchored,
 )
-from .map_grow import map_add, map_fuse, fuse_observations_from_map, map_views  # noqa: F401
+from .map_grow import map_add, map_fuse, fuse_observations_from_map, map_views, process_key_frame_from_map  # noqa: F401

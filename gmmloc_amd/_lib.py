@@ -70,6 +70,23 @@ class gl_map_fuse_out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("result", "repl_src", "repl_tgt", "obs_new_pos")] + [("repl_cap", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class gl_stereo_points_in(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("pose", "feat_uv", "feat_ur", "feat_depth", "feat_oct", "cand", "ncand", "held", "kf_row")]
+
+
+class gl_stereo_points_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("pts0", "new_feat", "new_pos", "new_assoc", "new_ref_kf", "att_mp", "att_kf", "att_feat", "n_new",
+                                          "feat_new", "stats")]
+
+
+class gl_temporal_points_in(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("pose", "feat_uv", "feat_depth", "feat_oct", "held", "last_outlier", "feat_desc")]
+
+
+class gl_temporal_points_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("temp_flag", "n_temp", "last_pt", "last_observed", "last_valid", "last_desc", "stats")]
+
+
 class gl_ba_window(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("Pcap", "Fcap", "Lcap", "Ocap")] + [(k, C.c_void_p) for k in BA_WINDOW_ARRAYS])
 
@@ -151,6 +168,8 @@ def load():
         "gl_check_map_association": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32] + [vp] * 6 + [i32, vp]),
         "gl_optimize_triangulation": (i32, [vp, vp, P(gl_camera), P(gl_params), i32] + [vp] * 11 + [i32, vp]),
         "gl_create_map_points": (i32, [vp, vp, P(gl_camera), P(gl_params), C.c_float, i32] + [vp] * 12 + [i32, vp, vp, vp]),
+        "gl_create_stereo_points": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, vp, i32, i32, C.c_float, vp]),
+        "gl_create_temporal_points": (i32, [vp, P(gl_camera), i32, i32, vp, C.c_float, vp]),
         "gl_optimize_current_pose": (i32, [vp, P(gl_camera), P(gl_params), i32, i32, vp, vp, vp, vp, vp, vp]),
         "gl_joint_optimization": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, i32, i32] + [vp] * 11),
         "gl_joint_optimization_stoppable": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, i32, i32] + [vp] * 12),

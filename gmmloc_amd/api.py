@@ -1312,3 +1312,10 @@ def create_map_points(ctx, gmm, cam, prm, pose1, uvr1, depth1, oct1, pose2, uvr2
     finally:
         ctx._exit()
     return x3d, typ, comp
+
+
+
+# the two depth-ordered walks (gl_create_stereo_points, gl_create_temporal_points) live in key_frame.py, as the calls that grow the map live
+# in map_grow.py; they are part of this interface
+from .key_frame import (STEREO_IN_DTYPES, STEREO_WALK_MAX, TEMPORAL_IN_DTYPES, TEMPORAL_LAST_DTYPES, create_stereo_points,  # noqa: E402, F401
+                        create_temporal_points)

@@ -333,6 +333,10 @@ int local_map_launch(Ctx* c, const gl_map_view* map, int B, int NF, const LocalM
 size_t local_map_gathered_place(void* base, int B, int NPcap, int NL, int NK, LocalMapGathered* out);  // bytes; base may be null (size only)
 int local_map_gather_launch(Ctx* c, const gl_map_view* map, int B, int NL, int NK, const LocalMapLists& L, const int32_t* last_mp,
                             const int32_t* kf_feat_mp, const LocalMapGathered& G);
+// (gl_point.hip) k_check_map_association, arguments as gl_check_map_association's and already checked
+int launch_check_map_association(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int N, const double* pose_dev,
+                                 double* pts_dev, const double* uvr_dev, const int32_t* octave_dev, const int32_t* cand_dev,
+                                 const int32_t* ncand_dev, int k, int32_t* out_comp_dev);
 // association launchers (gl_assoc.hip: all-pairs sweep; gl_grid.hip: cell index + sweep of the rest)
 int launch_assoc_brute(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2);
 int launch_assoc_sweep(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,

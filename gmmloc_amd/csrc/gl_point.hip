@@ -636,6 +636,19 @@ PtK make_ptk(const gl_camera* cam, const gl_params* prm) {
 
 }  // namespace
 
+// k_check_map_association for the callers inside the library (gl_keyframe.hip): B > 0, N > 0, k in 1..8, the context's device current
+int gl::launch_check_map_association(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int N, const double* pose_dev,
+                                     double* pts_dev, const double* uvr_dev, const int32_t* octave_dev, const int32_t* cand_dev,
+                                     const int32_t* ncand_dev, int k, int32_t* out_comp_dev) {
+  const int total = B * N;
+  k_check_map_association<<<(unsigned)(((size_t)total * CMA_LANES + 255) / 256), 256, 0, c->stream>>>(make_ptk(cam, prm), B, N, g->K, g->rec12, g->axis,
+                                                                   g->flags, g->nbs_ptr, g->nbs_idx, pose_dev, pts_dev,
+                                                                   uvr_dev, octave_dev, cand_dev, ncand_dev, k,
+                                                                   out_comp_dev);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
 extern "C" {
 
 int gl_optimize_point(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm, int N,
@@ -665,16 +678,9 @@ int gl_check_map_association(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera
   if (B == 0 || N == 0) return GL_OK;
   GL_REQUIRE(B > 0 && N > 0 && k >= 1 && k <= 8, "bad B / N / k");
   GL_REQUIRE(pose_dev && pts_dev && uvr_dev && octave_dev && cand_dev && ncand_dev && out_comp_dev, "null buffer");
-  gl::Ctx* c = gl::C(ctx);
-  gl::Gmm* g = gl::G(gmm);
-  GL_HIP(hipSetDevice(c->device));
-  const int total = B * N;
-  k_check_map_association<<<(unsigned)(((size_t)total * CMA_LANES + 255) / 256), 256, 0, c->stream>>>(make_ptk(cam, prm), B, N, g->K, g->rec12, g->axis,
-                                                                   g->flags, g->nbs_ptr, g->nbs_idx, pose_dev, pts_dev,
-                                                                   uvr_dev, octave_dev, cand_dev, ncand_dev, k,
-                                                                   out_comp_dev);
-  GL_HIP(hipGetLastError());
-  return GL_OK;
+  GL_HIP(hipSetDevice(gl::C(ctx)->device));
+  return gl::launch_check_map_association(gl::C(ctx), gl::G(gmm), cam, prm, B, N, pose_dev, pts_dev, uvr_dev, octave_dev, cand_dev, ncand_dev, k,
+                                          out_comp_dev);
 }
 
 int gl_optimize_triangulation(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm, int N,

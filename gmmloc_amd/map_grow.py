@@ -210,3 +210,47 @@ def fuse_observations_from_map(ctx, cam, map, ba, kf_tables, kf_row, cand_mp, th
     r = map_fuse(ctx, map, ba, kf_row, cand_mp, bi[0], sizes=(NMP, NKF, NOBS), want_new_pos=want_new_pos)
     r.update(best_idx=bi[0], best_dist=bd[0])
     return r
+
+
+def process_key_frame_from_map(ctx, gmm, cam, prm, map, ba, kf_tables, kf_row, feat_depth, held, th_depth, check_depth=True, k=5, sizes=None,
+                               mp_ref_kf=None, scale_factor=1.2):
+    """GMMLoc::processKeyFrame's GMM half for ONE key-frame row on the resident map (gmmloc_opt.cpp:20-113): associateMapElements ->
+    createMapPointsFromStereo, then the new points' descriptor, normal and distances - GMM.search2d -> api.create_stereo_points ->
+    map_add(new_kf = [kf_row], the new rows, their attach triples, the counts on the device) -> api.update_map_points(what = 3) on the
+    new rows.  The key-frame's own table rows (ba kf_pose / kf_twc / kf_uvr / kf_oct, kf_tables['desc'] (key-frame rows, NFK, 32) u8) are
+    the only upload of the pass; feat_depth (NFK,) f32 and held (NFK,) u8 (api.create_stereo_points) belong to them.  Needs mp_ref_kf
+    and the per-point arrays of the matchers in `map`.  One synchronise: map_add's 24-byte read.
+    -> the dict of map_add + cand (NFK,k) / ncand (NFK,) i32 (kept for createMapPoints), feat_new (NFK,) i32, stats (8,) i32 (device
+    tensors) and n_new.  After a truncation by map_add nothing is changed and nothing refreshed (n_new: what the walk made)."""
+    from .api import create_stereo_points, update_map_points
+    import torch
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct", "mp_assoc"))
+    for key in ("mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc"):
+        assert map.get(key) is not None, "map[%r]: missing" % key
+    desc = _tensor("kf_tables['desc']", kf_tables.get("desc"), "uint8", (map["kf_mp"].shape[0], NFK, 32), dev)
+    rk = _tensor("mp_ref_kf", mp_ref_kf, "int32", (NMPcap,), dev)
+    kf_row = int(kf_row)
+    assert 0 <= kf_row < NKF, "kf_row %d outside [0, %d)" % (kf_row, NKF)
+    _tensor("feat_depth", feat_depth, "float32", (NFK,), dev)
+    _tensor("held", held, "uint8", (NFK,), dev)
+    uvr = ba["kf_uvr"][kf_row]
+    pose, uv = ba["kf_pose"][kf_row][None].contiguous(), uvr[None, :, :2].contiguous()
+    cand, ncand, _, _ = gmm.search2d(cam, pose, uv, k=k)
+    row = torch.tensor([kf_row], dtype=torch.int32, device=dev)
+    s = create_stereo_points(ctx, gmm, cam, prm, dict(pose=pose, feat_uv=uv, feat_ur=uvr[None, :, 2].float().contiguous(), feat_depth=feat_depth[None],
+                                                      feat_oct=ba["kf_oct"][kf_row][None].contiguous(), cand=cand, ncand=ncand, held=held[None],
+                                                      kf_row=row), NMP, check_depth, th_depth)
+    r = map_add(ctx, map, ba, (NMP, NKF, NOBS), new_mp=dict(pos=s["new_pos"][0], assoc=s["new_assoc"][0], ref_kf=s["new_ref_kf"][0]),
+                new_kf=row, attach=dict(mp=s["att_mp"][0], kf=s["att_kf"][0], feat=s["att_feat"][0]), mp_ref_kf=rk,
+                n_new_mp=s["n_new"], n_attach=s["n_new"])
+    n_new = r["needed"][0] - NMP
+    if n_new > 0 and not r["status"] & (GROW_OBS_TRUNCATED | GROW_MP_TRUNCATED):
+        m2, b2 = r["map"], r["ba"]
+        new = slice(NMP, NMP + n_new)
+        update_map_points(ctx, dict(twc=b2["kf_twc"], valid=m2["kf_valid"], oct=b2["kf_oct"], desc=desc),
+                          dict(pos=m2["mp_pos"][new], valid=m2["mp_valid"][new], ref_kf=rk[new], obs_ptr=m2["obs_ptr"][NMP:], obs_kf=m2["obs_kf"],
+                               obs_feat=b2["obs_feat"]),
+                          dict(desc=m2["mp_desc"][new], normal=m2["mp_normal"][new], max_dist=m2["mp_max_dist"][new], min_dist=m2["mp_min_dist"][new]),
+                          what=3, scale_factor=scale_factor)
+    r.update(cand=cand[0], ncand=ncand[0], feat_new=s["feat_new"][0], stats=s["stats"][0], n_new=n_new)
+    return r

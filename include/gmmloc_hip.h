@@ -84,6 +84,8 @@ void gl_default_params(gl_params* p);
  * gl_check_map_association         | K bf           | as gl_optimize_point (+ the graph the GMM captured)                 | -
  * gl_optimize_triangulation        | K bf           | tri_lambda2 tri_str_thresh tri_check_str_chi2 sigma2_inv            | -
  * gl_create_map_points             | K bf size      | tri_lambda2 tri_str_thresh tri_check_str_chi2 sigma2_inv            | level ratios
+ * gl_create_stereo_points          | K bf           | as gl_check_map_association                                         | -
+ * gl_create_temporal_points        | K              | -                                                                   | -
  * gl_optimize_current_pose         | K bf           | sigma2_inv                                                          | -
  * gl_joint_optimization            | K bf           | ba_lambda2 tri_str_thresh ba_first_as_prior sigma2_inv              | -
  * gl_joint_optimization_stoppable  | K bf           | ba_lambda2 tri_str_thresh ba_first_as_prior sigma2_inv              | -
@@ -1048,6 +1050,91 @@ int gl_create_map_points(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* ca
                          const float* depth2_dev, const int32_t* oct2_dev, const int32_t* cand1_dev,
                          const int32_t* n1_dev, const int32_t* cand2_dev, const int32_t* n2_dev, int k, double* x3d_dev,
                          int32_t* type_dev, int32_t* comp_dev);
+
+/* ---- points from stereo depth: the two depth-ordered walks ------------------ */
+/* GMMLoc::createMapPointsFromStereo (gmmloc_opt.cpp:36-113) for B key-frames of NF feature slots (B = 1 live, B > 1 replay), between
+ * gl_search2d (whose table stays on the device) and gl_map_add (whose lists and device counts it writes).  Device pointers,
+ * asynchronous on the context's stream, no host synchronise; the context's scratch is written before it is read.
+ *  in:  pose B x 7 (getTcw); feat_uv B x NF x 2; feat_ur / feat_depth B x NF float; feat_oct B x NF (outside 0..7: a padding slot);
+ *       cand B x NF x k, ncand B x NF (gl_search2d; k in 1..8); held B x NF uint8: 0 = mappoints_[i] is null, 1 = a point with
+ *       countObservations() >= 1, 2 = a point without observation (a temporal one); kf_row B: the key-frame's row of the map.
+ *       mp_base: the map's NMP.  check_depth: !is_first (:30).  th_depth: frame::th_depth, compared as float.
+ *  The walk, statement for statement:
+ *   entries (:39-44)   the slots with depth > 0 as a float compare (NaN, +-0, negative: out; +inf: in), never a padding slot;
+ *   order (:49)        ascending (depth, index), the order of std::sort on the pairs;
+ *   create_new (:55-63) held != 1; a held == 2 slot is set to null first;
+ *   the point (:72)    Frame::unproject3: z (u - cx) / fx with z the float depth widened, then Twc.map;
+ *   the check (:75-80) ncand > 0: checkMapAssociation on that point; a null answer is a `continue` - the entry is neither counted nor
+ *                      tested for the break; otherwise a point is created (FromDepthGMM with the component, FromDepth for ncand == 0)
+ *                      and counted; a held == 1 entry is counted;
+ *   the break (:109)   after a counted entry: check_depth && depth > th_depth && num_points > 100, both strict; the entry that
+ *                      breaks has been processed; nothing behind it is touched (a held == 2 slot there keeps its point).
+ *  out: pts0 B x NF x 3 or NULL: the unprojected point of every entry (zeros elsewhere);
+ *       the new points of key-frame b in WALK order at [b x NF, b x NF + n_new[b]): new_feat, new_pos x 3 (the point as the check left
+ *       it), new_assoc (component or -1; FromDepthGMM exactly where >= 0), new_ref_kf = kf_row[b]; the attach triples att_mp = mp_base +
+ *       r, att_kf = kf_row[b], att_feat; entries from n_new[b] on are not written;  n_new B;
+ *       feat_new B x NF: r for the slot that now holds new point r, -1 untouched, -2 set to null and left so (held 2, walked, rejected);
+ *       stats B x 8: {entries, walked, n_new, n_rejected, num_points, broke, 0, 0}.
+ *  For B = 1 new_pos / new_assoc / new_ref_kf / n_new and att_* / n_new are gl_map_add's lists and device counts as they stand.
+ *  More than GL_STEREO_WALK_MAX slots per key-frame: GL_ERR_ARG, nothing is written. */
+#define GL_STEREO_WALK_MAX 4096
+typedef struct gl_stereo_points_in {
+  const double* pose;
+  const double* feat_uv;
+  const float* feat_ur;
+  const float* feat_depth;
+  const int32_t* feat_oct;
+  const int32_t* cand;
+  const int32_t* ncand;
+  const uint8_t* held;
+  const int32_t* kf_row;
+} gl_stereo_points_in;
+typedef struct gl_stereo_points_out {
+  double* pts0;
+  int32_t* new_feat;
+  double* new_pos;
+  int32_t* new_assoc;
+  int32_t* new_ref_kf;
+  int32_t* att_mp;
+  int32_t* att_kf;
+  int32_t* att_feat;
+  int32_t* n_new;
+  int32_t* feat_new;
+  int32_t* stats;
+} gl_stereo_points_out;
+int gl_create_stereo_points(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm, int B, int NF, int k,
+                            const gl_stereo_points_in* in, int mp_base, int check_depth, float th_depth,
+                            const gl_stereo_points_out* out);
+
+/* Tracking::createTemporalPoints (tracking.cpp:411-465) for B last frames that are no key-frames (:414 is the caller's): the same
+ * walk without a check - every entry is counted, the break is always armed (:462).
+ *  in:  pose B x 7 (the last frame's Tcw), feat_uv, feat_depth, feat_oct (padding only), held as above, last_outlier B x NF uint8
+ *       (the last frame's is_outlier_), feat_desc B x NF x 32.
+ *  out: temp_flag B x NF uint8 (1 = the slot now holds a temporal point), n_temp B, and IN PLACE, for the created points only, the rows
+ *       of gl_track_frame_chain's last-frame arrays: last_pt = the unprojected point, last_observed = 0, last_valid = !last_outlier
+ *       (clearTemporalPoints leaves a null slot's is_outlier_ alone and orb_matcher.cpp:432 reads it), last_desc = feat_desc.  The rows
+ *       of held == 1 slots and of slots that are not walked keep their bytes; a walked held == 2 slot is replaced (:453).
+ *       stats B x 8 or NULL: {entries, walked, n_temp, 0, num_pts, broke, 0, 0}. */
+typedef struct gl_temporal_points_in {
+  const double* pose;
+  const double* feat_uv;
+  const float* feat_depth;
+  const int32_t* feat_oct;
+  const uint8_t* held;
+  const uint8_t* last_outlier;
+  const uint8_t* feat_desc;
+} gl_temporal_points_in;
+typedef struct gl_temporal_points_out {
+  uint8_t* temp_flag;
+  int32_t* n_temp;
+  double* last_pt;
+  uint8_t* last_observed;
+  uint8_t* last_valid;
+  uint8_t* last_desc;
+  int32_t* stats;
+} gl_temporal_points_out;
+int gl_create_temporal_points(gl_ctx_t* ctx, const gl_camera* cam, int B, int NF, const gl_temporal_points_in* in, float th_depth,
+                              const gl_temporal_points_out* out);
 
 /* ---- pose refinement ------------------------------------------------------ */
 /* Tracking::optimizeCurrentPose (tracking_opt.cpp:21-217) for B frames.

@@ -13,6 +13,9 @@
 //                                                   removeMapPoint / the BA's erase loop on the resident map (cullKeyFrames, removeFromMap)
 //   Localization::processNewKeyFrame / createMapPoints / fuseObservations + Map::replaceMapPoint, what they ADD to the resident map
 //                                                   (localization.cpp:412-444, :299-321, map.cpp:112-150: addToMap, fuseObservationsInMap)
+//   GMMLoc::createMapPointsFromStereo               (gmmloc_opt.cpp:36-113: createMapPointsFromStereo; on the resident map, with the
+//                                                   association before it and the points' refresh behind it: processKeyFrameInMap)
+//   Tracking::createTemporalPoints                  (tracking.cpp:411-465: createTemporalPoints)
 //   north-star per-frame path: associate + structure-constrained refinement of one frame (trackFrame)
 // Host buffers in, host buffers out: each call stages through device memory owned by the
 // adapter (gl_malloc / gl_memcpy_*), so the host code never sees a HIP type.
@@ -35,7 +38,9 @@ namespace gmmloc_hip {
 // 4: cullKeyFrames / removeFromMap edit the resident map on the device; the erase_obs of jointOptimizationFromMap no longer ask for
 //    a re-upload of the CSR (pass them to removeFromMap); setResidentMapCapacity / addToMap / fuseObservationsInMap were added without
 //    a new version: no existing call changed meaning
-constexpr int kAdapterVersion = 4;
+// 5: createMapPointsFromStereo / createTemporalPoints / processKeyFrameInMap: the depth-ordered walks run on the device - a host that
+//    walked the answers of checkMapAssociation itself (INTEGRATION section 4 as it was) calls these instead
+constexpr int kAdapterVersion = 5;
 
 inline void check(int rc, const char* what) {
   if (rc != GL_OK) throw std::runtime_error(std::string(what) + ": " + gl_last_error_string());
@@ -500,6 +505,227 @@ class GMM {
       check(gl_memcpy_d2h(ctx_, r.repl_tgt.data(), d_tgt, (size_t)got[3] * 4), "d2h");
     }
     if (!(r.status & GL_MAP_GROW_OBS_TRUNCATED)) map_.NOBS = r.nobs;
+    return r;
+  }
+  // ---- points from stereo depth: the depth-ordered walks of GMMLoc::createMapPointsFromStereo (gmmloc_opt.cpp:36-113) and
+  // Tracking::createTemporalPoints (tracking.cpp:411-465) on the device (gl_create_stereo_points / gl_create_temporal_points).
+  struct FrameFeatures {          // one frame's features as the host holds them, NF slots
+    Pose Tcw;
+    std::vector<double> uv;       // NF x 2 (Feature::uv)
+    std::vector<float> ur, depth; // u_right, Feature::depth (-1: none)
+    std::vector<int32_t> oct;     // outside 0..7: a padding slot
+    std::vector<uint8_t> held;    // 0 = mappoints_[i] is null, 1 = countObservations() >= 1, 2 = a point without observation
+  };
+  // the new points in WALK order: feature, position (as checkMapAssociation left it), component (-1: FromDepth, else FromDepthGMM);
+  // feat_new[i]: the new point of slot i, -1 untouched, -2 set to null and left so; cand / ncand: kf->comps_ as a table (NF x num)
+  struct StereoPoints {
+    int32_t n_new = 0, stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // {entries, walked, n_new, n_rejected, num_points, broke, 0, 0}
+    std::vector<int32_t> new_feat, new_assoc, feat_new, cand, ncand;
+    std::vector<double> new_pos;
+  };
+  // associateMapElements + createMapPointsFromStereo for one key-frame: host vectors in, the points to create out.  One synchronise.
+  StereoPoints createMapPointsFromStereo(const FrameFeatures& f, int32_t kf_row, int32_t mp_base, bool check_depth, float th_depth, int num = 5) {
+    const size_t NF = f.oct.size();
+    if (f.uv.size() != NF * 2 || f.ur.size() != NF || f.depth.size() != NF || f.held.size() != NF)
+      throw std::runtime_error("createMapPointsFromStereo: arrays of different lengths");
+    StereoPoints r;
+    r.feat_new.assign(NF, -1);
+    r.cand.assign(NF * (size_t)num, -1);
+    r.ncand.assign(NF, 0);
+    if (!NF) return r;
+    size_t off = 64;
+    auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += (bytes + 63) / 64 * 64;
+      return at;
+    };
+    const size_t o_pose = take(56), o_uv = take(NF * 16), o_ur = take(NF * 4), o_dep = take(NF * 4), o_oct = take(NF * 4), o_held = take(NF),
+                 o_cand = take(NF * num * 4), o_nc = take(NF * 4), o_pos = take(NF * 24), o_int = take(7 * NF * 4);
+    char* b = pooled(6, off).as<char>();
+    auto put = [this](void* dst, const void* src, size_t bytes) { check(gl_memcpy_h2d(ctx_, dst, src, bytes), "h2d"); };
+    put(b + 48, &kf_row, 4);
+    put(b + o_pose, &f.Tcw, 56);
+    put(b + o_uv, f.uv.data(), NF * 16);
+    put(b + o_ur, f.ur.data(), NF * 4);
+    put(b + o_dep, f.depth.data(), NF * 4);
+    put(b + o_oct, f.oct.data(), NF * 4);
+    put(b + o_held, f.held.data(), NF);
+    gl_stereo_points_in in{};
+    in.pose = reinterpret_cast<double*>(b + o_pose);
+    in.feat_uv = reinterpret_cast<double*>(b + o_uv);
+    in.feat_ur = reinterpret_cast<float*>(b + o_ur);
+    in.feat_depth = reinterpret_cast<float*>(b + o_dep);
+    in.feat_oct = reinterpret_cast<int32_t*>(b + o_oct);
+    in.cand = reinterpret_cast<int32_t*>(b + o_cand);
+    in.ncand = reinterpret_cast<int32_t*>(b + o_nc);
+    in.held = reinterpret_cast<uint8_t*>(b + o_held);
+    in.kf_row = reinterpret_cast<int32_t*>(b + 48);
+    int32_t* ints = reinterpret_cast<int32_t*>(b + o_int);
+    gl_stereo_points_out out{};
+    out.new_pos = reinterpret_cast<double*>(b + o_pos);
+    out.new_feat = ints, out.new_assoc = ints + NF, out.new_ref_kf = ints + 2 * NF, out.att_mp = ints + 3 * NF, out.att_kf = ints + 4 * NF,
+    out.att_feat = ints + 5 * NF, out.feat_new = ints + 6 * NF;
+    out.n_new = reinterpret_cast<int32_t*>(b);
+    out.stats = reinterpret_cast<int32_t*>(b + 16);
+    check(gl_search2d(ctx_, gmm_, &cam_, 1, in.pose, (int)NF, in.feat_uv, nullptr, num, const_cast<int32_t*>(in.cand), const_cast<int32_t*>(in.ncand), 0,
+                      nullptr, nullptr),
+          "gl_search2d");
+    check(gl_create_stereo_points(ctx_, gmm_, &cam_, &prm_, 1, (int)NF, num, &in, mp_base, check_depth ? 1 : 0, th_depth, &out), "gl_create_stereo_points");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t head[12];
+    check(gl_memcpy_d2h(ctx_, head, b, 48), "d2h");
+    r.n_new = head[0];
+    std::memcpy(r.stats, head + 4, 32);
+    const size_t n = (size_t)r.n_new;
+    r.new_feat.resize(n), r.new_assoc.resize(n), r.new_pos.resize(n * 3);
+    if (n) {
+      check(gl_memcpy_d2h(ctx_, r.new_feat.data(), out.new_feat, n * 4), "d2h");
+      check(gl_memcpy_d2h(ctx_, r.new_assoc.data(), out.new_assoc, n * 4), "d2h");
+      check(gl_memcpy_d2h(ctx_, r.new_pos.data(), out.new_pos, n * 24), "d2h");
+    }
+    check(gl_memcpy_d2h(ctx_, r.feat_new.data(), out.feat_new, NF * 4), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.cand.data(), in.cand, NF * num * 4), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.ncand.data(), in.ncand, NF * 4), "d2h");
+    return r;
+  }
+  // createTemporalPoints for the last frame (not a key-frame: tracking.cpp:414 is the caller's): rows holds the last-frame arrays of
+  // gl_track_frame_chain as the host made them for the key-points; the rows of the slots that get a temporal point are rewritten
+  // (last_pt, last_observed = 0, last_valid = !last_outlier, last_desc = feat_desc), the others keep their bytes.  -> temp_flag per slot
+  struct LastFrameRows {
+    std::vector<double> last_pt;                              // NF x 3
+    std::vector<uint8_t> last_observed, last_valid, last_desc;  // NF, NF, NF x 32
+  };
+  std::vector<uint8_t> createTemporalPoints(const FrameFeatures& f, const std::vector<uint8_t>& last_outlier, const std::vector<uint8_t>& feat_desc,
+                                            float th_depth, LastFrameRows& rows) {
+    const size_t NF = f.oct.size();
+    if (f.uv.size() != NF * 2 || f.depth.size() != NF || f.held.size() != NF || last_outlier.size() != NF || feat_desc.size() != NF * 32 ||
+        rows.last_pt.size() != NF * 3 || rows.last_observed.size() != NF || rows.last_valid.size() != NF || rows.last_desc.size() != NF * 32)
+      throw std::runtime_error("createTemporalPoints: arrays of different lengths");
+    std::vector<uint8_t> flag(NF, 0);
+    if (!NF) return flag;
+    size_t off = 64;
+    auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += (bytes + 63) / 64 * 64;
+      return at;
+    };
+    const size_t o_pose = take(56), o_uv = take(NF * 16), o_dep = take(NF * 4), o_oct = take(NF * 4), o_held = take(NF), o_outl = take(NF),
+                 o_desc = take(NF * 32), o_flag = take(NF), o_pt = take(NF * 24), o_obs = take(NF), o_val = take(NF), o_ld = take(NF * 32);
+    char* b = pooled(7, off).as<char>();
+    auto put = [this](void* dst, const void* src, size_t bytes) { check(gl_memcpy_h2d(ctx_, dst, src, bytes), "h2d"); };
+    put(b + o_pose, &f.Tcw, 56);
+    put(b + o_uv, f.uv.data(), NF * 16);
+    put(b + o_dep, f.depth.data(), NF * 4);
+    put(b + o_oct, f.oct.data(), NF * 4);
+    put(b + o_held, f.held.data(), NF);
+    put(b + o_outl, last_outlier.data(), NF);
+    put(b + o_desc, feat_desc.data(), NF * 32);
+    put(b + o_pt, rows.last_pt.data(), NF * 24);
+    put(b + o_obs, rows.last_observed.data(), NF);
+    put(b + o_val, rows.last_valid.data(), NF);
+    put(b + o_ld, rows.last_desc.data(), NF * 32);
+    gl_temporal_points_in in{};
+    in.pose = reinterpret_cast<double*>(b + o_pose);
+    in.feat_uv = reinterpret_cast<double*>(b + o_uv);
+    in.feat_depth = reinterpret_cast<float*>(b + o_dep);
+    in.feat_oct = reinterpret_cast<int32_t*>(b + o_oct);
+    in.held = reinterpret_cast<uint8_t*>(b + o_held);
+    in.last_outlier = reinterpret_cast<uint8_t*>(b + o_outl);
+    in.feat_desc = reinterpret_cast<uint8_t*>(b + o_desc);
+    gl_temporal_points_out out{};
+    out.temp_flag = reinterpret_cast<uint8_t*>(b + o_flag);
+    out.n_temp = reinterpret_cast<int32_t*>(b);
+    out.last_pt = reinterpret_cast<double*>(b + o_pt);
+    out.last_observed = reinterpret_cast<uint8_t*>(b + o_obs);
+    out.last_valid = reinterpret_cast<uint8_t*>(b + o_val);
+    out.last_desc = reinterpret_cast<uint8_t*>(b + o_ld);
+    check(gl_create_temporal_points(ctx_, &cam_, 1, (int)NF, &in, th_depth, &out), "gl_create_temporal_points");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    check(gl_memcpy_d2h(ctx_, flag.data(), out.temp_flag, NF), "d2h");
+    check(gl_memcpy_d2h(ctx_, rows.last_pt.data(), out.last_pt, NF * 24), "d2h");
+    check(gl_memcpy_d2h(ctx_, rows.last_observed.data(), out.last_observed, NF), "d2h");
+    check(gl_memcpy_d2h(ctx_, rows.last_valid.data(), out.last_valid, NF), "d2h");
+    check(gl_memcpy_d2h(ctx_, rows.last_desc.data(), out.last_desc, NF * 32), "d2h");
+    return flag;
+  }
+  // GMMLoc::processKeyFrame's GMM half for key-frame kf_row of the resident map, whose own table rows the host has uploaded (the rows
+  // of kf_pose / kf_twc / kf_uvr / kf_oct in the views of setResidentMap, and the arrays below): gl_search2d -> gl_create_stereo_points ->
+  // gl_map_add (the key-frame becomes valid, the new rows, their attach triples; the counts stay on the device) -> gl_update_map_points
+  // on the new rows.  One synchronise.  After a truncation (status) nothing is changed: grow the buffers and call again.
+  struct KeyFrameRowsDev {
+    const double* uv;        // NFK x 2, kf_uvr's first two columns
+    const float* ur;         // NFK, its third as float
+    const float* depth;      // NFK
+    const uint8_t* held;     // NFK (FrameFeatures::held)
+    const uint8_t* kf_desc;  // key-frame rows x NFK x 32: every key-frame's descriptors (gl_update_map_points reads the observers')
+  };
+  struct KeyFrameResult {
+    int32_t nmp = 0, nobs = 0, n_attached = 0, n_skipped = 0, status = 0, n_new = 0, stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<int32_t> feat_new;                             // per slot, as StereoPoints::feat_new: new point r is map row (old NMP) + r
+    const int32_t* cand_dev = nullptr;                         // NFK x num / NFK on the device until the next processKeyFrameInMap:
+    const int32_t* ncand_dev = nullptr;                        //   kf->comps_ for createMapPoints
+  };
+  KeyFrameResult processKeyFrameInMap(int32_t kf_row, const KeyFrameRowsDev& d, bool check_depth, float th_depth, int32_t* mp_ref_kf_dev,
+                                      float scale_factor = 1.2f, int num = 5) {
+    if (kf_row < 0 || kf_row >= map_.NKF || !mp_ref_kf_dev) throw std::runtime_error("processKeyFrameInMap: kf_row / mp_ref_kf_dev");
+    const size_t NF = (size_t)map_.NFK;
+    const int32_t NMP0 = map_.NMP;
+    size_t off = 128;
+    auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += (bytes + 63) / 64 * 64;
+      return at;
+    };
+    const size_t o_cand = take(NF * num * 4), o_nc = take(NF * 4), o_pos = take(NF * 24), o_int = take(7 * NF * 4);
+    char* b = pooled(8, off).as<char>();  // {n_new | stats at 16 | kf_row at 48 | gl_map_add's result at 64}
+    check(gl_memcpy_h2d(ctx_, b + 48, &kf_row, 4), "h2d");
+    gl_stereo_points_in in{};
+    in.pose = map_ba_.kf_pose + (size_t)kf_row * 7;
+    in.feat_uv = d.uv, in.feat_ur = d.ur, in.feat_depth = d.depth, in.held = d.held;
+    in.feat_oct = map_ba_.kf_oct + (size_t)kf_row * NF;
+    in.cand = reinterpret_cast<int32_t*>(b + o_cand);
+    in.ncand = reinterpret_cast<int32_t*>(b + o_nc);
+    in.kf_row = reinterpret_cast<int32_t*>(b + 48);
+    int32_t* ints = reinterpret_cast<int32_t*>(b + o_int);
+    gl_stereo_points_out out{};
+    out.new_pos = reinterpret_cast<double*>(b + o_pos);
+    out.new_feat = ints, out.new_assoc = ints + NF, out.new_ref_kf = ints + 2 * NF, out.att_mp = ints + 3 * NF, out.att_kf = ints + 4 * NF,
+    out.att_feat = ints + 5 * NF, out.feat_new = ints + 6 * NF;
+    out.n_new = reinterpret_cast<int32_t*>(b);
+    out.stats = reinterpret_cast<int32_t*>(b + 16);
+    check(gl_search2d(ctx_, gmm_, &cam_, 1, in.pose, (int)NF, in.feat_uv, nullptr, num, const_cast<int32_t*>(in.cand), const_cast<int32_t*>(in.ncand), 0,
+                      nullptr, nullptr),
+          "gl_search2d");
+    check(gl_create_stereo_points(ctx_, gmm_, &cam_, &prm_, 1, (int)NF, num, &in, NMP0, check_depth ? 1 : 0, th_depth, &out), "gl_create_stereo_points");
+    const gl_map_edit ed = residentEdit(mp_ref_kf_dev);
+    gl_map_add_lists ls{};
+    ls.new_pos = out.new_pos, ls.new_assoc = out.new_assoc, ls.new_ref_kf = out.new_ref_kf, ls.n_new_mp = out.n_new, ls.new_mp_cap = (int32_t)NF;
+    ls.new_kf = in.kf_row, ls.new_kf_cap = 1;
+    ls.att_mp = out.att_mp, ls.att_kf = out.att_kf, ls.att_feat = out.att_feat, ls.n_attach = out.n_new, ls.attach_cap = (int32_t)NF;
+    gl_map_add_out ao{};
+    ao.result = reinterpret_cast<int32_t*>(b + 64);
+    check(gl_map_add(ctx_, map_.NMP, map_.NKF, map_.NFK, map_.NOBS, mp_cap_, obs_cap_, &ed, const_cast<double*>(map_.mp_pos), map_ba_.mp_assoc, &ls, &ao),
+          "gl_map_add");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t head[22];
+    check(gl_memcpy_d2h(ctx_, head, b, 88), "d2h");
+    KeyFrameResult r;
+    std::memcpy(r.stats, head + 4, 32);
+    r.nmp = head[16], r.nobs = head[17], r.n_attached = head[18], r.n_skipped = head[19], r.status = head[21];
+    r.n_new = r.nmp - NMP0;
+    r.cand_dev = in.cand, r.ncand_dev = in.ncand;
+    r.feat_new.resize(NF);
+    if (NF) check(gl_memcpy_d2h(ctx_, r.feat_new.data(), out.feat_new, NF * 4), "d2h");
+    if (r.status & (GL_MAP_GROW_MP_TRUNCATED | GL_MAP_GROW_OBS_TRUNCATED)) return r;
+    map_.NMP = r.nmp, map_.NOBS = r.nobs;
+    if (r.n_new > 0) {
+      const size_t p0 = (size_t)NMP0;
+      check(gl_update_map_points(ctx_, scale_factor, 3, r.n_new, map_.NKF, map_.NFK, map_.NOBS, map_ba_.kf_twc, map_.kf_valid, map_ba_.kf_oct, d.kf_desc,
+                                 map_.mp_pos + p0 * 3, map_.mp_valid + p0, mp_ref_kf_dev + p0, map_.obs_ptr + p0, map_.obs_kf, map_ba_.obs_feat,
+                                 const_cast<uint8_t*>(map_.mp_desc) + p0 * 32, const_cast<double*>(map_.mp_normal) + p0 * 3,
+                                 const_cast<float*>(map_.mp_max_dist) + p0, const_cast<float*>(map_.mp_min_dist) + p0),
+            "gl_update_map_points");
+    }
     return r;
   }
   const gl_map_view& residentMap() const { return map_; }

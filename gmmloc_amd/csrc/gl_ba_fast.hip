@@ -212,27 +212,32 @@ __global__ __launch_bounds__(PREP_T) void k_ba1_prep(BafKArgs A, const double* _
 }  // namespace
 
 // The instances of gl_ba_fast_impl.hpp: per namespace, its LDS capacity in points, waves at most, SPREAD (latency shape) or DENSE,
-// fp32-cached point step (option ba_step32), gauge anchor of the pose (prior edge / fixed pose), fixed observer key-frames.
+// fp32-cached point step (option ba_step32), gauge anchor of the pose (prior edge / fixed pose), fixed observer key-frames, and
+// `wide`: the plain DENSE instance for maps of more than 65 536 components (the others keep a thread's associations in registers,
+// 16 bits each).
 // -DGL_BAF_QUICK builds the first two alone (tools/baf_quick.sh: register / ISA checks).
 namespace {
 struct BafCfg {
   int mcap, nw;
-  bool spread, step32, prior, fixed;
+  bool spread, step32, prior, fixed, wide;
 };
-namespace bafd2000 { constexpr BafCfg kCfg{2000, 8, false, false, false, false}; }     // DENSE, exact step: 1 frame per CU
-namespace bafs { constexpr BafCfg kCfg{256, 8, true, false, false, false}; }           // SPREAD, exact step
+namespace bafd2000 { constexpr BafCfg kCfg{2000, 8, false, false, false, false, false}; }     // DENSE, exact step: 1 frame per CU
+namespace bafs { constexpr BafCfg kCfg{256, 8, true, false, false, false, false}; }           // SPREAD, exact step
 #ifndef GL_BAF_QUICK
-namespace bafd496 { constexpr BafCfg kCfg{496, 2, false, false, false, false}; }       // 4 frames per CU
-namespace bafd1000 { constexpr BafCfg kCfg{1000, 4, false, false, false, false}; }     // 2 frames per CU
-namespace bafs32 { constexpr BafCfg kCfg{256, 8, true, true, false, false}; }          // fp32-cached step: the SPREAD kernel
-namespace bafd2000s32 { constexpr BafCfg kCfg{2000, 8, false, true, false, false}; }   // ... and the largest DENSE class
-namespace bafd496p { constexpr BafCfg kCfg{496, 2, false, false, true, false}; }       // anchored (gl_track_frames_anchored), exact step
-namespace bafd1000p { constexpr BafCfg kCfg{992, 4, false, false, true, false}; }      // (992: two frames per CU with the prior edge's records)
-namespace bafd2000p { constexpr BafCfg kCfg{2000, 8, false, false, true, false}; }
-namespace bafsp { constexpr BafCfg kCfg{256, 8, true, false, true, false}; }
-namespace bafd496f { constexpr BafCfg kCfg{496, 2, false, false, true, true}; }        // anchored with fixed observer key-frames (F = 1 .. 4),
-namespace bafd1000f { constexpr BafCfg kCfg{984, 4, false, false, true, true}; }       // batch shape (984: with the key-frames' poses too)
-namespace bafd2000f { constexpr BafCfg kCfg{2000, 8, false, false, true, true}; }
+namespace bafd496 { constexpr BafCfg kCfg{496, 2, false, false, false, false, false}; }       // 4 frames per CU
+namespace bafd1000 { constexpr BafCfg kCfg{1000, 4, false, false, false, false, false}; }     // 2 frames per CU
+namespace bafs32 { constexpr BafCfg kCfg{256, 8, true, true, false, false, false}; }          // fp32-cached step: the SPREAD kernel
+namespace bafd2000s32 { constexpr BafCfg kCfg{2000, 8, false, true, false, false, false}; }   // ... and the largest DENSE class
+namespace bafd496p { constexpr BafCfg kCfg{496, 2, false, false, true, false, false}; }       // anchored (gl_track_frames_anchored), exact step
+namespace bafd1000p { constexpr BafCfg kCfg{992, 4, false, false, true, false, false}; }      // (992: two frames per CU with the prior edge's records)
+namespace bafd2000p { constexpr BafCfg kCfg{2000, 8, false, false, true, false, false}; }
+namespace bafsp { constexpr BafCfg kCfg{256, 8, true, false, true, false, false}; }
+namespace bafd496f { constexpr BafCfg kCfg{496, 2, false, false, true, true, false}; }        // anchored with fixed observer key-frames (F = 1 .. 4),
+namespace bafd1000f { constexpr BafCfg kCfg{984, 4, false, false, true, true, false}; }       // batch shape (984: with the key-frames' poses too)
+namespace bafd2000f { constexpr BafCfg kCfg{2000, 8, false, false, true, true, false}; }
+namespace bafd496w { constexpr BafCfg kCfg{496, 2, false, false, false, false, true}; }       // plain DENSE for maps of more than 65 536 components
+namespace bafd1000w { constexpr BafCfg kCfg{1000, 4, false, false, false, false, true}; }
+namespace bafd2000w { constexpr BafCfg kCfg{2000, 8, false, false, false, false, true}; }
 #endif
 }  // namespace
 #define GL_BAF_NS bafd2000
@@ -261,6 +266,12 @@ namespace bafd2000f { constexpr BafCfg kCfg{2000, 8, false, false, true, true}; 
 #define GL_BAF_NS bafd1000f
 #include "gl_ba_fast_impl.hpp"
 #define GL_BAF_NS bafd2000f
+#include "gl_ba_fast_impl.hpp"
+#define GL_BAF_NS bafd496w
+#include "gl_ba_fast_impl.hpp"
+#define GL_BAF_NS bafd1000w
+#include "gl_ba_fast_impl.hpp"
+#define GL_BAF_NS bafd2000w
 #include "gl_ba_fast_impl.hpp"
 namespace {
 // HW_REG_XCC_ID (hwreg 20, 4 bits): the XCD the wave runs on
@@ -325,17 +336,21 @@ static const BafInst kBafInst[] = {
     {bafd496f::kCfg, bafd496f::k_ba1_fast, bafd496f::kLdsBytes},
     {bafd1000f::kCfg, bafd1000f::k_ba1_fast, bafd1000f::kLdsBytes},
     {bafd2000f::kCfg, bafd2000f::k_ba1_fast, bafd2000f::kLdsBytes},
+    {bafd496w::kCfg, bafd496w::k_ba1_fast, bafd496w::kLdsBytes},
+    {bafd1000w::kCfg, bafd1000w::k_ba1_fast, bafd1000w::kLdsBytes},
+    {bafd2000w::kCfg, bafd2000w::k_ba1_fast, bafd2000w::kLdsBytes},
 };
 // The instance a launch takes: the flags of the launch, the smallest LDS class that holds the points of a workgroup (DENSE: the
 // frame, SPREAD: one group).  The fixed-observer instances carry the anchored code (the prior is a per-frame flag); the anchored
-// instances exist with the exact step only.
-static const BafInst* baf_instance(const Ctx* c, bool spread, bool prior, int F, int points) {
+// instances exist with the exact step only.  K: the components of the launch's map (only the plain DENSE instances depend on it).
+static const BafInst* baf_instance(const Ctx* c, bool spread, bool prior, int F, int points, int K) {
   const bool anch = prior || F > 0;
   const bool s32 = c->opt.ba_step32 != 0 && !anch;
+  const bool wide = !spread && !anch && !s32 && K > 65536;  // (the instances that keep the associations in registers)
   const BafInst* best = nullptr;
   for (const BafInst& in : kBafInst)
-    if (in.cfg.spread == spread && in.cfg.step32 == s32 && in.cfg.prior == anch && in.cfg.fixed == (F > 0) && in.cfg.mcap >= points &&
-        (!best || in.cfg.mcap < best->cfg.mcap))
+    if (in.cfg.spread == spread && in.cfg.step32 == s32 && in.cfg.prior == anch && in.cfg.fixed == (F > 0) && in.cfg.wide == wide &&
+        in.cfg.mcap >= points && (!best || in.cfg.mcap < best->cfg.mcap))
       best = &in;
   return best;
 }
@@ -352,7 +367,7 @@ int ba1_layout(Ctx* c, int B, int L, int F, bool prior, bool fast, Ba1Layout* ou
   if (c->opt.ba_shape == 1) spread = true;  // forced (tests); a shape that does not fit the device still goes DENSE
   if (F > 0 || !fast) spread = false;       // (fixed observers: batch-shaped instances only)
   if (spread) {
-    const BafInst* in = baf_instance(c, true, prior, 0, 64 * S);
+    const BafInst* in = baf_instance(c, true, prior, 0, 64 * S, 0);
     GL_REQUIRE(in, "no refine instance for this launch");
     GL_HIP(ensure_dynamic_lds(c, (const void*)in->kern, in->lds));
     int occ = 0;
@@ -392,8 +407,8 @@ int ba1_layout(Ctx* c, int B, int L, int F, bool prior, bool fast, Ba1Layout* ou
 }
 
 // one workgroup of G waves per frame; LDS class by stride (4 / 2 / 1 frames per CU)
-static int launch_dense(Ctx* c, BafKArgs a, int* frame_ctr) {
-  const BafInst* in = baf_instance(c, false, a.prior_all != nullptr, a.fxv.F, a.L);
+static int launch_dense(Ctx* c, BafKArgs a, int* frame_ctr, int K) {
+  const BafInst* in = baf_instance(c, false, a.prior_all != nullptr, a.fxv.F, a.L, K);
   GL_REQUIRE(in, "no refine instance for this launch");
   const int threads = 64 * a.G;
   GL_HIP(ensure_dynamic_lds(c, (const void*)in->kern, in->lds));
@@ -423,7 +438,7 @@ static int launch_dense(Ctx* c, BafKArgs a, int* frame_ctr) {
 // anything, and the one-workgroup kernel that follows redoes exactly those frames - same bits, so the caller never sees
 // which kernel answered.  (ba1_layout has checked that the launch fits the device.)
 static int launch_spread(Ctx* c, BafKArgs a) {
-  const BafInst* in = baf_instance(c, true, a.prior_all != nullptr, 0, 64 * a.S);
+  const BafInst* in = baf_instance(c, true, a.prior_all != nullptr, 0, 64 * a.S, 0);
   GL_REQUIRE(in, "no refine instance for this launch");
   GL_HIP(ensure_dynamic_lds(c, (const void*)in->kern, in->lds));
   a.NB = a.G;
@@ -479,11 +494,11 @@ int launch_ba1_fast(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params*
   }
   GL_HIP(hipGetLastError());
   TimerScope ts(c, GL_TIMER_BA);  // the refine kernel proper
-  if (!lay.spread) return launch_dense(c, a, frame_ctr);
+  if (!lay.spread) return launch_dense(c, a, frame_ctr, g->K);
   const int rc = launch_spread(c, a);
   if (rc != GL_OK || a.G == 1) return rc;  // (one workgroup per frame: nothing to follow up)
   a.nb_prev = a.G;  // follow-up: staged results of the complete frames -> the caller's buffers, the others redone
-  return launch_dense(c, a, frame_ctr);
+  return launch_dense(c, a, frame_ctr, g->K);
 }
 
 }  // namespace gl

@@ -54,6 +54,12 @@ constexpr int TSP = 256;                 // SPREAD: threads of a workgroup = the
 // where computeScale needs them).  The anchored instances keep the earlier forms: they are at 256 registers with spills, and some of
 // them spilled more with these (profiles/r8_kernel_meta.txt).
 constexpr bool kLean = !kPrior;
+// Resident associations (DENSE): the thread keeps the association indices of its <= 4 slots in registers for the whole frame (AssocW)
+// instead of reading one from the launch's scratch at the head of every slot of every pass.  The anchored instances and the fp32-step
+// instance keep the loads, like the earlier forms above: they are at 256 registers and spilled more with the indices resident
+// (profiles/r14_kernel_meta.txt).  kCfg.wide: the instances for maps of more than 65 536 components, whose indices do not fit the
+// 16 bits per slot: the loads too.
+constexpr bool kResident = !kSpread && !kPrior && !kStep32 && !kCfg.wide;
 
 #ifdef GL_BA_TRACE  // debug build: (currentChi, tempChi, lambda, rho) of every Levenberg trial of frame 0 -> its points
 __device__ double g_trace[10 * 128];
@@ -249,15 +255,17 @@ struct Lds {      // per-frame state, SoA over MCAP points (index = local point 
   int F, Lf;
 };
 // per-point flag bits + octave (bits 8..10) live in REGISTERS: 16 bits per point slot of the thread
+// (the kResident instances never touch `hi` - its register goes to the associations -; the others keep it: their register counts and
+// spills were measured with it, and four anchored instances spill more without, profiles/r14_kernel_meta.txt)
 struct FlagW {  // slots 0..3 in `lo`; `hi` for a slot 4, which no frame has (S <= 4) but the slot loops cannot prove it
   unsigned long long lo;
   unsigned hi;
 };
 GL_DEV int fw_get(const FlagW& fw, int i) {
-  return i < 4 ? (int)((fw.lo >> (16 * i)) & 0xffffull) : (int)(fw.hi & 0xffffu);
+  return kResident || i < 4 ? (int)((fw.lo >> (16 * i)) & 0xffffull) : (int)(fw.hi & 0xffffu);
 }
 GL_DEV void fw_or(FlagW& fw, int i, int bits) {
-  if (i < 4) fw.lo |= (unsigned long long)bits << (16 * i);
+  if (kResident || i < 4) fw.lo |= (unsigned long long)bits << (16 * i);
   else fw.hi |= (unsigned)bits;
 }
 GL_DEV void fw_activity(FlagW& fw, int i) {
@@ -266,8 +274,20 @@ GL_DEV void fw_activity(FlagW& fw, int i) {
   if ((fl & F_EXISTS) && !(fl & F_LEVR)) act |= F_AR;
   if ((fl & F_EXISTS) && (fl & F_ASSOC) && !(fl & F_LEVG)) act |= F_AG;
   if (kFixed && (fl & F_EXISTS) && ((fl / F_OFFF) & 15) != 15) act |= F_AF;
-  if (i < 4) fw.lo = (fw.lo & ~((unsigned long long)(F_AR | F_AG | F_AF) << (16 * i))) | ((unsigned long long)act << (16 * i));
+  if (kResident || i < 4) fw.lo = (fw.lo & ~((unsigned long long)(F_AR | F_AG | F_AF) << (16 * i))) | ((unsigned long long)act << (16 * i));
   else fw.hi = (fw.hi & ~(unsigned)(F_AR | F_AG | F_AF)) | (unsigned)act;
+}
+// kResident: the gated association of each slot, max(a, 0) in 16 bits per slot like the flags - the address part of the association
+// (load_pt's `ap`); "none" is what the flag word says (F_ASSOC clear <=> a < 0: k_ba1_prep), so every reader that looks at the flag
+// first sees the value it would have loaded.
+struct AssocW {
+  unsigned long long w;
+};
+GL_DEV void aw_set(AssocW& aw, int i, int a) { aw.w |= (unsigned long long)((a > 0 ? a : 0) & 0xffff) << (16 * i); }
+// the association of slot i (point l of the frame) as far as its address goes: equal to gassoc[l] wherever that is >= 0
+GL_DEV int aw_get(const AssocW& aw, const int32_t* __restrict__ gassoc, int i, int l) {
+  if (!kResident) return gassoc[l];
+  return (int)((aw.w >> (16 * i)) & 0xffffull);
 }
 
 // the canonical order of a frame of stride L and this thread's place in it
@@ -1295,17 +1315,20 @@ GL_DEV void restore_point(const Lds& D, int ll) {
 // The normalised observations and the plane records come from the launch's scratch in global memory (read-only after
 // the set-up, coalesced, L2-resident).  A point takes part in a pass iff one of its edges is active: one mask test
 // (slots beyond the frame never get a flag).
+// The plane record is addressed by the point's association.  kResident instances have it in registers (AssocW), so the loads of
+// the observation and of the record are issued together at the head of the slot: one L2 round trip.  The others read the
+// association from the scratch first: two dependent trips.
 // (Software-prefetching slot i+1 was measured: it costs 14 VGPRs -> 6 spilled registers and
 // ~1 GB of scratch writes per launch for no gain; the second wave of the SIMD hides the latency.)
-GL_DEV bool load_pt(const Lds& D, const Map& mp, FlagW fw, const double* __restrict__ gobn, const double* __restrict__ gnd,
-                    const int32_t* __restrict__ gassoc, int i, PtCtx& c) {
+GL_DEV bool load_pt(const Lds& D, const Map& mp, FlagW fw, const AssocW& aw, const double* __restrict__ gobn,
+                    const double* __restrict__ gnd, const int32_t* __restrict__ gassoc, int i, PtCtx& c) {
   c.fl = fw_get(fw, i);
   if (!(c.fl & (F_AR | F_AG | F_AF))) return false;
   c.l = mp.base + slot_off(mp, i);
   c.ll = mp.lbase + slot_off(mp, i);
 #pragma unroll
   for (int j = 0; j < 3; ++j) c.ob[j] = gobn[(size_t)c.l * 3 + j];
-  const int a = gassoc[c.l];
+  const int a = aw_get(aw, gassoc, i, c.l);
   const int ap = a > 0 ? a : 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) c.nd[j] = gnd[(size_t)ap * 4 + j];  // plane normal n and n . mean: the map's table, by component
@@ -1623,7 +1646,7 @@ GL_DEV void pt_pass_b_eval(const Uni& U, const GmmDev& gm, const Lds& D, const P
         GL_BAF_PRIO_SLOT(i);                                                  \
         PROF_S(trials, prof_pass, i);                                         \
         PtCtx c;                                                              \
-        if (!load_pt(D, mp, fw, gobn, gnd, gassoc, i, c)) continue;               \
+        if (!load_pt(D, mp, fw, aw, gobn, gnd, gassoc, i, c)) continue;           \
         GL_BAF_PROF_LOADS(i);                                                 \
         BODY;                                                                 \
         PROF_Q(trials, prof_pass, i, 2);                                      \
@@ -1632,7 +1655,7 @@ GL_DEV void pt_pass_b_eval(const Uni& U, const GmmDev& gm, const Lds& D, const P
   }
 
 // SparseOptimizer::optimize(iters), Levenberg
-GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map& mp, FlagW fw, Pose& P,
+GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map& mp, FlagW fw, const AssocW& aw, Pose& P,
                          const double* __restrict__ gobn, const int32_t* __restrict__ gassoc, const double* __restrict__ gnd,
                          const PtConst& pc, bool robust, int iters, const Red& R, int& trials, Coop& C, Anchor& An) {
   double acc[32];
@@ -1949,6 +1972,7 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   D.gchif = nullptr;
   R.S = S;
   FlagW fw = {0ull, 0u};
+  AssocW aw = {0ull};
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   PROF_K(0);
 #ifdef GL_BA_PROF
@@ -2047,6 +2071,7 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
       for (int j = 0; j < 3; ++j) D.sp[j * MCAP + ll] = pts_io[g * 3 + j];
       D.chir[ll] = 0.0;
       fw_or(fw, i, pv.pfl[gbase + l] & 0xffff);  // (the slot's 16 bits of fw)
+      if (kResident) aw_set(aw, i, gassoc[l]);
       if (kFixed) {  // edges the point does not have (not observed by that key-frame / no such key-frame) count as inactive
 #pragma unroll
         for (int kf = 0; kf < kMaxFixed; ++kf)
@@ -2098,7 +2123,7 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   PROF_K(1);
 #pragma unroll 1
   for (int phase = 0; phase < 3; ++phase) {
-    it3 = optimize_fast(U, gm, D, mp, fw, P, gobn, gassoc, gnd, pc, phase < 2, phase < 2 ? 5 : 40, R, trials, C, An);
+    it3 = optimize_fast(U, gm, D, mp, fw, aw, P, gobn, gassoc, gnd, pc, phase < 2, phase < 2 ? 5 : 40, R, trials, C, An);
     outer += it3 > 0 ? it3 : 0;
     PROF_K(2 + 2 * phase);
     if (phase == 2) break;
@@ -2110,7 +2135,7 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
       if (phase == 0) {  // fresh error of the degenerate GMM edges (:773-786)
         if ((fl & (F_ASSOC | F_DEG)) == (F_ASSOC | F_DEG)) {
           const double p[3] = {D.sp[ll], D.sp[MCAP + ll], D.sp[2 * MCAP + ll]};
-          const size_t ap = (size_t)gassoc[l];
+          const size_t ap = (size_t)aw_get(aw, gassoc, i, l);
           const double nd[4] = {gnd[ap * 4], gnd[ap * 4 + 1], gnd[ap * 4 + 2], gnd[ap * 4 + 3]};
           if (gmm_chi2_fast(U.lm, gm, nd, fl, -1, p) > k.str_thresh) fw_or(fw, i, F_LEVG);
         }
@@ -2166,7 +2191,7 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
     const size_t g = gbase + gperm[l];  // back to the caller's order
     const int fl = fw_get(fw, i);
     uint8_t dr = 0, er = 0;
-    int a = gassoc[l];
+    int a = gassoc[l];  // (read, not unpacked from `aw`: the output is the gated association itself, whatever negative value says "none")
     if (fl & F_EXISTS) {
       const double p[3] = {D.sp[ll], D.sp[MCAP + ll], D.sp[2 * MCAP + ll]};
       if ((fl & (F_ASSOC | F_DEG)) == (F_ASSOC | F_DEG)) {

@@ -1,6 +1,6 @@
 // The mapping thread on the resident map (gmmloc_hip.h): KeyFrame::updateConnections (keyframe.cpp:243-316), the window selection and
 // flattening of Localization::jointOptimization (localization_opt.cpp:460-516, :639-763) and its write-back (:837-853, :898-922), over
-// the caller-owned arrays of gl_map_view + gl_map_ba_view.  The rules, the reproduced quirks and the tie rule are in the header.
+// the caller-owned arrays of gl_map_view + gl_map_ba_view (mapdev::Map).  The rules, the reproduced quirks and the tie rule are in the header.
 // One workgroup per key-frame / window; every ORDER comes from a key that the inputs alone determine:
 //   connections  (a) a slot of the key-frame per thread: one integer atomic add per observation of the held point into the key-frame
 //                counters; (b) a contiguous run of key-frames per thread: how many reach 15, the best (count, lowest row); (c) every
@@ -14,11 +14,11 @@
 // context's scratch (device-scope atomics, atomic loads - same phases, same result).  The per-map-point word, the lists and the
 // position bits are always in the scratch: a word per map point does not fit LDS for a real map, and only the touched words are
 // initialised, so the cost follows the window, not the map.
-#include "gl_internal.hpp"
+#include "gl_map_dev.hpp"
 
 namespace {
 
-using namespace gl::mapdev;  // mp_ok, kf_ok, obs_range, block_excl_scan (shared with gl_map_edit.hip)
+using namespace gl::mapdev;  // Map, mp_ok, kf_ok, kf_row, slot_in, obs_range, Words, block_excl_scan, block_max, best_row
 
 constexpr int T_BW = 1024;
 constexpr int BW_KF_LDS = 4096;  // 2 x 16 KB of words
@@ -27,11 +27,8 @@ constexpr int W_NONE = -1, W_MARK = -2, W_INVALID = -3;
 constexpr int KEY_INF = 0x7fffffff;
 constexpr int CONN_TH = 15;  // keyframe.cpp:280
 
-typedef unsigned long long u64;
-
 struct BwArgs {
-  gl_map_view m;
-  gl_map_ba_view ba;
+  Map m;
   gl_ba_window w;
   int B;
   const int32_t* kf_row;
@@ -48,46 +45,15 @@ struct BwArgs {
   size_t maskw;
 };
 
-// words over the key-frame rows, in LDS or in global memory
-template <bool LDS>
-struct KfWords {
-  int* p;
-  __device__ __forceinline__ int get(int k) const {
-    if constexpr (LDS) return p[k];
-    else return __hip_atomic_load(p + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __device__ __forceinline__ void set(int k, int v) const {
-    if constexpr (LDS) p[k] = v;
-    else __hip_atomic_store(p + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __device__ __forceinline__ void add(int k) const { atomicAdd(p + k, 1); }
-  __device__ __forceinline__ void min_(int k, int v) const { atomicMin(p + k, v); }
-};
-
 __device__ __forceinline__ void bw_sync() {
   __threadfence();
   __syncthreads();
 }
 
-__device__ __forceinline__ u64 block_max(u64 v, u64* s_b, int tid) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const u64 t = __shfl_xor(v, o);
-    v = t > v ? t : v;
-  }
-  if ((tid & 63) == 0) s_b[tid >> 6] = v;
-  __syncthreads();
-  u64 r = 0ull;
-#pragma unroll
-  for (int i = 0; i < T_BW / 64; ++i) r = s_b[i] > r ? s_b[i] : r;
-  __syncthreads();
-  return r;
-}
-
 // (a) + (b) of the connections: on return the counters hold map_frame_weights_, n15 = the observers that reach the threshold and
 // best = count << 32 | (0x7fffffff - row) of the largest count at the lowest row (0: empty counter).  The counters are zero on entry.
 template <bool LDS>
-__device__ __forceinline__ void conn_count(const gl_map_view& m, int kf, KfWords<LDS> cnt, int tid, int* s_w, u64* s_b, int* n15, u64* best) {
+__device__ __forceinline__ void conn_count(const Map& m, int kf, Words<LDS> cnt, int tid, int* s_w, u64* s_b, int* n15, u64* best) {
   const int32_t* row = m.kf_mp + (size_t)kf * m.NFK;
   for (int j = tid; j < m.NFK; j += T_BW) {
     const int p = row[j];
@@ -96,7 +62,7 @@ __device__ __forceinline__ void conn_count(const gl_map_view& m, int kf, KfWords
     obs_range(m, p, &o0, &o1);
     for (int o = o0; o < o1; ++o) {
       const int k = m.obs_kf[o];
-      if (k < 0 || k >= m.NKF || k == kf) continue;  // (:268-269)
+      if (!kf_row(m, k) || k == kf) continue;  // (:268-269)
       cnt.add(k);
     }
   }
@@ -104,7 +70,7 @@ __device__ __forceinline__ void conn_count(const gl_map_view& m, int kf, KfWords
   __syncthreads();
   const int ck = (m.NKF + T_BW - 1) / T_BW;
   const int k0 = min(tid * ck, m.NKF), k1 = min(k0 + ck, m.NKF);
-  int n = 0;
+  int n = 0, tot;
   u64 b = 0ull;
   for (int k = k0; k < k1; ++k) {
     const int c = cnt.get(k);
@@ -113,10 +79,9 @@ __device__ __forceinline__ void conn_count(const gl_map_view& m, int kf, KfWords
     const u64 key = ((u64)(unsigned)c << 32) | (unsigned)(0x7fffffff - k);
     b = key > b ? key : b;
   }
-  int tot;
   block_excl_scan<T_BW>(n, s_w, tid, &tot);
   *n15 = tot;
-  *best = block_max(b, s_b, tid);
+  *best = block_max<T_BW>(b, s_b, tid);
 }
 // is key-frame k (count c) in ordered_keyframes_ (:287-300)
 __device__ __forceinline__ bool conn_keep(int k, int c, int n15, int best_row) { return n15 > 0 ? c >= CONN_TH : k == best_row; }
@@ -179,7 +144,7 @@ __global__ __launch_bounds__(T_BW) void k_connections(BwArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= a.B) return;
   const int NKF = a.m.NKF;
-  const KfWords<LDS> cnt = {LDS ? bw_lds : a.kf_words + (size_t)b * NKF};
+  const Words<LDS> cnt = {LDS ? bw_lds : a.kf_words + (size_t)b * NKF};
   for (int k = tid; k < NKF; k += T_BW) cnt.set(k, 0);
   if constexpr (!LDS) __threadfence();
   __syncthreads();
@@ -205,12 +170,12 @@ __global__ __launch_bounds__(T_BW) void k_connections(BwArgs a) {
     }
     return;
   }
-  const int best_row = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
+  const int brow = best_row(best);
   const int n = rank_selected(
       NKF, tid, s_w, s_rank,
       [&](int k) -> u64 {
         const int c = cnt.get(k);
-        return c > 0 && conn_keep(k, c, n15, best_row) ? conn_key(k, c) : 0ull;
+        return c > 0 && conn_keep(k, c, n15, brow) ? conn_key(k, c) : 0ull;
       },
       [&](int k, int r) {
         if (r < a.Ccap) {
@@ -228,7 +193,7 @@ __global__ __launch_bounds__(T_BW) void k_connections(BwArgs a) {
 // W_INVALID / W_MARK for the invalid ones), the feature in the key-frame's table.  fn(o, k, f, i) for the i-th of them; returns their
 // number.  Four entries at a time, their loads issued together.
 template <bool LDS, class Fn>
-__device__ __forceinline__ int for_each_edge(const BwArgs& a, const KfWords<LDS>& widx, int mp, Fn fn) {
+__device__ __forceinline__ int for_each_edge(const BwArgs& a, const Words<LDS>& widx, int mp, Fn fn) {
   int o0, o1, n = 0;
   obs_range(a.m, mp, &o0, &o1);
   for (int o = o0; o < o1; o += 4) {
@@ -237,11 +202,11 @@ __device__ __forceinline__ int for_each_edge(const BwArgs& a, const KfWords<LDS>
     for (int u = 0; u < 4; ++u) {
       const bool in = o + u < o1;
       k[u] = in ? a.m.obs_kf[o + u] : -1;
-      f[u] = in ? a.ba.obs_feat[o + u] : -1;
+      f[u] = in ? a.m.obs_feat[o + u] : -1;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      if (k[u] < 0 || k[u] >= a.m.NKF || f[u] < 0 || f[u] >= a.m.NFK) continue;
+      if (!slot_in(a.m, k[u], f[u])) continue;
       if (widx.get(k[u]) <= W_MARK) continue;
       fn(o + u, k[u], f[u], n);
       ++n;
@@ -260,7 +225,7 @@ __global__ __launch_bounds__(T_BW) void k_ba_window_build(BwArgs a) {
   if (b >= a.B) return;
   const int NKF = a.m.NKF, NFK = a.m.NFK, NMP = a.m.NMP;
   int* const words = LDS ? bw_lds : a.kf_words + (size_t)b * 2 * NKF;
-  const KfWords<LDS> cnt = {words}, widx = {words + NKF};  // cnt: the covisibility counter, later the first-observation key
+  const Words<LDS> cnt = {words}, widx = {words + NKF};  // cnt: the covisibility counter, later the first-observation key
   int32_t* const order = a.order + (size_t)b * NKF;
   int32_t* const mp_word = a.mp_word + (size_t)b * NMP;  // by map-point row: the first position; later by point l: its window index
   int32_t* const list = a.list + (size_t)b * NMP;
@@ -284,12 +249,12 @@ __global__ __launch_bounds__(T_BW) void k_ba_window_build(BwArgs a) {
   int n15;
   u64 best;
   conn_count<LDS>(a.m, kf, cnt, tid, s_w, s_b, &n15, &best);
-  const int best_row = best ? 0x7fffffff - (int)(unsigned)(best & 0xffffffffull) : -1;
+  const int brow = best ? best_row(best) : -1;
   const int P = 1 + rank_selected(
                         NKF, tid, s_w, s_rank,
                         [&](int k) -> u64 {  // the listed key-frames that are valid, in list order
                           const int c = cnt.get(k);
-                          return c > 0 && conn_keep(k, c, n15, best_row) && kf_ok(a.m, k) ? conn_key(k, c) : 0ull;
+                          return c > 0 && conn_keep(k, c, n15, brow) && kf_ok(a.m, k) ? conn_key(k, c) : 0ull;
                         },
                         [&](int k, int r) {
                           widx.set(k, 1 + r);
@@ -297,7 +262,7 @@ __global__ __launch_bounds__(T_BW) void k_ba_window_build(BwArgs a) {
                         });
   for (int k = tid; k < NKF; k += T_BW) {
     const int c = cnt.get(k);
-    if (c > 0 && conn_keep(k, c, n15, best_row) && !kf_ok(a.m, k)) widx.set(k, W_MARK);  // marked local, not added
+    if (c > 0 && conn_keep(k, c, n15, brow) && !kf_ok(a.m, k)) widx.set(k, W_MARK);  // marked local, not added
     cnt.set(k, KEY_INF);
   }
   if (tid == 0) {
@@ -378,7 +343,7 @@ __global__ __launch_bounds__(T_BW) void k_ba_window_build(BwArgs a) {
   for (int l = tid; l < Lall; l += T_BW) {
     const int mp = list[l];
     const int n = for_each_edge<LDS>(a, widx, mp, [](int, int, int, int) {});
-    lcnt[l] = (n << 1) | (n > 0 || a.ba.mp_assoc[mp] >= 0 ? 1 : 0);
+    lcnt[l] = (n << 1) | (n > 0 || a.m.mp_assoc[mp] >= 0 ? 1 : 0);
   }
   bw_sync();
   const int cl = (Lall + T_BW - 1) / T_BW;
@@ -411,13 +376,13 @@ __global__ __launch_bounds__(T_BW) void k_ba_window_build(BwArgs a) {
       const size_t ft = (size_t)k * NFK + f;
       w.win_obs[so + gi] = o;
       w.obs_pose[so + gi] = k;
-      w.obs_oct[so + gi] = a.ba.kf_oct[ft];
+      w.obs_oct[so + gi] = a.m.kf_oct[ft];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) w.obs_uvr[(so + gi) * 3 + c] = a.ba.kf_uvr[ft * 3 + c];
+      for (int c = 0; c < 3; ++c) w.obs_uvr[(so + gi) * 3 + c] = a.m.kf_uvr[ft * 3 + c];
     });
     if (li < 0 || li >= w.Lcap) continue;
     w.win_mp[sl + li] = mp;
-    w.assoc[sl + li] = a.ba.mp_assoc[mp];
+    w.assoc[sl + li] = a.m.mp_assoc[mp];
     w.obs_ptr[(size_t)b * (w.Lcap + 1) + li] = g0;
 #pragma unroll
     for (int c = 0; c < 3; ++c) w.points[(sl + li) * 3 + c] = a.m.mp_pos[(size_t)mp * 3 + c];
@@ -438,8 +403,8 @@ __global__ __launch_bounds__(T_BW) void k_ba_window_build(BwArgs a) {
     const int k = order[j];
     w.win_kf[sp + j] = k;
 #pragma unroll
-    for (int c = 0; c < 7; ++c) w.poses[(sp + j) * 7 + c] = a.ba.kf_pose[(size_t)k * 7 + c];
-    if (j < P && j < w.Pcap) w.prior[(size_t)b * w.Pcap + j] = k == a.ba.kf_first ? 1 : 0;
+    for (int c = 0; c < 7; ++c) w.poses[(sp + j) * 7 + c] = a.m.kf_pose[(size_t)k * 7 + c];
+    if (j < P && j < w.Pcap) w.prior[(size_t)b * w.Pcap + j] = k == a.m.kf_first ? 1 : 0;
   }
   if (tid == 0) {
     if (L <= w.Lcap) w.obs_ptr[(size_t)b * (w.Lcap + 1) + L] = nobs;
@@ -530,15 +495,6 @@ bool kf_in_lds(const gl::Ctx* c, const gl_map_view* m, int arrays) {
   return m->NKF <= BW_KF_LDS && (size_t)m->NKF * 4 * arrays + 2048 <= (size_t)c->lds_max;
 }
 
-int check_map(const gl_map_view* map) {
-  GL_REQUIRE(map, "null argument");
-  GL_REQUIRE(map->NMP >= 0 && map->NKF >= 0 && map->NFK >= 0 && map->NOBS >= 0, "bad NMP / NKF / NFK / NOBS");
-  GL_REQUIRE((int64_t)map->NKF * map->NFK < ((int64_t)1 << 31), "NKF x NFK must be below 2^31");
-  GL_REQUIRE(map->obs_ptr, "null obs_ptr");
-  GL_REQUIRE(map->NOBS == 0 || map->obs_kf, "null obs_kf");
-  GL_REQUIRE(map->NKF == 0 || map->NFK == 0 || map->kf_mp, "null kf_mp");
-  return GL_OK;
-}
 int check_window(const gl_ba_window* w) {
   GL_REQUIRE(w, "null argument");
   GL_REQUIRE(w->Pcap >= 1 && w->Fcap >= 0 && w->Lcap >= 1 && w->Ocap >= 1, "bad Pcap / Fcap / Lcap / Ocap");
@@ -555,13 +511,12 @@ extern "C" int gl_update_connections(gl_ctx_t* ctx, const gl_map_view* map, int 
   GL_REQUIRE(ctx, "null argument");
   GL_REQUIRE(B >= 0 && Ccap >= 1, "bad B / Ccap");
   if (B == 0) return GL_OK;
-  const int rc = check_map(map);
+  BwArgs a = {};
+  const int rc = map_from_view(__func__, map, nullptr, &a.m);
   if (rc != GL_OK) return rc;
   GL_REQUIRE(kf_row_dev && conn_kf_dev && conn_w_dev && n_conn_dev && status_dev, "null buffer");
   gl::Ctx* c = gl::C(ctx);
   GL_HIP(hipSetDevice(c->device));
-  BwArgs a = {};
-  a.m = *map;
   a.B = B;
   a.kf_row = kf_row_dev;
   a.Ccap = Ccap;
@@ -593,15 +548,14 @@ extern "C" int gl_ba_window_build(gl_ctx_t* ctx, const gl_map_view* map, const g
   GL_REQUIRE(ctx && ba, "null argument");
   GL_REQUIRE(B >= 0, "bad B");
   if (B == 0) return GL_OK;
-  int rc = check_map(map);
+  BwArgs a = {};
+  int rc = map_from_view(__func__, map, ba, &a.m);
   if (rc != GL_OK) return rc;
   rc = check_window(win);
   if (rc != GL_OK) return rc;
   GL_REQUIRE(kf_row_dev, "null buffer");
   GL_REQUIRE(map->NMP == 0 || (map->mp_pos && ba->mp_assoc), "null mp_pos / mp_assoc");
   GL_REQUIRE(map->NKF == 0 || ba->kf_pose, "null kf_pose");
-  GL_REQUIRE(map->NKF == 0 || map->NFK == 0 || (ba->kf_uvr && ba->kf_oct), "null kf_uvr / kf_oct");
-  GL_REQUIRE(map->NOBS == 0 || ba->obs_feat, "null obs_feat");
   gl::Ctx* c = gl::C(ctx);
   GL_HIP(hipSetDevice(c->device));
   const bool lds = kf_in_lds(c, map, 2);
@@ -615,9 +569,6 @@ extern "C" int gl_ba_window_build(gl_ctx_t* ctx, const gl_map_view* map, const g
   rc = gl::ctx_scratch(c, r.off, &scratch, gl::SCRATCH_BAWINDOW);
   if (rc != GL_OK) return rc;
   char* s = (char*)scratch;
-  BwArgs a = {};
-  a.m = *map;
-  a.ba = *ba;
   a.w = *win;
   a.B = B;
   a.kf_row = kf_row_dev;

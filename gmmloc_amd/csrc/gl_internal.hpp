@@ -157,7 +157,8 @@ enum {
   SCRATCH_LOCALMAP,  // gl_update_local_map's global-path counters / bitmask, and the local-map arrays gl_track_frame_chain_map gathers
                      // for its stages (which use the three blocks above)
   SCRATCH_BAWINDOW,  // gl_update_connections / gl_ba_window_build / _apply: per-window words over the map's rows and the window's lists
-  SCRATCH_MAPEDIT,   // gl_map_remove: the marks over the map's rows, the scan words and the copy of the CSR it moves from
+  SCRATCH_MAPEDIT,   // gl_map_remove, gl_map_add, gl_map_fuse: each call's marks over the map's rows and its lists, then the rebuild of the
+                     // CSR (mapdev::CsrRebuild, gl_map_dev.hpp): the scan words and the copy of the CSR it moves from
   SCRATCH_COUNT
 };
 
@@ -355,78 +356,5 @@ int launch_assoc_sweep64(Ctx* c, const Gmm* g, const double* pts, int N, int32_t
 int launch_assoc_index(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, bool resolve_all,
                        void* scratch);
 size_t assoc_index_scratch_bytes(int K, int N, bool resolve_all);
-
-#ifdef __HIPCC__
-// device helpers of the kernels that walk the resident map (gl_ba_window.hip, gl_map_edit.hip, gl_map_grow.hip)
-namespace mapdev {
-__device__ __forceinline__ bool mp_ok(const gl_map_view& m, int p) { return p >= 0 && p < m.NMP && (!m.mp_valid || m.mp_valid[p]); }
-__device__ __forceinline__ bool kf_ok(const gl_map_view& m, int k) { return !m.kf_valid || m.kf_valid[k]; }
-// the CSR range of point p, empty when it is not a sub-range of [0, NOBS]
-__device__ __forceinline__ void obs_range(const gl_map_view& m, int p, int* o0, int* o1) {
-  const int a = m.obs_ptr[p], b = m.obs_ptr[p + 1];
-  const bool ok = a >= 0 && b >= a && b <= m.NOBS;
-  *o0 = ok ? a : 0;
-  *o1 = ok ? b : 0;
-}
-// exclusive prefix sum of v over the workgroup's T threads; *total = the sum.  s_w: T / 64 words of LDS, free again on return.
-template <int T, class V>
-__device__ __forceinline__ V block_excl_scan(V v, V* s_w, int tid, V* total) {
-  const int lane = tid & 63, w = tid >> 6;
-  V inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const V t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  V base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < T / 64; ++i) {
-    const V x = s_w[i];
-    base += i < w ? x : 0;
-    tot += x;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-// the device-wide exclusive scan of the rebuilds of the CSR (gl_map_edit.hip, gl_map_grow.hip): SCAN_TILE words per workgroup of SCAN_T
-// threads, then ONE workgroup over the tiles' sums.  A word's place is cnt[i] + tile[i / SCAN_TILE] afterwards.
-typedef unsigned long long u64;
-constexpr int SCAN_T = 1024, SCAN_PER = 4, SCAN_TILE = SCAN_T * SCAN_PER;
-// workgroup b: the exclusive scan of cnt[0, n) inside tile b, the tile's sum to tile[b].  s_w: SCAN_T / 64 words of LDS.
-__device__ __forceinline__ void tile_scan(u64* cnt, u64* tile, size_t n, u64* s_w, int tid, int b) {
-  const size_t base = (size_t)b * SCAN_TILE + (size_t)tid * SCAN_PER;
-  u64 v[SCAN_PER], sum = 0;
-#pragma unroll
-  for (int u = 0; u < SCAN_PER; ++u) {
-    v[u] = base + u < n ? cnt[base + u] : 0ull;
-    sum += v[u];
-  }
-  u64 total;
-  u64 at = block_excl_scan<SCAN_T, u64>(sum, s_w, tid, &total);
-#pragma unroll
-  for (int u = 0; u < SCAN_PER; ++u) {
-    if (base + u < n) cnt[base + u] = at;
-    at += v[u];
-  }
-  if (tid == 0) tile[b] = total;
-}
-// one workgroup of SCAN_T threads: the exclusive scan of the tiles' sums in place; returns the grand total (every thread)
-__device__ __forceinline__ u64 tile_scan_top(u64* tile, int ntile, u64* s_w, int tid) {
-  u64 carry = 0;
-  for (int i0 = 0; i0 < ntile; i0 += SCAN_T) {
-    const int i = i0 + tid;
-    const u64 v = i < ntile ? tile[i] : 0ull;
-    u64 total;
-    const u64 at = block_excl_scan<SCAN_T, u64>(v, s_w, tid, &total);
-    if (i < ntile) tile[i] = carry + at;
-    carry += total;
-  }
-  return carry;
-}
-}  // namespace mapdev
-#endif
 
 }  // namespace gl

@@ -13,6 +13,7 @@
 //   k_temporal_walk the same walk without a check; writes the chain's last-frame rows in place
 #include "gl_device.hpp"
 #include "gl_internal.hpp"
+#include "gl_map_dev.hpp"  // block_excl_scan
 
 using namespace gld;
 

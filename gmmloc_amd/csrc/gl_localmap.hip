@@ -14,9 +14,13 @@
 // Counters (NKF <= LM_KF_LDS) and mask (NMP <= LM_MP_LDS) live in dynamic LDS sized to the map; beyond a bound that array lives in
 // global memory instead (kf_count itself or the context's scratch), written with device-scope atomics and read back with atomic
 // loads - same phases, same result.  Integer atomics only: nothing depends on the order the waves run in.
-#include "gl_internal.hpp"
+// k_local_map keeps gl_map_view as its argument and its own spelling of the map's rules (mapdev's mp_ok / obs_range / Words, gl_map_dev.hpp):
+// with mapdev::Map and the helpers it measured 1.4 % slower on the 1 500-key-frame map at B = 1 (profiles/r15_map_shared_time.txt).
+#include "gl_map_dev.hpp"
 
 namespace {
+
+using gl::mapdev::block_excl_scan;
 
 constexpr int T_LM = 1024;
 constexpr int LM_KF_LDS = 4096;     // 16 KB of counters
@@ -32,29 +36,6 @@ struct LmArgs {
   int32_t* cnt_glob;   // B x NKF (global counters), or null
   uint32_t* mask_glob; // B x words (global mask), or null
 };
-
-// exclusive prefix sum of v over the workgroup's T_LM threads; *total = the sum.  s_w: T_LM / 64 ints of LDS, free again on return.
-__device__ __forceinline__ int block_excl_scan(int v, int* s_w, int tid, int* total) {
-  const int lane = tid & 63, w = tid >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < T_LM / 64; ++i) {
-    const int x = s_w[i];
-    base += i < w ? x : 0;
-    tot += x;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
 
 template <bool CNT_LDS, bool MASK_LDS>
 __global__ __launch_bounds__(T_LM) void k_local_map(LmArgs a) {
@@ -149,7 +130,7 @@ __global__ __launch_bounds__(T_LM) void k_local_map(LmArgs a) {
     }
   }
   int nkf_total;
-  int pos = block_excl_scan(nloc, s_w, tid, &nkf_total);
+  int pos = block_excl_scan<T_LM>(nloc, s_w, tid, &nkf_total);
   for (int k = k0; k < k1 && nloc > 0; ++k) {
     if (cnt_get(k) > 0 && (!a.m.kf_valid || a.m.kf_valid[k])) {
       if (pos < a.L.KFcap) a.L.local_kf[(size_t)b * a.L.KFcap + pos] = k;
@@ -191,7 +172,7 @@ __global__ __launch_bounds__(T_LM) void k_local_map(LmArgs a) {
   int npt = 0;
   for (int w = w0; w < w1; ++w) npt += __popc(mask_get(w));
   int nmp_total;
-  int at = block_excl_scan(npt, s_w, tid, &nmp_total);
+  int at = block_excl_scan<T_LM>(npt, s_w, tid, &nmp_total);
   for (int w = w0; w < w1 && npt > 0; ++w) {
     uint32_t bits = mask_get(w);
     while (bits) {
@@ -294,11 +275,10 @@ namespace gl {
 int local_map_check(const gl_map_view* map, int B, int NF, const LocalMapLists& L, bool need_point_arrays) {
   GL_REQUIRE(map, "null argument");
   GL_REQUIRE(B >= 0 && NF >= 1 && L.KFcap >= 1 && L.NPcap >= 1, "bad B / NF / KFcap / NPcap");
-  GL_REQUIRE(map->NMP >= 0 && map->NKF >= 0 && map->NFK >= 0 && map->NOBS >= 0, "bad NMP / NKF / NFK / NOBS");
   if (B == 0) return GL_OK;
-  GL_REQUIRE(map->obs_ptr, "null obs_ptr");
-  GL_REQUIRE(map->NOBS == 0 || map->obs_kf, "null obs_kf");
-  GL_REQUIRE(map->NKF == 0 || map->NFK == 0 || map->kf_mp, "null kf_mp");
+  mapdev::Map m;  // (for its checks: the kernels below take the view itself)
+  const int rc = mapdev::map_from_view(__func__, map, nullptr, &m);
+  if (rc != GL_OK) return rc;
   if (need_point_arrays)
     GL_REQUIRE(map->NMP == 0 || (map->mp_pos && map->mp_normal && map->mp_max_dist && map->mp_min_dist && map->mp_desc),
                "null mp_pos / mp_normal / mp_max_dist / mp_min_dist / mp_desc");

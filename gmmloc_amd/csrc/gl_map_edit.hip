@@ -8,17 +8,18 @@
 //             wave, thread 0 decides.  One pass over the candidate's points' observations per candidate, like conn_count.
 //   removal   (a) k_me_mark: a flag per erased CSR position, a flag per removed point, the list RANK of every removed key-frame
 //             (atomicMin: a duplicate is harmless); (b) k_me_points: a point per thread - what it loses, its weight, the step at
-//             which it dies, the slots cleared, mp_ref_kf, its surviving count; (c) k_me_scan / k_me_scan_top: the exclusive scan of
-//             (surviving count | died << 32) over the points, 4 096 points per workgroup and one workgroup over the partial sums;
+//             which it dies, the slots cleared, mp_ref_kf, its surviving count; (c) csr_rebuild_scan / k_me_scan_top: the exclusive scan
+//             of (surviving count | died << 32) over the points, 4 096 points per workgroup and one workgroup over the partial sums;
 //             (d) k_me_move: a point per thread copies its surviving entries to their new places.  The move is NOT in place: obs_kf /
 //             obs_feat are first copied to the context's scratch and (d) reads the copy; the new obs_ptr is made in the scratch and
-//             copied over the old one last, because (d) still reads the old ranges.
+//             copied over the old one last, because (d) still reads the old ranges.  (c) and (d) are mapdev's rebuild of the CSR,
+//             shared with gl_map_add and gl_map_fuse; its scan kernel is defined here.
 // Everything is integer; the only atomics are atomicMin / atomicOr on words whose final value the inputs determine.
-#include "gl_internal.hpp"
+#include "gl_map_dev.hpp"
 
 namespace {
 
-using namespace gl::mapdev;
+using namespace gl::mapdev;  // Map, mp_ok, kf_ok, obs_range, obs_weight, list_len, tile_scan, CsrRebuild, csr_move_point
 
 constexpr int T_CULL = 1024;
 constexpr int T_ME = 256;
@@ -26,8 +27,7 @@ constexpr int RANK_NONE = 0x7f7f7f7f;  // (a byte pattern: the ranks are reset b
 
 // ---------------------------------------------------------------------------------------------------------------- culling
 struct CullArgs {
-  gl_map_view m;
-  gl_map_ba_view ba;
+  Map m;
   const float* kf_depth;
   float th_depth;
   int B, Ccap;
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(T_CULL) void k_cull_keyframes(CullArgs a) {
   __shared__ int s_cnt[2];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   if (b >= a.B) return;
-  const gl_map_view& m = a.m;
+  const Map& m = a.m;
   const int NKF = m.NKF, NFK = m.NFK, nw = (NKF + 31) >> 5;
   unsigned* const inC = cull_lds;
   unsigned* const seen = cull_lds + nw;
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(T_CULL) void k_cull_keyframes(CullArgs a) {
     int st = GL_CULL_JUDGED;
     if (kf < 0 || kf >= NKF) st = GL_CULL_BAD_ROW;
     else if (seen[kf >> 5] >> (kf & 31) & 1u) st = GL_CULL_DUPLICATE;
-    else if (kf == a.ba.kf_first) st = GL_CULL_FIRST;
+    else if (kf == m.kf_first) st = GL_CULL_FIRST;
     else if (!kf_ok(m, kf)) st = GL_CULL_INVALID;
     __syncthreads();  // (every thread has read `seen`)
     if (tid == 0 && st != GL_CULL_BAD_ROW && st != GL_CULL_DUPLICATE) seen[kf >> 5] |= 1u << (kf & 31);
@@ -83,18 +83,19 @@ __global__ __launch_bounds__(T_CULL) void k_cull_keyframes(CullArgs a) {
       if (!mp_ok(m, p)) continue;
       const float d = a.kf_depth[krow + i];
       if (d > a.th_depth || d < 0.f) continue;  // (:358-362; a slot that is not counted needs no walk)
-      const int oct = a.ba.kf_oct[krow + i];
+      const int oct = m.kf_oct[krow + i];
       int o0, o1, w = 0, near = 0;
       bool byC = false;
       obs_range(m, p, &o0, &o1);
-      for (int o = o0; o < o1; o += 2) {  // two entries at a time, their loads issued together
+      // (obs_weight's rule written out: two entries at a time, the loads of their u_right and octave issued together - measured)
+      for (int o = o0; o < o1; o += 2) {
         int k[2], f[2], oc[2];
         double ur[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const bool in = o + u < o1;
           k[u] = in ? m.obs_kf[o + u] : -1;
-          f[u] = in ? a.ba.obs_feat[o + u] : -1;
+          f[u] = in ? m.obs_feat[o + u] : -1;
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -103,8 +104,8 @@ __global__ __launch_bounds__(T_CULL) void k_cull_keyframes(CullArgs a) {
           byC = byC || gone;
           if (!(kin && !gone && f[u] >= 0 && f[u] < NFK)) k[u] = -1;  // (a feature outside the table: no octave, no weight)
           const size_t ft = k[u] >= 0 ? (size_t)k[u] * NFK + f[u] : 0;
-          ur[u] = a.ba.kf_uvr[ft * 3 + 2];
-          oc[u] = a.ba.kf_oct[ft];
+          ur[u] = m.kf_uvr[ft * 3 + 2];
+          oc[u] = m.kf_oct[ft];
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -144,24 +145,15 @@ __global__ __launch_bounds__(T_CULL) void k_cull_keyframes(CullArgs a) {
 
 // ---------------------------------------------------------------------------------------------------------------- removal
 struct EditArgs {
-  int NMP, NKF, NFK, NOBS;
-  gl_map_edit ed;
-  const double* kf_uvr;
-  int kf_first;
+  Map m;
   gl_map_remove_lists l;
   gl_map_remove_out out;
   // scratch
   int32_t* rank;    // NKF: the place of a removed key-frame in rm_kf, RANK_NONE
   uint8_t* pflag;   // NMP: 1 listed in rm_mp; 2 died in this call
   uint8_t* oflag;   // NOBS: 1 erased (a), then 1 lost (b)
-  u64* cnt;         // NMP: surviving entries | died << 32, then its exclusive scan inside the tile
-  u64* tile;        // a word per tile: its sum, then the exclusive scan of the sums
-  int32_t* okf;     // NOBS: obs_kf / obs_feat as they were
-  int32_t* ofeat;
-  int32_t* nptr;    // NMP + 1
+  CsrRebuild rb;    // cnt: surviving entries | died << 32
 };
-
-__device__ __forceinline__ int list_len(const int32_t* n, int cap) { return n ? min(max(*n, 0), cap) : cap; }
 
 __global__ __launch_bounds__(T_ME) void k_me_mark(EditArgs a) {
   const int g = blockIdx.x * T_ME + threadIdx.x, G = gridDim.x * T_ME;
@@ -169,22 +161,22 @@ __global__ __launch_bounds__(T_ME) void k_me_mark(EditArgs a) {
     const int n = list_len(a.l.n_erase, a.l.erase_cap);
     for (int i = g; i < n; i += G) {
       const int o = a.l.erase_obs[i];
-      if (o >= 0 && o < a.NOBS) a.oflag[o] = 1;
+      if (o >= 0 && o < a.m.NOBS) a.oflag[o] = 1;
     }
   }
   if (a.l.rm_mp) {
     const int n = list_len(a.l.n_rm_mp, a.l.rm_mp_cap);
     for (int i = g; i < n; i += G) {
       const int p = a.l.rm_mp[i];
-      if (p >= 0 && p < a.NMP && a.ed.mp_valid[p]) a.pflag[p] = 1;
+      if (mp_row(a.m, p) && a.m.mp_valid[p]) a.pflag[p] = 1;
     }
   }
   if (a.l.rm_kf) {
     const int n = list_len(a.l.n_rm_kf, a.l.rm_kf_cap);
     for (int i = g; i < n; i += G) {
       const int k = a.l.rm_kf[i];
-      if (k < 0 || k >= a.NKF || !a.ed.kf_valid[k]) continue;
-      if (k == a.kf_first) atomicOr(a.out.result + 2, GL_MAP_REMOVE_FIRST_REFUSED);  // (map.cpp:63)
+      if (!kf_row(a.m, k) || !a.m.kf_valid[k]) continue;
+      if (k == a.m.kf_first) atomicOr(a.out.result + 2, GL_MAP_REMOVE_FIRST_REFUSED);  // (map.cpp:63)
       else atomicMin(a.rank + k, i);
     }
   }
@@ -192,26 +184,21 @@ __global__ __launch_bounds__(T_ME) void k_me_mark(EditArgs a) {
 
 __global__ __launch_bounds__(T_ME) void k_me_points(EditArgs a) {
   const int p = blockIdx.x * T_ME + threadIdx.x;
-  if (p < a.NKF && a.rank[p] != RANK_NONE) a.ed.kf_valid[p] = 0;  // (the grid covers max(NMP, NKF) threads)
-  if (p >= a.NMP) return;
-  const int NKF = a.NKF, NFK = a.NFK;
-  const int r0 = a.ed.obs_ptr[p], r1 = a.ed.obs_ptr[p + 1];
-  const bool okr = r0 >= 0 && r1 >= r0 && r1 <= a.NOBS;
-  const int o0 = okr ? r0 : 0, o1 = okr ? r1 : 0;
-  if (!a.ed.mp_valid[p]) {  // a dead point ignores removals (mappoint.cpp:99): its entries, if it has any, stay
-    a.cnt[p] = (u64)(o1 - o0);
+  const Map& m = a.m;
+  if (p < m.NKF && a.rank[p] != RANK_NONE) m.kf_valid[p] = 0;  // (the grid covers max(NMP, NKF) threads)
+  if (p >= m.NMP) return;
+  int o0, o1;
+  obs_range(m, p, &o0, &o1);
+  if (!m.mp_valid[p]) {  // a dead point ignores removals (mappoint.cpp:99): its entries, if it has any, stay
+    a.rb.cnt[p] = (u64)(o1 - o0);
     for (int o = o0; o < o1; ++o) a.oflag[o] = 0;
     return;
   }
   const int pf = a.pflag[p];
-  auto weight = [&](int k, int f) -> int {
-    if (k < 0 || k >= NKF || f < 0 || f >= NFK) return 0;
-    return a.kf_uvr[((size_t)k * NFK + f) * 3 + 2] >= 0.0 ? 2 : 1;
-  };
-  auto rank_of = [&](int k) -> int { return k >= 0 && k < NKF ? a.rank[k] : RANK_NONE; };
+  auto rank_of = [&](int k) -> int { return kf_row(m, k) ? a.rank[k] : RANK_NONE; };
   int wtot = 0, w_er = 0, w_rk = 0, n_er = 0, n_rk = 0;
   for (int o = o0; o < o1; ++o) {
-    const int k = a.ed.obs_kf[o], w = weight(k, a.ed.obs_feat[o]);
+    const int k = m.obs_kf[o], w = obs_weight(m, k, m.obs_feat[o]);
     wtot += w;
     if (a.oflag[o]) {
       ++n_er;
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(T_ME) void k_me_points(EditArgs a) {
     }
   }
   if (!pf && n_er == 0 && n_rk == 0) {  // lost nothing: untouched
-    a.cnt[p] = (u64)(o1 - o0);
+    a.rb.cnt[p] = (u64)(o1 - o0);
     return;
   }
   // the step at which it dies: -1 in the point / erase phase, else the rank of the first removed observer that leaves w <= 2
@@ -231,29 +218,29 @@ __global__ __launch_bounds__(T_ME) void k_me_points(EditArgs a) {
   if (pf || (n_er > 0 && w1 <= 2)) t = -1;
   else if (n_rk > 0 && w1 - w_rk <= 2) {
     for (int o = o0; o < o1; ++o) {
-      const int re = a.oflag[o] ? RANK_NONE : rank_of(a.ed.obs_kf[o]);
+      const int re = a.oflag[o] ? RANK_NONE : rank_of(m.obs_kf[o]);
       if (re == RANK_NONE || re >= t) continue;
       int w = w1;
       for (int o2 = o0; o2 < o1; ++o2) {
-        const int k2 = a.ed.obs_kf[o2];
-        if (!a.oflag[o2] && rank_of(k2) <= re) w -= weight(k2, a.ed.obs_feat[o2]);
+        const int k2 = m.obs_kf[o2];
+        if (!a.oflag[o2] && rank_of(k2) <= re) w -= obs_weight(m, k2, m.obs_feat[o2]);
       }
       if (w <= 2) t = re;
     }
   }
   const bool dead = t != RANK_NONE;
-  const int ref = a.ed.mp_ref_kf ? a.ed.mp_ref_kf[p] : -1;
+  const int ref = m.mp_ref_kf ? m.mp_ref_kf[p] : -1;
   int keep = 0, first_k = -1;
   bool ref_lost = false;
   for (int o = o0; o < o1; ++o) {
-    const int k = a.ed.obs_kf[o], f = a.ed.obs_feat[o];
+    const int k = m.obs_kf[o], f = m.obs_feat[o];
     const bool er = a.oflag[o] != 0;
     const int rk = rank_of(k);
     const bool lost = dead || er || rk != RANK_NONE;
     // an erased observation clears its slot; a dying point clears its remaining observers', a removed key-frame's only if it died before
     const bool clear = er || (dead && (rk == RANK_NONE || t < rk));
-    if (clear && k >= 0 && k < NKF && f >= 0 && f < NFK) {
-      int32_t* slot = a.ed.kf_mp + (size_t)k * NFK + f;
+    if (clear && slot_in(m, k, f)) {
+      int32_t* slot = m.kf_mp + (size_t)k * m.NFK + f;
       if (*slot == p) *slot = -1;
     }
     a.oflag[o] = lost ? 1 : 0;
@@ -264,29 +251,29 @@ __global__ __launch_bounds__(T_ME) void k_me_points(EditArgs a) {
     }
   }
   if (dead) {
-    a.ed.mp_valid[p] = 0;
+    m.mp_valid[p] = 0;
     a.pflag[p] = 2;
-    a.cnt[p] = 1ull << 32;
+    a.rb.cnt[p] = 1ull << 32;
   } else {
-    a.cnt[p] = (u64)keep;
-    if (a.ed.mp_ref_kf && ref_lost && keep > 0) a.ed.mp_ref_kf[p] = first_k;
+    a.rb.cnt[p] = (u64)keep;
+    if (m.mp_ref_kf && ref_lost && keep > 0) m.mp_ref_kf[p] = first_k;
   }
 }
 
-// the exclusive scan of cnt inside every tile of SCAN_TILE points, the tile's sum to tile[]
-__global__ __launch_bounds__(SCAN_T) void k_me_scan(EditArgs a) {
+// the exclusive scan of cnt inside every tile of SCAN_TILE words, the tile's sum to tile[] (csr_rebuild_scan)
+__global__ __launch_bounds__(SCAN_T) void k_csr_scan(u64* cnt, u64* tile, const int32_t* n_dev, int n_host) {
   __shared__ u64 s_w[SCAN_T / 64];
-  tile_scan(a.cnt, a.tile, (size_t)a.NMP, s_w, threadIdx.x, blockIdx.x);
+  tile_scan(cnt, tile, n_dev ? (size_t)*n_dev : (size_t)n_host, s_w, threadIdx.x, blockIdx.x);
 }
 
 // one workgroup: the exclusive scan of the tile sums; the totals
 __global__ __launch_bounds__(SCAN_T) void k_me_scan_top(EditArgs a, int ntile) {
   __shared__ u64 s_w[SCAN_T / 64];
   const int tid = threadIdx.x;
-  const u64 carry = tile_scan_top(a.tile, ntile, s_w, tid);
+  const u64 carry = tile_scan_top(a.rb.tile, ntile, s_w, tid);
   if (tid == 0) {
     const int nobs = (int)(unsigned)(carry & 0xffffffffull), ndead = (int)(unsigned)(carry >> 32);
-    a.nptr[a.NMP] = nobs;
+    a.rb.nptr[a.m.NMP] = nobs;
     a.out.result[0] = nobs;
     a.out.result[1] = ndead;
     if (ndead > a.out.dead_cap) atomicOr(a.out.result + 2, GL_MAP_REMOVE_DEAD_TRUNCATED);
@@ -295,25 +282,18 @@ __global__ __launch_bounds__(SCAN_T) void k_me_scan_top(EditArgs a, int ntile) {
 
 __global__ __launch_bounds__(T_ME) void k_me_move(EditArgs a) {
   const int p = blockIdx.x * T_ME + threadIdx.x;
-  if (p >= a.NMP) return;
-  const u64 at = a.cnt[p] + a.tile[p / SCAN_TILE];
-  int to = (int)(unsigned)(at & 0xffffffffull);
-  const int di = (int)(unsigned)(at >> 32);
-  a.nptr[p] = to;
+  if (p >= a.m.NMP) return;
+  const int di = (int)(unsigned)(csr_place(a.rb, p) >> 32);
   if (a.pflag[p] == 2 && di < a.out.dead_cap) a.out.dead_mp[di] = p;
-  const int r0 = a.ed.obs_ptr[p], r1 = a.ed.obs_ptr[p + 1];
-  if (!(r0 >= 0 && r1 >= r0 && r1 <= a.NOBS)) return;
-  for (int o = r0; o < r1; ++o) {
-    if (a.oflag[o]) continue;  // (its obs_new_pos stays -1)
-    if (to >= a.NOBS) break;   // (overlapping ranges of a malformed CSR: never behind the arrays)
-    a.ed.obs_kf[to] = a.okf[o];
-    a.ed.obs_feat[to] = a.ofeat[o];
-    if (a.out.obs_new_pos) a.out.obs_new_pos[o] = to;
-    ++to;
-  }
+  // (a removal only compacts: the limit is NOBS)
+  csr_move_point(a.m, a.rb, p, a.m.NOBS, a.out.obs_new_pos, [&](int o) { return !a.oflag[o]; }, [](auto&) {});
 }
 
 }  // namespace
+
+void gl::mapdev::csr_rebuild_scan(gl::Ctx* c, const CsrRebuild& rb, int ntile, const int32_t* n_dev, int n_host) {
+  if (ntile > 0) k_csr_scan<<<ntile, SCAN_T, 0, c->stream>>>(rb.cnt, rb.tile, n_dev, n_host);
+}
 
 extern "C" int gl_cull_keyframes(gl_ctx_t* ctx, const gl_map_view* map, const gl_map_ba_view* ba, const float* kf_depth_dev, float th_depth, int B,
                                  int Ccap, const int32_t* cand_kf_dev, const int32_t* n_cand_dev, uint8_t* cull_dev, int32_t* num_mps_dev,
@@ -321,20 +301,16 @@ extern "C" int gl_cull_keyframes(gl_ctx_t* ctx, const gl_map_view* map, const gl
   GL_REQUIRE(ctx && map && ba, "null argument");
   GL_REQUIRE(B >= 0 && Ccap >= 1, "bad B / Ccap");
   if (B == 0) return GL_OK;
-  GL_REQUIRE(map->NMP >= 0 && map->NKF >= 0 && map->NFK >= 0 && map->NOBS >= 0, "bad NMP / NKF / NFK / NOBS");
-  GL_REQUIRE((int64_t)map->NKF * map->NFK < ((int64_t)1 << 31), "NKF x NFK must be below 2^31");
+  CullArgs a;
+  const int rc = map_from_view(__func__, map, ba, &a.m);
+  if (rc != GL_OK) return rc;
   GL_REQUIRE(map->NKF <= GL_CULL_MAX_KF, "more than GL_CULL_MAX_KF key-frames");
-  GL_REQUIRE(map->obs_ptr, "null obs_ptr");
-  GL_REQUIRE(map->NOBS == 0 || (map->obs_kf && ba->obs_feat), "null obs_kf / obs_feat");
-  GL_REQUIRE(map->NKF == 0 || map->NFK == 0 || (map->kf_mp && ba->kf_uvr && ba->kf_oct && kf_depth_dev), "null kf_mp / kf_uvr / kf_oct / kf_depth");
+  GL_REQUIRE(map->NKF == 0 || map->NFK == 0 || kf_depth_dev, "null kf_depth");
   GL_REQUIRE(cand_kf_dev && n_cand_dev && cull_dev && num_mps_dev && num_redundant_dev && cand_status_dev && cull_rows_dev && n_cull_dev, "null buffer");
   gl::Ctx* c = gl::C(ctx);
   GL_HIP(hipSetDevice(c->device));
   const size_t lds = (size_t)((map->NKF + 31) / 32) * 2 * 4;
   GL_REQUIRE_LDS(c, lds + 256);
-  CullArgs a;
-  a.m = *map;
-  a.ba = *ba;
   a.kf_depth = kf_depth_dev;
   a.th_depth = th_depth;
   a.B = B;
@@ -356,65 +332,46 @@ extern "C" int gl_cull_keyframes(gl_ctx_t* ctx, const gl_map_view* map, const gl
 extern "C" int gl_map_remove(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, const gl_map_edit* ed, const double* kf_uvr_dev, int kf_first,
                              const gl_map_remove_lists* lists, const gl_map_remove_out* out) {
   GL_REQUIRE(ctx && ed && lists && out, "null argument");
-  GL_REQUIRE(NMP >= 0 && NKF >= 0 && NFK >= 0 && NOBS >= 0, "bad NMP / NKF / NFK / NOBS");
-  GL_REQUIRE((int64_t)NKF * NFK < ((int64_t)1 << 31), "NKF x NFK must be below 2^31");
-  GL_REQUIRE(ed->obs_ptr, "null obs_ptr");
-  GL_REQUIRE(NMP == 0 || ed->mp_valid, "null mp_valid");
+  EditArgs a = {};
+  const int rc = map_from_edit(__func__, NMP, NKF, NFK, NOBS, ed, kf_uvr_dev, kf_first, &a.m);
+  if (rc != GL_OK) return rc;
   GL_REQUIRE(NKF == 0 || ed->kf_valid, "null kf_valid");
-  GL_REQUIRE(NKF == 0 || NFK == 0 || (ed->kf_mp && kf_uvr_dev), "null kf_mp / kf_uvr");
-  GL_REQUIRE(NOBS == 0 || (ed->obs_kf && ed->obs_feat), "null obs_kf / obs_feat");
+  GL_REQUIRE(NKF == 0 || NFK == 0 || kf_uvr_dev, "null kf_uvr");
   GL_REQUIRE(lists->rm_mp_cap >= 0 && lists->erase_cap >= 0 && lists->rm_kf_cap >= 0, "bad list capacity");
   GL_REQUIRE(out->result, "null result");
   GL_REQUIRE(out->dead_cap >= 0 && (out->dead_cap == 0 || out->dead_mp), "bad dead_cap / null dead_mp");
   gl::Ctx* c = gl::C(ctx);
   GL_HIP(hipSetDevice(c->device));
-  EditArgs a = {};
-  a.NMP = NMP;
-  a.NKF = NKF;
-  a.NFK = NFK;
-  a.NOBS = NOBS;
-  a.ed = *ed;
-  a.kf_uvr = kf_uvr_dev;
-  a.kf_first = kf_first;
   a.l = *lists;
   a.out = *out;
   if (!a.l.rm_mp || a.l.rm_mp_cap == 0) a.l.rm_mp = nullptr, a.l.rm_mp_cap = 0;
   if (!a.l.erase_obs || a.l.erase_cap == 0) a.l.erase_obs = nullptr, a.l.erase_cap = 0;
   if (!a.l.rm_kf || a.l.rm_kf_cap == 0) a.l.rm_kf = nullptr, a.l.rm_kf_cap = 0;
   GL_HIP(hipMemsetAsync(out->result, 0, 3 * sizeof(int32_t), c->stream));
-  const int ntile = (NMP + SCAN_TILE - 1) / SCAN_TILE;
+  const int ntile = csr_tiles(NMP);
   gl::Regions r = {0};
   // rank first, the flags next to each other: two memsets reset them
   const size_t o_rank = r.take((size_t)NKF * 4), o_pflag = r.take((size_t)NMP), o_oflag = r.take((size_t)NOBS), flags_end = r.off;
-  const size_t o_cnt = r.take((size_t)NMP * 8), o_tile = r.take((size_t)ntile * 8), o_okf = r.take((size_t)NOBS * 4), o_ofeat = r.take((size_t)NOBS * 4),
-               o_nptr = r.take(((size_t)NMP + 1) * 4);
   void* scratch = nullptr;
-  const int rs = gl::ctx_scratch(c, r.off, &scratch, gl::SCRATCH_MAPEDIT);
+  const int rs = gl::ctx_scratch(c, flags_end + csr_rebuild_place(nullptr, NMP, NOBS, nullptr), &scratch, gl::SCRATCH_MAPEDIT);
   if (rs != GL_OK) return rs;
   char* s = (char*)scratch;
   a.rank = (int32_t*)(s + o_rank);
   a.pflag = (uint8_t*)(s + o_pflag);
   a.oflag = (uint8_t*)(s + o_oflag);
-  a.cnt = (u64*)(s + o_cnt);
-  a.tile = (u64*)(s + o_tile);
-  a.okf = (int32_t*)(s + o_okf);
-  a.ofeat = (int32_t*)(s + o_ofeat);
-  a.nptr = (int32_t*)(s + o_nptr);
+  csr_rebuild_place(s + flags_end, NMP, NOBS, &a.rb);
   if (NKF > 0) GL_HIP(hipMemsetAsync(a.rank, 0x7f, (size_t)NKF * 4, c->stream));
   if (flags_end > o_pflag) GL_HIP(hipMemsetAsync(a.pflag, 0, flags_end - o_pflag, c->stream));
-  if (NOBS > 0) {
-    GL_HIP(hipMemcpyAsync(a.okf, ed->obs_kf, (size_t)NOBS * 4, hipMemcpyDeviceToDevice, c->stream));
-    GL_HIP(hipMemcpyAsync(a.ofeat, ed->obs_feat, (size_t)NOBS * 4, hipMemcpyDeviceToDevice, c->stream));
-    if (out->obs_new_pos) GL_HIP(hipMemsetAsync(out->obs_new_pos, 0xff, (size_t)NOBS * 4, c->stream));
-  }
+  const int rb = csr_rebuild_begin(c, a.rb, a.m, out->obs_new_pos);
+  if (rb != GL_OK) return rb;
   const int nlist = std::max(a.l.rm_mp_cap, std::max(a.l.erase_cap, a.l.rm_kf_cap));
   if (nlist > 0) k_me_mark<<<std::min((nlist + T_ME - 1) / T_ME, 1024), T_ME, 0, c->stream>>>(a);
   const int nrow = std::max(NMP, NKF);
   if (nrow > 0) k_me_points<<<(nrow + T_ME - 1) / T_ME, T_ME, 0, c->stream>>>(a);
-  if (ntile > 0) k_me_scan<<<ntile, SCAN_T, 0, c->stream>>>(a);
+  csr_rebuild_scan(c, a.rb, ntile, nullptr, NMP);
   k_me_scan_top<<<1, SCAN_T, 0, c->stream>>>(a, ntile);
   if (NMP > 0) k_me_move<<<(NMP + T_ME - 1) / T_ME, T_ME, 0, c->stream>>>(a);
   GL_HIP(hipGetLastError());
-  GL_HIP(hipMemcpyAsync(ed->obs_ptr, a.nptr, ((size_t)NMP + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
+  GL_HIP(hipMemcpyAsync(ed->obs_ptr, a.rb.nptr, ((size_t)NMP + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
   return GL_OK;
 }

@@ -917,7 +917,8 @@ int gl_map_remove(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, const gl_m
  * parallel over src's and tgt's entries.  The walk never edits the CSR: its state (a word per point, a chain of gained entries per
  * point in a log of NOBS + n_cand nodes, a flag per old entry, a stamp per key-frame) lives in the context's scratch, set and reset by
  * the call; one parallel rebuild (count, device-wide scan, stable move through a copy) writes obs_ptr / obs_kf / obs_feat.  The cost
- * follows the map plus the steps.
+ * follows the map plus the steps.  The map is taken as consistent; where CSR ranges overlap nothing is written at or behind OBScap, and
+ * a point whose CSR range is not inside [0, NOBS] has only its gained entries afterwards.
  * Both: integer stores and integer atomics only - the bytes do not depend on scheduling; asynchronous on the context's stream,
  * stateless, no host synchronise.  obs_kf / obs_feat behind the new NOBS are not written.  Map fields read / written:
  *   call        | reads                                                    | writes

@@ -87,6 +87,19 @@ class gl_temporal_points_out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("temp_flag", "n_temp", "last_pt", "last_observed", "last_valid", "last_desc", "stats")]
 
 
+class gl_map_kf_tables(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("kf_angle", "kf_desc", "kf_depth", "kf_nnode", "kf_node_id", "kf_node_ptr", "kf_node_idx", "kf_cand",
+                                           "kf_ncand")] + [("NNcap", C.c_int32), ("k", C.c_int32)])
+
+
+TRI_POINTS_ARRAYS = ("new_pos", "new_assoc", "new_ref_kf", "new_type", "new_nb", "new_feat1", "new_feat2", "att_mp", "att_kf", "att_feat", "n_new",
+                     "n_attach", "feat_new", "nb_stats", "fmat", "epipole", "status")
+
+
+class gl_tri_points_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in TRI_POINTS_ARRAYS] + [("new_cap", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class gl_ba_window(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("Pcap", "Fcap", "Lcap", "Ocap")] + [(k, C.c_void_p) for k in BA_WINDOW_ARRAYS])
 
@@ -168,6 +181,9 @@ def load():
         "gl_check_map_association": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32] + [vp] * 6 + [i32, vp]),
         "gl_optimize_triangulation": (i32, [vp, vp, P(gl_camera), P(gl_params), i32] + [vp] * 11 + [i32, vp]),
         "gl_create_map_points": (i32, [vp, vp, P(gl_camera), P(gl_params), C.c_float, i32] + [vp] * 12 + [i32, vp, vp, vp]),
+        "gl_tri_pair_setup": (i32, [vp, P(gl_camera), i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]),
+        "gl_create_map_points_from_map": (i32, [vp, vp, P(gl_camera), P(gl_params), C.c_float, vp, vp, vp, i32, vp, vp, i32, i32, i32, C.c_float,
+                                                i32, vp]),
         "gl_create_stereo_points": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, vp, i32, i32, C.c_float, vp]),
         "gl_create_temporal_points": (i32, [vp, P(gl_camera), i32, i32, vp, C.c_float, vp]),
         "gl_optimize_current_pose": (i32, [vp, P(gl_camera), P(gl_params), i32, i32, vp, vp, vp, vp, vp, vp]),

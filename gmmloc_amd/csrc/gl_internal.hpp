@@ -159,6 +159,8 @@ enum {
   SCRATCH_BAWINDOW,  // gl_update_connections / gl_ba_window_build / _apply: per-window words over the map's rows and the window's lists
   SCRATCH_MAPEDIT,   // gl_map_remove, gl_map_add, gl_map_fuse: each call's marks over the map's rows and its lists, then the rebuild of the
                      // CSR (mapdev::CsrRebuild, gl_map_dev.hpp): the scan words and the copy of the CSR it moves from
+  SCRATCH_MAPTRI,    // gl_create_map_points_from_map: the pair set-up, the gathered pair tables, the mask and the per-match arrays that its
+                     // stages (which use the main block and the cache) hand to one another
   SCRATCH_COUNT
 };
 
@@ -338,6 +340,22 @@ int local_map_gather_launch(Ctx* c, const gl_map_view* map, int B, int NL, int N
 int launch_check_map_association(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int N, const double* pose_dev,
                                  double* pts_dev, const double* uvr_dev, const int32_t* octave_dev, const int32_t* cand_dev,
                                  const int32_t* ncand_dev, int k, int32_t* out_comp_dev);
+// (gl_match_tri.hip) k_search_for_triangulation, arguments as gl_search_for_triangulation's and already checked
+int launch_search_for_triangulation(Ctx* c, float scale_factor, int B, int N1, int N2, int NN1, int NN2, const double* uv1_dev,
+                                    const float* ur1_dev, const int32_t* oct1_dev, const float* angle1_dev, const uint8_t* desc1_dev,
+                                    const uint8_t* has_mp1_dev, const int32_t* nnode1_dev, const int32_t* node_id1_dev,
+                                    const int32_t* node_ptr1_dev, const int32_t* node_idx1_dev, const double* uv2_dev, const float* ur2_dev,
+                                    const int32_t* oct2_dev, const float* angle2_dev, const uint8_t* desc2_dev, const uint8_t* has_mp2_dev,
+                                    const int32_t* nnode2_dev, const int32_t* node_id2_dev, const int32_t* node_ptr2_dev,
+                                    const int32_t* node_idx2_dev, const double* fmat_dev, const float* epipole_dev, int only_stereo,
+                                    int check_orientation, int32_t* match12_dev, int32_t* nmatches_dev);
+// (gl_point.hip) the three kernels of gl_create_map_points on a scratch region of the caller's
+size_t create_map_points_scratch_bytes(int N);
+int launch_create_map_points(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, float scale_factor, int N,
+                             const double* pose1_dev, const double* uvr1_dev, const float* depth1_dev, const int32_t* oct1_dev,
+                             const double* pose2_dev, const double* uvr2_dev, const float* depth2_dev, const int32_t* oct2_dev,
+                             const int32_t* cand1_dev, const int32_t* n1_dev, const int32_t* cand2_dev, const int32_t* n2_dev, int k,
+                             double* x3d_dev, int32_t* type_dev, int32_t* comp_dev, void* scratch);
 // association launchers (gl_assoc.hip: all-pairs sweep; gl_grid.hip: cell index + sweep of the rest)
 int launch_assoc_brute(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2);
 int launch_assoc_sweep(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,

@@ -382,25 +382,16 @@ extern "C" int gl_gather_triangulation_matches(gl_ctx_t* ctx, int B, int N1, int
   return GL_OK;
 }
 
-extern "C" int gl_search_for_triangulation(gl_ctx_t* ctx, float scale_factor, int B, int N1, int N2, int NN1, int NN2,
-                                           const double* uv1_dev, const float* ur1_dev, const int32_t* oct1_dev, const float* angle1_dev,
-                                           const uint8_t* desc1_dev, const uint8_t* has_mp1_dev, const int32_t* nnode1_dev,
-                                           const int32_t* node_id1_dev, const int32_t* node_ptr1_dev, const int32_t* node_idx1_dev,
-                                           const double* uv2_dev, const float* ur2_dev, const int32_t* oct2_dev, const float* angle2_dev,
-                                           const uint8_t* desc2_dev, const uint8_t* has_mp2_dev, const int32_t* nnode2_dev,
-                                           const int32_t* node_id2_dev, const int32_t* node_ptr2_dev, const int32_t* node_idx2_dev,
-                                           const double* fmat_dev, const float* epipole_dev, int only_stereo, int check_orientation,
-                                           int32_t* match12_dev, int32_t* nmatches_dev) {
-  GL_REQUIRE(ctx, "null context");
-  if (B == 0) return GL_OK;
-  GL_REQUIRE(B > 0 && N1 >= 1 && N2 >= 1 && NN1 >= 1 && NN2 >= 1, "bad B / N1 / N2 / NN1 / NN2");
-  GL_REQUIRE(N1 <= 4096 && N2 <= 4096, "N1 / N2 above the on-chip capacity (4096 features per key-frame)");
-  GL_REQUIRE(uv1_dev && ur1_dev && oct1_dev && angle1_dev && desc1_dev && has_mp1_dev && nnode1_dev && node_id1_dev && node_ptr1_dev &&
-                 node_idx1_dev && uv2_dev && ur2_dev && oct2_dev && angle2_dev && desc2_dev && has_mp2_dev && nnode2_dev && node_id2_dev &&
-                 node_ptr2_dev && node_idx2_dev && fmat_dev && epipole_dev && match12_dev && nmatches_dev,
-             "null buffer");
-  gl::Ctx* c = gl::C(ctx);
-  GL_HIP(hipSetDevice(c->device));
+// k_search_for_triangulation for the callers inside the library (gl_map_tri.hip): arguments as gl_search_for_triangulation's and
+// already checked, the context's device current.  The round cache is the launcher's own (SCRATCH_CACHE).
+int gl::launch_search_for_triangulation(Ctx* c, float scale_factor, int B, int N1, int N2, int NN1, int NN2, const double* uv1_dev,
+                                        const float* ur1_dev, const int32_t* oct1_dev, const float* angle1_dev, const uint8_t* desc1_dev,
+                                        const uint8_t* has_mp1_dev, const int32_t* nnode1_dev, const int32_t* node_id1_dev,
+                                        const int32_t* node_ptr1_dev, const int32_t* node_idx1_dev, const double* uv2_dev, const float* ur2_dev,
+                                        const int32_t* oct2_dev, const float* angle2_dev, const uint8_t* desc2_dev, const uint8_t* has_mp2_dev,
+                                        const int32_t* nnode2_dev, const int32_t* node_id2_dev, const int32_t* node_ptr2_dev,
+                                        const int32_t* node_idx2_dev, const double* fmat_dev, const float* epipole_dev, int only_stereo,
+                                        int check_orientation, int32_t* match12_dev, int32_t* nmatches_dev) {
   TriP P;
   P.N1 = N1;
   P.N2 = N2;
@@ -423,4 +414,29 @@ extern "C" int gl_search_for_triangulation(gl_ctx_t* ctx, float scale_factor, in
                                                         epipole_dev, match12_dev, nmatches_dev, c->counters, (uint4*)cache);
   GL_HIP(hipGetLastError());
   return GL_OK;
+}
+
+extern "C" int gl_search_for_triangulation(gl_ctx_t* ctx, float scale_factor, int B, int N1, int N2, int NN1, int NN2,
+                                           const double* uv1_dev, const float* ur1_dev, const int32_t* oct1_dev, const float* angle1_dev,
+                                           const uint8_t* desc1_dev, const uint8_t* has_mp1_dev, const int32_t* nnode1_dev,
+                                           const int32_t* node_id1_dev, const int32_t* node_ptr1_dev, const int32_t* node_idx1_dev,
+                                           const double* uv2_dev, const float* ur2_dev, const int32_t* oct2_dev, const float* angle2_dev,
+                                           const uint8_t* desc2_dev, const uint8_t* has_mp2_dev, const int32_t* nnode2_dev,
+                                           const int32_t* node_id2_dev, const int32_t* node_ptr2_dev, const int32_t* node_idx2_dev,
+                                           const double* fmat_dev, const float* epipole_dev, int only_stereo, int check_orientation,
+                                           int32_t* match12_dev, int32_t* nmatches_dev) {
+  GL_REQUIRE(ctx, "null context");
+  if (B == 0) return GL_OK;
+  GL_REQUIRE(B > 0 && N1 >= 1 && N2 >= 1 && NN1 >= 1 && NN2 >= 1, "bad B / N1 / N2 / NN1 / NN2");
+  GL_REQUIRE(N1 <= 4096 && N2 <= 4096, "N1 / N2 above the on-chip capacity (4096 features per key-frame)");
+  GL_REQUIRE(uv1_dev && ur1_dev && oct1_dev && angle1_dev && desc1_dev && has_mp1_dev && nnode1_dev && node_id1_dev && node_ptr1_dev &&
+                 node_idx1_dev && uv2_dev && ur2_dev && oct2_dev && angle2_dev && desc2_dev && has_mp2_dev && nnode2_dev && node_id2_dev &&
+                 node_ptr2_dev && node_idx2_dev && fmat_dev && epipole_dev && match12_dev && nmatches_dev,
+             "null buffer");
+  gl::Ctx* c = gl::C(ctx);
+  GL_HIP(hipSetDevice(c->device));
+  return gl::launch_search_for_triangulation(c, scale_factor, B, N1, N2, NN1, NN2, uv1_dev, ur1_dev, oct1_dev, angle1_dev, desc1_dev, has_mp1_dev,
+                                             nnode1_dev, node_id1_dev, node_ptr1_dev, node_idx1_dev, uv2_dev, ur2_dev, oct2_dev, angle2_dev,
+                                             desc2_dev, has_mp2_dev, nnode2_dev, node_id2_dev, node_ptr2_dev, node_idx2_dev, fmat_dev, epipole_dev,
+                                             only_stereo, check_orientation, match12_dev, nmatches_dev);
 }

@@ -649,6 +649,48 @@ int gl::launch_check_map_association(Ctx* c, const Gmm* g, const gl_camera* cam,
   return GL_OK;
 }
 
+// the three kernels of gl_create_map_points for the callers inside the library (gl_map_tri.hip): arguments as gl_create_map_points' and
+// already checked, the context's device current; `scratch`: create_map_points_scratch_bytes(N) bytes, written before they are read
+size_t gl::create_map_points_scratch_bytes(int N) { return (size_t)N * (2 * 24 + 4) + 64; }
+int gl::launch_create_map_points(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, float scale_factor, int N,
+                                 const double* pose1_dev, const double* uvr1_dev, const float* depth1_dev, const int32_t* oct1_dev,
+                                 const double* pose2_dev, const double* uvr2_dev, const float* depth2_dev, const int32_t* oct2_dev,
+                                 const int32_t* cand1_dev, const int32_t* n1_dev, const int32_t* cand2_dev, const int32_t* n2_dev, int k,
+                                 double* x3d_dev, int32_t* type_dev, int32_t* comp_dev, void* scratch) {
+  double* b1 = (double*)scratch;
+  double* b2 = b1 + (size_t)N * 3;
+  int32_t* stage = (int32_t*)(b2 + (size_t)N * 3);
+  TriK t;
+  t.fx = cam->fx;
+  t.fy = cam->fy;
+  t.cx = cam->cx;
+  t.cy = cam->cy;
+  t.ffx = (float)cam->fx;
+  t.ffy = (float)cam->fy;
+  t.fcx = (float)cam->cx;
+  t.fcy = (float)cam->cy;
+  t.invfx = 1.0f / t.ffx;
+  t.invfy = 1.0f / t.ffy;
+  t.mbf = (float)cam->bf;
+  t.mb = t.mbf / t.ffx;
+  t.ratio_factor = 1.5f * scale_factor;
+  gl_match::pyramid_scales(scale_factor, t.sf, t.sigma2, nullptr);
+  t.width = cam->width;
+  t.height = cam->height;
+  const int grid = (N + 63) / 64;
+  k_tri_pre<<<grid, 64, 0, c->stream>>>(t, N, pose1_dev, uvr1_dev, depth1_dev, pose2_dev, uvr2_dev, depth2_dev, x3d_dev, stage,
+                                        b1, b2);
+  GL_HIP(hipGetLastError());
+  k_optimize_triangulation<<<(int)(((size_t)N * TRI_LANES + 255) / 256), 256, 0, c->stream>>>(make_ptk(cam, prm), N, g->rec12, g->axis, g->flags, x3d_dev, pose1_dev,
+                                                       b1, oct1_dev, pose2_dev, b2, cand1_dev, n1_dev, cand2_dev, n2_dev, k,
+                                                       comp_dev);
+  GL_HIP(hipGetLastError());
+  k_tri_post<<<grid, 64, 0, c->stream>>>(t, N, pose1_dev, uvr1_dev, oct1_dev, pose2_dev, uvr2_dev, oct2_dev, stage, x3d_dev,
+                                         comp_dev, type_dev);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
 extern "C" {
 
 int gl_optimize_point(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm, int N,
@@ -721,43 +763,12 @@ int gl_create_map_points(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* ca
                  cand1_dev && n1_dev && cand2_dev && n2_dev && x3d_dev && type_dev && comp_dev,
              "null buffer");
   gl::Ctx* c = gl::C(ctx);
-  gl::Gmm* g = gl::G(gmm);
   GL_HIP(hipSetDevice(c->device));
   void* scratch = nullptr;
-  int rc = gl::ctx_scratch(c, (size_t)N * (2 * 24 + 4) + 64, &scratch);
+  int rc = gl::ctx_scratch(c, gl::create_map_points_scratch_bytes(N), &scratch);
   if (rc != GL_OK) return rc;
-  double* b1 = (double*)scratch;
-  double* b2 = b1 + (size_t)N * 3;
-  int32_t* stage = (int32_t*)(b2 + (size_t)N * 3);
-  TriK t;
-  t.fx = cam->fx;
-  t.fy = cam->fy;
-  t.cx = cam->cx;
-  t.cy = cam->cy;
-  t.ffx = (float)cam->fx;
-  t.ffy = (float)cam->fy;
-  t.fcx = (float)cam->cx;
-  t.fcy = (float)cam->cy;
-  t.invfx = 1.0f / t.ffx;
-  t.invfy = 1.0f / t.ffy;
-  t.mbf = (float)cam->bf;
-  t.mb = t.mbf / t.ffx;
-  t.ratio_factor = 1.5f * scale_factor;
-  gl_match::pyramid_scales(scale_factor, t.sf, t.sigma2, nullptr);
-  t.width = cam->width;
-  t.height = cam->height;
-  const int grid = (N + 63) / 64;
-  k_tri_pre<<<grid, 64, 0, c->stream>>>(t, N, pose1_dev, uvr1_dev, depth1_dev, pose2_dev, uvr2_dev, depth2_dev, x3d_dev, stage,
-                                        b1, b2);
-  GL_HIP(hipGetLastError());
-  k_optimize_triangulation<<<(int)(((size_t)N * TRI_LANES + 255) / 256), 256, 0, c->stream>>>(make_ptk(cam, prm), N, g->rec12, g->axis, g->flags, x3d_dev, pose1_dev,
-                                                       b1, oct1_dev, pose2_dev, b2, cand1_dev, n1_dev, cand2_dev, n2_dev, k,
-                                                       comp_dev);
-  GL_HIP(hipGetLastError());
-  k_tri_post<<<grid, 64, 0, c->stream>>>(t, N, pose1_dev, uvr1_dev, oct1_dev, pose2_dev, uvr2_dev, oct2_dev, stage, x3d_dev,
-                                         comp_dev, type_dev);
-  GL_HIP(hipGetLastError());
-  return GL_OK;
+  return gl::launch_create_map_points(c, gl::G(gmm), cam, prm, scale_factor, N, pose1_dev, uvr1_dev, depth1_dev, oct1_dev, pose2_dev, uvr2_dev,
+                                      depth2_dev, oct2_dev, cand1_dev, n1_dev, cand2_dev, n2_dev, k, x3d_dev, type_dev, comp_dev, scratch);
 }
 
 }  // extern "C"

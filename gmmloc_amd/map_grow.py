@@ -254,3 +254,155 @@ def process_key_frame_from_map(ctx, gmm, cam, prm, map, ba, kf_tables, kf_row, f
                           what=3, scale_factor=scale_factor)
     r.update(cand=cand[0], ncand=ncand[0], feat_new=s["feat_new"][0], stats=s["stats"][0], n_new=n_new)
     return r
+
+
+# ---- createMapPoints on the resident map (gl_tri_pair_setup, gl_create_map_points_from_map; rules in include/gmmloc_hip.h) -----------
+TRI_NB_MAX = 16
+TRI_SKIP_BEYOND, TRI_SKIP_BAD_ROW, TRI_SKIP_SELF, TRI_SKIP_INVALID, TRI_SKIP_REPEATED, TRI_SKIP_BASELINE = 1, 2, 4, 8, 16, 32
+TRI_NONE_SEARCHED = 1
+KF_TABLE_DTYPES = {"angle": "float32", "desc": "uint8", "depth": "float32", "nnode": "int32", "node_id": "int32", "node_ptr": "int32",
+                   "node_idx": "int32", "cand": "int32", "ncand": "int32"}
+
+
+def default_mb(cam):
+    """Frame::mb = mbf / fx in float (frame.cpp:24)"""
+    import numpy as np
+    return float(np.float32(cam.bf) / np.float32(cam.fx))
+
+
+def _kf_tables(kf_tables, rows, NFK, dev):
+    """dict of CUDA tensors (keys of KF_TABLE_DTYPES, `rows` key-frame rows each) -> gl_map_kf_tables"""
+    for key in kf_tables:
+        assert key in KF_TABLE_DTYPES, "kf_tables[%r]: unknown key" % key
+    NNcap = _tensor("kf_tables['node_id']", kf_tables.get("node_id"), "int32", (rows, None), dev).shape[1]
+    k = _tensor("kf_tables['cand']", kf_tables.get("cand"), "int32", (rows, NFK, None), dev).shape[2]
+    shapes = {"angle": (rows, NFK), "desc": (rows, NFK, 32), "depth": (rows, NFK), "nnode": (rows,), "node_id": (rows, NNcap),
+              "node_ptr": (rows, NNcap + 1), "node_idx": (rows, NFK), "cand": (rows, NFK, k), "ncand": (rows, NFK)}
+    t = _lib.gl_map_kf_tables()
+    for key, dt in KF_TABLE_DTYPES.items():
+        setattr(t, "kf_" + key, _ptr(_tensor("kf_tables[%r]" % key, kf_tables.get(key), dt, shapes[key], dev)))
+    t.NNcap, t.k = NNcap, k
+    return t
+
+
+def _conn(conn_kf, n_conn, dev):
+    _tensor("conn_kf", conn_kf, "int32", (None,), dev)
+    assert n_conn.is_cuda and n_conn.device == dev and str(n_conn.dtype) == "torch.int32" and n_conn.numel() == 1, "n_conn: one int32 on the device"
+    return conn_kf.shape[0]
+
+
+def tri_pair_setup(ctx, cam, ba, kf_valid, kf_row, conn_kf, n_conn, first_nb=0, n_nb=None, mb=None):
+    """gl_tri_pair_setup: per neighbour conn_kf[first_nb + j] of key-frame row kf_row the skip bits (TRI_SKIP_*), the fundamental matrix
+    and the epipole createMapPoints / searchForTriangulation compute before the search.  ba: kf_pose (NKF,7), kf_twc (NKF,3); kf_valid
+    (NKF,) u8 or None; conn_kf (Ccap,) i32 and n_conn (1,) i32 on the device (a row of update_connections' outputs).
+    -> (skip (n_nb,) i32, fmat (n_nb,9) f64, epipole (n_nb,2) f32)."""
+    import torch
+    dev = _tensor("ba['kf_pose']", ba.get("kf_pose"), "float64", (None, 7), None).device
+    NKF = ba["kf_pose"].shape[0]
+    _tensor("ba['kf_twc']", ba.get("kf_twc"), "float64", (NKF, 3), dev)
+    if kf_valid is not None:
+        _tensor("kf_valid", kf_valid, "uint8", (NKF,), dev)
+    cap = _conn(conn_kf, n_conn, dev)
+    n_nb = min(cap, TRI_NB_MAX) if n_nb is None else int(n_nb)
+    skip = torch.zeros(n_nb, dtype=torch.int32, device=dev)
+    fmat = torch.zeros((n_nb, 9), dtype=torch.float64, device=dev)
+    epi = torch.zeros((n_nb, 2), dtype=torch.float32, device=dev)
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_tri_pair_setup(ctx.h, C.byref(cam.c()), NKF, _ptr(kf_valid), _ptr(ba["kf_pose"]), _ptr(ba["kf_twc"]), int(kf_row),
+                                         _ptr(conn_kf), _ptr(n_conn), cap, int(first_nb), n_nb, default_mb(cam) if mb is None else float(mb),
+                                         _ptr(skip), _ptr(fmat), _ptr(epi)))
+    finally:
+        ctx._exit()
+    return skip, fmat, epi
+
+
+def tri_points_out(NFK, n_nb, new_cap=None, device="cuda"):
+    """the output arrays of create_map_points_on_map, zeroed: the lists of new_cap (default NFK) rows, att_* twice as many"""
+    import torch
+    cap = NFK if new_cap is None else int(new_cap)
+    z = lambda *sh: torch.zeros(sh, dtype=torch.int32, device=device)
+    return dict(new_pos=torch.zeros((cap, 3), dtype=torch.float64, device=device), new_assoc=z(cap), new_ref_kf=z(cap), new_type=z(cap), new_nb=z(cap),
+                new_feat1=z(cap), new_feat2=z(cap), att_mp=z(2 * cap), att_kf=z(2 * cap), att_feat=z(2 * cap), n_new=z(1), n_attach=z(1),
+                feat_new=z(NFK), nb_stats=z(n_nb, 8), fmat=torch.zeros((n_nb, 9), dtype=torch.float64, device=device),
+                epipole=torch.zeros((n_nb, 2), dtype=torch.float32, device=device), status=z(1))
+
+
+def create_map_points_on_map(ctx, gmm, cam, prm, map, ba, kf_tables, kf_row, conn_kf, n_conn, first_nb=0, n_nb=None, mb=None, mp_base=None,
+                             scale_factor=1.2, out=None):
+    """gl_create_map_points_from_map alone: the loop of Localization::createMapPoints for key-frame row kf_row over the neighbours
+    conn_kf[first_nb .. first_nb + n_nb) - the map is NOT written, nothing is read back.  map / ba: the dicts of api.update_connections /
+    api.ba_window_build cut to the map's sizes (kf_valid, kf_mp; kf_pose, kf_twc, kf_uvr, kf_oct); kf_tables: dict of KF_TABLE_DTYPES'
+    keys, one row per key-frame row of map['kf_mp'].  mp_base: the row the first new point will take (default: the map's NMP).
+    -> the dict of tri_points_out (device tensors; the lists are valid up to n_new / n_attach)."""
+    from .api import _map_ba_view, _map_view
+    v, dev = _map_view(map, False)
+    w = _map_ba_view(ba, v, dev, need=("kf_pose", "kf_twc", "kf_uvr", "kf_oct"))
+    assert ba.get("kf_twc") is not None, "ba['kf_twc']: missing"
+    t = _kf_tables(kf_tables, v.NKF, v.NFK, dev)
+    cap = _conn(conn_kf, n_conn, dev)
+    n_nb = min(cap, TRI_NB_MAX) if n_nb is None else int(n_nb)
+    if out is None:
+        out = tri_points_out(v.NFK, n_nb, device=dev)
+    o = _lib.gl_tri_points_out()
+    shapes = {"new_pos": (None, 3), "fmat": (n_nb, 9), "epipole": (n_nb, 2), "nb_stats": (n_nb, 8), "feat_new": (v.NFK,), "n_new": (1,),
+              "n_attach": (1,), "status": (1,)}
+    for key in _lib.TRI_POINTS_ARRAYS:
+        dt = "float64" if key in ("new_pos", "fmat") else "float32" if key == "epipole" else "int32"
+        if out.get(key) is None and key in ("fmat", "epipole"):
+            continue
+        setattr(o, key, _ptr(_tensor("out[%r]" % key, out.get(key), dt, shapes.get(key, (None,)), dev)))
+    o.new_cap = out["new_pos"].shape[0]
+    for key in ("new_assoc", "new_ref_kf", "new_type", "new_nb", "new_feat1", "new_feat2"):
+        assert out[key].shape[0] == o.new_cap, "out[%r]: %d rows, new_pos has %d" % (key, out[key].shape[0], o.new_cap)
+    for key in ("att_mp", "att_kf", "att_feat"):
+        assert out[key].shape[0] == 2 * o.new_cap, "out[%r]: needs 2 x %d entries" % (key, o.new_cap)
+    ctx._enter()
+    try:
+        _check(ctx.lib.gl_create_map_points_from_map(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), C.byref(v), C.byref(w),
+                                                     C.byref(t), int(kf_row), _ptr(conn_kf), _ptr(n_conn), cap, int(first_nb), n_nb,
+                                                     default_mb(cam) if mb is None else float(mb), v.NMP if mp_base is None else int(mp_base),
+                                                     C.byref(o)))
+    finally:
+        ctx._exit()
+    return out
+
+
+def create_map_points_from_map(ctx, gmm, cam, prm, map, ba, kf_tables, kf_row, nn=10, mb=None, first_nb=0, sizes=None, mp_ref_kf=None,
+                               scale_factor=1.2):
+    """Localization::createMapPoints (localization_opt.cpp:206-454) for ONE key-frame row on the resident map: api.update_connections
+    (kf_row) -> create_map_points_on_map over its neighbours [first_nb, first_nb + nn) -> map_add(the new rows, their attach triples, the
+    counts on the device) -> api.update_map_points(what = 3) on the new rows.  map / ba: the capacity buffers of this module with `sizes`;
+    needs the per-point arrays of the matchers, ba kf_pose / kf_twc / kf_uvr / kf_oct / mp_assoc and mp_ref_kf; kf_tables: dict of
+    KF_TABLE_DTYPES' keys over the key-frame rows of the buffers.  mb defaults to float32(cam.bf) / float32(cam.fx) (frame.cpp:24).
+    One synchronise: map_add's 24-byte read.
+    -> the dict of map_add + new_type, new_nb, feat_new, nb_stats (device tensors; new_type / new_nb cut to n_new) and n_new.  The host's
+    candidate_mappts_ gains the rows [NMP, NMP + n_new) and type_ comes from new_type.  After a truncation by map_add nothing is changed
+    and nothing refreshed (n_new: what the loop made)."""
+    from .api import update_connections, update_map_points
+    import torch
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct", "mp_assoc"))
+    for key in ("mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc"):
+        assert map.get(key) is not None, "map[%r]: missing" % key
+    rk = _tensor("mp_ref_kf", mp_ref_kf, "int32", (NMPcap,), dev)
+    kf_row, nn = int(kf_row), int(nn)
+    assert 0 <= kf_row < NKF, "kf_row %d outside [0, %d)" % (kf_row, NKF)
+    m1, b1 = map_views(map, ba, (NMP, NKF, NOBS))
+    kt = {key: t[:NKF] for key, t in kf_tables.items()}
+    view = {key: m1[key] for key in ("mp_valid", "obs_ptr", "obs_kf", "kf_valid", "kf_mp")}
+    conn = update_connections(ctx, view, torch.tensor([kf_row], dtype=torch.int32, device=dev), Ccap=max(first_nb + nn, 1))
+    s = create_map_points_on_map(ctx, gmm, cam, prm, view, {key: b1[key] for key in ("kf_pose", "kf_twc", "kf_uvr", "kf_oct")}, kt, kf_row,
+                                 conn["conn_kf"][0], conn["n_conn"], first_nb=first_nb, n_nb=nn, mb=mb, mp_base=NMP, scale_factor=scale_factor)
+    r = map_add(ctx, map, ba, (NMP, NKF, NOBS), new_mp=dict(pos=s["new_pos"], assoc=s["new_assoc"], ref_kf=s["new_ref_kf"]),
+                attach=dict(mp=s["att_mp"], kf=s["att_kf"], feat=s["att_feat"]), mp_ref_kf=rk, n_new_mp=s["n_new"], n_attach=s["n_attach"])
+    n_new = r["needed"][0] - NMP
+    if n_new > 0 and not r["status"] & (GROW_OBS_TRUNCATED | GROW_MP_TRUNCATED):
+        m2, b2 = r["map"], r["ba"]
+        new = slice(NMP, NMP + n_new)
+        update_map_points(ctx, dict(twc=b2["kf_twc"], valid=m2["kf_valid"], oct=b2["kf_oct"], desc=kt["desc"]),
+                          dict(pos=m2["mp_pos"][new], valid=m2["mp_valid"][new], ref_kf=rk[new], obs_ptr=m2["obs_ptr"][NMP:], obs_kf=m2["obs_kf"],
+                               obs_feat=b2["obs_feat"]),
+                          dict(desc=m2["mp_desc"][new], normal=m2["mp_normal"][new], max_dist=m2["mp_max_dist"][new], min_dist=m2["mp_min_dist"][new]),
+                          what=3, scale_factor=scale_factor)
+    r.update(new_type=s["new_type"][:n_new], new_nb=s["new_nb"][:n_new], feat_new=s["feat_new"], nb_stats=s["nb_stats"], n_new=n_new)
+    return r

@@ -73,7 +73,8 @@ void gl_default_params(gl_params* p);
  * (config.h:38) and the matchers / the projection loop cast them to float.  "K" = fx fy cx cy, "size" = width height,
  * "sigma2_inv" = the level table (build it for another pyramid as init_config.hpp:60-79 does for 1.2, in float arithmetic),
  * "-" = the argument is not taken.  Every function is checked on the device under non-default values of what it reads
- * (tests/configs.py, tests/test_gpu_configs.py).
+ * (tests/configs.py, tests/test_gpu_configs.py; gl_tri_pair_setup and gl_create_map_points_from_map under the cameras of
+ * tests/create_points_cases.py, one of them with fx != fy for the pair set-up, in tests/test_gpu_create_points.py).
  *
  * entry point                      | gl_camera      | gl_params                                                           | scale_factor
  * ---------------------------------+----------------+---------------------------------------------------------------------+-------------
@@ -84,6 +85,8 @@ void gl_default_params(gl_params* p);
  * gl_check_map_association         | K bf           | as gl_optimize_point (+ the graph the GMM captured)                 | -
  * gl_optimize_triangulation        | K bf           | tri_lambda2 tri_str_thresh tri_check_str_chi2 sigma2_inv            | -
  * gl_create_map_points             | K bf size      | tri_lambda2 tri_str_thresh tri_check_str_chi2 sigma2_inv            | level ratios
+ * gl_tri_pair_setup                | K              | -                                                                   | -
+ * gl_create_map_points_from_map    | K bf size      | as gl_create_map_points                                             | level ratios, sigma2
  * gl_create_stereo_points          | K bf           | as gl_check_map_association                                         | -
  * gl_create_temporal_points        | K              | -                                                                   | -
  * gl_optimize_current_pose         | K bf           | sigma2_inv                                                          | -
@@ -1051,6 +1054,120 @@ int gl_create_map_points(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* ca
                          const float* depth2_dev, const int32_t* oct2_dev, const int32_t* cand1_dev,
                          const int32_t* n1_dev, const int32_t* cand2_dev, const int32_t* n2_dev, int k, double* x3d_dev,
                          int32_t* type_dev, int32_t* comp_dev);
+
+/* ---- a key-frame's new map points, triangulated on the resident map ------------------------------------
+ * Localization::createMapPoints (localization_opt.cpp:206-454) for ONE key-frame row: the loop over its best covisible neighbours
+ * around gl_search_for_triangulation, the match gather and the per-match block of gl_create_map_points.  The loop is sequential:
+ * searchForTriangulation skips a feature of key-frame 1 that holds a map point (orb_matcher.cpp:183-186), createMapPoints gives it one
+ * (curr_kf_->addObservation(mappt, idx1), :433) before the next neighbour is searched, and the partner it would have taken goes to a
+ * later query - so B pairs in one batch of gl_search_for_triangulation are not the reference's result for one key-frame's neighbours.
+ *
+ * gl_map_kf_tables - the per-key-frame tables the triangulation reads and no other view carries; caller-owned device arrays,
+ * row-indexed like gl_map_ba_view (a new key-frame's rows are part of the one upload that stays):
+ *   kf_angle NKF x NFK f32 (key-point angle, degrees), kf_desc NKF x NFK x 32 u8 (the table of gl_fuse_search / gl_update_map_points),
+ *   kf_depth NKF x NFK f32 (Feature::depth, -1 = none); the DBoW2::FeatureVector as CSR like gl_search_for_triangulation's: kf_nnode
+ *   NKF, kf_node_id NKF x NNcap ascending, kf_node_ptr NKF x (NNcap + 1), kf_node_idx NKF x NFK; the candidate tables of gl_search2d
+ *   (kf->comps_): kf_cand NKF x NFK x k, kf_ncand NKF x NFK.
+ *
+ * gl_tri_pair_setup - what the loop computes per neighbour before it searches (:246-262, orb_matcher.cpp:146-161), for key-frame row
+ * kf_row and the neighbours conn_kf[first_nb .. first_nb + n_nb) of a DEVICE list of conn_cap entries with DEVICE length n_conn (the
+ * outputs of gl_update_connections; getBestCovisibilityKeyFrames(nn) is its first nn entries), n_nb <= GL_TRI_NB_MAX:
+ *   skip n_nb int32, bits: GL_TRI_SKIP_BEYOND the entry is at or behind min(n_conn, conn_cap); _BAD_ROW its row is outside [0, NKF);
+ *     _SELF row == kf_row; _INVALID kf_valid[row] == 0 (DECLARED: skipped - the reference's list holds no bad key-frame); _REPEATED the
+ *     row is listed earlier in the range (DECLARED: skipped, gl_map_add's rule for a repeated row); _BASELINE `baseline < kf2->mb`
+ *     exactly as :254-262: the double difference of kf_twc, its double norm sqrt((dx dx + dy dy) + dz dz), narrowed to float, float
+ *     compare against the float mb (a baseline EQUAL to mb is searched).  BEYOND and BAD_ROW stand alone; the others combine.
+ *   fmat n_nb x 9 f64 row-major = MathUtils::computeFundamentalMatrix(Tcw1, K, Tcw2, K) (math_utils.cpp:16-43), in this order - q
+ *     = (x y z w) as stored in kf_pose, not renormalised, (fx fy cx cy) the camera's FLOAT scalars widened:
+ *       R1 = q1.toRotationMatrix(), R2 likewise   (Eigen's: tx = 2 x ... R00 = 1 - (tyy + tzz), R01 = txy - twz, ...)
+ *       R = R1 R2^T:  Rij = (R1i0 R2j0 + R1i1 R2j1) + R1i2 R2j2        rot_c1_w * rot_c2_w.conjugate(), as matrices: the products of two
+ *                                                                      rotation matrices agree with a host's Eigen / numpy chain to
+ *                                                                      the rounding of the chain, a quaternion product does not
+ *       r = R t2:     ri = (Ri0 t2x + Ri1 t2y) + Ri2 t2z;   t12 = -r + t1
+ *       E = skew(t12) R without the zero products: E0j = (-tz) R1j + ty R2j, E1j = tz R0j + (-tx) R2j, E2j = (-ty) R0j + tx R1j
+ *       ifx = 1 / fx, ify = 1 / fy, mcx = -(cx / fx), mcy = -(cy / fy)          (K^-1 in closed form)
+ *       G = E K^-1:  Gi0 = Ei0 ifx, Gi1 = Ei1 ify, Gi2 = (Ei0 mcx + Ei1 mcy) + Ei2
+ *       F = K^-T G:  F0j = ifx G0j, F1j = ify G1j, F2j = (mcx G0j + mcy G1j) + G2j
+ *   epipole n_nb x 2 f32 (orb_matcher.cpp:156-161): C2 = q2 * t1 + t2 - Tcw1.translation(), not key-frame 1's centre: kept;
+ *     invz = 1.0f / (float)C2z; ex = (float)((fx C2x) (double)invz + cx), ey = (float)((fy C2y) (double)invz + cy).
+ *   A skipped neighbour (any bit) has fmat = 0 and epipole = 0.  The file is compiled without contraction and uses + - x / only (one
+ *   sqrt in the baseline), so the same statements in numpy give the same bits.
+ *
+ * gl_create_map_points_from_map - the whole loop for one key-frame and the neighbour range [first_nb, first_nb + n_nb), on the map of
+ * gl_update_connections (map: kf_valid, kf_mp; ba: kf_pose, kf_twc, kf_uvr, kf_oct) and the tables above.  THE MAP IS NOT WRITTEN:
+ * the outputs are gl_map_add's lists.  Asynchronous on the context's stream, stateless, no host synchronise; the context's scratch
+ * is written before it is read.  Enqueued, 2 + 6 n_nb launches whatever the device counts are:
+ *   1  the pair set-up                                                                  (k_tri_pair_setup)
+ *   2  the neighbours' rows gathered into dense pair tables; has_mp2[i] = kf_mp[kf2][i] != -1; a skipped neighbour gets nnode = 0, so
+ *      its search has no query and the stages behind it no match; the mask has_mp1[i] = kf_mp[kf_row][i] != -1 - the POINTER test of
+ *      getMapPoint(idx1), whatever mp_valid says of the row; feat_new = -1, n_new = n_attach = 0                        (k_tri_rows)
+ *   per neighbour, in list order:
+ *   3  gl_search_for_triangulation's kernel, B = 1, bOnlyStereo = false, no orientation check (ORBmatcher(0.6, false), :218, :266)
+ *   4  the matches in ascending idx1 (= matched_pairs) as the per-match arrays                                    (k_tri_match_rows)
+ *   5-7 the per-match block: the three kernels of gl_create_map_points over NFK slots (the slots behind the matches form no point)
+ *   8  accept (k_tri_accept): every match with type > 0, in that order, is appended at the running count n_new: new_pos x 3,
+ *      new_assoc (= comp; -1 exactly for types 1 and 3), new_ref_kf = kf_row, new_type 1..4, new_nb = its index in the list
+ *      (first_nb + j), new_feat1 / new_feat2, and the two triples (mp_base + r, kf_row, idx1), (mp_base + r, kf2, idx2) in that order
+ *      (:430-434) at att_*[2 r], [2 r + 1]; has_mp1[idx1] = 1, feat_new[idx1] = mp_base + r.  A rejected match (type 0: `continue`,
+ *      :346-404) leaves the mask alone: its feature asks again at the next neighbour.
+ * out: the lists (new_* new_cap entries, att_* 2 new_cap) with n_new / n_attach as device counts - gl_map_add's new_* / att_* lists
+ * and counts as they stand; feat_new NFK (-1: no new point); nb_stats n_nb x 8 int32 = {row (-1 beyond the list), skip bits, nmatches,
+ * created, rejected by type 0, 0, 0, 0}; fmat n_nb x 9 / epipole n_nb x 2 (NULL allowed); status int32: GL_TRI_NONE_SEARCHED when
+ * every neighbour of the range was skipped.  Entries of the lists from n_new (2 n_new) on are not written.
+ * new_cap < NFK is GL_ERR_ARG: a feature of key-frame 1 gains at most one point, so NFK rows never truncate.  NFK <= 4 096, NNcap
+ * and k in 1..8 as in gl_search_for_triangulation / gl_create_map_points, cam width / height set; n_nb > GL_TRI_NB_MAX is GL_ERR_ARG.
+ * After an argument error nothing has been written.
+ * The reference's `if (i > 0 && checkNewKeyFrames()) return` (:243) is the range: a host that must test between neighbours calls with
+ * n_nb = 1, applies gl_map_add (the mask is then read from the map it changed, mp_base is the new NMP) and calls again - the same
+ * kernels, the same result.  What stays with the host: computeDistinctiveDescriptors / updateNormalAndDepth of the new rows is
+ * gl_update_map_points after gl_map_add; candidate_mappts_ and type_ from new_type. */
+#define GL_TRI_NB_MAX 16
+#define GL_TRI_SKIP_BEYOND 1
+#define GL_TRI_SKIP_BAD_ROW 2
+#define GL_TRI_SKIP_SELF 4
+#define GL_TRI_SKIP_INVALID 8
+#define GL_TRI_SKIP_REPEATED 16
+#define GL_TRI_SKIP_BASELINE 32
+#define GL_TRI_NONE_SEARCHED 1
+typedef struct gl_map_kf_tables {
+  const float* kf_angle;
+  const uint8_t* kf_desc;
+  const float* kf_depth;
+  const int32_t* kf_nnode;
+  const int32_t* kf_node_id;
+  const int32_t* kf_node_ptr;
+  const int32_t* kf_node_idx;
+  const int32_t* kf_cand;
+  const int32_t* kf_ncand;
+  int32_t NNcap, k;
+} gl_map_kf_tables;
+typedef struct gl_tri_points_out {
+  double* new_pos;
+  int32_t* new_assoc;
+  int32_t* new_ref_kf;
+  int32_t* new_type;
+  int32_t* new_nb;
+  int32_t* new_feat1;
+  int32_t* new_feat2;
+  int32_t* att_mp;
+  int32_t* att_kf;
+  int32_t* att_feat;
+  int32_t* n_new;
+  int32_t* n_attach;
+  int32_t* feat_new;
+  int32_t* nb_stats;
+  double* fmat;
+  float* epipole;
+  int32_t* status;
+  int32_t new_cap, reserved_;
+} gl_tri_points_out;
+int gl_tri_pair_setup(gl_ctx_t* ctx, const gl_camera* cam, int NKF, const uint8_t* kf_valid_dev, const double* kf_pose_dev,
+                      const double* kf_twc_dev, int kf_row, const int32_t* conn_kf_dev, const int32_t* n_conn_dev, int conn_cap, int first_nb,
+                      int n_nb, float mb, int32_t* skip_dev, double* fmat_dev, float* epipole_dev);
+int gl_create_map_points_from_map(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, const gl_params* prm, float scale_factor,
+                                  const gl_map_view* map, const gl_map_ba_view* ba, const gl_map_kf_tables* kt, int kf_row,
+                                  const int32_t* conn_kf_dev, const int32_t* n_conn_dev, int conn_cap, int first_nb, int n_nb, float mb,
+                                  int mp_base, const gl_tri_points_out* out);
 
 /* ---- points from stereo depth: the two depth-ordered walks ------------------ */
 /* GMMLoc::createMapPointsFromStereo (gmmloc_opt.cpp:36-113) for B key-frames of NF feature slots (B = 1 live, B > 1 replay), between

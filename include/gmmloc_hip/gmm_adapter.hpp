@@ -16,6 +16,8 @@
 //   GMMLoc::createMapPointsFromStereo               (gmmloc_opt.cpp:36-113: createMapPointsFromStereo; on the resident map, with the
 //                                                   association before it and the points' refresh behind it: processKeyFrameInMap)
 //   Tracking::createTemporalPoints                  (tracking.cpp:411-465: createTemporalPoints)
+//   Localization::createMapPoints                   (localization_opt.cpp:206-454, the loop over the neighbours with the triangulation:
+//                                                   createMapPointsInMap on the resident map)
 //   north-star per-frame path: associate + structure-constrained refinement of one frame (trackFrame)
 // Host buffers in, host buffers out: each call stages through device memory owned by the
 // adapter (gl_malloc / gl_memcpy_*), so the host code never sees a HIP type.
@@ -40,6 +42,8 @@ namespace gmmloc_hip {
 //    a new version: no existing call changed meaning
 // 5: createMapPointsFromStereo / createTemporalPoints / processKeyFrameInMap: the depth-ordered walks run on the device - a host that
 //    walked the answers of checkMapAssociation itself (INTEGRATION section 4 as it was) calls these instead
+//    setResidentKeyFrameTables / createMapPointsInMap (the loop of Localization::createMapPoints on the resident map) were added
+//    without a new version: no existing call changed meaning
 constexpr int kAdapterVersion = 5;
 
 inline void check(int rc, const char* what) {
@@ -728,6 +732,82 @@ class GMM {
     }
     return r;
   }
+  // Localization::createMapPoints for key-frame kf_row of the resident map (localization_opt.cpp:206-454): gl_update_connections ->
+  // gl_create_map_points_from_map over its first nn neighbours -> gl_map_add (the new rows, their attach triples; the counts stay on the
+  // device) -> gl_update_map_points on the new rows.  setResidentKeyFrameTables: the per-key-frame tables the triangulation reads
+  // (gl_map_kf_tables; a new key-frame's rows belong to its one upload).  mb: Frame::mb (float(bf) / float(fx), frame.cpp:24).  One
+  // synchronise.  After a truncation (status) nothing is changed: grow the buffers and call again.  The new points are the map rows
+  // [old NMP, old NMP + n_new): candidate_mappts_ gains them, type_ comes from new_type.
+  void setResidentKeyFrameTables(const gl_map_kf_tables& t) { kf_tables_ = t; }
+  struct CreatePointsResult {
+    int32_t nmp = 0, nobs = 0, n_attached = 0, n_skipped = 0, status = 0, n_new = 0, tri_status = 0;
+    std::vector<int32_t> new_type, new_nb;  // n_new: MapPoint::type_ (1..4), the neighbour's index in the covisibility list
+    std::vector<int32_t> feat_new;          // NFK: the map row of the point a feature gained, -1 for none
+    std::vector<int32_t> nb_stats;          // nn x 8: {row, skip bits, nmatches, created, rejected, 0, 0, 0}
+  };
+  CreatePointsResult createMapPointsInMap(int32_t kf_row, int32_t nn, float mb, int32_t* mp_ref_kf_dev, float scale_factor = 1.2f) {
+    if (kf_row < 0 || kf_row >= map_.NKF || !mp_ref_kf_dev || nn < 0 || nn > GL_TRI_NB_MAX || !kf_tables_.kf_desc)
+      throw std::runtime_error("createMapPointsInMap: kf_row / nn / mp_ref_kf_dev / setResidentKeyFrameTables");
+    const size_t NF = (size_t)map_.NFK, n = (size_t)(nn > 0 ? nn : 1);
+    const int32_t NMP0 = map_.NMP;
+    size_t off = 128;
+    auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += (bytes + 63) / 64 * 64;
+      return at;
+    };
+    const size_t o_conn = take(2 * n * 4), o_pos = take(NF * 24), o_int = take(13 * NF * 4), o_st = take(n * 32);
+    // {gl_map_add's result at 0 | kf_row at 32 | n_conn 36 | conn status 40 | n_new 44 | n_attach 48 | status 52}
+    char* b = pooled(9, off).as<char>();
+    auto at = [b](size_t o) { return reinterpret_cast<int32_t*>(b + o); };
+    check(gl_memcpy_h2d(ctx_, b + 32, &kf_row, 4), "h2d");
+    int32_t* conn = at(o_conn);
+    check(gl_update_connections(ctx_, &map_, 1, at(32), (int)n, conn, conn + n, at(36), nullptr, at(40)), "gl_update_connections");
+    int32_t* ints = at(o_int);
+    gl_tri_points_out out{};
+    out.new_pos = reinterpret_cast<double*>(b + o_pos);
+    out.new_assoc = ints, out.new_ref_kf = ints + NF, out.new_type = ints + 2 * NF, out.new_nb = ints + 3 * NF, out.new_feat1 = ints + 4 * NF,
+    out.new_feat2 = ints + 5 * NF, out.att_mp = ints + 6 * NF, out.att_kf = ints + 8 * NF, out.att_feat = ints + 10 * NF, out.feat_new = ints + 12 * NF;
+    out.n_new = at(44), out.n_attach = at(48), out.status = at(52), out.nb_stats = at(o_st), out.new_cap = (int32_t)NF;
+    check(gl_create_map_points_from_map(ctx_, gmm_, &cam_, &prm_, scale_factor, &map_, &map_ba_, &kf_tables_, kf_row, conn, at(36), (int)n, 0, nn, mb, NMP0,
+                                        &out),
+          "gl_create_map_points_from_map");
+    const gl_map_edit ed = residentEdit(mp_ref_kf_dev);
+    gl_map_add_lists ls{};
+    ls.new_pos = out.new_pos, ls.new_assoc = out.new_assoc, ls.new_ref_kf = out.new_ref_kf, ls.n_new_mp = out.n_new, ls.new_mp_cap = (int32_t)NF;
+    ls.att_mp = out.att_mp, ls.att_kf = out.att_kf, ls.att_feat = out.att_feat, ls.n_attach = out.n_attach, ls.attach_cap = (int32_t)(2 * NF);
+    gl_map_add_out ao{};
+    ao.result = at(0);
+    check(gl_map_add(ctx_, map_.NMP, map_.NKF, map_.NFK, map_.NOBS, mp_cap_, obs_cap_, &ed, const_cast<double*>(map_.mp_pos), map_ba_.mp_assoc, &ls, &ao),
+          "gl_map_add");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t head[14];
+    check(gl_memcpy_d2h(ctx_, head, b, 56), "d2h");
+    CreatePointsResult r;
+    r.nmp = head[0], r.nobs = head[1], r.n_attached = head[2], r.n_skipped = head[3], r.status = head[5], r.tri_status = head[13];
+    r.n_new = r.nmp - NMP0;
+    r.feat_new.resize(NF);
+    r.nb_stats.resize((size_t)nn * 8);
+    r.new_type.resize((size_t)r.n_new);
+    r.new_nb.resize((size_t)r.n_new);
+    if (NF) check(gl_memcpy_d2h(ctx_, r.feat_new.data(), out.feat_new, NF * 4), "d2h");
+    if (nn) check(gl_memcpy_d2h(ctx_, r.nb_stats.data(), out.nb_stats, (size_t)nn * 32), "d2h");
+    if (r.n_new > 0) {
+      check(gl_memcpy_d2h(ctx_, r.new_type.data(), out.new_type, (size_t)r.n_new * 4), "d2h");
+      check(gl_memcpy_d2h(ctx_, r.new_nb.data(), out.new_nb, (size_t)r.n_new * 4), "d2h");
+    }
+    if (r.status & (GL_MAP_GROW_MP_TRUNCATED | GL_MAP_GROW_OBS_TRUNCATED)) return r;
+    map_.NMP = r.nmp, map_.NOBS = r.nobs;
+    if (r.n_new > 0) {
+      const size_t p0 = (size_t)NMP0;
+      check(gl_update_map_points(ctx_, scale_factor, 3, r.n_new, map_.NKF, map_.NFK, map_.NOBS, map_ba_.kf_twc, map_.kf_valid, map_ba_.kf_oct,
+                                 kf_tables_.kf_desc, map_.mp_pos + p0 * 3, map_.mp_valid + p0, mp_ref_kf_dev + p0, map_.obs_ptr + p0, map_.obs_kf,
+                                 map_ba_.obs_feat, const_cast<uint8_t*>(map_.mp_desc) + p0 * 32, const_cast<double*>(map_.mp_normal) + p0 * 3,
+                                 const_cast<float*>(map_.mp_max_dist) + p0, const_cast<float*>(map_.mp_min_dist) + p0),
+            "gl_update_map_points");
+    }
+    return r;
+  }
   const gl_map_view& residentMap() const { return map_; }
 
   gl_ctx_t* ctx() { return ctx_; }
@@ -808,6 +888,7 @@ class GMM {
   }
   gl_map_view map_{};
   gl_map_ba_view map_ba_{};
+  gl_map_kf_tables kf_tables_{};
   int32_t mp_cap_ = 0, obs_cap_ = 0;  // the rows of the per-point arrays, the entries of obs_kf / obs_feat
   size_t caps_[4] = {24, 24, 2048, 16384};  // Pcap, Fcap, Lcap, Ocap: grown on demand
   size_t win_off_[3] = {0, 0, 0};           // dropped, erase, erase_obs (consecutive)

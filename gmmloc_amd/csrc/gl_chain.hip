@@ -7,6 +7,7 @@
 // optimisation, marking what the frame has already seen - as four small kernels.  Every intermediate array lives in the
 // context's third scratch block (the stages themselves use the first two).
 #include "gl_internal.hpp"
+#include "gl_match_common.hpp"  // KfSide
 #include "gl_pose_compact.hpp"
 
 namespace {
@@ -426,9 +427,13 @@ int chain_front(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* prm, float
   // ---- Tracking::trackKeyFrame (:297-331) for the flagged frames: ORBmatcher(0.7, true).searchByBoW(ref_keyframe_, curr), the last
   // frame's pose, optimizeCurrentPose, outliers dropped.  The workgroups of the other frames return at once (no edge: their
   // optimisation returns at `edges().size() < 10`, on a scratch pose).
-  rc = gl::launch_bow_gated(ctx, 0.7f, 1, B, io->NK, NF, io->NNK, io->NNF, io->kf_angle, io->kf_desc, io->kf_has_mp, io->kf_nnode, io->kf_node_id,
-                            io->kf_node_ptr, io->kf_node_idx, io->feat_angle, io->feat_desc, io->feat_nnode, io->feat_node_id, io->feat_node_ptr,
-                            io->feat_node_idx, io->match_kf, S.nm_bow, S.fb_flag);
+  using gl_match::KfSide;
+  using gl_match::NodeList;
+  rc = gl::launch_bow_gated(
+      ctx, 0.7f, 1, B,
+      KfSide{nullptr, nullptr, nullptr, io->kf_angle, io->kf_desc, io->kf_has_mp, NodeList{io->kf_nnode, io->kf_node_id, io->kf_node_ptr, io->kf_node_idx, io->NK, io->NNK}},
+      KfSide{nullptr, nullptr, nullptr, io->feat_angle, io->feat_desc, nullptr, NodeList{io->feat_nnode, io->feat_node_id, io->feat_node_ptr, io->feat_node_idx, NF, io->NNF}},
+      io->match_kf, S.nm_bow, S.fb_flag);
   if (rc != GL_OK) return rc;
   ChainOpt ofb = {S.pose_fb, nullptr, nullptr, io->match_kf, S.fb_flag, 0, S.outl_fb, true, S.ninl, 1, -1, 0, io->pose_lw};
   rc = chain_optimise(ctx, cam, prm, B, NF, NL, NP, NK, io, S, ofb);

@@ -10,6 +10,12 @@
 
 #include "gmmloc_hip.h"
 
+namespace gl_match {  // gl_match_common.hpp
+struct KfSide;
+struct MatchSide;
+struct MatchPoints;
+}  // namespace gl_match
+
 namespace gl {
 
 void set_error(const char* fmt, ...);
@@ -300,10 +306,8 @@ int pose_compacted_launch(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* 
                           const PoseCompacted& pc);
 int optimize_current_pose_plain(gl_ctx_t* ctx, const gl_camera* cam, const gl_params* prm, int B, int M, double* pose_dev, const double* Xw_dev,
                                 const double* obs_dev, const int32_t* octave_dev, uint8_t* outlier_dev, int32_t* ninlier_dev, int nin_stride);
-int launch_bow_gated(gl_ctx_t* ctx, float nn_ratio, int check_orientation, int B, int N1, int N2, int NN1, int NN2, const float* angle1_dev,
-                     const uint8_t* desc1_dev, const uint8_t* has_mp1_dev, const int32_t* nnode1_dev, const int32_t* node_id1_dev,
-                     const int32_t* node_ptr1_dev, const int32_t* node_idx1_dev, const float* angle2_dev, const uint8_t* desc2_dev,
-                     const int32_t* nnode2_dev, const int32_t* node_id2_dev, const int32_t* node_ptr2_dev, const int32_t* node_idx2_dev,
+// (gl_match_bow.hip) gl_search_by_bow on the two sides (gl_match_common.hpp) with a per-frame switch, checks included
+int launch_bow_gated(gl_ctx_t* ctx, float nn_ratio, int check_orientation, int B, const gl_match::KfSide& side1, const gl_match::KfSide& side2,
                      int32_t* match21_dev, int32_t* nmatches_dev, const int32_t* run_flag);
 int launch_match_frame_gated(gl_ctx_t* ctx, const gl_camera* cam, float scale_factor, int B, int NF, int NL, const double* pose_cw, const double* pose_lw,
                              const double* feat_uv, const float* feat_ur, const int32_t* feat_oct, const float* feat_angle, const uint8_t* feat_desc,
@@ -340,22 +344,14 @@ int local_map_gather_launch(Ctx* c, const gl_map_view* map, int B, int NL, int N
 int launch_check_map_association(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, int B, int N, const double* pose_dev,
                                  double* pts_dev, const double* uvr_dev, const int32_t* octave_dev, const int32_t* cand_dev,
                                  const int32_t* ncand_dev, int k, int32_t* out_comp_dev);
-// (gl_match_tri.hip) k_search_for_triangulation, arguments as gl_search_for_triangulation's and already checked
-int launch_search_for_triangulation(Ctx* c, float scale_factor, int B, int N1, int N2, int NN1, int NN2, const double* uv1_dev,
-                                    const float* ur1_dev, const int32_t* oct1_dev, const float* angle1_dev, const uint8_t* desc1_dev,
-                                    const uint8_t* has_mp1_dev, const int32_t* nnode1_dev, const int32_t* node_id1_dev,
-                                    const int32_t* node_ptr1_dev, const int32_t* node_idx1_dev, const double* uv2_dev, const float* ur2_dev,
-                                    const int32_t* oct2_dev, const float* angle2_dev, const uint8_t* desc2_dev, const uint8_t* has_mp2_dev,
-                                    const int32_t* nnode2_dev, const int32_t* node_id2_dev, const int32_t* node_ptr2_dev,
-                                    const int32_t* node_idx2_dev, const double* fmat_dev, const float* epipole_dev, int only_stereo,
-                                    int check_orientation, int32_t* match12_dev, int32_t* nmatches_dev);
-// (gl_point.hip) the three kernels of gl_create_map_points on a scratch region of the caller's
+// (gl_match_tri.hip) k_search_for_triangulation on the two sides, the values as gl_search_for_triangulation's and already checked
+int launch_search_for_triangulation(Ctx* c, float scale_factor, int B, const gl_match::KfSide& side1, const gl_match::KfSide& side2,
+                                    const double* fmat_dev, const float* epipole_dev, int only_stereo, int check_orientation, int32_t* match12_dev,
+                                    int32_t* nmatches_dev);
+// (gl_point.hip) the three kernels of gl_create_map_points over N matches on a scratch region of the caller's
 size_t create_map_points_scratch_bytes(int N);
-int launch_create_map_points(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, float scale_factor, int N,
-                             const double* pose1_dev, const double* uvr1_dev, const float* depth1_dev, const int32_t* oct1_dev,
-                             const double* pose2_dev, const double* uvr2_dev, const float* depth2_dev, const int32_t* oct2_dev,
-                             const int32_t* cand1_dev, const int32_t* n1_dev, const int32_t* cand2_dev, const int32_t* n2_dev, int k,
-                             double* x3d_dev, int32_t* type_dev, int32_t* comp_dev, void* scratch);
+int launch_create_map_points(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, float scale_factor, int N, int k,
+                             const gl_match::MatchSide& side1, const gl_match::MatchSide& side2, const gl_match::MatchPoints& out, void* scratch);
 // association launchers (gl_assoc.hip: all-pairs sweep; gl_grid.hip: cell index + sweep of the rest)
 int launch_assoc_brute(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2);
 int launch_assoc_sweep(Ctx* c, const Gmm* g, const double* pts, int N, int32_t* idx, double* d2, const int32_t* list,

@@ -20,6 +20,7 @@
 #include "gl_match_common.hpp"
 
 using namespace gld;
+using namespace gl_match;  // KfSide, KfPointSide, MatchSide, MatchPoints, NodeList, gather_match
 
 namespace {
 
@@ -128,51 +129,32 @@ __global__ __launch_bounds__(64) void k_tri_pair_setup(PairK k, int NKF, const u
   }
 }
 
-// one key-frame side as the search and the match gather read it; per neighbour j the arrays start at j x (their row size)
-struct Side2 {
-  double* uv;       // n x N x 2
-  float* ur;        // n x N
-  int32_t* oct;     // n x N
-  float* angle;     // n x N
-  uint8_t* desc;    // n x N x 32
-  uint8_t* has_mp;  // n x N
-  float* depth;     // n x N
-  int32_t* cand;    // n x N x k
-  int32_t* ncand;   // n x N
-  int32_t* nnode;   // n
-  int32_t* nid;     // n x NN
-  int32_t* nptr;    // n x (NN + 1)
-  int32_t* nidx;    // n x N
-  double* pose;     // n x 7
+// The map's key-frame tables, a row per key-frame: a side of NKF "pairs", but for two tables the map keeps in a form of its own
+struct KfTables {
+  const double* kf_uvr;  // NKF x N x 3: (u, v, u_right) interleaved, all double
+  const int32_t* kf_mp;  // NKF x N: a feature's map point (-1: none) where a side has a byte
+  KfSide match;          // uv / ur / has_mp null
+  KfPointSide point;     // uv / ur null
 };
-struct KfTables {  // the map's side of the gather
-  const double* kf_pose;
-  const double* kf_uvr;
-  const int32_t* kf_oct;
-  const int32_t* kf_mp;
-  const float* kf_angle;
-  const uint8_t* kf_desc;
-  const float* kf_depth;
-  const int32_t* kf_nnode;
-  const int32_t* kf_node_id;
-  const int32_t* kf_node_ptr;
-  const int32_t* kf_node_idx;
-  const int32_t* kf_cand;
-  const int32_t* kf_ncand;
-};
+// (k_tri_rows is the one writer of key-frame 1's dense tables and of the pair tables, which everything after it reads as sides)
+template <class V>
+GL_DEV V* mut(const V* p) {
+  return const_cast<V*>(p);
+}
 
-__global__ __launch_bounds__(ROW_T) void k_tri_rows(int N, int NN, int k, int kf_row, int n_nb, KfTables t, const int32_t* __restrict__ skip,
-                                                    const int32_t* __restrict__ rows, double* __restrict__ uv1, float* __restrict__ ur1,
-                                                    uint8_t* __restrict__ mask, Side2 s, int32_t* __restrict__ feat_new,
-                                                    int32_t* __restrict__ n_new, int32_t* __restrict__ n_attach, int32_t* __restrict__ status) {
-  const int tid = threadIdx.x;
+// side1 / point1: key-frame 1 (the map's row, dense uv / ur / mask); side2 / point2: the pair tables, neighbour j's at pair(j)
+__global__ __launch_bounds__(ROW_T) void k_tri_rows(int kf_row, int n_nb, KfTables t, const int32_t* __restrict__ skip,
+                                                    const int32_t* __restrict__ rows, KfSide side1, KfSide side2, KfPointSide point2,
+                                                    int32_t* __restrict__ feat_new, int32_t* __restrict__ n_new, int32_t* __restrict__ n_attach,
+                                                    int32_t* __restrict__ status) {
+  const int tid = threadIdx.x, N = side2.nodes.N, NN = side2.nodes.NN, k = point2.k;
   if (blockIdx.x == 0) {
     const size_t f0 = (size_t)kf_row * N;
     for (int i = tid; i < N; i += ROW_T) {
-      uv1[2 * i] = t.kf_uvr[(f0 + i) * 3];
-      uv1[2 * i + 1] = t.kf_uvr[(f0 + i) * 3 + 1];
-      ur1[i] = (float)t.kf_uvr[(f0 + i) * 3 + 2];
-      mask[i] = t.kf_mp[f0 + i] != -1 ? 1 : 0;  // getMapPoint(idx1) != nullptr: the pointer alone, whatever mp_valid says
+      mut(side1.uv)[2 * i] = t.kf_uvr[(f0 + i) * 3];
+      mut(side1.uv)[2 * i + 1] = t.kf_uvr[(f0 + i) * 3 + 1];
+      mut(side1.ur)[i] = (float)t.kf_uvr[(f0 + i) * 3 + 2];
+      mut(side1.has_mp)[i] = t.kf_mp[f0 + i] != -1 ? 1 : 0;  // getMapPoint(idx1) != nullptr: the pointer alone, whatever mp_valid says
       feat_new[i] = -1;
     }
     if (tid == 0) {
@@ -185,51 +167,48 @@ __global__ __launch_bounds__(ROW_T) void k_tri_rows(int N, int NN, int k, int kf
     return;
   }
   const int j = blockIdx.x - 1;
+  const KfSide d = side2.pair(j);
   if (skip[j] != 0) {  // no vocabulary node: the search finds no query, the stages behind it no match
     if (tid == 0) {
-      s.nnode[j] = 0;
-      s.nptr[(size_t)j * (NN + 1)] = 0;
+      mut(d.nodes.nnode)[0] = 0;
+      mut(d.nodes.node_ptr)[0] = 0;
     }
     return;
   }
   const int row = rows[j];
-  const size_t f0 = (size_t)row * N, d0 = (size_t)j * N;
+  const size_t f0 = (size_t)row * N;
+  const KfSide m = t.match.pair(row);
+  const KfPointSide pm = t.point.pair(row), pd = point2.pair(j);
   for (int i = tid; i < N; i += ROW_T) {
-    s.uv[(d0 + i) * 2] = t.kf_uvr[(f0 + i) * 3];
-    s.uv[(d0 + i) * 2 + 1] = t.kf_uvr[(f0 + i) * 3 + 1];
-    s.ur[d0 + i] = (float)t.kf_uvr[(f0 + i) * 3 + 2];
-    s.oct[d0 + i] = t.kf_oct[f0 + i];
-    s.angle[d0 + i] = t.kf_angle[f0 + i];
-    s.has_mp[d0 + i] = t.kf_mp[f0 + i] != -1 ? 1 : 0;
-    s.depth[d0 + i] = t.kf_depth[f0 + i];
-    s.ncand[d0 + i] = t.kf_ncand[f0 + i];
-    s.nidx[d0 + i] = t.kf_node_idx[f0 + i];
-    for (int c = 0; c < k; ++c) s.cand[(d0 + i) * k + c] = t.kf_cand[(f0 + i) * k + c];
+    mut(d.uv)[i * 2] = t.kf_uvr[(f0 + i) * 3];
+    mut(d.uv)[i * 2 + 1] = t.kf_uvr[(f0 + i) * 3 + 1];
+    mut(d.ur)[i] = (float)t.kf_uvr[(f0 + i) * 3 + 2];
+    mut(d.oct)[i] = m.oct[i];
+    mut(d.angle)[i] = m.angle[i];
+    mut(d.has_mp)[i] = t.kf_mp[f0 + i] != -1 ? 1 : 0;
+    mut(pd.depth)[i] = pm.depth[i];
+    mut(pd.ncand)[i] = pm.ncand[i];
+    mut(d.nodes.node_idx)[i] = m.nodes.node_idx[i];
+    for (int c = 0; c < k; ++c) mut(pd.cand)[(size_t)i * k + c] = pm.cand[(size_t)i * k + c];
   }
-  const uint4* dsrc = (const uint4*)(t.kf_desc + f0 * 32);
-  uint4* ddst = (uint4*)(s.desc + d0 * 32);
+  const uint4* dsrc = (const uint4*)m.desc;
+  uint4* ddst = (uint4*)mut(d.desc);
   for (int i = tid; i < 2 * N; i += ROW_T) ddst[i] = dsrc[i];
-  for (int i = tid; i < NN; i += ROW_T) s.nid[(size_t)j * NN + i] = t.kf_node_id[(size_t)row * NN + i];
-  for (int i = tid; i <= NN; i += ROW_T) s.nptr[(size_t)j * (NN + 1) + i] = t.kf_node_ptr[(size_t)row * (NN + 1) + i];
-  if (tid < 7) s.pose[(size_t)j * 7 + tid] = t.kf_pose[(size_t)row * 7 + tid];
-  if (tid == 0) s.nnode[j] = min(max(t.kf_nnode[row], 0), NN);
+  for (int i = tid; i < NN; i += ROW_T) mut(d.nodes.node_id)[i] = m.nodes.node_id[i];
+  for (int i = tid; i <= NN; i += ROW_T) mut(d.nodes.node_ptr)[i] = m.nodes.node_ptr[i];
+  if (tid < 7) mut(pd.pose)[tid] = pm.pose[tid];
+  if (tid == 0) mut(d.nodes.nnode)[0] = min(max(m.nodes.nnode[0], 0), NN);
 }
 
-struct MatchOut {  // the per-match arrays of gl_create_map_points, N slots
-  double *pose1, *uvr1, *pose2, *uvr2;
-  float *depth1, *depth2;
-  int32_t *oct1, *oct2, *cand1, *cand2, *n1, *n2, *idx1, *idx2, *count;
-};
-
 // matches12 of ONE pair -> the per-match arrays in ascending feature index of key-frame 1 (= matched_pairs), as k_tri_gather makes
-// them; key-frame 1's side straight from its map row, key-frame 2's from the pair tables.  The slots behind the matches become
-// problems the create block leaves at once: octave -1 (k_optimize_triangulation returns), identity poses and monocular key-points
-// on the optical axis (k_tri_pre forms no point, k_tri_post writes type 0).
-__global__ __launch_bounds__(ROW_T) void k_tri_match_rows(int N, int k, int kf_row, int j, KfTables t, const float* __restrict__ ur1,
-                                                          Side2 s, const int32_t* __restrict__ match, MatchOut o) {
+// them; a: key-frame 1, b: the pair's tables.  The slots behind the matches become problems the create block leaves at once: octave
+// -1 (k_optimize_triangulation returns), identity poses and monocular key-points on the optical axis (k_tri_pre forms no point,
+// k_tri_post writes type 0).
+__global__ __launch_bounds__(ROW_T) void k_tri_match_rows(KfPointSide a, KfPointSide b, const int32_t* __restrict__ match, MatchSide oa,
+                                                          MatchSide ob, int32_t* __restrict__ idx1, int32_t* __restrict__ idx2,
+                                                          int32_t* __restrict__ count) {
   __shared__ int s_w[ROW_T / 64];
-  const int tid = threadIdx.x;
-  const size_t f0 = (size_t)kf_row * N, d0 = (size_t)j * N;
+  const int tid = threadIdx.x, N = a.N, k = a.k;
   int run = 0;
   for (int i0 = 0; i0 < N; i0 += ROW_T) {
     const int i = i0 + tid;
@@ -239,43 +218,23 @@ __global__ __launch_bounds__(ROW_T) void k_tri_match_rows(int N, int k, int kf_r
     const int at = run + gl::mapdev::block_excl_scan<ROW_T, int>(on ? 1 : 0, s_w, tid, &total);
     run += total;
     if (on) {
-#pragma unroll
-      for (int r = 0; r < 7; ++r) {
-        o.pose1[(size_t)at * 7 + r] = t.kf_pose[(size_t)kf_row * 7 + r];
-        o.pose2[(size_t)at * 7 + r] = s.pose[(size_t)j * 7 + r];
-      }
-      o.uvr1[(size_t)at * 3] = t.kf_uvr[(f0 + i) * 3];
-      o.uvr1[(size_t)at * 3 + 1] = t.kf_uvr[(f0 + i) * 3 + 1];
-      o.uvr1[(size_t)at * 3 + 2] = (double)ur1[i];
-      o.uvr2[(size_t)at * 3] = s.uv[(d0 + m2) * 2];
-      o.uvr2[(size_t)at * 3 + 1] = s.uv[(d0 + m2) * 2 + 1];
-      o.uvr2[(size_t)at * 3 + 2] = (double)s.ur[d0 + m2];
-      o.depth1[at] = t.kf_depth[f0 + i];
-      o.depth2[at] = s.depth[d0 + m2];
-      o.oct1[at] = t.kf_oct[f0 + i];
-      o.oct2[at] = s.oct[d0 + m2];
-      o.n1[at] = t.kf_ncand[f0 + i];
-      o.n2[at] = s.ncand[d0 + m2];
-      for (int c = 0; c < k; ++c) {
-        o.cand1[(size_t)at * k + c] = t.kf_cand[(f0 + i) * k + c];
-        o.cand2[(size_t)at * k + c] = s.cand[(d0 + m2) * k + c];
-      }
-      o.idx1[at] = i;
-      o.idx2[at] = m2;
+      gather_match(a, b, 0, i, m2, oa, ob, at);
+      idx1[at] = i;
+      idx2[at] = m2;
     }
   }
   for (int at = run + tid; at < N; at += ROW_T) {
 #pragma unroll
-    for (int r = 0; r < 7; ++r) o.pose1[(size_t)at * 7 + r] = o.pose2[(size_t)at * 7 + r] = r == 3 ? 1.0 : 0.0;
+    for (int r = 0; r < 7; ++r) oa.pose[(size_t)at * 7 + r] = ob.pose[(size_t)at * 7 + r] = r == 3 ? 1.0 : 0.0;
 #pragma unroll
-    for (int r = 0; r < 3; ++r) o.uvr1[(size_t)at * 3 + r] = o.uvr2[(size_t)at * 3 + r] = r == 2 ? -1.0 : 0.0;
-    o.depth1[at] = o.depth2[at] = -1.0f;
-    o.oct1[at] = o.oct2[at] = -1;
-    o.n1[at] = o.n2[at] = 0;
-    for (int c = 0; c < k; ++c) o.cand1[(size_t)at * k + c] = o.cand2[(size_t)at * k + c] = -1;
-    o.idx1[at] = o.idx2[at] = -1;
+    for (int r = 0; r < 3; ++r) oa.uvr[(size_t)at * 3 + r] = ob.uvr[(size_t)at * 3 + r] = r == 2 ? -1.0 : 0.0;
+    oa.depth[at] = ob.depth[at] = -1.0f;
+    oa.oct[at] = ob.oct[at] = -1;
+    oa.ncand[at] = ob.ncand[at] = 0;
+    for (int c = 0; c < k; ++c) oa.cand[(size_t)at * k + c] = ob.cand[(size_t)at * k + c] = -1;
+    idx1[at] = idx2[at] = -1;
   }
-  if (tid == 0) *o.count = run;
+  if (tid == 0) *count = run;
 }
 
 struct AcceptOut {
@@ -344,6 +303,70 @@ PairK make_pairk(const gl_camera* cam) {
   return PairK{(double)(float)cam->fx, (double)(float)cam->fy, (double)(float)cam->cx, (double)(float)cam->cy};
 }
 
+// per neighbour: what k_tri_pair_setup leaves, and the search's match count
+struct PairWork {
+  int32_t *skip, *rows;
+  double* fmat;       // x 9
+  float* epipole;     // x 2
+  int32_t* nmatches;
+  PairWork pair(int j) const { return PairWork{skip + j, rows + j, fmat + (size_t)j * 9, epipole + (size_t)j * 2, nmatches + j}; }
+};
+
+// The scratch of gl_create_map_points_from_map (SCRATCH_MAPTRI): the byte offset of each region, in the order of the stages
+struct TriLayout {
+  TriLayout(int n_nb, int N_, int NN_, int k_) : n((size_t)(n_nb > 0 ? n_nb : 1)), N((size_t)N_), NN((size_t)NN_), k((size_t)k_) {}
+  const size_t n, N, NN, k;
+  gl::Regions rg{0};
+  const size_t skip = rg.take(n * 4), rows = rg.take(n * 4), fmat = rg.take(n * 72), epi = rg.take(n * 8), nm = rg.take(n * 4);  // PairWork
+  const size_t uv1 = rg.take(N * 16), ur1 = rg.take(N * 4), mask = rg.take(N);  // key-frame 1, dense
+  // the pair tables, n neighbours
+  const size_t uv2 = rg.take(n * N * 16), ur2 = rg.take(n * N * 4), oct2 = rg.take(n * N * 4), ang2 = rg.take(n * N * 4),
+               desc2 = rg.take(n * N * 32), mp2 = rg.take(n * N), dep2 = rg.take(n * N * 4), cand2 = rg.take(n * N * k * 4),
+               nc2 = rg.take(n * N * 4), nn2 = rg.take(n * 4), nid2 = rg.take(n * NN * 4), nptr2 = rg.take(n * (NN + 1) * 4),
+               nidx2 = rg.take(n * N * 4), pose2 = rg.take(n * 56);
+  const size_t match = rg.take(N * 4);  // matches12 of the current pair
+  // the per-match arrays, N slots
+  const size_t m_pose1 = rg.take(N * 56), m_uvr1 = rg.take(N * 24), m_pose2 = rg.take(N * 56), m_uvr2 = rg.take(N * 24),
+               m_dep1 = rg.take(N * 4), m_dep2 = rg.take(N * 4), m_oct1 = rg.take(N * 4), m_oct2 = rg.take(N * 4),
+               m_cand1 = rg.take(N * k * 4), m_cand2 = rg.take(N * k * 4), m_n1 = rg.take(N * 4), m_n2 = rg.take(N * 4),
+               m_idx1 = rg.take(N * 4), m_idx2 = rg.take(N * 4), count = rg.take(4);
+  // gl_create_map_points' results and its own scratch
+  const size_t x3d = rg.take(N * 24), type = rg.take(N * 4), comp = rg.take(N * 4), create = rg.take(gl::create_map_points_scratch_bytes((int)N));
+  const size_t end = rg.off;
+};
+
+// base + layout -> what the stages take
+struct TriScratch {
+  PairWork nb;
+  double* uv1;  // key-frame 1: dense (u, v), u_right, and the mask that grows from neighbour to neighbour
+  float* ur1;
+  uint8_t* mask;
+  KfSide side2;        // the pair tables as the search reads them, neighbour j's at pair(j)
+  KfPointSide point2;  // ... and as the match gather does
+  int32_t* match;
+  MatchSide m1, m2;
+  int32_t *idx1, *idx2, *count;
+  MatchPoints pts;
+  void* create;
+};
+struct At {  // the start of a region as the pointer its member is
+  char* p;
+  template <class V>
+  operator V*() const {
+    return (V*)p;
+  }
+};
+TriScratch tri_scratch(void* base, const TriLayout& L) {
+  auto at = [base](size_t off) { return At{(char*)base + off}; };
+  const int N = (int)L.N, NN = (int)L.NN, k = (int)L.k;
+  const KfSide side2{at(L.uv2), at(L.ur2), at(L.oct2), at(L.ang2), at(L.desc2), at(L.mp2), NodeList{at(L.nn2), at(L.nid2), at(L.nptr2), at(L.nidx2), N, NN}};
+  return TriScratch{PairWork{at(L.skip), at(L.rows), at(L.fmat), at(L.epi), at(L.nm)}, at(L.uv1), at(L.ur1), at(L.mask), side2,
+                    KfPointSide{at(L.pose2), side2.uv, side2.ur, at(L.dep2), side2.oct, at(L.cand2), at(L.nc2), N, k}, at(L.match),
+                    MatchSide{at(L.m_pose1), at(L.m_uvr1), at(L.m_dep1), at(L.m_oct1), at(L.m_cand1), at(L.m_n1)},
+                    MatchSide{at(L.m_pose2), at(L.m_uvr2), at(L.m_dep2), at(L.m_oct2), at(L.m_cand2), at(L.m_n2)}, at(L.m_idx1), at(L.m_idx2),
+                    at(L.count), MatchPoints{at(L.x3d), at(L.type), at(L.comp)}, at(L.create)};
+}
+
 }  // namespace
 
 extern "C" {
@@ -388,71 +411,45 @@ int gl_create_map_points_from_map(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_c
              "null output buffer (only fmat / epipole are optional)");
   gl::Ctx* c = gl::C(ctx);
   GL_HIP(hipSetDevice(c->device));
-  GL_REQUIRE_LDS(c, gl_match::NodeQueries::matcher_lds(N, N, NN, NN));
-  const size_t n = (size_t)(n_nb > 0 ? n_nb : 1), Nz = (size_t)N;
-  gl::Regions rg{0};
-  const size_t o_skip = rg.take(n * 4), o_rows = rg.take(n * 4), o_fmat = rg.take(n * 72), o_epi = rg.take(n * 8), o_nm = rg.take(n * 4),
-               o_uv1 = rg.take(Nz * 16), o_ur1 = rg.take(Nz * 4), o_mask = rg.take(Nz), o_uv2 = rg.take(n * Nz * 16), o_ur2 = rg.take(n * Nz * 4),
-               o_oct2 = rg.take(n * Nz * 4), o_ang2 = rg.take(n * Nz * 4), o_desc2 = rg.take(n * Nz * 32), o_mp2 = rg.take(n * Nz),
-               o_dep2 = rg.take(n * Nz * 4), o_cand2 = rg.take(n * Nz * k * 4), o_nc2 = rg.take(n * Nz * 4), o_nn2 = rg.take(n * 4),
-               o_nid2 = rg.take(n * NN * 4), o_nptr2 = rg.take(n * ((size_t)NN + 1) * 4), o_nidx2 = rg.take(n * Nz * 4),
-               o_pose2 = rg.take(n * 56), o_match = rg.take(Nz * 4), o_mp1 = rg.take(Nz * 56), o_mu1 = rg.take(Nz * 24),
-               o_mp2p = rg.take(Nz * 56), o_mu2 = rg.take(Nz * 24), o_md1 = rg.take(Nz * 4), o_md2 = rg.take(Nz * 4), o_mo1 = rg.take(Nz * 4),
-               o_mo2 = rg.take(Nz * 4), o_mc1 = rg.take(Nz * k * 4), o_mc2 = rg.take(Nz * k * 4), o_mn1 = rg.take(Nz * 4),
-               o_mn2 = rg.take(Nz * 4), o_mi1 = rg.take(Nz * 4), o_mi2 = rg.take(Nz * 4), o_cnt = rg.take(4), o_x3d = rg.take(Nz * 24),
-               o_type = rg.take(Nz * 4), o_comp = rg.take(Nz * 4), o_cmp = rg.take(gl::create_map_points_scratch_bytes(N));
+  GL_REQUIRE_LDS(c, NodeQueries::matcher_lds(N, N, NN, NN));
+  const TriLayout L(n_nb, N, NN, k);
   void* scratch = nullptr;
-  const int rs = gl::ctx_scratch(c, rg.off, &scratch, gl::SCRATCH_MAPTRI);
+  const int rs = gl::ctx_scratch(c, L.end, &scratch, gl::SCRATCH_MAPTRI);
   if (rs != GL_OK) return rs;
-  char* S = (char*)scratch;
-  int32_t* skip = (int32_t*)(S + o_skip);
-  int32_t* rows = (int32_t*)(S + o_rows);
-  double* fmat = (double*)(S + o_fmat);
-  float* epi = (float*)(S + o_epi);
-  int32_t* nm = (int32_t*)(S + o_nm);
-  double* uv1 = (double*)(S + o_uv1);
-  float* ur1 = (float*)(S + o_ur1);
-  uint8_t* mask = (uint8_t*)(S + o_mask);
-  const Side2 s2{(double*)(S + o_uv2),    (float*)(S + o_ur2),    (int32_t*)(S + o_oct2), (float*)(S + o_ang2),   (uint8_t*)(S + o_desc2),
-                 (uint8_t*)(S + o_mp2),   (float*)(S + o_dep2),   (int32_t*)(S + o_cand2), (int32_t*)(S + o_nc2), (int32_t*)(S + o_nn2),
-                 (int32_t*)(S + o_nid2),  (int32_t*)(S + o_nptr2), (int32_t*)(S + o_nidx2), (double*)(S + o_pose2)};
-  int32_t* match = (int32_t*)(S + o_match);
-  const MatchOut mo{(double*)(S + o_mp1),  (double*)(S + o_mu1),  (double*)(S + o_mp2p), (double*)(S + o_mu2),  (float*)(S + o_md1),
-                    (float*)(S + o_md2),   (int32_t*)(S + o_mo1), (int32_t*)(S + o_mo2), (int32_t*)(S + o_mc1), (int32_t*)(S + o_mc2),
-                    (int32_t*)(S + o_mn1), (int32_t*)(S + o_mn2), (int32_t*)(S + o_mi1), (int32_t*)(S + o_mi2), (int32_t*)(S + o_cnt)};
-  double* x3d = (double*)(S + o_x3d);
-  int32_t* type = (int32_t*)(S + o_type);
-  int32_t* comp = (int32_t*)(S + o_comp);
-  const KfTables t{ba->kf_pose,  ba->kf_uvr,     ba->kf_oct,      map->kf_mp,      kt->kf_angle, kt->kf_desc, kt->kf_depth,
-                   kt->kf_nnode, kt->kf_node_id, kt->kf_node_ptr, kt->kf_node_idx, kt->kf_cand,  kt->kf_ncand};
+  const TriScratch sc = tri_scratch(scratch, L);
+  // the map's rows as sides of NKF "pairs"; key-frame 1: its row, with the dense (u, v) / u_right tables and the mask of k_tri_rows
+  const KfTables t{ba->kf_uvr, map->kf_mp,
+                   KfSide{nullptr, nullptr, ba->kf_oct, kt->kf_angle, kt->kf_desc, nullptr,
+                          NodeList{kt->kf_nnode, kt->kf_node_id, kt->kf_node_ptr, kt->kf_node_idx, N, NN}},
+                   KfPointSide{ba->kf_pose, nullptr, nullptr, kt->kf_depth, ba->kf_oct, kt->kf_cand, kt->kf_ncand, N, k}};
+  KfSide side1 = t.match.pair(kf_row);
+  KfPointSide point1 = t.point.pair(kf_row);
+  side1.uv = point1.uv = sc.uv1;
+  side1.ur = point1.ur = sc.ur1;
+  side1.has_mp = sc.mask;
   const AcceptOut ao{(u64*)out->new_pos, out->new_assoc, out->new_ref_kf, out->new_type, out->new_nb,   out->new_feat1, out->new_feat2, out->att_mp,
                      out->att_kf,        out->att_feat,  out->n_new,      out->n_attach, out->feat_new, out->nb_stats,  out->new_cap};
 
   if (n_nb > 0) {
     k_tri_pair_setup<<<1, 64, 0, c->stream>>>(make_pairk(cam), NKF, map->kf_valid, ba->kf_pose, ba->kf_twc, kf_row, conn_kf_dev, n_conn_dev,
-                                              conn_cap, first_nb, n_nb, mb, skip, rows, fmat, epi, out->fmat, out->epipole);
+                                              conn_cap, first_nb, n_nb, mb, sc.nb.skip, sc.nb.rows, sc.nb.fmat, sc.nb.epipole, out->fmat,
+                                              out->epipole);
     GL_HIP(hipGetLastError());
   }
-  k_tri_rows<<<1 + n_nb, ROW_T, 0, c->stream>>>(N, NN, k, kf_row, n_nb, t, skip, rows, uv1, ur1, mask, s2, out->feat_new, out->n_new,
+  k_tri_rows<<<1 + n_nb, ROW_T, 0, c->stream>>>(kf_row, n_nb, t, sc.nb.skip, sc.nb.rows, side1, sc.side2, sc.point2, out->feat_new, out->n_new,
                                                 out->n_attach, out->status);
   GL_HIP(hipGetLastError());
-  const size_t f1 = (size_t)kf_row * N;
   for (int j = 0; j < n_nb; ++j) {
-    const size_t d = (size_t)j * N;
+    const PairWork nb = sc.nb.pair(j);
     // ORBmatcher matcher(0.6, false): no orientation check; bOnlyStereo = false (:266)
-    int rc = gl::launch_search_for_triangulation(
-        c, scale_factor, 1, N, N, NN, NN, uv1, ur1, ba->kf_oct + f1, kt->kf_angle + f1, kt->kf_desc + f1 * 32, mask, kt->kf_nnode + kf_row,
-        kt->kf_node_id + (size_t)kf_row * NN, kt->kf_node_ptr + (size_t)kf_row * (NN + 1), kt->kf_node_idx + f1, s2.uv + d * 2, s2.ur + d,
-        s2.oct + d, s2.angle + d, s2.desc + d * 32, s2.has_mp + d, s2.nnode + j, s2.nid + (size_t)j * NN, s2.nptr + (size_t)j * (NN + 1),
-        s2.nidx + d, fmat + (size_t)j * 9, epi + (size_t)j * 2, 0, 0, match, nm + j);
+    int rc = gl::launch_search_for_triangulation(c, scale_factor, 1, side1, sc.side2.pair(j), nb.fmat, nb.epipole, 0, 0, sc.match, nb.nmatches);
     if (rc != GL_OK) return rc;
-    k_tri_match_rows<<<1, ROW_T, 0, c->stream>>>(N, k, kf_row, j, t, ur1, s2, match, mo);
+    k_tri_match_rows<<<1, ROW_T, 0, c->stream>>>(point1, sc.point2.pair(j), sc.match, sc.m1, sc.m2, sc.idx1, sc.idx2, sc.count);
     GL_HIP(hipGetLastError());
-    rc = gl::launch_create_map_points(c, gl::G(gmm), cam, prm, scale_factor, N, mo.pose1, mo.uvr1, mo.depth1, mo.oct1, mo.pose2, mo.uvr2, mo.depth2,
-                                      mo.oct2, mo.cand1, mo.n1, mo.cand2, mo.n2, k, x3d, type, comp, S + o_cmp);
+    rc = gl::launch_create_map_points(c, gl::G(gmm), cam, prm, scale_factor, N, k, sc.m1, sc.m2, sc.pts, sc.create);
     if (rc != GL_OK) return rc;
-    k_tri_accept<<<1, ROW_T, 0, c->stream>>>(N, kf_row, j, first_nb + j, mp_base, skip, rows, nm, mo.count, mo.idx1, mo.idx2, (const u64*)x3d, type,
-                                             comp, mask, ao);
+    k_tri_accept<<<1, ROW_T, 0, c->stream>>>(N, kf_row, j, first_nb + j, mp_base, sc.nb.skip, sc.nb.rows, sc.nb.nmatches, sc.count, sc.idx1, sc.idx2,
+                                             (const u64*)sc.pts.x3d, sc.pts.type, sc.pts.comp, sc.mask, ao);
     GL_HIP(hipGetLastError());
   }
   return GL_OK;

@@ -22,40 +22,29 @@ namespace {
 using namespace gl_match;
 constexpr int T_B = 512;
 
-__global__ __launch_bounds__(T_B) void k_search_by_bow(int B, int N1, int N2, int NN1, int NN2, float nn_ratio, int check_orientation,
-                                                       const float* __restrict__ angle1_all, const uint8_t* __restrict__ desc1_all,
-                                                       const uint8_t* __restrict__ mp1_all, const int32_t* __restrict__ nn1_all,
-                                                       const int32_t* __restrict__ nid1_all, const int32_t* __restrict__ nptr1_all,
-                                                       const int32_t* __restrict__ nidx1_all, const float* __restrict__ angle2_all,
-                                                       const uint8_t* __restrict__ desc2_all, const int32_t* __restrict__ nn2_all,
-                                                       const int32_t* __restrict__ nid2_all, const int32_t* __restrict__ nptr2_all,
-                                                       const int32_t* __restrict__ nidx2_all, int32_t* __restrict__ match_all,
-                                                       int32_t* __restrict__ nmatches_all, int32_t* __restrict__ counters, uint4* __restrict__ cache_all,
+__global__ __launch_bounds__(T_B) void k_search_by_bow(int B, float nn_ratio, int check_orientation, KfSide side1, KfSide side2,
+                                                       int32_t* __restrict__ match_all, int32_t* __restrict__ nmatches_all,
+                                                       int32_t* __restrict__ counters, uint4* __restrict__ cache_all,
                                                        const int32_t* __restrict__ run_flag) {
   extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+  const int N1 = side1.nodes.N, N2 = side2.nodes.N;
   int32_t* owner = lds;            // N2: lowest query that claimed the frame feature in the previous round (INT_MAX: nobody)
   int32_t* owner_n = owner + N2;   // N2: being rebuilt
   int32_t* choice = owner_n + N2;  // N1 (by query): the frame feature an ACCEPTING query takes, else -1
-  const NodeQueries nodes(choice + N1, N1, NN1, NN2);
+  const NodeQueries nodes(choice + N1, N1, side1.nodes.NN, side2.nodes.NN);
   const int32_t *q_idx1 = nodes.q_idx1, *q_lo = nodes.q_lo, *q_hi = nodes.q_hi;
   __shared__ int s_changed, s_hist[32], s_keep[4], s_cnt[T_B / 64];
   const int f = blockIdx.x, tid = threadIdx.x;
   if (f >= B) return;
   if (run_flag && run_flag[f] == 0) return;  // (gl_track_frame_chain's trackKeyFrame fallback: only the frames that need it)
-  const uint32_t* desc1 = (const uint32_t*)(desc1_all + (size_t)f * N1 * 32);
-  const uint8_t* mp1 = mp1_all + (size_t)f * N1;
-  const uint32_t* desc2 = (const uint32_t*)(desc2_all + (size_t)f * N2 * 32);
-  const int nn1 = min(nn1_all[f], NN1), nn2 = min(nn2_all[f], NN2);
-  const int32_t* nid1 = nid1_all + (size_t)f * NN1;
-  const int32_t* nptr1 = nptr1_all + (size_t)f * (NN1 + 1);
-  const int32_t* nidx1 = nidx1_all + (size_t)f * N1;
-  const int32_t* nid2 = nid2_all + (size_t)f * NN2;
-  const int32_t* nptr2 = nptr2_all + (size_t)f * (NN2 + 1);
-  const int32_t* nidx2 = nidx2_all + (size_t)f * N2;
+  const KfSide s1 = side1.pair(f), s2 = side2.pair(f);  // (side 2 is a frame: no uv / ur / oct / has_mp)
+  const uint32_t *desc1 = (const uint32_t*)s1.desc, *desc2 = (const uint32_t*)s2.desc;
+  const uint8_t* mp1 = s1.has_mp;
+  const int32_t* nidx2 = s2.nodes.node_idx;
 
   // ---- queries: the key-frame's features that hold a valid map point ----
   for (int a = tid; a < N1; a += T_B) choice[a] = -1;
-  const int nq = nodes.setup<T_B>(tid, N1, N2, nn1, nn2, nid1, nptr1, nidx1, nid2, nptr2, [&](int i1) { return mp1[i1] != 0; });
+  const int nq = nodes.setup<T_B>(tid, s1.nodes, s2.nodes, [&](int i1) { return mp1[i1] != 0; });
   for (int i = tid; i < N2; i += T_B) owner[i] = INT_MAX;
   __syncthreads();
 
@@ -184,10 +173,8 @@ __global__ __launch_bounds__(T_B) void k_search_by_bow(int B, int N1, int N2, in
   // ---- rotation consistency (:362-374, :391-405) ------------------------------------------------------------------------
   // (in the fixed point every accepting query owns its choice)
   if (check_orientation) {
-    const float* angle1 = angle1_all + (size_t)f * N1;
-    const float* angle2 = angle2_all + (size_t)f * N2;
     rotation_filter<T_B>(
-        tid, nq, s_hist, s_keep, [&](int m) { return choice[m] >= 0; }, [&](int m) { return angle1[q_idx1[m]] - angle2[choice[m]]; },
+        tid, nq, s_hist, s_keep, [&](int m) { return choice[m] >= 0; }, [&](int m) { return s1.angle[q_idx1[m]] - s2.angle[choice[m]]; },
         [&](int m) { choice[m] = -1; });
   }
 
@@ -211,23 +198,25 @@ extern "C" int gl_search_by_bow(gl_ctx_t* ctx, float nn_ratio, int check_orienta
                                 const int32_t* node_id1_dev, const int32_t* node_ptr1_dev, const int32_t* node_idx1_dev,
                                 const float* angle2_dev, const uint8_t* desc2_dev, const int32_t* nnode2_dev, const int32_t* node_id2_dev,
                                 const int32_t* node_ptr2_dev, const int32_t* node_idx2_dev, int32_t* match21_dev, int32_t* nmatches_dev) {
-  return gl::launch_bow_gated(ctx, nn_ratio, check_orientation, B, N1, N2, NN1, NN2, angle1_dev, desc1_dev, has_mp1_dev, nnode1_dev, node_id1_dev,
-                              node_ptr1_dev, node_idx1_dev, angle2_dev, desc2_dev, nnode2_dev, node_id2_dev, node_ptr2_dev, node_idx2_dev, match21_dev,
-                              nmatches_dev, nullptr);
+  return gl::launch_bow_gated(
+      ctx, nn_ratio, check_orientation, B,
+      KfSide{nullptr, nullptr, nullptr, angle1_dev, desc1_dev, has_mp1_dev, NodeList{nnode1_dev, node_id1_dev, node_ptr1_dev, node_idx1_dev, N1, NN1}},
+      KfSide{nullptr, nullptr, nullptr, angle2_dev, desc2_dev, nullptr, NodeList{nnode2_dev, node_id2_dev, node_ptr2_dev, node_idx2_dev, N2, NN2}},
+      match21_dev, nmatches_dev, nullptr);
 }
 
-// the same with a per-frame switch (run_flag B int32, 0: the frame's workgroup returns at once and writes nothing; null: every frame)
-int gl::launch_bow_gated(gl_ctx_t* ctx, float nn_ratio, int check_orientation, int B, int N1, int N2, int NN1, int NN2, const float* angle1_dev,
-                         const uint8_t* desc1_dev, const uint8_t* has_mp1_dev, const int32_t* nnode1_dev, const int32_t* node_id1_dev,
-                         const int32_t* node_ptr1_dev, const int32_t* node_idx1_dev, const float* angle2_dev, const uint8_t* desc2_dev,
-                         const int32_t* nnode2_dev, const int32_t* node_id2_dev, const int32_t* node_ptr2_dev, const int32_t* node_idx2_dev,
-                         int32_t* match21_dev, int32_t* nmatches_dev, const int32_t* run_flag) {
+// the same with a per-frame switch (run_flag B int32, 0: the frame's workgroup returns at once and writes nothing; null: every frame).
+// The sides' uv / ur / oct and side 2's has_mp are not read.
+int gl::launch_bow_gated(gl_ctx_t* ctx, float nn_ratio, int check_orientation, int B, const KfSide& side1, const KfSide& side2, int32_t* match21_dev,
+                         int32_t* nmatches_dev, const int32_t* run_flag) {
+  const NodeList &l1 = side1.nodes, &l2 = side2.nodes;
+  const int N1 = l1.N, N2 = l2.N, NN1 = l1.NN, NN2 = l2.NN;
   GL_REQUIRE(ctx, "null context");
   if (B == 0) return GL_OK;
   GL_REQUIRE(B > 0 && N1 >= 1 && N2 >= 1 && NN1 >= 1 && NN2 >= 1, "bad B / N1 / N2 / NN1 / NN2");
   GL_REQUIRE(N1 <= 4096 && N2 <= 4096, "N1 / N2 above the on-chip capacity (4096 features per frame)");
-  GL_REQUIRE(angle1_dev && desc1_dev && has_mp1_dev && nnode1_dev && node_id1_dev && node_ptr1_dev && node_idx1_dev && angle2_dev &&
-                 desc2_dev && nnode2_dev && node_id2_dev && node_ptr2_dev && node_idx2_dev && match21_dev && nmatches_dev,
+  GL_REQUIRE(side1.angle && side1.desc && side1.has_mp && l1.nnode && l1.node_id && l1.node_ptr && l1.node_idx && side2.angle && side2.desc &&
+                 l2.nnode && l2.node_id && l2.node_ptr && l2.node_idx && match21_dev && nmatches_dev,
              "null buffer");
   gl::Ctx* c = gl::C(ctx);
   GL_HIP(hipSetDevice(c->device));
@@ -239,9 +228,8 @@ int gl::launch_bow_gated(gl_ctx_t* ctx, float nn_ratio, int check_orientation, i
     const int rc = gl::ctx_scratch(c, (size_t)B * N1 * sizeof(uint4), &cache, gl::SCRATCH_CACHE);
     if (rc != GL_OK) return rc;
   }
-  k_search_by_bow<<<B, T_B, lds, c->stream>>>(B, N1, N2, NN1, NN2, nn_ratio, check_orientation, angle1_dev, desc1_dev, has_mp1_dev, nnode1_dev,
-                                              node_id1_dev, node_ptr1_dev, node_idx1_dev, angle2_dev, desc2_dev, nnode2_dev, node_id2_dev,
-                                              node_ptr2_dev, node_idx2_dev, match21_dev, nmatches_dev, c->counters, (uint4*)cache, run_flag);
+  k_search_by_bow<<<B, T_B, lds, c->stream>>>(B, nn_ratio, check_orientation, side1, side2, match21_dev, nmatches_dev, c->counters, (uint4*)cache,
+                                              run_flag);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

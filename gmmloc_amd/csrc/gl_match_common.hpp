@@ -275,6 +275,45 @@ __device__ __forceinline__ int node_of(const int32_t* __restrict__ ptr, int nn, 
   return lo;
 }
 
+// p + at x stride.  A member nobody reads is null: it stays so on the host; a kernel does not pay a select per pointer for a value it
+// never uses (k_search_for_triangulation: two spilled scalar registers).
+template <class V>
+__host__ __device__ __forceinline__ const V* pair_row(const V* p, size_t at, size_t stride) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return p + at * stride;
+#else
+  return p ? p + at * stride : p;
+#endif
+}
+
+// One side's feature vector for B pairs, N features and NN node slots a pair
+struct NodeList {
+  const int32_t* nnode;     // B
+  const int32_t* node_id;   // B x NN, ascending
+  const int32_t* node_ptr;  // B x (NN + 1)
+  const int32_t* node_idx;  // B x N, list order
+  int N, NN;
+};
+
+// What a node matcher reads of one key-frame (or frame) of B pairs.  A matcher that does not read a member leaves it null.
+struct KfSide {
+  const double* uv;       // B x N x 2
+  const float* ur;        // B x N
+  const int32_t* oct;     // B x N
+  const float* angle;     // B x N
+  const uint8_t* desc;    // B x N x 32
+  const uint8_t* has_mp;  // B x N
+  NodeList nodes;         // (its N, NN are the side's)
+  // the side of pair f alone: THE place a side's strides are applied
+  __host__ __device__ __forceinline__ KfSide pair(int f) const {
+    const size_t N = (size_t)nodes.N, NN = (size_t)nodes.NN;
+    return KfSide{pair_row(uv, f, 2 * N),    pair_row(ur, f, N),   pair_row(oct, f, N), pair_row(angle, f, N),
+                  pair_row(desc, f, 32 * N), pair_row(has_mp, f, N),
+                  NodeList{pair_row(nodes.nnode, f, 1), pair_row(nodes.node_id, f, NN), pair_row(nodes.node_ptr, f, NN + 1),
+                           pair_row(nodes.node_idx, f, N), nodes.N, nodes.NN}};
+  }
+};
+
 struct NodeQueries {
   static __host__ __device__ constexpr size_t words(int N1, int NN1, int NN2) { return 3 * (size_t)N1 + (size_t)NN1 + 2 * (size_t)NN2 + 2; }
   // LDS of a whole node matcher in bytes: owner, owner_n (N2 each), choice (N1), then the tables below
@@ -291,24 +330,23 @@ struct NodeQueries {
   __device__ __forceinline__ NodeQueries(int32_t* lds, int N1, int NN1, int NN2)
       : q_idx1(lds), q_lo(lds + N1), q_hi(lds + 2 * N1), s_nptr1(lds + 3 * N1), s_nid2(s_nptr1 + NN1 + 1), s_nptr2(s_nid2 + NN2) {}
 
-  // eligible(i1): may feature i1 of key-frame 1 ask at all.  Returns the number of queries; they are written by then, a barrier of
-  // the caller makes them visible.
+  // l1, l2: the two lists of ONE pair.  eligible(i1): may feature i1 of key-frame 1 ask at all.  Returns the number of queries; they
+  // are written by then, a barrier of the caller makes them visible.
   template <int T, class Eligible>
-  __device__ __forceinline__ int setup(int tid, int N1, int N2, int nn1, int nn2, const int32_t* __restrict__ nid1,
-                                       const int32_t* __restrict__ nptr1, const int32_t* __restrict__ nidx1, const int32_t* __restrict__ nid2,
-                                       const int32_t* __restrict__ nptr2, Eligible eligible) const {
-    const int nq = nn1 > 0 ? min(nptr1[nn1], N1) : 0;  // list entries of key-frame 1
-    for (int i = tid; i <= nn1; i += T) s_nptr1[i] = nptr1[i];
+  __device__ __forceinline__ int setup(int tid, const NodeList& l1, const NodeList& l2, Eligible eligible) const {
+    const int N1 = l1.N, N2 = l2.N, nn1 = min(*l1.nnode, l1.NN), nn2 = min(*l2.nnode, l2.NN);
+    const int nq = nn1 > 0 ? min(l1.node_ptr[nn1], N1) : 0;  // list entries of key-frame 1
+    for (int i = tid; i <= nn1; i += T) s_nptr1[i] = l1.node_ptr[i];
     for (int i = tid; i <= nn2; i += T) {
-      s_nptr2[i] = nptr2[i];
-      if (i < nn2) s_nid2[i] = nid2[i];
+      s_nptr2[i] = l2.node_ptr[i];
+      if (i < nn2) s_nid2[i] = l2.node_id[i];
     }
     __syncthreads();
     for (int a = tid; a < N1; a += T) {
       int idx1 = -1, lo = 0, hi = 0;
       if (a < nq) {
         const int n1 = node_of(s_nptr1, nn1, a);
-        const int id = nid1[n1];
+        const int id = l1.node_id[n1];
         int l = 0, h = nn2;  // lower_bound of id in nid2
         while (l < h) {
           const int mid = (l + h) >> 1;
@@ -316,7 +354,7 @@ struct NodeQueries {
           else h = mid;
         }
         if (l < nn2 && s_nid2[l] == id) {
-          const int i1 = nidx1[a];
+          const int i1 = l1.node_idx[a];
           if (i1 >= 0 && i1 < N1 && eligible(i1)) {
             idx1 = i1;
             lo = s_nptr2[l];
@@ -436,6 +474,66 @@ __device__ __forceinline__ void count_matches(int tid, int cnt, int* s_cnt, int3
       atomicAdd(&counters[1], rounds);
       atomicAdd(&counters[2], 1);
     }
+  }
+}
+
+// ---- matches -> the per-match arrays of gl_create_map_points -----------------------------------------------------------------------
+// What the triangulation reads of one key-frame of B pairs (N features, k candidate components a feature)
+struct KfPointSide {
+  const double* pose;    // B x 7
+  const double* uv;      // B x N x 2
+  const float* ur;       // B x N
+  const float* depth;    // B x N
+  const int32_t* oct;    // B x N
+  const int32_t* cand;   // B x N x k
+  const int32_t* ncand;  // B x N
+  int N, k;
+  __host__ __device__ __forceinline__ KfPointSide pair(int f) const {
+    const size_t Nz = (size_t)N;
+    return KfPointSide{pair_row(pose, f, 7),  pair_row(uv, f, 2 * Nz),   pair_row(ur, f, Nz),    pair_row(depth, f, Nz),
+                       pair_row(oct, f, Nz), pair_row(cand, f, Nz * k), pair_row(ncand, f, Nz), N, k};
+  }
+};
+// The per-match arrays of one side: a slot per match
+struct MatchSide {
+  double* pose;    // x 7
+  double* uvr;     // x 3
+  float* depth;
+  int32_t* oct;
+  int32_t* cand;   // x k
+  int32_t* ncand;
+};
+// What gl_create_map_points leaves per match
+struct MatchPoints {
+  double* x3d;  // x 3
+  int32_t* type;
+  int32_t* comp;
+};
+// match (i, j) of pair f -> slot `at`: what Localization::createMapPoints reads per match (localization_opt.cpp:286-420)
+__device__ __forceinline__ void gather_match(const KfPointSide& side1, const KfPointSide& side2, int f, int i, int j, const MatchSide& oa,
+                                             const MatchSide& ob, int at) {
+  const KfPointSide a = side1.pair(f), b = side2.pair(f);
+  const int k = a.k;
+#pragma unroll
+  for (int r = 0; r < 7; ++r) {
+    oa.pose[(size_t)at * 7 + r] = a.pose[r];
+    ob.pose[(size_t)at * 7 + r] = b.pose[r];
+  }
+  oa.uvr[(size_t)at * 3] = a.uv[(size_t)i * 2];
+  oa.uvr[(size_t)at * 3 + 1] = a.uv[(size_t)i * 2 + 1];
+  oa.uvr[(size_t)at * 3 + 2] = (double)a.ur[i];
+  ob.uvr[(size_t)at * 3] = b.uv[(size_t)j * 2];
+  ob.uvr[(size_t)at * 3 + 1] = b.uv[(size_t)j * 2 + 1];
+  ob.uvr[(size_t)at * 3 + 2] = (double)b.ur[j];
+  oa.depth[at] = a.depth[i];
+  ob.depth[at] = b.depth[j];
+  oa.oct[at] = a.oct[i];
+  ob.oct[at] = b.oct[j];
+  oa.ncand[at] = a.ncand[i];
+  ob.ncand[at] = b.ncand[j];
+  for (int c = 0; c < k; ++c) {
+    oa.cand[(size_t)at * k + c] = a.cand[(size_t)i * k + c];
+    ob.cand[(size_t)at * k + c] = b.cand[(size_t)j * k + c];
   }
 }
 

@@ -19,6 +19,7 @@
 #include <climits>
 
 #include "gl_internal.hpp"
+#include "gl_map_dev.hpp"  // block_excl_scan
 #include "gl_match_common.hpp"
 
 namespace {
@@ -27,53 +28,44 @@ using namespace gl_match;
 constexpr int T_T = 512;
 
 struct TriP {
-  int N1, N2, NN1, NN2, only_stereo, check_orientation;
+  int only_stereo, check_orientation;
   float sf[8], sigma2[8];
 };
 
+// (positional __restrict__ parameters, which the launcher unpacks: two KfSide by value spill scalar registers, r16_kf_side_kernel_meta.txt)
 __global__ __launch_bounds__(T_T) void k_search_for_triangulation(
-    TriP P, int B, const double* __restrict__ uv1_all, const float* __restrict__ ur1_all, const int32_t* __restrict__ oct1_all,
-    const float* __restrict__ angle1_all, const uint8_t* __restrict__ desc1_all, const uint8_t* __restrict__ mp1_all,
-    const int32_t* __restrict__ nn1_all, const int32_t* __restrict__ nid1_all, const int32_t* __restrict__ nptr1_all,
-    const int32_t* __restrict__ nidx1_all, const double* __restrict__ uv2_all, const float* __restrict__ ur2_all,
-    const int32_t* __restrict__ oct2_all, const float* __restrict__ angle2_all, const uint8_t* __restrict__ desc2_all,
-    const uint8_t* __restrict__ mp2_all, const int32_t* __restrict__ nn2_all, const int32_t* __restrict__ nid2_all,
-    const int32_t* __restrict__ nptr2_all, const int32_t* __restrict__ nidx2_all, const double* __restrict__ fmat_all,
-    const float* __restrict__ epi_all, int32_t* __restrict__ match_all, int32_t* __restrict__ nmatches_all, int32_t* __restrict__ counters, uint4* __restrict__ cache_all) {
+    TriP P, int B, int N1, int N2, int NN1, int NN2, const double* __restrict__ uv1_all, const float* __restrict__ ur1_all,
+    const int32_t* __restrict__ oct1_all, const float* __restrict__ angle1_all, const uint8_t* __restrict__ desc1_all,
+    const uint8_t* __restrict__ mp1_all, const int32_t* __restrict__ nn1_all, const int32_t* __restrict__ nid1_all,
+    const int32_t* __restrict__ nptr1_all, const int32_t* __restrict__ nidx1_all, const double* __restrict__ uv2_all,
+    const float* __restrict__ ur2_all, const int32_t* __restrict__ oct2_all, const float* __restrict__ angle2_all,
+    const uint8_t* __restrict__ desc2_all, const uint8_t* __restrict__ mp2_all, const int32_t* __restrict__ nn2_all,
+    const int32_t* __restrict__ nid2_all, const int32_t* __restrict__ nptr2_all, const int32_t* __restrict__ nidx2_all,
+    const double* __restrict__ fmat_all, const float* __restrict__ epi_all, int32_t* __restrict__ match_all, int32_t* __restrict__ nmatches_all,
+    int32_t* __restrict__ counters, uint4* __restrict__ cache_all) {
   extern __shared__ __attribute__((aligned(16))) int32_t lds[];
-  const int N1 = P.N1, N2 = P.N2;
   int32_t* owner = lds;             // N2: lowest query that picked the feature in the previous round (-1: not available at all)
   int32_t* owner_n = owner + N2;    // N2: being rebuilt
   int32_t* choice = owner_n + N2;   // N1 (by query)
-  const NodeQueries nodes(choice + N1, N1, P.NN1, P.NN2);
+  const NodeQueries nodes(choice + N1, N1, NN1, NN2);
   const int32_t *q_idx1 = nodes.q_idx1, *q_lo = nodes.q_lo, *q_hi = nodes.q_hi;
   __shared__ int s_changed, s_hist[32], s_keep[4], s_cnt[T_T / 64];
   const int f = blockIdx.x, tid = threadIdx.x;
   if (f >= B) return;
-  const double* uv1 = uv1_all + (size_t)f * N1 * 2;
-  const float* ur1 = ur1_all + (size_t)f * N1;
-  const int32_t* oct1 = oct1_all + (size_t)f * N1;
-  const uint32_t* desc1 = (const uint32_t*)(desc1_all + (size_t)f * N1 * 32);
-  const uint8_t* mp1 = mp1_all + (size_t)f * N1;
-  const double* uv2 = uv2_all + (size_t)f * N2 * 2;
-  const float* ur2 = ur2_all + (size_t)f * N2;
-  const int32_t* oct2 = oct2_all + (size_t)f * N2;
-  const uint32_t* desc2 = (const uint32_t*)(desc2_all + (size_t)f * N2 * 32);
-  const uint8_t* mp2 = mp2_all + (size_t)f * N2;
-  const int nn1 = min(nn1_all[f], P.NN1), nn2 = min(nn2_all[f], P.NN2);
-  const int32_t* nid1 = nid1_all + (size_t)f * P.NN1;
-  const int32_t* nptr1 = nptr1_all + (size_t)f * (P.NN1 + 1);
-  const int32_t* nidx1 = nidx1_all + (size_t)f * N1;
-  const int32_t* nid2 = nid2_all + (size_t)f * P.NN2;
-  const int32_t* nptr2 = nptr2_all + (size_t)f * (P.NN2 + 1);
-  const int32_t* nidx2 = nidx2_all + (size_t)f * N2;
+  const KfSide s1 = KfSide{uv1_all, ur1_all, oct1_all, angle1_all, desc1_all, mp1_all, NodeList{nn1_all, nid1_all, nptr1_all, nidx1_all, N1, NN1}}.pair(f);
+  const KfSide s2 = KfSide{uv2_all, ur2_all, oct2_all, angle2_all, desc2_all, mp2_all, NodeList{nn2_all, nid2_all, nptr2_all, nidx2_all, N2, NN2}}.pair(f);
+  const double *uv1 = s1.uv, *uv2 = s2.uv;
+  const float *ur1 = s1.ur, *ur2 = s2.ur;
+  const int32_t *oct1 = s1.oct, *oct2 = s2.oct, *nidx2 = s2.nodes.node_idx;
+  const uint32_t *desc1 = (const uint32_t*)s1.desc, *desc2 = (const uint32_t*)s2.desc;
+  const uint8_t *mp1 = s1.has_mp, *mp2 = s2.has_mp;
   const double* F = fmat_all + (size_t)f * 9;
   const float ex = epi_all[2 * f], ey = epi_all[2 * f + 1];
 
   // ---- queries: list entry a of key-frame 1 -> its feature and the partner list of the same node in key-frame 2 ----
   // (who may ask: not the features with a map point, nor the mono ones under only-stereo)
   for (int a = tid; a < N1; a += T_T) choice[a] = -1;
-  const int nq = nodes.setup<T_T>(tid, N1, N2, nn1, nn2, nid1, nptr1, nidx1, nid2, nptr2,
+  const int nq = nodes.setup<T_T>(tid, s1.nodes, s2.nodes,
                                   [&](int i1) { return oct1[i1] >= 0 && !mp1[i1] && !(P.only_stereo && !(ur1[i1] >= 0)); });
   for (int i = tid; i < N2; i += T_T) owner[i] = (oct2[i] >= 0 && !mp2[i] && !(P.only_stereo && !(ur2[i] >= 0))) ? INT_MAX : -1;
   __syncthreads();
@@ -230,10 +222,8 @@ __global__ __launch_bounds__(T_T) void k_search_for_triangulation(
   // ---- rotation consistency (:235-246, :264-281) ----------------------------------------------------------------------
   // (a query keeps its choice iff it owns it: in the fixed point every choice is owned by its query)
   if (P.check_orientation) {
-    const float* angle1 = angle1_all + (size_t)f * N1;
-    const float* angle2 = angle2_all + (size_t)f * N2;
     rotation_filter<T_T>(
-        tid, nq, s_hist, s_keep, [&](int m) { return choice[m] >= 0; }, [&](int m) { return angle1[q_idx1[m]] - angle2[choice[m]]; },
+        tid, nq, s_hist, s_keep, [&](int m) { return choice[m] >= 0; }, [&](int m) { return s1.angle[q_idx1[m]] - s2.angle[choice[m]]; },
         [&](int m) { choice[m] = -1; });
   }
 
@@ -279,73 +269,27 @@ __global__ __launch_bounds__(256) void k_tri_offsets(int B, const int32_t* __res
   }
 }
 
-struct TriKf {  // one key-frame side of the gather (strides N, k candidates)
-  const double* pose;    // B x 7
-  const double* uv;      // B x N x 2
-  const float* ur;       // B x N
-  const float* depth;    // B x N
-  const int32_t* oct;    // B x N
-  const int32_t* cand;   // B x N x k
-  const int32_t* ncand;  // B x N
-};
-struct TriOut {
-  double* pose;
-  double* uvr;
-  float* depth;
-  int32_t* oct;
-  int32_t* cand;
-  int32_t* ncand;
-};
-
-__global__ __launch_bounds__(256) void k_tri_gather(int B, int N1, int N2, int k, int cap, const int32_t* __restrict__ match_all,
-                                                    const int32_t* __restrict__ pair_off, TriKf a, TriKf b, TriOut oa, TriOut ob,
-                                                    int32_t* __restrict__ pair_of, int32_t* __restrict__ idx1_of, int32_t* __restrict__ idx2_of) {
-  __shared__ int s_w[4], s_base;
-  const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__global__ __launch_bounds__(256) void k_tri_gather(int B, int cap, const int32_t* __restrict__ match_all, const int32_t* __restrict__ pair_off,
+                                                    KfPointSide a, KfPointSide b, MatchSide oa, MatchSide ob, int32_t* __restrict__ pair_of,
+                                                    int32_t* __restrict__ idx1_of, int32_t* __restrict__ idx2_of) {
+  __shared__ int s_w[4];
+  const int f = blockIdx.x, tid = threadIdx.x;
   if (f >= B) return;
-  const int32_t* match = match_all + (size_t)f * N1;
-  if (tid == 0) s_base = pair_off[f];
-  __syncthreads();
-  for (int i0 = 0; i0 < N1; i0 += 256) {
+  const int32_t* match = match_all + (size_t)f * a.N;
+  int run = pair_off[f];
+  for (int i0 = 0; i0 < a.N; i0 += 256) {
     const int i = i0 + tid;
-    const int j = i < N1 ? match[i] : -1;
-    const bool on = j >= 0 && j < N2;
-    const unsigned long long bal = __ballot(on);
-    if (lane == 0) s_w[wave] = __popcll(bal);
-    __syncthreads();
-    int before = s_base;
-    for (int w = 0; w < wave; ++w) before += s_w[w];
-    const int at = before + __popcll(bal & ((1ull << lane) - 1ull));
+    const int j = i < a.N ? match[i] : -1;
+    const bool on = j >= 0 && j < b.N;
+    int total;
+    const int at = run + gl::mapdev::block_excl_scan<256, int>(on ? 1 : 0, s_w, tid, &total);
+    run += total;
     if (on && at < cap) {
-      const size_t g1 = (size_t)f * N1 + i, g2 = (size_t)f * N2 + j;
-#pragma unroll
-      for (int r = 0; r < 7; ++r) {
-        oa.pose[(size_t)at * 7 + r] = a.pose[(size_t)f * 7 + r];
-        ob.pose[(size_t)at * 7 + r] = b.pose[(size_t)f * 7 + r];
-      }
-      oa.uvr[(size_t)at * 3] = a.uv[g1 * 2];
-      oa.uvr[(size_t)at * 3 + 1] = a.uv[g1 * 2 + 1];
-      oa.uvr[(size_t)at * 3 + 2] = (double)a.ur[g1];
-      ob.uvr[(size_t)at * 3] = b.uv[g2 * 2];
-      ob.uvr[(size_t)at * 3 + 1] = b.uv[g2 * 2 + 1];
-      ob.uvr[(size_t)at * 3 + 2] = (double)b.ur[g2];
-      oa.depth[at] = a.depth[g1];
-      ob.depth[at] = b.depth[g2];
-      oa.oct[at] = a.oct[g1];
-      ob.oct[at] = b.oct[g2];
-      oa.ncand[at] = a.ncand[g1];
-      ob.ncand[at] = b.ncand[g2];
-      for (int c = 0; c < k; ++c) {
-        oa.cand[(size_t)at * k + c] = a.cand[g1 * k + c];
-        ob.cand[(size_t)at * k + c] = b.cand[g2 * k + c];
-      }
+      gather_match(a, b, f, i, j, oa, ob, at);
       pair_of[at] = f;
       idx1_of[at] = i;
       idx2_of[at] = j;
     }
-    __syncthreads();
-    if (tid == 0) s_base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();
   }
 }
 
@@ -372,35 +316,27 @@ extern "C" int gl_gather_triangulation_matches(gl_ctx_t* ctx, int B, int N1, int
   gl::Ctx* c = gl::C(ctx);
   GL_HIP(hipSetDevice(c->device));
   k_tri_offsets<<<1, 256, 0, c->stream>>>(B, nmatches_dev, pair_off_dev);
-  k_tri_gather<<<B, 256, 0, c->stream>>>(B, N1, N2, k, cap, match12_dev, pair_off_dev,
-                                         TriKf{pose1_dev, uv1_dev, ur1_dev, depth1_dev, oct1_dev, cand1_dev, ncand1_dev},
-                                         TriKf{pose2_dev, uv2_dev, ur2_dev, depth2_dev, oct2_dev, cand2_dev, ncand2_dev},
-                                         TriOut{m_pose1_dev, m_uvr1_dev, m_depth1_dev, m_oct1_dev, m_cand1_dev, m_n1_dev},
-                                         TriOut{m_pose2_dev, m_uvr2_dev, m_depth2_dev, m_oct2_dev, m_cand2_dev, m_n2_dev}, m_pair_dev, m_idx1_dev,
+  k_tri_gather<<<B, 256, 0, c->stream>>>(B, cap, match12_dev, pair_off_dev,
+                                         KfPointSide{pose1_dev, uv1_dev, ur1_dev, depth1_dev, oct1_dev, cand1_dev, ncand1_dev, N1, k},
+                                         KfPointSide{pose2_dev, uv2_dev, ur2_dev, depth2_dev, oct2_dev, cand2_dev, ncand2_dev, N2, k},
+                                         MatchSide{m_pose1_dev, m_uvr1_dev, m_depth1_dev, m_oct1_dev, m_cand1_dev, m_n1_dev},
+                                         MatchSide{m_pose2_dev, m_uvr2_dev, m_depth2_dev, m_oct2_dev, m_cand2_dev, m_n2_dev}, m_pair_dev, m_idx1_dev,
                                          m_idx2_dev);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
 
-// k_search_for_triangulation for the callers inside the library (gl_map_tri.hip): arguments as gl_search_for_triangulation's and
+// k_search_for_triangulation for the callers inside the library (gl_map_tri.hip): the values as gl_search_for_triangulation's and
 // already checked, the context's device current.  The round cache is the launcher's own (SCRATCH_CACHE).
-int gl::launch_search_for_triangulation(Ctx* c, float scale_factor, int B, int N1, int N2, int NN1, int NN2, const double* uv1_dev,
-                                        const float* ur1_dev, const int32_t* oct1_dev, const float* angle1_dev, const uint8_t* desc1_dev,
-                                        const uint8_t* has_mp1_dev, const int32_t* nnode1_dev, const int32_t* node_id1_dev,
-                                        const int32_t* node_ptr1_dev, const int32_t* node_idx1_dev, const double* uv2_dev, const float* ur2_dev,
-                                        const int32_t* oct2_dev, const float* angle2_dev, const uint8_t* desc2_dev, const uint8_t* has_mp2_dev,
-                                        const int32_t* nnode2_dev, const int32_t* node_id2_dev, const int32_t* node_ptr2_dev,
-                                        const int32_t* node_idx2_dev, const double* fmat_dev, const float* epipole_dev, int only_stereo,
-                                        int check_orientation, int32_t* match12_dev, int32_t* nmatches_dev) {
+int gl::launch_search_for_triangulation(Ctx* c, float scale_factor, int B, const KfSide& side1, const KfSide& side2, const double* fmat_dev,
+                                        const float* epipole_dev, int only_stereo, int check_orientation, int32_t* match12_dev,
+                                        int32_t* nmatches_dev) {
   TriP P;
-  P.N1 = N1;
-  P.N2 = N2;
-  P.NN1 = NN1;
-  P.NN2 = NN2;
   P.only_stereo = only_stereo;
   P.check_orientation = check_orientation;
   pyramid_scales(scale_factor, P.sf, P.sigma2, nullptr);
-  const size_t lds = NodeQueries::matcher_lds(N1, N2, NN1, NN2);
+  const int N1 = side1.nodes.N;
+  const size_t lds = NodeQueries::matcher_lds(N1, side2.nodes.N, side1.nodes.NN, side2.nodes.NN);
   GL_REQUIRE_LDS(c, lds);
   GL_HIP(gl::ensure_dynamic_lds(c, (const void*)k_search_for_triangulation, lds));
   void* cache = nullptr;  // 16 bytes per query: its three best partners of round 1 (the kernel's round loop)
@@ -408,9 +344,10 @@ int gl::launch_search_for_triangulation(Ctx* c, float scale_factor, int B, int N
     const int rc = gl::ctx_scratch(c, (size_t)B * N1 * sizeof(uint4), &cache, gl::SCRATCH_CACHE);
     if (rc != GL_OK) return rc;
   }
-  k_search_for_triangulation<<<B, T_T, lds, c->stream>>>(P, B, uv1_dev, ur1_dev, oct1_dev, angle1_dev, desc1_dev, has_mp1_dev, nnode1_dev,
-                                                        node_id1_dev, node_ptr1_dev, node_idx1_dev, uv2_dev, ur2_dev, oct2_dev, angle2_dev,
-                                                        desc2_dev, has_mp2_dev, nnode2_dev, node_id2_dev, node_ptr2_dev, node_idx2_dev, fmat_dev,
+  const NodeList &l1 = side1.nodes, &l2 = side2.nodes;
+  k_search_for_triangulation<<<B, T_T, lds, c->stream>>>(P, B, N1, l2.N, l1.NN, l2.NN, side1.uv, side1.ur, side1.oct, side1.angle, side1.desc,
+                                                        side1.has_mp, l1.nnode, l1.node_id, l1.node_ptr, l1.node_idx, side2.uv, side2.ur, side2.oct,
+                                                        side2.angle, side2.desc, side2.has_mp, l2.nnode, l2.node_id, l2.node_ptr, l2.node_idx, fmat_dev,
                                                         epipole_dev, match12_dev, nmatches_dev, c->counters, (uint4*)cache);
   GL_HIP(hipGetLastError());
   return GL_OK;
@@ -435,8 +372,9 @@ extern "C" int gl_search_for_triangulation(gl_ctx_t* ctx, float scale_factor, in
              "null buffer");
   gl::Ctx* c = gl::C(ctx);
   GL_HIP(hipSetDevice(c->device));
-  return gl::launch_search_for_triangulation(c, scale_factor, B, N1, N2, NN1, NN2, uv1_dev, ur1_dev, oct1_dev, angle1_dev, desc1_dev, has_mp1_dev,
-                                             nnode1_dev, node_id1_dev, node_ptr1_dev, node_idx1_dev, uv2_dev, ur2_dev, oct2_dev, angle2_dev,
-                                             desc2_dev, has_mp2_dev, nnode2_dev, node_id2_dev, node_ptr2_dev, node_idx2_dev, fmat_dev, epipole_dev,
-                                             only_stereo, check_orientation, match12_dev, nmatches_dev);
+  return gl::launch_search_for_triangulation(
+      c, scale_factor, B,
+      KfSide{uv1_dev, ur1_dev, oct1_dev, angle1_dev, desc1_dev, has_mp1_dev, NodeList{nnode1_dev, node_id1_dev, node_ptr1_dev, node_idx1_dev, N1, NN1}},
+      KfSide{uv2_dev, ur2_dev, oct2_dev, angle2_dev, desc2_dev, has_mp2_dev, NodeList{nnode2_dev, node_id2_dev, node_ptr2_dev, node_idx2_dev, N2, NN2}},
+      fmat_dev, epipole_dev, only_stereo, check_orientation, match12_dev, nmatches_dev);
 }

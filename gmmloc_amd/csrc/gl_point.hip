@@ -652,11 +652,8 @@ int gl::launch_check_map_association(Ctx* c, const Gmm* g, const gl_camera* cam,
 // the three kernels of gl_create_map_points for the callers inside the library (gl_map_tri.hip): arguments as gl_create_map_points' and
 // already checked, the context's device current; `scratch`: create_map_points_scratch_bytes(N) bytes, written before they are read
 size_t gl::create_map_points_scratch_bytes(int N) { return (size_t)N * (2 * 24 + 4) + 64; }
-int gl::launch_create_map_points(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, float scale_factor, int N,
-                                 const double* pose1_dev, const double* uvr1_dev, const float* depth1_dev, const int32_t* oct1_dev,
-                                 const double* pose2_dev, const double* uvr2_dev, const float* depth2_dev, const int32_t* oct2_dev,
-                                 const int32_t* cand1_dev, const int32_t* n1_dev, const int32_t* cand2_dev, const int32_t* n2_dev, int k,
-                                 double* x3d_dev, int32_t* type_dev, int32_t* comp_dev, void* scratch) {
+int gl::launch_create_map_points(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params* prm, float scale_factor, int N, int k,
+                                 const gl_match::MatchSide& s1, const gl_match::MatchSide& s2, const gl_match::MatchPoints& out, void* scratch) {
   double* b1 = (double*)scratch;
   double* b2 = b1 + (size_t)N * 3;
   int32_t* stage = (int32_t*)(b2 + (size_t)N * 3);
@@ -678,15 +675,12 @@ int gl::launch_create_map_points(Ctx* c, const Gmm* g, const gl_camera* cam, con
   t.width = cam->width;
   t.height = cam->height;
   const int grid = (N + 63) / 64;
-  k_tri_pre<<<grid, 64, 0, c->stream>>>(t, N, pose1_dev, uvr1_dev, depth1_dev, pose2_dev, uvr2_dev, depth2_dev, x3d_dev, stage,
-                                        b1, b2);
+  k_tri_pre<<<grid, 64, 0, c->stream>>>(t, N, s1.pose, s1.uvr, s1.depth, s2.pose, s2.uvr, s2.depth, out.x3d, stage, b1, b2);
   GL_HIP(hipGetLastError());
-  k_optimize_triangulation<<<(int)(((size_t)N * TRI_LANES + 255) / 256), 256, 0, c->stream>>>(make_ptk(cam, prm), N, g->rec12, g->axis, g->flags, x3d_dev, pose1_dev,
-                                                       b1, oct1_dev, pose2_dev, b2, cand1_dev, n1_dev, cand2_dev, n2_dev, k,
-                                                       comp_dev);
+  k_optimize_triangulation<<<(int)(((size_t)N * TRI_LANES + 255) / 256), 256, 0, c->stream>>>(
+      make_ptk(cam, prm), N, g->rec12, g->axis, g->flags, out.x3d, s1.pose, b1, s1.oct, s2.pose, b2, s1.cand, s1.ncand, s2.cand, s2.ncand, k, out.comp);
   GL_HIP(hipGetLastError());
-  k_tri_post<<<grid, 64, 0, c->stream>>>(t, N, pose1_dev, uvr1_dev, oct1_dev, pose2_dev, uvr2_dev, oct2_dev, stage, x3d_dev,
-                                         comp_dev, type_dev);
+  k_tri_post<<<grid, 64, 0, c->stream>>>(t, N, s1.pose, s1.uvr, s1.oct, s2.pose, s2.uvr, s2.oct, stage, out.x3d, out.comp, out.type);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
@@ -767,8 +761,14 @@ int gl_create_map_points(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* ca
   void* scratch = nullptr;
   int rc = gl::ctx_scratch(c, gl::create_map_points_scratch_bytes(N), &scratch);
   if (rc != GL_OK) return rc;
-  return gl::launch_create_map_points(c, gl::G(gmm), cam, prm, scale_factor, N, pose1_dev, uvr1_dev, depth1_dev, oct1_dev, pose2_dev, uvr2_dev,
-                                      depth2_dev, oct2_dev, cand1_dev, n1_dev, cand2_dev, n2_dev, k, x3d_dev, type_dev, comp_dev, scratch);
+  // (the launcher only reads the per-match arrays)
+  auto side = [](const double* pose, const double* uvr, const float* depth, const int32_t* oct, const int32_t* cand, const int32_t* n) {
+    return gl_match::MatchSide{const_cast<double*>(pose), const_cast<double*>(uvr), const_cast<float*>(depth),
+                               const_cast<int32_t*>(oct), const_cast<int32_t*>(cand), const_cast<int32_t*>(n)};
+  };
+  return gl::launch_create_map_points(c, gl::G(gmm), cam, prm, scale_factor, N, k, side(pose1_dev, uvr1_dev, depth1_dev, oct1_dev, cand1_dev, n1_dev),
+                                      side(pose2_dev, uvr2_dev, depth2_dev, oct2_dev, cand2_dev, n2_dev),
+                                      gl_match::MatchPoints{x3d_dev, type_dev, comp_dev}, scratch);
 }
 
 }  // extern "C"

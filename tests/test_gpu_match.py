@@ -262,6 +262,85 @@ def test_search_gather_create_map_points_chain_on_device(gpu, oracle, map_v1):
     oracle.gmm_destroy(h)
 
 
+def _widen_nodes(torch, side, extra):
+    """`extra` unused columns behind a packed side's node_id / node_ptr tables (node_ptr continued with its last value, nnode as it
+    is): the same lists under a larger NN stride"""
+    out = dict(side)
+    out["node_id"] = torch.cat([side["node_id"], torch.zeros_like(side["node_id"][:, :1]).expand(-1, extra)], 1).contiguous()
+    out["node_ptr"] = torch.cat([side["node_ptr"], side["node_ptr"][:, -1:].expand(-1, extra)], 1).contiguous()
+    return out
+
+
+def test_pair_strides_all_different(gpu, oracle):
+    """The strides of a batch - N1 = 120, N2 = 130 features, NN1 = 8, NN2 = 11 node slots, all different - each applied to its own axis
+    and side: gl_search_for_triangulation and gl_search_by_bow bit for bit against the oracle per pair (at least one match per pair and
+    mode: the oracle's own counts on these inputs), gl_gather_triangulation_matches against the same gather in numpy (copies: exact)."""
+    torch, ctx = gpu
+    cam = api.Camera()
+    shapes = ((65, 70, 5), (64, 130, 8), (120, 64, 3))
+    pairs = [synth.synth_tri_search_pair(N1, N2, 900 + i, cam, nodes, pad=1) for i, (N1, N2, nodes) in enumerate(shapes)]
+    k1, k2, fm, ep = _pack_pairs(torch, pairs)
+    k2 = _widen_nodes(torch, k2, 3)
+    assert (k1["oct"].shape[1], k2["oct"].shape[1], k1["node_id"].shape[1], k2["node_id"].shape[1]) == (120, 130, 8, 11)
+    match_ft = None
+    for (only_stereo, chk), counts in (((False, True), (7, 4, 8)), ((True, False), (6, 1, 3))):
+        match, nm = api.search_for_triangulation(ctx, k1, k2, fm, ep, only_stereo, chk)
+        torch.cuda.synchronize()
+        mh, nh = match.cpu().numpy(), nm.cpu().numpy()
+        for b, p in enumerate(pairs):
+            m_ref, n_ref = oracle.search_for_triangulation(p["kf1"], p["kf2"], p["fmat"], p["epipole"], only_stereo, chk)
+            assert n_ref == counts[b], (only_stereo, chk, b, n_ref)
+            assert np.array_equal(mh[b, :len(m_ref)], m_ref) and (mh[b, len(m_ref):] == -1).all() and nh[b] == n_ref, (only_stereo, chk, b)
+        if match_ft is None:
+            match_ft, nm_ft = match, nm
+
+    bows = [synth.synth_bow_pair(N1, N2, 900 + i, cam, nodes) for i, (N1, N2, nodes) in enumerate(shapes)]
+    kf, fr = _pack_bow(torch, bows)
+    fr = _widen_nodes(torch, fr, 3)
+    assert (kf["angle"].shape[1], fr["angle"].shape[1], kf["node_id"].shape[1], fr["node_id"].shape[1]) == (120, 130, 8, 11)
+    match, nm = api.search_by_bow(ctx, kf, fr, 0.7, True)
+    torch.cuda.synchronize()
+    mh, nh = match.cpu().numpy(), nm.cpu().numpy()
+    for b, p in enumerate(bows):
+        m_ref, n_ref = oracle.search_by_bow(p[0], p[1], 0.7, True)
+        assert n_ref == (12, 11, 12)[b], (b, n_ref)
+        assert np.array_equal(mh[b, :len(m_ref)], m_ref) and (mh[b, len(m_ref):] == -1).all() and nh[b] == n_ref, b
+
+    # the (False, True) matches through the gather: sides as in test_search_gather_create_map_points_chain_on_device, k = 3
+    K, B = 3, len(pairs)
+    rng = np.random.default_rng(5)
+    host = []
+    for key, N in (("kf1", 120), ("kf2", 130)):
+        t = dict(pose=np.zeros((B, 7)), uv=np.zeros((B, N, 2)), ur=np.full((B, N), -1.0, np.float32), depth=np.full((B, N), -1.0, np.float32),
+                 oct=np.zeros((B, N), np.int32), cand=np.full((B, N, K), -1, np.int32), ncand=np.zeros((B, N), np.int32))
+        for b, p in enumerate(pairs):
+            k = p[key]
+            n = len(k["oct"])
+            t["pose"][b] = p["pose1" if key == "kf1" else "pose2"]
+            t["uv"][b, :n], t["ur"][b, :n], t["oct"][b, :n] = k["uv"], k["ur"], k["oct"]
+            t["depth"][b, :n] = np.where(k["ur"] >= 0, cam.bf / np.maximum(k["uv"][:, 0] - k["ur"], 1e-3), -1.0)
+            t["cand"][b, :n] = rng.integers(0, 1000, (n, K))
+            t["ncand"][b, :n] = rng.integers(0, K + 1, n)
+        host.append(t)
+    s1, s2 = ({q: torch.from_numpy(v).cuda() for q, v in t.items()} for t in host)
+    off, m = api.gather_triangulation_matches(ctx, match_ft, nm_ft, s1, s2)
+    torch.cuda.synchronize()
+    mh = match_ft.cpu().numpy()
+    pr, i1 = np.nonzero(mh >= 0)  # row-major: by pair, ascending feature of key-frame 1
+    i2 = mh[pr, i1]
+    total = len(pr)
+    assert total == 19 and np.array_equal(off.cpu().numpy(), np.concatenate([[0], np.cumsum((mh >= 0).sum(1))]))
+    a, b2 = host
+    ref = dict(pair=pr, idx1=i1, idx2=i2, pose1=a["pose"][pr], pose2=b2["pose"][pr],
+               uvr1=np.concatenate([a["uv"][pr, i1], a["ur"][pr, i1, None].astype(np.float64)], 1),
+               uvr2=np.concatenate([b2["uv"][pr, i2], b2["ur"][pr, i2, None].astype(np.float64)], 1),
+               depth1=a["depth"][pr, i1], depth2=b2["depth"][pr, i2], oct1=a["oct"][pr, i1], oct2=b2["oct"][pr, i2],
+               cand1=a["cand"][pr, i1], cand2=b2["cand"][pr, i2], n1=a["ncand"][pr, i1], n2=b2["ncand"][pr, i2])
+    assert set(ref) == set(m)
+    for q, v in ref.items():
+        assert np.array_equal(m[q][:total].cpu().numpy(), v), q
+
+
 def _pack_bow(torch, pairs):
     """list of (kf, fr) dicts -> the batched CUDA tensors of api.search_by_bow (strides = the maxima, padding slots: no map point /
     not in any list)"""

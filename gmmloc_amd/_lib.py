@@ -70,6 +70,11 @@ class gl_map_fuse_out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("result", "repl_src", "repl_tgt", "obs_new_pos")] + [("repl_cap", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class gl_map_stats(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("mp_visible", "mp_found", "mp_ref_idx", "kf_idx", "cand", "n_cand")] +
+                [("cand_cap", C.c_int32), ("reserved_", C.c_int32)])
+
+
 class gl_stereo_points_in(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("pose", "feat_uv", "feat_ur", "feat_depth", "feat_oct", "cand", "ncand", "held", "kf_row")]
 
@@ -175,6 +180,11 @@ def load():
         "gl_map_remove": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
         "gl_map_add": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "gl_map_fuse": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
+        "gl_map_stats_track": (i32, [vp, i32, vp, i32, i32, i32] + [vp] * 7),
+        "gl_map_stats_new_points": (i32, [vp, i32, i32, vp, i32, i32, vp, vp, vp]),
+        "gl_map_cand_append": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+        "gl_map_stats_merge": (i32, [vp, i32, vp, vp, vp, i32, vp]),
+        "gl_cull_map_points": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
         "gl_search_local_points": (i32, [vp, vp, C.c_float, i32, i32, i32] + [vp] * 13 + [C.c_float, C.c_float, vp, vp, vp]),
         "gl_gather_triangulation_matches": (i32, [vp, i32, i32, i32, i32, i32] + [vp] * 32),
         "gl_optimize_point": (i32, [vp, vp, P(gl_camera), P(gl_params), i32] + [vp] * 10),

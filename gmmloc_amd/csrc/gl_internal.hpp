@@ -164,7 +164,8 @@ enum {
                      // for its stages (which use the three blocks above)
   SCRATCH_BAWINDOW,  // gl_update_connections / gl_ba_window_build / _apply: per-window words over the map's rows and the window's lists
   SCRATCH_MAPEDIT,   // gl_map_remove, gl_map_add, gl_map_fuse: each call's marks over the map's rows and its lists, then the rebuild of the
-                     // CSR (mapdev::CsrRebuild, gl_map_dev.hpp): the scan words and the copy of the CSR it moves from
+                     // CSR (mapdev::CsrRebuild, gl_map_dev.hpp): the scan words and the copy of the CSR it moves from; gl_cull_map_points:
+                     // a first-occurrence word per map point, the copy of the candidate list and its scan words
   SCRATCH_MAPTRI,    // gl_create_map_points_from_map: the pair set-up, the gathered pair tables, the mask and the per-match arrays that its
                      // stages (which use the main block and the cache) hand to one another
   SCRATCH_COUNT

@@ -1,8 +1,9 @@
-// The resident map as the kernels see it (gl_ba_window.hip, gl_map_edit.hip, gl_map_grow.hip): ONE description of the caller-owned
-// arrays, one copy of each rule that reads them, and the rebuild of the CSR that gl_map_remove, gl_map_add and gl_map_fuse share.  The
-// C-ABI hands the same arrays over as gl_map_view + gl_map_ba_view or as sizes + gl_map_edit; map_from_view / map_from_edit turn either
-// into a Map and carry the argument checks every entry point has in common (gl_localmap.hip takes those and the workgroup scan; its
-// kernel keeps the view and its own spelling of the rules, see there).
+// The resident map as the kernels see it (gl_ba_window.hip, gl_map_edit.hip, gl_map_grow.hip, gl_map_stats.hip): ONE description of the
+// caller-owned arrays, one copy of each rule that reads them, and the rebuild of the CSR that gl_map_remove, gl_map_add and gl_map_fuse
+// share.  The C-ABI hands the same arrays over as gl_map_view + gl_map_ba_view or as sizes + gl_map_edit; map_from_view / map_from_edit
+// turn either into a Map and carry the argument checks every entry point has in common; stats_from_c does the same for the counters and
+// the candidate list of gl_map_stats (gl_localmap.hip takes those and the workgroup scan; its kernel keeps the view and its own
+// spelling of the rules, see there).
 #pragma once
 #include "gl_internal.hpp"
 
@@ -88,6 +89,29 @@ inline int map_from_edit(const char* who, int NMP, int NKF, int NFK, int NOBS, c
   m->mp_ref_kf = ed->mp_ref_kf;
   m->kf_uvr = kf_uvr;
   m->kf_first = kf_first;
+  return GL_OK;
+}
+// The counters and the candidate list of gl_map_stats (gl_map_stats.hip) as the kernels see them: NMP = the rows that count, NMPcap =
+// the rows the arrays have.  A field the entry point does not need may be null; stats_from_c says which it needs.
+struct Stats {
+  int NMP, NMPcap, NKF;
+  int32_t *visible, *found, *ref_idx;
+  const int32_t* kf_idx;  // null = the row itself
+  int32_t *cand, *n_cand;
+  int cand_cap;
+};
+enum { STATS_COUNTERS = 1, STATS_REF = 2, STATS_CAND = 4 };
+inline int stats_from_c(const char* who, const gl_map_stats* st, int NMP, int NMPcap, int NKF, int need, Stats* s) {
+  GL_MAP_REQUIRE(st, "null gl_map_stats");
+  GL_MAP_REQUIRE(NMP >= 0 && NMPcap >= NMP && NKF >= 0, "bad NMP / NMPcap / NKF");
+  GL_MAP_REQUIRE(!(need & STATS_COUNTERS) || NMPcap == 0 || (st->mp_visible && st->mp_found), "null mp_visible / mp_found");
+  GL_MAP_REQUIRE(!(need & STATS_REF) || NMPcap == 0 || st->mp_ref_idx, "null mp_ref_idx");
+  GL_MAP_REQUIRE(!(need & STATS_CAND) || (st->cand_cap >= 0 && st->n_cand && (st->cand_cap == 0 || st->cand)), "bad cand_cap / null cand / n_cand");
+  *s = Stats{};
+  s->NMP = NMP, s->NMPcap = NMPcap, s->NKF = NKF;
+  s->visible = st->mp_visible, s->found = st->mp_found, s->ref_idx = st->mp_ref_idx;
+  s->kf_idx = st->kf_idx;
+  s->cand = st->cand, s->n_cand = st->n_cand, s->cand_cap = st->cand_cap;
   return GL_OK;
 }
 #undef GL_MAP_REQUIRE

@@ -403,8 +403,8 @@ int gl_project_map_points(gl_ctx_t* ctx, const gl_camera* cam, float scale_facto
                           double* viewcos_dev, double* dist_dev, uint8_t* inview_dev);
 /* Tracking::searchLocalPoints (tracking.cpp:213-270), the device part in one call: gl_project_map_points followed by
  * gl_search_by_projection (ORBmatcher(0.8), th 3 - or 5 for the first two frames) on its outputs, which stay in the context's
- * scratch.  Arguments as in the two calls; inview_dev (B x NP uint8, may be null): is_in_view_ per map point for the host's
- * num_visible_++ (tracking.cpp:251). */
+ * scratch.  Arguments as in the two calls; inview_dev (B x NP uint8, may be null): is_in_view_ per map point, for num_visible_++
+ * (tracking.cpp:251) - the host's, or gl_map_stats_track's on the device. */
 int gl_search_local_points(gl_ctx_t* ctx, const gl_camera* cam, float scale_factor, int B, int NF, int NP, const double* feat_uv_dev,
                            const float* feat_ur_dev, const int32_t* feat_oct_dev, const uint8_t* feat_desc_dev,
                            const uint8_t* feat_taken_dev, const double* pose_cw_dev, const double* t_wc_dev, const double* mp_pos_dev,
@@ -472,7 +472,8 @@ int gl_update_map_points(gl_ctx_t* ctx, float scale_factor, int what, int NP, in
  *      gl_track_frame_chain_front (1, 2, 2b)  ->  its own updateLocalMap  ->  gl_track_frame_chain_back (3, 4)
  * - one round trip instead of three; front needs drop_src (and drop_kf with the fallback) as OUTPUT buffers, back reads match_last /
  * match_kf / drop_src / drop_kf and the to_local maps against the NEW local map.
- * What the host keeps doing: num_visible_ / num_found_ / countObservations bookkeeping, the decision on counts2[0] / counts2[3]
+ * What the host keeps doing: countObservations bookkeeping (num_visible_ / num_found_: gl_map_stats_track on these outputs, or the
+ * host's own), the decision on counts2[0] / counts2[3]
  * (without the fallback buffers: on counts[0] < 20 as before).  All pointers are DEVICE pointers; layouts as in the single calls. */
 typedef struct gl_track_chain_io {
   /* current frame: B x NF (x 2 / x 32) */
@@ -800,7 +801,7 @@ typedef struct gl_map_edit {
 } gl_map_edit;
 /* Three lists of rows on the device, any of them NULL / empty.  The length of a list is *n_x when n_x is given (a device int32,
  * clamped to [0, x_cap]) and x_cap otherwise.
- *   rm_mp      map-point rows (Localization::removeMapPoints :127-152 and a host's own culling decide them)
+ *   rm_mp      map-point rows (rm_mp / n_rm of gl_cull_map_points - Localization::removeMapPoints :127-152 - or a host's own culling)
  *   erase_obs  CSR positions: erase_obs / n_erase of gl_ba_window_apply (row b of a batch)
  *   rm_kf      key-frame rows IN REMOVAL ORDER: cull_rows / n_cull of gl_cull_keyframes */
 typedef struct gl_map_remove_lists {
@@ -914,7 +915,8 @@ int gl_map_remove(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, const gl_m
  * NOBS grows only by the attaches, so the capacity is checked BEFORE anything runs: OBScap >= NOBS + n_cand, else result[0] =
  * NOBS + n_cand with GL_MAP_GROW_OBS_TRUNCATED and nothing else is written.  That figure is an UPPER BOUND, not the size the edit
  * produces: a list of which few candidates attach, or whose replaces drop entries, is refused all the same below it.
- * What stays with the host, from repl_src / repl_tgt: num_visible_ / num_found_ (:142-143), ptr_replaced_, mappoints_.erase, and
+ * What stays with the host, from repl_src / repl_tgt: ptr_replaced_, mappoints_.erase (num_visible_ / num_found_, :142-143, are
+ * gl_map_stats_merge's on the same two lists), and
  * computeDistinctiveDescriptors of tgt (:144) - gl_update_map_points on the resident arrays before the next key-frame's search.
  * The steps depend on one another through slots, counts and gained entries, so ONE workgroup walks the list; inside a step it works in
  * parallel over src's and tgt's entries.  The walk never edits the CSR: its state (a word per point, a chain of gained entries per
@@ -965,6 +967,93 @@ typedef struct gl_map_fuse_out {
 } gl_map_fuse_out;
 int gl_map_fuse(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, int OBScap, const gl_map_edit* ed, const double* kf_uvr_dev, int kf,
                 int n_cand, const int32_t* cand_mp_dev, const int32_t* best_idx_dev, const gl_map_fuse_out* out);
+
+/* ---- the resident map's found / visible counters and Localization::removeMapPoints -------------
+ * Per map point the reference keeps num_visible_ and num_found_ (std::atomic_int, both 1 from the key-frame constructor,
+ * mappoint.cpp:18-19) and the const ref_idx_ (the idx_ of the key-frame that made the point, mappoint.cpp:18; -1 by default,
+ * mappoint.h:86); the mapping thread keeps the std::list candidate_mappts_.  gl_map_stats holds them on the device beside the arrays
+ * of gl_map_edit: caller-owned, row-indexed like it, with capacities like gl_map_add.  The five calls below keep them current from
+ * the tracker's and the mapper's own outputs and run removeMapPoints on them; nothing is copied to the host.
+ * Every writer of the reference, and the call that is it here:
+ *   tracking.cpp:213-225     every FEATURE of the frame that holds a valid map point: num_visible_ += 1 (a point   gl_map_stats_track
+ *                            held by two features: +2; an invalid point is un-held instead)
+ *   tracking.cpp:249-254     every local map point the frame does not hold that passes project3 and                gl_map_stats_track
+ *                            checkScaleAndVisible (is_in_view_): num_visible_ += 1
+ *   tracking.cpp:279-292     after trackLocalMap's optimisation every feature that holds a map point and is no     gl_map_stats_track
+ *                            outlier: num_found_ += 1
+ *   tracking.cpp:62-72       a lost frame returns before the three rows above                                      gl_map_stats_track
+ *   mappoint.cpp:18-19       a new point: both counters 1, ref_idx_ = the key-frame's idx_                         gl_map_stats_new_points
+ *   map.cpp:124-125,142-143  replaceMapPoint(src, tgt): tgt's counters += src's; nothing when src == tgt (:113)    gl_map_stats_merge
+ *   localization.cpp:433, localization_opt.cpp:442, localization_gmm.cpp:445  candidate_mappts_.push_back          gl_map_cand_append
+ *   localization.cpp:127-152 removeMapPoints                                                                       gl_cull_map_points
+ * Counter arithmetic is 32-bit two's-complement wrap-around (fetch_add on atomic_int), so the order of the adds never matters.
+ * All five: asynchronous on the context's stream, stateless, no host synchronise; integer stores and integer atomics only - the bytes
+ * do not depend on scheduling; MALFORMED input is skipped as in gl_update_local_map (a row outside its table counts nothing and
+ * changes nothing), nothing is read or written out of bounds.  A temporal point has no row and no counter. */
+typedef struct gl_map_stats {
+  int32_t* mp_visible;   /* NMPcap: num_visible_ */
+  int32_t* mp_found;     /* NMPcap: num_found_ */
+  int32_t* mp_ref_idx;   /* NMPcap: ref_idx_ */
+  const int32_t* kf_idx; /* NKF: idx_ of the key-frame row; NULL = the row itself */
+  int32_t* cand;         /* cand_cap: candidate_mappts_ as map-point rows, in list order */
+  int32_t* n_cand;       /* 1 device int32, in/out (read clamped to [0, cand_cap]) */
+  int32_t cand_cap, reserved_;
+} gl_map_stats;
+#define GL_MAP_STATS_MP_TRUNCATED 1   /* gl_map_stats_new_points: rows at or above NMPcap were not written */
+#define GL_MAP_STATS_CAND_TRUNCATED 2 /* gl_map_cand_append: the list would exceed cand_cap, nothing appended */
+#define GL_MAP_STATS_BAD_ROW 4        /* gl_cull_map_points: the list held a row outside [0, NMP) (verdict 5) */
+/* The three tracker rows of the table for B frames, on what gl_track_frame_chain_map left on the device (or gl_track_frame_chain_front
+ * -> host -> _back with the host's own local_mp): feat_mp B x NF int32, match_local B x NF int32 (an index into local_mp's row),
+ * outlier B x NF uint8, inview B x NPcap uint8, local_mp B x NPcap int32, n_local_mp B int32, counts2 B x 4 int32 or NULL (every frame
+ * tracked).  A frame with counts2[3] == 2 (lost) adds nothing.  For a tracked frame b:
+ *   visible[feat_mp[i]] += 1              per feature with feat_mp[i] >= 0 (the chain has un-held the invalid ones)
+ *   visible[local_mp[s]] += 1             per slot s < min(n_local_mp, NPcap) with inview[s]
+ *   found[r] += 1                         per feature with !outlier[i], r = local_mp[match_local[i]] when match_local[i] >= 0 (a
+ *                                         match_local at or above NPcap: none), else feat_mp[i], and r >= 0
+ * The increments of the B frames sum; a row outside [0, NMP) counts nothing.  Only mp_visible / mp_found of `st` are read. */
+int gl_map_stats_track(gl_ctx_t* ctx, int NMP, const gl_map_stats* st, int B, int NF, int NPcap, const int32_t* feat_mp_dev,
+                       const int32_t* match_local_dev, const uint8_t* outlier_dev, const uint8_t* inview_dev, const int32_t* local_mp_dev,
+                       const int32_t* n_local_mp_dev, const int32_t* counts2_dev);
+/* The rows [first, first + n) - n the host's, or *n_dev (clamped to [0, n]) when given: n_new_mp of gl_map_add_lists - get visible =
+ * found = 1 and ref_idx = kf_idx[new_ref_kf[j]] (the row new_ref_kf[j] itself when kf_idx is NULL; -1, the reference's default, when it
+ * is outside [0, NKF)).  new_ref_kf n int32: the list gl_map_add took.  Rows at or above NMPcap (or below 0) are not written:
+ * *status_dev (1 int32, always written) = GL_MAP_STATS_MP_TRUNCATED then, else 0. */
+int gl_map_stats_new_points(gl_ctx_t* ctx, int NMPcap, int NKF, const gl_map_stats* st, int first, int n, const int32_t* n_dev,
+                            const int32_t* new_ref_kf_dev, int32_t* status_dev);
+/* candidate_mappts_.push_back in order: the device list rows_dev (already_mp / n_already of gl_map_add), or with rows_dev NULL the
+ * row range [first, first + n) (the new rows of createMapPoints), n as above, appended to cand at *n_cand.  If the result would exceed
+ * cand_cap NOTHING is appended, *n_cand stays and the status is GL_MAP_STATS_CAND_TRUNCATED; result_dev 2 int32 = {the size of the list
+ * afterwards - after a truncation the size NEEDED -, status}.  One workgroup. */
+int gl_map_cand_append(gl_ctx_t* ctx, const gl_map_stats* st, const int32_t* rows_dev, int first, int n, const int32_t* n_dev,
+                       int32_t* result_dev);
+/* repl_src / repl_tgt of gl_map_fuse, n steps (or *n_dev clamped to [0, n]: result[3] of gl_map_fuse against repl_cap), IN STEP ORDER:
+ * visible[tgt] += visible[src], found[tgt] += found[src] (map.cpp:142-143).  A step with src == tgt or with a row outside [0, NMP)
+ * changes nothing.  The target of one step may be the source of a later one (a -> b, then b -> c): the result is that of the walk in
+ * list order.  One workgroup: per 1 024 steps it gathers the at most 2 048 rows into LDS (one slot per distinct row), one lane walks
+ * the steps there, the slots are scattered back. */
+int gl_map_stats_merge(gl_ctx_t* ctx, int NMP, const gl_map_stats* st, const int32_t* repl_src_dev, const int32_t* repl_tgt_dev, int n,
+                       const int32_t* n_dev);
+/* Localization::removeMapPoints (localization.cpp:127-152) on the UNEDITED map (gl_map_edit is only read; kf_uvr for the weight) for
+ * the key-frame row kf_row: curr_idx = kf_idx[kf_row] (kf_row when kf_idx is NULL).  Per entry of cand, in list order, the first true
+ * branch wins:
+ *   1  not_valid_ (mp_valid == 0)                                                      -> erased from the list
+ *   2  (float)num_found_ / (float)num_visible_ < 0.25f (int -> float and the division   -> removeMapPoint, erased
+ *      rounded to nearest; 0/0 = NaN and n/0 = inf are not below 0.25f: they fall through)
+ *   3  curr_idx - ref_idx_ >= 2 (in 64 bits on the int32 values) and the point's        -> removeMapPoint, erased
+ *      WEIGHTED COUNT (gl_cull_keyframes; 0 for a CSR range outside [0, NOBS]) <= 3
+ *   4  curr_idx - ref_idx_ >= 3                                                         -> erased
+ *   0  otherwise                                                                        -> kept
+ *   5  DECLARED (the reference's list holds no such entry): a row outside [0, NMP)      -> erased, not removed
+ * Map::removeMapPoint (map.cpp:40-58) touches only the removed point and the slots that hold it, so a verdict depends on no verdict
+ * before it - but for a row listed twice: its later occurrence finds not_valid_ (verdict 1) when the first one removed it and is
+ * judged like the first otherwise.  The walk is therefore one parallel pass over a snapshot, a candidate per thread, with a
+ * first-occurrence rule decided by LIST INDEX (atomicMin on a word per point in the context's scratch, set by the call), never by
+ * arrival.  Out: verdict cand_cap int32 (the old n entries are written); cand compacted IN PLACE, stable, through a copy in the
+ * scratch, *n_cand = kept; rm_mp cand_cap int32 + *n_rm_dev: the removed rows in list order, each once, at its first occurrence -
+ * rm_mp / n_rm_mp of gl_map_remove_lists as they stand; result 4 int32 = {kept, removed, erased without removal, status}.  The map and
+ * the counters are not written. */
+int gl_cull_map_points(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, const gl_map_edit* ed, const double* kf_uvr_dev,
+                       const gl_map_stats* st, int kf_row, int32_t* rm_mp_dev, int32_t* n_rm_dev, int32_t* verdict_dev, int32_t* result_dev);
 
 /* Localization::fuseObservations (localization.cpp:226-318), the matching half, for B key-frames: per candidate map point the most
  * similar feature inside Frame::getFeaturesInArea(u, v, th * scale_factors[level]) (frame.cpp:121-177) with octave level - 1 or

@@ -18,6 +18,9 @@
 //   Tracking::createTemporalPoints                  (tracking.cpp:411-465: createTemporalPoints)
 //   Localization::createMapPoints                   (localization_opt.cpp:206-454, the loop over the neighbours with the triangulation:
 //                                                   createMapPointsInMap on the resident map)
+//   Localization::removeMapPoints                   (localization.cpp:127-152) with num_visible_ / num_found_ / ref_idx_ and
+//                                                   candidate_mappts_ kept on the device (setResidentMapStats, trackStats, growStats,
+//                                                   mergeStats, removeMapPointsInMap)
 //   north-star per-frame path: associate + structure-constrained refinement of one frame (trackFrame)
 // Host buffers in, host buffers out: each call stages through device memory owned by the
 // adapter (gl_malloc / gl_memcpy_*), so the host code never sees a HIP type.
@@ -44,6 +47,8 @@ namespace gmmloc_hip {
 //    walked the answers of checkMapAssociation itself (INTEGRATION section 4 as it was) calls these instead
 //    setResidentKeyFrameTables / createMapPointsInMap (the loop of Localization::createMapPoints on the resident map) were added
 //    without a new version: no existing call changed meaning
+//    setResidentMapStats / trackStats / growStats / mergeStats / removeMapPointsInMap likewise: a host that mirrored the counters keeps
+//    working, one that calls these drops its mirror and the copies back of inview, feat_mp, match_local, outlier and repl_src / repl_tgt
 constexpr int kAdapterVersion = 5;
 
 inline void check(int rc, const char* what) {
@@ -808,6 +813,94 @@ class GMM {
     }
     return r;
   }
+  // ---- num_visible_ / num_found_ / ref_idx_ and candidate_mappts_ on the device (gl_map_stats, gmmloc_hip.h): the host keeps no
+  // mirror of the counters and copies nothing back to add 1 to them.  setResidentMapStats: the caller-owned device arrays, mp_visible /
+  // mp_found / mp_ref_idx with the rows of setResidentMapCapacity, cand with cand_cap entries.
+  void setResidentMapStats(const gl_map_stats& st) { stats_ = st; }
+  // trackStats: the three counter rules of the tracker (tracking.cpp:213-225, :249-254, :279-292) for B frames, on the DEVICE outputs of
+  // gl_track_frame_chain_map (or of _front / _back with the host's local_mp); counts2_dev may be null (every frame tracked).  Enqueued only.
+  void trackStats(int B, int NF, int NPcap, const int32_t* feat_mp_dev, const int32_t* match_local_dev, const uint8_t* outlier_dev,
+                  const uint8_t* inview_dev, const int32_t* local_mp_dev, const int32_t* n_local_mp_dev, const int32_t* counts2_dev = nullptr) {
+    check(gl_map_stats_track(ctx_, map_.NMP, &stats_, B, NF, NPcap, feat_mp_dev, match_local_dev, outlier_dev, inview_dev, local_mp_dev, n_local_mp_dev,
+                             counts2_dev),
+          "gl_map_stats_track");
+  }
+  // growStats, after addToMap / createMapPointsInMap: the rows [first, first + new_ref_kf.size()) get their counters and ref_idx_
+  // (mappoint.cpp:18-19), candidate_mappts_ gains already_mp (AddResult::already_mp, localization.cpp:433) and - for the rows of
+  // createMapPoints (localization_opt.cpp:442) - the new rows themselves.  status: GL_MAP_STATS_MP_TRUNCATED / _CAND_TRUNCATED (the
+  // append that would not fit added nothing; n_cand is then the size NEEDED).
+  struct GrowStatsResult {
+    int32_t status = 0, n_cand = 0;
+  };
+  GrowStatsResult growStats(int32_t first, const std::vector<int32_t>& new_ref_kf, const std::vector<int32_t>& already_mp, bool new_rows_are_candidates) {
+    const size_t nn = new_ref_kf.size(), na = already_mp.size();
+    char* b = pooled(10, 64 + (nn + na) * 4).as<char>();
+    int32_t* res = reinterpret_cast<int32_t*>(b);  // {status of the rows | append: size, status | append: size, status}
+    int32_t *d_ref = reinterpret_cast<int32_t*>(b + 64), *d_already = d_ref + nn;
+    if (nn) check(gl_memcpy_h2d(ctx_, d_ref, new_ref_kf.data(), nn * 4), "h2d");
+    if (na) check(gl_memcpy_h2d(ctx_, d_already, already_mp.data(), na * 4), "h2d");
+    check(gl_map_stats_new_points(ctx_, mp_cap_, map_.NKF, &stats_, first, (int)nn, nullptr, nn ? d_ref : nullptr, res), "gl_map_stats_new_points");
+    check(gl_map_cand_append(ctx_, &stats_, na ? d_already : nullptr, 0, (int)na, nullptr, res + 1), "gl_map_cand_append");
+    check(gl_map_cand_append(ctx_, &stats_, nullptr, first, new_rows_are_candidates ? (int)nn : 0, nullptr, res + 3), "gl_map_cand_append");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t got[5];
+    check(gl_memcpy_d2h(ctx_, got, res, 20), "d2h");
+    GrowStatsResult r;
+    r.status = got[0] | got[2] | got[4];
+    r.n_cand = got[3];
+    return r;
+  }
+  // mergeStats: FuseResult::repl_src / repl_tgt in step order, tgt's counters += src's (map.cpp:142-143).  Enqueued only (the lists
+  // are copied before the call returns).
+  void mergeStats(const std::vector<int32_t>& repl_src, const std::vector<int32_t>& repl_tgt) {
+    const size_t n = repl_src.size();
+    if (repl_tgt.size() != n) throw std::runtime_error("mergeStats: lists of different lengths");
+    if (!n) return;
+    int32_t* d = pooled(10, 2 * n * 4).as<int32_t>();
+    check(gl_memcpy_h2d(ctx_, d, repl_src.data(), n * 4), "h2d");
+    check(gl_memcpy_h2d(ctx_, d + n, repl_tgt.data(), n * 4), "h2d");
+    check(gl_map_stats_merge(ctx_, map_.NMP, &stats_, d, d + n, (int)n, nullptr), "gl_map_stats_merge");
+  }
+  // removeMapPointsInMap: Localization::removeMapPoints (localization.cpp:127-152) for key-frame kf_row - gl_cull_map_points on the
+  // resident map and the counters, its rm_mp / device count straight into gl_map_remove; one synchronise.  verdict: one per OLD entry
+  // of the list (0 kept, 1 invalid, 2 ratio, 3 young and few, 4 aged out, 5 row outside the table); remove.dead_mp: for the host's
+  // mappoints_.erase.
+  struct RemoveMapPointsResult {
+    int32_t kept = 0, removed = 0, erased = 0, status = 0;
+    std::vector<int32_t> verdict, rm_mp;
+    RemoveResult remove;
+  };
+  RemoveMapPointsResult removeMapPointsInMap(int32_t kf_row, int32_t* mp_ref_kf_dev = nullptr) {
+    const size_t cap = (size_t)stats_.cand_cap, NMP = (size_t)map_.NMP;
+    char* b = pooled(10, 64 + (2 * cap + NMP) * 4).as<char>();
+    int32_t* res = reinterpret_cast<int32_t*>(b);  // {kept, removed, erased, status | n_rm | gl_map_remove's result (3)}
+    int32_t *d_rm = reinterpret_cast<int32_t*>(b + 64), *d_verdict = d_rm + cap, *d_dead = d_verdict + cap;
+    const gl_map_edit ed = residentEdit(mp_ref_kf_dev);
+    check(gl_cull_map_points(ctx_, map_.NMP, map_.NKF, map_.NFK, map_.NOBS, &ed, map_ba_.kf_uvr, &stats_, kf_row, cap ? d_rm : nullptr, res + 4,
+                             cap ? d_verdict : nullptr, res),
+          "gl_cull_map_points");
+    gl_map_remove_lists ls{};
+    ls.rm_mp = cap ? d_rm : nullptr, ls.n_rm_mp = res + 4, ls.rm_mp_cap = (int32_t)cap;
+    gl_map_remove_out out{};
+    out.result = res + 5;
+    out.dead_mp = NMP ? d_dead : nullptr;
+    out.dead_cap = (int32_t)NMP;
+    check(gl_map_remove(ctx_, map_.NMP, map_.NKF, map_.NFK, map_.NOBS, &ed, map_ba_.kf_uvr, map_ba_.kf_first, &ls, &out), "gl_map_remove");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t got[8];
+    check(gl_memcpy_d2h(ctx_, got, res, 32), "d2h");
+    RemoveMapPointsResult r;
+    r.kept = got[0], r.removed = got[1], r.erased = got[2], r.status = got[3];
+    r.verdict.resize((size_t)(got[0] + got[1] + got[2]));
+    r.rm_mp.resize((size_t)got[1]);
+    if (!r.verdict.empty()) check(gl_memcpy_d2h(ctx_, r.verdict.data(), d_verdict, r.verdict.size() * 4), "d2h");
+    if (!r.rm_mp.empty()) check(gl_memcpy_d2h(ctx_, r.rm_mp.data(), d_rm, r.rm_mp.size() * 4), "d2h");
+    r.remove.nobs = got[5], r.remove.status = got[7];
+    r.remove.dead_mp.resize((size_t)got[6]);
+    if (got[6]) check(gl_memcpy_d2h(ctx_, r.remove.dead_mp.data(), d_dead, (size_t)got[6] * 4), "d2h");
+    map_.NOBS = r.remove.nobs;
+    return r;
+  }
   const gl_map_view& residentMap() const { return map_; }
 
   gl_ctx_t* ctx() { return ctx_; }
@@ -889,6 +982,7 @@ class GMM {
   gl_map_view map_{};
   gl_map_ba_view map_ba_{};
   gl_map_kf_tables kf_tables_{};
+  gl_map_stats stats_{};
   int32_t mp_cap_ = 0, obs_cap_ = 0;  // the rows of the per-point arrays, the entries of obs_kf / obs_feat
   size_t caps_[4] = {24, 24, 2048, 16384};  // Pcap, Fcap, Lcap, Ocap: grown on demand
   size_t win_off_[3] = {0, 0, 0};           // dropped, erase, erase_obs (consecutive)

@@ -97,6 +97,10 @@ class gl_map_kf_tables(C.Structure):
                                            "kf_ncand")] + [("NNcap", C.c_int32), ("k", C.c_int32)])
 
 
+class gl_bow_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("word_id", "node", "weight", "nnode", "node_id", "node_ptr", "node_idx", "status")]
+
+
 TRI_POINTS_ARRAYS = ("new_pos", "new_assoc", "new_ref_kf", "new_type", "new_nb", "new_feat1", "new_feat2", "att_mp", "att_kf", "att_feat", "n_new",
                      "n_attach", "feat_new", "nb_stats", "fmat", "epipole", "status")
 
@@ -164,6 +168,12 @@ def load():
         "gl_search_by_projection_frame": (i32, [vp, P(gl_camera), C.c_float, i32, i32, i32] + [vp] * 13 + [C.c_float, i32, i32, vp, vp]),
         "gl_search_for_triangulation": (i32, [vp, C.c_float, i32, i32, i32, i32, i32] + [vp] * 22 + [i32, i32, vp, vp]),
         "gl_search_by_bow": (i32, [vp, C.c_float, i32, i32, i32, i32, i32, i32] + [vp] * 15),
+        "gl_voc_file_read": (i32, [C.c_char_p, vp, vp, vp, vp, i32, P(i32), P(i32)]),
+        "gl_voc_create": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, P(vp)]),
+        "gl_voc_load_file": (i32, [vp, C.c_char_p, P(vp)]),
+        "gl_voc_destroy": (i32, [vp]),
+        "gl_voc_info": (i32, [vp, P(C.c_double)]),
+        "gl_bow_transform": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, P(gl_bow_out)]),
         "gl_fuse_search": (i32, [vp, vp, C.c_float, i32, i32, i32] + [vp] * 8 + [C.c_float, vp, vp]),
         "gl_project_map_points": (i32, [vp, vp, C.c_float, i32, i32] + [vp] * 12),
         "gl_level_steps": (i32, [C.c_float, vp]),

@@ -266,6 +266,32 @@ inline gl::Ctx* C(gl_ctx_t* c) { return (gl::Ctx*)c; }
 int read_gmm_file(const char* path, std::vector<double>& mean, std::vector<double>& cov);
 int write_gmm_file(const char* path, const double* mean, const double* cov, const uint8_t* flags, int K);
 
+// vocabulary file and tree rules (gl_io.cpp); the device object (gl_bow.hip)
+struct VocFile {
+  int n_nodes = 0, k = 0, L = 0;  // n_nodes: root included; the arrays hold the records of the nodes 1 .. n_nodes - 1
+  std::vector<int32_t> parent;
+  std::vector<uint8_t> desc, is_leaf;
+  std::vector<float> weight;
+};
+struct VocLayout {
+  std::vector<int32_t> nchild, first;  // by node id (root = 0): child count, layout position of the first child
+  std::vector<int32_t> pos, word;      // by record (node id - 1): layout position, word id (-1: not a leaf)
+  int n_words = 0, max_children = 0, min_leaf_level = 0;
+};
+int voc_check(int n_nodes, const int32_t* parent, const uint8_t* is_leaf, int err, VocLayout* out);
+int read_voc_file(const char* path, VocFile* out);
+// Device-resident, immutable vocabulary.  The records in layout order (VocLayout::pos): the children of a node are contiguous and in
+// child order, the root's children come first.
+//   desc  n_rec x 32 B   the node's descriptor (two 16-byte halves)
+//   meta  n_rec x int4   {node id, child count (0: a leaf), layout position of the first child | word id of a leaf, weight bits}
+struct Voc {
+  int device = 0;
+  int n_nodes = 0, n_words = 0, k = 0, L = 0, max_children = 0, min_leaf_level = 0, root_children = 0;
+  size_t bytes = 0;
+  void* desc = nullptr;
+  void* meta = nullptr;
+};
+
 // fixed observer key-frames of gl_track_frames_anchored (the caller's device arrays: gmmloc_hip.h, gl_track_anchor)
 struct TrackFixed {
   int F;

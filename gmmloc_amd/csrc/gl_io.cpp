@@ -6,6 +6,7 @@
 //   3 repeated double mean [packed], 4 repeated double covariance [packed].
 // The reference loader ignores fields 1-2 and recomputes them
 // (gmm_utils.cpp:50-61); covariance is read row-major (:54-59).
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -151,9 +152,119 @@ int write_gmm_file(const char* path, const double* mean, const double* cov, cons
   return GL_OK;
 }
 
+
+// ---- the DBoW2 vocabulary (gmmloc_hip.h: "the DBoW2 vocabulary and ORBVocabulary::transform") ------------------------------------------
+// The consistency rules of a tree given as records, and what the device layout needs of it: child counts, the layout position of
+// every record (the records in the order (parent, id): a node's children are contiguous and in child order, the children of node p
+// start at first[p]), word ids, levels.  `err` is what a violation returns: GL_ERR_FORMAT from a file, GL_ERR_ARG from arrays.
+int voc_check(int n_nodes, const int32_t* parent, const uint8_t* is_leaf, int err, VocLayout* out) {
+  auto bad = [&](const char* what, long node) {
+    set_error("vocabulary: %s (node %ld)", what, node);
+    return err;
+  };
+  if (n_nodes < 2) return bad("fewer than two nodes", 0L);
+  const size_t n_rec = (size_t)n_nodes - 1;
+  VocLayout& v = *out;
+  v.nchild.assign(n_nodes, 0);
+  v.first.assign(n_nodes, 0);
+  v.pos.assign(n_rec, 0);
+  v.word.assign(n_rec, -1);
+  std::vector<int32_t> level(n_nodes, 0);
+  for (size_t i = 0; i < n_rec; ++i) {
+    const long id = (long)i + 1;
+    if (parent[i] < 0 || parent[i] >= id) return bad("parent outside [0, own id)", id);
+    if (parent[i] > 0 && is_leaf[parent[i] - 1]) return bad("a record flagged leaf has a child", (long)parent[i]);
+    ++v.nchild[parent[i]];
+    level[id] = level[parent[i]] + 1;
+  }
+  v.n_words = v.max_children = 0;
+  v.min_leaf_level = INT32_MAX;
+  int32_t at = 0;
+  for (int p = 0; p < n_nodes; ++p) {
+    v.first[p] = at;
+    at += v.nchild[p];
+    if (v.nchild[p] > v.max_children) v.max_children = v.nchild[p];
+    if (p > 0) {
+      if (is_leaf[p - 1]) {
+        v.word[p - 1] = v.n_words++;
+        if (level[p] < v.min_leaf_level) v.min_leaf_level = level[p];
+      } else if (v.nchild[p] == 0) {
+        return bad("a record not flagged leaf has no child", (long)p);
+      }
+    }
+  }
+  std::vector<int32_t> cursor(v.first);
+  for (size_t i = 0; i < n_rec; ++i) v.pos[i] = cursor[parent[i]]++;
+  return GL_OK;
+}
+
+// loadFromBinaryFile (TemplatedVocabulary.h:1477-1522) without its phantom record: exactly nb_nodes - 1 records
+int read_voc_file(const char* path, VocFile* out) {
+  FILE* f = fopen(path, "rb");
+  if (!f) {
+    set_error("cannot open vocabulary file: %s", path);
+    return GL_ERR_IO;
+  }
+  std::vector<uint8_t> buf;
+  {
+    std::vector<uint8_t> tmp(1 << 20);
+    size_t n;
+    while ((n = fread(tmp.data(), 1, tmp.size(), f)) > 0) buf.insert(buf.end(), tmp.begin(), tmp.begin() + n);
+  }
+  fclose(f);
+  if (buf.size() < 24) return fail("vocabulary file shorter than its header");
+  uint32_t nb_nodes, size_node;
+  int32_t kL[2];
+  memcpy(&nb_nodes, &buf[0], 4);
+  memcpy(&size_node, &buf[4], 4);
+  memcpy(kL, &buf[8], 8);
+  if (size_node != 41) return fail("vocabulary file: size_node != 41");
+  if (nb_nodes < 2 || nb_nodes > (uint32_t)INT32_MAX) return fail("vocabulary file: nb_nodes outside [2, 2^31)");
+  const size_t n_rec = (size_t)nb_nodes - 1;
+  if (buf.size() != 24 + n_rec * 41) return fail("vocabulary file shorter or longer than its header says");
+  out->n_nodes = (int)nb_nodes;
+  out->k = kL[0];
+  out->L = kL[1];
+  out->parent.resize(n_rec);
+  out->desc.resize(n_rec * 32);
+  out->weight.resize(n_rec);
+  out->is_leaf.resize(n_rec);
+  for (size_t i = 0; i < n_rec; ++i) {
+    const uint8_t* r = &buf[24 + i * 41];
+    memcpy(&out->parent[i], r, 4);
+    memcpy(&out->desc[i * 32], r + 4, 32);
+    memcpy(&out->weight[i], r + 36, 4);
+    out->is_leaf[i] = r[40] ? 1 : 0;  // `if (buf[8+F::L])`, :1508
+  }
+  VocLayout lay;
+  return voc_check(out->n_nodes, out->parent.data(), out->is_leaf.data(), GL_ERR_FORMAT, &lay);
+}
+
 }  // namespace gl
 
 extern "C" {
+
+int gl_voc_file_read(const char* path, int32_t* parent, uint8_t* desc, float* weight, uint8_t* is_leaf, int cap, int* n_nodes_out,
+                     int* k_L_out) {
+  GL_REQUIRE(path && n_nodes_out, "null argument");
+  gl::VocFile v;
+  const int rc = gl::read_voc_file(path, &v);
+  if (rc != GL_OK) return rc;
+  const size_t n_rec = (size_t)v.n_nodes - 1;
+  if (parent || desc || weight || is_leaf) {
+    GL_REQUIRE(cap >= 0 && (size_t)cap >= n_rec, "output capacity too small");
+    if (parent) memcpy(parent, v.parent.data(), 4 * n_rec);
+    if (desc) memcpy(desc, v.desc.data(), 32 * n_rec);
+    if (weight) memcpy(weight, v.weight.data(), 4 * n_rec);
+    if (is_leaf) memcpy(is_leaf, v.is_leaf.data(), n_rec);
+  }
+  *n_nodes_out = v.n_nodes;
+  if (k_L_out) {
+    k_L_out[0] = v.k;
+    k_L_out[1] = v.L;
+  }
+  return GL_OK;
+}
 
 int gl_gmm_file_read(const char* path, double* mean, double* cov, int cap, int* K_out) {
   GL_REQUIRE(path && K_out, "null argument");

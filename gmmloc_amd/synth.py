@@ -794,3 +794,67 @@ def synth_held_points(m, B, NF, seed, hold_frac=0.6, twice_frac=0.05):
         if len(at):
             feat_mp[b, tw] = feat_mp[b, rng.choice(at, len(tw))]
     return feat_mp
+
+
+def synth_vocabulary(k, L, seed, interleave=True, early_leaf_frac=0.0, stop_frac=0.05, dup_frac=0.05, flip_bits=4):
+    """A DBoW2 vocabulary tree as the four record arrays of gl_voc_create: k children per inner node, depth L (1 + k + ... + k^L
+    nodes with the root when early_leaf_frac = 0; (10, 6) is the shape of the ORB vocabulary).  Records come level by level, so a
+    parent's id is below its children's; with `interleave` the records of a level are shuffled, so that the children of one node
+    are interleaved with those of others in id order and node ids are not monotone in tree position.
+    A child's descriptor is its parent's with every bit flipped with probability 2^-flip_bits, and with probability dup_frac a copy of
+    the sibling before it: siblings are close, equal distances and exact ties happen.  early_leaf_frac of the nodes above level L are
+    leaves; stop_frac of the leaves have weight 0.0f (stopped words), the others a positive float.
+    -> dict(parent (n,) i32, desc (n,32) u8, weight (n,) f32, is_leaf (n,) u8, k, L), n = nodes without the root."""
+    rng = np.random.default_rng(seed)
+    parent, desc, leaf = [], [], []
+    prev_ids, prev_desc, next_id = np.zeros(1, np.int64), np.zeros((1, 32), np.uint8), 1
+    for level in range(1, L + 1):
+        n = len(prev_ids) * k
+        if n == 0:
+            break
+        par = np.repeat(prev_ids, k)
+        mask = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        for _ in range(flip_bits - 1):
+            mask &= rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        d = np.repeat(prev_desc, k, axis=0) ^ mask
+        dup = np.nonzero((rng.uniform(size=n) < dup_frac) & (np.arange(n) % k != 0))[0]
+        for j in dup:  # (ascending: a run of copies copies the run's head)
+            d[j] = d[j - 1]
+        lf = np.ones(n, bool) if level == L else rng.uniform(size=n) < early_leaf_frac
+        order = rng.permutation(n) if interleave else np.arange(n)
+        par, d, lf = par[order], d[order], lf[order]
+        ids = next_id + np.arange(n)
+        next_id += n
+        parent.append(par)
+        desc.append(d)
+        leaf.append(lf)
+        prev_ids, prev_desc = ids[~lf], d[~lf]
+    parent = np.concatenate(parent).astype(np.int32)
+    is_leaf = np.concatenate(leaf).astype(np.uint8)
+    weight = rng.uniform(0.01, 12.0, len(parent)).astype(np.float32)
+    weight[(rng.uniform(size=len(parent)) < stop_frac) & (is_leaf != 0)] = 0.0
+    return dict(parent=parent, desc=np.ascontiguousarray(np.concatenate(desc)), weight=weight, is_leaf=is_leaf, k=int(k), L=int(L))
+
+
+def synth_vocabulary_descriptors(voc, n, seed, max_flips=3):
+    """n descriptors near node descriptors of a vocabulary: a random record's descriptor with 0 .. max_flips bits flipped -> (n,32) u8"""
+    rng = np.random.default_rng(seed)
+    out = voc["desc"][rng.integers(0, len(voc["parent"]), n)].copy()
+    for i in range(n):
+        bits = rng.choice(256, int(rng.integers(0, max_flips + 1)), replace=False)
+        np.bitwise_xor.at(out[i], bits // 8, (1 << (bits % 8)).astype(np.uint8))
+    return out
+
+
+def write_vocabulary_file(path, voc, scoring=0, weighting=0, nb_nodes=None, size_node=41):
+    """The binary vocabulary file: uint32 nb_nodes (root included), uint32 size_node, int32 k, L, scoring, weighting, then one 41-byte
+    record {int32 parent, 32 descriptor bytes, float weight, uint8 is_leaf} per node.  nb_nodes / size_node override the header (tests
+    of the reader's refusals)."""
+    n = len(voc["parent"])
+    rec = np.zeros(n, dtype=np.dtype([("parent", "<i4"), ("desc", "u1", 32), ("weight", "<f4"), ("is_leaf", "u1")]))
+    assert rec.dtype.itemsize == 41
+    rec["parent"], rec["desc"], rec["weight"], rec["is_leaf"] = voc["parent"], voc["desc"], voc["weight"], voc["is_leaf"]
+    with open(path, "wb") as f:
+        f.write(np.array([n + 1 if nb_nodes is None else nb_nodes, size_node], "<u4").tobytes())
+        f.write(np.array([voc["k"], voc["L"], scoring, weighting], "<i4").tobytes())
+        f.write(rec.tobytes())

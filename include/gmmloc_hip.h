@@ -23,7 +23,8 @@
  *   - all arithmetic is IEEE fp64 (the reference's scalar_t = double,
  *     common/eigen_types.h:6); float config scalars stay float (config.h:38-89).
  *   - a gl_gmm_t is immutable after creation and may be shared by contexts /
- *     host threads; a gl_ctx_t (stream + scratch) belongs to one host thread.
+ *     host threads, and so is a gl_voc_t; a gl_ctx_t (stream + scratch) belongs
+ *     to one host thread.
  */
 #ifndef GMMLOC_HIP_H_
 #define GMMLOC_HIP_H_
@@ -37,12 +38,14 @@ extern "C" {
 
 typedef struct gl_gmm gl_gmm_t;
 typedef struct gl_ctx gl_ctx_t;
+typedef struct gl_voc gl_voc_t;
 
 enum gl_status {
   GL_OK = 0,
   GL_ERR_ARG = -1,     /* bad argument (reference: CHECK / CHECK_NOTNULL aborts) */
   GL_ERR_IO = -2,      /* file cannot be opened (gmm_utils.cpp:19-22 -> false)   */
-  GL_ERR_FORMAT = -3,  /* malformed .gmm stream (gmm_utils.cpp:27-35,44-51)      */
+  GL_ERR_FORMAT = -3,  /* malformed .gmm stream (gmm_utils.cpp:27-35,44-51) or
+                          vocabulary file (gl_voc_file_read)                     */
   GL_ERR_DEVICE = -4,  /* HIP runtime error                                      */
   GL_ERR_NOMEM = -5
 };
@@ -111,7 +114,7 @@ void gl_default_params(gl_params* p);
  *
  * tri_lambda2 weighs the structure edge of the per-point optimisations (and scales their threshold, tri_str_thresh * tri_lambda2);
  * ba_lambda2 does both for the pose / window optimisations (threshold tri_str_thresh * ba_lambda2).  gl_search_by_bow,
- * gl_associate3d, gl_knn3d, gl_update_local_map, the gl_ba_window_* / gl_map_* calls read none of the three. */
+ * gl_bow_transform, gl_associate3d, gl_knn3d, gl_update_local_map, the gl_ba_window_* / gl_map_* calls read none of the three. */
 
 const char* gl_last_error_string(void); /* thread-local */
 int gl_device_count(void);
@@ -1082,6 +1085,78 @@ int gl_search_by_bow(gl_ctx_t* ctx, float nn_ratio, int check_orientation, int B
                      const int32_t* node_id1_dev, const int32_t* node_ptr1_dev, const int32_t* node_idx1_dev,
                      const float* angle2_dev, const uint8_t* desc2_dev, const int32_t* nnode2_dev, const int32_t* node_id2_dev,
                      const int32_t* node_ptr2_dev, const int32_t* node_idx2_dev, int32_t* match21_dev, int32_t* nmatches_dev);
+
+/* ---- the DBoW2 vocabulary and ORBVocabulary::transform (orb_vocabulary.cpp:20-40): the PRODUCER of the feature vectors above -------
+ * The reference converts a frame's descriptors and calls TemplatedVocabulary::transform(features, bow_vec, feat_vec, 4)
+ * (orb_dbow2/include/orb_dbow2/dbow2/TemplatedVocabulary.h:1150-1218) for every key-frame (gmmloc_opt.cpp:25) and for a frame that
+ * falls back to trackKeyFrame (tracking.cpp:298).  Only the FeatureVector is built here: bow_vec_ has no reader in gmmloc/.
+ *
+ * The tree.  Node 0 is the root; the other nodes have the ids 1, 2, ... of their records, a parent in [0, own id), a 32-byte
+ * descriptor, a float weight and a leaf flag.  A node's children are ordered by id (loadFromBinaryFile pushes them in file order,
+ * :1497-1517); word ids count the leaf-flagged records in id order (:1508-1513).
+ *
+ * Per feature (TemplatedVocabulary::transform(feature, word_id, weight, nid, levelsup), :1241-1283): start at the root; at each node
+ * take the child with the smallest FORB::distance (256-bit Hamming), `d < best_d`, so the FIRST of equal children in child order
+ * wins; stop at a node without children.  word_id / weight are that leaf's; nid is the node reached at level L - levelsup (level 1 =
+ * the root's children), 0 when L - levelsup <= 0.  A feature enters the feature vector iff `weight > 0` (:1181, :1209): 0.0f,
+ * -0.0f and NaN are stopped words.  FeatureVector is a std::map<NodeId, vector<unsigned>>: nodes ascending by id, the features of a
+ * node ascending by index.
+ *
+ * DECLARED:
+ *   - phantom node: `while (!f.eof())` (:1497) reads one record more than the file holds and appends a copy of the last node to that
+ *     node's parent.  Its descriptor equals an earlier sibling's, so under the strict compare it never wins: the reader here takes
+ *     exactly nb_nodes - 1 records and makes none.
+ *   - rejected input (the reference indexes out of range or never terminates): size_node != 41, nb_nodes < 2, a parent outside
+ *     [0, own id), a record flagged leaf that has a child, a record not flagged leaf without one, a file shorter or longer than its
+ *     header says: GL_ERR_FORMAT from the file readers, GL_ERR_ARG from gl_voc_create (its arrays are arguments).
+ *   - shallow leaf: a feature that reaches a leaf above level L - levelsup leaves *nid unwritten in the reference (:1275 never
+ *     fires); here nid is that leaf's id.
+ *   - levelsup < 0 is GL_ERR_ARG.
+ *
+ * File (loadFromBinaryFile, :1477-1522): uint32 nb_nodes (root included), uint32 size_node, int32 k, int32 L, int32 scoring, int32
+ * weighting, then nb_nodes - 1 records of 41 bytes {int32 parent, 32 descriptor bytes, float weight, uint8 is_leaf}.
+ *
+ * gl_voc_file_read - host only, like gl_gmm_file_read: *n_nodes_out = nb_nodes, k_L_out[2] = {k, L} (NULL allowed); the records of
+ *   the nodes 1 .. nb_nodes - 1 into parent (cap) int32, desc (cap x 32) uint8, weight (cap) float, is_leaf (cap) uint8, cap >=
+ *   nb_nodes - 1; all four NULL: the counts alone.
+ * gl_voc_create - the same arrays (n_nodes - 1 records, host pointers) and the same consistency checks; synchronous.  The nodes are
+ *   laid out on the device so that the children of a node are contiguous and in child order.  k is informative; L sets the level
+ *   of nid.  A gl_voc_t is immutable and may be used by every context of its device.
+ * gl_voc_info - info[7] = {nodes (root included), words, k, L, largest child count, shallowest leaf level, device bytes}.
+ *
+ * gl_bow_transform - the transform for B frames of NF feature slots: feat_desc B x NF x 32 uint8; feat_oct B x NF int32, < 0 marks a
+ *   padding slot (the matchers' convention), NULL: every slot is a feature.  Asynchronous on the context's stream, stateless, no host
+ *   synchronise; the context's scratch is written before it is read.  B <= 65 535 (B = 0: nothing is done), 1 <= NF <= 4 096, 1 <= NNcap
+ *   <= 4 096, 0 <= levelsup (the reference passes 4); feat_desc aligned to 16 bytes, as the matchers read it.  out:
+ *     word_id, node B x NF int32, weight B x NF float - per feature, stopped words included; a padding slot gets -1 / -1 / 0; each
+ *       may be NULL;
+ *     nnode B, node_id B x NNcap ascending, node_ptr B x (NNcap + 1), node_idx B x NF - exactly the arrays of gl_search_by_bow,
+ *       gl_search_for_triangulation, gl_track_chain_io.feat_node_* and a row of gl_map_kf_tables;
+ *     status B int32: 0, or GL_BOW_NODES_TRUNCATED for a frame with more distinct nodes than NNcap: its true count goes into nnode,
+ *       its node_id / node_ptr / node_idx stay untouched, its per-feature outputs are complete.
+ *   Not written: node_id from nnode on, node_ptr from nnode + 1 on, node_idx from node_ptr[nnode] on.
+ *   After an argument error nothing has been written. */
+typedef struct gl_bow_out {
+  int32_t* word_id;
+  int32_t* node;
+  float* weight;
+  int32_t* nnode;
+  int32_t* node_id;
+  int32_t* node_ptr;
+  int32_t* node_idx;
+  int32_t* status;
+} gl_bow_out;
+#define GL_BOW_NODES_TRUNCATED 1
+#define GL_BOW_MAX_FEATURES 4096
+int gl_voc_file_read(const char* path, int32_t* parent, uint8_t* desc, float* weight, uint8_t* is_leaf, int cap, int* n_nodes_out,
+                     int* k_L_out);
+int gl_voc_create(gl_ctx_t* ctx, int n_nodes, const int32_t* parent, const uint8_t* desc, const float* weight, const uint8_t* is_leaf, int k,
+                  int L, gl_voc_t** out);
+int gl_voc_load_file(gl_ctx_t* ctx, const char* path, gl_voc_t** out);
+int gl_voc_destroy(gl_voc_t* voc);
+int gl_voc_info(const gl_voc_t* voc, double info[7]);
+int gl_bow_transform(gl_ctx_t* ctx, const gl_voc_t* voc, int levelsup, int B, int NF, int NNcap, const uint8_t* feat_desc_dev,
+                     const int32_t* feat_oct_dev, const gl_bow_out* out);
 /* The matches of gl_search_for_triangulation as the per-match arrays of gl_create_map_points, without leaving the device:
  * what Localization::createMapPoints reads per matched pair (localization_opt.cpp:286-420) - the two key-frames' poses,
  * key-points, depths, octaves and candidate components (kf->comps_[idx]).  Inputs per pair and key-frame: pose B x 7, uv B x N x 2,
@@ -1152,7 +1227,8 @@ int gl_create_map_points(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* ca
  * later query - so B pairs in one batch of gl_search_for_triangulation are not the reference's result for one key-frame's neighbours.
  *
  * gl_map_kf_tables - the per-key-frame tables the triangulation reads and no other view carries; caller-owned device arrays,
- * row-indexed like gl_map_ba_view (a new key-frame's rows are part of the one upload that stays):
+ * row-indexed like gl_map_ba_view (a new key-frame's rows are part of the one upload that stays, but for the feature vector's four
+ * arrays, which gl_bow_transform writes in place from kf_desc's row):
  *   kf_angle NKF x NFK f32 (key-point angle, degrees), kf_desc NKF x NFK x 32 u8 (the table of gl_fuse_search / gl_update_map_points),
  *   kf_depth NKF x NFK f32 (Feature::depth, -1 = none); the DBoW2::FeatureVector as CSR like gl_search_for_triangulation's: kf_nnode
  *   NKF, kf_node_id NKF x NNcap ascending, kf_node_ptr NKF x (NNcap + 1), kf_node_idx NKF x NFK; the candidate tables of gl_search2d

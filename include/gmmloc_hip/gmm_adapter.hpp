@@ -49,6 +49,7 @@ namespace gmmloc_hip {
 //    without a new version: no existing call changed meaning
 //    setResidentMapStats / trackStats / growStats / mergeStats / removeMapPointsInMap likewise: a host that mirrored the counters keeps
 //    working, one that calls these drops its mirror and the copies back of inview, feat_mp, match_local, outlier and repl_src / repl_tgt
+//    loadVocabulary / bowTransform / bowTransformIntoTables likewise: a host that runs its own DBoW2 and uploads feat_vec_ keeps working
 constexpr int kAdapterVersion = 5;
 
 inline void check(int rc, const char* what) {
@@ -903,6 +904,74 @@ class GMM {
   }
   const gl_map_view& residentMap() const { return map_; }
 
+  // ORBVocabulary::loadFromBinaryFile and ORBVocabulary::transform(descriptors, bow_vec, feat_vec, levelsup) (orb_vocabulary.cpp:20-40;
+  // gmmloc_opt.cpp:25 for a key-frame, tracking.cpp:298 for a frame that falls back to trackKeyFrame) on the device: gl_voc_load_file /
+  // gl_bow_transform.  Only the FeatureVector is made (bow_vec_ has no reader in gmmloc/).  loadVocabulary: false on failure like
+  // loadGMMModel.  bowTransform: descriptors N x 32 bytes in feature order (N <= 4 096) -> the flattened feature vector of INTEGRATION
+  // section 6 (node_id ascending; the features of node n are node_idx[node_ptr[n] .. node_ptr[n + 1])); one upload, one synchronise.
+  bool loadVocabulary(const std::string& path) {
+    if (voc_) gl_voc_destroy(voc_);
+    voc_ = nullptr;
+    return gl_voc_load_file(ctx_, path.c_str(), &voc_) == GL_OK;
+  }
+  struct FeatureVector {
+    std::vector<int32_t> node_id, node_ptr, node_idx;
+  };
+  FeatureVector bowTransform(const std::vector<uint8_t>& descriptors, int levelsup = 4) {
+    if (!voc_ || descriptors.size() % 32) throw std::runtime_error("bowTransform: loadVocabulary / descriptors of 32 bytes");
+    FeatureVector fv;
+    const size_t N = descriptors.size() / 32;
+    fv.node_ptr.assign(1, 0);
+    if (!N) return fv;
+    size_t off = 64;  // {nnode at 0 | status at 4}
+    auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += (bytes + 63) / 64 * 64;
+      return at;
+    };
+    const size_t o_desc = take(N * 32), o_id = take(N * 4), o_ptr = take((N + 1) * 4), o_idx = take(N * 4);
+    char* b = pooled(12, off).as<char>();
+    auto at = [b](size_t o) { return reinterpret_cast<int32_t*>(b + o); };
+    check(gl_memcpy_h2d(ctx_, b + o_desc, descriptors.data(), N * 32), "h2d");
+    gl_bow_out out{};
+    out.nnode = at(0), out.status = at(4), out.node_id = at(o_id), out.node_ptr = at(o_ptr), out.node_idx = at(o_idx);
+    check(gl_bow_transform(ctx_, voc_, levelsup, 1, (int)N, (int)N, reinterpret_cast<const uint8_t*>(b + o_desc), nullptr, &out), "gl_bow_transform");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t nnode = 0;
+    check(gl_memcpy_d2h(ctx_, &nnode, b, 4), "d2h");  // (NNcap = N: never truncated)
+    fv.node_id.resize(nnode);
+    fv.node_ptr.resize((size_t)nnode + 1);
+    if (nnode) check(gl_memcpy_d2h(ctx_, fv.node_id.data(), b + o_id, (size_t)nnode * 4), "d2h");
+    check(gl_memcpy_d2h(ctx_, fv.node_ptr.data(), b + o_ptr, ((size_t)nnode + 1) * 4), "d2h");
+    fv.node_idx.resize(fv.node_ptr[nnode]);
+    if (!fv.node_idx.empty()) check(gl_memcpy_d2h(ctx_, fv.node_idx.data(), b + o_idx, fv.node_idx.size() * 4), "d2h");
+    return fv;
+  }
+  // The feature vector of key-frame row kf_row written in place into the resident tables (setResidentKeyFrameTables: kf_desc[kf_row] is
+  // read, kf_nnode / kf_node_id / kf_node_ptr / kf_node_idx [kf_row] are written; the padding slots are those of the resident kf_oct when
+  // setResidentMap gave one).  Nothing is uploaded and nothing read back but the status word: GL_BOW_NODES_TRUNCATED when the key-frame
+  // has more nodes than the tables' NNcap (its row is then untouched, kf_nnode[kf_row] holds the count needed).
+  int32_t bowTransformIntoTables(int32_t kf_row, int levelsup = 4) {
+    if (!voc_ || kf_row < 0 || kf_row >= map_.NKF || !kf_tables_.kf_desc)
+      throw std::runtime_error("bowTransformIntoTables: loadVocabulary / kf_row / setResidentKeyFrameTables");
+    const size_t NF = (size_t)map_.NFK, NN = (size_t)kf_tables_.NNcap, r = (size_t)kf_row;
+    int32_t* status = pooled(13, 64).as<int32_t>();
+    gl_bow_out out{};
+    out.nnode = const_cast<int32_t*>(kf_tables_.kf_nnode) + r;
+    out.node_id = const_cast<int32_t*>(kf_tables_.kf_node_id) + r * NN;
+    out.node_ptr = const_cast<int32_t*>(kf_tables_.kf_node_ptr) + r * (NN + 1);
+    out.node_idx = const_cast<int32_t*>(kf_tables_.kf_node_idx) + r * NF;
+    out.status = status;
+    check(gl_bow_transform(ctx_, voc_, levelsup, 1, (int)NF, (int)NN, kf_tables_.kf_desc + r * NF * 32, map_ba_.kf_oct ? map_ba_.kf_oct + r * NF : nullptr,
+                           &out),
+          "gl_bow_transform");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t st = 0;
+    check(gl_memcpy_d2h(ctx_, &st, status, 4), "d2h");
+    return st;
+  }
+  gl_voc_t* vocabulary() { return voc_; }
+
   gl_ctx_t* ctx() { return ctx_; }
   gl_gmm_t* handle() { return gmm_; }
   gl_params& params() { return prm_; }
@@ -914,6 +983,8 @@ class GMM {
     if (stage_ && ctx_) gl_free_host(ctx_, stage_);
     stage_ = nullptr;
     stage_bytes_ = 0;
+    if (voc_) gl_voc_destroy(voc_);
+    voc_ = nullptr;
     if (gmm_) gl_gmm_destroy(gmm_);
     if (ctx_) gl_ctx_destroy(ctx_);
     gmm_ = nullptr;
@@ -992,6 +1063,7 @@ class GMM {
   size_t stage_bytes_ = 0;
   gl_ctx_t* ctx_ = nullptr;
   gl_gmm_t* gmm_ = nullptr;
+  gl_voc_t* voc_ = nullptr;
   gl_params prm_;
   gl_camera cam_{};
 };

@@ -1,0 +1,150 @@
+"""ORBVocabulary's binary reader and TemplatedVocabulary::transform(features, v, fv, levelsup), restated sequentially in plain Python /
+numpy (orb_dbow2/include/orb_dbow2/dbow2/TemplatedVocabulary.h:1477-1522, :1150-1218, :1241-1283; FORB::distance = the 256-bit Hamming
+distance), statement for statement, with the behaviours include/gmmloc_hip.h declares: no phantom record, the listed files refused, a
+shallow leaf is its own node, a negative levelsup refused.  What gl_voc_file_read / gl_bow_transform are held to, bit for bit.
+
+A vocabulary is the dict of gmmloc_amd.synth.synth_vocabulary: parent / desc / weight / is_leaf of the nodes 1 .. n, k, L."""
+import struct
+
+import numpy as np
+
+POPCOUNT = np.array([bin(v).count("1") for v in range(256)], np.int64)
+
+
+class FormatError(ValueError):
+    pass
+
+
+def check(parent, is_leaf):
+    """the consistency rules of the records (what the reference's loader assumes and never tests)"""
+    n = len(parent)
+    if n < 1:
+        raise FormatError("nb_nodes < 2")
+    nchild = [0] * (n + 1)
+    for i in range(n):
+        nid = i + 1
+        p = int(parent[i])
+        if not 0 <= p < nid:
+            raise FormatError("node %d: parent %d outside [0, own id)" % (nid, p))
+        if p > 0 and is_leaf[p - 1]:
+            raise FormatError("node %d is flagged leaf and has the child %d" % (p, nid))
+        nchild[p] += 1
+    for i in range(n):
+        if not is_leaf[i] and nchild[i + 1] == 0:
+            raise FormatError("node %d is not flagged leaf and has no child" % (i + 1))
+
+
+def read_file(path):
+    """loadFromBinaryFile (:1477-1522) -> the vocabulary dict; FormatError for the files gmmloc_hip.h lists"""
+    data = open(path, "rb").read()
+    if len(data) < 24:
+        raise FormatError("shorter than the header")
+    nb_nodes, size_node, k, L, scoring, weighting = struct.unpack("<IIiiii", data[:24])
+    if size_node != 41:
+        raise FormatError("size_node != 41")
+    if nb_nodes < 2:
+        raise FormatError("nb_nodes < 2")
+    n = nb_nodes - 1
+    if len(data) != 24 + 41 * n:
+        raise FormatError("shorter or longer than the header says")
+    parent, desc, weight, is_leaf = np.zeros(n, np.int32), np.zeros((n, 32), np.uint8), np.zeros(n, np.float32), np.zeros(n, np.uint8)
+    for i in range(n):  # nid = i + 1
+        buf = data[24 + 41 * i:24 + 41 * (i + 1)]
+        parent[i] = struct.unpack("<i", buf[:4])[0]
+        desc[i] = np.frombuffer(buf[4:36], np.uint8)
+        weight[i] = np.frombuffer(buf[36:40], "<f4")[0]
+        is_leaf[i] = 1 if buf[40] else 0
+    check(parent, is_leaf)
+    return dict(parent=parent, desc=desc, weight=weight, is_leaf=is_leaf, k=k, L=L)
+
+
+class Tree:
+    """m_nodes: children in id order (= push_back order of the loader), word ids counting the leaf-flagged records in id order"""
+
+    def __init__(self, voc):
+        check(voc["parent"], voc["is_leaf"])
+        parent = np.asarray(voc["parent"], np.int64)
+        n = len(parent)
+        self.L = int(voc["L"])
+        self.desc = np.concatenate([np.zeros((1, 32), np.uint8), np.asarray(voc["desc"], np.uint8).reshape(n, 32)])  # by node id
+        self.weight = np.concatenate([np.zeros(1, np.float32), np.asarray(voc["weight"], np.float32)])
+        order = np.argsort(parent, kind="stable")  # the records by (parent, id)
+        self.child_ids = order + 1
+        self.child_ptr = np.concatenate([[0], np.cumsum(np.bincount(parent, minlength=n + 1))])
+        self.word_id = np.concatenate([[-1], np.where(np.asarray(voc["is_leaf"]) != 0, np.cumsum(np.asarray(voc["is_leaf"]) != 0) - 1, -1)])
+
+    def children(self, nid):
+        return self.child_ids[self.child_ptr[nid]:self.child_ptr[nid + 1]]
+
+    def distance(self, feature, nid):
+        return int(POPCOUNT[feature ^ self.desc[nid]].sum())
+
+    def transform_feature(self, feature, levelsup):
+        """:1241-1283 -> (word_id, weight, nid)"""
+        nid_level = self.L - levelsup
+        nid = 0 if nid_level <= 0 else None
+        final_id = 0
+        current_level = 0
+        while True:
+            current_level += 1
+            nodes = self.children(final_id)
+            final_id = int(nodes[0])
+            best_d = self.distance(feature, final_id)
+            for c in nodes[1:]:
+                d = self.distance(feature, int(c))
+                if d < best_d:
+                    best_d = d
+                    final_id = int(c)
+            if current_level == nid_level:
+                nid = final_id
+            if len(self.children(final_id)) == 0:  # isLeaf()
+                break
+        if nid is None:  # DECLARED: the reference leaves *nid unwritten; here the shallow leaf is its own node
+            nid = final_id
+        return int(self.word_id[final_id]), self.weight[final_id], nid
+
+
+def transform(tree, desc, octave=None, levelsup=4):
+    """:1150-1218 for one frame of NF slots (octave < 0: a padding slot, which is no feature) ->
+    (word_id (NF,) i32, node (NF,) i32, weight (NF,) f32, fv: list of (node id, [feature indices]) ascending by node id)"""
+    if levelsup < 0:
+        raise ValueError("negative levelsup")
+    NF = len(desc)
+    word, node, weight = -np.ones(NF, np.int32), -np.ones(NF, np.int32), np.zeros(NF, np.float32)
+    fv = {}
+    for i in range(NF):
+        if octave is not None and octave[i] < 0:
+            continue
+        wid, w, nid = tree.transform_feature(np.asarray(desc[i], np.uint8), levelsup)
+        word[i], node[i], weight[i] = wid, nid, w
+        if w > 0:  # not stopped
+            fv.setdefault(nid, []).append(i)
+    return word, node, weight, sorted(fv.items())
+
+
+def csr(fv, NF, nn_cap, fill=-7):
+    """the feature vector as the arrays of gl_bow_transform on buffers filled with `fill`: (nnode, node_id (nn_cap,), node_ptr
+    (nn_cap + 1,), node_idx (NF,), status); more nodes than nn_cap: status 1, the true count, the three arrays untouched"""
+    node_id, node_ptr, node_idx = np.full(nn_cap, fill, np.int32), np.full(nn_cap + 1, fill, np.int32), np.full(NF, fill, np.int32)
+    if len(fv) > nn_cap:
+        return len(fv), node_id, node_ptr, node_idx, 1
+    at = 0
+    for r, (nid, feats) in enumerate(fv):
+        node_id[r], node_ptr[r] = nid, at
+        node_idx[at:at + len(feats)] = feats
+        at += len(feats)
+    node_ptr[len(fv)] = at
+    return len(fv), node_id, node_ptr, node_idx, 0
+
+
+def transform_batch(tree, desc, octave=None, levelsup=4, nn_cap=None, fill=-7):
+    """B frames -> dict of arrays shaped as gl_bow_transform's outputs (CSR buffers pre-filled with `fill`)"""
+    B, NF = desc.shape[:2]
+    nn_cap = NF if nn_cap is None else nn_cap
+    out = dict(word_id=np.zeros((B, NF), np.int32), node=np.zeros((B, NF), np.int32), weight=np.zeros((B, NF), np.float32),
+               nnode=np.zeros(B, np.int32), node_id=np.zeros((B, nn_cap), np.int32), node_ptr=np.zeros((B, nn_cap + 1), np.int32),
+               node_idx=np.zeros((B, NF), np.int32), status=np.zeros(B, np.int32))
+    for b in range(B):
+        out["word_id"][b], out["node"][b], out["weight"][b], fv = transform(tree, desc[b], None if octave is None else octave[b], levelsup)
+        out["nnode"][b], out["node_id"][b], out["node_ptr"][b], out["node_idx"][b], out["status"][b] = csr(fv, NF, nn_cap, fill)
+    return out

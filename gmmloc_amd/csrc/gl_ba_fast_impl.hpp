@@ -240,7 +240,10 @@ struct Lds {      // per-frame state, SoA over MCAP points (index = local point 
   // 6 x MCAP doubles, two lifetimes sharing one slot per point:
   //   pass A -> pass B : the factors of D (ldl3_factor_fast, 6 fp64)   [kStep32: 12 fp32 words {u = D^-1 b (3), A D^-1 (3x3)}]
   //   pass B -> accept : backup of the point (3 fp64) while the trial point sits in `sp`; restored only
-  //                      when the trial is rejected.
+  //                      when the trial is rejected.  (Rows 3..5 are free in that lifetime.  Carrying {1 / z, rho, rho'} of an
+  //                      accepted trial's evaluation through them into the next pass A - which computes the same bits again -
+  //                      was built twice and measured slower both times, 31 VALU instructions fewer per point notwithstanding:
+  //                      three LDS writes and three reads per point and trial cost more; profiles/r18_carry_ab.txt)
   double* un;
   // 24 uniform constants: [0..7] sx = fx^2 / sigma^2 and [8..15] sy = fy^2 / sigma^2 per pyramid octave (the residuals
   // are kept in NORMALISED image coordinates, see reproj_n), [16..19] Huber {delta, delta^2} mono / stereo
@@ -356,14 +359,22 @@ GL_DEV void rot_sym(const double* R, const double* Hg, double* Hc) {
   Hc[5] = RH[6] * R[6] + RH[7] * R[7] + RH[8] * R[8];
 }
 
+// The map's tables (GmmDev: plane records, component records, world-frame blocks) are read-only GLOBAL memory.  The struct reaches the
+// kernel word by word (ld_karg), which hides that from the compiler: through the plain pointers every such load was a generic (flat)
+// one, which counts in the LDS counter as well as in the memory counter and returns out of order with LDS reads - the wait for the
+// point in LDS at the head of a slot then had to be a wait for everything.  The loads name the address space themselves
+// (profiles/r18_carry_ab.txt: -1.5 % on the batch refine; `pnflag`, which IS LDS behind a generic pointer, stays as it is).
+typedef const double __attribute__((address_space(1))) cdouble_g;
+
 // GMM edge of a NON-degenerate component (rare): EdgePt2Gaussian, e = L^T d, J = L^T, so
 // J^T J = L L^T (precomputed per component, world frame), b = -L L^T d, chi2 = d^T L L^T d.
 GL_DEV double gmm_nondeg(const GmmDev& gm, int a, const double* R, const double* p, double* Hc, double* bc) {
+  const cdouble_g* const hgw = (const cdouble_g*)gm.hgw + (size_t)a * 6;
+  const cdouble_g* const rec = (const cdouble_g*)gm.rec12 + (size_t)a * 12;
   double Hg[6];
 #pragma unroll
-  for (int i = 0; i < 6; ++i) Hg[i] = gm.hgw[(size_t)a * 6 + i];
-  const double d[3] = {p[0] - gm.rec12[(size_t)a * 12], p[1] - gm.rec12[(size_t)a * 12 + 1],
-                       p[2] - gm.rec12[(size_t)a * 12 + 2]};
+  for (int i = 0; i < 6; ++i) Hg[i] = hgw[i];
+  const double d[3] = {p[0] - rec[0], p[1] - rec[1], p[2] - rec[2]};
   double Hd[3];
   sym3_mul_vec(Hg, d, Hd);
   const double chi = d[0] * Hd[0] + d[1] * Hd[1] + d[2] * Hd[2];
@@ -1321,7 +1332,7 @@ GL_DEV void restore_point(const Lds& D, int ll) {
 // (Software-prefetching slot i+1 was measured: it costs 14 VGPRs -> 6 spilled registers and
 // ~1 GB of scratch writes per launch for no gain; the second wave of the SIMD hides the latency.)
 GL_DEV bool load_pt(const Lds& D, const Map& mp, FlagW fw, const AssocW& aw, const double* __restrict__ gobn,
-                    const double* __restrict__ gnd, const int32_t* __restrict__ gassoc, int i, PtCtx& c) {
+                    const cdouble_g* __restrict__ gnd, const int32_t* __restrict__ gassoc, int i, PtCtx& c) {
   c.fl = fw_get(fw, i);
   if (!(c.fl & (F_AR | F_AG | F_AF))) return false;
   c.l = mp.base + slot_off(mp, i);
@@ -1351,7 +1362,7 @@ struct PtConst {
   double ob[3], nd[4];
   int a;
 };
-GL_DEV void load_const(const Map& mp, FlagW fw, const double* __restrict__ gobn, const double* __restrict__ gnd,
+GL_DEV void load_const(const Map& mp, FlagW fw, const double* __restrict__ gobn, const cdouble_g* __restrict__ gnd,
                        const int32_t* __restrict__ gassoc, PtConst& pc) {
 #pragma unroll
   for (int j = 0; j < 3; ++j) pc.ob[j] = 0.0;
@@ -1656,7 +1667,7 @@ GL_DEV void pt_pass_b_eval(const Uni& U, const GmmDev& gm, const Lds& D, const P
 
 // SparseOptimizer::optimize(iters), Levenberg
 GL_DEV int optimize_fast(const Uni& U, const GmmDev& gm, const Lds& D, const Map& mp, FlagW fw, const AssocW& aw, Pose& P,
-                         const double* __restrict__ gobn, const int32_t* __restrict__ gassoc, const double* __restrict__ gnd,
+                         const double* __restrict__ gobn, const int32_t* __restrict__ gassoc, const cdouble_g* __restrict__ gnd,
                          const PtConst& pc, bool robust, int iters, const Red& R, int& trials, Coop& C, Anchor& An) {
   double acc[32];
 #pragma unroll
@@ -2040,7 +2051,7 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   // launch scratch written by k_ba1_prep, read-only here: plane records, normalised observations, permutation, flags,
   // gated associations (all but perm in the permuted order)
   const PrepView pv = prep_view(pn_all, B, L);
-  const double* gnd = gm.plane4;
+  const cdouble_g* gnd = (const cdouble_g*)gm.plane4;
   const double* gobn = pv.gobn + gbase * 3;
   const int32_t* gperm = pv.perm + gbase;
   const int32_t* gassoc = pv.assoc_p + gbase;

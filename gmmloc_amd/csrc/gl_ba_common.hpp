@@ -304,6 +304,28 @@ GL_DEV double block_max(double v, double* lds) {
   return m;
 }
 
+// ---- rules of Localization::jointOptimization that depend on their arguments alone (both shapes of gl_ba_gen.hip call them) ----
+// setForceStopFlag (localization_opt.cpp:541-542) / SparseOptimizer::optimize `i < iterations && !terminate()`: the stop word as
+// last seen (> 0: stop; < 0: a budget of -value outer iterations) against the outer iterations done so far
+GL_DEV bool ba_stop_now(int stop_seen, int done_iters) { return stop_seen > 0 || (stop_seen < 0 && done_iters >= -stop_seen); }
+// reprojection gate of an edge (:791-825, :855-879): chi2 above the 95 % bound of its type (3 / 2 degrees of freedom), or the point
+// not in front of the camera
+constexpr double CHI2_STEREO = 7.815, CHI2_MONO = 5.991;
+GL_DEV bool reproj_outlier(double chi2, bool stereo, double z) { return chi2 > (stereo ? CHI2_STEREO : CHI2_MONO) || !(z > 0.0); }
+// OptimizationAlgorithmLevenberg::solve: lambda and nu after a trial of gain ratio rho
+GL_DEV void lm_update(double rho, bool accept, double& lambda, double& ni) {
+  if (accept) {
+    const double uu = 2 * rho - 1;
+    double alpha = 1. - uu * uu * uu;
+    alpha = fmin(alpha, 2. / 3.);
+    lambda *= fmax(1. / 3., alpha);
+    ni = 2;
+  } else {
+    lambda *= ni;
+    ni *= 2;
+  }
+}
+
 struct GmmDev {
   const double* rec12;
   const double* axis;

@@ -13,7 +13,10 @@
 //       S = Hpp - sum W D^-1 W^T and g = bp - sum W D^-1 b without a single atomic.
 //   solve  in-place right-looking LDL^T of the 6P x 6P system by the whole workgroup.
 //   P3  back-substitution per point, trial state, new errors, rho test.
-// Control flow and gating as in gl_ba.hip (g2o Levenberg, 5 / 5 / 40 schedule).
+// Control flow and gating as in gl_ba.hip (g2o Levenberg, 5 / 5 / 40 schedule).  The reference's rules - set-up, which vertices are
+// active, prior edges, lambda init, right-hand side, trial poses, the Levenberg verdict and what follows it, the two gates and the
+// outputs - are stated ONCE, in the section "The RULES of jointOptimization" below (and ba_stop_now / reproj_outlier / lm_update in
+// gl_ba_common.hpp, diag_terms next to the solve): this kernel and the pipelined shape further down (kp_*) both call them.
 //
 // A problem is worked on by NB co-resident workgroups (cooperative launch): the point / observation
 // loops and the (j1, j2) blocks are strided over all of them, phases are separated by a
@@ -86,13 +89,12 @@ struct GenP {
   unsigned epoch;      // barriers passed
   double* part;        // NB x 4 partial sums
   int* flagg;          // [0] solve status, [1] the stop word as workgroup 0 last saw it
-  // setForceStopFlag (localization_opt.cpp:541-542): optional stop word, polled once per Levenberg trial by workgroup 0 and
-  // acted on where g2o tests terminate(): before an outer iteration.  > 0: stop; < 0: a budget of -value outer iterations
+  // optional stop word, polled once per Levenberg trial by workgroup 0 and acted on where g2o tests terminate(): before an outer
+  // iteration (ba_stop_now, gl_ba_common.hpp)
   const int32_t* stop;
   int stop_seen, done_iters;
   int trials;  // Levenberg trials so far (linearise + reduce + solve + evaluate): the unit of the kernel's algorithmic work
 };
-GL_DEV bool stop_now(const GenP& G) { return G.stop_seen > 0 || (G.stop_seen < 0 && G.done_iters >= -G.stop_seen); }
 GL_DEV int stop_word_load(const int32_t* w) { return __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 
 // k_ba_gen (the persistent kernel) keeps the ~40 addresses of a problem's state in a TABLE at the end of the problem's scratch area
@@ -290,6 +292,142 @@ GL_DEV void store_pose_Rt(const SE3& T, double* Rt) {
   Rt[10] = T.t[1];
   Rt[11] = T.t[2];
 }
+
+// =====================================================================================================================
+// The RULES of jointOptimization, each stated once for both launch shapes (the persistent kernel k_ba_gen_t / gen_optimize and
+// the pipelined kernels kp_*): the body for one pose, point, observation or row, or the scalar decision.  A caller brings its own
+// work distribution and its own order of partial sums; the argument-only rules (ba_stop_now, reproj_outlier, lm_update) are in
+// gl_ba_common.hpp, the diagonal terms of the assembled system in diag_terms / diag_terms_in_place next to the solve.
+// ---- set-up ----
+// pose j of the P + F: {R, t}; vSE3->setFixed(idx_ == 0) (:578-580); a free pose's prior measures e->setMeasurement(kf->getTcw())
+GL_DEV void setup_pose(const GenP& G, const BaK& k, int j) {
+  const SE3 T = se3_load(G.poses + (size_t)j * 7);
+  store_pose_Rt(T, G.Rt + (size_t)j * 12);
+  bool fr = j < G.P;
+  if (fr && G.prior[j] && !k.first_as_prior) fr = false;
+  G.pfree[j] = fr ? 1 : 0;
+  if (j < G.P) se3_store(se3_inverse(T), G.pinv + (size_t)j * 7);
+}
+// point l and its observations: every edge at level 0, no error yet (the partner table starts at -1 everywhere)
+GL_DEV void setup_point(const GenP& G, int l) {
+  G.lev_g[l] = 0;
+  for (int o = G.optr[l]; o < G.optr[l + 1]; ++o) {
+    G.opoint[o] = l;
+    G.lev_o[o] = 0;
+    G.chi_o[o] = 0.0;
+  }
+}
+// ---- initializeOptimization(0): a vertex is active when an edge at level 0 touches it ----
+GL_DEV int pose_active_by_prior(const GenP& G, const BaK& k, int j) { return (G.pfree[j] && G.prior[j] && k.first_as_prior) ? 1 : 0; }
+GL_DEV bool point_active_by_gmm(const GenP& G, int l, int lev_g) { return G.assoc[l] >= 0 && !lev_g; }
+// an observation at level `lev` in pose j: activates its point (returned) and its pose if that one is free (same-value stores)
+GL_DEV bool obs_activates(const GenP& G, int lev, int j) {
+  if (lev) return false;
+  if (G.pfree[j]) G.pact[j] = 1;
+  return true;
+}
+// ---- once per outer iteration: the prior edge of pose j linearised at `poses` (information, rhs, chi2; zeros without one) ----
+GL_DEV void prior_edge(const GenP& G, const BaK& k, int j, const double* poses) {
+  double H[36], b[6] = {0, 0, 0, 0, 0, 0}, chi = 0.0;
+  for (int r = 0; r < 36; ++r) H[r] = 0.0;
+  if (G.pact[j] && G.prior[j] && k.first_as_prior)
+    chi = prior_terms(se3_load(G.pinv + (size_t)j * 7), se3_load(poses + (size_t)j * 7), true, H, b);
+  for (int r = 0; r < 36; ++r) G.prH[(size_t)j * 36 + r] = H[r];
+  for (int r = 0; r < 6; ++r) G.prb[(size_t)j * 6 + r] = b[r];
+  G.pchi[j] = chi;
+}
+// ---- computeLambdaInit: 1e-5 x the largest diagonal element of the undamped system, nu = 2 ----
+// row i of the pose part joins the running maximum md (S: the Schur pass without damping, diagonal blocks only); active poses only
+GL_DEV double lambda_init_row(const GenP& G, const double* S, int ld, int i, double md) {
+  const int j = i / 6, r = i - 6 * j;
+  return G.pact[j] ? fmax(md, fabs(S[(size_t)i * ld + i] + G.prH[(size_t)j * 36 + r * 6 + r])) : md;
+}
+GL_DEV void lambda_init(double max_diag, double& lambda, double& ni) {
+  lambda = 1e-5 * max_diag;
+  ni = 2.0;
+}
+// ---- per trial ----
+// row i of the right-hand side: the Schur pass's g plus the prior's part, which also joins b_p (kept for the scale of rho)
+GL_DEV double rhs_row(const GenP& G, const BaK& k, int i) {
+  const int j = i / 6;
+  double v = G.gv[i];
+  if (G.pact[j] && G.prior[j] && k.first_as_prior) {
+    const double b = G.prb[i];
+    v += b;
+    G.bp[i] += b;
+  }
+  G.dxv[i] = v;
+  return v;
+}
+// trial state of pose j: exp(dx) T (the step of an inactive pose, or of a failed solve, is zeroed), its {R, t}, the prior's chi2 there
+GL_DEV void trial_pose(const GenP& G, const BaK& k, int j, bool ok) {
+  const SE3 T = se3_load(G.poses + (size_t)j * 7);
+  SE3 Tn = T;
+  if (G.pact[j] && ok) {
+    double dx[6];
+    for (int r = 0; r < 6; ++r) dx[r] = G.dxv[6 * j + r];
+    Tn = se3_mul(se3_exp(dx), T);
+  } else {
+    for (int r = 0; r < 6; ++r) G.dxv[6 * j + r] = 0.0;
+  }
+  se3_store(Tn, G.qN + (size_t)j * 7);
+  store_pose_Rt(Tn, G.RtN + (size_t)j * 12);
+  G.pchi2[j] = (G.pact[j] && G.prior[j] && k.first_as_prior)
+                   ? prior_terms(se3_load(G.pinv + (size_t)j * 7), Tn, false, nullptr, nullptr)
+                   : 0.0;
+}
+// The Levenberg verdict on a trial (OptimizationAlgorithmLevenberg::solve).  scale / tempChi come in as the callers' sums over the
+// points (the linear model's gain, the robust chi2 at the trial state); added here, in this order: the prior chi2 in pose order, then
+// dx . (lambda dx + b_p) in ascending i, then the failed solve's override, then + 1e-3.  Returns accept; rho, lambda, nu and the
+// current chi2 are updated.
+GL_DEV bool lm_verdict(double scale, double tempChi, const double* pchi2, const double* dxv, const double* bp, int P, bool ok,
+                       double& lambda, double& ni, double& currentChi, double& rho) {
+  const int n = 6 * P;
+  for (int j = 0; j < P; ++j) tempChi += pchi2[j];
+  for (int i = 0; i < n; ++i) scale += dxv[i] * (lambda * dxv[i] + bp[i]);
+  if (!ok) tempChi = 1.7976931348623157e308;
+  scale += 1e-3;
+  rho = (currentChi - tempChi) / scale;
+  const bool accept = rho > 0 && isfinite(tempChi);
+  lm_update(rho, accept, lambda, ni);
+  if (accept) currentChi = tempChi;
+  return accept;
+}
+// what follows the qmax-th trial of outer iteration `it` (0-based) of an optimize(iters) that has done done_iters outer iterations
+// before this one: 0 retry (g2o's retry loop: rho < 0, fewer than 10 trials, terminate() not raised), 1 next outer iteration,
+// 2 the stage is over (10 trials, rho == 0, the iterations used up, or the stop test before the next one)
+GL_DEV int lm_next(double rho, int qmax, int it, int iters, int stop_seen, int done_iters) {
+  if (rho < 0 && qmax < 10 && !(stop_seen > 0)) return 0;
+  return (qmax == 10 || rho == 0 || it + 1 >= iters || ba_stop_now(stop_seen, done_iters + 1)) ? 2 : 1;
+}
+// an accepted trial becomes the current state: pose j (with its {R, t}), point l (`active`, `pn`: its flag and its trial position)
+GL_DEV void accept_pose(const GenP& G, int j) {
+  if (!G.pact[j]) return;
+  for (int r = 0; r < 7; ++r) G.poses[(size_t)j * 7 + r] = G.qN[(size_t)j * 7 + r];
+  for (int r = 0; r < 12; ++r) G.Rt[(size_t)j * 12 + r] = G.RtN[(size_t)j * 12 + r];
+}
+GL_DEV void accept_point(const GenP& G, int l, int active, const double* pn) {
+  if (!active) return;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) G.pts[(size_t)l * 3 + i] = pn[i];
+}
+// ---- the gates between the stages, and the outputs (same predicates at the final state) ----
+// structure gate of point l (:773-786; `dropped`, :837-853): a degenerate component whose GMM error exceeds the threshold
+GL_DEV bool structure_over(const BaK& k, const GmmRef& g, const double* p) { return g.has && g.deg && gmm_chi2(k, g, p) > k.str_thresh; }
+GL_DEV bool structure_outlier(const GenP& G, const BaK& k, const GmmDev& gm, int l) {
+  GmmRef g;
+  load_gmm(G.assoc[l], gm.axis, gm.rec12, gm.sqrt_info, gm.flags, g);
+  return structure_over(k, g, G.pts + (size_t)l * 3);
+}
+// reprojection gate of observation o of point l (bDoMore; `erase`): the chi2 of its last evaluation, the depth at the current state
+GL_DEV bool reproj_gate(const GenP& G, int o, int l) {
+  const double* Rt = G.Rt + (size_t)G.opose[o] * 12;
+  const double* p = G.pts + (size_t)l * 3;
+  const double z = Rt[6] * p[0] + Rt[7] * p[1] + Rt[8] * p[2] + Rt[11];
+  const bool stereo = !(G.ouvr[(size_t)o * 3 + 2] < 0);
+  return reproj_outlier(G.chi_o[o], stereo, z);
+}
+// =====================================================================================================================
 
 // reprojection linearisation in the camera frame: q, A (sym6), a; returns chi2, rho0
 GL_DEV void lin_obs(const BaK& k, const double* R, const double* t, const double* p, const double* ob, int oc,
@@ -898,6 +1036,20 @@ GL_DEV double diag_terms(const GenP& G, const BaK& k, double lambda, int r, int 
   if (r == c) v += lambda;
   return v;
 }
+// the same terms written into the matrix, for the whole diagonal block of pose j, where a solve factorises in place (the flags read once:
+// as a loop over diag_terms() the one-workgroup persistent kernel was 9 % slower on a 1 + 1 window)
+GL_DEV void diag_terms_in_place(const GenP& G, const BaK& k, double lambda, double* S, int ld, int j) {
+  if (!G.pact[j]) {
+    for (int r = 0; r < 6; ++r) S[(size_t)(6 * j + r) * ld + 6 * j + r] = 1.0;
+    return;
+  }
+  if (G.prior[j] && k.first_as_prior) {
+    const double* H = G.prH + (size_t)j * 36;
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) S[(size_t)(6 * j + r) * ld + 6 * j + c] += H[r * 6 + c];
+  }
+  for (int r = 0; r < 6; ++r) S[(size_t)(6 * j + r) * ld + 6 * j + r] += lambda;
+}
 
 GL_DEV double readlane_f64(double v, int lane) {
   union {
@@ -1360,19 +1512,15 @@ GL_DEV int gen_optimize(const BaK& k, const GmmDev& gm, GenP& G, k_genp* sG, boo
   const int lpp = (G.NB * T_BA >= 4 * G.L) ? 4 : (G.NB * T_BA >= 2 * G.L) ? 2 : 1;
   double acc[32];
   // ---- initializeOptimization(0): active poses / points -----------------------------------
-  for (int j = GSTART; j < P; j += GSTRIDE) G.pact[j] = (G.pfree[j] && G.prior[j] && k.first_as_prior) ? 1 : 0;
+  for (int j = GSTART; j < P; j += GSTRIDE) G.pact[j] = pose_active_by_prior(G, k, j);
   prob_sync(G);
   GFRESH();
 #pragma unroll
   for (int i = 0; i < 32; ++i) acc[i] = 0.0;
   for (int l = GSTART; l < G.L; l += GSTRIDE) {
-    bool any = G.assoc[l] >= 0 && !G.lev_g[l];
+    bool any = point_active_by_gmm(G, l, G.lev_g[l]);
     for (int o = G.optr[l]; o < G.optr[l + 1]; ++o)
-      if (!G.lev_o[o]) {
-        any = true;
-        const int j = G.opose[o];
-        if (G.pfree[j]) G.pact[j] = 1;  // benign same-value race
-      }
+      if (obs_activates(G, G.lev_o[o], G.opose[o])) any = true;  // (benign same-value race on the pose's flag)
     G.lact[l] = any ? 1 : 0;
     if (any) acc[0] += 1.0;
   }
@@ -1390,24 +1538,15 @@ GL_DEV int gen_optimize(const BaK& k, const GmmDev& gm, GenP& G, k_genp* sG, boo
   int cj = 0;
   bool fresh = false;     // the records of the last point pass are those of the current state (point_relambda)
   double chi_keep = 0.0;  // this thread's part of the robust chi2 of that pass
-  for (int it = 0; it < iters; ++it) {
-    if (stop_now(G)) break;  // SparseOptimizer::optimize: `i < iterations && !terminate()`
+  int nx = (iters < 1 || ba_stop_now(G.stop_seen, G.done_iters)) ? 2 : 1;  // (the stop test in front of the first outer iteration; lm_next has the later ones)
+  for (int it = 0; nx == 1; ++it) {
     // Prior edges at the current state: that state changes once per outer iteration (an accepted trial ends the
     // inner loop), so their information / rhs / chi2 are formed here and not per trial, by the LAST threads of the
     // problem - which have no point of the first pass when the problem's threads outnumber its points - so that the
     // serial pose algebra overlaps the point pass; the barriers of that pass publish the result.
     {
       const int rev = G.NB * T_BA - 1 - (G.pb * T_BA + tid);
-      if (rev < P) {
-        const int j = rev;
-        double H[36], b[6] = {0, 0, 0, 0, 0, 0}, chi = 0.0;
-        for (int r = 0; r < 36; ++r) H[r] = 0.0;
-        if (G.pact[j] && G.prior[j] && k.first_as_prior)
-          chi = prior_terms(se3_load(G.pinv + (size_t)j * 7), se3_load(G.poses + (size_t)j * 7), true, H, b);
-        for (int r = 0; r < 36; ++r) G.prH[(size_t)j * 36 + r] = H[r];
-        for (int r = 0; r < 6; ++r) G.prb[(size_t)j * 6 + r] = b[r];
-        G.pchi[j] = chi;
-      }
+      if (rev < P) prior_edge(G, k, rev, G.poses);
     }
     if (it == 0) {  // computeLambdaInit
       double md = 0.0;
@@ -1419,14 +1558,11 @@ GL_DEV int gen_optimize(const BaK& k, const GmmDev& gm, GenP& G, k_genp* sG, boo
       pass_blocks(G, false, p2part);
       prob_sync(G);
       GFRESH();
-      for (int j = GSTART; j < P; j += GSTRIDE) {
-        if (!G.pact[j]) continue;
-        for (int r = 0; r < 6; ++r) md = fmax(md, fabs(S[(size_t)(6 * j + r) * ld + 6 * j + r] + G.prH[(size_t)j * 36 + r * 6 + r]));
-      }
+      for (int j = GSTART; j < P; j += GSTRIDE)
+        for (int r = 0; r < 6; ++r) md = lambda_init_row(G, S, ld, 6 * j + r, md);
       md = prob_max(G, md, red);
       GFRESH();
-      lambda = 1e-5 * md;
-      ni = 2.0;
+      lambda_init(md, lambda, ni);
     }
     double rho = 0.0, currentChi = 0.0;
     int qmax = 0;
@@ -1464,29 +1600,11 @@ GL_DEV int gen_optimize(const BaK& k, const GmmDev& gm, GenP& G, k_genp* sG, boo
         // one) and factorises it in the LDS work matrix; larger systems are factorised in place in global memory
         const bool small = n <= 128 && s_lds != nullptr;
         if (G.NB == 1 || !small) {
-          for (int j = tid; j < P; j += T_BA) {
-            if (!G.pact[j]) {
-              for (int r = 0; r < 6; ++r) S[(size_t)(6 * j + r) * ld + 6 * j + r] = 1.0;
-              continue;
-            }
-            if (G.prior[j] && k.first_as_prior) {
-              const double* H = G.prH + (size_t)j * 36;
-              for (int r = 0; r < 6; ++r)
-                for (int c = 0; c < 6; ++c) S[(size_t)(6 * j + r) * ld + 6 * j + c] += H[r * 6 + c];
-            }
-            for (int r = 0; r < 6; ++r) S[(size_t)(6 * j + r) * ld + 6 * j + r] += lambda;
-          }
+          for (int j = tid; j < P; j += T_BA) diag_terms_in_place(G, k, lambda, S, ld, j);
         }
         // right-hand side (+ the prior's), into the solve's LDS vector when the system is small enough for it
         for (int i = tid; i < n; i += T_BA) {
-          const int j = i / 6;
-          double v = G.gv[i];
-          if (G.pact[j] && G.prior[j] && k.first_as_prior) {
-            const double b = G.prb[i];
-            v += b;
-            G.bp[i] += b;
-          }
-          G.dxv[i] = v;
+          const double v = rhs_row(G, k, i);
           if (n <= 128) red[128 + i] = v;
         }
         __syncthreads();
@@ -1502,23 +1620,7 @@ GL_DEV int gen_optimize(const BaK& k, const GmmDev& gm, GenP& G, k_genp* sG, boo
         __syncthreads();
         GP_T(u2);
         GP_ADD(6, t3, u0); GP_ADD(8, u0, u2);
-        // trial poses
-        for (int j = tid; j < P; j += T_BA) {
-          const SE3 T = se3_load(G.poses + (size_t)j * 7);
-          SE3 Tn = T;
-          if (G.pact[j] && ok) {
-            double dx[6];
-            for (int r = 0; r < 6; ++r) dx[r] = G.dxv[6 * j + r];
-            Tn = se3_mul(se3_exp(dx), T);
-          } else {
-            for (int r = 0; r < 6; ++r) G.dxv[6 * j + r] = 0.0;
-          }
-          se3_store(Tn, G.qN + (size_t)j * 7);
-          store_pose_Rt(Tn, G.RtN + (size_t)j * 12);
-          G.pchi2[j] = (G.pact[j] && G.prior[j] && k.first_as_prior)
-                           ? prior_terms(se3_load(G.pinv + (size_t)j * 7), Tn, false, nullptr, nullptr)
-                           : 0.0;
-        }
+        for (int j = tid; j < P; j += T_BA) trial_pose(G, k, j, ok);
       }
       prob_sync(G);
       GFRESH();
@@ -1532,34 +1634,11 @@ GL_DEV int gen_optimize(const BaK& k, const GmmDev& gm, GenP& G, k_genp* sG, boo
       pass_trial_lpp(lpp, k, gm, G, robust, lambda, P, acc);
       prob_reduce<2>(G, acc, red);
       GFRESH();
-      double scale = acc[0], tempChi = acc[1];
-      for (int j = 0; j < P; ++j) tempChi += G.pchi2[j];
-      for (int i = 0; i < n; ++i) scale += G.dxv[i] * (lambda * G.dxv[i] + G.bp[i]);
-      if (!ok2) tempChi = 1.7976931348623157e308;
-      scale += 1e-3;
-      rho = (currentChi - tempChi) / scale;
-      if (rho > 0 && isfinite(tempChi)) {
-        const double uu = 2 * rho - 1;
-        double alpha = 1. - uu * uu * uu;
-        alpha = fmin(alpha, 2. / 3.);
-        lambda *= fmax(1. / 3., alpha);
-        ni = 2;
-        currentChi = tempChi;
-        fresh = false;
-        for (int j = GSTART; j < P; j += GSTRIDE) {
-          if (!G.pact[j]) continue;
-          for (int r = 0; r < 7; ++r) G.poses[(size_t)j * 7 + r] = G.qN[(size_t)j * 7 + r];
-          for (int r = 0; r < 12; ++r) G.Rt[(size_t)j * 12 + r] = G.RtN[(size_t)j * 12 + r];
-        }
-        for (int l = GSTART; l < G.L; l += GSTRIDE) {
-          if (!G.lact[l]) continue;
-#pragma unroll
-          for (int i = 0; i < 3; ++i) G.pts[(size_t)l * 3 + i] = G.pn[(size_t)l * 3 + i];
-        }
-      } else {
-        lambda *= ni;
-        ni *= 2;
-        fresh = true;
+      const bool accept = lm_verdict(acc[0], acc[1], G.pchi2, G.dxv, G.bp, P, ok2, lambda, ni, currentChi, rho);
+      fresh = !accept;
+      if (accept) {
+        for (int j = GSTART; j < P; j += GSTRIDE) accept_pose(G, j);
+        for (int l = GSTART; l < G.L; l += GSTRIDE) accept_point(G, l, G.lact[l], G.pn + (size_t)l * 3);
       }
       prob_sync(G);
       GFRESH();
@@ -1567,10 +1646,10 @@ GL_DEV int gen_optimize(const BaK& k, const GmmDev& gm, GenP& G, k_genp* sG, boo
       ++G.trials;
       GP_T(t5);
       GP_ADD(0, t0, t1); GP_ADD(1, t1, t2); GP_ADD(2, t2, t3); GP_ADD(3, t3, t4); GP_ADD(4, t4, t5); GP_ADD(5, 0, 1);
-    } while (rho < 0 && qmax < 10 && !(G.stop_seen > 0));  // (g2o's retry loop tests terminate() too)
+      nx = lm_next(rho, qmax, it, iters, G.stop_seen, G.done_iters);
+    } while (nx == 0);
     ++cj;
     ++G.done_iters;
-    if (qmax == 10 || rho == 0) break;
   }
   return cj;
 }
@@ -1617,22 +1696,8 @@ __global__ __launch_bounds__(T_BA) void k_ba_gen_t(BaK k, GmmDev gm, int B, int 
   GFRESH();
 
   // ---- setup --------------------------------------------------------------------------------------
-  for (int j = GSTART; j < P + F; j += GSTRIDE) {
-    const SE3 T = se3_load(G.poses + (size_t)j * 7);
-    store_pose_Rt(T, G.Rt + (size_t)j * 12);
-    bool fr = j < P;
-    if (fr && G.prior[j] && !k.first_as_prior) fr = false;  // vSE3->setFixed(idx_ == 0) (:578-580)
-    G.pfree[j] = fr ? 1 : 0;
-    if (j < P) se3_store(se3_inverse(T), G.pinv + (size_t)j * 7);  // e->setMeasurement(kf->getTcw())
-  }
-  for (int l = GSTART; l < L; l += GSTRIDE) {
-    G.lev_g[l] = 0;
-    for (int o = G.optr[l]; o < G.optr[l + 1]; ++o) {
-      G.opoint[o] = l;
-      G.lev_o[o] = 0;
-      G.chi_o[o] = 0.0;
-    }
-  }
+  for (int j = GSTART; j < P + F; j += GSTRIDE) setup_pose(G, k, j);
+  for (int l = GSTART; l < L; l += GSTRIDE) setup_point(G, l);
   for (size_t i = GSTART; i < (size_t)nobs * P; i += GSTRIDE) G.plm[i] = -1;
   prob_sync(G);
   GFRESH();
@@ -1695,16 +1760,16 @@ __global__ __launch_bounds__(T_BA) void k_ba_gen_t(BaK k, GmmDev gm, int B, int 
   GFRESH();
   double* s_lds = s_in_lds ? dyn_lds : nullptr;
 
-  // ---- schedule (:770-828) ---------------------------------------------------------------------------
+  // ---- schedule: optimize(5), structure gate, optimize(5), reprojection gate, optimize(40) -----------------
   // (three inlined copies of the optimiser, each with its constants folded: a loop over the stages gives a third of
   // the code but other contraction decisions, i.e. other last bits than the validated build)
   gen_optimize(k, gm, G, sG, true, 5, red, &s_flag, s_lds, p2part);
   prob_sync(G);
   GFRESH();
-  for (int l = GSTART; l < L; l += GSTRIDE) {
+  for (int l = GSTART; l < L; l += GSTRIDE) {  // structure_outlier, written out: through the call this kernel's scratch grew from 24 to 40 bytes
     GmmRef g;
     load_gmm(G.assoc[l], gm.axis, gm.rec12, gm.sqrt_info, gm.flags, g);
-    if (g.has && g.deg && gmm_chi2(k, g, G.pts + (size_t)l * 3) > k.str_thresh) G.lev_g[l] = 1;
+    if (structure_over(k, g, G.pts + (size_t)l * 3)) G.lev_g[l] = 1;
   }
   prob_sync(G);
   GFRESH();
@@ -1712,15 +1777,10 @@ __global__ __launch_bounds__(T_BA) void k_ba_gen_t(BaK k, GmmDev gm, int B, int 
   prob_sync(G);
   GFRESH();
   int it3 = 0;
-  if (!stop_now(G)) {  // bDoMore (:791-796)
+  if (!ba_stop_now(G.stop_seen, G.done_iters)) {  // bDoMore
     for (int l = GSTART; l < L; l += GSTRIDE)
-      for (int o = G.optr[l]; o < G.optr[l + 1]; ++o) {
-        const double* Rt = G.Rt + (size_t)G.opose[o] * 12;
-        const double* p = G.pts + (size_t)l * 3;
-        const double z = Rt[6] * p[0] + Rt[7] * p[1] + Rt[8] * p[2] + Rt[11];
-        const bool stereo = !(G.ouvr[(size_t)o * 3 + 2] < 0);
-        if (G.chi_o[o] > (stereo ? 7.815 : 5.991) || !(z > 0.0)) G.lev_o[o] = 1;
-      }
+      for (int o = G.optr[l]; o < G.optr[l + 1]; ++o)
+        if (reproj_gate(G, o, l)) G.lev_o[o] = 1;
     prob_sync(G);
     GFRESH();
     // the partner table forgets the edges that are now at level 1
@@ -1734,18 +1794,10 @@ __global__ __launch_bounds__(T_BA) void k_ba_gen_t(BaK k, GmmDev gm, int B, int 
     prob_sync(G);
     GFRESH();
   }
-  // ---- outputs (:837-879) ---------------------------------------------------------------------------
+  // ---- outputs: the two gates at the final state ---------------------------------------------------------
   for (int l = GSTART; l < L; l += GSTRIDE) {
-    GmmRef g;
-    load_gmm(G.assoc[l], gm.axis, gm.rec12, gm.sqrt_info, gm.flags, g);
-    const double* p = G.pts + (size_t)l * 3;
-    dropped_all[(size_t)f * L + l] = (g.has && g.deg && gmm_chi2(k, g, p) > k.str_thresh) ? 1 : 0;
-    for (int o = G.optr[l]; o < G.optr[l + 1]; ++o) {
-      const double* Rt = G.Rt + (size_t)G.opose[o] * 12;
-      const double z = Rt[6] * p[0] + Rt[7] * p[1] + Rt[8] * p[2] + Rt[11];
-      const bool stereo = !(G.ouvr[(size_t)o * 3 + 2] < 0);
-      erase_all[(size_t)f * NOBS + o] = (G.chi_o[o] > (stereo ? 7.815 : 5.991) || !(z > 0.0)) ? 1 : 0;
-    }
+    dropped_all[(size_t)f * L + l] = structure_outlier(G, k, gm, l) ? 1 : 0;
+    for (int o = G.optr[l]; o < G.optr[l + 1]; ++o) erase_all[(size_t)f * NOBS + o] = reproj_gate(G, o, l) ? 1 : 0;
   }
   if (G.pb == 0 && tid == 0 && iters_all) iters_all[f] = it3;
   if (G.pb == 0 && tid == 0 && trials_out) trials_out[f] = G.trials;
@@ -1842,30 +1894,22 @@ GL_DEV void genp_init(GenP& G, const PipeA& a, int f, int NB, int pb) {
   genp_problem(G, f, a.B, a.P, a.F, a.L, a.NOBS, a.poses, a.prior, a.pts, a.assoc, a.optr, a.opose, a.ouvr, a.ooct, a.stop, a.scratch, a.per);
 }
 
-// prior edges at the current state (once per outer iteration: gen_optimize does the same)
+// prior edges at the current state, a thread per pose
 GL_DEV void pipe_priors(const BaK& k, GenP& G, const double* poses) {
   const int NT = blockDim.x;
-  for (int j = threadIdx.x; j < G.P; j += NT) {
-    double H[36], b[6] = {0, 0, 0, 0, 0, 0}, chi = 0.0;
-    for (int r = 0; r < 36; ++r) H[r] = 0.0;
-    if (G.pact[j] && G.prior[j] && k.first_as_prior)
-      chi = prior_terms(se3_load(G.pinv + (size_t)j * 7), se3_load(poses + (size_t)j * 7), true, H, b);
-    for (int r = 0; r < 36; ++r) G.prH[(size_t)j * 36 + r] = H[r];
-    for (int r = 0; r < 6; ++r) G.prb[(size_t)j * 6 + r] = b[r];
-    G.pchi[j] = chi;
-  }
+  for (int j = threadIdx.x; j < G.P; j += NT) prior_edge(G, k, j, poses);
 }
-GL_DEV bool pipe_stop_now(const PipeSt* st) { return st->stop_seen > 0 || (st->stop_seen < 0 && st->done_iters >= -st->stop_seen); }
+GL_DEV bool pipe_stop_now(const PipeSt* st) { return ba_stop_now(st->stop_seen, st->done_iters); }
 
 
-// ---- the end of a stage (k_ba_gen's schedule code between its three optimize() calls, :773-879), spread over the kernels of ONE
+// ---- the end of a stage (what k_ba_gen does between its three optimize() calls, by the same rules), spread over the kernels of ONE
 // cycle so that nothing that walks the points or the observations sits on a single workgroup (one workgroup took 75 k cycles per
 // stage change at 12 600 observations, 280 k at 58 600 - 4 - 6 % of the whole call):
 //   (A) the head kernel, by point (each workgroup its own points, right after it has accepted them): the fresh error of the
-//       degenerate GMM edges after stage 0 (:773-786), the point half of initializeOptimization(0) of the next stage - or, after
-//       the last stage, the `dropped` output;
-//   (B) the Schur pass's grid, by observation: the reprojection gate after stage 1 (bDoMore, :791-796), the observation half of
-//       initializeOptimization(0) (same-value stores) - or the `erase` output;
+//       degenerate GMM edges after stage 0 (structure_outlier), the point half of initializeOptimization(0) of the next stage - or,
+//       after the last stage, the `dropped` output;
+//   (B) the Schur pass's grid, by observation: the reprojection gate after stage 1 (reproj_gate), the observation half of
+//       initializeOptimization(0) (obs_activates: same-value stores) - or the `erase` output;
 //   (C) the solve kernel's workgroup: the counts, the loop variables of the next stage, its prior edges - or the scalar outputs.
 // A stage that does not run (nothing active: optimize() returns -1; or the stop word) leaves `adv` set and the next cycle does
 // the next gate.  ds = the stage that has ended (-1: none yet, the call opens), the same in the three kernels of the cycle.
@@ -1875,46 +1919,34 @@ GL_DEV void pipe_adv_points(const PipeA& a, const GenP& G, const PipeSt& q, int 
   const int ds = q.stage, next = pipe_next_stage(q), per = T_BA / a.lpp, tid = threadIdx.x;
   if (tid < per) {
     for (int l = pb * per + tid; l < G.L; l += a.nba * per) {
-      GmmRef g;
-      load_gmm(G.assoc[l], a.gm.axis, a.gm.rec12, a.gm.sqrt_info, a.gm.flags, g);
-      const bool over = g.has && g.deg && gmm_chi2(a.k, g, G.pts + (size_t)l * 3) > a.k.str_thresh;
+      const bool over = structure_outlier(G, a.k, a.gm, l);
       int lg = G.lev_g[l];
       if (ds == 0 && over) {
         lg = 1;
         G.lev_g[l] = 1;
       }
       if (next >= 3) a.dropped[(size_t)f * G.L + l] = over ? 1 : 0;
-      else G.lact[l] = (G.assoc[l] >= 0 && !lg) ? 1 : 0;
+      else G.lact[l] = point_active_by_gmm(G, l, lg) ? 1 : 0;
     }
   }
   if (pb == 0 && next < 3)
-    for (int j = tid; j < G.P; j += T_BA) G.pact[j] = (G.pfree[j] && G.prior[j] && a.k.first_as_prior) ? 1 : 0;
+    for (int j = tid; j < G.P; j += T_BA) G.pact[j] = pose_active_by_prior(G, a.k, j);
 }
-// (B) `w` of `nw` waves of the problem; the reprojection gate of an observation at the current state: stale chi2 above the threshold
-// of its edge type, or the point behind the camera (:799-825, :855-879)
+// (B) `w` of `nw` waves of the problem
 GL_DEV void pipe_adv_obs(const PipeA& a, const GenP& G, const PipeSt& q, int f, int w, int nw) {
   const int ds = q.stage, next = pipe_next_stage(q), lane = threadIdx.x & 63, nobs = G.nobs;
   const bool gate = ds == 1 && !pipe_stop_now(&q);
   uint8_t* er = a.erase + (size_t)f * a.NOBS;
   for (int o = w * 64 + lane; o < nobs; o += nw * 64) {
     const int l = G.opoint[o], j = G.opose[o];
-    const double chi = G.chi_o[o], ur = G.ouvr[(size_t)o * 3 + 2];
     int lv = G.lev_o[o];
-    const int fr = G.pfree[j];
-    const double* Rt = G.Rt + (size_t)j * 12;
-    const double* p = G.pts + (size_t)l * 3;
-    const double z = Rt[6] * p[0] + Rt[7] * p[1] + Rt[8] * p[2] + Rt[11];
-    const bool bad = chi > (!(ur < 0) ? 7.815 : 5.991) || !(z > 0.0);
+    const bool bad = reproj_gate(G, o, l);
     if (gate && bad) {
       lv = 1;
       G.lev_o[o] = 1;  // (the Schur pass of this shape tests the level flags itself: no sweep of the partner table)
     }
-    if (next >= 3) {
-      er[o] = bad ? 1 : 0;
-    } else if (!lv) {
-      G.lact[l] = 1;
-      if (fr) G.pact[j] = 1;
-    }
+    if (next >= 3) er[o] = bad ? 1 : 0;
+    else if (obs_activates(G, lv, j)) G.lact[l] = 1;
   }
 }
 // (C)
@@ -1996,7 +2028,7 @@ __global__ __launch_bounds__(T_BA) void kp_setup_init(PipeA a) {
       for (int i = 0; i < 16; ++i) st->dbg[i] = 0;
 #endif
       const int sw = a.stop ? stop_word_load(a.stop) : 0;
-      st->stage = sw > 0 ? 3 : -1;  // `if (pbStopFlag) if (*pbStopFlag) return;` (:765-767): nothing is written
+      st->stage = sw > 0 ? 3 : -1;  // the stop word set on entry, as in k_ba_gen_t: nothing is written
       st->adv = 1;                  // cycle 0 opens stage 0 (initializeOptimization(0): pipe_adv_*)
       st->init = 0;
       st->pend = 0;
@@ -2021,23 +2053,9 @@ __global__ __launch_bounds__(T_BA) void kp_setup_init(PipeA a) {
         atomicSub(a.unfinished, 1);
       }
     }
-    for (int j = tid; j < P + F; j += T_BA) {
-      const SE3 T = se3_load(G.poses + (size_t)j * 7);
-      store_pose_Rt(T, G.Rt + (size_t)j * 12);
-      bool fr = j < P;
-      if (fr && G.prior[j] && !a.k.first_as_prior) fr = false;  // vSE3->setFixed(idx_ == 0) (:578-580)
-      G.pfree[j] = fr ? 1 : 0;
-      if (j < P) se3_store(se3_inverse(T), G.pinv + (size_t)j * 7);  // e->setMeasurement(kf->getTcw())
-    }
+    for (int j = tid; j < P + F; j += T_BA) setup_pose(G, a.k, j);
   }
-  for (int l = GSTART; l < L; l += GSTRIDE) {
-    G.lev_g[l] = 0;
-    for (int o = G.optr[l]; o < G.optr[l + 1]; ++o) {
-      G.opoint[o] = l;
-      G.lev_o[o] = 0;
-      G.chi_o[o] = 0.0;
-    }
-  }
+  for (int l = GSTART; l < L; l += GSTRIDE) setup_point(G, l);
   for (size_t i = GSTART; i < (size_t)G.nobs * P; i += GSTRIDE) G.plm[i] = -1;
 }
 // (2) / (4) pose-major CSR of the free poses' observations, ascending within a pose: a stable counting sort - a wave per 512
@@ -2164,34 +2182,15 @@ GL_DEV void pipe_judge(const PipeA& a, const GenP& G, const PipeSt& in, PipeSt& 
   const double* bps = dxs + n;
   const double* pc2 = bps + n;
   q = in;
-  const double lambda = q.lambda;
   if (q.qmax == 0) q.currentChi = q.chiA;
-  for (int j = 0; j < P; ++j) tempChi += pc2[j];
-  for (int i = 0; i < n; ++i) scale += dxs[i] * (lambda * dxs[i] + bps[i]);
-  if (!q.ok) tempChi = 1.7976931348623157e308;
-  scale += 1e-3;
-  const double rho = (q.currentChi - tempChi) / scale;
-  const bool acc = rho > 0 && isfinite(tempChi);
-  if (acc) {
-    const double uu = 2 * rho - 1;
-    double alpha = 1. - uu * uu * uu;
-    alpha = fmin(alpha, 2. / 3.);
-    q.lambda = lambda * fmax(1. / 3., alpha);
-    q.ni = 2;
-    q.currentChi = tempChi;
-  } else {
-    q.lambda = lambda * q.ni;
-    q.ni *= 2;
-  }
-  q.rho = rho;
+  const bool acc = lm_verdict(scale, tempChi, pc2, dxs, bps, P, q.ok != 0, q.lambda, q.ni, q.currentChi, q.rho);
   q.qmax += 1;
   q.trials += 1;
-  int nx = 0;  // 0 retry, 1 next outer iteration, 2 stage over
-  if (!(rho < 0 && q.qmax < 10 && !(q.stop_seen > 0))) {  // the outer iteration is over
+  const int nx = lm_next(q.rho, q.qmax, q.it, q.iters_max, q.stop_seen, q.done_iters);
+  if (nx != 0) {  // the outer iteration is over
     q.cj += 1;
     q.done_iters += 1;
     q.it += 1;
-    nx = (q.qmax == 10 || rho == 0 || q.it >= q.iters_max || pipe_stop_now(&q)) ? 2 : 1;
     q.qmax = 0;
   }
   q.pend = 0;
@@ -2316,25 +2315,15 @@ __global__ __launch_bounds__(T_BA) void kp_lin(PipeA a) {
   }
   // its points: trial -> current
   if (accept) {
-    if (has && la0) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) G.pts[(size_t)l0 * 3 + i] = pn0[i];
-    }
+    if (has) accept_point(G, l0, la0, pn0);  // (flag and trial position fetched above)
     for (int l = l0 + a.nba * per; l < G.L; l += a.nba * per) {  // (further rounds: none with nba = ceil(L lpp / T_BA))
       if (tid >= per) break;
-      if (!G.lact[l]) continue;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) G.pts[(size_t)l * 3 + i] = G.pn[(size_t)l * 3 + i];
+      accept_point(G, l, G.lact[l], G.pn + (size_t)l * 3);
     }
   }
   if (pb == 0) {
-    if (accept) {
-      for (int j = tid; j < P; j += T_BA) {
-        if (!G.pact[j]) continue;
-        for (int r = 0; r < 7; ++r) G.poses[(size_t)j * 7 + r] = G.qN[(size_t)j * 7 + r];
-        for (int r = 0; r < 12; ++r) G.Rt[(size_t)j * 12 + r] = G.RtN[(size_t)j * 12 + r];
-      }
-    }
+    if (accept)
+      for (int j = tid; j < P; j += T_BA) accept_pose(G, j);
     // the state the next outer iteration linearises the prior edges at (k_ba_gen: once per outer iteration)
     if (next == 1) pipe_priors(a.k, G, accept ? G.qN : G.poses);
     if (tid == 0) *sc = s_q;
@@ -2576,20 +2565,10 @@ __global__ __launch_bounds__(T_SOLVE) void kp_solve(PipeA a) {
   }
   double mine = 0.0;
   if (init) {
-    for (int i = tid; i < n; i += T_SOLVE) {
-      const int j = i / 6, r = i - 6 * j;
-      if (G.pact[j]) mine = fabs(G.S[(size_t)i * ld + i] + G.prH[(size_t)j * 36 + r * 6 + r]);
-    }
+    for (int i = tid; i < n; i += T_SOLVE) mine = lambda_init_row(G, G.S, ld, i, mine);
   } else {
     for (int i = tid; i < n; i += T_SOLVE) {
-      const int j = i / 6;
-      double v = G.gv[i];
-      if (G.pact[j] && G.prior[j] && a.k.first_as_prior) {
-        const double b = G.prb[i];
-        v += b;
-        G.bp[i] += b;
-      }
-      G.dxv[i] = v;
+      const double v = rhs_row(G, a.k, i);
       if (small) red[128 + i] = v;
     }
   }
@@ -2602,11 +2581,10 @@ __global__ __launch_bounds__(T_SOLVE) void kp_solve(PipeA a) {
 #ifdef GL_PIPE_PROF
   const long long s1 = clock64();
 #endif
-  if (init) {  // computeLambdaInit: 1e-5 x the largest diagonal of H_pp (+ prior) and H_ll
+  if (init) {  // computeLambdaInit over H_pp (+ prior) and H_ll
     md = fmax(md, block_max(mine, red));
     if (tid == 0) {
-      st->lambda = 1e-5 * md;
-      st->ni = 2.0;
+      lambda_init(md, st->lambda, st->ni);
       st->init = 0;
       st->pend = 0;
     }
@@ -2631,18 +2609,7 @@ __global__ __launch_bounds__(T_SOLVE) void kp_solve(PipeA a) {
            : n <= 80 ? ldlt_solve_teams<5>(GL, a.k, lambda, G.S, ld, W, ld, G.dxv, n, &s_flag, red)
                      : ldlt_solve_teams<8>(GL, a.k, lambda, G.S, ld, W, ld, G.dxv, n, &s_flag, red);
     } else {  // the scalar-pivot path factorises in global memory: the diagonal terms go in first
-      for (int j = tid; j < P; j += T_SOLVE) {
-        if (!G.pact[j]) {
-          for (int r = 0; r < 6; ++r) G.S[(size_t)(6 * j + r) * ld + 6 * j + r] = 1.0;
-          continue;
-        }
-        if (G.prior[j] && a.k.first_as_prior) {
-          const double* H = G.prH + (size_t)j * 36;
-          for (int r = 0; r < 6; ++r)
-            for (int c = 0; c < 6; ++c) G.S[(size_t)(6 * j + r) * ld + 6 * j + c] += H[r * 6 + c];
-        }
-        for (int r = 0; r < 6; ++r) G.S[(size_t)(6 * j + r) * ld + 6 * j + r] += lambda;
-      }
+      for (int j = tid; j < P; j += T_SOLVE) diag_terms_in_place(G, a.k, lambda, G.S, ld, j);
       __syncthreads();
       ok = ldlt_solve_large(G.S, G.dxv, n, ld, &s_flag);
     }
@@ -2651,22 +2618,7 @@ __global__ __launch_bounds__(T_SOLVE) void kp_solve(PipeA a) {
 #ifdef GL_PIPE_PROF
   const long long s3 = clock64();
 #endif
-  for (int j = tid; j < P; j += T_SOLVE) {  // trial poses
-    const SE3 T = se3_load(G.poses + (size_t)j * 7);
-    SE3 Tn = T;
-    if (G.pact[j] && ok) {
-      double dx[6];
-      for (int r = 0; r < 6; ++r) dx[r] = G.dxv[6 * j + r];
-      Tn = se3_mul(se3_exp(dx), T);
-    } else {
-      for (int r = 0; r < 6; ++r) G.dxv[6 * j + r] = 0.0;
-    }
-    se3_store(Tn, G.qN + (size_t)j * 7);
-    store_pose_Rt(Tn, G.RtN + (size_t)j * 12);
-    G.pchi2[j] = (G.pact[j] && G.prior[j] && a.k.first_as_prior)
-                     ? prior_terms(se3_load(G.pinv + (size_t)j * 7), Tn, false, nullptr, nullptr)
-                     : 0.0;
-  }
+  for (int j = tid; j < P; j += T_SOLVE) trial_pose(G, a.k, j, ok);
   if (tid == 0) {
     st->ok = ok ? 1 : 0;
     st->chiA = chiA;

@@ -11,7 +11,7 @@ gt = np.load(G + "/gt_sync.npz")["V1_01_easy"]
 cam, prm = api.Camera(), api.Params()
 ctx = gmmloc_amd.Context(0); g = gmmloc_amd.GMM(ctx, mean, cov, prm)
 if os.environ.get("BAGEN_MODE"):
-    ctx.set_option("bagen_mode", int(os.environ["BAGEN_MODE"]))  # 1 persistent kernel, 2 pipelined shape
+    ctx.set_option("bagen_mode", int(os.environ["BAGEN_MODE"]))  # 1 persistent kernel, 2 pipelined shape, 3 persistent, whole batch in one launch
 T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
 for (P, F, L, prior) in [(1, 0, 120, False), (1, 1, 200, True), (2, 2, 400, True), (4, 2, 800, False), (8, 4, 1500, True),
                          (12, 4, 2000, True), (20, 8, 3000, True), (21, 2, 1000, True), (22, 2, 1000, True)]:
@@ -28,3 +28,5 @@ for (P, F, L, prior) in [(1, 0, 120, False), (1, 1, 200, True), (2, 2, 400, True
             h = hashlib.sha1(poses.cpu().numpy().tobytes() + pts.cpu().numpy().tobytes()
                              + b"".join(x.cpu().numpy().tobytes() for x in out if hasattr(x, "cpu"))).hexdigest()[:16]
             print("P%d F%d L%d seed %d nb %d  %s" % (P, F, L, seed, nb, h), flush=True)
+# (not 0: a many-workgroup window fell back to one workgroup, and the nb 0 lines above say nothing about that shape)
+print("GL_COUNTER_BA_COOP_FALLBACK %d" % ctx.counter_read(3), flush=True)

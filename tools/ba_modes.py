@@ -1,6 +1,6 @@
 """Persistent kernel (bagen_mode 1) against the pipelined shape (2) of gl_joint_optimization over window sizes and small batches (ms per call):
    python tools/ba_modes.py"""
-import os, sys, time
+import functools, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, gmmloc_amd
 from gmmloc_amd import api
@@ -13,9 +13,14 @@ ctx = gmmloc_amd.Context(0); g = gmmloc_amd.GMM(ctx, mean, cov, prm)
 T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
+@functools.lru_cache(maxsize=None)
+def problem(P, F, L):
+    return make_ba_problem(mean, cov, gt, cam, P, F, L, 100)
+
+
 def timed(P, F, L, B, mode, reps=4):
     ctx.set_option("bagen_mode", mode)
-    p = make_ba_problem(mean, cov, gt, cam, P, F, L, 100)
+    p = problem(P, F, L)
     idx, d2 = g.associate3d(T(p["points"]))
     assoc = torch.where(d2 <= 9.0, idx, torch.full_like(idx, -1)).reshape(1, L).repeat(B, 1).contiguous()
     rep = lambda a: T(np.repeat(a[None], B, 0))

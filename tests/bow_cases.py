@@ -150,6 +150,12 @@ _INTER = voc([0, 0, 1, 2, 1, 2], [bits(0), bits(1), bits(0, 2), bits(1, 2), bits
 CASES["interleaved_ids"] = case(_INTER, [bits(1, 3), bits(0, 2), bits(0, 3), bits(1, 2), bits(0, 3)], levelsup=0, word_id=[3, 0, 2, 1, 2],
                                 node=[6, 3, 5, 4, 5], weight=[4, 1, 3, 2, 3], fv=[(3, [1]), (4, [3]), (5, [2, 4]), (6, [0])])
 
+# ---- the last record of the file is the unique nearest child, at distance 0.  The reference's loader reads one record too many and
+# appends a copy of the last record to its parent as a further child and word (the phantom, declared deviation 1): it stands behind the
+# last child at the same distance, and only the strict `d < best_d` keeps it out - word 4, not the phantom's word 5.  The last record
+# under an inner node: node 14 of _DEEP, feature 0 of levelsup_0 ------------------------------------------------------------------------
+CASES["last_record_nearest"] = case(flat(5), [bits(*range(28, 35)), near(4, 4), near(3, 4)], expect_child=[4, 4, 3])
+
 # ---- padding slots (oct < 0) at both ends: no feature, -1 / -1 / 0 -----------------------------------------------------------------------
 CASES["padding_both_ends"] = case(flat(3), [near(0, 0), near(2, 2), near(1, 1), near(2, 2), near(0, 0)], oct=[-1, 0, 3, 7, -1],
                                   word_id=[-1, 2, 1, 2, -1], node=[-1, 3, 2, 3, -1], weight=[0, 1, 1, 1, 0], fv=[(2, [2]), (3, [1, 3])])

@@ -79,8 +79,8 @@ class Tree:
     def distance(self, feature, nid):
         return int(POPCOUNT[feature ^ self.desc[nid]].sum())
 
-    def transform_feature(self, feature, levelsup):
-        """:1241-1283 -> (word_id, weight, nid)"""
+    def descend(self, feature, levelsup):
+        """:1241-1278 -> (final_id, nid); nid None where the reference's *nid is never written"""
         nid_level = self.L - levelsup
         nid = 0 if nid_level <= 0 else None
         final_id = 0
@@ -99,6 +99,11 @@ class Tree:
                 nid = final_id
             if len(self.children(final_id)) == 0:  # isLeaf()
                 break
+        return final_id, nid
+
+    def transform_feature(self, feature, levelsup):
+        """:1241-1283 -> (word_id, weight, nid)"""
+        final_id, nid = self.descend(feature, levelsup)
         if nid is None:  # DECLARED: the reference leaves *nid unwritten; here the shallow leaf is its own node
             nid = final_id
         return int(self.word_id[final_id]), self.weight[final_id], nid

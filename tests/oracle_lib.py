@@ -323,7 +323,85 @@ class Oracle:
         return idx, dist, cnt
 
 
+class DBoW2Ref:
+    """The reference's own DBoW2 (oracle/dbow2_ref.cpp -> oracle/_ref/libdbow2_ref.so): thin methods over the dbref_ interface."""
+    NID_UNSET = 0xFFFFFFFF  # what `nid` holds where the per-feature transform left it unwritten
+
+    def __init__(self, lib):
+        self.lib = lib
+        lib.dbref_load.restype = C.c_void_p
+        lib.dbref_load.argtypes = [C.c_char_p]
+        lib.dbref_destroy.argtypes = [C.c_void_p]
+        lib.dbref_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.dbref_nodes.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int]
+        lib.dbref_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+        lib.dbref_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
+        lib.dbref_distance.argtypes = [C.c_void_p, C.c_void_p]
+
+    def load(self, path):
+        """loadFromBinaryFile on a well-formed file -> handle"""
+        h = self.lib.dbref_load(str(path).encode())
+        assert h, "the wrapper refused %s (not a well-formed vocabulary file)" % path
+        return C.c_void_p(h)
+
+    def destroy(self, h):
+        self.lib.dbref_destroy(h)
+
+    def info(self, h):
+        v = np.zeros(4, np.int32)
+        self.lib.dbref_info(h, _p(v))
+        return dict(nodes=int(v[0]), words=int(v[1]), k=int(v[2]), L=int(v[3]))
+
+    def nodes(self, h):
+        """per node id (root and phantom included): parent, desc, weight (float32, the file's bits), word_id (-1: no word),
+        children as child_ptr / child_ids in stored order"""
+        n = self.info(h)["nodes"]
+        out = dict(parent=np.zeros(n, np.int32), desc=np.zeros((n, 32), np.uint8), weight=np.zeros(n, np.uint32), word_id=np.zeros(n, np.int32),
+                   child_ptr=np.zeros(n + 1, np.int32), child_ids=np.zeros(n, np.int32))
+        total = self.lib.dbref_nodes(h, _p(out["parent"]), _p(out["desc"]), _p(out["weight"]), _p(out["word_id"]), _p(out["child_ptr"]),
+                                     _p(out["child_ids"]), n)
+        assert total == n - 1, (total, n)  # every node but the root is somebody's child
+        out["child_ids"] = out["child_ids"][:total].copy()
+        out["weight"] = out["weight"].view(np.float32)
+        return out
+
+    def transform(self, h, desc, levelsup):
+        """the per-feature transform -> word (n,) i32, weight (n,) f32, nid (n,) u32 (NID_UNSET: left unwritten), final node (n,) i32"""
+        desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        n = len(desc)
+        word, wbits, nid, final = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.int32)
+        self.lib.dbref_transform(h, _p(desc), n, int(levelsup), _p(word), _p(wbits), _p(nid), _p(final))
+        return word, wbits.view(np.float32), nid, final
+
+    def frame(self, h, desc, levelsup):
+        """-> (fv by addFeature on the per-feature results, fv of the vector overload or None where it was not run, features whose
+        nid was left unwritten); a feature vector is [(node id, [feature indices])] in map order"""
+        desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        n = len(desc)
+        arrs = [[np.zeros(1, np.int32), np.zeros(max(n, 1), np.int32), np.zeros(n + 1, np.int32), np.zeros(max(n, 1), np.int32)] for _ in range(2)]
+        unwritten = self.lib.dbref_frame(h, _p(desc), n, int(levelsup), *[_p(a) for a in arrs[0] + arrs[1]])
+        fvs = []
+        for nn, nid, ptr, idx in arrs:
+            fvs.append(None if nn[0] < 0 else [(int(nid[r]), idx[ptr[r]:ptr[r + 1]].tolist()) for r in range(int(nn[0]))])
+        return fvs[0], fvs[1], int(unwritten)
+
+    def distance(self, a, b):
+        a, b = np.ascontiguousarray(a, dtype=np.uint8), np.ascontiguousarray(b, dtype=np.uint8)
+        assert a.size == 32 and b.size == 32
+        return int(self.lib.dbref_distance(_p(a), _p(b)))
+
+
 _cached = None
+_dbow2 = False
+
+
+def load_dbow2():
+    """DBoW2Ref, or None where oracle/_ref/libdbow2_ref.so was not built (no reference tree)"""
+    global _dbow2
+    if _dbow2 is False:
+        so = os.path.join(ODIR, "_ref", "libdbow2_ref.so")
+        _dbow2 = DBoW2Ref(C.CDLL(so)) if os.path.exists(so) else None
+    return _dbow2
 
 
 def build():

@@ -89,7 +89,31 @@ class gl_temporal_points_in(C.Structure):
 
 
 class gl_temporal_points_out(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("temp_flag", "n_temp", "last_pt", "last_observed", "last_valid", "last_desc", "stats")]
+    _fields_ = [(k, C.c_void_p) for k in ("temp_flag", "n_temp", "last_pt", "last_observed", "last_valid", "last_desc", "stats", "last_mp")]
+
+
+class gl_frame_end_in(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("feat_mp", "match_last", "match_local", "match_kf", "outlier", "local_mp", "n_local_mp", "counts2", "ref_kf",
+                                          "last_observed", "feat_depth")]
+
+
+class gl_kf_rule(C.Structure):
+    _fields_ = [("num_kfs", C.c_int32), ("frame_idx", C.c_int32), ("kf_frame_idx", C.c_int32), ("fps", C.c_float), ("is_idle", C.c_int32),
+                ("n_queue", C.c_int32)]
+
+
+class gl_frame_end_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("held_mp", "held", "stat", "ratio_map")]
+
+
+class gl_frame_next_in(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("pose_tracked", "pose_prev", "ref_kf", "feat_new", "mp_replaced")] +
+                [("mp_base", C.c_int32), ("NMPcap", C.c_int32)])
+
+
+class gl_frame_next_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("t_rc", "t_cr", "pose_lw", "pose_cw", "held_mp", "last_pt", "last_valid", "last_observed", "held", "status",
+                                          "last_desc")]
 
 
 class gl_map_kf_tables(C.Structure):
@@ -195,6 +219,9 @@ def load():
         "gl_map_cand_append": (i32, [vp, vp, vp, i32, i32, vp, vp]),
         "gl_map_stats_merge": (i32, [vp, i32, vp, vp, vp, i32, vp]),
         "gl_cull_map_points": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+        "gl_track_frame_end": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, C.c_float, vp, vp]),
+        "gl_map_note_replaced": (i32, [vp, i32, vp, vp, vp, i32, vp]),
+        "gl_track_frame_next": (i32, [vp, vp, vp, i32, i32, vp, vp]),
         "gl_search_local_points": (i32, [vp, vp, C.c_float, i32, i32, i32] + [vp] * 13 + [C.c_float, C.c_float, vp, vp, vp]),
         "gl_gather_triangulation_matches": (i32, [vp, i32, i32, i32, i32, i32] + [vp] * 32),
         "gl_optimize_point": (i32, [vp, vp, P(gl_camera), P(gl_params), i32] + [vp] * 10),

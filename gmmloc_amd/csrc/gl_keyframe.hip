@@ -206,7 +206,7 @@ __global__ __launch_bounds__(WALK_T) void k_temporal_walk(UnK k, int NF, float t
                                                           uint8_t* __restrict__ temp_flag, int32_t* __restrict__ n_temp,
                                                           double* __restrict__ last_pt, uint8_t* __restrict__ last_observed,
                                                           uint8_t* __restrict__ last_valid, uint8_t* __restrict__ last_desc,
-                                                          int32_t* __restrict__ stats) {
+                                                          int32_t* __restrict__ stats, int32_t* __restrict__ last_mp) {
   __shared__ WalkShared s;
   const int b = blockIdx.x, tid = threadIdx.x;
   const size_t f0 = (size_t)b * NF;
@@ -234,6 +234,7 @@ __global__ __launch_bounds__(WALK_T) void k_temporal_walk(UnK k, int NF, float t
     last_valid[g] = last_outlier[g] ? 0 : 1;  // orb_matcher.cpp:432 reads the slot's is_outlier_, which nothing has cleared
     for (int c = 0; c < 32; ++c) last_desc[g * 32 + c] = feat_desc[g * 32 + c];
     temp_flag[g] = 1;
+    if (last_mp) last_mp[g] = -1;  // mappoints_[i] is the temporal point now (:453): no row
     ++made;
   }
   u64 total;
@@ -311,7 +312,7 @@ int gl_create_temporal_points(gl_ctx_t* ctx, const gl_camera* cam, int B, int NF
   GL_HIP(hipSetDevice(c->device));
   k_temporal_walk<<<B, WALK_T, 0, c->stream>>>(make_unk(cam), NF, th_depth, in->pose, in->feat_uv, in->feat_depth, in->feat_oct, in->held,
                                                in->last_outlier, in->feat_desc, out->temp_flag, out->n_temp, out->last_pt,
-                                               out->last_observed, out->last_valid, out->last_desc, out->stats);
+                                               out->last_observed, out->last_valid, out->last_desc, out->stats, out->last_mp);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

@@ -60,12 +60,13 @@ def create_stereo_points(ctx, gmm, cam, prm, kf, mp_base, check_depth, th_depth,
     return r
 
 
-def create_temporal_points(ctx, cam, fr, last, th_depth):
+def create_temporal_points(ctx, cam, fr, last, th_depth, last_mp=None):
     """gl_create_temporal_points: Tracking::createTemporalPoints (tracking.cpp:411-465) for B last frames (rules: gmmloc_hip.h).  fr:
     dict of CUDA tensors pose (B,7) f64, feat_uv (B,NF,2) f64, feat_depth (B,NF) f32, feat_oct (B,NF) i32, held (B,NF) u8,
     last_outlier (B,NF) u8, feat_desc (B,NF,32) u8; last: the chain's last-frame arrays last_pt (B,NF,3) f64, last_observed /
     last_valid (B,NF) u8, last_desc (B,NF,32) u8, written IN PLACE for the created points.  -> dict(temp_flag (B,NF) u8, n_temp (B,)
-    i32, stats (B,8) i32).  Nothing is read back."""
+    i32, stats (B,8) i32).  last_mp (B,NF) i32 or None: the slots' map rows (frame_step.frame_next's held_mp), set to -1 IN PLACE for the
+    created points.  Nothing is read back."""
     import torch
     for key in fr:
         assert key in TEMPORAL_IN_DTYPES, "fr[%r]: unknown key" % key
@@ -83,6 +84,8 @@ def create_temporal_points(ctx, cam, fr, last, th_depth):
              stats=torch.zeros((B, 8), dtype=torch.int32, device=dev))
     for key, t in r.items():
         setattr(o, key, _ptr(t))
+    if last_mp is not None:
+        o.last_mp = _ptr(_tensor("last_mp", last_mp, "int32", (B, NF), dev))
     ctx._enter()
     try:
         _check(ctx.lib.gl_create_temporal_points(ctx.h, C.byref(cam.c()), B, NF, C.byref(i), float(th_depth), C.byref(o)))

@@ -918,8 +918,8 @@ int gl_map_remove(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, const gl_m
  * NOBS grows only by the attaches, so the capacity is checked BEFORE anything runs: OBScap >= NOBS + n_cand, else result[0] =
  * NOBS + n_cand with GL_MAP_GROW_OBS_TRUNCATED and nothing else is written.  That figure is an UPPER BOUND, not the size the edit
  * produces: a list of which few candidates attach, or whose replaces drop entries, is refused all the same below it.
- * What stays with the host, from repl_src / repl_tgt: ptr_replaced_, mappoints_.erase (num_visible_ / num_found_, :142-143, are
- * gl_map_stats_merge's on the same two lists), and
+ * What stays with the host, from repl_src / repl_tgt: mappoints_.erase (num_visible_ / num_found_, :142-143, are gl_map_stats_merge's on
+ * the same two lists, ptr_replaced_, :126, is gl_map_note_replaced's), and
  * computeDistinctiveDescriptors of tgt (:144) - gl_update_map_points on the resident arrays before the next key-frame's search.
  * The steps depend on one another through slots, counts and gained entries, so ONE workgroup walks the list; inside a step it works in
  * parallel over src's and tgt's entries.  The walk never edits the CSR: its state (a word per point, a chain of gained entries per
@@ -1397,7 +1397,9 @@ int gl_create_stereo_points(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera*
  *       of gl_track_frame_chain's last-frame arrays: last_pt = the unprojected point, last_observed = 0, last_valid = !last_outlier
  *       (clearTemporalPoints leaves a null slot's is_outlier_ alone and orb_matcher.cpp:432 reads it), last_desc = feat_desc.  The rows
  *       of held == 1 slots and of slots that are not walked keep their bytes; a walked held == 2 slot is replaced (:453).
- *       stats B x 8 or NULL: {entries, walked, n_temp, 0, num_pts, broke, 0, 0}. */
+ *       stats B x 8 or NULL: {entries, walked, n_temp, 0, num_pts, broke, 0, 0}.
+ *       last_mp B x NF int32 or NULL, IN PLACE: -1 for the created points - the slot's mappoints_[i] is the temporal point now (:453),
+ *       which has no row; the other entries keep their bytes.  gl_track_frame_next's held_mp is passed here. */
 typedef struct gl_temporal_points_in {
   const double* pose;
   const double* feat_uv;
@@ -1415,9 +1417,156 @@ typedef struct gl_temporal_points_out {
   uint8_t* last_valid;
   uint8_t* last_desc;
   int32_t* stats;
+  int32_t* last_mp;
 } gl_temporal_points_out;
 int gl_create_temporal_points(gl_ctx_t* ctx, const gl_camera* cam, int B, int NF, const gl_temporal_points_in* in, float th_depth,
                               const gl_temporal_points_out* out);
+
+/* ---- frame end and hand-over: from one tracked frame to the next on the device ------------------ */
+/* What the reference does between two calls of gl_track_frame_chain_map - the tail of Tracking::track, GMMLoc::needNewKeyFrame,
+ * Map::updateFrameInfo, the pose block of GMMLoc::processFrame, Tracking::updateLastFrame - as three calls on the chain's own outputs
+ * and the resident map.  All three: one workgroup per frame (gl_map_note_replaced: one workgroup), asynchronous on the context's
+ * stream, stateless, no scratch; the counts are integer reductions, so the bytes do not depend on scheduling; MALFORMED input is
+ * skipped as in gl_update_local_map / gl_map_stats_track (a row outside its table holds nothing and counts nothing), nothing is read
+ * or written out of bounds; NF is bounded as in the chain (3 072).
+ *
+ * gl_track_frame_end: tracking.cpp:85-116 and gmmloc.cpp:324-364 for B frames.  Device pointers, the arrays gl_track_frame_chain_map
+ * left: feat_mp / match_last / match_local B x NF int32, match_kf B x NF (NULL without the fallback), outlier B x NF uint8, local_mp
+ * B x NPcap, n_local_mp B, counts2 B x 4 (NULL: every frame tracked by the motion model), ref_kf B (of gl_local_map_io; read with a
+ * rule only), last_observed B x NL uint8 (NULL = all observed), feat_depth B x NF float.  `map` + `ba`: the resident map (obs_ptr,
+ * kf_mp, mp_valid; kf_uvr and obs_feat for the weights).
+ *   what a feature holds after searchLocalPoints: the row r = local_mp[match_local[i]] when match_local[i] is in [0, min(n_local_mp,
+ *       NPcap)), else feat_mp[i] (a point the chain un-held as invalid has left all three).  r outside [0, NMP): no row.  A feature
+ *       without a row and with match_last[i] >= 0 whose last-frame slot has last_observed == 0 holds a TEMPORAL point: no row,
+ *       countObservations() == 0.  countObservations() of a row is the WEIGHTED COUNT of gl_cull_keyframes; every `> 0` / `< 1` test
+ *       below reads it as "the CSR range of the row is not empty" (an observation weighs at least 1).
+ *   trackLocalMap (:279-292)       a held point with outlier[i] becomes null, is_outlier_ keeps its value; num_match_inliers = the
+ *                                  held non-outlier features whose point has observations.
+ *   the statistics (:88-102)       taken after that: num_total = the features with depth > 0 && depth < th_depth as float compares (NaN,
+ *                                  +-0: out); num_map = those of them that still hold a point with observations; ratio_map =
+ *                                  (float)num_map / (float)max(1, num_total), one IEEE division.
+ *   clearTemporalPoints (:379-388) a held point without observations becomes null - a temporal point, and a row whose CSR range is
+ *   and :107-111                   empty.  Its `is_outlier_ = false` can only meet a slot that is false already (the outlier ones
+ *                                  were nulled by trackLocalMap), and :107-111 finds no held outlier any more: the frame's final
+ *                                  is_outlier_ IS the chain's `outlier`, byte for byte.  No array is written for it;
+ *                                  gl_create_temporal_points takes `outlier` as last_outlier.
+ *   Hence a temporal point leaves no trace in any output: held or not, its slot ends null, uncounted, with the flag the chain gave
+ *   it.  match_last, match_kf, last_observed and NL are part of the call for that statement (tests/frame_step_ref.py carries the
+ *   temporal points and is_outlier_ through every statement); the kernel has no use for them, and all three pointers may be NULL.
+ *   a lost frame (counts2[3] == 2, :65-71)  stat = {0, 10, 0, 0, 0, 0, 0, 0} and NO other output of that frame is written (the
+ *                                  reference returns before last_frame_ advances: the rows of frame t - 1 stay the last frame's).
+ *   QUIRK, reproduced: after a successful trackKeyFrame (counts2[3] == 1) stat_.res is still false - :55 cleared it, nothing sets it
+ *   again.  res = (mode == 0).  A host that goes on after the fallback decides on counts2[3], not on res.
+ *   needNewKeyFrame (with `rule` only; without: num_ref_matches = verdict = 0), gmmloc.cpp:327-361 in the reference's types:
+ *       num_ref_matches = KeyFrame::countMapPoints(num_kfs <= 2 ? 2 : 3) of key-frame row ref_kf[b] (keyframe.cpp:212-231): the slots
+ *                         of kf_mp[ref_kf] that hold a row of [0, NMP) which is valid in mp_valid and whose weighted count reaches
+ *                         the threshold; a ref_kf outside [0, NKF): 0
+ *       c1a = (float)frame_idx >= (float)kf_frame_idx + fps
+ *       c1b = (float)num_match_inliers < (float)num_ref_matches * 0.25f || ratio_map < 0.3f
+ *       c2  = ((float)num_match_inliers < (float)num_ref_matches * (num_kfs < 2 ? 0.4f : 0.75f) ||
+ *              ratio_map < (num_match_inliers > 300 ? 0.2f : 0.35f)) && num_match_inliers > 15
+ *       (c1a || c1b || is_idle) && c2 (:349): idle -> GL_KF_NEED; else GL_KF_INTERRUPT_BA (interruptBA() would have been called), and
+ *       GL_KF_NEED with it when n_queue < 3 (:357).
+ *  out: held_mp B x NF int32 - the final mappoints_ as map rows, -1 none: the next frame's last_mp, and a new key-frame's kf_mp row
+ *       as KeyFrame(*frame) copies it; held B x NF uint8 - 0 / 1, the flags of gl_create_stereo_points (no held point is temporal
+ *       any more); stat B x 8 int32 = {res, num_match_inliers, num_map, num_total, num_ref_matches, verdict, 0, 0}; ratio_map B float. */
+#define GL_KF_NEED 1
+#define GL_KF_INTERRUPT_BA 2
+typedef struct gl_frame_end_in {
+  const int32_t* feat_mp;
+  const int32_t* match_last;
+  const int32_t* match_local;
+  const int32_t* match_kf;
+  const uint8_t* outlier;
+  const int32_t* local_mp;
+  const int32_t* n_local_mp;
+  const int32_t* counts2;
+  const int32_t* ref_kf;
+  const uint8_t* last_observed;
+  const float* feat_depth;
+} gl_frame_end_in;
+typedef struct gl_kf_rule { /* host scalars, valid for the whole call */
+  int32_t num_kfs;      /* map_->countKeyFrames() */
+  int32_t frame_idx;    /* curr_frame_->idx_ */
+  int32_t kf_frame_idx; /* curr_keyframe_->frame_idx_ */
+  float fps;            /* camera::fps */
+  int32_t is_idle;      /* localizer_->is_idle_ */
+  int32_t n_queue;      /* localizer_->countKFsInQueue() */
+} gl_kf_rule;
+typedef struct gl_frame_end_out {
+  int32_t* held_mp;
+  uint8_t* held;
+  int32_t* stat;
+  float* ratio_map;
+} gl_frame_end_out;
+int gl_track_frame_end(gl_ctx_t* ctx, const gl_map_view* map, const gl_map_ba_view* ba, int B, int NF, int NL, int NPcap,
+                       const gl_frame_end_in* in, float th_depth, const gl_kf_rule* rule, const gl_frame_end_out* out);
+
+/* MapPoint::ptr_replaced_ as a device array: mp_replaced NMPcap int32, caller-owned, -1 = none.  repl_src / repl_tgt of gl_map_fuse,
+ * n steps (or *n_dev clamped to [0, n], as in gl_map_stats_merge): mp_replaced[src] = tgt with the result of the sequential loop IN
+ * STEP ORDER (map.cpp:126: a later step on the same src wins).  A step with src == tgt (:113) or with a row outside [0, NMPcap)
+ * changes nothing.  Enqueued beside gl_map_stats_merge.  One workgroup; per 1 024 steps a step stores unless a later one of the
+ * chunk names the same source. */
+int gl_map_note_replaced(gl_ctx_t* ctx, int NMPcap, int32_t* mp_replaced_dev, const int32_t* repl_src_dev, const int32_t* repl_tgt_dev, int n,
+                         const int32_t* n_dev);
+
+/* gl_track_frame_next: Map::updateFrameInfo (map.cpp:23-38), the pose block of GMMLoc::processFrame (gmmloc.cpp:269-292),
+ * Tracking::updateLastFrame (tracking.cpp:397-408) and the last-frame rows of frame t + 1, for B frames.  Called after the key-frame
+ * pass, if one ran, and before the next chain call: it reads the map as it is NOW (positions after the BA, validity and observations
+ * after the culls).
+ *  in:  pose_tracked B x 7 (frame t's Tcw out of the chain); pose_prev B x 7 (the previous frame's pose as THIS call refreshed it one
+ *       frame earlier - its pose_lw; NULL: no frame before, the data->idx == 1 branch); ref_kf B (the frame's ref_keyframe_ row NOW:
+ *       the new key-frame's row after processKeyFrame, gmmloc_opt.cpp:27); held_mp B x NF in/out; feat_new B x NF + mp_base (of
+ *       gl_create_stereo_points; NULL: no key-frame was made); mp_replaced NMPcap int32 (NULL: nothing was replaced), NMPcap >= NMP;
+ *       of `map` mp_pos, obs_ptr, and of `ba` kf_pose.
+ *  poses (SE3Quat with the normalisation every product does):
+ *       t_rc = Tcw(ref_kf) * inverse(pose_tracked), t_cr = inverse(t_rc)               (map.cpp:29, :33)
+ *       pose_lw = t_cr * Tcw(ref_kf)                                                   (gmmloc.cpp:275)
+ *       pose_cw = pose_lw without pose_prev, else (pose_lw * inverse(pose_prev)) * pose_lw   (:284-290)
+ *       A ref_kf outside [0, NKF) leaves the four poses unwritten: status GL_FRAME_NEXT_BAD_REF.
+ *  rows, in this order:
+ *       held_mp[i] = mp_base + feat_new[i] where feat_new[i] >= 0 (the key-frame's new points, gmmloc_opt.cpp:100; a sum outside
+ *       [0, NMP) changes nothing), -1 where it is -2;
+ *       then ONE step of mp_replaced (tracking.cpp:402-405: no chain is followed, and the row it names may itself be invalid); an
+ *       entry outside [0, NMP) changes nothing.
+ *  then per slot, row = held_mp[i] (outside [0, NMP): none, the entry keeps its value):
+ *       last_pt = mp_pos[row], zeros without a row; last_valid = a row; last_observed = its CSR range is not empty;
+ *       held (of gl_create_temporal_points) = 0 none, 1 observed, 2 a row without observations: a row culled since the frame's end, or
+ *       the row one step of mp_replaced led to when that row was itself replaced or culled (A -> B -> C gives B, which is invalid).
+ *       createTemporalPoints replaces such a slot (:441, :453): held_mp goes to gl_create_temporal_points as out->last_mp, which sets
+ *       the replaced slots to -1, so that the next chain call sees a temporal point there and not a row that holds nothing (a frame
+ *       that became a key-frame makes no temporal points and keeps its rows).
+ *  last_oct / last_angle of frame t + 1 are frame t's own feature buffers: no copy is made, the caller passes them on.  So is
+ *  last_desc for a host that matches against the features' descriptors (out->last_desc NULL: nothing is copied).  The reference
+ *  matches a last-frame slot by its MAP POINT's descriptor (gl_search_by_projection_frame): with out->last_desc B x NF x 32 given, the
+ *  slots with a row get mp_desc[row] (map->mp_desc required), the others keep their bytes - gl_create_temporal_points writes the
+ *  temporal ones.
+ *  out: t_rc, t_cr, pose_lw, pose_cw B x 7; held_mp; last_pt B x NF x 3; last_valid, last_observed, held B x NF uint8; status B. */
+#define GL_FRAME_NEXT_BAD_REF 1
+typedef struct gl_frame_next_in {
+  const double* pose_tracked;
+  const double* pose_prev;
+  const int32_t* ref_kf;
+  const int32_t* feat_new;
+  const int32_t* mp_replaced;
+  int32_t mp_base;
+  int32_t NMPcap;
+} gl_frame_next_in;
+typedef struct gl_frame_next_out {
+  double* t_rc;
+  double* t_cr;
+  double* pose_lw;
+  double* pose_cw;
+  int32_t* held_mp;
+  double* last_pt;
+  uint8_t* last_valid;
+  uint8_t* last_observed;
+  uint8_t* held;
+  int32_t* status;
+  uint8_t* last_desc; /* NULL allowed */
+} gl_frame_next_out;
+int gl_track_frame_next(gl_ctx_t* ctx, const gl_map_view* map, const gl_map_ba_view* ba, int B, int NF, const gl_frame_next_in* in,
+                        const gl_frame_next_out* out);
 
 /* ---- pose refinement ------------------------------------------------------ */
 /* Tracking::optimizeCurrentPose (tracking_opt.cpp:21-217) for B frames.

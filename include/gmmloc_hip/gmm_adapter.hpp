@@ -21,6 +21,9 @@
 //   Localization::removeMapPoints                   (localization.cpp:127-152) with num_visible_ / num_found_ / ref_idx_ and
 //                                                   candidate_mappts_ kept on the device (setResidentMapStats, trackStats, growStats,
 //                                                   mergeStats, removeMapPointsInMap)
+//   the tail of Tracking::track, GMMLoc::needNewKeyFrame, Map::updateFrameInfo, the pose block of GMMLoc::processFrame,
+//   Tracking::updateLastFrame                       (tracking.cpp:85-116, gmmloc.cpp:324-364, map.cpp:23-38, gmmloc.cpp:269-292,
+//                                                   tracking.cpp:397-408: endFrame, noteReplaced, nextFrame on the resident map)
 //   north-star per-frame path: associate + structure-constrained refinement of one frame (trackFrame)
 // Host buffers in, host buffers out: each call stages through device memory owned by the
 // adapter (gl_malloc / gl_memcpy_*), so the host code never sees a HIP type.
@@ -50,6 +53,8 @@ namespace gmmloc_hip {
 //    setResidentMapStats / trackStats / growStats / mergeStats / removeMapPointsInMap likewise: a host that mirrored the counters keeps
 //    working, one that calls these drops its mirror and the copies back of inview, feat_mp, match_local, outlier and repl_src / repl_tgt
 //    loadVocabulary / bowTransform / bowTransformIntoTables likewise: a host that runs its own DBoW2 and uploads feat_vec_ keeps working
+//    endFrame / noteReplaced / nextFrame likewise: a host that builds mappoints_ and the next frame's rows from the chain's copies back
+//    keeps working, one that calls these drops the loop and the copies
 constexpr int kAdapterVersion = 5;
 
 inline void check(int rc, const char* what) {
@@ -901,6 +906,34 @@ class GMM {
     if (got[6]) check(gl_memcpy_d2h(ctx_, r.remove.dead_mp.data(), d_dead, (size_t)got[6] * 4), "d2h");
     map_.NOBS = r.remove.nobs;
     return r;
+  }
+  // ---- frame end and hand-over on the device (gl_track_frame_end / gl_map_note_replaced / gl_track_frame_next, gmmloc_hip.h): the loop
+  // over the features that followed a tracked frame - mappoints_, the next frame's last-frame rows, the held flags, the refreshed pose
+  // and the motion-model prediction, TrackStat and needNewKeyFrame - on the chain's own device outputs and the resident map.  Device
+  // pointers in and out, enqueued only: a run of non-key frames reads back stat (8 int32 per frame) and nothing else.
+  // endFrame: the tail of Tracking::track (tracking.cpp:85-116) and, with a rule, GMMLoc::needNewKeyFrame (gmmloc.cpp:324-364).
+  void endFrame(int B, int NF, int NL, int NPcap, const gl_frame_end_in& in, float th_depth, const gl_kf_rule* rule, const gl_frame_end_out& out) {
+    check(gl_track_frame_end(ctx_, &map_, &map_ba_, B, NF, NL, NPcap, &in, th_depth, rule, &out), "gl_track_frame_end");
+  }
+  // noteReplaced: FuseResult::repl_src / repl_tgt in step order into ptr_replaced_ as the device array mp_replaced (the rows of
+  // setResidentMapCapacity, -1 = none; map.cpp:126).  Called beside mergeStats; the lists are copied before the call returns.
+  void noteReplaced(int32_t* mp_replaced_dev, const std::vector<int32_t>& repl_src, const std::vector<int32_t>& repl_tgt) {
+    const size_t n = repl_src.size();
+    if (repl_tgt.size() != n) throw std::runtime_error("noteReplaced: lists of different lengths");
+    if (!n) return;
+    int32_t* d = pooled(14, 2 * n * 4).as<int32_t>();
+    check(gl_memcpy_h2d(ctx_, d, repl_src.data(), n * 4), "h2d");
+    check(gl_memcpy_h2d(ctx_, d + n, repl_tgt.data(), n * 4), "h2d");
+    check(gl_map_note_replaced(ctx_, mp_cap_, mp_replaced_dev, d, d + n, (int)n, nullptr), "gl_map_note_replaced");
+  }
+  // nextFrame: Map::updateFrameInfo, the pose block of GMMLoc::processFrame, Tracking::updateLastFrame and the last-frame rows of the
+  // next chain call, on the resident map as it is NOW (after the key-frame pass, if one ran).  in.mp_replaced, when given, has the rows
+  // of setResidentMapCapacity (in.NMPcap is set here).  For a frame that is no key-frame gl_create_temporal_points follows on the rows
+  // written here, with out.held_mp as its out->last_mp: a held == 2 slot it replaces gets -1 there (createTemporalPoints above works on
+  // host vectors: its caller sets last_mp = -1 where the returned flag is set).
+  void nextFrame(int B, int NF, gl_frame_next_in in, const gl_frame_next_out& out) {
+    in.NMPcap = mp_cap_;
+    check(gl_track_frame_next(ctx_, &map_, &map_ba_, B, NF, &in, &out), "gl_track_frame_next");
   }
   const gl_map_view& residentMap() const { return map_; }
 

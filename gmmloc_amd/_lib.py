@@ -75,6 +75,10 @@ class gl_map_stats(C.Structure):
                 [("cand_cap", C.c_int32), ("reserved_", C.c_int32)])
 
 
+class gl_map_covis(C.Structure):
+    _fields_ = [("NKFcap", C.c_int32), ("Wcap", C.c_int32)] + [(k, C.c_void_p) for k in ("cov_kf", "cov_w", "cov_n", "cov_nord", "best_cov")]
+
+
 class gl_stereo_points_in(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("pose", "feat_uv", "feat_ur", "feat_depth", "feat_oct", "cand", "ncand", "held", "kf_row")]
 
@@ -219,6 +223,11 @@ def load():
         "gl_map_cand_append": (i32, [vp, vp, vp, i32, i32, vp, vp]),
         "gl_map_stats_merge": (i32, [vp, i32, vp, vp, vp, i32, vp]),
         "gl_cull_map_points": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+        "gl_covis_update": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "gl_covis_remove": (i32, [vp, i32, vp, i32, vp, vp, i32, vp]),
+        "gl_covis_best": (i32, [vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+        "gl_fuse_targets": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "gl_fuse_candidates": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "gl_track_frame_end": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, C.c_float, vp, vp]),
         "gl_map_note_replaced": (i32, [vp, i32, vp, vp, vp, i32, vp]),
         "gl_track_frame_next": (i32, [vp, vp, vp, i32, i32, vp, vp]),

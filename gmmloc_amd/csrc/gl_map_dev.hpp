@@ -197,6 +197,96 @@ struct Words {
 // the row of a key count << 32 | (0x7fffffff - row): the largest count, then the lowest row
 __device__ __forceinline__ int best_row(u64 best) { return 0x7fffffff - (int)(unsigned)(best & 0xffffffffull); }
 
+// ---- KeyFrame::updateConnections' counter and its order (gl_ba_window.hip: gl_update_connections, gl_ba_window_build; gl_covis.hip:
+// gl_covis_update).  One workgroup of T_CONN threads per key-frame.
+constexpr int T_CONN = 1024;
+constexpr int CONN_TH = 15;  // keyframe.cpp:280
+// (a) + (b) of the connections: on return the counters hold map_frame_weights_, n15 = the observers that reach the threshold and
+// best = count << 32 | (0x7fffffff - row) of the largest count at the lowest row (0: empty counter).  The counters are zero on entry.
+template <bool LDS>
+__device__ __forceinline__ void conn_count(const Map& m, int kf, Words<LDS> cnt, int tid, int* s_w, u64* s_b, int* n15, u64* best) {
+  const int32_t* row = m.kf_mp + (size_t)kf * m.NFK;
+  for (int j = tid; j < m.NFK; j += T_CONN) {
+    const int p = row[j];
+    if (!mp_ok(m, p)) continue;
+    int o0, o1;
+    obs_range(m, p, &o0, &o1);
+    for (int o = o0; o < o1; ++o) {
+      const int k = m.obs_kf[o];
+      if (!kf_row(m, k) || k == kf) continue;  // (:268-269)
+      cnt.add(k);
+    }
+  }
+  if constexpr (!LDS) __threadfence();
+  __syncthreads();
+  const int ck = (m.NKF + T_CONN - 1) / T_CONN;
+  const int k0 = min(tid * ck, m.NKF), k1 = min(k0 + ck, m.NKF);
+  int n = 0, tot;
+  u64 b = 0ull;
+  for (int k = k0; k < k1; ++k) {
+    const int c = cnt.get(k);
+    if (c <= 0) continue;
+    n += c >= CONN_TH;
+    const u64 key = ((u64)(unsigned)c << 32) | (unsigned)(0x7fffffff - k);
+    b = key > b ? key : b;
+  }
+  block_excl_scan<T_CONN>(n, s_w, tid, &tot);
+  *n15 = tot;
+  *best = block_max<T_CONN>(b, s_b, tid);
+}
+// is key-frame k (count c) in ordered_keyframes_ (:287-300)
+__device__ __forceinline__ bool conn_keep(int k, int c, int n15, int best_row) { return n15 > 0 ? c >= CONN_TH : k == best_row; }
+// the order of ordered_keyframes_ as a key, smaller first: weight descending, then the lowest row (never 0)
+__device__ __forceinline__ u64 conn_key(int k, int c) { return (((u64)(unsigned)(0x7fffffff - c) << 32) | (unsigned)k) + 1ull; }
+
+// The place of every SELECTED key-frame among the selected ones, by key: sel(k) = its key (distinct, non-zero) or 0, out(k, rank).
+// A contiguous run of key-frames per thread; the selected ones are compacted into LDS (RANK_LDS of them: a covisible list or a set of
+// fixed key-frames is tens of rows) and each counts the keys below its own; a larger selection counts over the whole table instead.
+// Returns their number.  Ends with a fence and a barrier.
+constexpr int RANK_LDS = 1024;
+struct RankLds {
+  u64 key[RANK_LDS];
+  int row[RANK_LDS];
+};
+template <class Sel, class Out>
+__device__ __forceinline__ int rank_selected(int NKF, int tid, int* s_w, RankLds& s, Sel sel, Out out) {
+  const int ck = (NKF + T_CONN - 1) / T_CONN;
+  const int k0 = min(tid * ck, NKF), k1 = min(k0 + ck, NKF);
+  int n = 0;
+  for (int k = k0; k < k1; ++k) n += sel(k) != 0ull;
+  int total;
+  int at = block_excl_scan<T_CONN>(n, s_w, tid, &total);
+  if (total <= RANK_LDS) {
+    for (int k = k0; k < k1 && n > 0; ++k) {
+      const u64 key = sel(k);
+      if (!key) continue;
+      s.key[at] = key;
+      s.row[at++] = k;
+    }
+    __syncthreads();
+    for (int i = tid; i < total; i += T_CONN) {
+      const u64 key = s.key[i];
+      int r = 0;
+      for (int i2 = 0; i2 < total; ++i2) r += s.key[i2] < key;
+      out(s.row[i], r);
+    }
+  } else {
+    for (int k = k0; k < k1 && n > 0; ++k) {
+      const u64 key = sel(k);
+      if (!key) continue;
+      int r = 0;
+      for (int k2 = 0; k2 < NKF; ++k2) {
+        const u64 key2 = sel(k2);
+        r += key2 != 0ull && key2 < key;
+      }
+      out(k, r);
+    }
+  }
+  __threadfence();
+  __syncthreads();
+  return total;
+}
+
 // ---- the device-wide exclusive scan of the rebuilds of the CSR: SCAN_TILE words per workgroup of SCAN_T threads, then ONE workgroup
 // over the tiles' sums.  A word's place is cnt[i] + tile[i / SCAN_TILE] afterwards.
 constexpr int SCAN_T = 1024, SCAN_PER = 4, SCAN_TILE = SCAN_T * SCAN_PER;

@@ -651,7 +651,8 @@ int gl_track_frame_chain_map(gl_ctx_t* ctx, const gl_camera* cam, const gl_param
  * getVectorCovisibleKeyFrames(); getBestCovisibilityKeyFrames(n) is its first n entries (createMapPoints, searchInNeighbors).
  * DECLARED DEVIATION: the reference breaks ties of weight - and the tie for the single largest - by POINTER value (sort on
  * pair<int, KeyFrame*>; unordered_map order for nmax).  Here ties go to the LOWEST key-frame row first.
- * What stays with the host: addConnection on the OTHER key-frames (:293, :299) - their own lists are the host's bookkeeping.
+ * This call only RECOUNTS the key-frame's own list.  addConnection on the OTHER key-frames (:293, :299), removeConnection and best_cov_kf_
+ * are gl_covis_update / gl_covis_remove on the resident graph (gl_map_covis, below); a host without it keeps that bookkeeping itself.
  * Malformed input is skipped as in gl_update_local_map; a kf_row outside [0, NKF) gives n_conn = 0 and GL_CONN_BAD_ROW.
  * One workgroup per key-frame, integer atomics only; counters in LDS up to 4 096 key-frames, in the context's scratch above. */
 #define GL_CONN_KEPT 1
@@ -1057,6 +1058,94 @@ int gl_map_stats_merge(gl_ctx_t* ctx, int NMP, const gl_map_stats* st, const int
  * the counters are not written. */
 int gl_cull_map_points(gl_ctx_t* ctx, int NMP, int NKF, int NFK, int NOBS, const gl_map_edit* ed, const double* kf_uvr_dev,
                        const gl_map_stats* st, int kf_row, int32_t* rm_mp_dev, int32_t* n_rm_dev, int32_t* verdict_dev, int32_t* result_dev);
+
+/* ---- the covisibility graph as part of the resident map ----
+ * What a key-frame's connection containers hold is STORED STATE, not a function of the observations: the lists its last
+ * updateConnections left, patched by every later addConnection from another key-frame (keyframe.cpp:293, :299, :116-128) and every
+ * removeConnection of a culled one (map.cpp:67-68, keyframe.cpp:318-330).  searchInNeighbors reads those lists of OTHER key-frames
+ * (localization.cpp:170), so the graph is kept on the device, row-indexed like gl_map_view, NKFcap rows:
+ *   cov_kf, cov_w   NKFcap x Wcap int32   map_frame_weights_ of the row in the DECLARED ORDER: weight descending, ties to the lowest
+ *                                         key-frame row first (the tie rule of gl_update_connections)
+ *   cov_n           NKFcap int32          the number of entries
+ *   cov_nord        NKFcap int32          the length of ordered_keyframes_ / ordered_weights_, ALWAYS A PREFIX of the row:
+ *                                           after the row's own updateConnections the entries with w >= 15, or the single largest if
+ *                                           none reaches 15 (:291-300) - in a descending row both are prefixes, and with the tie rule
+ *                                           the single largest is entry 0;
+ *                                           after an addConnection that inserted or changed a weight, or a removeConnection that erased
+ *                                           something, updateBestCovisibles rebuilds the list from the WHOLE weight map, entries below
+ *                                           15 included (:130-150): cov_nord = cov_n.  REPRODUCED, not repaired.
+ *   best_cov        NKFcap int32          best_cov_kf_, -1 = none
+ * A new row starts with cov_n = cov_nord = 0, best_cov = -1.  A reader cuts cov_n to [0, Wcap] and cov_nord to [0, cov_n].
+ * The calls below: caller-owned device arrays, asynchronous on the context's stream, stateless (what a call reads of the context's
+ * scratch it has written itself), integer stores and integer atomics whose final value the inputs determine - no byte depends on
+ * scheduling -, no scratch memory in any kernel.  A row outside its table (an entry of a list, an entry of cov_kf) is skipped and
+ * counted (GL_COVIS_BAD_ROW); nothing is read or written out of bounds.  Every call writes result, 4 int32, [1] = the status bits.
+ * CAPACITY, as in gl_map_add: gl_covis_update first finds the widest row it would produce; above Wcap it writes nothing to the graph,
+ * sets GL_COVIS_W_TRUNCATED and returns the width it needs in result[0] - the host re-strides the tables and calls again.
+ * DECLARED DEVIATIONS, together:
+ *   tie order        the reference sorts pair<int, KeyFrame*> and breaks ties of weight by POINTER; here the lowest row comes first
+ *   target order     the reference iterates an unordered_set<KeyFrame*> (localization.cpp:183, :193); tgt_kf is in INSERTION order.  The
+ *                    order decides results because the fuses are sequential
+ *   empty list       Map::removeKeyFrame indexes ordered_keyframes_[0] of a key-frame whose list is empty (map.cpp:82, undefined);
+ *                    here best_cov stays as it is and GL_COVIS_EMPTY_LIST is set */
+typedef struct gl_map_covis {
+  int32_t NKFcap;
+  int32_t Wcap;
+  int32_t* cov_kf;
+  int32_t* cov_w;
+  int32_t* cov_n;
+  int32_t* cov_nord;
+  int32_t* best_cov;
+} gl_map_covis;
+#define GL_COVIS_W_TRUNCATED 8     /* (beside GL_CONN_KEPT / _TRUNCATED / _BAD_ROW in the same word) */
+#define GL_COVIS_EMPTY_LIST 16
+#define GL_COVIS_BAD_ROW 32
+#define GL_COVIS_LIST_TRUNCATED 64 /* tgt_kf / cand_mp: the true count is above the capacity, the first entries are written */
+/* KeyFrame::updateConnections WITH its side effects (keyframe.cpp:243-316) for ONE key-frame row kf_row of `map`:
+ *   1  the counter of gl_update_connections (its kernel's counting: an invalid observer is counted like any other)
+ *   2  (:275-276) empty counter: nothing changes, status GL_CONN_KEPT, n_conn = 0
+ *   3  (:312) the own row becomes the WHOLE counter in the declared order; cov_nord = the entries >= 15, or 1
+ *   4  (:293, :299) for every observer with a count >= 15 - the single largest if there is none - addConnection(kf_row, w) on THAT row,
+ *      whatever its state (an invalid key-frame's row gains the entry too): absent -> inserted in order; present with another weight
+ *      -> changed and moved; in both cases that row's cov_nord = cov_n.  Present with the same weight -> nothing, cov_nord stays.
+ *   5  conn_kf / conn_w (Ccap int32) / n_conn (1 int32) exactly as gl_update_connections writes them for the row: a drop-in for it at
+ *      processNewKeyFrame (localization.cpp:440) and at the end of searchInNeighbors (:223).
+ * result = {the widest row of the call, status (GL_CONN_* | GL_COVIS_W_TRUNCATED), other rows changed, 0}.  Wcap x 8 bytes of LDS. */
+int gl_covis_update(gl_ctx_t* ctx, const gl_map_view* map, const gl_map_covis* cov, int kf_row, int Ccap, int32_t* conn_kf_dev, int32_t* conn_w_dev,
+                    int32_t* n_conn_dev, int32_t* result_dev);
+/* The graph part of Map::removeKeyFrame (map.cpp:60-87) for the rows cull_rows[0 .. n) IN REMOVAL ORDER, n = *n_cull_dev cut to
+ * [0, cull_cap] (cull_cap when NULL): cull_rows / n_cull of gl_cull_keyframes.  Per listed row r, one after the other:
+ *   (:63)     r == kf_first: skipped
+ *   (:67-68)  every row NAMED IN r's weights loses its entry for r if it has one (removeConnection), and then has cov_nord = cov_n.  A
+ *             row that names r but is not named BY r keeps its dangling entry, as in the reference: readers filter on kf_valid
+ *   (:82-84)  best_cov[r] = entry 0 of r's ordered list (empty: DECLARED above); cov_n[r] = cov_nord[r] = 0.  A row listed twice meets
+ *             the empty list at its second occurrence.
+ * It stands beside gl_map_remove(rm_kf) and touches no observation, so the order of the two does not matter.  The host re-parents
+ * frame_info_ (:89-104) from best_cov.  result = {rows removed, status, entries erased, rows skipped as malformed}. */
+int gl_covis_remove(gl_ctx_t* ctx, int NKF, const gl_map_covis* cov, int kf_first, const int32_t* cull_rows_dev, const int32_t* n_cull_dev,
+                    int cull_cap, int32_t* result_dev);
+/* getBestCovisibilityKeyFrames(N) (keyframe.cpp:163-170; N <= 0: getVectorCovisibleKeyFrames, :152-155) for B rows kf_row: conn_kf /
+ * conn_w B x Ccap int32 = the first min(N, cov_nord) entries, n_conn B int32 their TRUE number (above Ccap: the first Ccap, status
+ * GL_CONN_TRUNCATED) - the lists gl_create_map_points_from_map, gl_cull_keyframes and gl_tri_pair_setup take.  A row outside [0, NKF):
+ * n_conn = 0.  result = {0, status, 0, rows outside the table}. */
+int gl_covis_best(gl_ctx_t* ctx, int NKF, const gl_map_covis* cov, int B, const int32_t* kf_row_dev, int N, int Ccap, int32_t* conn_kf_dev,
+                  int32_t* conn_w_dev, int32_t* n_conn_dev, int32_t* result_dev);
+/* The target key-frames of Localization::searchInNeighbors (localization.cpp:155-179; nn = 10, nn2 = 5 there): for each of the first nn
+ * entries kf1 of kf_row's ordered list - invalid or already a target: skipped, and with it its second neighbours (:162-164) - kf1 is
+ * inserted, then each of the first nn2 entries kf2 of kf1's ordered list that is valid, not yet a target and not kf_row (:172-174).
+ * kf_valid NKF uint8 (NULL: all valid).  tgt_kf Tcap int32 in INSERTION order (declared above), *n_tgt the true count (at most
+ * nn + nn x nn2 <= 4 096; above Tcap: the first Tcap, GL_COVIS_LIST_TRUNCATED).  result = {count, status, 0, entries skipped as malformed}. */
+int gl_fuse_targets(gl_ctx_t* ctx, int NKF, const gl_map_covis* cov, const uint8_t* kf_valid_dev, int kf_row, int nn, int nn2, int Tcap,
+                    int32_t* tgt_kf_dev, int32_t* n_tgt_dev, int32_t* result_dev);
+/* The candidates of the reverse fuse (localization.cpp:188-206): the targets tgt_kf[0 .. n) in list order (n = *n_tgt cut to
+ * [0, Tcap]), each target's kf_mp slots ascending; a non-null valid point is appended at its FIRST occurrence (the fuse_tgt_kf_ stamp).
+ * Validity is the map's when the call runs - after the forward fuses.  kf_idx = curr_kf_->idx_: fuse_tgt_kf_ starts at 0
+ * (mappoint.h:95), so for kf_idx == 0 every point looks stamped and the list is empty - REPRODUCED.  First occurrence is decided by
+ * atomicMin of (target position x NFK + slot) on a word per point in the context's scratch (set by the call), then flags, the
+ * device-wide scan of the CSR rebuilds and a compaction.  cand_mp cand_cap int32, *n_cand the true count (above cand_cap: the first
+ * cand_cap, GL_COVIS_LIST_TRUNCATED).  result = {count, status, 0, targets outside the table}. */
+int gl_fuse_candidates(gl_ctx_t* ctx, const gl_map_view* map, const int32_t* tgt_kf_dev, const int32_t* n_tgt_dev, int Tcap, int kf_idx,
+                       int cand_cap, int32_t* cand_mp_dev, int32_t* n_cand_dev, int32_t* result_dev);
 
 /* Localization::fuseObservations (localization.cpp:226-318), the matching half, for B key-frames: per candidate map point the most
  * similar feature inside Frame::getFeaturesInArea(u, v, th * scale_factors[level]) (frame.cpp:121-177) with octave level - 1 or

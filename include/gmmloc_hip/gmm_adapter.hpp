@@ -937,6 +937,110 @@ class GMM {
   }
   const gl_map_view& residentMap() const { return map_; }
 
+  // ---- the covisibility graph on the device (gl_map_covis, gmmloc_hip.h): map_frame_weights_, ordered_keyframes_ and best_cov_kf_ of
+  // every key-frame as caller-owned device arrays beside the resident map - the host mirrors no connection container, addConnection and
+  // removeConnection included.  setResidentCovisibility: the tables (NKFcap rows of Wcap entries; a new row: cov_n = cov_nord = 0,
+  // best_cov = -1).
+  void setResidentCovisibility(const gl_map_covis& tables, int32_t Wcap) {
+    cov_ = tables;
+    cov_.Wcap = Wcap;
+  }
+  // updateConnectionsInMap: KeyFrame::updateConnections WITH its addConnection on the other rows (keyframe.cpp:243-316) for key-frame
+  // kf_row, at processNewKeyFrame (localization.cpp:440) and at the end of searchInNeighbors (:223).  conn_kf / conn_w: the ordered list
+  // (at most Ccap entries of n_conn).  status & GL_COVIS_W_TRUNCATED: the graph is untouched and `widest` is the Wcap the call needs -
+  // re-stride cov_kf / cov_w, setResidentCovisibility, call again.  One synchronise.
+  struct ConnectionsResult {
+    int32_t n_conn = 0, widest = 0, status = 0, n_changed = 0;
+    std::vector<int32_t> conn_kf, conn_w;
+  };
+  ConnectionsResult updateConnectionsInMap(int32_t kf_row, int32_t Ccap = 256) {
+    const size_t C = (size_t)Ccap;
+    char* b = pooled(15, 64 + 2 * C * 4).as<char>();
+    int32_t* res = reinterpret_cast<int32_t*>(b);  // {result (4) | n_conn}
+    int32_t* d_kf = reinterpret_cast<int32_t*>(b + 64);
+    check(gl_covis_update(ctx_, &map_, &cov_, kf_row, Ccap, d_kf, d_kf + C, res + 4, res), "gl_covis_update");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t got[5];
+    check(gl_memcpy_d2h(ctx_, got, res, 20), "d2h");
+    ConnectionsResult r;
+    r.widest = got[0], r.status = got[1], r.n_changed = got[2], r.n_conn = got[4];
+    const size_t n = (size_t)std::min(got[4], Ccap);
+    r.conn_kf.resize(n);
+    r.conn_w.resize(n);
+    if (n) {
+      check(gl_memcpy_d2h(ctx_, r.conn_kf.data(), d_kf, n * 4), "d2h");
+      check(gl_memcpy_d2h(ctx_, r.conn_w.data(), d_kf + C, n * 4), "d2h");
+    }
+    return r;
+  }
+  // removeFromGraph: the graph part of Map::removeKeyFrame (map.cpp:60-87) for cull_rows IN REMOVAL ORDER (CullResult::cull_rows), beside
+  // the gl_map_remove that takes the same list.  best_cov[r] afterwards is where the host re-parents frame_info_ (:89-104).
+  struct GraphRemoveResult {
+    int32_t removed = 0, status = 0, erased = 0, malformed = 0;
+    std::vector<int32_t> best_cov;  // per listed row, after the call
+  };
+  GraphRemoveResult removeFromGraph(const std::vector<int32_t>& cull_rows) {
+    const size_t n = cull_rows.size();
+    char* b = pooled(15, 64 + n * 4).as<char>();
+    int32_t* res = reinterpret_cast<int32_t*>(b);
+    int32_t* d_rows = reinterpret_cast<int32_t*>(b + 64);
+    if (n) check(gl_memcpy_h2d(ctx_, d_rows, cull_rows.data(), n * 4), "h2d");
+    check(gl_covis_remove(ctx_, map_.NKF, &cov_, map_ba_.kf_first, n ? d_rows : nullptr, nullptr, (int)n, res), "gl_covis_remove");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t got[4];
+    check(gl_memcpy_d2h(ctx_, got, res, 16), "d2h");
+    GraphRemoveResult r;
+    r.removed = got[0], r.status = got[1], r.erased = got[2], r.malformed = got[3];
+    r.best_cov.assign(n, -1);
+    for (size_t i = 0; i < n; ++i)
+      if (cull_rows[i] >= 0 && cull_rows[i] < map_.NKF) check(gl_memcpy_d2h(ctx_, &r.best_cov[i], cov_.best_cov + cull_rows[i], 4), "d2h");
+    return r;
+  }
+  // bestCovisible: getBestCovisibilityKeyFrames(N) (keyframe.cpp:163-170; N <= 0: getVectorCovisibleKeyFrames) of key-frame kf_row.
+  std::vector<int32_t> bestCovisible(int32_t kf_row, int32_t N, int32_t Ccap = 256) {
+    const size_t C = (size_t)Ccap;
+    char* b = pooled(15, 64 + 2 * C * 4).as<char>();
+    int32_t* res = reinterpret_cast<int32_t*>(b);  // {result (4) | n_conn | kf_row}
+    int32_t* d_kf = reinterpret_cast<int32_t*>(b + 64);
+    check(gl_memcpy_h2d(ctx_, res + 5, &kf_row, 4), "h2d");
+    check(gl_covis_best(ctx_, map_.NKF, &cov_, 1, res + 5, N, Ccap, d_kf, d_kf + C, res + 4, res), "gl_covis_best");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t n = 0;
+    check(gl_memcpy_d2h(ctx_, &n, res + 4, 4), "d2h");
+    std::vector<int32_t> out((size_t)std::min(std::max(n, 0), Ccap));
+    if (!out.empty()) check(gl_memcpy_d2h(ctx_, out.data(), d_kf, out.size() * 4), "d2h");
+    return out;
+  }
+  // searchInNeighborsInMap: the two lists of Localization::searchInNeighbors on the graph and the resident map - the target key-frames
+  // (localization.cpp:155-179) in insertion order, and, called again with `reverse` once the host has run its forward fuses
+  // (fuseObservationsInMap per target with the snapshot of kf_row's points), the candidates of the reverse fuse (:188-206) on the map
+  // as it is then.  The fuses between the two stay the host's sequence of gl_project_map_points -> gl_fuse_search ->
+  // fuseObservationsInMap, as INTEGRATION section 6 step 0.c lists it; updateConnectionsInMap(kf_row) closes the function.
+  struct NeighborLists {
+    int32_t status = 0;
+    std::vector<int32_t> tgt_kf, cand_mp;
+  };
+  NeighborLists searchInNeighborsInMap(int32_t kf_row, int32_t kf_idx, bool reverse = false, int32_t nn = 10, int32_t nn2 = 5) {
+    const size_t T = (size_t)nn + (size_t)nn * nn2, cap = reverse ? T * (size_t)map_.NFK : 0;
+    char* b = pooled(15, 64 + (T + cap) * 4).as<char>();
+    int32_t* res = reinterpret_cast<int32_t*>(b);  // {targets' result (4) | n_tgt | candidates' result (4) | n_cand}
+    int32_t* d_tgt = reinterpret_cast<int32_t*>(b + 64);
+    int32_t* d_cand = d_tgt + T;
+    check(gl_fuse_targets(ctx_, map_.NKF, &cov_, map_.kf_valid, kf_row, nn, nn2, (int)T, d_tgt, res + 4, res), "gl_fuse_targets");
+    if (reverse)
+      check(gl_fuse_candidates(ctx_, &map_, d_tgt, res + 4, (int)T, kf_idx, (int)cap, cap ? d_cand : nullptr, res + 9, res + 5), "gl_fuse_candidates");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    int32_t got[10] = {0};
+    check(gl_memcpy_d2h(ctx_, got, res, reverse ? 40 : 20), "d2h");
+    NeighborLists r;
+    r.status = got[1] | got[6];
+    r.tgt_kf.resize((size_t)std::min<int32_t>(got[4], (int32_t)T));
+    if (!r.tgt_kf.empty()) check(gl_memcpy_d2h(ctx_, r.tgt_kf.data(), d_tgt, r.tgt_kf.size() * 4), "d2h");
+    r.cand_mp.resize(reverse ? (size_t)std::min<int64_t>(got[9], (int64_t)cap) : 0);
+    if (!r.cand_mp.empty()) check(gl_memcpy_d2h(ctx_, r.cand_mp.data(), d_cand, r.cand_mp.size() * 4), "d2h");
+    return r;
+  }
+
   // ORBVocabulary::loadFromBinaryFile and ORBVocabulary::transform(descriptors, bow_vec, feat_vec, levelsup) (orb_vocabulary.cpp:20-40;
   // gmmloc_opt.cpp:25 for a key-frame, tracking.cpp:298 for a frame that falls back to trackKeyFrame) on the device: gl_voc_load_file /
   // gl_bow_transform.  Only the FeatureVector is made (bow_vec_ has no reader in gmmloc/).  loadVocabulary: false on failure like
@@ -1087,6 +1191,7 @@ class GMM {
   gl_map_ba_view map_ba_{};
   gl_map_kf_tables kf_tables_{};
   gl_map_stats stats_{};
+  gl_map_covis cov_{};
   int32_t mp_cap_ = 0, obs_cap_ = 0;  // the rows of the per-point arrays, the entries of obs_kf / obs_feat
   size_t caps_[4] = {24, 24, 2048, 16384};  // Pcap, Fcap, Lcap, Ocap: grown on demand
   size_t win_off_[3] = {0, 0, 0};           // dropped, erase, erase_obs (consecutive)

@@ -12,6 +12,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from ._host import (MAP_BA_DTYPES, MAP_TABLES, MAP_VIEW_DTYPES, MAP_VIEW_POINT_KEYS, GLError, _check, _count, _map_ba_view,  # noqa: F401
+                    _map_edit, _map_view, _outputs, _ptr, _tensor)
 
 ASSOC_BRUTE = 0
 ASSOC_KNN5_EUCLID = 1
@@ -22,15 +24,6 @@ F_MEAN, F_COV, F_COV_INV, F_DET, F_SCALE, F_AXIS, F_SQRT_INFO, F_FLAGS, F_NBS_PT
 TIMER_ASSOC, TIMER_REFINE_POSE, TIMER_BA, TIMER_BA_PREP = 0, 1, 2, 3
 COUNTER_BA_REDONE, COUNTER_MATCH_ROUNDS, COUNTER_MATCH_UNITS = 0, 1, 2
 COUNTER_ASSOC_SCREEN_VERIFIED, COUNTER_ASSOC_SCREEN_FALLBACK = 4, 5
-
-
-class GLError(RuntimeError):
-    pass
-
-
-def _check(rc):
-    if rc != 0:
-        raise GLError("libgmmloc_hip error %d: %s" % (rc, _lib.load().gl_last_error_string().decode()))
 
 
 @dataclass
@@ -66,22 +59,15 @@ class Params:
         return np.array(list(self._c.sigma2_inv), dtype=np.float32)
 
 
-def _ptr(t):
-    if t is None:
-        return None
-    assert t.is_cuda and t.is_contiguous(), "device buffers must be contiguous CUDA tensors"
-    return C.c_void_p(t.data_ptr())
-
-
 class Context:
     """gl_ctx_t: device + HIP stream + scratch.
 
     The context owns a dedicated torch stream (``ctx.stream``) and launches every kernel on
     it.  (torch's default stream is NOT ordered with kernels an external library puts on
     HIP's null stream -- measured on the MI355X box -- so the null stream is never used.)
-    The wrappers below order the context stream against torch's current stream with
-    events (``_enter`` / ``_exit``); under ``with torch.cuda.stream(ctx.stream):`` both are
-    no-ops and calls are fully asynchronous.
+    Every wrapper enqueues through ``call``, which orders the context stream against torch's
+    current stream with events (``_enter`` / ``_exit``); under
+    ``with torch.cuda.stream(ctx.stream):`` both are no-ops and calls are fully asynchronous.
     """
 
     def __init__(self, device=0):
@@ -104,6 +90,14 @@ class Context:
         cur = self.torch.cuda.current_stream(self.device)
         if cur != self.stream:
             cur.wait_stream(self.stream)
+
+    def call(self, fn, *args):
+        """the one enqueue: fn(ctx handle, *args) between _enter and _exit, its return code checked (GLError)"""
+        self._enter()
+        try:
+            _check(fn(self.h, *args))
+        finally:
+            self._exit()
 
     def synchronize(self):
         _check(self.lib.gl_ctx_synchronize(self.h))
@@ -215,11 +209,7 @@ class GMM:
         N = pts.shape[0]
         idx = torch.empty(N, dtype=torch.int32, device=pts.device)
         d2 = torch.empty(N, dtype=torch.float64, device=pts.device) if want_d2 else None
-        self.ctx._enter()
-        try:
-            _check(self.lib.gl_associate3d(self.ctx.h, self.h, _ptr(pts), N, mode, _ptr(idx), _ptr(d2)))
-        finally:
-            self.ctx._exit()
+        self.ctx.call(self.lib.gl_associate3d, self.h, _ptr(pts), N, mode, _ptr(idx), _ptr(d2))
         return idx, d2
 
     def index_info(self):
@@ -237,11 +227,7 @@ class GMM:
         """Number of (point, component) evaluations the cell index performs for these points."""
         import torch
         out = torch.zeros(1, dtype=torch.int64, device=pts.device)
-        self.ctx._enter()
-        try:
-            _check(self.lib.gl_assoc_index_work(self.ctx.h, self.h, _ptr(pts), pts.shape[0], _ptr(out)))
-        finally:
-            self.ctx._exit()
+        self.ctx.call(self.lib.gl_assoc_index_work, self.h, _ptr(pts), pts.shape[0], _ptr(out))
         return int(out.item())
 
     def knn3d(self, pts, k=5):
@@ -249,11 +235,7 @@ class GMM:
         N = pts.shape[0]
         idx = torch.empty((N, k), dtype=torch.int32, device=pts.device)
         dist = torch.empty((N, k), dtype=torch.float64, device=pts.device)
-        self.ctx._enter()
-        try:
-            _check(self.lib.gl_knn3d(self.ctx.h, self.h, _ptr(pts), N, k, _ptr(idx), _ptr(dist)))
-        finally:
-            self.ctx._exit()
+        self.ctx.call(self.lib.gl_knn3d, self.h, _ptr(pts), N, k, _ptr(idx), _ptr(dist))
         return idx, dist
 
     def queryPoint(self, pts):
@@ -282,12 +264,8 @@ def optimize_current_pose(ctx, cam, prm, pose, Xw, obs, octave, outlier=None):
     if outlier is None:
         outlier = torch.zeros((B, M), dtype=torch.uint8, device=pose.device)
     nin = torch.zeros(B, dtype=torch.int32, device=pose.device)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_optimize_current_pose(ctx.h, C.byref(cam.c()), C.byref(prm.c()), B, M, _ptr(pose), _ptr(Xw),
-                                                _ptr(obs), _ptr(octave), _ptr(outlier), _ptr(nin)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_optimize_current_pose, C.byref(cam.c()), C.byref(prm.c()), B, M, _ptr(pose), _ptr(Xw), _ptr(obs), _ptr(octave), _ptr(outlier),
+             _ptr(nin))
     return outlier, nin
 
 
@@ -300,12 +278,8 @@ def track_frames(ctx, gmm, cam, prm, pose, Xw, obs, octave, want_d2=True):
     B, M = octave.shape
     assoc = torch.empty((B, M), dtype=torch.int32, device=pose.device)
     d2 = torch.empty((B, M), dtype=torch.float64, device=pose.device) if want_d2 else None
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_track_frames(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, M, _ptr(pose), _ptr(Xw),
-                                       _ptr(obs), _ptr(octave), _ptr(assoc), _ptr(d2)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_track_frames, gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, M, _ptr(pose), _ptr(Xw), _ptr(obs), _ptr(octave), _ptr(assoc),
+             _ptr(d2))
     return assoc, d2
 
 
@@ -323,12 +297,8 @@ def track_frames_anchored(ctx, gmm, cam, prm, pose, Xw, obs, octave, prior=None,
     d2 = torch.empty((B, M), dtype=torch.float64, device=pose.device) if want_d2 else None
     erase = torch.zeros((B, M, F), dtype=torch.uint8, device=pose.device) if (want_erase and F) else None
     an = _lib.gl_track_anchor(_ptr(prior), F, _ptr(fixed_pose), _ptr(fixed_obs), _ptr(fixed_oct), _ptr(erase))
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_track_frames_anchored(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, M, _ptr(pose), _ptr(Xw),
-                                                _ptr(obs), _ptr(octave), _ptr(assoc), _ptr(d2), C.byref(an)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_track_frames_anchored, gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, M, _ptr(pose), _ptr(Xw), _ptr(obs), _ptr(octave),
+             _ptr(assoc), _ptr(d2), C.byref(an))
     return assoc, d2, erase
 
 
@@ -397,12 +367,8 @@ def _gmm_search2d(self, cam, pose, uv, nfeat=None, k=5, view_cap=0):
     ncand = torch.empty((B, N), dtype=torch.int32, device=uv.device)
     vids = torch.empty((B, view_cap), dtype=torch.int32, device=uv.device) if view_cap else None
     nview = torch.empty(B, dtype=torch.int32, device=uv.device) if view_cap else None
-    self.ctx._enter()
-    try:
-        _check(self.lib.gl_search2d(self.ctx.h, self.h, C.byref(cam.c()), B, _ptr(pose), N, _ptr(uv), _ptr(nfeat), k,
-                                    _ptr(cand), _ptr(ncand), view_cap, _ptr(vids), _ptr(nview)))
-    finally:
-        self.ctx._exit()
+    self.ctx.call(self.lib.gl_search2d, self.h, C.byref(cam.c()), B, _ptr(pose), N, _ptr(uv), _ptr(nfeat), k, _ptr(cand), _ptr(ncand), view_cap,
+                  _ptr(vids), _ptr(nview))
     return cand, ncand, vids, nview
 
 
@@ -418,13 +384,8 @@ def optimize_point(ctx, gmm, cam, prm, pts, uvr, octave, pose, comp, proj_z2):
     c2p = torch.empty(N, dtype=torch.float64, device=dev)
     c2s = torch.empty(N, dtype=torch.float64, device=dev)
     est = torch.empty((N, 3), dtype=torch.float64, device=dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_optimize_point(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), N, _ptr(pts), _ptr(uvr),
-                                         _ptr(octave), _ptr(pose), _ptr(comp), _ptr(proj_z2), _ptr(res), _ptr(c2p),
-                                         _ptr(c2s), _ptr(est)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_optimize_point, gmm.h, C.byref(cam.c()), C.byref(prm.c()), N, _ptr(pts), _ptr(uvr), _ptr(octave), _ptr(pose), _ptr(comp),
+             _ptr(proj_z2), _ptr(res), _ptr(c2p), _ptr(c2s), _ptr(est))
     return res, c2p, c2s, est
 
 
@@ -434,12 +395,8 @@ def check_map_association(ctx, gmm, cam, prm, pose, pts, uvr, octave, cand, ncan
     import torch
     B, N, k = cand.shape
     out = torch.empty((B, N), dtype=torch.int32, device=pts.device)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_check_map_association(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, N, _ptr(pose),
-                                                _ptr(pts), _ptr(uvr), _ptr(octave), _ptr(cand), _ptr(ncand), k, _ptr(out)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_check_map_association, gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, N, _ptr(pose), _ptr(pts), _ptr(uvr), _ptr(octave),
+             _ptr(cand), _ptr(ncand), k, _ptr(out))
     return out
 
 
@@ -448,13 +405,8 @@ def optimize_triangulation(ctx, gmm, cam, prm, x3d, pose1, uvr1, oct1, pose2, uv
     import torch
     N, k = cand1.shape
     out = torch.empty(N, dtype=torch.int32, device=x3d.device)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_optimize_triangulation(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), N, _ptr(x3d),
-                                                 _ptr(pose1), _ptr(uvr1), _ptr(oct1), _ptr(pose2), _ptr(uvr2), _ptr(oct2),
-                                                 _ptr(cand1), _ptr(n1), _ptr(cand2), _ptr(n2), k, _ptr(out)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_optimize_triangulation, gmm.h, C.byref(cam.c()), C.byref(prm.c()), N, _ptr(x3d), _ptr(pose1), _ptr(uvr1), _ptr(oct1),
+             _ptr(pose2), _ptr(uvr2), _ptr(oct2), _ptr(cand1), _ptr(n1), _ptr(cand2), _ptr(n2), k, _ptr(out))
     return out
 
 
@@ -470,20 +422,12 @@ def joint_optimization(ctx, gmm, cam, prm, P, F, poses, prior, points, assoc, ob
     dropped = torch.zeros((B, L), dtype=torch.uint8, device=dev)
     erase = torch.zeros((B, NOBS), dtype=torch.uint8, device=dev)
     iters = torch.zeros(B, dtype=torch.int32, device=dev)
-    ctx._enter()
-    try:
-        if stop_flag is None:
-            _check(ctx.lib.gl_joint_optimization(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, P, F, L, NOBS,
-                                                 _ptr(poses), _ptr(prior), _ptr(points), _ptr(assoc), _ptr(obs_ptr),
-                                                 _ptr(obs_pose), _ptr(obs_uvr), _ptr(obs_oct), _ptr(dropped), _ptr(erase),
-                                                 _ptr(iters)))
-        else:
-            _check(ctx.lib.gl_joint_optimization_stoppable(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, P, F, L, NOBS,
-                                                           _ptr(poses), _ptr(prior), _ptr(points), _ptr(assoc), _ptr(obs_ptr),
-                                                           _ptr(obs_pose), _ptr(obs_uvr), _ptr(obs_oct), _ptr(dropped), _ptr(erase),
-                                                           _ptr(iters), _ptr(stop_flag)))
-    finally:
-        ctx._exit()
+    args = [gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, P, F, L, NOBS, _ptr(poses), _ptr(prior), _ptr(points), _ptr(assoc), _ptr(obs_ptr),
+            _ptr(obs_pose), _ptr(obs_uvr), _ptr(obs_oct), _ptr(dropped), _ptr(erase), _ptr(iters)]
+    if stop_flag is None:
+        ctx.call(ctx.lib.gl_joint_optimization, *args)
+    else:
+        ctx.call(ctx.lib.gl_joint_optimization_stoppable, *args, _ptr(stop_flag))
     return dropped, erase, iters
 
 
@@ -496,14 +440,9 @@ def search_by_projection(ctx, cam, feat_uv, feat_ur, feat_oct, feat_desc, feat_t
     NP = mp_level.shape[1]
     match = torch.empty((B, NF), dtype=torch.int32, device=feat_oct.device)
     nm = torch.empty(B, dtype=torch.int32, device=feat_oct.device)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_search_by_projection(ctx.h, C.byref(cam.c()), float(scale_factor), B, NF, NP, _ptr(feat_uv),
-                                               _ptr(feat_ur), _ptr(feat_oct), _ptr(feat_desc), _ptr(feat_taken), _ptr(mp_uvr),
-                                               _ptr(mp_level), _ptr(mp_viewcos), _ptr(mp_valid), _ptr(mp_desc), float(th),
-                                               float(nn_ratio), _ptr(match), _ptr(nm)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_search_by_projection, C.byref(cam.c()), float(scale_factor), B, NF, NP, _ptr(feat_uv), _ptr(feat_ur), _ptr(feat_oct),
+             _ptr(feat_desc), _ptr(feat_taken), _ptr(mp_uvr), _ptr(mp_level), _ptr(mp_viewcos), _ptr(mp_valid), _ptr(mp_desc), float(th),
+             float(nn_ratio), _ptr(match), _ptr(nm))
     return match, nm
 
 
@@ -518,14 +457,9 @@ def search_local_points(ctx, cam, feat_uv, feat_ur, feat_oct, feat_desc, feat_ta
     match = torch.empty((B, NF), dtype=torch.int32, device=dev)
     nm = torch.empty(B, dtype=torch.int32, device=dev)
     inview = torch.empty((B, NP), dtype=torch.uint8, device=dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_search_local_points(ctx.h, C.byref(cam.c()), float(scale_factor), B, NF, NP, _ptr(feat_uv), _ptr(feat_ur), _ptr(feat_oct),
-                                              _ptr(feat_desc), _ptr(feat_taken), _ptr(pose_cw), _ptr(t_wc), _ptr(mp_pos), _ptr(mp_normal),
-                                              _ptr(mp_max_dist), _ptr(mp_min_dist), _ptr(mp_cand), _ptr(mp_desc), float(th), float(nn_ratio),
-                                              _ptr(match), _ptr(nm), _ptr(inview)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_search_local_points, C.byref(cam.c()), float(scale_factor), B, NF, NP, _ptr(feat_uv), _ptr(feat_ur), _ptr(feat_oct),
+             _ptr(feat_desc), _ptr(feat_taken), _ptr(pose_cw), _ptr(t_wc), _ptr(mp_pos), _ptr(mp_normal), _ptr(mp_max_dist), _ptr(mp_min_dist),
+             _ptr(mp_cand), _ptr(mp_desc), float(th), float(nn_ratio), _ptr(match), _ptr(nm), _ptr(inview))
     return match, nm, inview
 
 
@@ -601,12 +535,8 @@ def track_frame_chain(ctx, cam, prm, a, th_mm=7.0, th_local=3.0, nn_ratio=0.8, m
     else:
         out["pose"].copy_(a["pose_cw"])
     io = _chain_io(a, out)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_track_frame_chain(ctx.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), B, NF, NL, NP, C.byref(io),
-                                            float(th_mm), float(th_local), float(nn_ratio), int(bool(mono))))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_track_frame_chain, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), B, NF, NL, NP, C.byref(io), float(th_mm),
+             float(th_local), float(nn_ratio), int(bool(mono)))
     return out
 
 
@@ -618,12 +548,8 @@ def track_frame_chain_front(ctx, cam, prm, a, th_mm=7.0, mono=False, scale_facto
     NL, NP = a["last_oct"].shape[1], a["mp_cand"].shape[1]
     out = _chain_out(a)
     io = _chain_io(a, out)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_track_frame_chain_front(ctx.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), B, NF, NL, NP, C.byref(io),
-                                                  float(th_mm), int(bool(mono))))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_track_frame_chain_front, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), B, NF, NL, NP, C.byref(io), float(th_mm),
+             int(bool(mono)))
     return out
 
 
@@ -636,57 +562,13 @@ def track_frame_chain_back(ctx, cam, prm, a, out, th_local=3.0, nn_ratio=0.8, sc
     if out["inview"].shape[1] != NP:
         out["inview"] = torch.zeros((B, NP), dtype=torch.uint8, device=a["feat_oct"].device)
     io = _chain_io(a, out)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_track_frame_chain_back(ctx.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), B, NF, NL, NP, C.byref(io),
-                                                 float(th_local), float(nn_ratio)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_track_frame_chain_back, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), B, NF, NL, NP, C.byref(io), float(th_local),
+             float(nn_ratio))
     return out
 
 
-# The whole map as device arrays (gl_map_view): what update_map_points reads and writes + the key-frames' mappoints_ table.
-MAP_VIEW_DTYPES = {"mp_valid": "uint8", "obs_ptr": "int32", "obs_kf": "int32", "kf_valid": "uint8", "kf_mp": "int32", "mp_pos": "float64",
-                   "mp_normal": "float64", "mp_max_dist": "float32", "mp_min_dist": "float32", "mp_desc": "uint8"}
-MAP_VIEW_POINT_KEYS = ("mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc")
+# The whole map as device arrays (gl_map_view, gl_map_ba_view): _host.MAP_TABLES and what is derived from it
 LOCAL_MAP_STATUS_KEPT, LOCAL_MAP_STATUS_MP_TRUNCATED, LOCAL_MAP_STATUS_KF_TRUNCATED = 1, 2, 4
-
-
-def _tensor(name, t, dtype, shape, device):
-    """`t` is a contiguous CUDA tensor of that dtype and shape (None in the shape: any extent) on `device` - or raise."""
-    assert t is not None, "%s: missing" % name
-    assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch." + dtype, \
-        "%s: expected a contiguous CUDA %s tensor, got %s%s" % (name, dtype, t.dtype, "" if t.is_contiguous() else " (not contiguous)")
-    assert device is None or t.device == device, "%s: on %s, expected %s" % (name, t.device, device)
-    assert t.dim() == len(shape) and all(w is None or int(w) == int(h) for w, h in zip(shape, t.shape)), \
-        "%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape))
-    return t
-
-
-def _map_view(m, need_points):
-    """dict of CUDA tensors -> (gl_map_view, device).  Keys of MAP_VIEW_DTYPES; mp_valid / kf_valid optional (all valid); the per-point
-    arrays only where `need_points`."""
-    for k in m:
-        assert k in MAP_VIEW_DTYPES, "map[%r]: unknown key" % k
-    dev = _tensor("map['obs_ptr']", m.get("obs_ptr"), "int32", (None,), None).device
-    NMP = m["obs_ptr"].shape[0] - 1
-    assert NMP >= 0, "map['obs_ptr']: needs NMP + 1 entries"
-    _tensor("map['obs_kf']", m.get("obs_kf"), "int32", (None,), dev)
-    _tensor("map['kf_mp']", m.get("kf_mp"), "int32", (None, None), dev)
-    NKF, NFK = m["kf_mp"].shape
-    if m.get("mp_valid") is not None:
-        _tensor("map['mp_valid']", m["mp_valid"], "uint8", (NMP,), dev)
-    if m.get("kf_valid") is not None:
-        _tensor("map['kf_valid']", m["kf_valid"], "uint8", (NKF,), dev)
-    shapes = {"mp_pos": (NMP, 3), "mp_normal": (NMP, 3), "mp_max_dist": (NMP,), "mp_min_dist": (NMP,), "mp_desc": (NMP, 32)}
-    for k in MAP_VIEW_POINT_KEYS:
-        if need_points or m.get(k) is not None:
-            _tensor("map[%r]" % k, m.get(k), MAP_VIEW_DTYPES[k], shapes[k], dev)
-    v = _lib.gl_map_view()
-    v.NMP, v.NKF, v.NFK, v.NOBS = NMP, NKF, NFK, m["obs_kf"].shape[0]
-    for k in MAP_VIEW_DTYPES:
-        setattr(v, k, _ptr(m[k]) if m.get(k) is not None else None)
-    return v, dev
 
 
 def local_map_lists(B, KFcap, NPcap, NKF=None, device="cuda"):
@@ -725,13 +607,8 @@ def update_local_map(ctx, map, feat_mp, lists):
     _tensor("feat_mp", feat_mp, "int32", (None, None), dev)
     B, NF = feat_mp.shape
     KFcap, NPcap = _check_lists(lists, B, v.NKF, dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_update_local_map(ctx.h, C.byref(v), B, NF, KFcap, NPcap, _ptr(feat_mp), _ptr(lists["local_kf"]),
-                                           _ptr(lists["n_local_kf"]), _ptr(lists["local_mp"]), _ptr(lists["n_local_mp"]),
-                                           _ptr(lists["ref_kf"]), _ptr(lists.get("kf_count")), _ptr(lists["status"])))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_update_local_map, C.byref(v), B, NF, KFcap, NPcap, _ptr(feat_mp), _ptr(lists["local_kf"]), _ptr(lists["n_local_kf"]),
+             _ptr(lists["local_mp"]), _ptr(lists["n_local_mp"]), _ptr(lists["ref_kf"]), _ptr(lists.get("kf_count")), _ptr(lists["status"]))
     return lists
 
 
@@ -795,17 +672,12 @@ def track_frame_chain_map(ctx, cam, prm, a, map, lm, th_mm=7.0, th_local=3.0, nn
     l.last_mp, l.kf_feat_mp, l.feat_mp, l.KFcap = _ptr(lm["last_mp"]), _ptr(lm["kf_feat_mp"]) if fbk else None, _ptr(out["feat_mp"]), KFcap
     for k in ("local_kf", "n_local_kf", "local_mp", "n_local_mp", "ref_kf", "kf_count", "status"):
         setattr(l, k, _ptr(lists[k]) if lists.get(k) is not None else None)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_track_frame_chain_map(ctx.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), B, NF, NL, NPcap, C.byref(io),
-                                                C.byref(v), C.byref(l), float(th_mm), float(th_local), float(nn_ratio), int(bool(mono))))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_track_frame_chain_map, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), B, NF, NL, NPcap, C.byref(io), C.byref(v),
+             C.byref(l), float(th_mm), float(th_local), float(nn_ratio), int(bool(mono)))
     return out
 
 
 # ---- the mapping thread on the resident map: covisibility, the local-BA window, the write-back (gmmloc_hip.h)
-MAP_BA_DTYPES = {"kf_pose": "float64", "kf_twc": "float64", "kf_uvr": "float64", "kf_oct": "int32", "obs_feat": "int32", "mp_assoc": "int32"}
 CONN_KEPT, CONN_TRUNCATED, CONN_BAD_ROW = 1, 2, 4
 BA_WINDOW_NO_CONN, BA_WINDOW_P_TRUNCATED, BA_WINDOW_F_TRUNCATED, BA_WINDOW_L_TRUNCATED, BA_WINDOW_O_TRUNCATED, BA_WINDOW_BAD_ROW = 1, 2, 4, 8, 16, 32
 BA_WINDOW_TRUNCATED, BA_WINDOW_DROPPED_SHIFT = 30, 8
@@ -814,50 +686,24 @@ BA_WINDOW_DTYPES = {"poses": "float64", "prior": "uint8", "points": "float64", "
                     "status": "int32"}
 
 
-def _map_ba_view(ba, v, dev, need=None):
-    """dict of CUDA tensors (keys of MAP_BA_DTYPES; kf_twc optional; `need`: the keys a call reads when it does not read them all) +
-    kf_first (int, -1: none) -> gl_map_ba_view for the map view v"""
-    for k in ba:
-        assert k in MAP_BA_DTYPES or k == "kf_first", "ba[%r]: unknown key" % k
-    shapes = {"kf_pose": (v.NKF, 7), "kf_twc": (v.NKF, 3), "kf_uvr": (v.NKF, v.NFK, 3), "kf_oct": (v.NKF, v.NFK), "obs_feat": (v.NOBS,),
-              "mp_assoc": (v.NMP,)}
-    w = _lib.gl_map_ba_view()
-    for k, dt in MAP_BA_DTYPES.items():
-        if ba.get(k) is None and (k == "kf_twc" or (need is not None and k not in need)):
-            continue
-        setattr(w, k, _ptr(_tensor("ba[%r]" % k, ba.get(k), dt, shapes[k], dev)))
-    w.kf_first = int(ba.get("kf_first", -1))
-    return w
-
-
 def update_connections(ctx, map, kf_row, Ccap=None, out=None, want_count=False):
     """gl_update_connections: KeyFrame::updateConnections (keyframe.cpp:243-316) for the B key-frame rows kf_row (B,) i32 on the map
     of update_local_map (rules and the tie rule - lowest row first: gmmloc_hip.h).  -> dict(conn_kf (B,Ccap), conn_w (B,Ccap), n_conn
     (B,) the true lengths, status (B,)[, kf_count (B,NKF)]); `out`: the same dict to write into (a key-frame with an empty counter
     keeps its lists)."""
-    import torch
     v, dev = _map_view(map, False)
     _tensor("kf_row", kf_row, "int32", (None,), dev)
     B = kf_row.shape[0]
-    if out is None:
-        assert Ccap is not None, "Ccap or out"
-        z = lambda *sh: torch.zeros(sh, dtype=torch.int32, device=dev)
-        out = dict(conn_kf=torch.full((B, Ccap), -1, dtype=torch.int32, device=dev), conn_w=z(B, Ccap), n_conn=z(B), status=z(B))
-        if want_count:
-            out["kf_count"] = z(B, v.NKF)
-    _tensor("out['conn_kf']", out.get("conn_kf"), "int32", (B, None), dev)
-    Ccap = out["conn_kf"].shape[1]
-    _tensor("out['conn_w']", out.get("conn_w"), "int32", (B, Ccap), dev)
-    for k in ("n_conn", "status"):
-        _tensor("out[%r]" % k, out.get(k), "int32", (B,), dev)
-    if out.get("kf_count") is not None:
-        _tensor("out['kf_count']", out["kf_count"], "int32", (B, v.NKF), dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_update_connections(ctx.h, C.byref(v), B, _ptr(kf_row), Ccap, _ptr(out["conn_kf"]), _ptr(out["conn_w"]),
-                                             _ptr(out["n_conn"]), _ptr(out.get("kf_count")), _ptr(out["status"])))
-    finally:
-        ctx._exit()
+    if out is not None:  # (its own capacity, and kf_count if it holds one)
+        Ccap = _tensor("out['conn_kf']", out.get("conn_kf"), "int32", (B, None), dev).shape[1]
+        want_count = out.get("kf_count") is not None
+    assert Ccap is not None, "Ccap or out"
+    spec = dict(conn_kf=("int32", (B, Ccap), -1), conn_w=("int32", (B, Ccap), 0), n_conn=("int32", (B,), 0), status=("int32", (B,), 0))
+    if want_count:
+        spec["kf_count"] = ("int32", (B, v.NKF), 0)
+    out = _outputs(out, spec, dev)
+    ctx.call(ctx.lib.gl_update_connections, C.byref(v), B, _ptr(kf_row), Ccap, _ptr(out["conn_kf"]), _ptr(out["conn_w"]), _ptr(out["n_conn"]),
+             _ptr(out.get("kf_count")), _ptr(out["status"]))
     return out
 
 
@@ -902,11 +748,7 @@ def ba_window_build(ctx, map, ba, kf_row, slab):
     w = _map_ba_view(ba, v, dev)
     win, B = _ba_window(slab, dev)
     _tensor("kf_row", kf_row, "int32", (B,), dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_ba_window_build(ctx.h, C.byref(v), C.byref(w), B, _ptr(kf_row), C.byref(win)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_ba_window_build, C.byref(v), C.byref(w), B, _ptr(kf_row), C.byref(win))
     return slab
 
 
@@ -923,12 +765,8 @@ def ba_window_apply(ctx, map, ba, slab):
     _tensor("slab['iters']", slab.get("iters"), "int32", (B,), dev)
     _tensor("slab['erase_obs']", slab.get("erase_obs"), "int32", (B, win.Ocap), dev)
     _tensor("slab['n_erase']", slab.get("n_erase"), "int32", (B,), dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_ba_window_apply(ctx.h, C.byref(v), _ptr(map["mp_pos"]), C.byref(w), B, C.byref(win), _ptr(slab["dropped"]),
-                                          _ptr(slab["erase"]), _ptr(slab["iters"]), _ptr(slab["erase_obs"]), _ptr(slab["n_erase"])))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_ba_window_apply, C.byref(v), _ptr(map["mp_pos"]), C.byref(w), B, C.byref(win), _ptr(slab["dropped"]), _ptr(slab["erase"]),
+             _ptr(slab["iters"]), _ptr(slab["erase_obs"]), _ptr(slab["n_erase"]))
     return slab["erase_obs"], slab["n_erase"]
 
 
@@ -946,20 +784,13 @@ def joint_optimization_from_map(ctx, gmm, cam, prm, map, ba, kf_row, caps, stop_
     caps = tuple(int(c) for c in caps)
     if slab is None:
         slab = ba_window_slab(1, *caps, device=dev)
-
-    def run(fn, *args):
-        ctx._enter()
-        try:
-            _check(fn(ctx.h, *args))
-        finally:
-            ctx._exit()
     for attempt in range(2):
         win, B = _ba_window(slab, dev)
         assert B == 1, "slab: one window"
         if "kf_row" not in slab:
             slab["kf_row"] = torch.zeros(1, dtype=torch.int32, device=dev)
         slab["kf_row"].fill_(int(kf_row))
-        run(ctx.lib.gl_ba_window_build, C.byref(v), C.byref(w), 1, _ptr(slab["kf_row"]), C.byref(win))
+        ctx.call(ctx.lib.gl_ba_window_build, C.byref(v), C.byref(w), 1, _ptr(slab["kf_row"]), C.byref(win))
         # the one round trip: sizes and status to the host, a synchronise
         P, F, L, nobs, status = torch.cat((slab["sizes"][0], slab["status"])).tolist()
         if not status & BA_WINDOW_TRUNCATED:
@@ -976,13 +807,13 @@ def joint_optimization_from_map(ctx, gmm, cam, prm, map, ba, kf_row, caps, stop_
                 _ptr(s["assoc"]), _ptr(s["obs_ptr"]), _ptr(s["obs_pose"]), _ptr(s["obs_uvr"]), _ptr(s["obs_oct"]), _ptr(s["dropped"]),
                 _ptr(s["erase"]), _ptr(s["iters"])]
         if stop_flag is None:
-            run(ctx.lib.gl_joint_optimization, *args)
+            ctx.call(ctx.lib.gl_joint_optimization, *args)
         else:
-            run(ctx.lib.gl_joint_optimization_stoppable, *(args + [_ptr(stop_flag)]))
+            ctx.call(ctx.lib.gl_joint_optimization_stoppable, *args, _ptr(stop_flag))
     for k, sh in (("erase_obs", (1, win.Ocap)), ("n_erase", (1,))):
         _tensor("slab[%r]" % k, s.get(k), "int32", sh, dev)
-    run(ctx.lib.gl_ba_window_apply, C.byref(v), _ptr(map["mp_pos"]), C.byref(w), 1, C.byref(win), _ptr(s["dropped"]), _ptr(s["erase"]),
-        _ptr(s["iters"]), _ptr(s["erase_obs"]), _ptr(s["n_erase"]))
+    ctx.call(ctx.lib.gl_ba_window_apply, C.byref(v), _ptr(map["mp_pos"]), C.byref(w), 1, C.byref(win), _ptr(s["dropped"]), _ptr(s["erase"]),
+             _ptr(s["iters"]), _ptr(s["erase_obs"]), _ptr(s["n_erase"]))
     n_erase = int(slab["n_erase"][0])
     return dict(slab=slab, P=P, F=F, L=L, nobs=nobs, status=status, caps=caps, win_kf=s["win_kf"][0, :P + F], win_mp=s["win_mp"][0, :L],
                 assoc_dropped=s["dropped"][0, :L], obs_erase=s["erase"][0, :nobs], iters=s["iters"], erase_obs=s["erase_obs"][0, :n_erase])
@@ -1001,26 +832,16 @@ def cull_keyframes(ctx, map, ba, kf_depth, th_depth, cand, n_cand, out=None):
     order (rules, the weighted count, malformed input, the bound on NKF: gmmloc_hip.h).  kf_depth (NKF,NFK) f32; th_depth float.  The map
     is not modified.  -> dict(cull (B,Ccap) u8, num_mps, num_redundant, cand_status (B,Ccap) i32, cull_rows (B,Ccap) i32 + n_cull (B,):
     the culled rows in list order, what map_remove takes as rm_kf); `out`: the same dict to write into."""
-    import torch
     v, dev = _map_view(map, False)
     w = _map_ba_view(ba, v, dev, need=("kf_uvr", "kf_oct", "obs_feat"))
     _tensor("kf_depth", kf_depth, "float32", (v.NKF, v.NFK), dev)
     B, Ccap = _tensor("cand", cand, "int32", (None, None), dev).shape
     _tensor("n_cand", n_cand, "int32", (B,), dev)
-    if out is None:
-        out = {k: torch.zeros((B, Ccap), dtype=getattr(torch, dt), device=dev) for k, dt in CULL_DTYPES.items()}
-        out["cull_rows"].fill_(-1)
-        out["n_cull"] = torch.zeros(B, dtype=torch.int32, device=dev)
-    for k, dt in CULL_DTYPES.items():
-        _tensor("out[%r]" % k, out.get(k), dt, (B, Ccap), dev)
-    _tensor("out['n_cull']", out.get("n_cull"), "int32", (B,), dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_cull_keyframes(ctx.h, C.byref(v), C.byref(w), _ptr(kf_depth), float(th_depth), B, max(Ccap, 1), _ptr(cand), _ptr(n_cand),
-                                         _ptr(out["cull"]), _ptr(out["num_mps"]), _ptr(out["num_redundant"]), _ptr(out["cand_status"]),
-                                         _ptr(out["cull_rows"]), _ptr(out["n_cull"])))
-    finally:
-        ctx._exit()
+    spec = {k: (dt, (B, Ccap), -1 if k == "cull_rows" else 0) for k, dt in CULL_DTYPES.items()}
+    out = _outputs(out, dict(spec, n_cull=("int32", (B,), 0)), dev)
+    ctx.call(ctx.lib.gl_cull_keyframes, C.byref(v), C.byref(w), _ptr(kf_depth), float(th_depth), B, max(Ccap, 1), _ptr(cand), _ptr(n_cand),
+             _ptr(out["cull"]), _ptr(out["num_mps"]), _ptr(out["num_redundant"]), _ptr(out["cand_status"]), _ptr(out["cull_rows"]),
+             _ptr(out["n_cull"]))
     return out
 
 
@@ -1030,9 +851,7 @@ def _row_list(name, rows, n, dev):
         assert n is None, "n_%s without %s" % (name, name)
         return None, None, 0
     _tensor(name, rows, "int32", (None,), dev)
-    if n is not None:
-        assert n.is_cuda and n.device == dev and str(n.dtype) == "torch.int32" and n.numel() == 1, "n_%s: one int32 on the device" % name
-    return _ptr(rows), (_ptr(n) if n is not None else None), rows.shape[0]
+    return _ptr(rows), _count("n_" + name, n, dev), rows.shape[0]
 
 
 def map_remove(ctx, map, ba, erase_obs=None, rm_kf=None, rm_mp=None, n_erase=None, n_rm_kf=None, n_rm_mp=None, mp_ref_kf=None, dead_cap=None,
@@ -1048,12 +867,7 @@ def map_remove(ctx, map, ba, erase_obs=None, rm_kf=None, rm_mp=None, n_erase=Non
     v, dev = _map_view(map, False)
     _map_ba_view(ba, v, dev, need=("kf_uvr", "obs_feat"))
     assert map.get("mp_valid") is not None and map.get("kf_valid") is not None, "map_remove: mp_valid and kf_valid are written, both are needed"
-    ed = _lib.gl_map_edit()
-    for k in ("mp_valid", "kf_valid", "kf_mp", "obs_ptr", "obs_kf"):
-        setattr(ed, k, _ptr(map[k]))
-    ed.obs_feat = _ptr(ba["obs_feat"])
-    if mp_ref_kf is not None:
-        ed.mp_ref_kf = _ptr(_tensor("mp_ref_kf", mp_ref_kf, "int32", (v.NMP,), dev))
+    ed = _map_edit(map, ba, mp_ref_kf, v.NMP, dev)
     ls = _lib.gl_map_remove_lists()
     ls.rm_mp, ls.n_rm_mp, ls.rm_mp_cap = _row_list("rm_mp", rm_mp, n_rm_mp, dev)
     ls.erase_obs, ls.n_erase, ls.erase_cap = _row_list("erase_obs", erase_obs, n_erase, dev)
@@ -1064,12 +878,8 @@ def map_remove(ctx, map, ba, erase_obs=None, rm_kf=None, rm_mp=None, n_erase=Non
     new_pos = torch.zeros(v.NOBS, dtype=torch.int32, device=dev) if want_new_pos else None
     o = _lib.gl_map_remove_out()
     o.result, o.dead_mp, o.obs_new_pos, o.dead_cap = _ptr(result), (_ptr(dead) if dead_cap else None), _ptr(new_pos), dead_cap
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_map_remove(ctx.h, v.NMP, v.NKF, v.NFK, v.NOBS, C.byref(ed), _ptr(ba["kf_uvr"]), int(ba.get("kf_first", -1)), C.byref(ls),
-                                     C.byref(o)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_map_remove, v.NMP, v.NKF, v.NFK, v.NOBS, C.byref(ed), _ptr(ba["kf_uvr"]), int(ba.get("kf_first", -1)), C.byref(ls),
+             C.byref(o))
     nobs, n_dead, status = result.tolist()  # the one round trip
     r = dict(map=dict(map, obs_kf=map["obs_kf"][:nobs]), ba=dict(ba, obs_feat=ba["obs_feat"][:nobs]), nobs=nobs, status=status,
              dead_mp=dead[:min(n_dead, dead_cap)], n_dead=n_dead)
@@ -1106,14 +916,9 @@ def search_by_projection_frame(ctx, cam, pose_cw, pose_lw, feat_uv, feat_ur, fea
     NL = last_oct.shape[1]
     match = torch.empty((B, NF), dtype=torch.int32, device=feat_oct.device)
     nm = torch.empty(B, dtype=torch.int32, device=feat_oct.device)
-    ctx._enter()
-    _check(ctx.lib.gl_search_by_projection_frame(ctx.h, C.byref(cam.c()), float(scale_factor), B, NF, NL, _ptr(pose_cw),
-                                                 _ptr(pose_lw), _ptr(feat_uv), _ptr(feat_ur), _ptr(feat_oct),
-                                                 _ptr(feat_angle), _ptr(feat_desc), _ptr(feat_taken), _ptr(last_pt),
-                                                 _ptr(last_valid), _ptr(last_oct), _ptr(last_angle), _ptr(last_desc),
-                                                 float(th), int(bool(mono)), int(bool(check_orientation)), _ptr(match),
-                                                 _ptr(nm)))
-    ctx._exit()
+    ctx.call(ctx.lib.gl_search_by_projection_frame, C.byref(cam.c()), float(scale_factor), B, NF, NL, _ptr(pose_cw), _ptr(pose_lw), _ptr(feat_uv),
+             _ptr(feat_ur), _ptr(feat_oct), _ptr(feat_angle), _ptr(feat_desc), _ptr(feat_taken), _ptr(last_pt), _ptr(last_valid), _ptr(last_oct),
+             _ptr(last_angle), _ptr(last_desc), float(th), int(bool(mono)), int(bool(check_orientation)), _ptr(match), _ptr(nm))
     return match, nm
 
 
@@ -1145,13 +950,8 @@ def search_for_triangulation(ctx, kf1, kf2, fmat, epipole, only_stereo=False, ch
     dev = kf1["oct"].device
     match = torch.empty((B, N1), dtype=torch.int32, device=dev)
     nm = torch.empty(B, dtype=torch.int32, device=dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_search_for_triangulation(ctx.h, float(scale_factor), B, N1, N2, NN1, NN2, *[_ptr(kf1[k]) for k in KF_KEYS],
-                                                   *[_ptr(kf2[k]) for k in KF_KEYS], _ptr(fmat), _ptr(epipole), int(bool(only_stereo)),
-                                                   int(bool(check_orientation)), _ptr(match), _ptr(nm)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_search_for_triangulation, float(scale_factor), B, N1, N2, NN1, NN2, *[_ptr(kf1[k]) for k in KF_KEYS],
+             *[_ptr(kf2[k]) for k in KF_KEYS], _ptr(fmat), _ptr(epipole), int(bool(only_stereo)), int(bool(check_orientation)), _ptr(match), _ptr(nm))
     return match, nm
 
 
@@ -1174,13 +974,8 @@ def project_map_points(ctx, cam, pose_cw, t_wc, pos, normal, max_dist, min_dist,
     viewcos = torch.empty((B, NP), dtype=torch.float64, device=dev)
     dist = torch.empty((B, NP), dtype=torch.float64, device=dev)
     inview = torch.empty((B, NP), dtype=torch.uint8, device=dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_project_map_points(ctx.h, C.byref(cam.c()), float(scale_factor), B, NP, _ptr(pose_cw), _ptr(t_wc), _ptr(pos), _ptr(normal),
-                                             _ptr(max_dist), _ptr(min_dist), _ptr(cand), _ptr(uvr), _ptr(level), _ptr(viewcos), _ptr(dist),
-                                             _ptr(inview)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_project_map_points, C.byref(cam.c()), float(scale_factor), B, NP, _ptr(pose_cw), _ptr(t_wc), _ptr(pos), _ptr(normal),
+             _ptr(max_dist), _ptr(min_dist), _ptr(cand), _ptr(uvr), _ptr(level), _ptr(viewcos), _ptr(dist), _ptr(inview))
     return uvr, level, viewcos, dist, inview
 
 
@@ -1208,14 +1003,9 @@ def update_map_points(ctx, kf, mp, out, what=3, scale_factor=1.2):
     NP = mp["obs_ptr"].shape[0] - 1
     NOBS = mp["obs_kf"].shape[0] if mp.get("obs_kf") is not None else 0
     g = lambda d, k: _ptr(d.get(k))
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_update_map_points(ctx.h, float(scale_factor), int(what), NP, NKF, NFK, NOBS, g(kf, "twc"), g(kf, "valid"),
-                                            g(kf, "oct"), g(kf, "desc"), g(mp, "pos"), g(mp, "valid"), g(mp, "ref_kf"), g(mp, "obs_ptr"),
-                                            g(mp, "obs_kf"), g(mp, "obs_feat"), g(out, "desc"), g(out, "normal"), g(out, "max_dist"),
-                                            g(out, "min_dist")))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_update_map_points, float(scale_factor), int(what), NP, NKF, NFK, NOBS, g(kf, "twc"), g(kf, "valid"), g(kf, "oct"),
+             g(kf, "desc"), g(mp, "pos"), g(mp, "valid"), g(mp, "ref_kf"), g(mp, "obs_ptr"), g(mp, "obs_kf"), g(mp, "obs_feat"), g(out, "desc"),
+             g(out, "normal"), g(out, "max_dist"), g(out, "min_dist"))
     return out
 
 
@@ -1228,12 +1018,8 @@ def fuse_search(ctx, cam, feat_uv, feat_ur, feat_oct, feat_desc, mp_uvr, mp_leve
     NP = mp_level.shape[1]
     bi = torch.empty((B, NP), dtype=torch.int32, device=feat_oct.device)
     bd = torch.empty((B, NP), dtype=torch.int32, device=feat_oct.device)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_fuse_search(ctx.h, C.byref(cam.c()), float(scale_factor), B, NF, NP, _ptr(feat_uv), _ptr(feat_ur), _ptr(feat_oct),
-                                      _ptr(feat_desc), _ptr(mp_uvr), _ptr(mp_level), _ptr(mp_valid), _ptr(mp_desc), float(th), _ptr(bi), _ptr(bd)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_fuse_search, C.byref(cam.c()), float(scale_factor), B, NF, NP, _ptr(feat_uv), _ptr(feat_ur), _ptr(feat_oct), _ptr(feat_desc),
+             _ptr(mp_uvr), _ptr(mp_level), _ptr(mp_valid), _ptr(mp_desc), float(th), _ptr(bi), _ptr(bd))
     return bi, bd
 
 
@@ -1252,14 +1038,9 @@ def search_by_bow(ctx, kf, fr, nn_ratio=0.7, check_orientation=True):
     dev = kf["angle"].device
     match = torch.empty((B, N2), dtype=torch.int32, device=dev)
     nm = torch.empty(B, dtype=torch.int32, device=dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_search_by_bow(ctx.h, float(nn_ratio), int(bool(check_orientation)), B, N1, N2, NN1, NN2,
-                                        *[_ptr(kf[k]) for k in ("angle", "desc", "has_mp", "nnode", "node_id", "node_ptr", "node_idx")],
-                                        *[_ptr(fr[k]) for k in ("angle", "desc", "nnode", "node_id", "node_ptr", "node_idx")],
-                                        _ptr(match), _ptr(nm)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_search_by_bow, float(nn_ratio), int(bool(check_orientation)), B, N1, N2, NN1, NN2,
+             *[_ptr(kf[k]) for k in ("angle", "desc", "has_mp", "nnode", "node_id", "node_ptr", "node_idx")],
+             *[_ptr(fr[k]) for k in ("angle", "desc", "nnode", "node_id", "node_ptr", "node_idx")], _ptr(match), _ptr(nm))
     return match, nm
 
 
@@ -1283,13 +1064,9 @@ def gather_triangulation_matches(ctx, match12, nmatches, side1, side2, cap=None)
              pair=torch.full((cap,), -1, dtype=torch.int32, device=dev), idx1=torch.full((cap,), -1, dtype=torch.int32, device=dev),
              idx2=torch.full((cap,), -1, dtype=torch.int32, device=dev))
     keys = ("pose", "uv", "ur", "depth", "oct", "cand", "ncand")
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_gather_triangulation_matches(
-            ctx.h, B, N1, N2, k, cap, _ptr(match12), _ptr(nmatches), *[_ptr(side1[q]) for q in keys], *[_ptr(side2[q]) for q in keys], _ptr(off),
-            *[_ptr(m[q]) for q in ("pose1", "uvr1", "depth1", "oct1", "cand1", "n1", "pose2", "uvr2", "depth2", "oct2", "cand2", "n2", "pair", "idx1", "idx2")]))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_gather_triangulation_matches, B, N1, N2, k, cap, _ptr(match12), _ptr(nmatches), *[_ptr(side1[q]) for q in keys],
+             *[_ptr(side2[q]) for q in keys], _ptr(off),
+             *[_ptr(m[q]) for q in ("pose1", "uvr1", "depth1", "oct1", "cand1", "n1", "pose2", "uvr2", "depth2", "oct2", "cand2", "n2", "pair", "idx1", "idx2")])
     return off, m
 
 
@@ -1303,14 +1080,9 @@ def create_map_points(ctx, gmm, cam, prm, pose1, uvr1, depth1, oct1, pose2, uvr2
     x3d = torch.empty((N, 3), dtype=torch.float64, device=dev)
     typ = torch.empty(N, dtype=torch.int32, device=dev)
     comp = torch.empty(N, dtype=torch.int32, device=dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_create_map_points(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), N,
-                                            _ptr(pose1), _ptr(uvr1), _ptr(depth1), _ptr(oct1), _ptr(pose2), _ptr(uvr2),
-                                            _ptr(depth2), _ptr(oct2), _ptr(cand1), _ptr(n1), _ptr(cand2), _ptr(n2), k,
-                                            _ptr(x3d), _ptr(typ), _ptr(comp)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_create_map_points, gmm.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), N, _ptr(pose1), _ptr(uvr1), _ptr(depth1),
+             _ptr(oct1), _ptr(pose2), _ptr(uvr2), _ptr(depth2), _ptr(oct2), _ptr(cand1), _ptr(n1), _ptr(cand2), _ptr(n2), k, _ptr(x3d), _ptr(typ),
+             _ptr(comp))
     return x3d, typ, comp
 
 

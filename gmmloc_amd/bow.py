@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .api import _check, _ptr, _tensor
+from ._host import _check, _ptr, _tensor
 
 BOW_NODES_TRUNCATED = 1
 BOW_MAX_FEATURES = 4096
@@ -109,11 +109,7 @@ def transform(ctx, voc, desc, oct=None, levelsup=4, nn_cap=None, out=None, per_f
     for key, sh in shapes.items():
         if out.get(key) is not None:
             setattr(o, key, _ptr(_tensor("out[%r]" % key, out[key], "float32" if key == "weight" else "int32", sh, dev)))
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_bow_transform(ctx.h, voc.h, int(levelsup), B, NF, nn_cap, _ptr(desc), _ptr(oct), C.byref(o)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_bow_transform, voc.h, int(levelsup), B, NF, nn_cap, _ptr(desc), _ptr(oct), C.byref(o))
     return out
 
 

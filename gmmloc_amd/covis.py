@@ -8,7 +8,7 @@ Every wrapper only enqueues and returns device tensors; update_connections_in_ma
 import ctypes as C
 
 from . import _lib, map_grow
-from .api import _check, _map_view, _ptr, _tensor
+from ._host import _count, _map_buffers, _map_view, _ptr, _tensor
 
 CONN_KEPT, CONN_TRUNCATED, CONN_BAD_ROW = 1, 2, 4
 COVIS_W_TRUNCATED, COVIS_EMPTY_LIST, COVIS_BAD_ROW, COVIS_LIST_TRUNCATED = 8, 16, 32, 64
@@ -55,14 +55,6 @@ def _cov(cov, dev=None):
     return s, NKFcap, Wcap, dev
 
 
-def _call(ctx, fn, *args):
-    ctx._enter()
-    try:
-        _check(fn(ctx.h, *args))
-    finally:
-        ctx._exit()
-
-
 def _zeros(n, dev):
     import torch
     return torch.zeros(n, dtype=torch.int32, device=dev)
@@ -79,8 +71,8 @@ def covis_update(ctx, map, cov, kf_row, Ccap=256):
     kf_row, Ccap = int(kf_row), int(Ccap)
     assert 0 <= kf_row < v.NKF, "kf_row %d outside [0, %d)" % (kf_row, v.NKF)
     out = dict(conn_kf=_zeros(Ccap, dev), conn_w=_zeros(Ccap, dev), n_conn=_zeros(1, dev), result=_zeros(4, dev))
-    _call(ctx, ctx.lib.gl_covis_update, C.byref(v), C.byref(s), kf_row, Ccap, _ptr(out["conn_kf"]), _ptr(out["conn_w"]), _ptr(out["n_conn"]),
-          _ptr(out["result"]))
+    ctx.call(ctx.lib.gl_covis_update, C.byref(v), C.byref(s), kf_row, Ccap, _ptr(out["conn_kf"]), _ptr(out["conn_w"]), _ptr(out["n_conn"]),
+             _ptr(out["result"]))
     return out
 
 
@@ -103,10 +95,8 @@ def covis_remove(ctx, cov, NKF, cull_rows, n_cull=None, kf_first=-1):
     NKF = int(NKF)
     assert 0 <= NKF <= NKFcap, "NKF %d outside [0, %d]" % (NKF, NKFcap)
     cap = _tensor("cull_rows", cull_rows, "int32", (None,), dev).shape[0]
-    if n_cull is not None:
-        assert n_cull.is_cuda and n_cull.device == dev and str(n_cull.dtype) == "torch.int32" and n_cull.numel() == 1, "n_cull: one int32 on the device"
     result = _zeros(4, dev)
-    _call(ctx, ctx.lib.gl_covis_remove, NKF, C.byref(s), int(kf_first), _ptr(cull_rows) if cap else None, _ptr(n_cull), cap, _ptr(result))
+    ctx.call(ctx.lib.gl_covis_remove, NKF, C.byref(s), int(kf_first), _ptr(cull_rows) if cap else None, _count("n_cull", n_cull, dev), cap, _ptr(result))
     return result
 
 
@@ -120,8 +110,8 @@ def covis_best(ctx, cov, NKF, kf_row, N=0, Ccap=256):
     import torch
     out = dict(conn_kf=torch.zeros((B, Ccap), dtype=torch.int32, device=dev), conn_w=torch.zeros((B, Ccap), dtype=torch.int32, device=dev),
                n_conn=_zeros(B, dev), result=_zeros(4, dev))
-    _call(ctx, ctx.lib.gl_covis_best, NKF, C.byref(s), B, _ptr(kf_row), int(N), Ccap, _ptr(out["conn_kf"]), _ptr(out["conn_w"]), _ptr(out["n_conn"]),
-          _ptr(out["result"]))
+    ctx.call(ctx.lib.gl_covis_best, NKF, C.byref(s), B, _ptr(kf_row), int(N), Ccap, _ptr(out["conn_kf"]), _ptr(out["conn_w"]), _ptr(out["n_conn"]),
+             _ptr(out["result"]))
     return out
 
 
@@ -138,8 +128,8 @@ def fuse_targets(ctx, cov, kf_valid, NKF, kf_row, nn=10, nn2=5, Tcap=None):
     Tcap = nn + nn * nn2 if Tcap is None else int(Tcap)
     buf = _zeros(1 + Tcap, dev)
     out = dict(list=buf, n_tgt=buf[:1], tgt_kf=buf[1:], result=_zeros(4, dev))
-    _call(ctx, ctx.lib.gl_fuse_targets, NKF, C.byref(s), _ptr(kf_valid), int(kf_row), nn, nn2, Tcap, _ptr(out["tgt_kf"]) if Tcap else None,
-          _ptr(out["n_tgt"]), _ptr(out["result"]))
+    ctx.call(ctx.lib.gl_fuse_targets, NKF, C.byref(s), _ptr(kf_valid), int(kf_row), nn, nn2, Tcap, _ptr(out["tgt_kf"]) if Tcap else None,
+             _ptr(out["n_tgt"]), _ptr(out["result"]))
     return out
 
 
@@ -150,11 +140,11 @@ def fuse_candidates(ctx, map, tgt_kf, n_tgt, kf_idx, cand_cap=None):
     -> dict(cand_mp (cand_cap,) i32, n_cand (1,) i32, result (4,) i32 = {count, status, 0, targets outside the table})."""
     v, dev = _map_view(map, False)
     Tcap = _tensor("tgt_kf", tgt_kf, "int32", (None,), dev).shape[0]
-    assert n_tgt.is_cuda and n_tgt.device == dev and str(n_tgt.dtype) == "torch.int32" and n_tgt.numel() == 1, "n_tgt: one int32 on the device"
+    assert _count("n_tgt", n_tgt, dev) is not None, "n_tgt: missing"
     cand_cap = Tcap * v.NFK if cand_cap is None else int(cand_cap)
     out = dict(cand_mp=_zeros(cand_cap, dev), n_cand=_zeros(1, dev), result=_zeros(4, dev))
-    _call(ctx, ctx.lib.gl_fuse_candidates, C.byref(v), _ptr(tgt_kf) if Tcap else None, _ptr(n_tgt), Tcap, int(kf_idx), cand_cap,
-          _ptr(out["cand_mp"]) if cand_cap else None, _ptr(out["n_cand"]), _ptr(out["result"]))
+    ctx.call(ctx.lib.gl_fuse_candidates, C.byref(v), _ptr(tgt_kf) if Tcap else None, _ptr(n_tgt), Tcap, int(kf_idx), cand_cap,
+             _ptr(out["cand_mp"]) if cand_cap else None, _ptr(out["n_cand"]), _ptr(out["result"]))
     return out
 
 
@@ -213,7 +203,7 @@ def search_in_neighbors_from_map(ctx, cam, map, ba, cov, kf_tables, kf_row, kf_i
     A fuse that OBScap refuses (GROW_OBS_TRUNCATED) ends the loop: `status` carries the bit and the steps after it are not run.
     -> dict(sizes, map, ba: after the call; tgt_kf: the list (host); n_fused, n_attached, n_replaced: per fuse, the reverse one last;
     n_cand (host); conn: the dict of covis_update or None; status: the bits of the calls or-ed - the fuses', COVIS_*)."""
-    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = map_grow._buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct"))
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _map_buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct"))
     rk = _tensor("mp_ref_kf", mp_ref_kf, "int32", (NMPcap,), dev)
     kf_row = int(kf_row)
     assert 0 <= kf_row < NKF, "kf_row %d outside [0, %d)" % (kf_row, NKF)

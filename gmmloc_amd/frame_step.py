@@ -6,8 +6,7 @@ nothing is read back."""
 import ctypes as C
 
 from . import _lib
-from .api import _check, _map_ba_view, _map_view, _ptr, _tensor
-from .map_stats import _call, _count
+from ._host import _count, _map_ba_view, _map_view, _outputs, _ptr, _tensor
 
 KF_NEED, KF_INTERRUPT_BA = 1, 2  # GL_KF_*
 FRAME_NEXT_BAD_REF = 1           # GL_FRAME_NEXT_BAD_REF
@@ -30,7 +29,6 @@ def frame_end(ctx, map, ba, chain, lm, feat_depth, th_depth, NL=None, last_obser
     last_observed (B,NL) u8 or None; rule: a gl_kf_rule (kf_rule(...)) or None; map / ba: the dicts of api.map_remove (ba: kf_uvr,
     obs_feat - read with a rule only).  -> dict(held_mp (B,NF) i32, held (B,NF) u8, stat (B,8) i32, ratio_map (B,) f32); out: the dict
     of an earlier call, used again (a lost frame keeps its rows)."""
-    import torch
     v, dev = _map_view(map, False)
     B, NF = _tensor("chain['feat_mp']", chain.get("feat_mp"), "int32", (None, None), dev).shape
     assert NF <= MAX_NF, "NF %d above %d" % (NF, MAX_NF)
@@ -57,14 +55,12 @@ def frame_end(ctx, map, ba, chain, lm, feat_depth, th_depth, NL=None, last_obser
         assert isinstance(rule, _lib.gl_kf_rule), "rule: a gl_kf_rule (frame_step.kf_rule)"
         assert lm.get("ref_kf") is not None, "lm['ref_kf']: missing"
         w = _map_ba_view(ba, v, dev, need=("kf_uvr", "obs_feat"))
-    if out is None:
-        out = dict(held_mp=torch.full((B, NF), -1, dtype=torch.int32, device=dev), held=torch.zeros((B, NF), dtype=torch.uint8, device=dev),
-                   stat=torch.zeros((B, 8), dtype=torch.int32, device=dev), ratio_map=torch.zeros(B, dtype=torch.float32, device=dev))
+    out = _outputs(out, dict(held_mp=("int32", (B, NF), -1), held=("uint8", (B, NF), 0), stat=("int32", (B, 8), 0), ratio_map=("float32", (B,), 0)), dev)
     o = _lib.gl_frame_end_out()
-    for k, dt, sh in (("held_mp", "int32", (B, NF)), ("held", "uint8", (B, NF)), ("stat", "int32", (B, 8)), ("ratio_map", "float32", (B,))):
-        setattr(o, k, _ptr(_tensor("out[%r]" % k, out.get(k), dt, sh, dev)))
-    _call(ctx, ctx.lib.gl_track_frame_end, C.byref(v), C.byref(w) if w is not None else None, B, NF, NL, NPcap, C.byref(i), float(th_depth),
-          C.byref(rule) if rule is not None else None, C.byref(o))
+    for k in ("held_mp", "held", "stat", "ratio_map"):
+        setattr(o, k, _ptr(out[k]))
+    ctx.call(ctx.lib.gl_track_frame_end, C.byref(v), C.byref(w) if w is not None else None, B, NF, NL, NPcap, C.byref(i), float(th_depth),
+             C.byref(rule) if rule is not None else None, C.byref(o))
     return out
 
 
@@ -77,7 +73,7 @@ def note_replaced(ctx, mp_replaced, repl_src, repl_tgt, n=None, n_dev=None):
     _tensor("repl_tgt", repl_tgt, "int32", (cap,), dev)
     n = cap if n is None else int(n)
     assert 0 <= n <= cap, "n %d outside [0, %d]" % (n, cap)
-    _call(ctx, ctx.lib.gl_map_note_replaced, NMPcap, _ptr(mp_replaced), _ptr(repl_src), _ptr(repl_tgt), n, _count("n_dev", n_dev, dev))
+    ctx.call(ctx.lib.gl_map_note_replaced, NMPcap, _ptr(mp_replaced), _ptr(repl_src), _ptr(repl_tgt), n, _count("n_dev", n_dev, dev))
 
 
 def frame_next(ctx, map, ba, pose_tracked, pose_prev, ref_kf, held_mp, feat_new=None, mp_base=0, mp_replaced=None, want_desc=False, out=None):
@@ -86,7 +82,6 @@ def frame_next(ctx, map, ba, pose_tracked, pose_prev, ref_kf, held_mp, feat_new=
     i32 or None; map: obs_ptr, obs_kf, kf_mp, mp_pos (+ mp_desc with want_desc); ba: kf_pose.  -> dict(t_rc, t_cr, pose_lw, pose_cw
     (B,7) f64, held_mp (the tensor passed in), last_pt (B,NF,3) f64, last_valid / last_observed / held (B,NF) u8, status (B,) i32[,
     last_desc (B,NF,32) u8: the rows' map-point descriptors, zeros elsewhere]); out: the dict of an earlier call, used again."""
-    import torch
     v, dev = _map_view(map, False)
     assert v.NMP == 0 or map.get("mp_pos") is not None, "map['mp_pos']: missing"
     w = _map_ba_view(ba, v, dev, need=("kf_pose",))
@@ -104,25 +99,18 @@ def frame_next(ctx, map, ba, pose_tracked, pose_prev, ref_kf, held_mp, feat_new=
         i.NMPcap = _tensor("mp_replaced", mp_replaced, "int32", (None,), dev).shape[0]
         assert i.NMPcap >= v.NMP, "mp_replaced has %d rows, the map %d" % (i.NMPcap, v.NMP)
         i.mp_replaced = _ptr(mp_replaced)
-    if out is None:
-        f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
-        u8 = lambda *s: torch.zeros(s, dtype=torch.uint8, device=dev)
-        out = dict(t_rc=f64(B, 7), t_cr=f64(B, 7), pose_lw=f64(B, 7), pose_cw=f64(B, 7), last_pt=f64(B, NF, 3), last_valid=u8(B, NF),
-                   last_observed=u8(B, NF), held=u8(B, NF), status=torch.zeros(B, dtype=torch.int32, device=dev))
-        if want_desc:
-            out["last_desc"] = u8(B, NF, 32)
-    out["held_mp"] = held_mp
-    o = _lib.gl_frame_next_out()
-    shapes = {"t_rc": ("float64", (B, 7)), "t_cr": ("float64", (B, 7)), "pose_lw": ("float64", (B, 7)), "pose_cw": ("float64", (B, 7)),
-              "held_mp": ("int32", (B, NF)), "last_pt": ("float64", (B, NF, 3)), "last_valid": ("uint8", (B, NF)), "last_observed": ("uint8", (B, NF)),
-              "held": ("uint8", (B, NF)), "status": ("int32", (B,)), "last_desc": ("uint8", (B, NF, 32))}
-    for k, (dt, sh) in shapes.items():
-        if k == "last_desc" and out.get(k) is None:
-            continue
-        setattr(o, k, _ptr(_tensor("out[%r]" % k, out.get(k), dt, sh, dev)))
-    if out.get("last_desc") is not None:
+    spec = {k: ("float64", (B, 7), 0) for k in ("t_rc", "t_cr", "pose_lw", "pose_cw")}
+    spec.update(last_pt=("float64", (B, NF, 3), 0), last_valid=("uint8", (B, NF), 0), last_observed=("uint8", (B, NF), 0), held=("uint8", (B, NF), 0),
+                status=("int32", (B,), 0))
+    if want_desc if out is None else out.get("last_desc") is not None:  # (optional: an `out` without it gets none)
         assert v.NMP == 0 or map.get("mp_desc") is not None, "map['mp_desc']: missing"
-    _call(ctx, ctx.lib.gl_track_frame_next, C.byref(v), C.byref(w), B, NF, C.byref(i), C.byref(o))
+        spec["last_desc"] = ("uint8", (B, NF, 32), 0)
+    out = _outputs(out, spec, dev)
+    out["held_mp"] = held_mp  # (the caller's tensor, checked above)
+    o = _lib.gl_frame_next_out()
+    for k in (*spec, "held_mp"):
+        setattr(o, k, _ptr(out[k]))
+    ctx.call(ctx.lib.gl_track_frame_next, C.byref(v), C.byref(w), B, NF, C.byref(i), C.byref(o))
     return out
 
 

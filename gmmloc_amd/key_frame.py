@@ -6,7 +6,7 @@ tests/test_gpu_key_frame_create_context.py."""
 import ctypes as C
 
 from . import _lib
-from .api import _check, _ptr, _tensor
+from ._host import _outputs, _ptr, _tensor
 
 STEREO_WALK_MAX = 4096  # GL_STEREO_WALK_MAX
 STEREO_IN_DTYPES = {"pose": "float64", "feat_uv": "float64", "feat_ur": "float32", "feat_depth": "float32", "feat_oct": "int32", "cand": "int32",
@@ -29,7 +29,6 @@ def create_stereo_points(ctx, gmm, cam, prm, kf, mp_base, check_depth, th_depth,
     -> dict of CUDA tensors: new_feat / new_assoc / new_ref_kf / att_mp / att_kf / att_feat (B,NF) i32 and new_pos (B,NF,3) f64, of
     which the first n_new[b] of row b are written (the rest is zero); n_new (B,) i32; feat_new (B,NF) i32; stats (B,8) i32[; pts0
     (B,NF,3) f64].  out: such a dict to write into instead of a fresh one.  Nothing is read back."""
-    import torch
     for key in kf:
         assert key in STEREO_IN_DTYPES, "kf[%r]: unknown key" % key
     dev = _tensor("kf['feat_oct']", kf.get("feat_oct"), "int32", (None, None), None).device
@@ -39,24 +38,16 @@ def create_stereo_points(ctx, gmm, cam, prm, kf, mp_base, check_depth, th_depth,
     i = _lib.gl_stereo_points_in()
     for key, dt in STEREO_IN_DTYPES.items():
         setattr(i, key, _ptr(_tensor("kf[%r]" % key, kf.get(key), dt, shapes[key], dev)))
-    z = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)
-    if out is None:
-        r = dict(new_feat=z(B, NF), new_pos=torch.zeros((B, NF, 3), dtype=torch.float64, device=dev), new_assoc=z(B, NF), new_ref_kf=z(B, NF),
-                 att_mp=z(B, NF), att_kf=z(B, NF), att_feat=z(B, NF), n_new=z(B), feat_new=z(B, NF), stats=z(B, 8))
-        if want_pts0:
-            r["pts0"] = torch.zeros((B, NF, 3), dtype=torch.float64, device=dev)
-    else:
-        r = out
+    spec = {key: ("int32", (B, NF), 0) for key in ("new_feat", "new_assoc", "new_ref_kf", "att_mp", "att_kf", "att_feat", "feat_new")}
+    spec.update(new_pos=("float64", (B, NF, 3), 0), n_new=("int32", (B,), 0), stats=("int32", (B, 8), 0))
+    if want_pts0 if out is None else out.get("pts0") is not None:
+        spec["pts0"] = ("float64", (B, NF, 3), 0)
+    r = _outputs(out, spec, dev)
     o = _lib.gl_stereo_points_out()
-    for key, t in r.items():
-        shape = (B, NF, 3) if key in ("new_pos", "pts0") else (B,) if key == "n_new" else (B, 8) if key == "stats" else (B, NF)
-        setattr(o, key, _ptr(_tensor("out[%r]" % key, t, "float64" if key in ("new_pos", "pts0") else "int32", shape, dev)))
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_create_stereo_points(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, NF, k, C.byref(i), int(mp_base),
-                                               int(bool(check_depth)), float(th_depth), C.byref(o)))
-    finally:
-        ctx._exit()
+    for key in spec:
+        setattr(o, key, _ptr(r[key]))
+    ctx.call(ctx.lib.gl_create_stereo_points, gmm.h, C.byref(cam.c()), C.byref(prm.c()), B, NF, k, C.byref(i), int(mp_base), int(bool(check_depth)),
+             float(th_depth), C.byref(o))
     return r
 
 
@@ -86,9 +77,5 @@ def create_temporal_points(ctx, cam, fr, last, th_depth, last_mp=None):
         setattr(o, key, _ptr(t))
     if last_mp is not None:
         o.last_mp = _ptr(_tensor("last_mp", last_mp, "int32", (B, NF), dev))
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_create_temporal_points(ctx.h, C.byref(cam.c()), B, NF, C.byref(i), float(th_depth), C.byref(o)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_create_temporal_points, C.byref(cam.c()), B, NF, C.byref(i), float(th_depth), C.byref(o))
     return r

@@ -2,77 +2,26 @@
 gl_map_fuse (the second half of fuseObservations with Map::replaceMapPoint); rules in include/gmmloc_hip.h.
 
 The arrays keep their allocation and the counts grow.  `map` / `ba` are the dicts of api.map_remove whose tensors are the CAPACITY
-buffers - the per-point arrays NMPcap rows (obs_ptr NMPcap + 1), obs_kf / obs_feat OBScap entries, the key-frame tables at least NKF
-rows - and `sizes` = (NMP, NKF, NOBS) says how much of them the map fills (None: all of it).  Every call returns the new sizes and
+buffers - each table's leading dimension at its capacity instead of its extent (_host.MAP_TABLES: NMPcap for NMP, OBScap for NOBS, at
+least NKF key-frame rows) - and `sizes` = (NMP, NKF, NOBS) says how much of them the map fills (None: all of it).  Every call returns the new sizes and
 `map` / `ba` cut to them (views of the same tensors): what the readers (api.update_connections, api.ba_window_build, ...) take."""
 import ctypes as C
 
 from . import _lib
-from .api import MAP_BA_DTYPES, MAP_VIEW_DTYPES, _check, _ptr, _tensor, fuse_search, project_map_points
+from ._host import MAP_TABLES, _count, _extents, _map_ba_view, _map_buffers, _map_edit, _map_view, _ptr, _tensor
+from .api import fuse_search, project_map_points
 
 GROW_OBS_TRUNCATED, GROW_MP_TRUNCATED, FUSE_REPL_TRUNCATED, ADD_ALREADY_TRUNCATED = 1, 2, 4, 8
-_PER_POINT = ("mp_valid", "mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc", "mp_assoc")
-_PER_KF = ("kf_valid", "kf_mp", "kf_pose", "kf_twc", "kf_uvr", "kf_oct")
-_PER_OBS = ("obs_kf", "obs_feat")
-_TRAIL = {"mp_pos": (3,), "mp_normal": (3,), "mp_desc": (32,), "kf_pose": (7,), "kf_twc": (3,)}
+_PER_POINT = tuple(k for k, t in MAP_TABLES.items() if t.lead == "NMP" and t.where)  # the tables of NMPcap rows in `map` / `ba`: what a test pads
 
 
 def map_views(map, ba, sizes):
-    """the two dicts cut to sizes = (NMP, NKF, NOBS): views of the same tensors, the dicts the readers of the resident map take"""
+    """the two dicts cut to sizes = (NMP, NKF, NOBS): views of the same tensors, the dicts the readers of the resident map take - each
+    table's leading dimension cut to the extent it follows (_host.MAP_TABLES), anything else as it is"""
     NMP, NKF, NOBS = sizes
-    def cut(k, t):
-        if t is None or not hasattr(t, "shape"):
-            return t
-        n = NMP + 1 if k == "obs_ptr" else NMP if k in _PER_POINT else NKF if k in _PER_KF else NOBS if k in _PER_OBS else None
-        return t if n is None else t[:n]
+    ext = _extents(NMP, NKF, None, NOBS)
+    cut = lambda k, t: t[:ext[MAP_TABLES[k].lead]] if k in MAP_TABLES and hasattr(t, "shape") else t
     return {k: cut(k, t) for k, t in map.items()}, {k: cut(k, t) for k, t in ba.items()}
-
-
-def _buffers(map, ba, sizes, need_ba):
-    """check every tensor of the two dicts against the capacities and `sizes` -> (NMP, NKF, NFK, NOBS, NMPcap, OBScap, device)"""
-    for k in map:
-        assert k in MAP_VIEW_DTYPES, "map[%r]: unknown key" % k
-    for k in ba:
-        assert k in MAP_BA_DTYPES or k == "kf_first", "ba[%r]: unknown key" % k
-    dev = _tensor("map['obs_ptr']", map.get("obs_ptr"), "int32", (None,), None).device
-    NMPcap = map["obs_ptr"].shape[0] - 1
-    assert NMPcap >= 0, "map['obs_ptr']: needs NMPcap + 1 entries"
-    OBScap = _tensor("map['obs_kf']", map.get("obs_kf"), "int32", (None,), dev).shape[0]
-    KFcap, NFK = _tensor("map['kf_mp']", map.get("kf_mp"), "int32", (None, None), dev).shape
-    NMP, NKF, NOBS = (NMPcap, KFcap, OBScap) if sizes is None else (int(v) for v in sizes)
-    assert 0 <= NMP <= NMPcap and 0 <= NKF <= KFcap and 0 <= NOBS <= OBScap, \
-        "sizes %s outside the buffers (NMPcap %d, key-frame rows %d, OBScap %d)" % ((NMP, NKF, NOBS), NMPcap, KFcap, OBScap)
-    assert map.get("mp_valid") is not None and map.get("kf_valid") is not None, "mp_valid and kf_valid are written, both are needed"
-    _tensor("map['mp_valid']", map["mp_valid"], "uint8", (NMPcap,), dev)
-    _tensor("map['kf_valid']", map["kf_valid"], "uint8", (KFcap,), dev)
-    _tensor("ba['obs_feat']", ba.get("obs_feat"), "int32", (OBScap,), dev)
-    for d, name, dtypes in ((map, "map", MAP_VIEW_DTYPES), (ba, "ba", MAP_BA_DTYPES)):
-        for k, t in d.items():
-            if t is None or k == "kf_first" or k in ("obs_ptr", "obs_kf", "kf_mp", "mp_valid", "kf_valid", "obs_feat"):
-                continue
-            lead = NMPcap if k in _PER_POINT else KFcap
-            shape = (lead, NFK, 3) if k == "kf_uvr" else (lead, NFK) if k == "kf_oct" else (lead,) + _TRAIL.get(k, ())
-            _tensor("%s[%r]" % (name, k), t, dtypes[k], shape, dev)
-    for k in need_ba:
-        assert ba.get(k) is not None, "ba[%r]: missing" % k
-    return NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev
-
-
-def _edit(map, ba, mp_ref_kf, NMPcap, dev):
-    ed = _lib.gl_map_edit()
-    for k in ("mp_valid", "kf_valid", "kf_mp", "obs_ptr", "obs_kf"):
-        setattr(ed, k, _ptr(map[k]))
-    ed.obs_feat = _ptr(ba["obs_feat"])
-    if mp_ref_kf is not None:
-        ed.mp_ref_kf = _ptr(_tensor("mp_ref_kf", mp_ref_kf, "int32", (NMPcap,), dev))
-    return ed
-
-
-def _count(name, n, dev):
-    if n is None:
-        return None
-    assert n.is_cuda and n.device == dev and str(n.dtype) == "torch.int32" and n.numel() == 1, "n_%s: one int32 on the device" % name
-    return _ptr(n)
 
 
 def map_add(ctx, map, ba, sizes=None, new_mp=None, new_kf=None, attach=None, walk_kf=None, mp_ref_kf=None, n_new_mp=None, n_new_kf=None,
@@ -86,8 +35,8 @@ def map_add(ctx, map, ba, sizes=None, new_mp=None, new_kf=None, attach=None, wal
     NOBS,) i32: all -1 after a truncation]).  One 24-byte copy and one synchronise."""
     import torch
     need = ("mp_assoc",) if new_mp is not None else ()
-    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _buffers(map, ba, sizes, need)
-    ed = _edit(map, ba, mp_ref_kf, NMPcap, dev)
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _map_buffers(map, ba, sizes, need)
+    ed = _map_edit(map, ba, mp_ref_kf, NMPcap, dev)
     ls = _lib.gl_map_add_lists()
     if new_mp is not None:
         for k in new_mp:
@@ -98,12 +47,12 @@ def map_add(ctx, map, ba, sizes=None, new_mp=None, new_kf=None, attach=None, wal
         ls.new_assoc = _ptr(_tensor("new_mp['assoc']", new_mp.get("assoc"), "int32", (n,), dev))
         if mp_ref_kf is not None or new_mp.get("ref_kf") is not None:
             ls.new_ref_kf = _ptr(_tensor("new_mp['ref_kf']", new_mp.get("ref_kf"), "int32", (n,), dev))
-        ls.n_new_mp = _count("new_mp", n_new_mp, dev)
+        ls.n_new_mp = _count("n_new_mp", n_new_mp, dev)
     else:
         assert n_new_mp is None, "n_new_mp without new_mp"
     if new_kf is not None:
         ls.new_kf, ls.new_kf_cap = _ptr(_tensor("new_kf", new_kf, "int32", (None,), dev)), new_kf.shape[0]
-        ls.n_new_kf = _count("new_kf", n_new_kf, dev)
+        ls.n_new_kf = _count("n_new_kf", n_new_kf, dev)
     else:
         assert n_new_kf is None, "n_new_kf without new_kf"
     if attach is not None:
@@ -113,12 +62,12 @@ def map_add(ctx, map, ba, sizes=None, new_mp=None, new_kf=None, attach=None, wal
         ls.att_mp, ls.attach_cap = _ptr(attach["mp"]), n
         ls.att_kf = _ptr(_tensor("attach['kf']", attach.get("kf"), "int32", (n,), dev))
         ls.att_feat = _ptr(_tensor("attach['feat']", attach.get("feat"), "int32", (n,), dev))
-        ls.n_attach = _count("attach", n_attach, dev)
+        ls.n_attach = _count("n_attach", n_attach, dev)
     else:
         assert n_attach is None, "n_attach without attach"
     if walk_kf is not None:
         ls.walk_kf, ls.walk_cap = _ptr(_tensor("walk_kf", walk_kf, "int32", (None,), dev)), walk_kf.shape[0]
-        ls.n_walk = _count("walk", n_walk, dev)
+        ls.n_walk = _count("n_walk", n_walk, dev)
     else:
         assert n_walk is None, "n_walk without walk_kf"
     already_cap = ls.walk_cap * NFK if already_cap is None else int(already_cap)
@@ -127,12 +76,8 @@ def map_add(ctx, map, ba, sizes=None, new_mp=None, new_kf=None, attach=None, wal
     new_pos = torch.zeros(NOBS, dtype=torch.int32, device=dev) if want_new_pos else None
     o = _lib.gl_map_add_out()
     o.result, o.already_mp, o.obs_new_pos, o.already_cap = _ptr(result), (_ptr(already) if already_cap else None), _ptr(new_pos), already_cap
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_map_add(ctx.h, NMP, NKF, NFK, NOBS, NMPcap, OBScap, C.byref(ed), _ptr(map.get("mp_pos")), _ptr(ba.get("mp_assoc")),
-                                  C.byref(ls), C.byref(o)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_map_add, NMP, NKF, NFK, NOBS, NMPcap, OBScap, C.byref(ed), _ptr(map.get("mp_pos")), _ptr(ba.get("mp_assoc")), C.byref(ls),
+             C.byref(o))
     nmp, nobs, n_att, n_skip, n_already, status = result.tolist()  # the one round trip
     cut = status & (GROW_OBS_TRUNCATED | GROW_MP_TRUNCATED)
     now = (NMP, NKF, NOBS) if cut else (nmp, NKF, nobs)
@@ -152,8 +97,8 @@ def map_fuse(ctx, map, ba, kf_row, cand_mp, best_idx, sizes=None, repl_cap=None,
     NOBS,) i32: -1 for an entry that is gone]).  After a truncation `needed` holds NOBS + n as its third size: the UPPER BOUND the call
     checks before it runs (every candidate may attach), not the size the edit would produce.  One 20-byte copy and one synchronise."""
     import torch
-    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _buffers(map, ba, sizes, ("kf_uvr",))
-    ed = _edit(map, ba, None, NMPcap, dev)
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _map_buffers(map, ba, sizes, ("kf_uvr",))
+    ed = _map_edit(map, ba, None, NMPcap, dev)
     kf_row = int(kf_row)
     assert 0 <= kf_row < NKF, "kf_row %d outside [0, %d)" % (kf_row, NKF)
     n = _tensor("cand_mp", cand_mp, "int32", (None,), dev).shape[0]
@@ -166,12 +111,7 @@ def map_fuse(ctx, map, ba, kf_row, cand_mp, best_idx, sizes=None, repl_cap=None,
     o = _lib.gl_map_fuse_out()
     o.result, o.obs_new_pos, o.repl_cap = _ptr(result), _ptr(new_pos), repl_cap
     o.repl_src, o.repl_tgt = (_ptr(src), _ptr(tgt)) if repl_cap else (None, None)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_map_fuse(ctx.h, NMP, NKF, NFK, NOBS, OBScap, C.byref(ed), _ptr(ba["kf_uvr"]), kf_row, n, _ptr(cand_mp), _ptr(best_idx),
-                                   C.byref(o)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_map_fuse, NMP, NKF, NFK, NOBS, OBScap, C.byref(ed), _ptr(ba["kf_uvr"]), kf_row, n, _ptr(cand_mp), _ptr(best_idx), C.byref(o))
     nobs, n_fused, n_att, n_repl, status = result.tolist()  # the one round trip
     now = (NMP, NKF, NOBS) if status & GROW_OBS_TRUNCATED else (NMP, NKF, nobs)
     m2, b2 = map_views(map, ba, now)
@@ -190,7 +130,7 @@ def fuse_observations_from_map(ctx, cam, map, ba, kf_tables, kf_row, cand_mp, th
     (key-frame rows, NFK, 32) u8).  cand_mp (n,) i32.  -> the dict of map_fuse + best_idx, best_dist (n,) i32.  A candidate that already
     observes kf_row is matched like any other and dropped by map_fuse's own test (:237)."""
     import torch
-    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct"))
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _map_buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct"))
     for k in ("mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc"):
         assert map.get(k) is not None, "map[%r]: missing" % k
     desc = _tensor("kf_tables['desc']", kf_tables.get("desc"), "uint8", (map["kf_mp"].shape[0], NFK, 32), dev)
@@ -224,7 +164,7 @@ def process_key_frame_from_map(ctx, gmm, cam, prm, map, ba, kf_tables, kf_row, f
     tensors) and n_new.  After a truncation by map_add nothing is changed and nothing refreshed (n_new: what the walk made)."""
     from .api import create_stereo_points, update_map_points
     import torch
-    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct", "mp_assoc"))
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _map_buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct", "mp_assoc"))
     for key in ("mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc"):
         assert map.get(key) is not None, "map[%r]: missing" % key
     desc = _tensor("kf_tables['desc']", kf_tables.get("desc"), "uint8", (map["kf_mp"].shape[0], NFK, 32), dev)
@@ -286,9 +226,8 @@ def _kf_tables(kf_tables, rows, NFK, dev):
 
 
 def _conn(conn_kf, n_conn, dev):
-    _tensor("conn_kf", conn_kf, "int32", (None,), dev)
-    assert n_conn.is_cuda and n_conn.device == dev and str(n_conn.dtype) == "torch.int32" and n_conn.numel() == 1, "n_conn: one int32 on the device"
-    return conn_kf.shape[0]
+    assert _count("n_conn", n_conn, dev) is not None, "n_conn: missing"
+    return _tensor("conn_kf", conn_kf, "int32", (None,), dev).shape[0]
 
 
 def tri_pair_setup(ctx, cam, ba, kf_valid, kf_row, conn_kf, n_conn, first_nb=0, n_nb=None, mb=None):
@@ -307,13 +246,8 @@ def tri_pair_setup(ctx, cam, ba, kf_valid, kf_row, conn_kf, n_conn, first_nb=0, 
     skip = torch.zeros(n_nb, dtype=torch.int32, device=dev)
     fmat = torch.zeros((n_nb, 9), dtype=torch.float64, device=dev)
     epi = torch.zeros((n_nb, 2), dtype=torch.float32, device=dev)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_tri_pair_setup(ctx.h, C.byref(cam.c()), NKF, _ptr(kf_valid), _ptr(ba["kf_pose"]), _ptr(ba["kf_twc"]), int(kf_row),
-                                         _ptr(conn_kf), _ptr(n_conn), cap, int(first_nb), n_nb, default_mb(cam) if mb is None else float(mb),
-                                         _ptr(skip), _ptr(fmat), _ptr(epi)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_tri_pair_setup, C.byref(cam.c()), NKF, _ptr(kf_valid), _ptr(ba["kf_pose"]), _ptr(ba["kf_twc"]), int(kf_row), _ptr(conn_kf),
+             _ptr(n_conn), cap, int(first_nb), n_nb, default_mb(cam) if mb is None else float(mb), _ptr(skip), _ptr(fmat), _ptr(epi))
     return skip, fmat, epi
 
 
@@ -335,7 +269,6 @@ def create_map_points_on_map(ctx, gmm, cam, prm, map, ba, kf_tables, kf_row, con
     api.ba_window_build cut to the map's sizes (kf_valid, kf_mp; kf_pose, kf_twc, kf_uvr, kf_oct); kf_tables: dict of KF_TABLE_DTYPES'
     keys, one row per key-frame row of map['kf_mp'].  mp_base: the row the first new point will take (default: the map's NMP).
     -> the dict of tri_points_out (device tensors; the lists are valid up to n_new / n_attach)."""
-    from .api import _map_ba_view, _map_view
     v, dev = _map_view(map, False)
     w = _map_ba_view(ba, v, dev, need=("kf_pose", "kf_twc", "kf_uvr", "kf_oct"))
     assert ba.get("kf_twc") is not None, "ba['kf_twc']: missing"
@@ -357,14 +290,9 @@ def create_map_points_on_map(ctx, gmm, cam, prm, map, ba, kf_tables, kf_row, con
         assert out[key].shape[0] == o.new_cap, "out[%r]: %d rows, new_pos has %d" % (key, out[key].shape[0], o.new_cap)
     for key in ("att_mp", "att_kf", "att_feat"):
         assert out[key].shape[0] == 2 * o.new_cap, "out[%r]: needs 2 x %d entries" % (key, o.new_cap)
-    ctx._enter()
-    try:
-        _check(ctx.lib.gl_create_map_points_from_map(ctx.h, gmm.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), C.byref(v), C.byref(w),
-                                                     C.byref(t), int(kf_row), _ptr(conn_kf), _ptr(n_conn), cap, int(first_nb), n_nb,
-                                                     default_mb(cam) if mb is None else float(mb), v.NMP if mp_base is None else int(mp_base),
-                                                     C.byref(o)))
-    finally:
-        ctx._exit()
+    ctx.call(ctx.lib.gl_create_map_points_from_map, gmm.h, C.byref(cam.c()), C.byref(prm.c()), float(scale_factor), C.byref(v), C.byref(w),
+             C.byref(t), int(kf_row), _ptr(conn_kf), _ptr(n_conn), cap, int(first_nb), n_nb, default_mb(cam) if mb is None else float(mb),
+             v.NMP if mp_base is None else int(mp_base), C.byref(o))
     return out
 
 
@@ -381,7 +309,7 @@ def create_map_points_from_map(ctx, gmm, cam, prm, map, ba, kf_tables, kf_row, n
     and nothing refreshed (n_new: what the loop made)."""
     from .api import update_connections, update_map_points
     import torch
-    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct", "mp_assoc"))
+    NMP, NKF, NFK, NOBS, NMPcap, OBScap, dev = _map_buffers(map, ba, sizes, ("kf_pose", "kf_twc", "kf_uvr", "kf_oct", "mp_assoc"))
     for key in ("mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc"):
         assert map.get(key) is not None, "map[%r]: missing" % key
     rk = _tensor("mp_ref_kf", mp_ref_kf, "int32", (NMPcap,), dev)

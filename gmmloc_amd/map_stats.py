@@ -7,7 +7,7 @@ Every wrapper only enqueues: what it returns are device tensors, nothing is read
 import ctypes as C
 
 from . import _lib
-from .api import _check, _map_ba_view, _map_view, _ptr, _tensor
+from ._host import _count, _map_ba_view, _map_edit, _map_view, _outputs, _ptr, _tensor
 
 STATS_MP_TRUNCATED, STATS_CAND_TRUNCATED, STATS_BAD_ROW = 1, 2, 4
 VERDICT_KEPT, VERDICT_INVALID, VERDICT_RATIO, VERDICT_YOUNG_FEW, VERDICT_AGED, VERDICT_BAD_ROW = 0, 1, 2, 3, 4, 5
@@ -39,21 +39,6 @@ def _stats(stats, dev=None):
     return s, NMPcap, dev
 
 
-def _count(name, n, dev):
-    if n is None:
-        return None
-    assert n.is_cuda and n.device == dev and str(n.dtype) == "torch.int32" and n.numel() == 1, "%s: one int32 on the device" % name
-    return _ptr(n)
-
-
-def _call(ctx, fn, *args):
-    ctx._enter()
-    try:
-        _check(fn(ctx.h, *args))
-    finally:
-        ctx._exit()
-
-
 def map_stats_track(ctx, stats, NMP, feat_mp, match_local, outlier, inview, local_mp, n_local_mp, counts2=None):
     """gl_map_stats_track: the tracker's three rules for B frames on the chain's outputs - feat_mp / match_local (B,NF) i32, outlier
     (B,NF) u8, inview (B,NPcap) u8, local_mp (B,NPcap) i32, n_local_mp (B,) i32, counts2 (B,4) i32 or None (every frame tracked).
@@ -69,8 +54,8 @@ def map_stats_track(ctx, stats, NMP, feat_mp, match_local, outlier, inview, loca
     _tensor("n_local_mp", n_local_mp, "int32", (B,), dev)
     if counts2 is not None:
         _tensor("counts2", counts2, "int32", (B, 4), dev)
-    _call(ctx, ctx.lib.gl_map_stats_track, NMP, C.byref(s), B, NF, NPcap, _ptr(feat_mp), _ptr(match_local), _ptr(outlier), _ptr(inview),
-          _ptr(local_mp), _ptr(n_local_mp), _ptr(counts2))
+    ctx.call(ctx.lib.gl_map_stats_track, NMP, C.byref(s), B, NF, NPcap, _ptr(feat_mp), _ptr(match_local), _ptr(outlier), _ptr(inview),
+             _ptr(local_mp), _ptr(n_local_mp), _ptr(counts2))
 
 
 def map_stats_new_points(ctx, stats, NKF, first, new_ref_kf, n=None, n_dev=None):
@@ -84,7 +69,7 @@ def map_stats_new_points(ctx, stats, NKF, first, new_ref_kf, n=None, n_dev=None)
     if stats.get("kf_idx") is not None:
         assert stats["kf_idx"].shape[0] >= int(NKF), "stats['kf_idx']: fewer than NKF rows"
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _call(ctx, ctx.lib.gl_map_stats_new_points, NMPcap, int(NKF), C.byref(s), int(first), n, _count("n_dev", n_dev, dev), _ptr(new_ref_kf), _ptr(status))
+    ctx.call(ctx.lib.gl_map_stats_new_points, NMPcap, int(NKF), C.byref(s), int(first), n, _count("n_dev", n_dev, dev), _ptr(new_ref_kf), _ptr(status))
     return status
 
 
@@ -101,7 +86,7 @@ def map_cand_append(ctx, stats, rows=None, n_dev=None, first=0, n=None):
     else:
         assert n is not None, "a row range needs n"
     result = torch.zeros(2, dtype=torch.int32, device=dev)
-    _call(ctx, ctx.lib.gl_map_cand_append, C.byref(s), _ptr(rows), int(first), int(n), _count("n_dev", n_dev, dev), _ptr(result))
+    ctx.call(ctx.lib.gl_map_cand_append, C.byref(s), _ptr(rows), int(first), int(n), _count("n_dev", n_dev, dev), _ptr(result))
     return result
 
 
@@ -115,7 +100,7 @@ def map_stats_merge(ctx, stats, NMP, repl_src, repl_tgt, n=None, n_dev=None):
     _tensor("repl_tgt", repl_tgt, "int32", (cap,), dev)
     n = cap if n is None else int(n)
     assert 0 <= n <= cap, "n %d outside [0, %d]" % (n, cap)
-    _call(ctx, ctx.lib.gl_map_stats_merge, NMP, C.byref(s), _ptr(repl_src), _ptr(repl_tgt), n, _count("n_dev", n_dev, dev))
+    ctx.call(ctx.lib.gl_map_stats_merge, NMP, C.byref(s), _ptr(repl_src), _ptr(repl_tgt), n, _count("n_dev", n_dev, dev))
 
 
 def cull_map_points(ctx, map, ba, stats, kf_row, out=None):
@@ -123,7 +108,6 @@ def cull_map_points(ctx, map, ba, stats, kf_row, out=None):
     api.map_remove cut to the map's sizes (mp_valid, kf_mp, obs_ptr, obs_kf; kf_uvr, obs_feat).  stats['cand'] / ['n_cand'] are compacted
     IN PLACE.  -> dict(rm_mp (cand_cap,) i32, n_rm (1,) i32: rm_mp / n_rm_mp of api.map_remove; verdict (cand_cap,) i32: the old entries;
     result (4,) i32 = {kept, removed, erased without removal, status}), device tensors.  out: the dict of an earlier call, used again."""
-    import torch
     v, dev = _map_view(map, False)
     _map_ba_view(ba, v, dev, need=("kf_uvr", "obs_feat"))
     assert map.get("mp_valid") is not None, "map['mp_valid']: missing"
@@ -133,18 +117,11 @@ def cull_map_points(ctx, map, ba, stats, kf_row, out=None):
         assert stats["kf_idx"].shape[0] >= v.NKF, "stats['kf_idx']: fewer than NKF rows"
     kf_row = int(kf_row)
     assert 0 <= kf_row < v.NKF, "kf_row %d outside [0, %d)" % (kf_row, v.NKF)
-    ed = _lib.gl_map_edit()
-    for k in ("mp_valid", "kf_valid", "kf_mp", "obs_ptr", "obs_kf"):
-        setattr(ed, k, _ptr(map[k]) if map.get(k) is not None else None)
-    ed.obs_feat = _ptr(ba["obs_feat"])
+    ed = _map_edit(map, ba, None, v.NMP, dev)  # (kf_valid may be missing: all valid)
     cap = s.cand_cap
-    if out is None:
-        out = dict(rm_mp=torch.zeros(cap, dtype=torch.int32, device=dev), n_rm=torch.zeros(1, dtype=torch.int32, device=dev),
-                   verdict=torch.zeros(cap, dtype=torch.int32, device=dev), result=torch.zeros(4, dtype=torch.int32, device=dev))
-    for k, n in (("rm_mp", cap), ("n_rm", 1), ("verdict", cap), ("result", 4)):
-        _tensor("out[%r]" % k, out.get(k), "int32", (n,), dev)
-    _call(ctx, ctx.lib.gl_cull_map_points, v.NMP, v.NKF, v.NFK, v.NOBS, C.byref(ed), _ptr(ba["kf_uvr"]), C.byref(s), kf_row,
-          _ptr(out["rm_mp"]) if cap else None, _ptr(out["n_rm"]), _ptr(out["verdict"]) if cap else None, _ptr(out["result"]))
+    out = _outputs(out, {k: ("int32", (n,), 0) for k, n in (("rm_mp", cap), ("n_rm", 1), ("verdict", cap), ("result", 4))}, dev)
+    ctx.call(ctx.lib.gl_cull_map_points, v.NMP, v.NKF, v.NFK, v.NOBS, C.byref(ed), _ptr(ba["kf_uvr"]), C.byref(s), kf_row,
+             _ptr(out["rm_mp"]) if cap else None, _ptr(out["n_rm"]), _ptr(out["verdict"]) if cap else None, _ptr(out["result"]))
     return out
 
 

@@ -36,11 +36,7 @@ def dev_map(torch, m):
 
 def _finish(torch, ctx, fn, out):
     def call(torch, ctx):
-        ctx._enter()
-        try:
-            api._check(fn())
-        finally:
-            ctx._exit()
+        ctx.call(lambda _h: fn())
         torch.cuda.synchronize()
     run(call, torch, ctx)
     out.check()

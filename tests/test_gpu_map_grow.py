@@ -387,7 +387,7 @@ def test_arguments(gpu):
         map_grow.map_fuse(ctx, md, bd, sizes[1], z(1), z(1), sizes=sizes)
     with pytest.raises(AssertionError, match="shape"):
         map_grow.map_fuse(ctx, md, bd, 0, z(2), z(3), sizes=sizes)
-    ed = map_grow._edit(md, bd, None, NMP + 4, md["obs_ptr"].device)
+    ed = api._map_edit(md, bd, None, NMP + 4, md["obs_ptr"].device)
     ls, o = map_grow._lib.gl_map_add_lists(), map_grow._lib.gl_map_add_out()
     res = z(6)
     o.result = api._ptr(res)

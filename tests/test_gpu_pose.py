@@ -197,12 +197,8 @@ def test_optimize_current_pose_compacted_problems(gpu, oracle, map_v1, gt_sync, 
         octv = torch.from_numpy(np.stack([f["octave"] for f in fr])).cuda()
         outl = torch.from_numpy(flags_in.copy()).cuda()
         nin = torch.zeros(len(fr), dtype=torch.int32).cuda()
-        ctx._enter()
-        try:
-            api._check(ctx.lib.gl_optimize_current_pose(ctx.h, api.C.byref(cam.c()), api.C.byref(prm.c()), len(fr), M, api._ptr(pose), api._ptr(Xw),
-                                                        api._ptr(obs), api._ptr(octv), api._ptr(outl), api._ptr(nin)))
-        finally:
-            ctx._exit()
+        ctx.call(ctx.lib.gl_optimize_current_pose, api.C.byref(cam.c()), api.C.byref(prm.c()), len(fr), M, api._ptr(pose), api._ptr(Xw), api._ptr(obs),
+                 api._ptr(octv), api._ptr(outl), api._ptr(nin))
         torch.cuda.synchronize()
         return pose.cpu().numpy(), outl.cpu().numpy(), nin.cpu().numpy()
 

@@ -168,7 +168,7 @@ def kernels_leg():
                 and a["ba"]["obs_feat"].cpu().numpy().tobytes() == rs.rows1["obs_feat"].tobytes()
             assert same, name
         # the library calls themselves on structs made once (the wrappers' validation costs more host time than the kernels run)
-        ed = map_grow._edit(rs.md, rs.bd, rs.rk, rs.caps[0], rs.rk.device)
+        ed = api._map_edit(rs.md, rs.bd, rs.rk, rs.caps[0], rs.rk.device)
         kw = rs.add_kw
         ls = _lib.gl_map_add_lists()
         ls.new_pos, ls.new_assoc, ls.new_ref_kf, ls.new_mp_cap = p(kw["new_mp"]["pos"]), p(kw["new_mp"]["assoc"]), p(kw["new_mp"]["ref_kf"]), len(kw["new_mp"]["assoc"])

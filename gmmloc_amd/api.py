@@ -888,22 +888,35 @@ def map_remove(ctx, map, ba, erase_obs=None, rm_kf=None, rm_mp=None, n_erase=Non
     return r
 
 
-def mapping_pass_from_map(ctx, gmm, cam, prm, map, ba, kf_row, caps, kf_depth, th_depth, Ccap=64, mp_ref_kf=None, stop_flag=None, slab=None):
+def mapping_pass_from_map(ctx, gmm, cam, prm, map, ba, kf_row, caps, kf_depth, th_depth, Ccap=64, mp_ref_kf=None, stop_flag=None, slab=None,
+                          kf_tables=None, cov=None):
     """What Localization::spinOnce (localization.cpp:97-107) does to the map after a key-frame's local BA, on the resident map with nothing
     flattened or uploaded: joint_optimization_from_map -> map_remove(erase_obs) -> update_connections(kf_row) -> cull_keyframes on that
-    list -> map_remove(rm_kf).  -> dict(ba: the dict of joint_optimization_from_map; map, ba_rows: the edited dicts; conn, cull: the
-    dicts of update_connections / cull_keyframes (B = 1); the host's bookkeeping lists as int lists: erased (CSR positions of the map on
-    entry), dead_by_erase, culled (key-frame rows in list order), dead_by_cull (map-point rows); status of the two removals)."""
+    list -> map_remove(rm_kf).  With kf_tables (dict(desc), as covis.refresh_points takes it) and mp_ref_kf, the window's points get their
+    updateNormalAndDepth (localization_opt.cpp:921) behind the erase, as the reference has it; with cov (the graph of covis.py) the culled
+    key-frames leave the stored graph too (covis.covis_remove, the graph part of Map::removeKeyFrame, map.cpp:77-87).  A host that keeps
+    per-point normals or the graph on the device passes both; without them the two steps are the caller's.
+    -> dict(ba: the dict of joint_optimization_from_map; map, ba_rows: the edited dicts; conn, cull: the dicts of update_connections /
+    cull_keyframes (B = 1); the host's bookkeeping lists as int lists: erased (CSR positions of the map on entry), dead_by_erase, culled
+    (key-frame rows in list order), dead_by_cull (map-point rows); status of the two removals[; covis_result: covis_remove's (4,) i32])."""
     import torch
     r = joint_optimization_from_map(ctx, gmm, cam, prm, map, ba, kf_row, caps, stop_flag=stop_flag, slab=slab)
     e = map_remove(ctx, map, ba, erase_obs=r["slab"]["erase_obs"][0], n_erase=r["slab"]["n_erase"], mp_ref_kf=mp_ref_kf)
     dev = map["obs_ptr"].device
+    NMP, NKF = map["obs_ptr"].shape[0] - 1, map["kf_mp"].shape[0]
+    if kf_tables is not None and mp_ref_kf is not None:
+        from .covis import refresh_points
+        refresh_points(ctx, e["map"], e["ba"], kf_tables, mp_ref_kf, (NMP, NKF, e["nobs"]), r["win_mp"], 2)
     conn = update_connections(ctx, e["map"], torch.full((1,), int(kf_row), dtype=torch.int32, device=dev), Ccap=Ccap)
     cull = cull_keyframes(ctx, e["map"], e["ba"], kf_depth, th_depth, conn["conn_kf"], conn["n_conn"])
     k = map_remove(ctx, e["map"], e["ba"], rm_kf=cull["cull_rows"][0], n_rm_kf=cull["n_cull"], mp_ref_kf=mp_ref_kf)
+    out = {}
+    if cov is not None:
+        from .covis import covis_remove
+        out["covis_result"] = covis_remove(ctx, cov, NKF, cull["cull_rows"][0], cull["n_cull"], int(ba.get("kf_first", -1)))
     n_cull = int(cull["n_cull"][0])
     return dict(ba=r, map=k["map"], ba_rows=k["ba"], conn=conn, cull=cull, erased=r["erase_obs"].tolist(), dead_by_erase=e["dead_mp"].tolist(),
-                culled=cull["cull_rows"][0, :n_cull].tolist(), dead_by_cull=k["dead_mp"].tolist(), status=(e["status"], k["status"]))
+                culled=cull["cull_rows"][0, :n_cull].tolist(), dead_by_cull=k["dead_mp"].tolist(), status=(e["status"], k["status"]), **out)
 
 
 def search_by_projection_frame(ctx, cam, pose_cw, pose_lw, feat_uv, feat_ur, feat_oct, feat_angle, feat_desc, feat_taken,

@@ -1722,11 +1722,19 @@ int gl_track_frames(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera* cam, co
  *                   (gl_params.ba_first_as_prior != 0) or fixed pose (== 0: only the points move);
  *   F               fixed observer key-frames per frame, 0 .. GL_TRACK_MAX_FIXED;
  *   fixed_pose_dev  B x F x 7; fixed_obs_dev B x M x F x 3 (u, v, u_right; u_right < 0 => mono);
- *   fixed_oct_dev   B x M x F int32 (< 0: point not observed by that key-frame);
- *   fixed_erase_dev B x M x F uint8 out or NULL (observations the reference would erase, :855-879).
- * F == 0 runs on the on-chip refine of gl_track_frames (the prior costs one 6x6 block per Levenberg trial); F > 0 is
- * packed into flat problems (P = 1) and solved by the general kernel of gl_joint_optimization.  Same arithmetic as
- * jointOptimization with P = 1: parity tests against the oracle's joint_optimization(P = 1, prior / F fixed). */
+ *   fixed_oct_dev   B x M x F int32: the octave of the observation, 0 .. 7 (the sigma^2 table has eight levels);
+ *                   < 0: point not observed by that key-frame, fixed_obs_dev is not read there;
+ *   fixed_erase_dev B x M x F uint8 out or NULL (observations the reference would erase, :855-879; 0 where not
+ *                   observed and in slots with octave_dev < 0).
+ * Three routes, the same verdicts from each:
+ *   F == 0                      the on-chip refine of gl_track_frames (the prior costs one 6x6 block per Levenberg trial);
+ *   1 <= F <= 4 and M <= 2000   on chip too: the fixed observers' edges are evaluated inside the per-frame refine;
+ *   F > 4, or M > 2000, or option ba_fixed_pack = 1: packed into flat problems (P = 1, the frame's own observation
+ *                               of a point first, then the fixed key-frames' in index order) and solved by the general
+ *                               kernel of gl_joint_optimization.
+ * F > GL_TRACK_MAX_FIXED is refused before anything is launched.  Same arithmetic as jointOptimization with P = 1:
+ * parity tests against the oracle's joint_optimization(P = 1, prior / F fixed), and a hand-built case on either side
+ * of every decision on every route (tests/optim_cases.py, call "anchored"). */
 #define GL_TRACK_MAX_FIXED 8
 typedef struct gl_track_anchor {
   const uint8_t* prior_dev;

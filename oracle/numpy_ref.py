@@ -680,13 +680,14 @@ def optimize_current_pose(pose7, Xw, obs, octave, cam, prm, chi2_mono=5.991, chi
 def joint_optimization(P, F, poses7, has_prior, points, assoc, obs_ptr, obs_pose, obs_uvr, obs_oct, comps, mean,
                        cam, prm, chi2_mono=5.991, chi2_stereo=7.815, cast=float, depth_test=True, stale=True,
                        str_level_scale=1.0, str_drop_scale=1.0, prior_as_edge=None, str_all=False, ignore_level_last=False,
-                       trace=None, **lm):
+                       is_mono=lambda ur: ur < 0, depth_pose=lambda j: j, trace=None, **lm):
     """localization_opt.cpp:456-925 on the flat problem (see oracle/gmmloc_oracle.cpp).
     The keyword arguments are the comparisons of the function, with the reference's as defaults, for tests that alter one at a
     time (tests/test_optim_cases.py): the observation thresholds (:799-828 and :855-879), a cast on both sides of them,
     the isDepthPositive half, whether the final verdict reads the chi2 an excluded edge was left with (stale) or
     recomputes it, the structure threshold at :773 and at :837 scaled, ba_first_as_prior overridden, the structure test applied to
-    every association (str_all), and the levels ignored in the last optimize().  trace: a dict that
+    every association (str_all), the levels ignored in the last optimize(), what makes an observation monocular (is_mono) and the
+    key-frame in whose camera the depth of an edge is taken (depth_pose).  trace: a dict that
     receives the chi2 every verdict was taken on (str_level, obs_level, str_drop, obs_erase, the last one also recomputed at the
     final state as obs_fresh) and the optimize() records (lm).  **lm: Problem's keyword arguments."""
     pb = Problem(cam, prm, **lm)
@@ -723,7 +724,7 @@ def joint_optimization(P, F, poses7, has_prior, points, assoc, obs_ptr, obs_pose
                     gmm_deg[l] = e
             pb.edges.append(e)
         for o in range(obs_ptr[l], obs_ptr[l + 1]):
-            mono = obs_uvr[o, 2] < 0
+            mono = bool(is_mono(obs_uvr[o, 2]))
             s = float(prm.sigma2_inv[obs_oct[o]])
             e = dict(kind="ba_mono" if mono else "ba_stereo", pt=l, pose=int(obs_pose[o]), meas=obs_uvr[o],
                      info=s * np.eye(2 if mono else 3), robust=True, delta=fdelta(5.991 if mono else 7.815),
@@ -745,7 +746,7 @@ def joint_optimization(P, F, poses7, has_prior, points, assoc, obs_ptr, obs_pose
     pb.activate(0)
     pb.optimize(5)
     for e in eobs:
-        pc = pb.poses[e["pose"]].map(pb.points[e["pt"]])
+        pc = pb.poses[depth_pose(e["pose"])].map(pb.points[e["pt"]])
         if cast(e["chi2"]) > th_of(e) or (depth_test and not pc[2] > 0):
             e["level"] = 1
         e["robust"] = False
@@ -763,7 +764,7 @@ def joint_optimization(P, F, poses7, has_prior, points, assoc, obs_ptr, obs_pose
             dropped[l] = 1
     erase = np.zeros(len(eobs), np.uint8)
     for o, e in enumerate(eobs):
-        pc = pb.poses[e["pose"]].map(pb.points[e["pt"]])
+        pc = pb.poses[depth_pose(e["pose"])].map(pb.points[e["pt"]])
         c = e["chi2"] if stale else pb.chi2(e)
         erase[o] = 1 if (cast(c) > th_of(e) or (depth_test and not pc[2] > 0)) else 0
     if trace is not None:

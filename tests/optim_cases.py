@@ -1,4 +1,5 @@
-"""Named scenes of a dozen points and a few key-frames on both sides of the decisions the three Levenberg optimisers make, built by hand in
+"""Named scenes of a dozen points and a few key-frames on both sides of the decisions the Levenberg optimisers make (three entry points and
+the anchored form of the per-frame one), built by hand in
 numpy, for tests/test_optim_cases.py (CPU: the C++ oracle and oracle/numpy_ref.py both give the output each case declares) and
 tests/test_gpu_optim_cases.py (every case through every launch shape of its kernel).  Test infrastructure.
 
@@ -38,6 +39,21 @@ The decisions and the reference lines (DECISIONS holds the same list; the oracle
     ba.pose_unobserved  og_graph.hpp initializeOptimization                     a free key-frame without an edge: its bytes; the same key-frame with three edges
     ba.single_mono      og_graph.hpp solve                                      a point with one monocular observation (a block of rank 2); with one stereo one
     ba.prior_or_fixed   :560-581  has_prior                                     on key-frame 1: a prior edge (ba_first_as_prior 1) or the vertex fixed (0)
+  the fixed observers' edges of gl_track_frames_anchored (gl_ba_fast_impl.hpp: the kFixed instances of k_ba1_fast;
+  gl_ba_gen.hip: k_track_pack -> k_ba_gen -> k_track_unpack)                                   call "anchored"
+    fx.chi2_level       :799      stale chi2 > 5.991 / 7.815 per fixed column   (1 -/+ 1e-6), mono and stereo, octaves 0, 2, 7, F = 1 .. 4, first and last column
+    fx.depth            :806, :862  !(zf > 0) in the OBSERVER's camera          an observer turned away, chi2 exactly 0: erased; facing: kept; one of three
+    fx.depth_own_camera :806, :862  the frame's own depth is not the edge's     a point behind the frame and in front of both observers: their edges stay
+    fx.stale_erase      :855-879  as ba.stale_erase, both on fixed observers    B in the first column (the converted case) and in the last
+    fx.mono_by_uright   k_ba1_prep  u_right < 0 of a fixed observation          -0.0 and +0.0 stereo (96 px off: erased); -5e-324, -1 mono
+    fx.not_observed     gl_track_anchor  fixed_oct < 0 / octave < 0             an edge, a key-frame, a key-frame turned away, a slot: the bits of the frame without it
+    fx.point_keeps_fixed_edges / fx.point_leaves  initializeOptimization        the own edge excluded: one fixed edge stays; none (frozen); none but a GMM edge; F = 1 and 4
+    fx.str_level / fx.str_drop  :773-786 / :837-853                             as ba.str_level / ba.str_drop with the point started ON its plane, inside the gate
+    fx.prior_or_fixed   :560-581  the frame's own pose                          prior edge: moves; fixed: its bytes; neither: moves further
+    fx.float_vs_double  :806      doubles                                       ba.float_vs_double with both edges on fixed observers: erased
+    and, re-expressed in the dense layout by anchored_from_ba (CONVERTED), under their own keys: the eight ba_obs_chi2_*, ba_depth_fixed_*,
+    ba_stale_erase*, ba_point_leaves / _stays, ba_assoc_minus_1, ba_rho_*, ba_lm_*; with twins built for this call where its own association
+    (argmin + gate) would not make the case's: anc_assoc_0, anc_gate_at_9 / _above_9, anc_far_from_plane / anc_dragged_off_blob
   Levenberg (og_graph.hpp)
     lm.rho_zero         :765      rho == 0 ends optimize()                      the exact scene on all three calls: iters == 1, everything unchanged; scenes that move
     lm.reject           :748-763  a rejected trial: restored, lambda *= ni      a start 3 m off: two rejections in a row (ni reaches 8); a start accepted at once;
@@ -59,17 +75,25 @@ final value, which is held to numpy_ref's within 1e-9 (oracle) and to the oracle
 equal bits alone and in a batch.  gl_track_frames returns no `iters`: its exact scenes declare `outer` = 3, the outer iterations of the
 three optimize() together, read from the statistics buffer.
 
+gl_track_frames_anchored returns no `iters` either (`outer` = 3 on its exact scenes, written by the on-chip route alone: the packed route
+leaves the statistics buffer's second half as it was) and no verdict on the frame's OWN observation: fixed_erase is declared in full, the
+own verdict is held as through gl_track_frames, by what the point does.
+
 Decisions WITHOUT a case, and why:
-  ba.float_vs_double through gl_track_frames: a frame sees a point once, so no second observation can cancel the first one's pull and the
-    point moves: the chi2 is then one an optimisation ends on, reproducible to a relative 1e-8 only on the ORACLE itself (along a ladder
-    of 1e-9 steps of one offset its own verdict flipped back and forth at three of 28 steps), against a gap of 2.93e-8.  Not buildable.
-  ba.stale_erase through gl_track_frames: the stale chi2 is read at :855-879 only, to fill the erase mask, which this call does not
-    return; pose, points and associations do not depend on it.  The anchored call's fixed_erase is held by tests/test_gpu_anchor.py.
-  ba.str_level apart from ba.str_drop through gl_track_frames: with one observation per point nothing can be removed between :773 and
-    :837, so a chi2 above the threshold at :773 is above it at :837 too (3.4 against 0.64 in track_str_above) and one below stays below:
-    the track cases cross both with one scalar and are filed under ba.str_drop; the two are told apart in the local BA's own cases.
-  ba.vertex_leaves / ba.pose_unobserved / ba.prior_or_fixed / ba.single_mono through gl_track_frames: one free pose that sees every point
-    once, in the frame's own observation; none of these vertices exists.
+  Through plain gl_track_frames (F = 0) a frame sees a point once and no erase mask comes back, so ba.float_vs_double, ba.stale_erase,
+    ba.str_level apart from ba.str_drop (3.4 against 0.64 in track_str_above: one scalar crosses both) and ba.vertex_leaves /
+    ba.prior_or_fixed cannot show there.  With fixed observers they can, and are built through the anchored call: fx.float_vs_double
+    (measured distance of the device's chi2 from the oracle's: 0 steps of 1.52e-9 on the on-chip route, which evaluates the edge in
+    normalised coordinates, and 0 steps on the packed one, against a quarter of the gap of 7.3e-9), fx.stale_erase, fx.str_level /
+    fx.str_drop, fx.point_leaves / fx.point_keeps_fixed_edges, fx.prior_or_fixed.
+  ba.pose_unobserved and the key-frame half of ba.vertex_leaves through either per-frame call: the one free pose sees every kept point in
+    the frame's own observation, and a fixed key-frame is no vertex: no free key-frame without edges exists.  (A frame whose every own
+    edge is excluded at :799 keeps the GMM edges or the prior; one with neither is the unanchored call on an empty map.)
+  ba.single_mono through either per-frame call: a point seen once, monocular, exists there, but what the "ba" case declares - that
+    lambda alone makes the rank-2 block solvable - shows only in where an ill-conditioned point ends (the parity tests compare such
+    points at 1e-5, not 1e-6): no integer and no byte depends on it.  Held by the local BA's own cases.
+  ba_far_from_blob converted: its point lies 0.3 m from a 0.1 m blob, d2 = 9 (1 - 1.3e-15): on the gate, where one ulp of an input is
+    the other side.  ba.nondegenerate has anc_far_from_plane / anc_dragged_off_blob instead, the gate anc_gate_at_9 / _above_9.
   A chi2 EXACTLY at 5.991f / 7.815f after an optimisation: not reproducible, as above.  The float cases therefore use stationary scenes
     whose chi2 is exact (see FLOAT_TARGET below).
 """
@@ -157,6 +181,28 @@ def associate(backend, mean, cov, pts):
         backend.gmm_destroy(h)
 
 
+def anchored_pack(data, keep, assoc, observed=lambda fo: fo >= 0):
+    """the flat problem of an "anchored" frame, in the order k_track_pack documents (gl_ba_gen.hip): the kept points in slot order, per
+    point the frame's own observation first, then the fixed key-frames' in index order -> (the "ba" data, [(slot, column or -1)] per observation)"""
+    F = len(data["fixed_pose"])
+    ptr, op, ou, oo, slot = [0], [], [], [], []
+    for l in keep:
+        op.append(0), ou.append(data["obs"][l]), oo.append(data["oct"][l]), slot.append((int(l), -1))
+        for j in range(F):
+            if observed(data["fixed_oct"][l, j]):
+                op.append(1 + j), ou.append(data["fixed_obs"][l, j]), oo.append(data["fixed_oct"][l, j]), slot.append((int(l), j))
+        ptr.append(len(op))
+    ba = dict(mean=data["mean"], cov=data["cov"], P=1, F=F, poses=np.concatenate([data["pose"][None], np.asarray(data["fixed_pose"], f64).reshape(F, 7)]),
+              prior=np.array([data["prior"]], np.uint8), points=data["Xw"][keep], assoc=assoc, obs_ptr=np.array(ptr, np.int32), obs_pose=np.array(op, np.int32),
+              obs_uvr=np.array(ou, f64).reshape(-1, 3), obs_oct=np.array(oo, np.int32), prm=data.get("prm"))
+    return ba, slot
+
+
+def anchored_obs(data, l, j):
+    """the index of the observation of slot l from fixed column j (-1: the frame's own) in the packed problem"""
+    return anchored_pack(data, np.nonzero(data["oct"] >= 0)[0], None)[1].index((l, j))
+
+
 def run(backend, call, data, **alt):
     """One call of a case on the oracle object or on numpy_ref -> dict of outputs, named as the device's.  alt: keyword arguments of
     numpy_ref's optimisers (one comparison altered); trace=True returns numpy_ref's instrumentation under "trace"."""
@@ -185,6 +231,22 @@ def run(backend, call, data, **alt):
         assoc, dd, pts = -np.ones(len(keep), np.int32), np.zeros(len(keep)), data["Xw"].copy()
         assoc[keep], dd[keep], pts[keep] = np.where(o["dropped"] == 1, -1, a0), d2, o["points"]
         return dict(pose=o["poses"][0], points=pts, assoc=assoc, d2=dd, iters=o["iters"], trace=o.get("trace"))  # (iters: of the last optimize(40))
+    if call == "anchored":  # gl_track_frames_anchored: the same association, then jointOptimization with one free pose and F fixed observers
+        keep = np.nonzero(data["oct"] >= 0)[0]
+        M, F = len(data["oct"]), len(data["fixed_pose"])
+        idx, d2 = associate(backend, mean, cov, data["Xw"][keep])
+        a0 = np.where(gate(d2), idx, -1).astype(np.int32)
+        ba, slot = anchored_pack(data, keep, a0, alt.pop("observed", lambda fo: fo >= 0))
+        o = run(backend, "ba", ba, trace=want_trace, **alt) if is_np else run(backend, "ba", ba)
+        assoc, dd, pts = -np.ones(M, np.int32), np.zeros(M), data["Xw"].copy()
+        assoc[keep], dd[keep], pts[keep] = np.where(o["dropped"] == 1, -1, a0), d2, o["points"]
+        fe, own = np.zeros((M, F), np.uint8), np.zeros(M, np.uint8)
+        for e, (l, j) in zip(o["erase"], slot):
+            if j < 0:
+                own[l] = e  # (the verdict on the frame's own observation: no output of the device's call; for the converter's check)
+            else:
+                fe[l, j] = e
+        return dict(pose=o["poses"][0], points=pts, assoc=assoc, d2=dd, fixed_erase=fe, own_erase=own, iters=o["iters"], trace=o.get("trace"))
     assert call == "ba"
     args = (data["P"], data["F"], data["poses"], data["prior"], data["points"], assoc_of(data["assoc"]), data["obs_ptr"], data["obs_pose"], data["obs_uvr"], data["obs_oct"])
     if is_np:
@@ -227,6 +289,20 @@ D("ba.single_mono", "og_graph.hpp solve", "a 3 x 3 block of rank 2 is solvable t
 D("ba.prior_or_fixed", "localization_opt.cpp:560-581", "has_prior: an EdgeSE3QuatPrior, or the vertex fixed")
 D("lm.rho_zero", "og_graph.hpp:765", "rho == 0 ends optimize()")
 D("lm.reject", "og_graph.hpp:748-763", "a rejected trial is restored, lambda *= ni, ni *= 2")
+
+# the fixed-observer edges of gl_track_frames_anchored (call "anchored"): the device's own copy of every decision on a fixed edge
+D("fx.chi2_level", "localization_opt.cpp:799; gl_ba_fast_impl.hpp k_ba1_fast, phase 1 of the levels", "stale chi2 > 5.991 / 7.815 per fixed column, octaves 0, 2, 7")
+D("fx.depth", "localization_opt.cpp:806, :862; k_ba1_fast !(zf > 0)", "the depth of a fixed edge in the OBSERVER's camera")
+D("fx.depth_own_camera", "localization_opt.cpp:806, :862", "the frame's own depth says nothing about a fixed edge")
+D("fx.stale_erase", "localization_opt.cpp:855-879; k_ba1_fast outputs", "fixed_erase reads the chi2 an excluded fixed edge was left with")
+D("fx.mono_by_uright", "localization_opt.cpp:706-760; gl_ba_fast.hip k_ba1_prep", "u_right < 0 of a fixed observation is monocular")
+D("fx.not_observed", "gmmloc_hip.h gl_track_anchor", "fixed_oct < 0, or octave < 0 of the slot: no edge, whatever fixed_obs holds")
+D("fx.point_keeps_fixed_edges", "og_graph.hpp initializeOptimization(level)", "a point whose own edge is excluded stays active on one fixed edge")
+D("fx.point_leaves", "og_graph.hpp initializeOptimization(level)", "every reprojection edge excluded: the point leaves, unless a GMM edge holds it")
+D("fx.str_level", "localization_opt.cpp:773-786", "the structure threshold after the first optimize(5), with fixed observers")
+D("fx.str_drop", "localization_opt.cpp:837-853", "the structure threshold at the end, with fixed observers")
+D("fx.prior_or_fixed", "localization_opt.cpp:560-581", "the frame's own pose: prior edge, fixed, or free")
+D("fx.float_vs_double", "localization_opt.cpp:806", "chi2 > 5.991 in doubles on a fixed edge")
 
 P0 = np.array([0, 0, 0, 1, 0.01, 0, 0], f64)  # the start of the pose cases that are not exact: 1 cm off
 
@@ -308,6 +384,58 @@ SOLVED = {
     "track_obs_chi2_stereo_above": "0x1.368cd5e580dbbp+5",
     "track_str_below": "0x1.78600711e0613p-3",
     "track_str_above": "0x1.78602254af717p-3",
+    "fx_chi2_mono_oct0_F1_below": "0x1.9cc02563ece52p+2",
+    "fx_chi2_mono_oct0_F1_above": "0x1.9cc030008685bp+2",
+    "fx_chi2_mono_oct0_F2_below": "0x1.ed867c0e60d76p+1",
+    "fx_chi2_mono_oct0_F2_above": "0x1.ed8690983acc7p+1",
+    "fx_chi2_mono_oct0_F3_below": "0x1.aa64d5686f47ap+1",
+    "fx_chi2_mono_oct0_F3_above": "0x1.aa64e9f0e6e20p+1",
+    "fx_chi2_mono_oct0_F4_below": "0x1.8c12cba49ac2ep+1",
+    "fx_chi2_mono_oct0_F4_above": "0x1.8c12e191ac176p+1",
+    "fx_chi2_mono_oct2_F1_below": "0x1.8eac6763fcb8bp+2",
+    "fx_chi2_mono_oct2_F1_above": "0x1.8eac763c2ec15p+2",
+    "fx_chi2_mono_oct2_F2_below": "0x1.1fef3a621885ep+2",
+    "fx_chi2_mono_oct2_F2_above": "0x1.1fef492ad9461p+2",
+    "fx_chi2_mono_oct2_F3_below": "0x1.08cad9a9fd8b1p+2",
+    "fx_chi2_mono_oct2_F3_above": "0x1.08cae9a03c7e6p+2",
+    "fx_chi2_mono_oct2_F4_below": "0x1.fc97e27328310p+1",
+    "fx_chi2_mono_oct2_F4_above": "0x1.fc9801c42933ap+1",
+    "fx_chi2_mono_oct7_F1_below": "0x1.3a33d069ab879p+3",
+    "fx_chi2_mono_oct7_F1_above": "0x1.3a33e3d00c7edp+3",
+    "fx_chi2_mono_oct7_F2_below": "0x1.251fd7f216d7fp+3",
+    "fx_chi2_mono_oct7_F2_above": "0x1.251feab7acef8p+3",
+    "fx_chi2_mono_oct7_F3_below": "0x1.2084b294f1683p+3",
+    "fx_chi2_mono_oct7_F3_above": "0x1.2084c53776abbp+3",
+    "fx_chi2_mono_oct7_F4_below": "0x1.1e6afcf83b6e4p+3",
+    "fx_chi2_mono_oct7_F4_above": "0x1.1e6b0f5ccb90bp+3",
+    "fx_chi2_stereo_oct0_F1_below": "0x1.c1ba3e57eab93p+2",
+    "fx_chi2_stereo_oct0_F1_above": "0x1.c1ba4cfb5d169p+2",
+    "fx_chi2_stereo_oct0_F2_below": "0x1.18f6c8de24d3fp+2",
+    "fx_chi2_stereo_oct0_F2_above": "0x1.18f6d4a3d6c76p+2",
+    "fx_chi2_stereo_oct0_F3_below": "0x1.e6bd6e1258f6bp+1",
+    "fx_chi2_stereo_oct0_F3_above": "0x1.e6bd858a16728p+1",
+    "fx_chi2_stereo_oct0_F4_below": "0x1.c44cc3d450bd1p+1",
+    "fx_chi2_stereo_oct0_F4_above": "0x1.c44cdd3d5568fp+1",
+    "fx_chi2_stereo_oct2_F1_below": "0x1.b737b53aa94b9p+2",
+    "fx_chi2_stereo_oct2_F1_above": "0x1.b737c6d56905ap+2",
+    "fx_chi2_stereo_oct2_F2_below": "0x1.48850af246d9cp+2",
+    "fx_chi2_stereo_oct2_F2_above": "0x1.48851bda7bc35p+2",
+    "fx_chi2_stereo_oct2_F3_below": "0x1.2e61aec188646p+2",
+    "fx_chi2_stereo_oct2_F3_above": "0x1.2e61c13cf414ap+2",
+    "fx_chi2_stereo_oct2_F4_below": "0x1.226db86818c98p+2",
+    "fx_chi2_stereo_oct2_F4_above": "0x1.226dca4437711p+2",
+    "fx_chi2_stereo_oct7_F1_below": "0x1.662ce58f20104p+3",
+    "fx_chi2_stereo_oct7_F1_above": "0x1.662cfbb31d1a4p+3",
+    "fx_chi2_stereo_oct7_F2_below": "0x1.4ec69de05d0b1p+3",
+    "fx_chi2_stereo_oct7_F2_above": "0x1.4ec6b34e89c5bp+3",
+    "fx_chi2_stereo_oct7_F3_below": "0x1.49862baff0f90p+3",
+    "fx_chi2_stereo_oct7_F3_above": "0x1.498640f4a1292p+3",
+    "fx_chi2_stereo_oct7_F4_below": "0x1.47203b9b3359ep+3",
+    "fx_chi2_stereo_oct7_F4_above": "0x1.472050cd7de43p+3",
+    "fx_str_level_below": "0x1.426d4424419fbp-6",
+    "fx_str_drop_below": "0x1.ce59935189760p-4",
+    "fx_str_level_above": "0x1.426cd525107ddp-6",
+    "fx_str_drop_above": "0x1.ce59b21158c8bp-4",
 }
 
 
@@ -598,7 +726,8 @@ for _n, _tz, _side, _q in (("ba_lm_reject", 3.0, "two rejections", 3), ("ba_lm_a
 # 128 +/- D_FLOAT and the residuals are exact), the start is a stationary point, optimize() stops on rho == 0, and both edges have
 # chi2 = D_FLOAT^2 exactly, in any expression order.
 # Measured on the MI355X (test_gpu_optim_cases.py::test_float_gap_distance): moving D_FLOAT in steps of 2^-29 px (1.52e-9 of chi2), the device's
-# verdict flips on the same step as the oracle's in both optimisers: its chi2 is within 1.52e-9 of the oracle's, against a quarter of the gap of 7.3e-9.
+# verdict flips on the same step as the oracle's in both optimisers and, on a fixed observer's edge of gl_track_frames_anchored, on the on-chip
+# route (normalised coordinates) and on the packed one (step -9 each, distance 0 steps): its chi2 is within 1.52e-9 of the oracle's, against a quarter of the gap of 7.3e-9.
 # (fx = 512 is a power of two and the octave is 0: the device's normalised-coordinate chi2 is this chi2 bit for bit, so the figure is about
 # the comparison - cast, constant, strictness -, not about the expression order on another camera.)
 FLOAT_TARGET = TH_MONO * (1 + 1.5e-8)
@@ -639,7 +768,7 @@ add("ba_float_vs_double_below_both", "ba", "ba.float_vs_double", "below both", b
 def float_probe(name, ks):
     """the data of a float case with its offset moved by k * FLOAT_STEP for the k in ks: the step at which the verdict of an
     implementation flips tells where it puts chi2 against its threshold"""
-    mk = pose_float_data if name.startswith("pose") else ba_float_data
+    mk = pose_float_data if name.startswith("pose") else ba_float_data  # ("anc_float_vs_double": the "ba" data, for anchored_from_ba)
     return [mk(D_FLOAT + k * FLOAT_STEP) for k in ks]
 
 
@@ -755,6 +884,330 @@ for _side, _f in (("below", 1 - REL), ("above", 1 + REL)):
         band=dict(thr=TH_STR100, side=_side, q=lambda b, _data=_data: track_q(_data, "str_level", 1) if b is numpy_ref else None), fixed=[("obs", (1, 2))])
 
 
+# ============================================================ gl_track_frames_anchored =================================================
+# The dense layout of the entry point: pose (7), Xw / obs (M x 3), oct (M), prior (0 / 1), fixed_pose (F x 7), fixed_obs (M x F x 3),
+# fixed_oct (M x F; < 0: not observed), mean, cov, prm.  The high-precision statement is jointOptimization(P = 1, F fixed) on the
+# problem anchored_pack() builds.  Outputs: pose, points, assoc (-1 where dropped or ungated), d2, fixed_erase (M x F).
+def anchored_from_ba(data):
+    """a "ba" case in the dense layout -> (data, [(slot, column or -1)] per observation of the "ba" case).  Needs P == 1, every point seen
+    exactly once by key-frame 0 and at most once by a fixed one, and the call's own association (argmin + gate on the case's map) to
+    reproduce the case's."""
+    assert data["P"] == 1
+    L, F = len(data["points"]), data["F"]
+    d = dict(pose=data["poses"][0].copy(), Xw=data["points"].copy(), obs=np.zeros((L, 3)), oct=-np.ones(L, np.int32), prior=int(data["prior"][0]),
+             fixed_pose=data["poses"][1:].copy(), fixed_obs=np.zeros((L, F, 3)), fixed_oct=-np.ones((L, F), np.int32), mean=data["mean"], cov=data["cov"])
+    if data.get("prm"):
+        d["prm"] = data["prm"]
+    slot = []
+    for l in range(L):
+        for o in range(data["obs_ptr"][l], data["obs_ptr"][l + 1]):
+            k = int(data["obs_pose"][o])
+            if k == 0:
+                assert d["oct"][l] < 0
+                d["obs"][l], d["oct"][l] = data["obs_uvr"][o], data["obs_oct"][o]
+            else:
+                assert d["fixed_oct"][l, k - 1] < 0
+                d["fixed_obs"][l, k - 1], d["fixed_oct"][l, k - 1] = data["obs_uvr"][o], data["obs_oct"][o]
+            slot.append((l, k - 1))
+        assert d["oct"][l] >= 0, "a point the frame itself does not see"
+    idx, d2 = associate(numpy_ref, np.asarray(d["mean"], f64), np.asarray(d["cov"], f64).reshape(-1, 3, 3), d["Xw"])
+    assert np.array_equal(np.where(d2 <= 9.0, idx, -1), data["assoc"]), "the call's own association is not the case's"
+    return d, slot
+
+
+def fe_of(L, F, *ones):
+    m = np.zeros((L, F), np.uint8)
+    for l, j in ones:
+        m[l, j] = 1
+    return m
+
+
+def anc_q(data, key, l, j=None):
+    """numpy_ref's instrumentation of an "anchored" case: the chi2 a verdict was taken on, for the observation of slot l from column j
+    (obs_level) or for point l (str_level, str_drop)"""
+    def q(backend):
+        if backend is not numpy_ref:
+            return None
+        return float(run(numpy_ref, "anchored", data, trace=True)["trace"][key][l if j is None else anchored_obs(data, l, j)])
+    return q
+
+
+CONVERTED = {}  # name of the "anchored" case -> (name of the "ba" case, its observations' (slot, column))
+KEEP_WANT = ("iters", "unchanged", "moved_points", "at_identity", "first_q", "n_last", "n_shrinks", "frozen_points")
+
+
+def convert(ba_name, decision=None):
+    c = CASES[ba_name]
+    d, slot = anchored_from_ba(c.data)
+    L, F = d["fixed_oct"].shape
+    w = {k: v for k, v in c.want.items() if k in KEEP_WANT}
+    w["assoc"] = np.where(c.want["dropped"][:L] == 1, -1, c.data["assoc"]).astype(np.int32)
+    w["fixed_erase"] = fe_of(L, F, *[s for o, s in enumerate(slot) if s[1] >= 0 and c.want["erase"][o]])
+    if "at_exact" in c.want:
+        w["at_exact"] = {l: (c.data["points"][l], v) for l, v in c.want["at_exact"].items()}
+    if w.get("iters") == 1:
+        w["outer"] = 3
+    if d["prior"] and not (d.get("prm") or {}).get("ba_first_as_prior", 1):
+        w["pose_bytes"] = True
+    fixed = []
+    for k, i in c.fixed:
+        if k == "obs_uvr":
+            l, j = slot[i[0]]
+            fixed.append(("obs", (l, i[1])) if j < 0 else ("fixed_obs", (l, j, i[1])))
+        else:
+            fixed.append((k, i))
+    band = None
+    if c.band:  # (every banded case that is converted takes its band at :799, on one observation)
+        o = [i for k, i in c.fixed if k == "obs_uvr"][0][0]
+        band = dict(thr=c.band["thr"], side=c.band["side"], q=anc_q(d, "obs_level", *slot[o]))
+    n = add("anc_" + ba_name[3:], "anchored", decision or c.decision, c.side, d, w, band=band, fixed=fixed)
+    CONVERTED[n] = (ba_name, slot)
+    return n
+
+
+for _n in [n for n in list(CASES) if n.startswith("ba_obs_chi2_")] + ["ba_depth_fixed_behind", "ba_depth_fixed_in_front", "ba_stale_erase", "ba_stale_erase_not_excluded",
+                                                                       "ba_point_leaves", "ba_point_stays", "ba_assoc_minus_1", "ba_rho_zero", "ba_rho_nonzero",
+                                                                       "ba_lm_reject", "ba_lm_accept"]:
+    convert(_n)
+convert("ba_float_vs_double", "fx.float_vs_double")
+convert("ba_float_vs_double_below_both", "fx.float_vs_double")
+
+
+def anc_data(F, L=12, prior=1, comps=None, prm=None):
+    """the first L points of grid(), seen exactly and in stereo by the frame and by F fixed key-frames, all at the identity"""
+    X = grid()[:L].copy()
+    mean, cov = mk_map(comps) if comps is not None else NOMAP
+    d = dict(pose=ID7.copy(), Xw=X, obs=project(ID7, X), oct=np.zeros(L, np.int32), prior=prior, fixed_pose=np.tile(ID7, (F, 1)),
+             fixed_obs=np.repeat(project(ID7, X)[:, None], F, 1), fixed_oct=np.zeros((L, F), np.int32), mean=mean, cov=cov)
+    if prm:
+        d["prm"] = prm
+    return d
+
+
+NONE = lambda L: -np.ones(L, np.int32)
+
+# The twins of the "ba" cases whose association the call itself would not make: their point lies 1 cm (ba_assoc_0: d2 = 100) or 0.3 m
+# (ba_far_from_plane: d2 = 90 000) from a 1 mm plane, outside the gate d2 <= 9, or 0.3 m from a 0.1 m blob (ba_far_from_blob: d2 = 9 (1 - 1.3e-15), ON
+# the gate, where one ulp of an input decides).  ba.assoc_none: the plane 2 mm behind point 1 (d2 = 4: associated,
+# the point moves towards it); the converted ba_assoc_minus_1 is the other side, gated out.  ba.nondegenerate: point 1 starts ON its
+# component and every observation of it is that of a point 0.3 m deeper (ba_lambda2 = 100): off a plane it is dropped, off a blob nothing is.
+_d = anc_data(1, comps=[plane(0.0, -0.25, 2.002), blob(0.0, 0.0, -50.0)])
+_a = NONE(12)
+_a[1] = 0
+add("anc_assoc_0", "anchored", "ba.assoc_none", "associated (anchored)", _d, dict(assoc=_a, fixed_erase=fe_of(12, 1), moved_points=[1]))
+# the gate itself, as track_gate_at_9 / track_gate_above_9: point 5 exactly 3 sigma from a unit-covariance component, and one ulp farther
+for _n, _x, _side in (("anc_gate_at_9", 3.0, "d2 = 9.0 (anchored)"), ("anc_gate_above_9", float(np.nextafter(3.0, 4.0)), "d2 > 9.0 (anchored)")):
+    _d = anc_data(1, comps=[blob(0.0, 0.25, 8.0, 1.0)])
+    _d["Xw"][5] = (_x, 0.25, 8.0)
+    _d["obs"][5] = _d["fixed_obs"][5, 0] = project(ID7, _d["Xw"][5])
+    _a = NONE(12)
+    _a[5] = 0 if _x == 3.0 else -1
+    add(_n, "anchored", "ba.assoc_none", _side, _d, dict(assoc=_a, fixed_erase=fe_of(12, 1), d2_of={5: 9.0} if _x == 3.0 else {}),
+        fixed=[("Xw", (5, 0)), ("Xw", (5, 1)), ("Xw", (5, 2)), ("mean", None), ("cov", None)])
+for _n, _comp, _side in (("anc_far_from_plane", plane, "degenerate (anchored)"), ("anc_dragged_off_blob", blob, "not degenerate (anchored)")):
+    _d = anc_data(1, comps=[_comp(0.0, -0.25, 2.0), blob(0.0, 0.0, -50.0)], prm=STR_PRM)
+    _d["obs"][1] = _d["fixed_obs"][1, 0] = project(ID7, np.array([0.0, -0.25, 2.3]))
+    _a = NONE(12)
+    _a[1] = -1 if _comp is plane else 0
+    add(_n, "anchored", "ba.nondegenerate", _side, _d, dict(assoc=_a, fixed_erase=fe_of(12, 1), moved_points=[1]))
+
+
+# fx.chi2_level: the ba_thr_data scene with F = 1 ... 4: eight points, the frame and every fixed key-frame see each of them exactly, but the
+# observation of point 0 from column kf, d px off in u (monocular, or stereo with u_right exact).  The exact observations hold the point, so d is
+# solved per (mono, octave, F); the twin with the edge in the last column reuses it (the same problem with two key-frames exchanged).  Octave 7
+# is the last entry of the sigma^2 table and the edge of the level mask.
+def fx_thr_data(d, octave, mono, F=1, kf=0):
+    a = anc_data(F, 8)
+    a["fixed_obs"][0, kf] = sh(PR[0], d, mono=mono)
+    a["fixed_oct"][0, kf] = octave
+    return a
+
+
+for _mono, _thr in ((True, TH_MONO), (False, TH_STEREO)):
+    for _oct in (0, 2, 7):
+        for _F in (1, 2, 3, 4):
+            for _side, _f in (("below", 1 - REL), ("above", 1 + REL)):
+                _k = "fx_chi2_%s_oct%d_F%d_%s" % ("mono" if _mono else "stereo", _oct, _F, _side)
+                _d = scalar(_k, lambda o=_oct, m=_mono, F=_F, t=_thr * _f, s=1.2 ** _oct: secant(lambda d: anc_q(fx_thr_data(d, o, m, F), "obs_level", 0, 0)(numpy_ref), t, 4.0 * s, 6.0 * s))
+                for _kf in sorted({0, _F - 1}):
+                    _data = fx_thr_data(_d, _oct, _mono, _F, _kf)
+                    add("fx_chi2_%s_oct%d_F%d_kf%d_%s" % ("mono" if _mono else "stereo", _oct, _F, _kf, _side), "anchored", "fx.chi2_level", _side, _data,
+                        dict(assoc=NONE(8), fixed_erase=fe_of(8, _F, *([(0, _kf)] if _side == "above" else []))),
+                        band=dict(thr=_thr, side=_side, q=anc_q(_data, "obs_level", 0, _kf)), fixed=[("fixed_obs", (0, _kf, 0))])
+
+# fx.depth: a key-frame turned by RY7 looks away from point 0; its monocular measurement is the point's projection through the negative z, so
+# chi2 is exactly 0 and the edge goes on !(zf > 0) in THAT camera alone (F = 1; the twin faces the point).  Third scene: F = 3, the
+# middle key-frame looks away, the two others see every point exactly: one column of fixed_erase, and nothing moves.
+for _n, _F, _kf, _pose, _side in (("fx_depth_behind", 1, 0, RY7, "behind the observer"), ("fx_depth_in_front", 1, 0, ID7, "in front of the observer"),
+                                  ("fx_depth_behind_one_of_three", 3, 1, RY7, "behind one observer of three")):
+    _d = anc_data(_F)
+    _d["fixed_pose"][_kf] = _pose
+    _d["fixed_oct"][1:, _kf] = -1
+    _d["fixed_obs"][0, _kf] = sh(project(_pose, grid()[0]), mono=True)
+    add(_n, "anchored", "fx.depth", _side, _d, dict(assoc=NONE(12), fixed_erase=fe_of(12, _F, *([(0, _kf)] if _pose is RY7 else [])), iters=1, outer=3, unchanged=True))
+
+# fx.depth_own_camera: point 0 lies BEHIND the frame (its own monocular measurement is the projection through the negative z: that edge goes),
+# both observers are turned by RY7 and face it, with exact observations of it alone: their edges stay.  The twin: nothing is behind anything.
+_d = anc_data(2)
+_d["Xw"][0] = (-0.5, -0.25, -2.0)
+_d["obs"][0] = sh(project(ID7, _d["Xw"][0]), mono=True)
+_d["fixed_pose"][:] = RY7
+_d["fixed_oct"][1:] = -1
+_d["fixed_obs"][0, :] = project(RY7, _d["Xw"][0])
+add("fx_depth_own_camera_behind", "anchored", "fx.depth_own_camera", "behind the frame, in front of both observers", _d, dict(assoc=NONE(12), fixed_erase=fe_of(12, 2), iters=1, outer=3, unchanged=True))
+add("fx_depth_own_camera_in_front", "anchored", "fx.depth_own_camera", "in front of all three", anc_data(2), dict(assoc=NONE(12), fixed_erase=fe_of(12, 2), iters=1, outer=3, unchanged=True))
+
+# fx.stale_erase: the construction of ba_stale_erase (whose converted form has B in column 0 and A in column 1) with B in the LAST column
+for _n, _dB, _side, _er in (("fx_stale_erase_last_column", 2.2, "erased on the stale chi2, last column", [(0, 0), (0, 1)]), ("fx_stale_erase_last_column_not_excluded", 1.0, "kept, last column", [(0, 0)])):
+    _d = anc_data(2)
+    _d["fixed_obs"][0, 0], _d["fixed_obs"][0, 1] = sh(PR[0], -30.0, 0, -30.0), sh(PR[0], _dB, mono=True)
+    add(_n, "anchored", "fx.stale_erase", _side, _d, dict(assoc=NONE(12), fixed_erase=fe_of(12, 2, *_er)))
+
+# fx.mono_by_uright: the observation of point 0 from column 0 is exact in u and v, its u_right 0 - 96 px from the point's.  Stereo: erased
+for _n, _ur, _side in (("fx_uright_minus_0", -0.0, "stereo"), ("fx_uright_plus_0", 0.0, "stereo"), ("fx_uright_minus_denormal", -5e-324, "mono"), ("fx_uright_minus_1", -1.0, "mono")):
+    _d = anc_data(2)
+    _d["fixed_obs"][0, 0, 2] = _ur
+    add(_n, "anchored", "fx.mono_by_uright", _side, _d, dict(assoc=NONE(12), fixed_erase=fe_of(12, 2, *([(0, 0)] if _side == "stereo" else []))), fixed=[("fixed_obs", (0, 0, 2))])
+
+
+# fx.not_observed: what is marked not observed is not read.  The frame moves (the observation of point 0 from column 0 is 3 px off), and
+# its outputs are those of the twin (`same_as`: data, the twin's rows and columns in this case), bit for bit
+def moving(F):
+    d = anc_data(F)
+    d["fixed_obs"][0, 0] = sh(PR[0], 3.0)
+    return d
+
+
+WILD = np.array([900.0, -700.0, 5.0])
+_t = moving(2)
+_t["fixed_oct"][0, 1] = -1
+_d = dict(_t, fixed_obs=_t["fixed_obs"].copy())
+_d["fixed_obs"][0, 1] = WILD
+add("fx_not_observed_edge", "anchored", "fx.not_observed", "one edge", _d, dict(assoc=NONE(12), fixed_erase=fe_of(12, 2), moved_points=[0], same_as=(_t, np.arange(12), np.arange(2))))
+for _n, _pose, _side in (("fx_not_observed_keyframe", ID7, "a key-frame"), ("fx_not_observed_keyframe_turned", RY7, "a key-frame that looks away")):
+    _d = moving(3)
+    _d["fixed_oct"][:, 1] = -1
+    _d["fixed_obs"][:, 1] = WILD
+    _d["fixed_pose"][1] = _pose
+    add(_n, "anchored", "fx.not_observed", _side, _d, dict(assoc=NONE(12), fixed_erase=fe_of(12, 3), moved_points=[0], same_as=(moving(2), np.arange(12), np.array([0, 2]))))
+_d = moving(2)
+for _k, _v in (("Xw", [[0.3, 0.1, 3.0]]), ("obs", [WILD]), ("oct", [-1]), ("fixed_obs", [[WILD, WILD]]), ("fixed_oct", [[0, 3]])):
+    _d[_k] = np.concatenate([_d[_k][:5], np.array(_v, _d[_k].dtype), _d[_k][5:]])
+_a = fe_of(13, 2)
+add("fx_not_observed_slot", "anchored", "fx.not_observed", "a slot without a map point", _d, dict(assoc=NONE(13), fixed_erase=_a, moved_points=[0], same_as=(moving(2), np.array([0, 1, 2, 3, 4, 6, 7, 8, 9, 10, 11, 12]), np.arange(2))))
+
+# fx.point_keeps_fixed_edges / fx.point_leaves: the frame's own observation of point 0 is 40 px off (monocular) and excluded at :799.
+#   keeps:  one fixed edge (the LAST column, 1 px off in u and u_right) stays and holds the point (`held`: it ends within 1 cm of its start, and moves)
+#   leaves: every fixed edge is excluded too (40 px each, against one another) and nothing is associated: no level-0 edge, the point
+#           keeps the bits of the second optimize(5) (frozen_points, by numpy_ref's instrumentation)
+#   held by the map: as `leaves`, but point 0 starts 1 cm beside a tight blob, inside the gate: the GMM edge keeps it active and it ends at the centre
+# each with F = 1 and F = 4 (the other columns of `keeps` are 40 px off as well), so that the test for "a fixed edge left" meets one bit and four
+OFF4 = ((-40.0, 0.0, 40.0), (40.0, 40.0, -40.0), (-40.0, -40.0, -40.0), (0.0, 40.0, 40.0))
+
+
+def fx_point_data(F, stays, comps=None):
+    d = anc_data(F, comps=comps)
+    d["obs"][0] = sh(PR[0], 40.0, mono=True)
+    for j in range(F):
+        d["fixed_obs"][0, j] = sh(PR[0], *OFF4[j])
+    if stays:
+        d["fixed_obs"][0, F - 1] = sh(PR[0], 1.0, 0.0, 1.0)
+    return d
+
+
+for _F in (1, 4):
+    _all = [(0, j) for j in range(_F)]
+    add("fx_point_keeps_one_edge_F%d" % _F, "anchored", "fx.point_keeps_fixed_edges", "one fixed edge of %d stays" % _F, fx_point_data(_F, True),
+        dict(assoc=NONE(12), fixed_erase=fe_of(12, _F, *_all[:-1]), held={0: 0.01}))
+    add("fx_point_leaves_F%d" % _F, "anchored", "fx.point_leaves", "no edge left, F = %d" % _F, fx_point_data(_F, False),
+        dict(assoc=NONE(12), fixed_erase=fe_of(12, _F, *_all), frozen_points=[0], n_shrinks=True))
+    _d = fx_point_data(_F, False, comps=[blob(-0.49, -0.25, 2.0, 0.011), blob(0.0, 0.0, -50.0)])
+    _a = NONE(12)
+    _a[0] = 0
+    add("fx_point_held_by_map_F%d" % _F, "anchored", "fx.point_leaves", "the GMM edge keeps it, F = %d" % _F, _d,
+        dict(assoc=_a, fixed_erase=fe_of(12, _F, *_all), at_mean={0: (0, True)}))
+
+
+# fx.str_level / fx.str_drop: str_a_data / str_b_data with point 1 started ON its 1 mm plane (d2 = 0: inside the gate), where the "ba" cases
+# start it at z = 2, 2 cm and 11 cm off.  (a): the frame and two observers exact, two observers outlying; (b): the frame and one
+# observer exact, one outlying.  One scalar, the plane's offset, per side
+def fx_str_data(mk, p):
+    b = mk(p)
+    b["points"] = b["points"].copy()
+    b["points"][1, 2] = b["mean"][0][2]
+    return anchored_from_ba(b)[0]
+
+
+for _side, _f in (("below", 1 - REL), ("above", 1 + REL)):
+    _p = scalar("fx_str_level_" + _side, lambda t=TH_STR100 * _f: secant(lambda p: anc_q(fx_str_data(str_a_data, p), "str_level", 1)(numpy_ref), t, 0.02, 0.03))
+    _data = fx_str_data(str_a_data, _p)
+    _a = NONE(12)
+    _a[1] = 0
+    add("fx_str_level_" + _side, "anchored", "fx.str_level", _side, _data, dict(assoc=_a, fixed_erase=fe_of(12, 4, (1, 2), (1, 3)), at_exact={1: (grid()[1], _side == "above")}),
+        band=dict(thr=TH_STR100, side=_side, q=anc_q(_data, "str_level", 1)), fixed=[("mean", (0, 2)), ("Xw", (1, 2))])
+    _p = scalar("fx_str_drop_" + _side, lambda t=TH_STR100 * _f: secant(lambda p: anc_q(fx_str_data(str_b_data, p), "str_drop", 1)(numpy_ref), t, 0.09, 0.10))
+    _data = fx_str_data(str_b_data, _p)
+    _a = NONE(12)
+    _a[1] = -1 if _side == "above" else 0
+    add("fx_str_drop_" + _side, "anchored", "fx.str_drop", _side, _data, dict(assoc=_a, fixed_erase=fe_of(12, 2, (1, 1)), at_exact={1: (grid()[1], False)}),
+        band=dict(thr=TH_STR100, side=_side, q=anc_q(_data, "str_drop", 1)), fixed=[("mean", (0, 2)), ("Xw", (1, 2))])
+
+# fx.prior_or_fixed: the ba_prior_row1 idea on the frame's own pose: its eight observations are 1 px off in u and u_right, two fixed
+# observers are exact.  With the prior edge the pose moves; fixed, it keeps its bytes and the points move; without either it moves
+# further than under the prior (`further_than`: against the same implementation's pose on the named case)
+for _n, _pr, _fp, _side in (("fx_prior_as_prior", 1, 1, "prior edge"), ("fx_prior_as_fixed", 1, 0, "fixed"), ("fx_prior_none", 0, 1, "free")):
+    _d = anc_data(2, 8, prior=_pr, prm=dict(ba_first_as_prior=_fp))
+    _d["obs"] = np.stack([sh(PR[l], 1.0, 0, 1.0) for l in range(8)])
+    _w = dict(assoc=NONE(8), fixed_erase=fe_of(8, 2))
+    _w.update(dict(pose_bytes=True, moved_points=list(range(8))) if (_pr and not _fp) else dict(moved_pose=True))
+    if not _pr:
+        _w["further_than"] = "fx_prior_as_prior"
+    add(_n, "anchored", "fx.prior_or_fixed", _side, _d, _w)
+
+
+def pad_anchored(data, M, F, where="behind"):
+    """an "anchored" case with M slots and F fixed key-frames: the added slots have octave -1 and the added key-frames (at the identity)
+    observe nothing; the padding lies behind the case's rows and columns, or in front of them -> (data, rows, columns of the case)"""
+    n, f = data["fixed_oct"].shape
+    rows, cols = (np.arange(n), np.arange(f)) if where == "behind" else (np.arange(M - n, M), np.arange(F - f, F))
+    d = dict(data, Xw=np.ones((M, 3)), obs=np.zeros((M, 3)), oct=-np.ones(M, np.int32), fixed_pose=np.tile(ID7, (F, 1)),
+             fixed_obs=np.zeros((M, F, 3)), fixed_oct=-np.ones((M, F), np.int32))
+    for k in ("Xw", "obs", "oct"):
+        d[k][rows] = data[k]
+    d["fixed_pose"][cols] = data["fixed_pose"]
+    d["fixed_obs"][np.ix_(rows, cols)], d["fixed_oct"][np.ix_(rows, cols)] = data["fixed_obs"], data["fixed_oct"]
+    return d, rows, cols
+
+
+def unpad_anchored(o, d, rows, cols):
+    """the outputs on a padded case brought back to the case's rows and columns; the padding's: assoc -1, fixed_erase 0, the point's bytes"""
+    pad = np.ones(len(d["oct"]), bool)
+    pad[rows] = False
+    assert (o["assoc"][pad] == -1).all() and o["points"][pad].tobytes() == d["Xw"][pad].tobytes(), "a padding slot was written"
+    fe = o["fixed_erase"].copy()
+    fe[np.ix_(rows, cols)] = 0
+    assert not fe.any(), "fixed_erase set in the padding"
+    out = dict(o, assoc=o["assoc"][rows], points=o["points"][rows], d2=o["d2"][rows], fixed_erase=o["fixed_erase"][np.ix_(rows, cols)])
+    return out
+
+
+def check_related(c, o, other):
+    """what a case declares against ANOTHER run of the same implementation (other: that run's outputs): `same_as` - the twin without the
+    column or slot that is marked not observed - by the bytes; `further_than` - the pose has moved further than the named case's"""
+    w = c.want
+    if "same_as" in w:
+        _, rows, cols = w["same_as"]
+        assert o["pose"].tobytes() == other["pose"].tobytes() and o["points"][rows].tobytes() == other["points"].tobytes(), (c.name, "not the twin's bytes")
+        assert np.array_equal(o["assoc"][rows], other["assoc"]) and np.array_equal(o["fixed_erase"][np.ix_(rows, cols)], other["fixed_erase"]), (c.name, "not the twin's integers")
+    if "further_than" in w:
+        assert np.abs(o["pose"] - c.data["pose"]).max() > np.abs(other["pose"] - c.data["pose"]).max() > 1e-6, (c.name, o["pose"], other["pose"])
+
+
+def related_data(c):
+    """the data of the run check_related compares with, or None"""
+    return c.want["same_as"][0] if "same_as" in c.want else CASES[c.want["further_than"]].data if "further_than" in c.want else None
+
+
 # ---- padding to a common launch shape ------------------------------------------------------------------------------------------------
 def pad_rows(data, M):
     """a pose / track case with M slots: the rows beyond its own have octave -1 (no map point)"""
@@ -800,7 +1253,40 @@ def check_declared(c, o, data=None, want=None):
             if "q_round0" in w:
                 assert tr[0]["lm"][0]["q"] == w["q_round0"], (c.name, tr[0]["lm"][0])
         return
-    if c.call == "track":
+    if c.call == "anchored":  # (o: in the case's own rows and columns - unpad_anchored brings a padded run there)
+        assert eq("assoc") and eq("fixed_erase"), (c.name, o["assoc"], o["fixed_erase"])
+        start = lambda l: np.abs(o["points"][l] - data["Xw"][l]).max()
+        for l, v in w.get("d2_of", {}).items():
+            assert o["d2"][l] == v, (c.name, "d2", o["d2"][l])
+        if w.get("unchanged"):
+            assert o["pose"].tobytes() == data["pose"].tobytes() and o["points"].tobytes() == data["Xw"].tobytes(), (c.name, "not the input's bytes")
+        if w.get("pose_bytes"):
+            assert o["pose"].tobytes() == data["pose"].tobytes(), (c.name, "a fixed pose moved", o["pose"])
+        if w.get("moved_pose"):
+            assert np.abs(o["pose"] - data["pose"]).max() > 1e-6, (c.name, "pose", o["pose"])
+        for l in np.nonzero(data["oct"] < 0)[0]:  # a slot without a map point is no vertex
+            assert o["points"][l].tobytes() == data["Xw"][l].tobytes(), (c.name, "slot", l)
+        for l in w.get("moved_points", ()):
+            assert start(l) > 1e-6, (c.name, "point", l)
+        for l, r in w.get("held", {}).items():
+            assert 1e-6 < start(l) < r, (c.name, "point", l, start(l))
+        for l, (x, v) in w.get("at_exact", {}).items():
+            assert (np.abs(o["points"][l] - x).max() < 1e-6) == v, (c.name, "point", l, o["points"][l])
+        if w.get("at_identity"):
+            assert np.abs(o["pose"] - ID7).max() < 1e-6, (c.name, o["pose"])
+        for l, (a, v) in w.get("at_mean", {}).items():
+            dist = np.abs(o["points"][l] - np.asarray(data["mean"])[a]).max()
+            assert (dist < 1e-6) == v and (v or dist > 4e-4), (c.name, "point", l, dist)
+        if tr:
+            if "first_q" in w:
+                assert tr["lm"][0]["q"][0] == w["first_q"] and tr["lm"][0]["ni_max"] >= 2.0 ** w["first_q"], (c.name, tr["lm"][0])
+            if "n_last" in w or "n_shrinks" in w:
+                assert (tr["lm"][0]["n"] > tr["lm"][-1]["n"]) == bool(w.get("n_shrinks")) and w.get("n_last", tr["lm"][-1]["n"]) == tr["lm"][-1]["n"], (c.name, [t["n"] for t in tr["lm"]])
+            for l in w.get("frozen_points", ()):  # (every slot of such a case holds a point: slot l is vertex l)
+                assert o["points"][l].tobytes() == tr["state_level"][1][l].tobytes(), (c.name, "point", l)
+        if "outer" in w and "outer" in o:
+            assert o["outer"] == w["outer"], (c.name, o["outer"])
+    elif c.call == "track":
         assert eq("assoc", len(c.data["oct"])), (c.name, o["assoc"])
         for l, v in w.get("d2_of", {}).items():
             assert o["d2"][l] == v, (c.name, "d2", o["d2"][l])

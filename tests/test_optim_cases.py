@@ -1,7 +1,10 @@
 """The hand-built optimiser cases (tests/optim_cases.py) on the CPU: the C++ oracle and oracle/numpy_ref.py both give the output every case
 declares; the cases at a threshold sit in their band; every decision has two sides; every case is STABLE (12 re-orderings of its edges and
 36 one-ulp perturbations of its inputs leave every declared integer where it is and move the oracle's pose by less than 1e-6); and the
-cases can fail: numpy_ref with one comparison altered (ALTERED below) misses the declared output of at least one case of that decision."""
+cases can fail: numpy_ref with one comparison altered (ALTERED below) misses the declared output of at least one case of that decision.
+The cases of gl_track_frames_anchored (call "anchored") get the same: their re-orderings permute the point slots and the fixed columns,
+every decision that has such cases is held by one of them alone, every one at a threshold bites on its own, and each case converted from
+a local-BA case is shown to be that case (the oracle on both forms: equal masks, the pose to 1e-12)."""
 import numpy as np
 import pytest
 
@@ -20,7 +23,7 @@ def outputs(backend, name):
     if key not in _memo:
         c = oc.CASES[name]
         o = oc.run(backend, c.call, c.data, trace=True) if backend is numpy_ref else oc.run(backend, c.call, c.data)
-        if backend is numpy_ref and c.call == "track":
+        if backend is numpy_ref and c.call in ("track", "anchored"):
             o["outer"] = sum(len(t["q"]) for t in o["trace"]["lm"])
         _memo[key] = o
     return _memo[key]
@@ -41,6 +44,25 @@ def test_case_gives_declared_output(oracle, name):
         np.testing.assert_allclose(o_orc["points"][k], o_np["points"][k], rtol=0, atol=1e-9)
     for k in c.want.get("frozen_poses", ()):
         assert max(pose_err(o_orc["poses"][k], o_np["poses"][k])) < 1e-9
+    if c.call == "anchored":
+        assert np.array_equal(o_np["d2"] <= 9.0, o_orc["d2"] <= 9.0) and np.allclose(o_np["d2"], o_orc["d2"], rtol=1e-9, atol=0), name
+        rel = oc.related_data(c)
+        if rel is not None:  # the twin without the column or slot, or the case this one moves further than: on the same implementation
+            oc.check_related(c, o_np, oc.run(numpy_ref, "anchored", rel))
+            oc.check_related(c, o_orc, oc.run(oracle, "anchored", rel))
+
+
+@pytest.mark.parametrize("name", sorted(oc.CONVERTED))
+def test_converted_case_is_the_case_it_came_from(oracle, name):
+    """anchored_from_ba re-expresses a local-BA case in the dense layout of gl_track_frames_anchored: the oracle on the case as written ("ba")
+    and on the converted one ("anchored") gives the same erase mask, the same dropped associations and the same pose to 1e-12."""
+    c = oc.CASES[name]
+    ba_name, slot = oc.CONVERTED[name]
+    b = oc.CASES[ba_name]
+    o_ba, o_an = outputs(oracle, ba_name), outputs(oracle, name)
+    erase = np.array([o_an["own_erase"][l] if j < 0 else o_an["fixed_erase"][l, j] for l, j in slot], np.uint8)
+    assert np.array_equal(erase, o_ba["erase"]) and np.array_equal(o_an["assoc"], np.where(o_ba["dropped"] == 1, -1, b.data["assoc"])), name
+    assert max(pose_err(o_an["pose"], o_ba["poses"][0])) < 1e-12 and np.abs(o_an["points"] - o_ba["points"]).max() < 1e-12, name
 
 
 BANDED = [n for n in NAMES if oc.CASES[n].band]
@@ -81,7 +103,7 @@ def test_every_decision_has_two_sides_and_an_alteration():
 
 
 # ---- stability ------------------------------------------------------------------------------------------------------------------------
-INTS = {"pose": ("outl", "nin"), "ba": ("dropped", "erase"), "track": ("assoc",)}
+INTS = {"pose": ("outl", "nin"), "ba": ("dropped", "erase"), "track": ("assoc",), "anchored": ("assoc", "fixed_erase")}
 
 
 def reorder(c, rng):
@@ -103,6 +125,24 @@ def reorder(c, rng):
                     o[k] = v
             return o
         return d, back
+    if c.call == "anchored":  # the point slots and the fixed columns
+        perm, cperm = rng.permutation(len(d["oct"])), rng.permutation(len(d["fixed_pose"]))
+        for k in ("Xw", "obs", "oct"):
+            d[k] = c.data[k][perm]
+        d["fixed_pose"] = c.data["fixed_pose"][cperm]
+        d["fixed_obs"], d["fixed_oct"] = c.data["fixed_obs"][np.ix_(perm, cperm)], c.data["fixed_oct"][np.ix_(perm, cperm)]
+
+        def back(o):
+            o = dict(o)
+            for k in ("assoc", "points", "d2", "own_erase"):
+                v = np.empty_like(o[k])
+                v[perm] = o[k]
+                o[k] = v
+            v = np.empty_like(o["fixed_erase"])
+            v[np.ix_(perm, cperm)] = o["fixed_erase"]
+            o["fixed_erase"] = v
+            return o
+        return d, back
     L = len(d["points"])
     perm = rng.permutation(L)  # the points, and the observations within each point
     sel = np.concatenate([rng.permutation(np.arange(d["obs_ptr"][l], d["obs_ptr"][l + 1])) for l in perm]).astype(int)
@@ -121,7 +161,8 @@ def reorder(c, rng):
     return d, back
 
 
-FLOAT_KEYS = {"pose": ("pose", "Xw", "obs"), "track": ("pose", "Xw", "obs", "mean", "cov"), "ba": ("poses", "points", "obs_uvr", "mean", "cov")}
+FLOAT_KEYS = {"pose": ("pose", "Xw", "obs"), "track": ("pose", "Xw", "obs", "mean", "cov"), "ba": ("poses", "points", "obs_uvr", "mean", "cov"),
+              "anchored": ("pose", "Xw", "obs", "fixed_pose", "fixed_obs", "mean", "cov")}
 
 
 def one_ulp(c, rng):
@@ -133,7 +174,7 @@ def one_ulp(c, rng):
         a0 = np.array(c.data[k], float)
         a = ulp_variants(a0, 1, rng)[0]
         i = tuple(int(x) for x in np.argwhere(a != a0)[0])
-        if (k, None) in fixed or (k, i) in fixed or (k in ("obs", "obs_uvr") and i[-1] == 2 and a0[i] < 0):
+        if (k, None) in fixed or (k, i) in fixed or (k in ("obs", "obs_uvr", "fixed_obs") and i[-1] == 2 and a0[i] < 0):
             continue
         return dict(c.data, **{k: a})
 
@@ -147,17 +188,18 @@ def test_case_is_stable(oracle, name):
     ref = outputs(oracle, name)
     rng = np.random.default_rng(len(name))
     pk = "poses" if c.call == "ba" else "pose"
-    for probe in range(48):
+    for probe in range(48):  # (an "anchored" case: the 12 re-orderings permute its point slots and its fixed columns)
         if probe < 12:
             d, back = reorder(c, rng)
             o = back(oc.run(oracle, c.call, d))
             want = c.want
         else:
-            o = oc.run(oracle, c.call, one_ulp(c, rng))
-            want = {k: v for k, v in c.want.items() if k not in ("iters", "unchanged", "unchanged_poses", "d2_of", "outer")}
+            d = one_ulp(c, rng)
+            o = oc.run(oracle, c.call, d)
+            want = {k: v for k, v in c.want.items() if k not in ("iters", "unchanged", "unchanged_poses", "pose_bytes", "d2_of", "outer")}
         for k in INTS[c.call]:
             assert np.array_equal(o[k], ref[k]), (name, probe, k)
-        oc.check_declared(c, o, want=want)
+        oc.check_declared(c, o, want=want, data=d if c.call == "anchored" and probe >= 12 else None)
         for a, b in zip(np.atleast_2d(o[pk]), np.atleast_2d(ref[pk])):
             assert max(pose_err(a, b)) < 1e-6, (name, probe, pose_err(a, b))
 
@@ -188,6 +230,18 @@ ALTERED = {
     "ba.prior_or_fixed": [dict(prior_as_edge=True), dict(prior_as_edge=False)],
     "lm.rho_zero": [dict(rho_stop=False)],
     "lm.reject": [dict(raise_lambda=False)],
+    "fx.chi2_level": [dict(chi2_mono=5.991 * UP, chi2_stereo=7.815 * UP), dict(chi2_mono=5.991 * DOWN, chi2_stereo=7.815 * DOWN)],
+    "fx.depth": [dict(depth_test=False), dict(depth_pose=lambda j: 0)],  # (no depth test; the depth taken in the frame's camera)
+    "fx.depth_own_camera": [dict(depth_pose=lambda j: 0)],
+    "fx.stale_erase": [dict(stale=False)],
+    "fx.mono_by_uright": [dict(is_mono=lambda ur: ur <= 0), dict(is_mono=lambda ur: bool(np.signbit(ur))), dict(is_mono=lambda ur: ur < -1e-300)],
+    "fx.not_observed": [dict(observed=lambda fo: fo >= -1)],
+    "fx.point_keeps_fixed_edges": [dict(ignore_level_last=True)],
+    "fx.point_leaves": [dict(ignore_level_last=True)],
+    "fx.str_level": [dict(str_level_scale=UP), dict(str_level_scale=DOWN)],
+    "fx.str_drop": [dict(str_drop_scale=UP), dict(str_drop_scale=DOWN)],
+    "fx.prior_or_fixed": [dict(prior_as_edge=True), dict(prior_as_edge=False)],
+    "fx.float_vs_double": [dict(cast=F32)],
 }
 ALTERATIONS = [(d, i) for d in sorted(ALTERED) for i in range(len(ALTERED[d]))]
 
@@ -202,14 +256,46 @@ def test_altered_comparison_changes_a_declared_output(decision, i):
         c = oc.CASES[n]
         if c.decision != decision:
             continue
-        if ("gate" in alt) != (c.call == "track") and ("gate" in alt or "assoc_of" in alt):
-            continue  # (the gate is gl_track_frames', the meaning of assoc < 0 the local BA's)
-        try:
-            with np.errstate(all="ignore"):  # (an undamped singular system overflows: that is the point of that alteration)
-                o = oc.run(numpy_ref, c.call, c.data, trace=True, **alt)
-            if c.call == "track":
-                o["outer"] = sum(len(t["q"]) for t in o["trace"]["lm"])
-            oc.check_declared(c, o)
-        except (AssertionError, np.linalg.LinAlgError):
+        if misses(c, alt):
             missed.append(n)
     assert missed, (decision, sorted(alt))
+
+
+_missed = {}
+
+
+def misses(c, alt):
+    """whether numpy_ref with the alteration no longer gives what the case declares; None where the alteration does not apply to the call"""
+    if (c.name, id(alt)) not in _missed:  # (alt: one of ALTERED's dicts; the three tests below ask about the same pairs)
+        _missed[c.name, id(alt)] = _misses(c, alt)
+    return _missed[c.name, id(alt)]
+
+
+def _misses(c, alt):
+    if ("gate" in alt) != (c.call in ("track", "anchored")) and ("gate" in alt or "assoc_of" in alt):
+        return None  # (the gate is gl_track_frames' and the anchored call's, the meaning of assoc < 0 the local BA's)
+    try:
+        with np.errstate(all="ignore"):  # (an undamped singular system overflows: that is the point of that alteration)
+            o = oc.run(numpy_ref, c.call, c.data, trace=True, **alt)
+        if c.call in ("track", "anchored"):
+            o["outer"] = sum(len(t["q"]) for t in o["trace"]["lm"])
+        oc.check_declared(c, o)
+    except (AssertionError, np.linalg.LinAlgError):
+        return True
+    return False
+
+
+ANCHORED_ALTERATIONS = [(d, i) for d, i in ALTERATIONS if any(c.decision == d for c in oc.CASES.values() if c.call == "anchored") and "assoc_of" not in ALTERED[d][i]]
+
+
+@pytest.mark.parametrize("decision,i", ANCHORED_ALTERATIONS, ids=["%s-%d" % a for a in ANCHORED_ALTERATIONS])
+def test_altered_comparison_changes_an_anchored_output(decision, i):
+    """The same on the cases of gl_track_frames_anchored alone: every decision that has "anchored" cases is held by one of THEM."""
+    assert [n for n in oc.names("anchored") if oc.CASES[n].decision == decision and misses(oc.CASES[n], ALTERED[decision][i])], (decision, i)
+
+
+@pytest.mark.parametrize("name", [n for n in BANDED if oc.CASES[n].call == "anchored" and oc.CASES[n].band["side"] != "float"])
+def test_anchored_threshold_case_bites(name):
+    """every "anchored" case at a threshold, on its own: the threshold moved by a relative 1e-5 to its side changes a declared output"""
+    c = oc.CASES[name]
+    assert any(misses(c, alt) for alt in ALTERED[c.decision]), name

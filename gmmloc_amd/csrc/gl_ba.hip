@@ -497,10 +497,13 @@ static int track_frames_impl(gl_ctx_t* ctx, const gl_gmm_t* gmm, const gl_camera
   const size_t n = (size_t)B * M;
   // on-chip fast path (gl_ba_fast.hip) for M <= 2000; option ba_slow forces the general kernel
   const bool fast = (c->opt.ba_slow == 0 || fixed) && gl::ba1_fast_supported(M);
-  gl::Ba1Layout lay;
-  int rc = gl::ba1_layout(c, B, M, fixed ? fixed->F : 0, prior_dev != nullptr, fast, &lay);
-  if (rc != GL_OK) return rc;
   const bool use_grid = g->grid.enabled && c->opt.assoc_grid != 0;
+  // the fused front (ba1_layout decides: batch shape, an instance that has it, option ba_front) serves the plain call on the cell
+  // index whose caller does not ask for the chi2 values; every other call runs the kernels below unchanged
+  const bool front_ok = fast && use_grid && !d2_dev && !prior_dev && !fixed;
+  gl::Ba1Layout lay;
+  int rc = gl::ba1_layout(c, B, M, fixed ? fixed->F : 0, prior_dev != nullptr, fast, &lay, front_ok, g->K);
+  if (rc != GL_OK) return rc;
   const size_t assoc_bytes =
       use_grid ? gl::assoc_index_scratch_bytes(g->K, (int)n, d2_dev != nullptr) : gl::assoc_scratch_bytes(g->K, (int)n);
   // | association scratch (used first, dead afterwards) ... reused by the refine | d2 (if the caller does not want it) |

@@ -60,6 +60,11 @@ struct BafKArgs {
   FixedV fxv;
   int32_t* edges_out;
   int* frame_ctr;
+  // the fused front (kFront instances, ba1_front): != 0 - the refine makes each frame's records in its own set-up, k_ba1_prep does not
+  // run; pn_all then holds one set of records per WORKGROUP of the launch.  obs_all, d2_all: the inputs k_ba1_prep would have read.
+  int front, nwg;  // (nwg: the workgroups of the launch)
+  const double* obs_all;
+  const double* d2_all;
 };
 __host__ __device__ inline PrepView prep_view(double* scratch, int B, int L) {
   PrepView v;
@@ -221,6 +226,8 @@ struct BafCfg {
   int mcap, nw;
   bool spread, step32, prior, fixed, wide;
 };
+// the instances that carry the fused front (kFront): plain DENSE and its wide twins
+constexpr bool baf_front(const BafCfg& c) { return !c.spread && !c.step32 && !c.prior && !c.fixed; }
 namespace bafd2000 { constexpr BafCfg kCfg{2000, 8, false, false, false, false, false}; }     // DENSE, exact step: 1 frame per CU
 namespace bafs { constexpr BafCfg kCfg{256, 8, true, false, false, false, false}; }           // SPREAD, exact step
 #ifndef GL_BAF_QUICK
@@ -359,7 +366,25 @@ static const BafInst* baf_instance(const Ctx* c, bool spread, bool prior, int F,
 // batches) and the device holds all of them at once, DENSE otherwise.  Both add in the same order: the choice never shows in
 // the results (option ba_shape forces one: 0 DENSE, 1 SPREAD where it fits).  Then the scratch of that shape: only SPREAD has
 // exchange words and a staging area.  !fast: the general kernel's regions alone.
-int ba1_layout(Ctx* c, int B, int L, int F, bool prior, bool fast, Ba1Layout* out) {
+// The workgroups of a batch-shaped launch: persistent ones (option ba_persist, default on), as many as the device holds at once,
+// drawing their frames from frame_ctr, where the batch is larger than that; else one per frame.
+static int dense_grid(Ctx* c, const BafInst* in, int B, int G, int* grid, bool* persistent) {
+  GL_HIP(ensure_dynamic_lds(c, (const void*)in->kern, in->lds));
+  *grid = B;
+  *persistent = false;
+  if (c->opt.ba_persist != 0) {
+    int occ = 0;
+    (void)ctx_occupancy(c, (const void*)in->kern, 64 * G, in->lds, &occ);
+    if (occ > 0 && (long)occ * c->ncu < (long)B) {
+      *grid = occ * c->ncu;
+      *persistent = true;
+    }
+  }
+  return GL_OK;
+}
+
+// front_ok: the call is one the fused front serves (track_frames_impl); K: the components of the map.
+int ba1_layout(Ctx* c, int B, int L, int F, bool prior, bool fast, Ba1Layout* out, bool front_ok, int K) {
   int G, S;
   canon_order(L, &G, &S);
   bool spread = (long)B * G <= 2 * c->ncu;  // two workgroups of 256 threads fit a CU (LDS 2 x 80 KB, 2 waves per SIMD; checked below)
@@ -381,13 +406,28 @@ int ba1_layout(Ctx* c, int B, int L, int F, bool prior, bool fast, Ba1Layout* ou
   Ba1Layout& o = *out;
   o = Ba1Layout{};
   o.spread = spread;
+  // The fused front: a batch-shaped launch of an instance that has it (kFront) makes the records of a frame in the refine's own
+  // set-up, one set per WORKGROUP of the launch instead of one per frame (option ba_front, default 1; 0: k_ba1_prep, A/B and tests)
+  size_t nrec = n;
+  if (fast && !spread && front_ok && c->opt.ba_front != 0) {
+    const BafInst* in = baf_instance(c, false, prior, F, L, K);
+    GL_REQUIRE(in, "no refine instance for this launch");
+    if (baf_front(in->cfg)) {
+      int grid = 0;
+      bool persistent = false;
+      const int rc = dense_grid(c, in, B, G, &grid, &persistent);
+      if (rc != GL_OK) return rc;
+      o.front = true;
+      nrec = (size_t)grid * L;
+    }
+  }
   Regions r{0};
   if (!fast) {
     o.trial = r.take(n * 3 * sizeof(double));
     o.chi = r.take(n * sizeof(double));
     o.lev = r.take(n);
   } else {
-    o.rec = r.take(n * (3 * sizeof(double) + 3 * sizeof(int32_t)));
+    o.rec = r.take(nrec * (3 * sizeof(double) + 3 * sizeof(int32_t)));
     o.frame_ctr = r.take(sizeof(int));
     o.prior_mi = r.take((size_t)B * 12 * sizeof(double));
     if (spread) {
@@ -411,19 +451,15 @@ static int launch_dense(Ctx* c, BafKArgs a, int* frame_ctr, int K) {
   const BafInst* in = baf_instance(c, false, a.prior_all != nullptr, a.fxv.F, a.L, K);
   GL_REQUIRE(in, "no refine instance for this launch");
   const int threads = 64 * a.G;
-  GL_HIP(ensure_dynamic_lds(c, (const void*)in->kern, in->lds));
   a.NB = 1;
   a.parts = nullptr;
-  // persistent workgroups (option ba_persist, default on): as many as the device holds at once, drawing frames from frame_ctr
-  int grid = a.B;
-  if (c->opt.ba_persist != 0) {
-    int occ = 0;
-    (void)ctx_occupancy(c, (const void*)in->kern, threads, in->lds, &occ);
-    if (occ > 0 && (long)occ * c->ncu < (long)a.B) {
-      grid = occ * c->ncu;
-      a.frame_ctr = frame_ctr;
-    }
-  }
+  int grid = 0;
+  bool persistent = false;
+  const int rc = dense_grid(c, in, a.B, a.G, &grid, &persistent);
+  if (rc != GL_OK) return rc;
+  if (persistent) a.frame_ctr = frame_ctr;
+  a.nwg = grid;
+  GL_REQUIRE(!a.front || baf_front(in->cfg), "refine instance without the fused front");  // (ba1_layout chose the same instance)
   in->kern<<<grid, threads, in->lds, c->stream>>>(a);
   GL_HIP(hipGetLastError());
   return GL_OK;
@@ -487,6 +523,14 @@ int launch_ba1_fast(Ctx* c, const Gmm* g, const gl_camera* cam, const gl_params*
     a.stage = (double*)(scratch + lay.stage);
   }
   int* const frame_ctr = (int*)(scratch + lay.frame_ctr);
+  if (lay.front) {  // the refine's own set-up makes the records (ba1_front): no k_ba1_prep, the frame queue starts at zero
+    a.front = 1;
+    a.obs_all = obs;
+    a.d2_all = d2;
+    GL_HIP(hipMemsetAsync(frame_ctr, 0, sizeof(int), c->stream));
+    TimerScope ts(c, GL_TIMER_BA);
+    return launch_dense(c, a, frame_ctr, g->K);
+  }
   {  // set-up: gate, flags, normalised observations, the order the refine walks each frame in - and, before a latency-shape
      // launch, the zeros its exchange words start from
     TimerScope ts(c, GL_TIMER_BA_PREP);

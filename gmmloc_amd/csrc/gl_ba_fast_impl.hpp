@@ -60,6 +60,10 @@ constexpr bool kLean = !kPrior;
 // (profiles/r14_kernel_meta.txt).  kCfg.wide: the instances for maps of more than 65 536 components, whose indices do not fit the
 // 16 bits per slot: the loads too.
 constexpr bool kResident = !kSpread && !kPrior && !kStep32 && !kCfg.wide;
+// The fused front: the plain DENSE instances and their wide twins can make a frame's records in their own set-up (ba1_front) where
+// k_ba1_prep made them for the whole launch; the launcher says per launch whether they do (BafKArgs::front).  The others keep
+// k_ba1_prep: they are at 256 registers with spills, or run the latency shape.
+constexpr bool kFront = baf_front(kCfg);
 
 #ifdef GL_BA_TRACE  // debug build: (currentChi, tempChi, lambda, rho) of every Levenberg trial of frame 0 -> its points
 __device__ double g_trace[10 * 128];
@@ -1944,6 +1948,126 @@ constexpr int kLdsTb = kLdsFrt + (kFixed ? kMaxFixed * 12 : 0);       // SPREAD:
 constexpr size_t kLdsBytes = (kLdsTb + (kSpread ? 29 * TSP : 0)) * sizeof(double);
 
 typedef const BafKArgs __attribute__((address_space(4))) kargs_t;
+
+// The fused front (kFront instances, BafKArgs::front): the workgroup makes its frame's records itself, where k_ba1_prep made them for
+// the whole launch - the gate, the flag words, the stable three-class partition (same ascending order of the caller's index, so the
+// same permuted index lp as there), the normalised observations.  Round j, thread t takes point l = j NT + t of the caller's order
+// (NT = 64 G threads, S <= 4 rounds); the point goes straight to its place sp[lp] in LDS, its flag word and association are parked
+// in the `un` region (free until the first pass A), where the thread that owns slot lp picks them up behind the barrier.  What the
+// passes and the write-out read from global memory - normalised observation, perm, association - goes to the WORKGROUP's records
+// `srec` (index blockIdx.x, not the frame: a persistent workgroup rewrites them frame after frame, they stay in the caches).
+// The association and its chi2 are read from assoc_all / d2_all as k_ba1_prep reads them.
+// Every thread of the workgroup gets here (two barriers); the caller's barrier behind the previous frame's write-out orders the
+// reuse of `srec`.
+GL_DEV void ba1_front(double* smem, const int f, kargs_t* ka, const size_t srec) {
+  asm volatile("" : "+s"(ka));  // (its own reads of the argument segment: nothing shared with, or kept for, the passes)
+  const BaK __attribute__((address_space(4)))& k = ka->k;
+  const int L = ka->L, NW = ka->G, NT = 64 * NW;  // (from the argument segment: the launch dimensions would be hoisted and kept)
+  // An opaque copy of the thread index: what the front derives from it (lane masks, LDS addresses) is invariant over the frames of
+  // a persistent workgroup, and hoisted out of the frame loop it stayed live across the passes (eight spilled VGPRs).
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, wave = tid >> 6;
+  const size_t gbase = (size_t)f * L;
+  const double* const Xw = ka->pts_io + gbase * 3;
+  const double* const obs = ka->obs_all + gbase * 3;
+  const int32_t* const oct = ka->oct_all + gbase;
+  const int32_t* const assoc_in = ka->assoc_all + gbase;
+  const double* const d2_in = ka->d2_all + gbase;
+  const uint8_t* const cflags = ka->gm.flags;
+  const double gate = k.gate_chi2;
+  int32_t* const park = (int32_t*)(smem + kLdsUn);  // [0, MCAP): flag words, [MCAP, 2 MCAP): associations, by permuted index
+  int* const cnt = park + 2 * MCAP;                 // [4][NWC] non-degenerate-component points per (round, wave), then [4][NWC] empty slots
+  double x_[4][3], o_[4][3], d_[4];
+  int oc_[4], a_[4], fl_[4];
+  // every load of the thread's four rounds is requested before the first is used (clamped index: nothing to branch around)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int lc = min(j * NT + tid, L - 1);
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+      x_[j][e] = Xw[(size_t)lc * 3 + e];
+      o_[j][e] = obs[(size_t)lc * 3 + e];
+    }
+    oc_[j] = oct[lc];
+    a_[j] = assoc_in[lc];
+    d_[j] = d2_in[lc];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool in = j * NT + tid < L;
+    int a = a_[j];
+    if (gate >= 0 && !(d_[j] <= gate)) a = -1;
+    if (oc_[j] < 0) a = -1;
+    int fl = 0;
+    if (in && oc_[j] >= 0) {
+      fl = F_EXISTS | ((oc_[j] & 7) << 8);
+      if (!(o_[j][2] < 0)) fl |= F_STEREO;
+      if (a >= 0) fl |= F_ASSOC | ((cflags[a] & 1) ? F_DEG : 0);
+    }
+    a_[j] = a;
+    fl_[j] = fl;
+    const unsigned long long bal = __ballot((fl & (F_ASSOC | F_DEG)) == F_ASSOC);  // associated and not degenerate
+    const unsigned long long bal0 = __ballot(in && fl == 0);                        // no map point in the slot
+    if (lane == 0) {
+      cnt[j * NWC + wave] = __popcll(bal);
+      cnt[(4 + j) * NWC + wave] = __popcll(bal0);
+    }
+  }
+  __syncthreads();
+  int total = 0, total0 = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int w = 0; w < NWC; ++w)
+      if (w < NW) {
+        total += cnt[j * NWC + w];
+        total0 += cnt[(4 + j) * NWC + w];
+      }
+  const int n_others = L - total - total0, n_exist = L - total0;
+  const double ifx = 1.0 / k.fx, ify = 1.0 / k.fy;
+  const double cx = k.cx, cy = k.cy;
+  const PrepView pv = prep_view(ka->pn_all, ka->nwg, L);
+  int base = 0, base0 = 0;  // non-degenerate-component points / empty slots before this (round, wave)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int w = 0; w < NWC; ++w)
+      if (w < wave) {
+        base += cnt[j * NWC + w];
+        base0 += cnt[(4 + j) * NWC + w];
+      }
+    const int l = j * NT + tid;
+    const bool in = l < L;
+    const bool isnd = (fl_[j] & (F_ASSOC | F_DEG)) == F_ASSOC;
+    const bool isempty = in && fl_[j] == 0;
+    const unsigned long long bal = __ballot(isnd), bal0 = __ballot(isempty);
+    const int before = base + __popcll(bal & ((1ull << lane) - 1ull));
+    const int before0 = base0 + __popcll(bal0 & ((1ull << lane) - 1ull));
+    if (in) {
+      const int lp = isempty ? n_exist + before0 : isnd ? n_others + before : l - before - before0;  // stable in all three classes
+#pragma unroll
+      for (int e = 0; e < 3; ++e) smem[kLdsSp + e * MCAP + lp] = x_[j][e];
+      smem[kLdsChir + lp] = 0.0;
+      park[lp] = fl_[j];
+      park[MCAP + lp] = a_[j];
+      const size_t gp = srec + lp;
+      pv.perm[gp] = l;
+      pv.assoc_p[gp] = a_[j];
+      pv.gobn[gp * 3] = (o_[j][0] - cx) * ifx;
+      pv.gobn[gp * 3 + 1] = (o_[j][1] - cy) * ify;
+      pv.gobn[gp * 3 + 2] = (o_[j][2] - cx) * ifx;
+    }
+#pragma unroll
+    for (int w = 0; w < NWC; ++w)
+      if (w >= wave && w < NW) {  // the rest of this round: the bases now count everything before round j + 1
+        base += cnt[j * NWC + w];
+        base0 += cnt[(4 + j) * NWC + w];
+      }
+  }
+  __syncthreads();
+}
+
 GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   // the arguments the set-up and the passes use; the caller's OUTPUT arrays are read from the argument segment again where the
   // results are written (an opaque copy of the pointer: the compiler may not keep those ten pointers live across the passes)
@@ -2050,11 +2174,14 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
   const size_t gbase = (size_t)f * L;
   // launch scratch written by k_ba1_prep, read-only here: plane records, normalised observations, permutation, flags,
   // gated associations (all but perm in the permuted order)
-  const PrepView pv = prep_view(pn_all, B, L);
+  // (the fused front, ba1_front: the records are this WORKGROUP's, made below, and there is one set per workgroup of the launch)
+  const bool front = kFront && ka->front != 0;
+  const size_t srec = front ? (size_t)blockIdx.x * L : gbase;
+  const PrepView pv = prep_view(pn_all, front ? ka->nwg : B, L);
   const cdouble_g* gnd = (const cdouble_g*)gm.plane4;
-  const double* gobn = pv.gobn + gbase * 3;
-  const int32_t* gperm = pv.perm + gbase;
-  const int32_t* gassoc = pv.assoc_p + gbase;
+  const double* gobn = pv.gobn + srec * 3;
+  const int32_t* gperm = pv.perm + srec;
+  const int32_t* gassoc = pv.assoc_p + srec;
   const Uni U{uni(k.bf / k.fx), uni(k.ba_lambda2)};
   if (kFixed) {  // this frame's slices of the fixed-observer records (k_ba1_prep), its key-frames' poses into LDS
     D.F = fxv.F;
@@ -2070,7 +2197,19 @@ GL_DEV void ba1_fast_frame(double* smem, const unsigned fblock, kargs_t* ka) {
     *(int*)(R.tot + 61) = 0;  // a poll of the exchange gave up (SPREAD)
     R.tot[62] = 0.0;          // edge statistics {edges x trials, edges x outer iterations} as two ints (optimize_fast)
   }
-  {
+  if (kFront && front) {
+    ba1_front(smem, f, ka, srec);
+    const int32_t* const park = (const int32_t*)D.un;  // slot i of this thread is permuted point tid + 64 G i: its parked words
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int l = mp.base + slot_off(mp, i);
+      if (i < mp.S && l < L) {
+        fw_or(fw, i, park[l] & 0xffff);
+        if (kResident) aw_set(aw, i, park[MCAP + l]);
+        fw_activity(fw, i);
+      }
+    }
+  } else {
     const int ns = kSpread ? 1 : mp.S;
 #pragma unroll 1
     for (int i = 0; i < ns; ++i) {

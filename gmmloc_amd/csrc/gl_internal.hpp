@@ -113,6 +113,7 @@ struct Options {
   double ba_shape = -1;         // gl_track_frames refine: -1 auto, 0 one workgroup per frame, 1 one point per thread
   double ba_step32 = 0;         // 1: point step from an fp32 cache of the pass-A solve (faster, not the default)
   double ba_persist = 1;        // 1: the batch-shaped refine runs as persistent workgroups that draw their frames from a queue (0: one block per frame; A/B)
+  double ba_front = 1;          // 1: a batch-shaped gl_track_frames makes each frame's records in the refine's own set-up (0: k_ba1_prep; A/B, tests)
   double ba_slow = 0;           // 1: general kernel k_ba1 also for M <= 2000 (A/B)
   double ba_fixed_pack = 0;     // 1: gl_track_frames_anchored with fixed observers always through the general kernel (k_track_pack -> k_ba_gen; A/B, tests)
   double pose_waves = 0;        // gl_optimize_current_pose: 0 auto, 1 / 4 / 8 waves per frame
@@ -309,6 +310,9 @@ struct Ba1Layout {
   // on-chip path, from the start again (a launch runs one of the two kernels): per point the records of k_ba1_prep
   // (prep_view: 36 B); the frame queue of the persistent DENSE workgroups (an int); per frame the prior edge's inverse
   // measurement {R, t} (12 doubles)
+  // front: the refine makes those records in its own set-up (the fused front, gl_ba_fast_impl.hpp: ba1_front), k_ba1_prep does not
+  // run, and `rec` holds one frame's worth per WORKGROUP of the launch instead of per frame
+  bool front;
   size_t rec, frame_ctr, prior_mi;
   // latency shape only: per frame 2 G x 64 exchange words and {abort, done}; the staging area of its results
   // {points B x L x 3 | pose B x 8 | association B x L}, whose inner split the kernel keeps
@@ -318,7 +322,7 @@ struct Ba1Layout {
   size_t frt, fobn, foct, chif;
   size_t end;
 };
-int ba1_layout(Ctx* c, int B, int L, int F, bool prior, bool fast, Ba1Layout* out);
+int ba1_layout(Ctx* c, int B, int L, int F, bool prior, bool fast, Ba1Layout* out, bool front_ok = false, int K = 0);
 
 // launchers implemented across the .hip files
 int launch_build_components(Ctx* c, Gmm* g);

@@ -132,6 +132,8 @@ void* gl_ctx_stream(gl_ctx_t* ctx);
  *   ba_shape (-1 auto | 0 one workgroup per frame | 1 one point per thread; same bits either way),
  *   ba_persist (1; 0: the batch-shaped refine of gl_track_frames as one block per frame instead of persistent workgroups drawing frames
  *     from a queue - same bits; A/B),
+ *   ba_front (1; 0: a batch-shaped gl_track_frames without d2 output prepares every frame's records in a kernel of its own instead of
+ *     in the refine's set-up - same bits; A/B, tests),
  *   ba_step32 (1: fp32-cached point step in gl_track_frames, faster, NOT bit-compatible with the default),
  *   assoc_grid (0: every association is the plain N x K sweep, never the cell index),
  *   assoc_screen32 (0; 1: every all-pairs sweep - GL_ASSOC_EXHAUSTIVE, GL_ASSOC_BRUTE where it sweeps, the points the cell index

@@ -32,6 +32,7 @@ from tests import local_map_scenes as LS
 from tests import map_edit_ref as ER
 from tests import map_edit_scenes as ES
 from tests.chain_glue import TH_LOCAL, TH_MM
+from tests.gpu_helpers import T, to_dev
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -79,10 +80,6 @@ def options(ctx, **kw):
     finally:
         for k, v in saved.items():
             ctx.set_option(k, v)
-
-
-def T(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def H(torch, d):
@@ -502,11 +499,11 @@ def _check_search_local_points(oracle, out, B=2, NF=300, NP=700):
 # ---------------------------------------------------------------------------------------------------------------- the resident map
 @case("update_map_points", ["update_map_points"], ((40,), (3000,)))
 def _update_map_points(torch, ctx, extra):
-    from tests.test_gpu_map_points import dev, mixed_map, sentinel
+    from tests.test_gpu_map_points import mixed_map, sentinel
     m = mixed_map(11, extra=extra)
     NP = len(m["mp"]["obs_ptr"]) - 1
-    o = dev(torch, sentinel(NP))
-    api.update_map_points(ctx, dev(torch, m["kf"]), dev(torch, m["mp"]), o)
+    o = to_dev(torch, sentinel(NP))
+    api.update_map_points(ctx, to_dev(torch, m["kf"]), to_dev(torch, m["mp"]), o)
     out = H(torch, o)
     assert (out["desc"] != 0xA5).any(1).sum() > NP // 2
     return out
@@ -537,7 +534,7 @@ def _window_scene(name):
 
 
 def _update_connections(torch, ctx, name, B, with_count):
-    from tests.test_gpu_ba_window import conn_out, device_connections, to_dev
+    from tests.test_gpu_ba_window import conn_out, device_connections
     m, ba, rows = _window_scene(name)
     out = device_connections(torch, ctx, to_dev(torch, m), rows[:B], conn_out(B, 64, m["kf_mp"].shape[0] if with_count else None))
     assert (out["n_conn"] >= 1).sum() >= B - 2 and (out["conn_w"][:, 0] > 0).sum() >= B - 2, out["n_conn"]  # (every window of `tiny` lists its single largest)
@@ -559,7 +556,7 @@ def _window_ref(name):
 
 @case("ba_window_build", ["ba_window_build"], (("tiny",), ("small",)))
 def _ba_window_build(torch, ctx, name):
-    from tests.test_gpu_ba_window import device_build, to_dev
+    from tests.test_gpu_ba_window import device_build
     m, ba, rows = _window_scene(name)
     out = device_build(torch, ctx, to_dev(torch, m), to_dev(torch, ba), rows, BS.empty_slab(len(rows), _window_ref(name)[0]))
     assert (out["sizes"][:, 2] > 0).any() and not (out["status"] & BR.TRUNCATED).any()
@@ -568,7 +565,7 @@ def _ba_window_build(torch, ctx, name):
 
 @case("ba_window_apply", ["ba_window_apply"], (("tiny",), ("small",)))
 def _ba_window_apply(torch, ctx, name):
-    from tests.test_gpu_ba_window import fake_ba_outputs, to_dev
+    from tests.test_gpu_ba_window import fake_ba_outputs
     m, ba, rows = _window_scene(name)
     slab, dropped, erase, iters = fake_ba_outputs(_window_ref(name)[1], np.random.default_rng(9))
     md, bd = to_dev(torch, m), to_dev(torch, ba)
@@ -611,7 +608,6 @@ SLAB_OUT = BR.WINDOW_ARRAYS + ("sizes", "status", "dropped", "erase", "iters", "
 @case("joint_optimization_from_map", ["joint_optimization_from_map"], ((False,), (True,)),
       check=lambda oracle, out: _check_from_map(oracle, out))
 def _from_map(torch, ctx, big):
-    from tests.test_gpu_ba_window import to_dev
     m, ba, kf, _, _ = _geo_scene(big)
     md, bd = to_dev(torch, m), to_dev(torch, ba)
     r = api.joint_optimization_from_map(ctx, gmm_of(ctx), CAM(), PRM(), md, bd, kf, GEO_CAPS[big])
@@ -650,7 +646,6 @@ def _edit_scene(name):
 
 @case("cull_keyframes", ["cull_keyframes"], (("tiny",), ("small",)))
 def _cull(torch, ctx, name):
-    from tests.test_gpu_ba_window import to_dev
     from tests.test_gpu_map_edit import cull_out, device_cull, lists_of
     sc = _edit_scene(name)
     Ccap = len(sc["cand"]) + 6
@@ -674,7 +669,6 @@ PASS_KEYS = ("mp_valid", "kf_valid", "kf_mp", "obs_ptr")
 
 @case("mapping_pass_from_map", ["mapping_pass_from_map"], ((False,), (True,)), check=lambda oracle, out: _check_pass(oracle, out))
 def _pass(torch, ctx, big):
-    from tests.test_gpu_ba_window import to_dev
     m, _, kf, ba, depth = _geo_scene(big)
     md, bd = to_dev(torch, m), to_dev(torch, ba)
     rk = T(torch, ES.first_entry_kf(m))

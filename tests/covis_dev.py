@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from gmmloc_amd import api, covis
-from tests.test_gpu_context_state import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
+from tests.context_pass import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
 from tests.test_gpu_map_stats import Guarded
 
 GRAPH_KEYS = ("cov_kf", "cov_w", "cov_n", "cov_nord", "best_cov")

@@ -11,7 +11,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "gmmloc_hip/gmm_adapter.hpp"
+#include "driver_io.hpp"
 
 template <class T>
 static void rd(FILE* f, T* p, size_t n) {
@@ -26,10 +26,7 @@ int main(int argc, char** argv) {
   if (argc != 4 && argc != 5) return 2;  // model, frame, output [, gl_params as raw bytes: a non-default configuration]
   try {
     gmmloc_hip::GMM gmm;
-    if (!gmmloc_hip::GMM::loadGMMModel(argv[1], gmm)) {
-      fprintf(stderr, "loadGMMModel: %s\n", gmmloc_hip::GMM::last_error());
-      return 1;
-    }
+    if (!load_model(argv[1], gmm)) return 1;
     FILE* f = fopen(argv[2], "rb");
     if (!f) return 1;
     int32_t MN[4];

@@ -9,7 +9,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "gmmloc_hip/gmm_adapter.hpp"
+#include "driver_io.hpp"
 
 template <class T>
 static void rd(FILE* f, T* p, size_t n) {
@@ -24,10 +24,7 @@ int main(int argc, char** argv) {
   if (argc != 5) return 2;
   try {
     gmmloc_hip::GMM gmm;
-    if (!gmmloc_hip::GMM::loadGMMModel(argv[1], gmm)) {
-      fprintf(stderr, "loadGMMModel: %s\n", gmmloc_hip::GMM::last_error());
-      return 1;
-    }
+    if (!load_model(argv[1], gmm)) return 1;
     if (!gmm.loadVocabulary(argv[2])) {
       fprintf(stderr, "loadVocabulary: %s\n", gmmloc_hip::GMM::last_error());
       return 1;

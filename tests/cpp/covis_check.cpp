@@ -9,44 +9,15 @@
 // two lists of bestCovisible, each behind its length; {status, n_tgt} + tgt_kf; {status, n_tgt, n_cand} + tgt_kf + cand_mp; then,
 // downloaded: cov_kf, cov_w (NKF x Wcap), cov_n, cov_nord, best_cov (NKF).
 #include <cstdio>
-#include <fstream>
-#include <iostream>
 
-#include "gmmloc_hip/gmm_adapter.hpp"
+#include "driver_io.hpp"
 
 using namespace gmmloc_hip;
-
-template <class T>
-static std::vector<T> rd(std::ifstream& f, size_t n) {
-  std::vector<T> v(n);
-  f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(n * sizeof(T)));
-  return v;
-}
-template <class T>
-static void wr(std::ofstream& f, const std::vector<T>& v) {
-  f.write(reinterpret_cast<const char*>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
-}
-template <class T>
-static T* up(gl_ctx_t* ctx, const std::vector<T>& v) {
-  void* p = nullptr;
-  check(gl_malloc(ctx, v.size() * sizeof(T) + 8, &p), "gl_malloc");
-  if (!v.empty()) check(gl_memcpy_h2d(ctx, p, v.data(), v.size() * sizeof(T)), "h2d");
-  return static_cast<T*>(p);
-}
-template <class T>
-static std::vector<T> down(gl_ctx_t* ctx, const T* p, size_t n) {
-  std::vector<T> v(n);
-  if (n) check(gl_memcpy_d2h(ctx, v.data(), p, n * sizeof(T)), "d2h");
-  return v;
-}
 
 int main(int argc, char** argv) {
   if (argc < 4) return 2;
   GMM model;
-  if (!GMM::loadGMMModel(argv[1], model)) {
-    std::cerr << "loadGMMModel: " << GMM::last_error() << "\n";
-    return 1;
-  }
+  if (!load_model(argv[1], model)) return 1;
   std::ifstream in(argv[2], std::ios::binary);
   const auto hd = rd<int32_t>(in, 16);
   const int32_t NMP = hd[0], NKF = hd[1], NFK = hd[2], NOBS = hd[3], Wcap = hd[4], Ccap = hd[5], n_upd = hd[6], n_rm = hd[7], n_upd2 = hd[8];

@@ -13,44 +13,15 @@
 // downloaded: visible, found, ref_idx (NMPcap), n_cand + cand (cand_cap), mp_valid, kf_mp, obs_ptr, obs_kf, obs_feat (the new NOBS of
 // them), mp_ref_kf.
 #include <cstdio>
-#include <fstream>
-#include <iostream>
 
-#include "gmmloc_hip/gmm_adapter.hpp"
+#include "driver_io.hpp"
 
 using namespace gmmloc_hip;
-
-template <class T>
-static std::vector<T> rd(std::ifstream& f, size_t n) {
-  std::vector<T> v(n);
-  f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(n * sizeof(T)));
-  return v;
-}
-template <class T>
-static void wr(std::ofstream& f, const std::vector<T>& v) {
-  f.write(reinterpret_cast<const char*>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
-}
-template <class T>
-static T* up(gl_ctx_t* ctx, const std::vector<T>& v) {
-  void* p = nullptr;
-  check(gl_malloc(ctx, v.size() * sizeof(T) + 8, &p), "gl_malloc");
-  if (!v.empty()) check(gl_memcpy_h2d(ctx, p, v.data(), v.size() * sizeof(T)), "h2d");
-  return static_cast<T*>(p);
-}
-template <class T>
-static std::vector<T> down(gl_ctx_t* ctx, const T* p, size_t n) {
-  std::vector<T> v(n);
-  if (n) check(gl_memcpy_d2h(ctx, v.data(), p, n * sizeof(T)), "d2h");
-  return v;
-}
 
 int main(int argc, char** argv) {
   if (argc < 4) return 2;
   GMM model;
-  if (!GMM::loadGMMModel(argv[1], model)) {
-    std::cerr << "loadGMMModel: " << GMM::last_error() << "\n";
-    return 1;
-  }
+  if (!load_model(argv[1], model)) return 1;
   std::ifstream in(argv[2], std::ios::binary);
   const auto hd = rd<int32_t>(in, 16);
   const int32_t NMP = hd[0], NKF = hd[1], NFK = hd[2], NOBS = hd[3], kf_row = hd[4], kf_first = hd[5], NMPcap = hd[6], cand_cap = hd[7], n_cand = hd[8];

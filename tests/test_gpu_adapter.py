@@ -2,17 +2,14 @@
 associate / renderView+searchCorrespondence / queryPoint, the interface a gmmloc maintainer links) must give what
 the Python host gives through the same C-ABI: a g++-built driver runs one frame and the outputs are compared
 bit for bit."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import gmmloc_amd
 from gmmloc_amd import api
+from tests import cpp_driver
 from tests.test_gpu_pose import make_frames
 from tests.test_gpu_ba import make_ba_problem, run_gpu
-from tests.test_host_cabi import build_adapter_check
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +24,7 @@ def adapter_case(gpu, map_v1, gt_sync, tmp_path, cam, prm, default=False):
     import ctypes
     torch, ctx = gpu
     mean, cov = map_v1
-    exe = build_adapter_check(tmp_path)
+    exe = cpp_driver.build("adapter_check", tmp_path)
     g0 = api.GMM(ctx, mean, cov)
     g0.save(tmp_path / "m.gmm")
     g = api.GMM.load(ctx, tmp_path / "m.gmm")
@@ -52,15 +49,12 @@ def adapter_case(gpu, map_v1, gt_sync, tmp_path, cam, prm, default=False):
         pb_assoc.tofile(fh)
         for key, dt in (("obs_ptr", np.int32), ("obs_pose", np.int32), ("obs_uvr", np.float64), ("obs_oct", np.int32)):
             np.ascontiguousarray(pb[key], dt).tofile(fh)
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.dirname(gmmloc_amd._lib.LIB_PATH) + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
     extra = []
     if not default:
         with open(tmp_path / "params.bin", "wb") as fh:
             fh.write(ctypes.string_at(ctypes.byref(prm.c()), ctypes.sizeof(prm.c())))
-        extra = [str(tmp_path / "params.bin")]
-    r = subprocess.run([exe, str(tmp_path / "m.gmm"), str(tmp_path / "frame.bin"), str(tmp_path / "out.bin")] + extra, env=env,
-                       capture_output=True, text=True, timeout=300)
+        extra = [tmp_path / "params.bin"]
+    r = cpp_driver.run(exe, tmp_path / "m.gmm", tmp_path / "frame.bin", tmp_path / "out.bin", *extra)
     assert r.returncode == 0, r.stderr
     assert "components %d" % mean.shape[0] in r.stdout
     print(r.stdout)

@@ -9,14 +9,11 @@ from gmmloc_amd import api
 from tests import ba_window_ref as R
 from tests import ba_window_scenes as S
 from tests import map_point_ref as M
+from tests.gpu_helpers import to_dev
 
 pytestmark = pytest.mark.gpu
 
 SLAB_KEYS = R.WINDOW_ARRAYS + ("sizes", "status")
-
-
-def to_dev(torch, d):
-    return {k: (torch.from_numpy(np.ascontiguousarray(v)).cuda() if isinstance(v, np.ndarray) else v) for k, v in d.items() if v is not None}
 
 
 def to_host(d):

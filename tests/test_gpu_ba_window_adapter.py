@@ -2,36 +2,22 @@
 jointOptimizationFromMap) must give what the Python host gives through the same C-ABI: a g++-built driver
 (tests/cpp/ba_window_check.cpp) flattens the geometric scene of tests/ba_window_scenes.py, keeps it on the device, runs one key-frame's
 local BA from it, and every row it returns or leaves on the device is compared bit for bit."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import gmmloc_amd
 from gmmloc_amd import api
 from tests import ba_window_ref as R
 from tests import ba_window_scenes as S
-from tests.conftest import ROOT
+from tests import cpp_driver
 
 pytestmark = pytest.mark.gpu
-
-
-def build_driver(out_dir):
-    exe = os.path.join(str(out_dir), "ba_window_check")
-    libdir = os.path.dirname(gmmloc_amd._lib.LIB_PATH)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "ba_window_check.cpp"),
-           "-L" + libdir, "-lgmmloc_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def test_cpp_from_map_matches_python_host(gpu, map_v1, gt_sync, tmp_path):
     torch, ctx = gpu
     mean, cov = map_v1
     cam, prm = api.Camera(), api.Params()
-    exe = build_driver(tmp_path)
+    exe = cpp_driver.build("ba_window_check", tmp_path)
     g0 = api.GMM(ctx, mean, cov)
     g0.save(tmp_path / "m.gmm")
     g = api.GMM.load(ctx, tmp_path / "m.gmm")
@@ -42,10 +28,7 @@ def test_cpp_from_map_matches_python_host(gpu, map_v1, gt_sync, tmp_path):
         np.array([cam.fx, cam.fy, cam.cx, cam.cy, cam.bf], np.float64).tofile(fh)
         for a in (m["mp_valid"], m["kf_valid"], m["kf_mp"], m["mp_pos"], ba["kf_pose"], ba["kf_uvr"], ba["kf_oct"], ba["mp_assoc"]):
             np.ascontiguousarray(a).tofile(fh)
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.dirname(gmmloc_amd._lib.LIB_PATH) + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([exe, str(tmp_path / "m.gmm"), str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")], env=env, capture_output=True, text=True,
-                       timeout=300)
+    r = cpp_driver.run(exe, tmp_path / "m.gmm", tmp_path / "scene.bin", tmp_path / "out.bin")
     assert r.returncode == 0, r.stderr
     print(r.stdout)
     out = open(tmp_path / "out.bin", "rb")

@@ -3,14 +3,15 @@ the capacity rule, randomised vocabularies up to the shape of the ORB vocabulary
 context's history, and the C++ adapter.  The hand-built cases are in tests/test_gpu_bow_cases.py."""
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from gmmloc_amd import synth
 from tests import bow_ref as R
-from tests.test_gpu_bow_cases import FILL, OUT_KEYS, T, device_transform, device_voc, same, stop_on_device_error  # noqa: F401 (autouse fixture)
+from tests import cpp_driver
+from tests.gpu_helpers import stop_on_device_error  # noqa: F401 (autouse fixture)
+from tests.test_gpu_bow_cases import FILL, OUT_KEYS, T, device_transform, device_voc, same
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -238,7 +239,7 @@ def _large_call(torch, ctx):
 def test_same_bits_whatever_the_context_has_been_through(gpu):
     """the first call of a new context == after larger calls == on scratch filled with 0x00 / 0xFF, as it stands and as it is allocated"""
     from tests.context_cases import close_context, new_context
-    from tests.test_gpu_context_state import on_new_context, run
+    from tests.context_pass import on_new_context, run
     torch = gpu[0]
     ref = restated("small", 17, 117, (2, 1, 0.0), 1)
     same(on_new_context(torch, _small_call), ref, "new context")
@@ -256,22 +257,10 @@ def test_same_bits_whatever_the_context_has_been_through(gpu):
 
 
 # ---- the C++ adapter ---------------------------------------------------------------------------------------------------------------------------
-def build_bow_check(out_dir):
-    """g++-build tests/cpp/bow_check.cpp against include/gmmloc_hip/gmm_adapter.hpp and the in-tree library"""
-    from gmmloc_amd import _lib
-    exe = os.path.join(str(out_dir), "bow_check")
-    libdir = os.path.dirname(_lib.LIB_PATH)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "bow_check.cpp"),
-           "-L" + libdir, "-lgmmloc_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
 def test_cpp_adapter_gives_the_bytes_of_the_python_host(gpu, tmp_path):
-    from gmmloc_amd import _lib, bow
+    from gmmloc_amd import bow
     torch, ctx = gpu
-    exe = build_bow_check(tmp_path)
+    exe = cpp_driver.build("bow_check", tmp_path)
     v = host_voc("small")[0]
     synth.write_vocabulary_file(tmp_path / "voc.bin", v)
     N, NN, levelsup = 203, 16, 1
@@ -280,10 +269,7 @@ def test_cpp_adapter_gives_the_bytes_of_the_python_host(gpu, tmp_path):
         np.array([N, levelsup, NN], np.int32).tofile(fh)
         desc.tofile(fh)
         octave.tofile(fh)
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.dirname(_lib.LIB_PATH) + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([exe, os.path.join(GOLDEN, "v1.gmm"), str(tmp_path / "voc.bin"), str(tmp_path / "frame.bin"), str(tmp_path / "out.bin")], env=env,
-                       capture_output=True, text=True, timeout=300)
+    r = cpp_driver.run(exe, os.path.join(GOLDEN, "v1.gmm"), tmp_path / "voc.bin", tmp_path / "frame.bin", tmp_path / "out.bin")
     assert r.returncode == 0, r.stderr
     out = open(tmp_path / "out.bin", "rb")
     rd = lambda n: np.fromfile(out, np.int32, n)

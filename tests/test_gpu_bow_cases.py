@@ -1,28 +1,21 @@
 """gl_voc_create / gl_bow_transform on the device against the declared outputs of tests/bow_cases.py: word, node and weight bits per
 feature, and the feature vector as CSR on sentinel-filled buffers (what lies behind a frame's counts keeps the sentinel)."""
+import functools
+
 import numpy as np
 import pytest
 
 from tests import bow_cases as BC
 from tests import bow_ref as R
+from tests import gpu_helpers
+from tests.gpu_helpers import stop_on_device_error  # noqa: F401 (the fixture is autouse)
 
 pytestmark = pytest.mark.gpu
 FILL = -7
 OUT_KEYS = ("word_id", "node", "weight", "nnode", "node_id", "node_ptr", "node_idx", "status")
 
 
-@pytest.fixture(autouse=True)
-def stop_on_device_error(gpu):
-    """a HIP error met by a test is a finding: the session ends there, nothing more is started on the device"""
-    yield
-    try:
-        gpu[0].cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit("device error, nothing more is started: %s" % e, returncode=3)
-
-
-def T(torch, a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()  # (a copy: the shared inputs are read-only arrays)
+T = functools.partial(gpu_helpers.T, copy=True)  # (a copy: the shared inputs are read-only arrays)
 
 
 def device_voc(ctx, v):

@@ -16,6 +16,7 @@ from gmmloc_amd import api, synth
 from tests import chain_glue as G
 from tests import configs
 from tests.configs import ANISO, CONFIGS
+from tests.gpu_helpers import T
 from tests.test_gpu_pose import TOL_R, TOL_T, make_frames, pose_err
 from tests.test_gpu_pose import run_gpu as run_pose
 from tests.test_gpu_track import _run_track, oracle_track
@@ -24,10 +25,6 @@ from tests.test_oracle_configs import pose_frames, track_frames_of  # the frames
 pytestmark = pytest.mark.gpu
 
 cfgs = pytest.mark.parametrize("cfg", CONFIGS, ids=repr)
-
-
-def T(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 # ------------------------------------------------------------------ gl_optimize_current_pose
@@ -644,7 +641,8 @@ def test_joint_optimization_from_map(gpu, oracle, map_v1, gt_sync, cfg):
     from tests import ba_window_ref as R
     from tests import ba_window_scenes as S
     from tests.test_gpu_ba import check
-    from tests.test_gpu_ba_window import to_dev, to_host
+    from tests.gpu_helpers import to_dev
+    from tests.test_gpu_ba_window import to_host
     torch, ctx = gpu
     mean, cov = map_v1
     cam, prm, oprm = cfg.camera(), cfg.params(), cfg.orc_params(oracle)

@@ -21,64 +21,19 @@ module's own:
   timing    with the timers on, and with the statistics buffers registered: R[c]; a de-registered buffer is not written again.
 
 Equality is np.array_equal(..., equal_nan=True) on every key, same keys, shapes and dtypes."""
-import numpy as np
 import pytest
 
+from tests import context_pass
 from tests.context_cases import BY_NAME, CASES, TIMING_CASES, close_context, new_context
+from tests.context_pass import on_new_context, run, same, torch  # noqa: F401 (torch: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
 cases = pytest.mark.parametrize("c", CASES, ids=repr)
-_cold = {}  # (case name, which) -> outputs as the first call of a new context: made once, never modified
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU test collected without a GPU"
-    return torch
-
-
-def run(fn, torch, ctx):
-    """fn(torch, ctx) - but a HIP error is a finding, not a mismatch: the session ends there instead of starting more work on a device
-    that has just faulted"""
-    from gmmloc_amd import api
-    try:
-        return fn(torch, ctx)
-    except (api.GLError, RuntimeError) as e:
-        if any(w in str(e) for w in ("HIP", "hip", "illegal memory access", "error -4")):
-            pytest.exit("device error, nothing more is started: %s" % e, returncode=3)
-        raise
-
-
-def on_new_context(torch, fn, fill=None):
-    ctx = new_context()
-    try:
-        if fill is not None:
-            ctx.set_option("test_scratch_fill", fill)
-        return run(fn, torch, ctx)
-    finally:
-        close_context(ctx)
 
 
 def first_call(torch, c, which="small"):
-    key = (c.name, which)
-    if key not in _cold:
-        out = on_new_context(torch, getattr(c, which))
-        for v in out.values():
-            v.setflags(write=False)
-        _cold[key] = out
-    return _cold[key]
-
-
-def same(got, ref, c, leg):
-    assert sorted(got) == sorted(ref), (c.name, leg, sorted(got), sorted(ref))
-    for k in ref:
-        a, b = np.asarray(got[k]), ref[k]
-        assert a.dtype == b.dtype and a.shape == b.shape, (c.name, leg, k, a.dtype, b.dtype, a.shape, b.shape)
-        if not np.array_equal(a, b, equal_nan=True):
-            diff = ~((a == b) | ((a != a) & (b != b)))
-            raise AssertionError("case %s, leg %s, output %s: %d of %d elements differ" % (c.name, leg, k, int(diff.sum()), a.size))
+    return context_pass.first_call(torch, ("context_state", c.name, which), getattr(c, which))
 
 
 @cases
@@ -95,7 +50,7 @@ def test_shrink_and_regrow(torch, c):
     try:
         for leg, fn, ref in (("small first", c.small, ref_s), ("large after small", c.large, ref_l), ("small after large", c.small, ref_s),
                              ("large again", c.large, ref_l)):
-            same(run(fn, torch, ctx), ref, c, leg)
+            same(run(fn, torch, ctx), ref, c.name, leg)
     finally:
         close_context(ctx)
 
@@ -107,9 +62,9 @@ def test_after_everything_else(torch):
         for c in CASES:  # the polluter round
             run(c.large, torch, ctx)
         for c, ref in zip(CASES, refs):
-            same(run(c.small, torch, ctx), ref, c, "after every large call, table order")
+            same(run(c.small, torch, ctx), ref, c.name, "after every large call, table order")
         for c, ref in reversed(list(zip(CASES, refs))):
-            same(run(c.small, torch, ctx), ref, c, "after every large call, reverse order")
+            same(run(c.small, torch, ctx), ref, c.name, "after every large call, reverse order")
     finally:
         close_context(ctx)
 
@@ -123,10 +78,10 @@ def test_poisoned(torch, c, v):
         run(c.large, torch, ctx)
         ctx.set_option("test_scratch_fill", v)  # every block the context holds, now
         assert ctx.get_option("test_scratch_fill") == v
-        same(run(c.small, torch, ctx), ref, c, "blocks of the large call filled with 0x%02X" % v)
+        same(run(c.small, torch, ctx), ref, c.name, "blocks of the large call filled with 0x%02X" % v)
     finally:
         close_context(ctx)
-    same(on_new_context(torch, c.small, fill=v), ref, c, "new context, blocks filled with 0x%02X as they are allocated" % v)
+    same(on_new_context(torch, c.small, fill=v), ref, c.name, "new context, blocks filled with 0x%02X as they are allocated" % v)
 
 
 def test_scratch_fill_option(torch):
@@ -154,7 +109,7 @@ def test_timing_and_statistics(torch):
         ctx.timing(True)
         for _ in range(2):  # (the second round takes its events from the pool)
             for c, ref in zip(picked, refs):
-                same(run(c.small, torch, ctx), ref, c, "timers on")
+                same(run(c.small, torch, ctx), ref, c.name, "timers on")
         assert ctx.timing_read(api.TIMER_BA)[1] > 0 and ctx.timing_read(api.TIMER_REFINE_POSE)[1] > 0 and ctx.timing_read(api.TIMER_ASSOC)[1] > 0
         ctx.timing(False)
         SENT = -77
@@ -163,7 +118,7 @@ def test_timing_and_statistics(torch):
         ctx.set_stats_buffer(trials, iters)
         ctx.set_edge_stats_buffer(edges)
         for c, ref in zip(picked, refs):
-            same(run(c.small, torch, ctx), ref, c, "statistics buffers registered")
+            same(run(c.small, torch, ctx), ref, c.name, "statistics buffers registered")
             if c.name == "track_frames_batch_shape":  # (three frames: the refine writes their trial counts and edge sums)
                 assert (trials[:3] > 0).all() and (iters[:3] > 0).all() and (edges[:3] > 0).all(), "the registered buffers were never written"
         ctx.set_stats_buffer(None)  # n = 0
@@ -171,7 +126,7 @@ def test_timing_and_statistics(torch):
         for t in (trials, iters, edges):
             t.fill_(SENT)
         for c, ref in zip(picked, refs):
-            same(run(c.small, torch, ctx), ref, c, "statistics buffers de-registered")
+            same(run(c.small, torch, ctx), ref, c.name, "statistics buffers de-registered")
         torch.cuda.synchronize()
         assert all(bool((t == SENT).all()) for t in (trials, iters, edges)), "a de-registered statistics buffer was written"
     finally:

@@ -13,20 +13,11 @@ from tests import covis_cases as CC
 from tests import covis_dev as D
 from tests import covis_ref as R
 from tests import map_grow_scenes as GS
+from tests.gpu_helpers import stop_on_device_error  # noqa: F401 (the fixture is autouse)
 from tests.test_covis_ref import apply_step
 from tests.test_gpu_map_grow import refresh, upload, with_point_arrays
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def stop_on_device_error(gpu):
-    """a HIP error met by a test is a finding: the session ends there, nothing more is started on the device"""
-    yield
-    try:
-        gpu[0].cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit("device error, nothing more is started: %s" % e, returncode=3)
 
 
 def same_graph(got, want, what):

@@ -3,35 +3,21 @@ removeFromGraph, bestCovisible, searchInNeighborsInMap) must give what the Pytho
 (tests/cpp/covis_check.cpp) keeps a random map of tests/covis_cases.py and an empty graph on the device, updates every key-frame's
 connections, removes three rows, updates some again, asks for two lists of best covisibles and for the targets and candidates of
 searchInNeighbors; every list it returns and the graph it leaves on the device are compared bit for bit."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import gmmloc_amd
 from gmmloc_amd import api, covis
 from tests import covis_cases as CC
 from tests import covis_dev as D
-from tests.conftest import ROOT
+from tests import cpp_driver
 
 pytestmark = pytest.mark.gpu
-
-
-def build_driver(out_dir):
-    exe = os.path.join(str(out_dir), "covis_check")
-    libdir = os.path.dirname(gmmloc_amd._lib.LIB_PATH)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "covis_check.cpp"),
-           "-L" + libdir, "-lgmmloc_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def test_cpp_graph_matches_python_host(gpu, map_v1, tmp_path):
     torch, ctx = gpu
     mean, cov = map_v1
-    exe = build_driver(tmp_path)
+    exe = cpp_driver.build("covis_check", tmp_path)
     api.GMM(ctx, mean, cov).save(tmp_path / "m.gmm")
     m = CC.random_map(31)
     m["mp_valid"][np.random.default_rng(31).integers(0, CC.R_NMP, 40)] = 0
@@ -60,10 +46,7 @@ def test_cpp_graph_matches_python_host(gpu, map_v1, tmp_path):
         np.array(hd, np.int32).tofile(fh)
         for a in (m["mp_valid"], m["kf_valid"], m["kf_mp"], m["obs_ptr"], m["obs_kf"], np.array(upd, np.int32), np.array(rm, np.int32), np.array(upd2, np.int32)):
             np.ascontiguousarray(a).tofile(fh)
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.dirname(gmmloc_amd._lib.LIB_PATH) + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([exe, str(tmp_path / "m.gmm"), str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")], env=env, capture_output=True, text=True,
-                       timeout=300)
+    r = cpp_driver.run(exe, tmp_path / "m.gmm", tmp_path / "scene.bin", tmp_path / "out.bin")
     assert r.returncode == 0, r.stderr
     print(r.stdout)
     H = lambda t: t.cpu().numpy()

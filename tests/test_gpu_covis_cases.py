@@ -8,18 +8,9 @@ import pytest
 
 from tests import covis_cases as CC
 from tests import covis_dev as D
+from tests.gpu_helpers import stop_on_device_error  # noqa: F401 (the fixture is autouse)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def stop_on_device_error(gpu):
-    """a HIP error met by a test is a finding: the session ends there, nothing more is started on the device"""
-    yield
-    try:
-        gpu[0].cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit("device error, nothing more is started: %s" % e, returncode=3)
 
 
 @pytest.mark.parametrize("name", list(CC.UPDATE))

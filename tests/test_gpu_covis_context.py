@@ -1,8 +1,7 @@
 """The five calls of gmmloc_amd.covis and search_in_neighbors_from_map give the bits of the FIRST call of a new context whatever the
-context has been through - the pass of tests/test_gpu_map_stats_context.py for this module, with that file's pattern: on a cold
+context has been through - the pass of tests/context_pass.py for this module: on a cold
 context, after larger calls of themselves, after the other entry points of the resident map (which leave their marks in the two
 scratch blocks these calls use), with every scratch block filled with 0x00 / 0xFF, and with the timers on."""
-import copy
 import functools
 
 import numpy as np
@@ -12,10 +11,10 @@ from gmmloc_amd import api, covis
 from tests import covis_cases as CC
 from tests import covis_dev as D
 from tests import map_grow_scenes as GS
-from tests.context_cases import BY_NAME, close_context, gt_sync, map_v1, new_context
-from tests.test_gpu_context_state import on_new_context, run, torch  # noqa: F401 (torch: the module's fixture)
+from tests.context_cases import BY_NAME, gt_sync, map_v1
+from tests.context_pass import Pass, after_legs, at, poisoned, timers_on, torch  # noqa: F401 (torch: the module's fixture)
 from tests.test_gpu_covis import _host, _scene, cand_inputs
-from tests.test_gpu_map_grow_context import _add, _fuse, same
+from tests.test_gpu_map_grow_context import PASS as GROW  # (its prelude: map_add and map_fuse on the EuRoC-sized scene)
 
 pytestmark = pytest.mark.gpu
 
@@ -76,57 +75,22 @@ def _composite(torch, ctx, _):
 
 CALLS = {"graph": _graph, "graph_wide": _graph_wide, "fuse_candidates": _candidates, "search_in_neighbors_from_map": _composite}
 OTHERS = ("mapping_pass_from_map", "cull_keyframes", "map_remove", "ba_window_build", "update_map_points")
-_first = {}
-
-
-def first_call(torch, name):
-    if name not in _first:
-        _first[name] = on_new_context(torch, lambda t, c: CALLS[name](t, c, "small"))
-    return copy.deepcopy(_first[name])
+LARGE = tuple(at(fn, "large") for fn in CALLS.values())
+PASS = Pass("covis", CALLS, small=dict.fromkeys(CALLS, "small"), larger=lambda name: LARGE,
+            others=tuple(BY_NAME[other].large for other in OTHERS) + GROW.prelude, prelude=LARGE,
+            legs=("after the larger calls", "after the other map entry points"))
 
 
 @pytest.mark.parametrize("name", list(CALLS))
 def test_after_larger_calls_and_the_other_map_entry_points(torch, name):
-    fn = CALLS[name]
-    ref = first_call(torch, name)
-    ctx = new_context()
-    try:
-        same(run(lambda t, c: fn(t, c, "small"), torch, ctx), ref, (name, "first"))
-        for other in CALLS.values():
-            run(lambda t, c: other(t, c, "large"), torch, ctx)
-        same(run(lambda t, c: fn(t, c, "small"), torch, ctx), ref, (name, "after the larger calls"))
-        for other in OTHERS:
-            run(BY_NAME[other].large, torch, ctx)
-        run(lambda t, c: _add(t, c, "euroc"), torch, ctx)
-        run(lambda t, c: _fuse(t, c, "euroc"), torch, ctx)
-        same(run(lambda t, c: fn(t, c, "small"), torch, ctx), ref, (name, "after the other map entry points"))
-    finally:
-        close_context(ctx)
+    after_legs(torch, PASS, name)
 
 
 @pytest.mark.parametrize("v", [0x00, 0xFF], ids=["0x00", "0xFF"])
 @pytest.mark.parametrize("name", list(CALLS))
 def test_poisoned_scratch(torch, name, v):
-    fn = CALLS[name]
-    ref = first_call(torch, name)
-    ctx = new_context()
-    try:
-        for other in CALLS.values():
-            run(lambda t, c: other(t, c, "large"), torch, ctx)
-        ctx.set_option("test_scratch_fill", v)  # every block the context holds, now
-        same(run(lambda t, c: fn(t, c, "small"), torch, ctx), ref, (name, "blocks filled with 0x%02X" % v))
-    finally:
-        close_context(ctx)
-    same(on_new_context(torch, lambda t, c: fn(t, c, "small"), fill=v), ref, (name, "new context, blocks filled with 0x%02X as they are allocated" % v))
+    poisoned(torch, PASS, name, v)
 
 
 def test_timers_on(torch):
-    refs = {name: first_call(torch, name) for name in CALLS}
-    ctx = new_context()
-    try:
-        ctx.timing(True)
-        for _ in range(2):
-            for name, fn in CALLS.items():
-                same(run(lambda t, c: fn(t, c, "small"), torch, ctx), refs[name], (name, "timers on"))
-    finally:
-        close_context(ctx)
+    timers_on(torch, PASS)

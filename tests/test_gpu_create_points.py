@@ -19,6 +19,7 @@ from oracle import numpy_ref
 from tests import create_points_cases as cc
 from tests import create_points_ref as ref
 from tests import keyframe_cases as kc
+from tests.gpu_helpers import T, gmm_of, stop_on_device_error  # noqa: F401 (the fixture is autouse)
 from tests.test_create_points_ref import INT_KEYS, SEEDED_CAMS, check_ints, run_model, seeded_pairs
 
 pytestmark = pytest.mark.gpu
@@ -27,28 +28,6 @@ f32, f64 = np.float32, np.float64
 MAP_KEYS = ("kf_valid", "kf_mp", "mp_valid", "obs_ptr", "obs_kf")
 BA_KEYS = ("kf_pose", "kf_twc", "kf_uvr", "kf_oct")
 OUT_LISTS = ref.LIST_KEYS + ("new_pos",)
-_gmm = {}
-
-
-@pytest.fixture(autouse=True)
-def stop_on_device_error(gpu):
-    """a HIP error met by a test is a finding: the session ends there, nothing more is started on the device"""
-    yield
-    try:
-        gpu[0].cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit("device error, nothing more is started: %s" % e, returncode=3)
-
-
-def T(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def gmm_of(ctx, mean, cov):
-    key = (mean.tobytes(), cov.tobytes())
-    if key not in _gmm:
-        _gmm[key] = api.GMM(ctx, mean, cov.reshape(-1, 9))
-    return _gmm[key]
 
 
 def dev_scene(torch, sc):

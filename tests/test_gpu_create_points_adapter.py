@@ -2,35 +2,22 @@
 createMapPointsInMap) must give what the Python host gives through the same C-ABI: a g++-built driver (tests/cpp/create_points_check.cpp)
 takes the generated key-frames of tests/test_gpu_create_points.py in capacity buffers; every list it returns and every byte it leaves in
 the buffers is compared with map_grow.create_map_points_from_map's."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import gmmloc_amd
 from gmmloc_amd import api, map_grow
+from tests import cpp_driver
 from tests import create_points_cases as cc
-from tests.conftest import ROOT
-from tests.test_gpu_create_points import T, resident, stop_on_device_error  # noqa: F401 (the fixture is autouse here too)
+from tests.gpu_helpers import T, stop_on_device_error  # noqa: F401 (the fixture is autouse here too)
+from tests.test_gpu_create_points import resident
 from tests.test_gpu_map_grow import refresh
 
 pytestmark = pytest.mark.gpu
 
 
-def build_driver(out_dir):
-    exe = os.path.join(str(out_dir), "create_points_check")
-    libdir = os.path.dirname(gmmloc_amd._lib.LIB_PATH)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "create_points_check.cpp"),
-           "-L" + libdir, "-lgmmloc_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
 def test_cpp_create_points_matches_python_host(gpu, tmp_path):
     torch, ctx = gpu
-    exe = build_driver(tmp_path)
+    exe = cpp_driver.build("create_points_check", tmp_path)
     sc, nn = cc.generated(257, 6, 23), 4
     api.GMM(ctx, sc.mean, sc.cov.reshape(-1, 9)).save(tmp_path / "m.gmm")
     g = api.GMM.load(ctx, tmp_path / "m.gmm")  # (the map both hosts read: the file)
@@ -51,10 +38,7 @@ def test_cpp_create_points_matches_python_host(gpu, tmp_path):
                   H(bd["kf_uvr"]), H(bd["kf_oct"]), H(md["mp_pos"]), H(md["mp_normal"]), H(md["mp_max_dist"]), H(md["mp_min_dist"]), H(md["mp_desc"]),
                   H(bd["mp_assoc"]), H(rk)) + tuple(sc.kt[k] for k in ("angle", "desc", "depth", "nnode", "node_id", "node_ptr", "node_idx", "cand", "ncand")):
             np.ascontiguousarray(a).tofile(fh)
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.dirname(gmmloc_amd._lib.LIB_PATH) + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([exe, str(tmp_path / "m.gmm"), str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")], env=env, capture_output=True, text=True,
-                       timeout=300)
+    r = cpp_driver.run(exe, tmp_path / "m.gmm", tmp_path / "scene.bin", tmp_path / "out.bin")
     assert r.returncode == 0, r.stderr
     print(r.stdout)
     p = map_grow.create_map_points_from_map(ctx, g, cam, api.Params(), md, bd, ktd, 0, nn=nn, mb=float(mb), sizes=sizes, mp_ref_kf=rk)

@@ -1,5 +1,5 @@
 """create_map_points_on_map (gl_create_map_points_from_map alone) and create_map_points_from_map give the bits of the FIRST call of a new
-context whatever the context has been through - the pass of tests/test_gpu_key_frame_create_context.py with its helpers: after larger
+context whatever the context has been through - the pass of tests/context_pass.py for these two: after larger
 calls of themselves, after every other map entry point and the three per-pair pieces (which leave their own bytes in the scratch blocks
 the loop's stages use), with every scratch block filled with 0x00 / 0xFF, and with the timers on."""
 import numpy as np
@@ -7,10 +7,10 @@ import pytest
 
 from gmmloc_amd import api, map_grow
 from tests import create_points_cases as cc
-from tests.context_cases import BY_NAME, close_context, new_context
-from tests.test_gpu_context_state import on_new_context, run, torch  # noqa: F401 (torch: the module's fixture)
-from tests.test_gpu_create_points import BA_KEYS, MAP_KEYS, T, resident, snapshot
-from tests.test_gpu_map_grow_context import same
+from tests.context_cases import BY_NAME
+from tests.context_pass import Pass, after_legs, at, poisoned, timers_on, torch  # noqa: F401 (torch: the module's fixture)
+from tests.gpu_helpers import T
+from tests.test_gpu_create_points import BA_KEYS, MAP_KEYS, resident, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -58,57 +58,24 @@ def _composite(torch, ctx, _):
         g.close()
 
 
-CALLS = {"create_map_points_on_map": (_loop, "small", "large"), "create_map_points_from_map": (_composite, None, None)}
-_first = {}
-
-
-def first_call(torch, name):
-    if name not in _first:
-        fn, small, _ = CALLS[name]
-        _first[name] = on_new_context(torch, lambda t, c: fn(t, c, small))
-    return _first[name]
+CALLS = {"create_map_points_on_map": _loop, "create_map_points_from_map": _composite}
+PASS = Pass("create_points", CALLS, small={"create_map_points_on_map": "small", "create_map_points_from_map": None},
+            larger=lambda name: (at(_loop, "large"),), others=tuple(BY_NAME[other].large for other in OTHERS), prelude=(at(_loop, "large"),),
+            legs=("after the larger call", "after the other entry points"))
 
 
 @pytest.mark.parametrize("name", list(CALLS))
 def test_after_larger_calls_and_the_other_entry_points(torch, name):
     """small, large, small on one context; then every other map entry point and the per-pair pieces (large), then small again: each small
     equals the first call of a new context"""
-    fn, small, large = CALLS[name]
-    ref = first_call(torch, name)
-    ctx = new_context()
-    try:
-        same(run(lambda t, c: fn(t, c, small), torch, ctx), ref, (name, "first"))
-        run(lambda t, c: _loop(t, c, "large"), torch, ctx)
-        same(run(lambda t, c: fn(t, c, small), torch, ctx), ref, (name, "after the larger call"))
-        for other in OTHERS:
-            run(BY_NAME[other].large, torch, ctx)
-        same(run(lambda t, c: fn(t, c, small), torch, ctx), ref, (name, "after the other entry points"))
-    finally:
-        close_context(ctx)
+    after_legs(torch, PASS, name)
 
 
 @pytest.mark.parametrize("v", [0x00, 0xFF], ids=["0x00", "0xFF"])
 @pytest.mark.parametrize("name", list(CALLS))
 def test_poisoned_scratch(torch, name, v):
-    fn, small, _ = CALLS[name]
-    ref = first_call(torch, name)
-    ctx = new_context()
-    try:
-        run(lambda t, c: _loop(t, c, "large"), torch, ctx)
-        ctx.set_option("test_scratch_fill", v)  # every block the context holds, now
-        same(run(lambda t, c: fn(t, c, small), torch, ctx), ref, (name, "blocks filled with 0x%02X" % v))
-    finally:
-        close_context(ctx)
-    same(on_new_context(torch, lambda t, c: fn(t, c, small), fill=v), ref, (name, "new context, blocks filled with 0x%02X as they are allocated" % v))
+    poisoned(torch, PASS, name, v)
 
 
 def test_timers_on(torch):
-    refs = {name: first_call(torch, name) for name in CALLS}
-    ctx = new_context()
-    try:
-        ctx.timing(True)
-        for _ in range(2):
-            for name, (fn, small, _) in CALLS.items():
-                same(run(lambda t, c: fn(t, c, small), torch, ctx), refs[name], (name, "timers on"))
-    finally:
-        close_context(ctx)
+    timers_on(torch, PASS)

@@ -9,7 +9,8 @@ import pytest
 from gmmloc_amd import synth
 from tests import dbow2_cases as DC
 from tests import oracle_lib
-from tests.test_gpu_bow_cases import FILL, T, device_transform, device_voc, same, stop_on_device_error  # noqa: F401 (autouse fixture)
+from tests.gpu_helpers import stop_on_device_error  # noqa: F401 (autouse fixture)
+from tests.test_gpu_bow_cases import FILL, T, device_transform, device_voc, same
 
 pytestmark = pytest.mark.gpu
 NAMES = list(DC.cases())

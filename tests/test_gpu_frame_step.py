@@ -19,8 +19,9 @@ from tests import frame_step_glue as G
 from tests import frame_step_ref as R
 from tests import frame_step_scenes as S
 from tests.chain_glue import TH_LOCAL, TH_MM
+from tests.context_pass import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
+from tests.gpu_helpers import stop_on_device_error, to_dev  # noqa: F401 (the fixture is autouse)
 from tests.test_frame_step_cases import check_end_case, check_next_rows, next_args, poison_end, pose_bound
-from tests.test_gpu_context_state import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -30,34 +31,19 @@ POSES = ("t_rc", "t_cr", "pose_lw", "pose_cw")
 RULE = dict(num_kfs=3, frame_idx=100, kf_frame_idx=90, fps=20.0, is_idle=1, n_queue=0)
 
 
-@pytest.fixture(autouse=True)
-def stop_on_device_error(gpu):
-    """a HIP error met by a test is a finding: the session ends there, nothing more is started on the device"""
-    yield
-    try:
-        gpu[0].cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit("device error, nothing more is started: %s" % e, returncode=3)
-
-
-def dev(torch, d, keys=None):
-    return {k: (torch.from_numpy(np.ascontiguousarray(v)).cuda() if isinstance(v, np.ndarray) else v) for k, v in d.items()
-            if v is not None and (keys is None or k in keys)}
-
-
 def host(d):
     return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in d.items()}
 
 
 def map_dev(torch, m, ba):
-    return dev(torch, m, MAP_KEYS), dict(dev(torch, ba, BA_KEYS), kf_first=int(ba.get("kf_first", -1)))
+    return to_dev(torch, m, MAP_KEYS), dict(to_dev(torch, ba, BA_KEYS), kf_first=int(ba.get("kf_first", -1)))
 
 
 def device_end(torch, ctx, md, bd, a, th_depth, rule=None, poison=None):
-    d = dev(torch, a)
+    d = to_dev(torch, a)
     chain = {k: d.get(k) for k in ("feat_mp", "match_last", "match_local", "outlier", "counts2")}
     lm = {k: d.get(k) for k in ("local_mp", "n_local_mp", "ref_kf")}
-    out = None if poison is None else dev(torch, poison)
+    out = None if poison is None else to_dev(torch, poison)
     def call(torch, c):
         r = frame_step.frame_end(c, md, bd, chain, lm, d["feat_depth"], th_depth, last_observed=d.get("last_observed"),
                                  rule=None if rule is None else frame_step.kf_rule(**rule), out=out)
@@ -68,7 +54,7 @@ def device_end(torch, ctx, md, bd, a, th_depth, rule=None, poison=None):
 
 def device_next(torch, ctx, md, bd, pose_tracked, pose_prev, ref_kf, held_mp, feat_new=None, mp_base=0, mp_replaced=None, poison=None, want_desc=True):
     T = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    out = None if poison is None else dev(torch, poison)
+    out = None if poison is None else to_dev(torch, poison)
     def call(torch, c):
         r = frame_step.frame_next(c, md, bd, T(pose_tracked), T(pose_prev), T(ref_kf), T(np.asarray(held_mp, np.int32)), feat_new=T(feat_new),
                                   mp_base=mp_base, mp_replaced=T(mp_replaced), want_desc=want_desc, out=out)
@@ -286,7 +272,7 @@ def test_malformed_rows_change_nothing_and_fault_nothing(gpu):
         keep[k], md[k] = padded(torch, m[k], fill)
     for k in ("mp_normal", "mp_max_dist", "mp_min_dist"):
         md[k] = torch.from_numpy(m[k]).cuda()
-    bd = dict(dev(torch, ba, BA_KEYS), kf_first=0)
+    bd = dict(to_dev(torch, ba, BA_KEYS), kf_first=0)
     bad = lambda shape: rng.choice(np.concatenate([np.arange(NMP, NMP + PAD // 2), np.arange(-PAD // 2, -1)]), shape).astype(np.int32)
     B, NF = 2, 65
     a = S.random_end(m, B, NF, 72)
@@ -406,9 +392,9 @@ class Resident:
         self.st["visible"][:NMP] = 1
         self.st["found"][:NMP] = 1
         self.mp_replaced = torch.full((NMP + GROW["mp"],), -1, dtype=torch.int32).cuda()
-        first = dev(torch, {k: np.asarray(v)[None] for k, v in q["first"].items()})
+        first = to_dev(torch, {k: np.asarray(v)[None] for k, v in q["first"].items()})
         # (without the optional kf_count: its row follows NKF, which a key-frame pass changes)
-        self.state = frame_step.first_state(first, first["last_mp"], dev(torch, {k: v for k, v in q["lists"].items() if k != "kf_count"}))
+        self.state = frame_step.first_state(first, first["last_mp"], to_dev(torch, {k: v for k, v in q["lists"].items() if k != "kf_count"}))
 
     def views(self):
         md, bd = self.grow.map_views(self.md, self.bd, self.sizes)
@@ -518,7 +504,7 @@ def device_leg(torch, ctx, q, between=None):
 
 
 def frame_dev(torch, f):
-    return dev(torch, {k: np.asarray(v)[None] for k, v in f.items()})
+    return to_dev(torch, {k: np.asarray(v)[None] for k, v in f.items()})
 
 
 def features_depth(f):
@@ -557,7 +543,7 @@ def host_leg(torch, ctx, q, between=None):
                           last_observed, f["feat_depth"][None], S.TH_DEPTH, rule=dict(RULE, frame_idx=100 + t), world=W)
         kw = {}
         if between is not None and t == between[0]:
-            begun = dict(chain=out, end=dev(torch, {k: end[k] for k in ("held_mp", "held")}), lm=lm)
+            begun = dict(chain=out, end=to_dev(torch, {k: end[k] for k in ("held_mp", "held")}), lm=lm)
             def pass_(torch, c):
                 r = between[1](c, M, q, begun, fd, extra)
                 torch.cuda.synchronize()

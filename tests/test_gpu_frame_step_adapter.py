@@ -3,36 +3,23 @@ through the same C-ABI: a g++-built driver (tests/cpp/frame_step_check.cpp) keep
 the device, ends the four frames of END, notes the steps of REPLACE['all'] and hands the frames of NEXT over with that array; every
 output it downloads is compared bit for bit with frame_step.frame_end / note_replaced / frame_next on the same bytes - and with the
 declared outputs of the cases."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import gmmloc_amd
 from gmmloc_amd import api, frame_step
+from tests import cpp_driver
 from tests import frame_step_cases as FC
-from tests.conftest import ROOT
 from tests.test_frame_step_cases import check_next_rows, next_args, poison_end
-from tests.test_gpu_frame_step import dev, device_next, host, map_dev
+from tests.gpu_helpers import to_dev
+from tests.test_gpu_frame_step import device_next, host, map_dev
 
 pytestmark = pytest.mark.gpu
-
-
-def build_driver(out_dir):
-    exe = os.path.join(str(out_dir), "frame_step_check")
-    libdir = os.path.dirname(gmmloc_amd._lib.LIB_PATH)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "frame_step_check.cpp"),
-           "-L" + libdir, "-lgmmloc_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def test_cpp_frame_step_matches_python_host(gpu, map_v1, tmp_path):
     torch, ctx = gpu
     mean, cov = map_v1
-    exe = build_driver(tmp_path)
+    exe = cpp_driver.build("frame_step_check", tmp_path)
     api.GMM(ctx, mean, cov).save(tmp_path / "m.gmm")
     m, ba, tracked, prev, ref_kf2, held = next_args()  # (after_map)
     NMP, (NKF, NFK), NOBS = len(m["mp_valid"]), m["kf_mp"].shape, len(m["obs_kf"])
@@ -52,17 +39,14 @@ def test_cpp_frame_step_matches_python_host(gpu, map_v1, tmp_path):
         fh.write(bytes(rule))
         for arr in (src, tgt, tracked, prev, ref_kf2, held, fn):
             np.ascontiguousarray(arr).tofile(fh)
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.dirname(gmmloc_amd._lib.LIB_PATH) + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([exe, str(tmp_path / "m.gmm"), str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")], env=env, capture_output=True, text=True,
-                       timeout=300)
+    r = cpp_driver.run(exe, tmp_path / "m.gmm", tmp_path / "scene.bin", tmp_path / "out.bin")
     assert r.returncode == 0, r.stderr
     print(r.stdout)
     # the same sequence from Python on the same bytes
     md, bd = map_dev(torch, m, ba)
-    d = dev(torch, a)
+    d = to_dev(torch, a)
     end = frame_step.frame_end(ctx, md, bd, d, d, d["feat_depth"], FC.TH_DEPTH, last_observed=d["last_observed"], rule=rule,
-                               out=dev(torch, poison_end(B, NF)))
+                               out=to_dev(torch, poison_end(B, NF)))
     rep = torch.full((FC.NMPCAP,), -1, dtype=torch.int32).cuda()
     frame_step.note_replaced(ctx, rep, torch.from_numpy(src).cuda(), torch.from_numpy(tgt).cuda())
     torch.cuda.synchronize()

@@ -16,6 +16,7 @@ from oracle import numpy_ref
 from tests import key_frame_create_cases as cc
 from tests import key_frame_create_ref as ref
 from tests import keyframe_cases as kc
+from tests.gpu_helpers import T, gmm_of, stop_on_device_error  # noqa: F401 (the fixture is autouse)
 from tests.test_key_frame_create_ref import INT_KEYS, check_stereo, check_temporal
 
 pytestmark = pytest.mark.gpu
@@ -23,28 +24,6 @@ pytestmark = pytest.mark.gpu
 f32, f64 = np.float32, np.float64
 LISTS = ("new_feat", "new_assoc", "new_ref_kf", "att_mp", "att_kf", "att_feat")
 IN_KEYS = tuple(api.STEREO_IN_DTYPES)
-_gmm = {}
-
-
-@pytest.fixture(autouse=True)
-def stop_on_device_error(gpu):
-    """a HIP error met by a test is a finding: the session ends there, nothing more is started on the device"""
-    yield
-    try:
-        gpu[0].cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit("device error, nothing more is started: %s" % e, returncode=3)
-
-
-def T(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def gmm_of(ctx, mean, cov):
-    key = (mean.tobytes(), cov.tobytes())
-    if key not in _gmm:
-        _gmm[key] = api.GMM(ctx, mean, cov.reshape(-1, 9))
-    return _gmm[key]
 
 
 def padded(fr, NF, off=0):

@@ -2,35 +2,22 @@
 processKeyFrameInMap) must give what the Python host gives through the same C-ABI: a g++-built driver (tests/cpp/key_frame_create_check.cpp)
 takes the key-frame of tests/test_gpu_key_frame_create.py's scene - host vectors for the two walks, the resident map in capacity buffers for
 the composite; every list it returns and every byte it leaves in the buffers is compared."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import gmmloc_amd
 from gmmloc_amd import api, map_grow
+from tests import cpp_driver
 from tests import key_frame_create_cases as cc
-from tests.conftest import ROOT
-from tests.test_gpu_key_frame_create import T, key_frame_scene, stop_on_device_error  # noqa: F401 (the fixture is autouse here too)
+from tests.gpu_helpers import T, stop_on_device_error  # noqa: F401 (the fixture is autouse here too)
+from tests.test_gpu_key_frame_create import key_frame_scene
 from tests.test_gpu_map_grow import refresh, upload, with_point_arrays
 
 pytestmark = pytest.mark.gpu
 
 
-def build_driver(out_dir):
-    exe = os.path.join(str(out_dir), "key_frame_create_check")
-    libdir = os.path.dirname(gmmloc_amd._lib.LIB_PATH)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "key_frame_create_check.cpp"),
-           "-L" + libdir, "-lgmmloc_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
 def test_cpp_key_frame_create_matches_python_host(gpu, map_v1, gt_sync, tmp_path):
     torch, ctx = gpu
-    exe = build_driver(tmp_path)
+    exe = cpp_driver.build("key_frame_create_check", tmp_path)
     api.GMM(ctx, *map_v1).save(tmp_path / "m.gmm")
     g = api.GMM.load(ctx, tmp_path / "m.gmm")  # (the map both hosts read: the file)
     sc, m0, ba0, K, held, depth, cam = key_frame_scene(map_v1, gt_sync)
@@ -52,10 +39,7 @@ def test_cpp_key_frame_create_matches_python_host(gpu, map_v1, gt_sync, tmp_path
                   H(bd["kf_uvr"]), H(bd["kf_oct"]), H(md["mp_pos"]), H(md["mp_normal"]), H(md["mp_max_dist"]), H(md["mp_min_dist"]), H(md["mp_desc"]),
                   H(bd["mp_assoc"]), H(rk), sc["kf_desc"], depth, held, outlier, last["last_pt"], last["last_observed"], last["last_valid"], last["last_desc"]):
             np.ascontiguousarray(a).tofile(fh)
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.dirname(gmmloc_amd._lib.LIB_PATH) + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([exe, str(tmp_path / "m.gmm"), str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")], env=env, capture_output=True, text=True,
-                       timeout=300)
+    r = cpp_driver.run(exe, tmp_path / "m.gmm", tmp_path / "scene.bin", tmp_path / "out.bin")
     assert r.returncode == 0, r.stderr
     print(r.stdout)
     # the same sequence from Python

@@ -1,5 +1,5 @@
 """create_stereo_points, create_temporal_points and process_key_frame_from_map give the bits of the FIRST call of a new context whatever
-the context has been through - the pass of tests/test_gpu_map_grow_context.py with its helpers: after larger calls of themselves, after
+the context has been through - the pass of tests/context_pass.py for these three: after larger calls of themselves, after
 mapping_pass_from_map (which leaves its own bytes in the scratch block the stereo call uses), with every scratch block filled with 0x00 /
 0xFF, and with the timers on."""
 import functools
@@ -10,10 +10,10 @@ import pytest
 from gmmloc_amd import api, map_grow
 from tests import key_frame_create_cases as cc
 from tests import keyframe_cases as kc
-from tests.context_cases import BY_NAME, close_context, gmm_of, gt_sync, map_v1, new_context
-from tests.test_gpu_context_state import on_new_context, run, torch  # noqa: F401 (torch: the module's fixture)
-from tests.test_gpu_key_frame_create import T, generated, key_frame_scene, padded, stacked
-from tests.test_gpu_map_grow_context import same
+from tests.context_cases import BY_NAME, gmm_of, gt_sync, map_v1
+from tests.context_pass import Pass, after_legs, at, poisoned, timers_on, torch  # noqa: F401 (torch: the module's fixture)
+from tests.gpu_helpers import T
+from tests.test_gpu_key_frame_create import generated, key_frame_scene, padded, stacked
 
 pytestmark = pytest.mark.gpu
 
@@ -69,57 +69,25 @@ def _composite(torch, ctx, _):
     return out
 
 
-CALLS = {"create_stereo_points": (_stereo, "small", "large"), "create_temporal_points": (_temporal, "small", "large"),
-         "process_key_frame_from_map": (_composite, None, None)}
-_first = {}
-
-
-def first_call(torch, name):
-    if name not in _first:
-        fn, small, _ = CALLS[name]
-        _first[name] = on_new_context(torch, lambda t, c: fn(t, c, small))
-    return _first[name]
+CALLS = {"create_stereo_points": _stereo, "create_temporal_points": _temporal, "process_key_frame_from_map": _composite}
+# (the composite has one size: the larger call is the stereo walk's)
+PASS = Pass("key_frame_create", CALLS, small={"create_stereo_points": "small", "create_temporal_points": "small", "process_key_frame_from_map": None},
+            larger=lambda name: (at(_stereo if name == "process_key_frame_from_map" else CALLS[name], "large"),),
+            others=(BY_NAME["mapping_pass_from_map"].large,), prelude=(at(_stereo, "large"),))
 
 
 @pytest.mark.parametrize("name", list(CALLS))
 def test_after_larger_calls_and_the_mapping_pass(torch, name):
     """small, large, small on one context; then mapping_pass_from_map (large), then small again: each small equals the first call of a
     new context"""
-    fn, small, large = CALLS[name]
-    ref = first_call(torch, name)
-    ctx = new_context()
-    try:
-        same(run(lambda t, c: fn(t, c, small), torch, ctx), ref, (name, "first"))
-        run(lambda t, c: (CALLS["create_stereo_points"][0] if large is None else fn)(t, c, "large"), torch, ctx)
-        same(run(lambda t, c: fn(t, c, small), torch, ctx), ref, (name, "after the larger call"))
-        run(BY_NAME["mapping_pass_from_map"].large, torch, ctx)
-        same(run(lambda t, c: fn(t, c, small), torch, ctx), ref, (name, "after mapping_pass_from_map"))
-    finally:
-        close_context(ctx)
+    after_legs(torch, PASS, name)
 
 
 @pytest.mark.parametrize("v", [0x00, 0xFF], ids=["0x00", "0xFF"])
 @pytest.mark.parametrize("name", list(CALLS))
 def test_poisoned_scratch(torch, name, v):
-    fn, small, _ = CALLS[name]
-    ref = first_call(torch, name)
-    ctx = new_context()
-    try:
-        run(lambda t, c: _stereo(t, c, "large"), torch, ctx)
-        ctx.set_option("test_scratch_fill", v)  # every block the context holds, now
-        same(run(lambda t, c: fn(t, c, small), torch, ctx), ref, (name, "blocks filled with 0x%02X" % v))
-    finally:
-        close_context(ctx)
-    same(on_new_context(torch, lambda t, c: fn(t, c, small), fill=v), ref, (name, "new context, blocks filled with 0x%02X as they are allocated" % v))
+    poisoned(torch, PASS, name, v)
 
 
 def test_timers_on(torch):
-    refs = {name: first_call(torch, name) for name in CALLS}
-    ctx = new_context()
-    try:
-        ctx.timing(True)
-        for _ in range(2):
-            for name, (fn, small, _) in CALLS.items():
-                same(run(lambda t, c: fn(t, c, small), torch, ctx), refs[name], (name, "timers on"))
-    finally:
-        close_context(ctx)
+    timers_on(torch, PASS)

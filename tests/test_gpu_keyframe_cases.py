@@ -14,6 +14,7 @@ import pytest
 
 from gmmloc_amd import api
 from tests import keyframe_cases as kc
+from tests.gpu_helpers import T
 
 pytestmark = pytest.mark.gpu
 
@@ -24,10 +25,6 @@ AWAY = np.array([0, 1, 0, 0, 0, 0, 0], np.float64)  # half a turn about y: looks
 KEYS = {"pt": kc.PT_KEYS, "cma": kc.CMA_KEYS, "tri": kc.TRI_KEYS, "cmp": kc.CMP_KEYS}
 CHI2 = ("c2p", "c2s")
 _ref, _gmm = {}, {}
-
-
-def T(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def reference(oracle, key, call, data):

@@ -10,6 +10,7 @@ from tests import chain_glue as G
 from tests import local_map_ref as R
 from tests import local_map_scenes as S
 from tests.chain_glue import TH_LOCAL, TH_MM
+from tests.gpu_helpers import to_dev
 from tests.test_gpu_chain import pack
 
 pytestmark = pytest.mark.gpu
@@ -18,10 +19,6 @@ MAP_KEYS = ("mp_valid", "obs_ptr", "obs_kf", "kf_valid", "kf_mp")
 POINT_KEYS = api.MAP_VIEW_POINT_KEYS
 CHAIN_OUT = ("pose", "pose_mm", "match_last", "match_kf", "match_local", "outlier", "counts", "counts2", "drop_src", "drop_kf", "inview")
 LIST_KEYS = ("local_kf", "n_local_kf", "local_mp", "n_local_mp", "ref_kf", "kf_count", "status")
-
-
-def to_dev(torch, d, keys=None):
-    return {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items() if v is not None and (keys is None or k in keys)}
 
 
 def to_host(d):

@@ -10,11 +10,11 @@ import pytest
 from gmmloc_amd import api
 from tests import ba_window_ref as R
 from tests import map_cases as MC
-from tests.test_gpu_ba_window import device_build, device_connections, to_dev
-from tests.test_gpu_context_state import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
+from tests.context_pass import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
+from tests.gpu_helpers import stop_on_device_error, to_dev  # noqa: F401  (autouse: the same after every test of this module)
+from tests.test_gpu_ba_window import device_build, device_connections
 from tests.test_gpu_local_map import device_update
 from tests.test_gpu_map_edit import device_cull
-from tests.test_gpu_map_grow import stop_on_device_error  # noqa: F401  (autouse: the same after every test of this module)
 
 pytestmark = pytest.mark.gpu
 

@@ -11,7 +11,8 @@ from tests import ba_window_scenes as S
 from tests import map_edit_ref as E
 from tests import map_edit_scenes as ES
 from tests import map_point_ref as M
-from tests.test_gpu_ba_window import to_dev, to_host
+from tests.gpu_helpers import to_dev
+from tests.test_gpu_ba_window import to_host
 
 pytestmark = pytest.mark.gpu
 

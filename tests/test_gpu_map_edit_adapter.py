@@ -2,36 +2,22 @@
 the Python host gives through the same C-ABI: a g++-built driver (tests/cpp/map_edit_check.cpp) keeps the `small` scene of
 tests/map_edit_scenes.py (octaves clamped) on the device, erases observations and points, culls the covisible key-frames of one
 key-frame and removes them; every list it returns and every row it leaves on the device is compared bit for bit."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import gmmloc_amd
 from gmmloc_amd import api
 from tests import ba_window_ref as R
+from tests import cpp_driver
 from tests import map_edit_scenes as ES
-from tests.conftest import ROOT
-from tests.test_gpu_ba_window import to_dev
+from tests.gpu_helpers import to_dev
 
 pytestmark = pytest.mark.gpu
-
-
-def build_driver(out_dir):
-    exe = os.path.join(str(out_dir), "map_edit_check")
-    libdir = os.path.dirname(gmmloc_amd._lib.LIB_PATH)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "map_edit_check.cpp"),
-           "-L" + libdir, "-lgmmloc_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def test_cpp_map_edit_matches_python_host(gpu, map_v1, tmp_path):
     torch, ctx = gpu
     mean, cov = map_v1
-    exe = build_driver(tmp_path)
+    exe = cpp_driver.build("map_edit_check", tmp_path)
     api.GMM(ctx, mean, cov).save(tmp_path / "m.gmm")
     sc = ES.scene("small", True)
     m, ba = sc["m"], sc["ba"]
@@ -45,10 +31,7 @@ def test_cpp_map_edit_matches_python_host(gpu, map_v1, tmp_path):
         for a in (m["mp_valid"], m["kf_valid"], m["kf_mp"], m["obs_ptr"], m["obs_kf"], ba["obs_feat"], ba["kf_uvr"], ba["kf_oct"], sc["kf_depth"], sc["mp_ref_kf"],
                   erase, rm_mp):
             np.ascontiguousarray(a).tofile(fh)
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.dirname(gmmloc_amd._lib.LIB_PATH) + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([exe, str(tmp_path / "m.gmm"), str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")], env=env, capture_output=True, text=True,
-                       timeout=300)
+    r = cpp_driver.run(exe, tmp_path / "m.gmm", tmp_path / "scene.bin", tmp_path / "out.bin")
     assert r.returncode == 0, r.stderr
     print(r.stdout)
     # the same sequence from Python on the same rows

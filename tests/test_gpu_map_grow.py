@@ -16,23 +16,14 @@ from tests import map_edit_scenes as ES
 from tests import map_grow_ref as G
 from tests import map_grow_scenes as GS
 from tests import map_point_ref as MP
-from tests.test_gpu_ba_window import to_dev, to_host
-from tests.test_gpu_context_state import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
+from tests.context_pass import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
+from tests.gpu_helpers import stop_on_device_error, to_dev  # noqa: F401 (the fixture is autouse)
+from tests.test_gpu_ba_window import to_host
 
 pytestmark = pytest.mark.gpu
 
 SENT = -9
 MAP_KEYS = ("mp_valid", "kf_valid", "kf_mp", "obs_ptr", "obs_kf", "obs_feat")
-
-
-@pytest.fixture(autouse=True)
-def stop_on_device_error(gpu):
-    """a HIP error met by a test is a finding: the session ends there, nothing more is started on the device"""
-    yield
-    try:
-        gpu[0].cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit("device error, nothing more is started: %s" % e, returncode=3)
 
 
 def padded(a, n, fill=SENT):

@@ -2,37 +2,24 @@
 fuseObservationsInMap) must give what the Python host gives through the same C-ABI: a g++-built driver (tests/cpp/map_grow_check.cpp)
 keeps the `small` scene of tests/map_grow_scenes.py on the device in capacity buffers, adds a key-frame's rows, points and observations
 and applies a list of fuse matches; every list it returns and every byte it leaves in the buffers is compared."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import gmmloc_amd
 from gmmloc_amd import api, map_grow
+from tests import cpp_driver
 from tests import map_edit_scenes as ES
 from tests import map_grow_ref as G
 from tests import map_grow_scenes as GS
-from tests.conftest import ROOT
-from tests.test_gpu_map_grow import stop_on_device_error, upload  # noqa: F401 (the fixture is autouse here too)
+from tests.gpu_helpers import stop_on_device_error  # noqa: F401 (the fixture is autouse here too)
+from tests.test_gpu_map_grow import upload
 
 pytestmark = pytest.mark.gpu
-
-
-def build_driver(out_dir):
-    exe = os.path.join(str(out_dir), "map_grow_check")
-    libdir = os.path.dirname(gmmloc_amd._lib.LIB_PATH)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "map_grow_check.cpp"),
-           "-L" + libdir, "-lgmmloc_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def test_cpp_map_grow_matches_python_host(gpu, map_v1, tmp_path):
     torch, ctx = gpu
     mean, cov = map_v1
-    exe = build_driver(tmp_path)
+    exe = cpp_driver.build("map_grow_check", tmp_path)
     api.GMM(ctx, mean, cov).save(tmp_path / "m.gmm")
     m, ba, ref_kf, ls = GS.add_lists(ES.scene("small", True), 2)
     NMP, (NKF, NFK), NOBS = len(m["mp_valid"]), m["kf_mp"].shape, len(m["obs_kf"])
@@ -50,10 +37,7 @@ def test_cpp_map_grow_matches_python_host(gpu, map_v1, tmp_path):
         for a in (H(md["mp_valid"]), H(md["kf_valid"]), H(md["kf_mp"]), H(md["obs_ptr"]), H(md["obs_kf"]), H(bd["obs_feat"]), ba["kf_uvr"], H(md["mp_pos"]),
                   H(bd["mp_assoc"]), H(rk), new["pos"], new["assoc"], new["ref_kf"], ls["new_kf"], att[:, 0], att[:, 1], att[:, 2], ls["walk_kf"], cand, best):
             np.ascontiguousarray(a).tofile(fh)
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.dirname(gmmloc_amd._lib.LIB_PATH) + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([exe, str(tmp_path / "m.gmm"), str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")], env=env, capture_output=True, text=True,
-                       timeout=300)
+    r = cpp_driver.run(exe, tmp_path / "m.gmm", tmp_path / "scene.bin", tmp_path / "out.bin")
     assert r.returncode == 0, r.stderr
     print(r.stdout)
     # the same sequence from Python on the same buffers

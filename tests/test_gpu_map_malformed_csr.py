@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from gmmloc_amd import _lib, api
-from tests.test_gpu_context_state import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
-from tests.test_gpu_map_grow import stop_on_device_error  # noqa: F401  (autouse: the same after every test of this module)
+from tests.context_pass import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
+from tests.gpu_helpers import stop_on_device_error  # noqa: F401  (autouse: the same after every test of this module)
 
 pytestmark = pytest.mark.gpu
 

@@ -6,6 +6,7 @@ import pytest
 
 from gmmloc_amd import api, synth
 from tests import map_point_ref as M
+from tests.gpu_helpers import to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -17,15 +18,11 @@ def sentinel(NP):
                 min_dist=np.full(NP, -2.0, np.float32))
 
 
-def dev(torch, d):
-    return {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()}
-
-
 def run_both(torch, ctx, m, what=3, init=None, scale_factor=1.2):
     NP = len(m["mp"]["obs_ptr"]) - 1
     ref = {k: v.copy() for k, v in (init or sentinel(NP)).items()}
-    out = dev(torch, ref)
-    api.update_map_points(ctx, dev(torch, m["kf"]), dev(torch, m["mp"]), out, what=what, scale_factor=scale_factor)
+    out = to_dev(torch, ref)
+    api.update_map_points(ctx, to_dev(torch, m["kf"]), to_dev(torch, m["mp"]), out, what=what, scale_factor=scale_factor)
     torch.cuda.synchronize()
     M.update_map_points_ref(m["kf"], m["mp"], ref, what=what, scale_factor=scale_factor)
     return {k: v.cpu().numpy() for k, v in out.items()}, ref
@@ -111,9 +108,9 @@ def test_invalid_and_malformed_points_untouched(gpu):
 def test_no_points_and_bad_arguments(gpu):
     torch, ctx = gpu
     m = synth.synth_map_points(50, 15)
-    kf, mp = dev(torch, m["kf"]), dev(torch, m["mp"])
+    kf, mp = to_dev(torch, m["kf"]), to_dev(torch, m["mp"])
     empty = dict(mp, obs_ptr=mp["obs_ptr"][:1].clone())
-    out = dev(torch, sentinel(50))
+    out = to_dev(torch, sentinel(50))
     api.update_map_points(ctx, kf, empty, out)  # NP = 0
     torch.cuda.synchronize()
     assert all((out[k].cpu().numpy() == v).all() for k, v in sentinel(50).items())
@@ -130,10 +127,10 @@ def test_no_points_and_bad_arguments(gpu):
 def test_same_bytes_twice(gpu):
     torch, ctx = gpu
     m = mixed_map(16, extra=5000)
-    kf, mp = dev(torch, m["kf"]), dev(torch, m["mp"])
+    kf, mp = to_dev(torch, m["kf"]), to_dev(torch, m["mp"])
     outs = []
     for _ in range(2):
-        out = dev(torch, sentinel(len(m["mp"]["obs_ptr"]) - 1))
+        out = to_dev(torch, sentinel(len(m["mp"]["obs_ptr"]) - 1))
         api.update_map_points(ctx, kf, mp, out)
         torch.cuda.synchronize()
         outs.append({k: v.cpu().numpy().tobytes() for k, v in out.items()})

@@ -14,22 +14,12 @@ from tests import map_edit_scenes as ES
 from tests import map_grow_scenes as GS
 from tests import map_stats_cases as SC
 from tests import map_stats_ref as R
-from tests.test_gpu_ba_window import to_dev
-from tests.test_gpu_context_state import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
+from tests.context_pass import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
+from tests.gpu_helpers import stop_on_device_error, to_dev  # noqa: F401 (the fixture is autouse)
 
 pytestmark = pytest.mark.gpu
 
 SENT, NGUARD = -9, 8
-
-
-@pytest.fixture(autouse=True)
-def stop_on_device_error(gpu):
-    """a HIP error met by a test is a finding: the session ends there, nothing more is started on the device"""
-    yield
-    try:
-        gpu[0].cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit("device error, nothing more is started: %s" % e, returncode=3)
 
 
 class Guarded:

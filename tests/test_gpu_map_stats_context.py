@@ -1,6 +1,5 @@
 """The five calls of gmmloc_amd.map_stats and remove_map_points_from_map give the bits of the FIRST call of a new context whatever the
-context has been through - the pass of tests/test_gpu_map_grow_context.py for this module, with that file's pattern and the helpers of
-tests/context_cases.py: after larger calls of themselves, after mapping_pass_from_map (which leaves gl_map_remove's marks in the
+context has been through - the pass of tests/context_pass.py for this module, with the helpers of tests/context_cases.py: after larger calls of themselves, after mapping_pass_from_map (which leaves gl_map_remove's marks in the
 scratch block gl_cull_map_points uses), with every scratch block filled with 0x00 / 0xFF, and with the timers on."""
 import functools
 
@@ -9,9 +8,8 @@ import pytest
 
 from tests import map_edit_scenes as ES
 from tests import map_stats_cases as SC
-from tests.context_cases import BY_NAME, close_context, new_context
-from tests.test_gpu_context_state import on_new_context, run, torch  # noqa: F401 (torch: the module's fixture)
-from tests.test_gpu_map_grow_context import same
+from tests.context_cases import BY_NAME
+from tests.context_pass import Pass, after_legs, at, poisoned, run, timers_on, torch  # noqa: F401 (torch: the module's fixture)
 from tests.test_gpu_map_stats import composite, device_cull, device_merge, device_track, make_stats
 
 pytestmark = pytest.mark.gpu
@@ -73,54 +71,22 @@ def _counters(torch, ctx, name):
 
 
 CALLS = {"counters": _counters, "cull_map_points": _cull, "remove_map_points_from_map": _composite}
-_first = {}
-
-
-def first_call(torch, name):
-    if name not in _first:
-        _first[name] = on_new_context(torch, lambda t, c: CALLS[name](t, c, "tiny"))
-    return _first[name]
+PASS = Pass("map_stats", CALLS, small=dict.fromkeys(CALLS, "tiny"), larger=lambda name: (at(CALLS[name], "small"),),
+            others=(BY_NAME["mapping_pass_from_map"].large,), prelude=(at(_composite, "small"),))
 
 
 @pytest.mark.parametrize("name", list(CALLS))
 def test_after_larger_calls_and_the_mapping_pass(torch, name):
     """small, large, small on one context; then mapping_pass_from_map (large), then small again: each small equals the first call of a
     new context"""
-    fn = CALLS[name]
-    ref = first_call(torch, name)
-    ctx = new_context()
-    try:
-        same(run(lambda t, c: fn(t, c, "tiny"), torch, ctx), ref, (name, "first"))
-        run(lambda t, c: fn(t, c, "small"), torch, ctx)
-        same(run(lambda t, c: fn(t, c, "tiny"), torch, ctx), ref, (name, "after the larger call"))
-        run(BY_NAME["mapping_pass_from_map"].large, torch, ctx)
-        same(run(lambda t, c: fn(t, c, "tiny"), torch, ctx), ref, (name, "after mapping_pass_from_map"))
-    finally:
-        close_context(ctx)
+    after_legs(torch, PASS, name)
 
 
 @pytest.mark.parametrize("v", [0x00, 0xFF], ids=["0x00", "0xFF"])
 @pytest.mark.parametrize("name", list(CALLS))
 def test_poisoned_scratch(torch, name, v):
-    fn = CALLS[name]
-    ref = first_call(torch, name)
-    ctx = new_context()
-    try:
-        run(lambda t, c: _composite(t, c, "small"), torch, ctx)
-        ctx.set_option("test_scratch_fill", v)  # every block the context holds, now
-        same(run(lambda t, c: fn(t, c, "tiny"), torch, ctx), ref, (name, "blocks filled with 0x%02X" % v))
-    finally:
-        close_context(ctx)
-    same(on_new_context(torch, lambda t, c: fn(t, c, "tiny"), fill=v), ref, (name, "new context, blocks filled with 0x%02X as they are allocated" % v))
+    poisoned(torch, PASS, name, v)
 
 
 def test_timers_on(torch):
-    refs = {name: first_call(torch, name) for name in CALLS}
-    ctx = new_context()
-    try:
-        ctx.timing(True)
-        for _ in range(2):
-            for name, fn in CALLS.items():
-                same(run(lambda t, c: fn(t, c, "tiny"), torch, ctx), refs[name], (name, "timers on"))
-    finally:
-        close_context(ctx)
+    timers_on(torch, PASS)

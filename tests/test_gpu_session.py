@@ -13,22 +13,13 @@ from gmmloc_amd import api, bow
 from tests import session_ref as SR
 from tests import session_scenes as SS
 from tests.context_cases import close_context, new_context
-from tests.test_gpu_context_state import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
+from tests.gpu_helpers import stop_on_device_error  # noqa: F401 (the fixture is autouse)
+from tests.context_pass import run  # (a HIP error ends the session: nothing more is started on a device that has faulted)
 
 pytestmark = pytest.mark.gpu
 
 POINT_KEYS = tuple(k for k, _, _ in SR.POINT_SPEC)
 _cache = {}
-
-
-@pytest.fixture(autouse=True)
-def stop_on_device_error(gpu):
-    """a HIP error met by a test is a finding: the session ends there, nothing more is started on the device"""
-    yield
-    try:
-        gpu[0].cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit("device error, nothing more is started: %s" % e, returncode=3)
 
 
 @pytest.fixture(scope="module")

@@ -96,6 +96,19 @@ class gl_temporal_points_out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("temp_flag", "n_temp", "last_pt", "last_observed", "last_valid", "last_desc", "stats", "last_mp")]
 
 
+class gl_stereo_in(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("feat_uv", "feat_oct", "feat_desc", "r_uv", "r_oct", "r_desc", "n_left", "n_right")]
+
+
+class gl_image_pyramid(C.Structure):
+    _fields_ = [("nlevels", C.c_int32), ("reserved_", C.c_int32), ("width", C.c_int32 * 8), ("height", C.c_int32 * 8), ("stride", C.c_int64 * 8),
+                ("offset", C.c_int64 * 8), ("frame_stride", C.c_int64), ("data", C.c_void_p)]
+
+
+class gl_stereo_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("feat_ur", "feat_depth", "match_r", "sad", "stat")]
+
+
 class gl_frame_end_in(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("feat_mp", "match_last", "match_local", "match_kf", "outlier", "local_mp", "n_local_mp", "counts2", "ref_kf",
                                           "last_observed", "feat_depth")]
@@ -242,6 +255,8 @@ def load():
                                                 i32, vp]),
         "gl_create_stereo_points": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, vp, i32, i32, C.c_float, vp]),
         "gl_create_temporal_points": (i32, [vp, P(gl_camera), i32, i32, vp, C.c_float, vp]),
+        "gl_stereo_matches": (i32, [vp, P(gl_camera), C.c_double, i32, i32, i32, P(gl_stereo_in), P(gl_image_pyramid), P(gl_image_pyramid),
+                                    P(gl_stereo_out)]),
         "gl_optimize_current_pose": (i32, [vp, P(gl_camera), P(gl_params), i32, i32, vp, vp, vp, vp, vp, vp]),
         "gl_joint_optimization": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, i32, i32] + [vp] * 11),
         "gl_joint_optimization_stoppable": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, i32, i32] + [vp] * 12),

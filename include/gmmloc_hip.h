@@ -111,6 +111,7 @@ void gl_default_params(gl_params* p);
  * gl_track_frame_chain_front       | K bf size      | sigma2_inv                                                          | level radii
  * gl_track_frame_chain_back        | K bf size      | sigma2_inv                                                          | radii, steps, band
  * gl_track_frame_chain_map         | K bf size      | sigma2_inv                                                          | radii, steps, band
+ * gl_stereo_matches                | fx bf height   | -                                                                   | level scales, inverses
  *
  * tri_lambda2 weighs the structure edge of the per-point optimisations (and scales their threshold, tri_str_thresh * tri_lambda2);
  * ba_lambda2 does both for the pose / window optimisations (threshold tri_str_thresh * ba_lambda2).  gl_search_by_bow,
@@ -1512,6 +1513,79 @@ typedef struct gl_temporal_points_out {
 } gl_temporal_points_out;
 int gl_create_temporal_points(gl_ctx_t* ctx, const gl_camera* cam, int B, int NF, const gl_temporal_points_in* in, float th_depth,
                               const gl_temporal_points_out* out);
+
+/* ---- stereo depth: Frame::computeStereoMatches (frame.cpp:179-349) for B frames ------------------- */
+/* The two feature columns the calls above read - feat_ur (u_right) and feat_depth - made on the device from the left features, the right
+ * key-points and the two image pyramids (GMMLoc::processFrame, gmmloc.cpp:259-261).  One workgroup per frame, asynchronous on the
+ * context's stream, device pointers only, no scratch, nothing of the context but its stream.  Every decision is integer arithmetic or a
+ * single IEEE binary32 operation (one rounding each, no contraction); the division of the parabola (:313-314) and mbf / disparity (:330)
+ * are correctly rounded.  The sequential model is tests/stereo_ref.py, the hand-built cases tests/stereo_cases.py.
+ *
+ *  cam: fx, bf (mbf = (float)bf, mb = (float)(bf / fx), maxD = mbf / mb in float), height (the rows of the row table).  scale_factor:
+ *  the level table of init_config.hpp:63-79 in float, scale_factors_inv[l] = 1.0f / scale_factors[l].
+ *  in:  the left features as the chain holds them: feat_uv B x NF x 2 double, feat_oct B x NF, feat_desc B x NF x 32; the right
+ *       key-points: r_uv B x NR x 2 FLOAT (kp.pt), r_oct B x NR, r_desc B x NR x 32; n_left / n_right B int32 or NULL (all NF / NR):
+ *       slots at or beyond a frame's count are padding - they join nothing and their outputs are -1.
+ *  left / right: the pyramids (gl_image_pyramid).  The level image is the ROI as in the reference: column 0 is the ROI's column 0 and
+ *       `cols` of :286 is width[l].
+ *  out: feat_ur, feat_depth B x NF float: u_right and depth, -1 / -1 for a feature without a match (and after the median rule's reset);
+ *       match_r B x NF int32 or NULL: the right index pushed at :332 - also for a feature the median rule resets -, -1 otherwise;
+ *       sad B x NF int32 or NULL: the best SAD of such a feature, -1 otherwise;
+ *       stat B x 4 int32 or NULL: {features that pass :261, entries of vDistIdx, entries reset by :341-348, the median SAD or -1}.
+ *
+ *  The rules as the reference states them (the model cites each line): the row band minr = floor(kpY - r) .. maxr = ceil(kpY + r) with
+ *  r = 2.0f * scale_factors[octave], in float; the left row is (size_t)(float)uv.y; candidates have levelL - 1 <= octave <= levelL + 1
+ *  and minU <= uR <= maxU (minU = uL - maxD, maxU = uL; a feature with maxU < 0 is skipped); the winner is the FIRST strict minimum
+ *  below 100 in ascending right index, and goes on iff its distance is below 75; scaleduL / scaledvL = round(double uv x (double)inv) in
+ *  double, scaleduR0 = round(uR0 x inv) in FLOAT, round half away from zero; skipped iff scaleduR0 < 0 or scaleduR0 + 11 >= width[l];
+ *  eleven 11 x 11 windows (incR = -5 .. 5), each with its own centre value subtracted, L1 distance in integers, first strict minimum,
+ *  dropped at incR = -5 / +5; deltaR = (d1 - d3) / (2.0f * (d1 + d3 - 2.0f * d2)), dropped outside [-1, 1]; bestuR = sf[l] *
+ *  ((float)scaleduR0 + (float)bestincR + deltaR); kept iff 0 <= uL - bestuR < maxD; a disparity of 0 becomes (float)0.01 with bestuR =
+ *  (float)((double)uL - 0.01); depth = mbf / disparity.  The median rule: median = the SAD at position n / 2 of the ascending list,
+ *  thDist = (1.5f * 1.4f) * (float)median, every entry with (float)sad >= thDist is reset to -1 / -1 - so a median of 0 resets ALL.
+ *
+ *  Deviations - each where the reference indexes out of range or throws:
+ *   1. the rows of a right key-point outside [0, height) are dropped (the reference writes past vRowIndices);
+ *   2. a left feature with (float)uv.y < 0 or (int)(float)uv.y outside [0, height) is skipped;
+ *   3. a left feature or right key-point whose octave is outside [0, nlevels) takes no part;
+ *   4. a feature any of whose twelve windows would leave its level image is skipped (cv::Mat::rowRange / colRange throw; :286 only tests
+ *      scaleduR0 >= 0 although the first right window starts at scaleduR0 - 10);
+ *   5. an empty vDistIdx changes nothing (the reference reads element 0 of an empty vector).
+ *  ORB key-points keep 16 px of border at their level, so no extractor output meets 1 - 4.
+ *
+ *  NF or NR above GL_STEREO_MATCH_MAX, nlevels outside 1 .. 8, a level with width / height < 1 or stride < width, B < 1, cam height < 1,
+ *  a NULL required pointer: GL_ERR_ARG, nothing is written. */
+#define GL_STEREO_MATCH_MAX 4096
+typedef struct gl_stereo_in {
+  const double* feat_uv;
+  const int32_t* feat_oct;
+  const uint8_t* feat_desc;
+  const float* r_uv;
+  const int32_t* r_oct;
+  const uint8_t* r_desc;
+  const int32_t* n_left;
+  const int32_t* n_right;
+} gl_stereo_in;
+/* B frames' pyramids in one byte buffer: pixel (x, y) of level l of frame b is data[b * frame_stride + offset[l] + y * stride[l] + x].
+ * The stride lets a host upload mvImagePyramid's bordered buffers as they stand. */
+typedef struct gl_image_pyramid {
+  int32_t nlevels; /* 1 .. 8 */
+  int32_t reserved_;
+  int32_t width[8], height[8];
+  int64_t stride[8]; /* bytes per row */
+  int64_t offset[8]; /* bytes from a frame's base */
+  int64_t frame_stride;
+  const uint8_t* data;
+} gl_image_pyramid;
+typedef struct gl_stereo_out {
+  float* feat_ur;
+  float* feat_depth;
+  int32_t* match_r;
+  int32_t* sad;
+  int32_t* stat;
+} gl_stereo_out;
+int gl_stereo_matches(gl_ctx_t* ctx, const gl_camera* cam, double scale_factor, int B, int NF, int NR, const gl_stereo_in* in,
+                      const gl_image_pyramid* left, const gl_image_pyramid* right, const gl_stereo_out* out);
 
 /* ---- frame end and hand-over: from one tracked frame to the next on the device ------------------ */
 /* What the reference does between two calls of gl_track_frame_chain_map - the tail of Tracking::track, GMMLoc::needNewKeyFrame,

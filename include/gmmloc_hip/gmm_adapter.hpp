@@ -16,6 +16,7 @@
 //   GMMLoc::createMapPointsFromStereo               (gmmloc_opt.cpp:36-113: createMapPointsFromStereo; on the resident map, with the
 //                                                   association before it and the points' refresh behind it: processKeyFrameInMap)
 //   Tracking::createTemporalPoints                  (tracking.cpp:411-465: createTemporalPoints)
+//   Frame::computeStereoMatches                     (frame.cpp:179-349: computeStereoMatches, u_right and depth of a frame's features)
 //   Localization::createMapPoints                   (localization_opt.cpp:206-454, the loop over the neighbours with the triangulation:
 //                                                   createMapPointsInMap on the resident map)
 //   Localization::removeMapPoints                   (localization.cpp:127-152) with num_visible_ / num_found_ / ref_idx_ and
@@ -55,6 +56,7 @@ namespace gmmloc_hip {
 //    loadVocabulary / bowTransform / bowTransformIntoTables likewise: a host that runs its own DBoW2 and uploads feat_vec_ keeps working
 //    endFrame / noteReplaced / nextFrame likewise: a host that builds mappoints_ and the next frame's rows from the chain's copies back
 //    keeps working, one that calls these drops the loop and the copies
+//    computeStereoMatches likewise: a host that runs the reference's own OpenCV code and uploads u_right / depth keeps working
 constexpr int kAdapterVersion = 5;
 
 inline void check(int rc, const char* what) {
@@ -662,6 +664,91 @@ class GMM {
     check(gl_memcpy_d2h(ctx_, rows.last_valid.data(), out.last_valid, NF), "d2h");
     check(gl_memcpy_d2h(ctx_, rows.last_desc.data(), out.last_desc, NF * 32), "d2h");
     return flag;
+  }
+  // ---- stereo depth: Frame::computeStereoMatches (frame.cpp:179-349) on the device (gl_stereo_matches; the rules and the declared
+  // deviations are in gmmloc_hip.h).  Host vectors in and out; a pyramid level is the ROI of mvImagePyramid[l] as it lies in its
+  // bordered buffer: the pointer to its first pixel, its size and the buffer's bytes per row.  One upload, one synchronise.
+  struct ImageLevel {
+    const uint8_t* ptr;
+    int32_t width, height;
+    int64_t stride;
+  };
+  struct RightKeyPoints {
+    std::vector<float> uv;        // NR x 2 (kp.pt)
+    std::vector<int32_t> oct;     // NR
+    std::vector<uint8_t> desc;    // NR x 32
+  };
+  struct StereoMatches {
+    std::vector<float> ur, depth;        // NF: Feature::u_right, Feature::depth (-1: none)
+    std::vector<int32_t> match_r, sad;   // NF: the right key-point and the best SAD of a feature pushed at :332, -1 otherwise
+    int32_t stat[4] = {0, 0, 0, -1};     // {features that pass :261, entries of vDistIdx, entries reset, the median SAD or -1}
+  };
+  StereoMatches computeStereoMatches(const std::vector<double>& uv, const std::vector<int32_t>& oct, const std::vector<uint8_t>& desc,
+                                     const RightKeyPoints& right, const std::vector<ImageLevel>& pyr_left,
+                                     const std::vector<ImageLevel>& pyr_right, double scale_factor = 1.2) {
+    const size_t NF = oct.size(), NR = right.oct.size(), NL = pyr_left.size();
+    if (uv.size() != NF * 2 || desc.size() != NF * 32 || right.uv.size() != NR * 2 || right.desc.size() != NR * 32)
+      throw std::runtime_error("computeStereoMatches: arrays of different lengths");
+    if (NL < 1 || NL > 8 || pyr_right.size() != NL) throw std::runtime_error("computeStereoMatches: 1 .. 8 levels, the same on both sides");
+    StereoMatches r;
+    r.ur.assign(NF, -1.0f), r.depth.assign(NF, -1.0f), r.match_r.assign(NF, -1), r.sad.assign(NF, -1);
+    if (!NF || !NR) return r;
+    size_t off = 64;
+    auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += (bytes + 63) / 64 * 64;
+      return at;
+    };
+    const size_t o_uv = take(NF * 16), o_oct = take(NF * 4), o_desc = take(NF * 32), o_ruv = take(NR * 8), o_roct = take(NR * 4),
+                 o_rdesc = take(NR * 32), o_ur = take(NF * 4), o_dep = take(NF * 4), o_m = take(NF * 4), o_sad = take(NF * 4);
+    gl_image_pyramid pyr[2] = {};
+    const std::vector<ImageLevel>* side[2] = {&pyr_left, &pyr_right};
+    size_t o_img[2][8], n_img[2][8];
+    for (int s = 0; s < 2; ++s) {
+      pyr[s].nlevels = (int32_t)NL;
+      const size_t base = off;
+      for (size_t l = 0; l < NL; ++l) {
+        const ImageLevel& im = (*side[s])[l];
+        if (!im.ptr || im.width < 1 || im.height < 1 || im.stride < im.width) throw std::runtime_error("computeStereoMatches: bad level image");
+        n_img[s][l] = (size_t)(im.height - 1) * (size_t)im.stride + (size_t)im.width;
+        o_img[s][l] = take(n_img[s][l]);
+        pyr[s].width[l] = im.width, pyr[s].height[l] = im.height, pyr[s].stride[l] = im.stride, pyr[s].offset[l] = (int64_t)(o_img[s][l] - base);
+      }
+      pyr[s].frame_stride = (int64_t)(off - base);
+    }
+    char* b = pooled(16, off).as<char>();
+    auto put = [this](void* dst, const void* src, size_t bytes) { check(gl_memcpy_h2d(ctx_, dst, src, bytes), "h2d"); };
+    put(b + o_uv, uv.data(), NF * 16);
+    put(b + o_oct, oct.data(), NF * 4);
+    put(b + o_desc, desc.data(), NF * 32);
+    put(b + o_ruv, right.uv.data(), NR * 8);
+    put(b + o_roct, right.oct.data(), NR * 4);
+    put(b + o_rdesc, right.desc.data(), NR * 32);
+    for (int s = 0; s < 2; ++s) {
+      for (size_t l = 0; l < NL; ++l) put(b + o_img[s][l], (*side[s])[l].ptr, n_img[s][l]);
+      pyr[s].data = reinterpret_cast<uint8_t*>(b + o_img[s][0]) - pyr[s].offset[0];  // (the side's base)
+    }
+    gl_stereo_in in{};
+    in.feat_uv = reinterpret_cast<double*>(b + o_uv);
+    in.feat_oct = reinterpret_cast<int32_t*>(b + o_oct);
+    in.feat_desc = reinterpret_cast<uint8_t*>(b + o_desc);
+    in.r_uv = reinterpret_cast<float*>(b + o_ruv);
+    in.r_oct = reinterpret_cast<int32_t*>(b + o_roct);
+    in.r_desc = reinterpret_cast<uint8_t*>(b + o_rdesc);
+    gl_stereo_out out{};
+    out.feat_ur = reinterpret_cast<float*>(b + o_ur);
+    out.feat_depth = reinterpret_cast<float*>(b + o_dep);
+    out.match_r = reinterpret_cast<int32_t*>(b + o_m);
+    out.sad = reinterpret_cast<int32_t*>(b + o_sad);
+    out.stat = reinterpret_cast<int32_t*>(b);
+    check(gl_stereo_matches(ctx_, &cam_, scale_factor, 1, (int)NF, (int)NR, &in, &pyr[0], &pyr[1], &out), "gl_stereo_matches");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    check(gl_memcpy_d2h(ctx_, r.ur.data(), out.feat_ur, NF * 4), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.depth.data(), out.feat_depth, NF * 4), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.match_r.data(), out.match_r, NF * 4), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.sad.data(), out.sad, NF * 4), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.stat, out.stat, 16), "d2h");
+    return r;
   }
   // GMMLoc::processKeyFrame's GMM half for key-frame kf_row of the resident map, whose own table rows the host has uploaded (the rows
   // of kf_pose / kf_twc / kf_uvr / kf_oct in the views of setResidentMap, and the arrays below): gl_search2d -> gl_create_stereo_points ->

@@ -23,6 +23,7 @@ from .map_grow import map_add, map_fuse, fuse_observations_from_map, map_views, 
 from . import bow  # noqa: F401
 from . import stereo  # noqa: F401
 from .stereo import stereo_matches  # noqa: F401
+from . import orb  # noqa: F401
 from .bow import Vocabulary  # noqa: F401
 from .map_stats import map_stats_alloc, track_frame_with_stats, remove_map_points_from_map  # noqa: F401
 from .frame_step import track_frame_step  # noqa: F401

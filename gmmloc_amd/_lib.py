@@ -109,6 +109,14 @@ class gl_stereo_out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("feat_ur", "feat_depth", "match_r", "sad", "stat")]
 
 
+class gl_orb_in(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("kp_xy", "kp_oct", "n_kp", "kp_angle", "pattern")] + [("blur_w", C.POINTER(C.c_int32)), ("scale_factor", C.c_double)]
+
+
+class gl_orb_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("desc", "angle", "moments", "uv32", "uv64", "stat")]
+
+
 class gl_frame_end_in(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("feat_mp", "match_last", "match_local", "match_kf", "outlier", "local_mp", "n_local_mp", "counts2", "ref_kf",
                                           "last_observed", "feat_depth")]
@@ -257,6 +265,8 @@ def load():
         "gl_create_temporal_points": (i32, [vp, P(gl_camera), i32, i32, vp, C.c_float, vp]),
         "gl_stereo_matches": (i32, [vp, P(gl_camera), C.c_double, i32, i32, i32, P(gl_stereo_in), P(gl_image_pyramid), P(gl_image_pyramid),
                                     P(gl_stereo_out)]),
+        "gl_orb_describe": (i32, [vp, i32, i32, P(gl_orb_in), P(gl_image_pyramid), P(gl_orb_out)]),
+        "gl_orb_default_blur": (i32, [C.c_double, P(C.c_int32)]),
         "gl_optimize_current_pose": (i32, [vp, P(gl_camera), P(gl_params), i32, i32, vp, vp, vp, vp, vp, vp]),
         "gl_joint_optimization": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, i32, i32] + [vp] * 11),
         "gl_joint_optimization_stoppable": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, i32, i32] + [vp] * 12),

@@ -198,6 +198,7 @@ struct Ctx {
   hipStream_t lane_stream[3] = {nullptr, nullptr, nullptr};  // further lanes of the pipelined local BA in batches (launch_ba_pipe)
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   int pipe_hint = 0;         // cycles the last pipelined local BA needed (the next call enqueues that many + 2 ahead)
+  const void* orb_pattern = nullptr;  // the device pattern gl_orb_describe has read back and found inside [-13, 13] (gmmloc_hip.h)
   // optional statistics buffer (gl_ctx_set_stats_buffer)
   int32_t* stats = nullptr;
   int32_t* stats_iters = nullptr;  // (gl_ctx_set_stats_buffers) outer Levenberg iterations per frame

@@ -112,6 +112,7 @@ void gl_default_params(gl_params* p);
  * gl_track_frame_chain_back        | K bf size      | sigma2_inv                                                          | radii, steps, band
  * gl_track_frame_chain_map         | K bf size      | sigma2_inv                                                          | radii, steps, band
  * gl_stereo_matches                | fx bf height   | -                                                                   | level scales, inverses
+ * gl_orb_describe                  | -              | -                                                                   | the EXTRACTOR's level scales
  *
  * tri_lambda2 weighs the structure edge of the per-point optimisations (and scales their threshold, tri_str_thresh * tri_lambda2);
  * ba_lambda2 does both for the pose / window optimisations (threshold tri_str_thresh * ba_lambda2).  gl_search_by_bow,
@@ -1586,6 +1587,88 @@ typedef struct gl_stereo_out {
 } gl_stereo_out;
 int gl_stereo_matches(gl_ctx_t* ctx, const gl_camera* cam, double scale_factor, int B, int NF, int NR, const gl_stereo_in* in,
                       const gl_image_pyramid* left, const gl_image_pyramid* right, const gl_stereo_out* out);
+
+/* ---- ORB orientation and descriptors: the second half of ORBextractor (orb_extractor.cpp) for B images ------------------- */
+/* IC_Angle (:77-101, :466-473), the 7 x 7 blur of every level (:1029-1030), the steered-BRIEF read (:104-147, :979-986) and the scaling
+ * of the key-points (:1039-1046), from the key-points AT THEIR LEVEL and the image pyramid gl_stereo_matches reads.  B is the number of
+ * pyramids in `pyr` (a stereo frame's two sides are B = 2 with one buffer, or two calls).  The pyramid, cv::FAST and the octree stay
+ * with the host.  Two kernels on the context's stream (k_orb_blur: the blurred pyramid into the context's main scratch block, same
+ * geometry, tightly packed, every byte written before k_orb_describe reads it), device pointers only except blur_w (4 host ints).
+ * The sequential model is tests/orb_ref.py, the hand-built cases tests/orb_cases.py.
+ *
+ *  in:  kp_xy B x N x 2 int32: the key-point at its level in ROI coordinates, pt + minBorder of :814-815 (cv::FAST gives integers, so
+ *       cvRound of :80 / :109 is the identity); kp_oct B x N int32; n_kp B int32 or NULL (all N): slots at or beyond it are padding;
+ *       kp_angle B x N float or NULL: when given the orientation is NOT computed, this angle (degrees) steers the descriptor and is
+ *       copied to `angle`, and `moments` is 0 0; pattern 512 x 2 int8 (x, y) on the device: the host's own bit_pattern_31_ - the
+ *       library ships none; blur_w: the symmetric 7-tap kernel in Q8, centre first (gl_orb_default_blur); scale_factor: the extractor's
+ *       own table (:408-418), sf[0] = 1.0f, sf[i] = (float)((double)sf[i - 1] * scale_factor) - NOT the table of init_config.hpp:63-79
+ *       (a float times (float)scale_factor), which gl_stereo_matches and the matchers use: for 1.2 the two differ from level 3 on, by one to five units in the last place.
+ *  out: desc B x N x 32 uint8; angle B x N float or NULL; moments B x N x 2 int32 {m_10, m_01} or NULL; uv32 B x N x 2 float or NULL:
+ *       kp.pt after :1045, (float)x * sf[oct], (float)y * sf[oct] - one float multiply, level 0 untouched; uv64 B x N x 2 double or
+ *       NULL: the same values widened, as Feature stores them; stat B x 2 int32 or NULL: {described, skipped} among the first n_kp.
+ *       A skipped or padding slot gets a zero descriptor, angle -1, moments 0 0 and uv -1 -1.
+ *
+ *  rule                   | reference        | stated as
+ *  -----------------------+------------------+------------------------------------------------------------------------------------
+ *  patch                  | :449-463         | rows v = -15 .. 15, columns |u| <= u_max[|v|], u_max = {15, 15, 15, 15, 14, 14, 14, 13, 13,
+ *                         |                  | 12, 11, 10, 9, 8, 6, 3}: 749 pixels
+ *  moments                | :78-98           | m_10 = sum u I(x + u, y + v), m_01 = sum v I(x + u, y + v) in int32 on the UNBLURRED level
+ *  angle                  | :100             | fastAtan2((float)m_01, (float)m_10), DECLARED here since OpenCV's binary is not at hand: ax = |x|,
+ *                         |                  | ay = |y|; c = min / (max + (float)DBL_EPSILON), c2 = c * c,
+ *                         |                  | a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c with p_k = (float)c_k * (float)(180 / pi), c_1 =
+ *                         |                  | 0.9997878412794807, c_3 = -0.3258083974640975, c_5 = 0.1555786518463281, c_7 = -0.04432655554792128;
+ *                         |                  | a = 90 - a when ay > ax, then 180 - a when x < 0, then 360 - a when y < 0; float, one rounding
+ *                         |                  | per operation, the division correctly rounded, no contraction; (0, 0) -> 0.  At most 0.0097
+ *                         |                  | degrees from atan2 (0.009547 for the polynomial itself, at min = max, plus the float roundings
+ *                         |                  | of values up to 360; a sample of 20 000 integer pairs gives 0.00954).  Parity with a host's OpenCV binary is UNPINNED;
+ *                         |                  | `moments` is the exact part.
+ *  blur                   | :1029-1030       | on the level's ROI alone (the reference clones the ROI: the bordered buffer's border is never
+ *                         |                  | read), BORDER_REFLECT_101 by index (-1 -> 1, n -> n - 2); row pass r = sum_k w[|k|] I(x + k, y),
+ *                         |                  | column pass s = sum_k w[|k|] r(x, y + k), both exact integer sums; the result is
+ *                         |                  | min((s + 2^15) >> 16, 255) in 32-bit integers.  Which weights an OpenCV build uses is unpinned:
+ *                         |                  | hence the argument.
+ *  steering               | :106-107         | angle_rad = angle * (float)(CV_PI / 180.f) in float; a = (float)cos((double)angle_rad),
+ *                         |                  | b = (float)sin((double)angle_rad)
+ *  sample (x, y)          | :112-114         | row cvRound(x * b + y * a), column cvRound(x * a - y * b) of the BLURRED level, relative to the
+ *                         |                  | key-point: float products and sums, one rounding each, no contraction; cvRound rounds half to even
+ *  bit j of byte i        | :116-143         | t0 < t1 for the samples 16 i + 2 j and 16 i + 2 j + 1
+ *  scaling                | :1039-1046       | see uv32
+ *
+ *  Deviations - each where the reference would index out of range:
+ *   1. a key-point whose octave is outside [0, nlevels) is skipped;
+ *   2. a key-point nearer than 19 px to an edge of its level image (x < 19, x > width - 20, y < 19 or y > height - 20) is skipped: the
+ *      patch needs 15 px, the pattern reaches cvRound(13 sqrt 2) = 18 px; the extractor's own key-points keep 19 px;
+ *   3. a pattern entry outside [-13, 13]: GL_ERR_ARG.  The pattern lies on the device, so the call reads it back (1 KB, waits for the
+ *      stream) when a context first sees the pointer and whenever the pointer changes - otherwise the call is asynchronous.  A host
+ *      that rewrites the table in place is not checked again; the kernel clamps every entry to [-13, 13], so no read leaves the image.
+ *
+ *  blur_w: non-negative, w[0] + 2 (w[1] + w[2] + w[3]) in 1 .. 512, else GL_ERR_ARG.  N above GL_ORB_MAX, nlevels outside 1 .. 8, a
+ *  level with width / height < 1, stride < width or a negative offset, B < 1, N < 1, a NULL required pointer: GL_ERR_ARG, nothing is
+ *  written.  The host-side time this call saves (sixteen level blurs and 2 x 1 200 descriptors per stereo frame) is NOT measured. */
+#define GL_ORB_MAX 4096
+typedef struct gl_orb_in {
+  const int32_t* kp_xy;
+  const int32_t* kp_oct;
+  const int32_t* n_kp;
+  const float* kp_angle;
+  const int8_t* pattern;
+  const int32_t* blur_w; /* HOST memory: 4 ints */
+  double scale_factor;
+} gl_orb_in;
+typedef struct gl_orb_out {
+  uint8_t* desc;
+  float* angle;
+  int32_t* moments;
+  float* uv32;
+  double* uv64;
+  int32_t* stat;
+} gl_orb_out;
+int gl_orb_describe(gl_ctx_t* ctx, int B, int N, const gl_orb_in* in, const gl_image_pyramid* pyr, const gl_orb_out* out);
+/* w[0 .. 3] = the Q8 taps of the 7-tap Gaussian of that sigma, centre first - a DECLARED rule: g_i = exp(-i^2 / (2 sigma^2)) in double,
+ * normalised over the seven taps, w[i] = nearbyint(256 g_i) for i = 1 .. 3 and the centre takes the remainder, w[0] = 256 - 2 (w[1] +
+ * w[2] + w[3]).  sigma = 2 (:1030): the unrounded taps are 55.32 48.82 33.56 17.96, w = {54, 49, 34, 18}.  sigma <= 0 or not finite,
+ * or a negative centre: GL_ERR_ARG. */
+int gl_orb_default_blur(double sigma, int32_t* w);
 
 /* ---- frame end and hand-over: from one tracked frame to the next on the device ------------------ */
 /* What the reference does between two calls of gl_track_frame_chain_map - the tail of Tracking::track, GMMLoc::needNewKeyFrame,

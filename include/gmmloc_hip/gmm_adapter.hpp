@@ -17,6 +17,8 @@
 //                                                   association before it and the points' refresh behind it: processKeyFrameInMap)
 //   Tracking::createTemporalPoints                  (tracking.cpp:411-465: createTemporalPoints)
 //   Frame::computeStereoMatches                     (frame.cpp:179-349: computeStereoMatches, u_right and depth of a frame's features)
+//   ORBextractor's orientation and descriptors      (orb_extractor.cpp:77-147, :1029-1046: orbDescribe; the pyramid, FAST and the octree
+//                                                   stay with the host)
 //   Localization::createMapPoints                   (localization_opt.cpp:206-454, the loop over the neighbours with the triangulation:
 //                                                   createMapPointsInMap on the resident map)
 //   Localization::removeMapPoints                   (localization.cpp:127-152) with num_visible_ / num_found_ / ref_idx_ and
@@ -57,6 +59,7 @@ namespace gmmloc_hip {
 //    endFrame / noteReplaced / nextFrame likewise: a host that builds mappoints_ and the next frame's rows from the chain's copies back
 //    keeps working, one that calls these drops the loop and the copies
 //    computeStereoMatches likewise: a host that runs the reference's own OpenCV code and uploads u_right / depth keeps working
+//    orbDescribe likewise: a host that runs the reference's ORBextractor to its end keeps working
 constexpr int kAdapterVersion = 5;
 
 inline void check(int rc, const char* what) {
@@ -748,6 +751,89 @@ class GMM {
     check(gl_memcpy_d2h(ctx_, r.match_r.data(), out.match_r, NF * 4), "d2h");
     check(gl_memcpy_d2h(ctx_, r.sad.data(), out.sad, NF * 4), "d2h");
     check(gl_memcpy_d2h(ctx_, r.stat, out.stat, 16), "d2h");
+    return r;
+  }
+  // ---- ORB orientation and descriptors: the regular half of ORBextractor (orb_extractor.cpp: IC_Angle, the 7 x 7 blur, the steered
+  // BRIEF read, the scaling of the key-points) for ONE image on the device (gl_orb_describe; the rules and the declared deviations are
+  // in gmmloc_hip.h).  kp_xy: the key-points AT THEIR LEVEL in ROI coordinates, kp_oct their octaves; pattern: the host's own
+  // bit_pattern_31_ as 512 x 2 int8 (checked here: an entry outside [-13, 13] throws); levels as for computeStereoMatches; blur_w: the
+  // four Q8 taps (empty: gl_orb_default_blur(2)); kp_angle: empty, or the angles that steer instead of the computed orientation.
+  // One upload, one synchronise.
+  struct OrbFeatures {
+    std::vector<uint8_t> desc;      // N x 32
+    std::vector<float> angle;       // N (-1: skipped)
+    std::vector<int32_t> moments;   // N x 2 {m_10, m_01}
+    std::vector<float> uv32;        // N x 2: kp.pt
+    std::vector<double> uv64;       // N x 2: Feature::uv
+    int32_t stat[2] = {0, 0};       // {described, skipped}
+  };
+  OrbFeatures orbDescribe(const std::vector<int32_t>& kp_xy, const std::vector<int32_t>& kp_oct, const std::vector<int8_t>& pattern,
+                          const std::vector<ImageLevel>& levels, std::vector<int32_t> blur_w = {}, double scale_factor = 1.2,
+                          const std::vector<float>& kp_angle = {}) {
+    const size_t N = kp_oct.size(), NL = levels.size();
+    if (kp_xy.size() != N * 2 || (!kp_angle.empty() && kp_angle.size() != N)) throw std::runtime_error("orbDescribe: arrays of different lengths");
+    if (pattern.size() != 1024) throw std::runtime_error("orbDescribe: the pattern has 512 x 2 entries");
+    for (int8_t v : pattern)
+      if (v < -13 || v > 13) throw std::runtime_error("orbDescribe: a pattern entry outside [-13, 13]");
+    if (NL < 1 || NL > 8) throw std::runtime_error("orbDescribe: 1 .. 8 levels");
+    if (blur_w.empty()) {
+      blur_w.resize(4);
+      check(gl_orb_default_blur(2.0, blur_w.data()), "gl_orb_default_blur");
+    }
+    if (blur_w.size() != 4) throw std::runtime_error("orbDescribe: blur_w has four taps");
+    OrbFeatures r;
+    r.desc.assign(N * 32, 0), r.angle.assign(N, -1.0f), r.moments.assign(N * 2, 0), r.uv32.assign(N * 2, -1.0f), r.uv64.assign(N * 2, -1.0);
+    if (!N) return r;
+    size_t off = 64;
+    auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += (bytes + 63) / 64 * 64;
+      return at;
+    };
+    const size_t o_pat = take(1024), o_xy = take(N * 8), o_oct = take(N * 4), o_ang = take(N * 4), o_desc = take(N * 32), o_angle = take(N * 4),
+                 o_mom = take(N * 8), o_uv32 = take(N * 8), o_uv64 = take(N * 16);
+    gl_image_pyramid pyr = {};
+    pyr.nlevels = (int32_t)NL;
+    size_t o_img[8], n_img[8];
+    const size_t base = off;
+    for (size_t l = 0; l < NL; ++l) {
+      const ImageLevel& im = levels[l];
+      if (!im.ptr || im.width < 1 || im.height < 1 || im.stride < im.width) throw std::runtime_error("orbDescribe: bad level image");
+      n_img[l] = (size_t)(im.height - 1) * (size_t)im.stride + (size_t)im.width;
+      o_img[l] = take(n_img[l]);
+      pyr.width[l] = im.width, pyr.height[l] = im.height, pyr.stride[l] = im.stride, pyr.offset[l] = (int64_t)(o_img[l] - base);
+    }
+    pyr.frame_stride = (int64_t)(off - base);
+    char* b = pooled(17, off).as<char>();
+    auto put = [this](void* dst, const void* src, size_t bytes) { check(gl_memcpy_h2d(ctx_, dst, src, bytes), "h2d"); };
+    put(b + o_pat, pattern.data(), 1024);
+    put(b + o_xy, kp_xy.data(), N * 8);
+    put(b + o_oct, kp_oct.data(), N * 4);
+    if (!kp_angle.empty()) put(b + o_ang, kp_angle.data(), N * 4);
+    for (size_t l = 0; l < NL; ++l) put(b + o_img[l], levels[l].ptr, n_img[l]);
+    pyr.data = reinterpret_cast<uint8_t*>(b + base);
+    gl_orb_in in{};
+    in.kp_xy = reinterpret_cast<int32_t*>(b + o_xy);
+    in.kp_oct = reinterpret_cast<int32_t*>(b + o_oct);
+    in.kp_angle = kp_angle.empty() ? nullptr : reinterpret_cast<float*>(b + o_ang);
+    in.pattern = reinterpret_cast<int8_t*>(b + o_pat);
+    in.blur_w = blur_w.data();
+    in.scale_factor = scale_factor;
+    gl_orb_out out{};
+    out.desc = reinterpret_cast<uint8_t*>(b + o_desc);
+    out.angle = reinterpret_cast<float*>(b + o_angle);
+    out.moments = reinterpret_cast<int32_t*>(b + o_mom);
+    out.uv32 = reinterpret_cast<float*>(b + o_uv32);
+    out.uv64 = reinterpret_cast<double*>(b + o_uv64);
+    out.stat = reinterpret_cast<int32_t*>(b);
+    check(gl_orb_describe(ctx_, 1, (int)N, &in, &pyr, &out), "gl_orb_describe");
+    check(gl_ctx_synchronize(ctx_), "sync");
+    check(gl_memcpy_d2h(ctx_, r.desc.data(), out.desc, N * 32), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.angle.data(), out.angle, N * 4), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.moments.data(), out.moments, N * 8), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.uv32.data(), out.uv32, N * 8), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.uv64.data(), out.uv64, N * 16), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.stat, out.stat, 8), "d2h");
     return r;
   }
   // GMMLoc::processKeyFrame's GMM half for key-frame kf_row of the resident map, whose own table rows the host has uploaded (the rows

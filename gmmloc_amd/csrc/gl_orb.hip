@@ -190,7 +190,7 @@ __global__ __launch_bounds__(DS_T) void k_orb_describe(const OrbArgs A, const in
     if (live) {
       ang = kp_angle ? kp_angle[at] : fast_atan2_deg((float)m01, (float)m10);  // :100
       const float rad = ang * (float)(3.1415926535897932384626433832795 / 180.f);  // :103, :106
-      const float ca = (float)cos((double)rad), sb = (float)sin((double)rad);  // :107
+      const float ca = (float)cos((double)rad), sb = (float)sin((double)rad);  // the correctly rounded float cos / sin (:107 calls libm's cosf / sinf: the header's `steering` row)
       const uint8_t* centre = A.blurred + (int64_t)b * A.bframe_stride + pick(A.boffset, oct) + (int64_t)y * w + x;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {

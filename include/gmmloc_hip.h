@@ -1620,15 +1620,22 @@ int gl_stereo_matches(gl_ctx_t* ctx, const gl_camera* cam, double scale_factor, 
  *                         |                  | a = 90 - a when ay > ax, then 180 - a when x < 0, then 360 - a when y < 0; float, one rounding
  *                         |                  | per operation, the division correctly rounded, no contraction; (0, 0) -> 0.  At most 0.0097
  *                         |                  | degrees from atan2 (0.009547 for the polynomial itself, at min = max, plus the float roundings
- *                         |                  | of values up to 360; a sample of 20 000 integer pairs gives 0.00954).  Parity with a host's OpenCV binary is UNPINNED;
- *                         |                  | `moments` is the exact part.
+ *                         |                  | of values up to 360; a sample of 20 000 integer pairs gives 0.00954).  Parity of this polynomial with a host's OpenCV binary is UNPINNED
+ *                         |                  |; the patch, `moments`, the argument order and everything from `steering` down are
+ *                         |                  | held to the reference's own extractor code (oracle/orb_ref.cpp, tests/test_orb_ref_pin.py).
  *  blur                   | :1029-1030       | on the level's ROI alone (the reference clones the ROI: the bordered buffer's border is never
  *                         |                  | read), BORDER_REFLECT_101 by index (-1 -> 1, n -> n - 2); row pass r = sum_k w[|k|] I(x + k, y),
  *                         |                  | column pass s = sum_k w[|k|] r(x, y + k), both exact integer sums; the result is
  *                         |                  | min((s + 2^15) >> 16, 255) in 32-bit integers.  Which weights an OpenCV build uses is unpinned:
  *                         |                  | hence the argument.
- *  steering               | :106-107         | angle_rad = angle * (float)(CV_PI / 180.f) in float; a = (float)cos((double)angle_rad),
- *                         |                  | b = (float)sin((double)angle_rad)
+ *  steering               | :103, :106-107   | angle_rad = angle * (float)(CV_PI / 180.f) in float.  The reference's `cos(angle)` / `sin(angle)` on
+ *                         |                  | that float are, under its `using namespace std` (:69), the FLOAT overloads of <cmath>: libm's cosf /
+ *                         |                  | sinf, whose last bit is that libm's choice (oracle/orb_ref.cpp asserts the overload).  The device's
+ *                         |                  | rule is the CORRECTLY ROUNDED float cosine and sine, computed as a = (float)cos((double)angle_rad),
+ *                         |                  | b = (float)sin((double)angle_rad): a stated deviation.  Measured against g++ 11.4 / glibc 2.35
+ *                         |                  |: that libm's a or b is the neighbouring float at 2.59 % of the angles k x 1e-5
+ *                         |                  | degrees (cos 1.30 %, sin 1.29 %), never further; on 27 300 key-points of random scenes no descriptor
+ *                         |                  | bit changes with it.  A libm-specific result is no target, and the device's own cosf would be a third choice.
  *  sample (x, y)          | :112-114         | row cvRound(x * b + y * a), column cvRound(x * a - y * b) of the BLURRED level, relative to the
  *                         |                  | key-point: float products and sums, one rounding each, no contraction; cvRound rounds half to even
  *  bit j of byte i        | :116-143         | t0 < t1 for the samples 16 i + 2 j and 16 i + 2 j + 1

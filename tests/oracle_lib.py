@@ -391,8 +391,66 @@ class DBoW2Ref:
         return int(self.lib.dbref_distance(_p(a), _p(b)))
 
 
+class OrbRef:
+    """The reference's own ORB extractor (oracle/orb_ref.cpp -> oracle/_ref/liborb_ref.so): thin methods over the orbref_ interface.
+    A level is a 2-D uint8 array whose rows may be strided (a view into a larger buffer is passed as it lies)."""
+
+    def __init__(self, lib):
+        self.lib = lib
+        lib.orbref_tables.restype = C.c_int
+        lib.orbref_tables.argtypes = [C.c_void_p] * 3
+        lib.orbref_orientation.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        lib.orbref_describe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.orbref_steering.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+
+    @staticmethod
+    def _level(img):
+        assert img.dtype == np.uint8 and img.ndim == 2 and img.strides[1] == 1 and img.strides[0] >= img.shape[1]
+        return img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0], img.strides[0]
+
+    def tables(self):
+        """-> dict(umax (16,) i32, pattern (512, 2) i32 - the extractor's own, npattern, scale_factor (8,) f32)"""
+        umax, pattern, sf = np.zeros(16, np.int32), np.zeros((512, 2), np.int32), np.zeros(8, np.float32)
+        n = self.lib.orbref_tables(_p(umax), _p(pattern), _p(sf))
+        assert n >= 0, "the extractor's tables do not have 16 and 8 entries"
+        return dict(umax=umax, pattern=pattern, npattern=int(n), scale_factor=sf)
+
+    def orientation(self, img, kp_xy):
+        """computeOrientation for key-points at least 15 px inside -> angle (n,) f32, m_10 (n,) i32, m_01 (n,) i32"""
+        kp_xy = np.ascontiguousarray(kp_xy, dtype=np.int32).reshape(-1, 2)
+        h, w = img.shape
+        assert ((kp_xy >= 15) & (kp_xy <= np.array([w - 16, h - 16]))).all(), "a patch would leave the level"
+        n = len(kp_xy)
+        angle, m10, m01 = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self.lib.orbref_orientation(*self._level(img), _p(kp_xy), n, _p(angle), _p(m10), _p(m01))
+        return angle, m10, m01
+
+    def describe(self, blurred, kp_xy, kp_angle, pattern=None):
+        """computeDescriptors on a blurred level for key-points at least 19 px inside; pattern (512, 2) int8 within [-13, 13], or
+        None: the extractor's own -> desc (n, 32) u8"""
+        kp_xy = np.ascontiguousarray(kp_xy, dtype=np.int32).reshape(-1, 2)
+        kp_angle = np.ascontiguousarray(kp_angle, dtype=np.float32).reshape(-1)
+        h, w = blurred.shape
+        assert len(kp_angle) == len(kp_xy) and ((kp_xy >= 19) & (kp_xy <= np.array([w - 20, h - 20]))).all(), "a sample would leave the level"
+        assert np.isfinite(kp_angle).all()
+        if pattern is not None:
+            pattern = np.ascontiguousarray(pattern, dtype=np.int8)
+            assert pattern.shape == (512, 2) and np.abs(pattern.astype(np.int32)).max() <= 13
+        desc = np.zeros((len(kp_xy), 32), np.uint8)
+        self.lib.orbref_describe(*self._level(blurred), _p(kp_xy), _p(kp_angle), len(kp_xy), _p(pattern), _p(desc))
+        return desc
+
+    def steering(self, kp_angle):
+        """(a, b) as computeOrbDescriptor's first two lines give them on this host -> (n, 2) f32"""
+        kp_angle = np.ascontiguousarray(kp_angle, dtype=np.float32).reshape(-1)
+        a, b = np.zeros(len(kp_angle), np.float32), np.zeros(len(kp_angle), np.float32)
+        self.lib.orbref_steering(_p(kp_angle), len(kp_angle), _p(a), _p(b))
+        return np.stack([a, b], 1)
+
+
 _cached = None
 _dbow2 = False
+_orb = {}
 
 
 def load_dbow2():
@@ -402,6 +460,15 @@ def load_dbow2():
         so = os.path.join(ODIR, "_ref", "libdbow2_ref.so")
         _dbow2 = DBoW2Ref(C.CDLL(so)) if os.path.exists(so) else None
     return _dbow2
+
+
+def load_orb_ref(contract=False):
+    """OrbRef, or None where oracle/_ref/liborb_ref.so was not built (no reference tree).  contract: the build with the reference's own
+    -O3 and contraction allowed - for measurements only"""
+    if contract not in _orb:
+        so = os.path.join(ODIR, "_ref", "liborb_ref_contract.so" if contract else "liborb_ref.so")
+        _orb[contract] = OrbRef(C.CDLL(so)) if os.path.exists(so) else None
+    return _orb[contract]
 
 
 def build():

@@ -123,7 +123,8 @@ def ic_angle(img, x, y, mut=()):
 
 
 def steer(angle):
-    """:106-107 -> (a, b) float32"""
+    """the declared steering -> (a, b) float32: the correctly rounded float cosine and sine.  (:106-107 call libm's cosf / sinf, one float
+    away at some angles: the header's `steering` row, tests/test_orb_ref_pin.py)"""
     rad = f32(f32(angle) * FACTOR_PI)
     return f32(math.cos(float(rad))), f32(math.sin(float(rad)))
 
@@ -166,9 +167,9 @@ def sample_offsets(pattern, a, b, mut=()):
     return cv_round(r, mut), cv_round(c, mut)
 
 
-def orb_descriptor(blurred, x, y, angle, pattern, mut=()):
-    """computeOrbDescriptor (:104-147) -> 32 bytes"""
-    a, b = steer(angle)
+def orb_descriptor(blurred, x, y, angle, pattern, mut=(), ab=None):
+    """computeOrbDescriptor (:104-147) -> 32 bytes.  ab: the steering (a, b) to use in place of steer(angle), as a host's libm gave it"""
+    a, b = steer(angle) if ab is None else (f32(ab[0]), f32(ab[1]))
     row, col = sample_offsets(pattern, a, b, mut)
     t = blurred[y + row, x + col].astype(np.int64)                        # GET_VALUE(0 .. 511)
     t0, t1 = t[0::2], t[1::2]
@@ -184,8 +185,9 @@ def live(levels, x, y, oct_):
     return EDGE_THRESHOLD <= x <= w - 1 - EDGE_THRESHOLD and EDGE_THRESHOLD <= y <= h - 1 - EDGE_THRESHOLD
 
 
-def describe(levels, kp_xy, kp_oct, pattern, blur_w, scale_factor=1.2, n_kp=None, kp_angle=None, mut=()):
+def describe(levels, kp_xy, kp_oct, pattern, blur_w, scale_factor=1.2, n_kp=None, kp_angle=None, mut=(), ab=None):
     """gl_orb_describe for ONE image: levels - its pyramid, 2-D uint8 arrays; kp_xy n x 2, kp_oct n; pattern 512 x 2 int8; blur_w 4 ints.
+    ab: n x 2 float32, the steering of every slot in place of steer(angle) (tests/test_orb_ref_pin.py: the reference host's own).
     -> dict(desc, angle, moments, uv32, uv64, stat) with n rows."""
     assert np.abs(pattern).max() <= REACH, "deviation 3: the call refuses this pattern"
     n = len(kp_oct)
@@ -208,7 +210,7 @@ def describe(levels, kp_xy, kp_oct, pattern, blur_w, scale_factor=1.2, n_kp=None
         else:
             angle = f32(kp_angle[i])
         out["angle"][i] = angle
-        out["desc"][i] = orb_descriptor(blurred[l], x, y, angle, pattern, mut)
+        out["desc"][i] = orb_descriptor(blurred[l], x, y, angle, pattern, mut, None if ab is None else ab[i])
         scale = sf[l] if l != 0 else f32(1.0)                              # :1039-1046
         out["uv32"][i] = (f32(f32(x) * scale), f32(f32(y) * scale))
         out["uv64"][i] = out["uv32"][i].astype(f64)

@@ -117,6 +117,10 @@ class gl_orb_out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("desc", "angle", "moments", "uv32", "uv64", "stat")]
 
 
+class gl_orb_detect_out(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("kp_xy", "kp_oct", "n_kp", "kp_response", "level_count", "stat", "cand_xy", "cand_resp", "cand_count")]
+
+
 class gl_frame_end_in(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("feat_mp", "match_last", "match_local", "match_kf", "outlier", "local_mp", "n_local_mp", "counts2", "ref_kf",
                                           "last_observed", "feat_depth")]
@@ -267,6 +271,11 @@ def load():
                                     P(gl_stereo_out)]),
         "gl_orb_describe": (i32, [vp, i32, i32, P(gl_orb_in), P(gl_image_pyramid), P(gl_orb_out)]),
         "gl_orb_default_blur": (i32, [C.c_double, P(C.c_int32)]),
+        "gl_orb_pyramid_layout": (i32, [i32, i32, i32, C.c_double, i32, i64, P(gl_image_pyramid)]),
+        "gl_orb_pyramid": (i32, [vp, i32, P(gl_image_pyramid), C.c_double]),
+        "gl_orb_features_per_level": (i32, [i32, i32, C.c_double, P(C.c_int32)]),
+        "gl_orb_detect_bound": (i32, [P(gl_image_pyramid), i32, C.c_double, P(C.c_int32)]),
+        "gl_orb_detect": (i32, [vp, i32, i32, P(gl_image_pyramid), i32, C.c_double, i32, i32, i32, P(gl_orb_detect_out)]),
         "gl_optimize_current_pose": (i32, [vp, P(gl_camera), P(gl_params), i32, i32, vp, vp, vp, vp, vp, vp]),
         "gl_joint_optimization": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, i32, i32] + [vp] * 11),
         "gl_joint_optimization_stoppable": (i32, [vp, vp, P(gl_camera), P(gl_params), i32, i32, i32, i32, i32] + [vp] * 12),

@@ -113,6 +113,8 @@ void gl_default_params(gl_params* p);
  * gl_track_frame_chain_map         | K bf size      | sigma2_inv                                                          | radii, steps, band
  * gl_stereo_matches                | fx bf height   | -                                                                   | level scales, inverses
  * gl_orb_describe                  | -              | -                                                                   | the EXTRACTOR's level scales
+ * gl_orb_pyramid(_layout)          | -              | -                                                                   | the EXTRACTOR's inverse scales
+ * gl_orb_detect                    | -              | -                                                                   | features per level
  *
  * tri_lambda2 weighs the structure edge of the per-point optimisations (and scales their threshold, tri_str_thresh * tri_lambda2);
  * ba_lambda2 does both for the pose / window optimisations (threshold tri_str_thresh * ba_lambda2).  gl_search_by_bow,
@@ -1591,8 +1593,8 @@ int gl_stereo_matches(gl_ctx_t* ctx, const gl_camera* cam, double scale_factor, 
 /* ---- ORB orientation and descriptors: the second half of ORBextractor (orb_extractor.cpp) for B images ------------------- */
 /* IC_Angle (:77-101, :466-473), the 7 x 7 blur of every level (:1029-1030), the steered-BRIEF read (:104-147, :979-986) and the scaling
  * of the key-points (:1039-1046), from the key-points AT THEIR LEVEL and the image pyramid gl_stereo_matches reads.  B is the number of
- * pyramids in `pyr` (a stereo frame's two sides are B = 2 with one buffer, or two calls).  The pyramid, cv::FAST and the octree stay
- * with the host.  Two kernels on the context's stream (k_orb_blur: the blurred pyramid into the context's main scratch block, same
+ * pyramids in `pyr` (a stereo frame's two sides are B = 2 with one buffer, or two calls).  The pyramid, cv::FAST and the octree are
+ * gl_orb_pyramid and gl_orb_detect below, whose outputs are this call's inputs.  Two kernels on the context's stream (k_orb_blur: the blurred pyramid into the context's main scratch block, same
  * geometry, tightly packed, every byte written before k_orb_describe reads it), device pointers only except blur_w (4 host ints).
  * The sequential model is tests/orb_ref.py, the hand-built cases tests/orb_cases.py.
  *
@@ -1676,6 +1678,99 @@ int gl_orb_describe(gl_ctx_t* ctx, int B, int N, const gl_orb_in* in, const gl_i
  * w[2] + w[3]).  sigma = 2 (:1030): the unrounded taps are 55.32 48.82 33.56 17.96, w = {54, 49, 34, 18}.  sigma <= 0 or not finite,
  * or a negative centre: GL_ERR_ARG. */
 int gl_orb_default_blur(double sigma, int32_t* w);
+
+/* ---- ORB detection: the first half of ORBextractor (orb_extractor.cpp) for B images ----------------------------------- */
+/* ComputePyramid (:1056-1080) and ComputeKeyPointsOctTree without its last loop (:739-819: the cell FAST and DistributeOctTree), so
+ * that a frame enters as its raw image: gl_orb_pyramid -> gl_orb_detect -> gl_orb_describe on one stream, the outputs of one the
+ * inputs of the next, nothing read back (orb.extract, GMM::orbExtract).  Asynchronous on the context's stream, device pointers only.
+ * Integer outputs of a sequential rule: a second run gives the same bytes.  The sequential model is tests/orb_detect_ref.py, the
+ * hand-built cases tests/orb_detect_cases.py.
+ *
+ * gl_orb_pyramid_layout (host only) fills the geometry of a pyramid of `nlevels` levels of a width x height image: stride = width[l] +
+ * row_pad, `lead` bytes in front of level 0, levels one behind the other, frame_stride their end; `data` is kept.
+ * gl_orb_pyramid computes levels 1 .. n - 1 of every frame from level 0, which the caller has written into the same buffer; one
+ * launch per level, a thread per pixel.  The 16 + 3 px border of :1072-1077 is NOT built: FAST on the reference's cells reads columns
+ * 16 .. cols - 17 of a level, resize reads the ROI alone, and every reader here takes ROI coordinates.  GL_ERR_ARG, nothing written:
+ * level sizes that are not the layout rule's for (width[0], height[0], scale_factor), levels or frames that overlap.
+ *
+ * gl_orb_detect: pyr as above; nfeatures, scale_factor, ini_th (20), min_th (7) the extractor's (:408-410); cand_cap: candidate slots
+ * per image and level in the context's main scratch block (1 .. 65 535); N: the output capacity per image.
+ *  out: kp_xy B x N x 2 int32: the key-point at its level in ROI coordinates, pt + minBorder of :814-815; kp_oct B x N int32; n_kp B -
+ *       exactly gl_orb_describe's inputs; kp_response B x N float or NULL (the corner score); level_count B x 8 or NULL; stat B x 4 or
+ *       NULL: {candidates, cells redone at min_th, key-points, overflow level mask}; cand_xy B x 8 x cand_cap x 2 int32, cand_resp
+ *       B x 8 x cand_cap float, cand_count B x 8, each or NULL: the candidate lists (vToDistributeKeys, ROI coordinates) for tests,
+ *       -1 -1 / 0 behind a level's count.  Slots at or beyond n_kp get xy -1 -1, octave -1, response 0.
+ *       Order: level ascending, within a level the order of the reference's vResultKeys (the node list's order).
+ *
+ *  rule                   | reference        | stated as
+ *  -----------------------+------------------+------------------------------------------------------------------------------------
+ *  level scales           | :413-424         | sf[0] = 1.0f, sf[i] = (float)((double)sf[i - 1] * scale_factor), inv[l] = 1.0f / sf[l]
+ *  level size             | :1058-1060       | cvRound((float)width * inv[l]) x cvRound((float)height * inv[l]), cvRound: half to even
+ *  resize                 | :1069            | each level from the level before it; OpenCV's 8-bit INTER_LINEAR in fixed point, DECLARED here
+ *                         |                  | since OpenCV's binary is not at hand: scale_x = 1.0 / ((double)dw / (double)sw); per destination
+ *                         |                  | column fx = (float)((dx + 0.5) * scale_x - 0.5) (double, one rounding per operation), sx =
+ *                         |                  | floor(fx), fx -= sx; sx < 0 gives (0, 0), sx >= sw - 1 gives (sw - 1, 0); a1 = cvRound(fx * 2048),
+ *                         |                  | a0 = cvRound((1.f - fx) * 2048) in float, half to even; row pass r = a0 S[sx] + a1 S[min(sx + 1,
+ *                         |                  | sw - 1)] in int32; the same in y gives b0, b1; the pixel is (((b0 * (r0 >> 4)) >> 16) + ((b1 *
+ *                         |                  | (r1 >> 4)) >> 16) + 2) >> 2.  Parity of this rule with a host's OpenCV build is UNPINNED (DESIGN
+ *                         |                  | section 2).
+ *  features per level     | :429-441         | gl_orb_features_per_level: factor = (float)(1.0 / scale_factor); n = (float)nfeatures * (1 -
+ *                         |                  | factor) / (1 - (float)pow((double)factor, (double)nlevels)) in float; level l < last takes
+ *                         |                  | cvRound(n), then n *= factor; the last level max(nfeatures - sum, 0)
+ *  cells                  | :743-778         | borders 16 and cols - 16 / rows - 16; width = cols - 32 as float, nCols = (int)(width / 30),
+ *                         |                  | wCell = ceil(width / nCols) (<= 59), rows alike; cell (i, j): iniX = 16 + j wCell, maxX = iniX +
+ *                         |                  | wCell + 6 clamped to cols - 16, skipped when iniX >= cols - 16 - 6 (rows: >= rows - 16 - 3)
+ *  what FAST computes     | :782-783         | rows [3, rows - 3), columns [3, cols - 3) of the cell image: these regions tile the level
+ *  segment test           | cv::FAST         | 9 contiguous of the 16 ring pixels of radius 3, all > v + th or all < v - th
+ *  score                  | cv::FAST         | the largest t at which the pixel still passes: the maximum over the 16 arcs of the arc's
+ *                         |                  | minimum of v - p (and of p - v), minus 1; it is the key-point's response
+ *  suppression            | cv::FAST (true)  | kept iff the score is strictly greater than the 8 neighbours'; a neighbour that is no corner at
+ *                         |                  | the current threshold, or outside the cell's region, counts 0
+ *  fallback               | :785-788         | a cell without a key-point at ini_th is redone at min_th
+ *  candidate order        | :763-797         | cells row-major, pixels row-major within a cell
+ *  initial nodes          | :535-572         | nIni = round((float)(maxX - minX) / (maxY - minY)), hX = (float)(maxX - minX) / nIni, edges
+ *                         |                  | (int)(hX * (float)i), assignment (int)(x / hX): float, one rounding per operation, the division
+ *                         |                  | correctly rounded
+ *  DivideNode             | :475-527         | halves ceil((float)(UR.x - UL.x) / 2), ceil((float)(BL.y - UL.y) / 2); x < UL.x + halfX, y < UL.y +
+ *                         |                  | halfY; keys keep their order: a stable 4-way split; a child with one key is bNoMore
+ *  phase-1 sweep          | :594-645         | children pushed to the FRONT, the parent erased: the reversed children, then the bNoMore nodes
+ *  stop tests             | :649, :653, :710 | size >= N_l or size == prevSize; phase 2 when size + 3 nToExpand > N_l
+ *  phase 2                | :655-712         | one node at a time, largest first, break at size >= N_l, repeated until a stop test holds
+ *  final pick             | :720-734         | per node in list order: the key of maximum response, the first of equals
+ *
+ *  Deviations:
+ *   1. a level with nCols < 1 or nRows < 1 (under 62 px) yields no key-points: the reference divides by zero;
+ *   2. nIni < 1 (a level more than twice as tall as wide) yields no key-points: the reference divides by zero;
+ *   3. the initial node index is clamped to nIni - 1;
+ *   4. phase 2 sorts (size, node POINTER) pairs (:664): equal sizes come out in address order, the allocator's choice.  Declared
+ *      instead: among equal sizes the node created last is divided first;
+ *   5. a level with more than cand_cap candidates sets its bit in stat[3] and that image yields n_kp = 0: the reference's list is
+ *      unbounded.
+ *  A level's result can exceed N_l: the first sweep leaves up to 4 nIni nodes whatever N_l is; a later sweep runs only when size +
+ *  3 nToExpand <= N_l, so it ends at or below N_l; phase 2 starts below N_l and a division adds at most 3.  Hence at most
+ *  max(N_l + 2, 4 nIni_l) per level (gl_orb_detect_bound; 0 for a level of deviation 1 or 2).  N below the sum over the levels or
+ *  above GL_ORB_MAX: GL_ERR_ARG.  Also GL_ERR_ARG, nothing written: thresholds outside 1 <= min_th <= ini_th <= 254, cand_cap outside
+ *  1 .. 65 535, a level above 32 767 px or more than 1 024 times as wide as tall, B < 1, a NULL required pointer.
+ *
+ *  The octree's working set per (image, level) is 4 bytes per candidate slot (two uint16 permutations) and 72 bytes per node of
+ *  max_l(bound_l) + 2: in LDS up to 56 KB, beyond that in the main scratch block.  The host time this saves is NOT measured. */
+typedef struct gl_orb_detect_out {
+  int32_t* kp_xy;
+  int32_t* kp_oct;
+  int32_t* n_kp;
+  float* kp_response;
+  int32_t* level_count;
+  int32_t* stat;
+  int32_t* cand_xy;
+  float* cand_resp;
+  int32_t* cand_count;
+} gl_orb_detect_out;
+int gl_orb_pyramid_layout(int width, int height, int nlevels, double scale_factor, int row_pad, int64_t lead, gl_image_pyramid* pyr);
+int gl_orb_pyramid(gl_ctx_t* ctx, int B, const gl_image_pyramid* pyr, double scale_factor);
+int gl_orb_features_per_level(int nfeatures, int nlevels, double scale_factor, int32_t* per_level);
+int gl_orb_detect_bound(const gl_image_pyramid* pyr, int nfeatures, double scale_factor, int32_t* per_level);
+int gl_orb_detect(gl_ctx_t* ctx, int B, int N, const gl_image_pyramid* pyr, int nfeatures, double scale_factor, int ini_th, int min_th, int cand_cap,
+                  const gl_orb_detect_out* out);
 
 /* ---- frame end and hand-over: from one tracked frame to the next on the device ------------------ */
 /* What the reference does between two calls of gl_track_frame_chain_map - the tail of Tracking::track, GMMLoc::needNewKeyFrame,

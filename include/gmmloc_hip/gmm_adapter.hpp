@@ -836,6 +836,150 @@ class GMM {
     check(gl_memcpy_d2h(ctx_, r.stat, out.stat, 8), "d2h");
     return r;
   }
+  // ---- ORB detection: the irregular half of ORBextractor (ComputePyramid, the cell FAST, DistributeOctTree) for ONE raw image on the
+  // device (gl_orb_pyramid, gl_orb_detect; the rules and the declared deviations are in gmmloc_hip.h).  orbExtract is the composite:
+  // the raw image goes up, gl_orb_pyramid -> gl_orb_detect -> gl_orb_describe run on the context's stream with detect's device arrays
+  // as describe's inputs, and nothing is read back before the one synchronise at the end.  orbPyramid and orbDetect run the first one or
+  // two stages alone.
+  struct OrbPyramidHost {
+    std::vector<std::vector<uint8_t>> levels;  // tightly packed
+    std::vector<int32_t> width, height;
+  };
+  struct OrbKeyPoints {
+    std::vector<int32_t> kp_xy;      // n x 2, AT THEIR LEVEL, ROI coordinates
+    std::vector<int32_t> kp_oct;     // n
+    std::vector<float> kp_response;  // n
+    int32_t level_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int32_t stat[4] = {0, 0, 0, 0};  // {candidates, cells redone at min_th, key-points, overflow level mask}
+    OrbFeatures features;            // orbExtract: of the n key-points
+  };
+  struct OrbDetectConfig {
+    int nfeatures = 1000, nlevels = 8;
+    double scale_factor = 1.2;
+    int ini_th = 20, min_th = 7, cand_cap = 8192;
+  };
+  OrbPyramidHost orbPyramid(const ImageLevel& image, int nlevels = 8, double scale_factor = 1.2) {
+    OrbStage s = orb_stage(image, OrbDetectConfig{0, nlevels, scale_factor, 20, 7, 1}, 0);
+    check(gl_ctx_synchronize(ctx_), "sync");
+    OrbPyramidHost r;
+    for (int l = 0; l < nlevels; ++l) {
+      r.width.push_back(s.pyr.width[l]), r.height.push_back(s.pyr.height[l]);
+      r.levels.emplace_back((size_t)s.pyr.width[l] * (size_t)s.pyr.height[l]);
+      check(gl_memcpy_d2h(ctx_, r.levels.back().data(), s.pyr.data + s.pyr.offset[l], r.levels.back().size()), "d2h");
+    }
+    return r;
+  }
+  OrbKeyPoints orbDetect(const ImageLevel& image) { return orbDetect(image, OrbDetectConfig()); }
+  OrbKeyPoints orbDetect(const ImageLevel& image, const OrbDetectConfig& cfg) { return orb_front(image, cfg, nullptr, {}); }
+  OrbKeyPoints orbExtract(const ImageLevel& image, const std::vector<int8_t>& pattern) { return orbExtract(image, pattern, OrbDetectConfig()); }
+  OrbKeyPoints orbExtract(const ImageLevel& image, const std::vector<int8_t>& pattern, const OrbDetectConfig& cfg, std::vector<int32_t> blur_w = {}) {
+    if (pattern.size() != 1024) throw std::runtime_error("orbExtract: the pattern has 512 x 2 entries");
+    for (int8_t v : pattern)
+      if (v < -13 || v > 13) throw std::runtime_error("orbExtract: a pattern entry outside [-13, 13]");
+    if (blur_w.empty()) {
+      blur_w.resize(4);
+      check(gl_orb_default_blur(2.0, blur_w.data()), "gl_orb_default_blur");
+    }
+    if (blur_w.size() != 4) throw std::runtime_error("orbExtract: blur_w has four taps");
+    return orb_front(image, cfg, &pattern, blur_w);
+  }
+
+ private:
+  struct OrbStage {
+    gl_image_pyramid pyr;
+    gl_orb_detect_out det;
+    char* rest;  // behind detect's outputs: describe's
+    size_t N;
+  };
+  // the raw image up, the pyramid built, detect enqueued (stage >= 1); `extra`: bytes kept behind detect's outputs
+  OrbStage orb_stage(const ImageLevel& im, const OrbDetectConfig& cfg, int stage, size_t extra = 0) {
+    if (!im.ptr || im.width < 1 || im.height < 1 || im.stride < im.width) throw std::runtime_error("orb: bad image");
+    OrbStage s{};
+    check(gl_orb_pyramid_layout(im.width, im.height, cfg.nlevels, cfg.scale_factor, 0, 0, &s.pyr), "gl_orb_pyramid_layout");
+    int32_t bound[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    size_t N = 1;
+    if (stage >= 1) {
+      check(gl_orb_detect_bound(&s.pyr, cfg.nfeatures, cfg.scale_factor, bound), "gl_orb_detect_bound");
+      N = 0;
+      for (int l = 0; l < cfg.nlevels; ++l) N += (size_t)bound[l];
+      N = N ? N : 1;
+    }
+    s.N = N;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += (bytes + 63) / 64 * 64;
+      return at;
+    };
+    const size_t o_img = take((size_t)s.pyr.frame_stride), o_xy = take(N * 8), o_oct = take(N * 4), o_resp = take(N * 4), o_n = take(4), o_lc = take(32),
+                 o_stat = take(16), o_rest = take(extra * N + 1024);
+    char* b = pooled(18, off).as<char>();
+    for (int y = 0; y < im.height && im.stride != im.width; ++y)  // level 0: stride = width
+      check(gl_memcpy_h2d(ctx_, b + o_img + (size_t)y * (size_t)im.width, im.ptr + (size_t)y * (size_t)im.stride, (size_t)im.width), "h2d");
+    if (im.stride == im.width) check(gl_memcpy_h2d(ctx_, b + o_img, im.ptr, (size_t)im.width * (size_t)im.height), "h2d");
+    s.pyr.data = reinterpret_cast<uint8_t*>(b + o_img);
+    check(gl_orb_pyramid(ctx_, 1, &s.pyr, cfg.scale_factor), "gl_orb_pyramid");
+    s.det.kp_xy = reinterpret_cast<int32_t*>(b + o_xy);
+    s.det.kp_oct = reinterpret_cast<int32_t*>(b + o_oct);
+    s.det.kp_response = reinterpret_cast<float*>(b + o_resp);
+    s.det.n_kp = reinterpret_cast<int32_t*>(b + o_n);
+    s.det.level_count = reinterpret_cast<int32_t*>(b + o_lc);
+    s.det.stat = reinterpret_cast<int32_t*>(b + o_stat);
+    s.rest = b + o_rest;
+    if (stage >= 1)
+      check(gl_orb_detect(ctx_, 1, (int)N, &s.pyr, cfg.nfeatures, cfg.scale_factor, cfg.ini_th, cfg.min_th, cfg.cand_cap, &s.det), "gl_orb_detect");
+    return s;
+  }
+  OrbKeyPoints orb_front(const ImageLevel& im, const OrbDetectConfig& cfg, const std::vector<int8_t>* pattern, const std::vector<int32_t>& blur_w) {
+    OrbStage s = orb_stage(im, cfg, 1, pattern ? 32 + 4 + 8 + 8 + 16 + 64 : 0);
+    const size_t N = s.N;
+    gl_orb_out out{};
+    if (pattern) {  // describe reads detect's arrays where they lie
+      char* p = s.rest;
+      check(gl_memcpy_h2d(ctx_, p, pattern->data(), 1024), "h2d");
+      gl_orb_in in{};
+      in.kp_xy = s.det.kp_xy, in.kp_oct = s.det.kp_oct, in.n_kp = s.det.n_kp;
+      in.pattern = reinterpret_cast<int8_t*>(p);
+      in.blur_w = blur_w.data();
+      in.scale_factor = cfg.scale_factor;
+      p += 1024;
+      out.desc = reinterpret_cast<uint8_t*>(p), p += (N * 32 + 15) / 16 * 16;
+      out.uv64 = reinterpret_cast<double*>(p), p += N * 16;
+      out.angle = reinterpret_cast<float*>(p), p += (N * 4 + 15) / 16 * 16;
+      out.moments = reinterpret_cast<int32_t*>(p), p += N * 8;
+      out.uv32 = reinterpret_cast<float*>(p), p += N * 8;
+      out.stat = reinterpret_cast<int32_t*>(p);
+      check(gl_orb_describe(ctx_, 1, (int)N, &in, &s.pyr, &out), "gl_orb_describe");
+    }
+    check(gl_ctx_synchronize(ctx_), "sync");
+    OrbKeyPoints r;
+    int32_t n = 0;
+    check(gl_memcpy_d2h(ctx_, &n, s.det.n_kp, 4), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.level_count, s.det.level_count, 32), "d2h");
+    check(gl_memcpy_d2h(ctx_, r.stat, s.det.stat, 16), "d2h");
+    const size_t k = (size_t)n;
+    r.kp_xy.resize(k * 2), r.kp_oct.resize(k), r.kp_response.resize(k);
+    if (k) {
+      check(gl_memcpy_d2h(ctx_, r.kp_xy.data(), s.det.kp_xy, k * 8), "d2h");
+      check(gl_memcpy_d2h(ctx_, r.kp_oct.data(), s.det.kp_oct, k * 4), "d2h");
+      check(gl_memcpy_d2h(ctx_, r.kp_response.data(), s.det.kp_response, k * 4), "d2h");
+    }
+    if (pattern) {
+      OrbFeatures& f = r.features;
+      f.desc.resize(k * 32), f.angle.resize(k), f.moments.resize(k * 2), f.uv32.resize(k * 2), f.uv64.resize(k * 2);
+      if (k) {
+        check(gl_memcpy_d2h(ctx_, f.desc.data(), out.desc, k * 32), "d2h");
+        check(gl_memcpy_d2h(ctx_, f.angle.data(), out.angle, k * 4), "d2h");
+        check(gl_memcpy_d2h(ctx_, f.moments.data(), out.moments, k * 8), "d2h");
+        check(gl_memcpy_d2h(ctx_, f.uv32.data(), out.uv32, k * 8), "d2h");
+        check(gl_memcpy_d2h(ctx_, f.uv64.data(), out.uv64, k * 16), "d2h");
+      }
+      check(gl_memcpy_d2h(ctx_, f.stat, out.stat, 8), "d2h");
+    }
+    return r;
+  }
+
+ public:
   // GMMLoc::processKeyFrame's GMM half for key-frame kf_row of the resident map, whose own table rows the host has uploaded (the rows
   // of kf_pose / kf_twc / kf_uvr / kf_oct in the views of setResidentMap, and the arrays below): gl_search2d -> gl_create_stereo_points ->
   // gl_map_add (the key-frame becomes valid, the new rows, their attach triples; the counts stay on the device) -> gl_update_map_points

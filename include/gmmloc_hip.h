@@ -1684,7 +1684,11 @@ int gl_orb_default_blur(double sigma, int32_t* w);
  * that a frame enters as its raw image: gl_orb_pyramid -> gl_orb_detect -> gl_orb_describe on one stream, the outputs of one the
  * inputs of the next, nothing read back (orb.extract, GMM::orbExtract).  Asynchronous on the context's stream, device pointers only.
  * Integer outputs of a sequential rule: a second run gives the same bytes.  The sequential model is tests/orb_detect_ref.py, the
- * hand-built cases tests/orb_detect_cases.py.
+ * hand-built cases tests/orb_detect_cases.py.  tests/test_orb_detect_ref_pin.py holds both to the reference's OWN ComputePyramid,
+ * ComputeKeyPointsOctTree, DistributeOctTree, DivideNode and detect() (oracle/orb_detect_ref.cpp), tests/test_gpu_orb_detect_ref.py the
+ * device: every row below from `features per level` to `final pick` and the level sizes are PINNED wherever the reference is determinate
+ * (deviation 4).  The rows `resize`, `segment test`, `score`, `suppression` and cvRound's half-to-even stay DECLARED: they are
+ * OpenCV's, which is not at hand, and the stand-in answers them with this project's own statement.
  *
  * gl_orb_pyramid_layout (host only) fills the geometry of a pyramid of `nlevels` levels of a width x height image: stride = width[l] +
  * row_pad, `lead` bytes in front of level 0, levels one behind the other, frame_stride their end; `data` is kept.
@@ -1739,11 +1743,20 @@ int gl_orb_default_blur(double sigma, int32_t* w);
  *  final pick             | :720-734         | per node in list order: the key of maximum response, the first of equals
  *
  *  Deviations:
- *   1. a level with nCols < 1 or nRows < 1 (under 62 px) yields no key-points: the reference divides by zero;
- *   2. nIni < 1 (a level more than twice as tall as wide) yields no key-points: the reference divides by zero;
+ *   1. a level with nCols < 1 or nRows < 1 (under 62 px) yields no key-points.  The reference's divisions there are FLOAT divisions
+ *      (:760-761, width / nCols): they give infinity and trap nothing; converting ceil(inf) to int is undefined, and the value is not
+ *      used: with nRows = 0 the row loop does not run, with nCols = 0 the column loop does not.  Run under g++ 11.4 -O2 on x86-64 the
+ *      reference makes no FAST call and returns no key-point on 61 x 92, 92 x 61 and 61 x 61 (tests/test_orb_detect_ref_pin.py), which is
+ *      what is stated here - a statement of the outcome, not of a defined behaviour;
+ *   2. nIni < 1 (a level more than twice as tall as wide) yields no key-points.  The reference's hX = (float)(maxX - minX) / 0 is
+ *      infinity and vpIniNodes is empty (:535-542): without a key it returns nothing, as here; its first key indexes element
+ *      (int)(x / inf) = 0 of the empty vector (:559), out of range.  That case is never run against it;
  *   3. the initial node index is clamped to nIni - 1;
- *   4. phase 2 sorts (size, node POINTER) pairs (:664): equal sizes come out in address order, the allocator's choice.  Declared
- *      instead: among equal sizes the node created last is divided first;
+ *   4. phase 2 sorts (size, node POINTER) pairs (:664): equal sizes come out in address order, the allocator's choice - two runs of
+ *      one binary on one input differ.  Declared instead: among equal sizes the node created last is divided first.  Against the
+ *      reference's own DistributeOctTree (g++ 11.4, glibc 2.35) the declared order is one of the orders it can take
+ *      and no more: on dense 256 x 224 scenes nearly every level has such a tie, and the declared answer was the host's on few of
+ *      them.  Where no sort sees equal sizes the reference's answer is determinate and equals this rule's in order (pinned);
  *   5. a level with more than cand_cap candidates sets its bit in stat[3] and that image yields n_kp = 0: the reference's list is
  *      unbounded.
  *  A level's result can exceed N_l: the first sweep leaves up to 4 nIni nodes whatever N_l is; a later sweep runs only when size +

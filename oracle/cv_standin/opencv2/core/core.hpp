@@ -13,10 +13,14 @@
 //   cv::fastAtan2    DECLARED here, defined in cv_standin/fast_atan2.cpp (the
 //                    rule of include/gmmloc_hip.h, one IEEE operation per
 //                    step; that file is always compiled -ffp-contract=off)
-//   cv::FAST, resize, copyMakeBorder, GaussianBlur, KeyPointsFilter: present
-//                    so that the extractor's detection half compiles; every
-//                    call throws - the pyramid, FAST, the octree and
-//                    OpenCV's blur are not what is pinned
+//   cv::FAST, resize, GaussianBlur: DECLARED here, defined in
+//                    cv_standin/hooks.cpp: each calls through a function
+//                    pointer whose default throws "not provided" - OpenCV's
+//                    FAST, resize and blur are nobody's to pin here; a wrapper
+//                    sets the pointers so that the reference's code AROUND
+//                    them runs (oracle/orb_detect_ref.cpp)
+//   cv::copyMakeBorder  BORDER_REFLECT_101, in cv_standin/hooks.cpp
+//   cv::KeyPointsFilter present so that ComputeKeyPointsOld compiles; throws
 //   cv::FileStorage  present so that the YAML save / load members compile:
 //   cv::FileNode     never open, every use throws
 // The standard headers at the end of the list are the ones the reference's
@@ -121,8 +125,23 @@ class Mat {
     data = store_->data();
   }
   void create(Size s, int type) { create(s.height, s.width, type); }
-  static Mat zeros(int r, int c, int type) { return Mat(r, c, type); }  // (a new store is value-initialised)
-  static Mat zeros(Size s, int type) { return Mat(s, type); }
+  // Mat::zeros is an EXPRESSION as in OpenCV: assigned to a matrix that already has its size and type it is written INTO that matrix
+  // (create() leaves it as it lies), so a row range of a larger matrix stays a view of it - ORBextractor::detect relies on that
+  // (:1033-1034, :981).  Elsewhere it makes a new store.
+  struct Zeros {
+    int rows, cols, type;
+  };
+  static Zeros zeros(int r, int c, int type) { return Zeros{r, c, type}; }
+  static Zeros zeros(Size s, int type) { return Zeros{s.height, s.width, type}; }
+  Mat(const Zeros& z) { *this = z; }
+  Mat& operator=(const Zeros& z) {
+    create(z.rows, z.cols, z.type);
+    for (int r = 0; r < rows; ++r) std::memset(data + (size_t)r * step, 0, (size_t)cols * elem_size(type_));
+    return *this;
+  }
+  // where this matrix lies in the store it shares (a wrapper reports a view's offset with these); caller memory has no store
+  const unsigned char* standin_store_begin() const { return store_ ? store_->data() : nullptr; }
+  size_t standin_store_size() const { return store_ ? store_->size() : 0; }
   Mat clone() const {  // compact, whatever the step of this one
     Mat m;
     if (data) {
@@ -192,10 +211,26 @@ enum { BORDER_REFLECT_101 = 4, BORDER_ISOLATED = 16 };
 enum { INTER_LINEAR = 1 };
 
 inline void standin_not_provided(const char* what) { throw std::runtime_error(std::string("cv stand-in: ") + what + " is not provided"); }
-inline void FAST(const Mat&, std::vector<KeyPoint>&, int, bool = true) { standin_not_provided("FAST"); }
-inline void resize(const Mat&, Mat, Size, double = 0, double = 0, int = INTER_LINEAR) { standin_not_provided("resize"); }
-inline void copyMakeBorder(const Mat&, Mat, int, int, int, int, int) { standin_not_provided("copyMakeBorder"); }
-inline void GaussianBlur(const Mat&, Mat, Size, double, double = 0, int = BORDER_REFLECT_101) { standin_not_provided("GaussianBlur"); }
+// DECLARED here, defined in cv_standin/hooks.cpp.  FAST, resize and GaussianBlur call through the pointers below, whose default throws
+// "not provided": a wrapper that wants the extractor's detection half to run sets them.  The destination is an output array as OpenCV
+// has it: created at the size asked for, which leaves a destination of that size - a view into a larger matrix included - as it lies.
+// This stand-in takes it by value, so a destination of ANOTHER size cannot be handed back and throws.
+//   FAST            hook(image view, key-points, threshold, nonmax): the view's data / step tell where in its parent it lies
+//   resize          hook(src, dst): dst has the size asked for; INTER_LINEAR only
+//   GaussianBlur    hook(src, dst, ksize, sigma): src is a compact copy, so the call may be in place; square kernels only
+//   copyMakeBorder  implemented: BORDER_REFLECT_101, with or without BORDER_ISOLATED (the source is never read beyond its own range,
+//                   which is what OpenCV does for a matrix that is no view and for an ISOLATED view).  A destination that already
+//                   holds the source as its view at (top, left) keeps those bytes; only the border is written.
+typedef void (*standin_fast_fn)(const Mat& image, std::vector<KeyPoint>& keypoints, int threshold, bool nonmax);
+typedef void (*standin_resize_fn)(const Mat& src, Mat& dst);
+typedef void (*standin_blur_fn)(const Mat& src, Mat& dst, int ksize, double sigma);
+extern standin_fast_fn standin_fast;
+extern standin_resize_fn standin_resize;
+extern standin_blur_fn standin_blur;
+void FAST(const Mat& image, std::vector<KeyPoint>& keypoints, int threshold, bool nonmax = true);
+void resize(const Mat& src, Mat dst, Size size, double fx = 0, double fy = 0, int interpolation = INTER_LINEAR);
+void copyMakeBorder(const Mat& src, Mat dst, int top, int bottom, int left, int right, int type);
+void GaussianBlur(const Mat& src, Mat dst, Size ksize, double sigma_x, double sigma_y = 0, int border = BORDER_REFLECT_101);
 class KeyPointsFilter {
  public:
   static void retainBest(std::vector<KeyPoint>&, int) { standin_not_provided("KeyPointsFilter::retainBest"); }

@@ -402,6 +402,152 @@ class OrbRef:
         lib.orbref_orientation.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 3
         lib.orbref_describe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.orbref_steering.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._detect_half = hasattr(lib, "orbref_distribute")  # (a library built before the detection half was wrapped has none of it)
+        if self._detect_half:
+            lib.orbref_last_error.restype = C.c_char_p
+            lib.orbref_set_hooks.argtypes = [self.FAST_CB, self.RESIZE_CB, self.BLUR_CB]
+            lib.orbref_set_hooks.restype = None
+            lib.orbref_fast_calls.argtypes = [C.c_void_p, C.c_int]
+            lib.orbref_features_per_level.argtypes = [C.c_int, C.c_void_p]
+            lib.orbref_distribute.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int]
+            lib.orbref_pyramid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int]
+            lib.orbref_pyramid_info.argtypes = [C.c_void_p]
+            lib.orbref_level_pixels.argtypes = [C.c_int, C.c_int, C.c_void_p]
+            lib.orbref_overwrite_borders.argtypes = [C.c_int]
+            lib.orbref_set_levels.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]
+            lib.orbref_key_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            lib.orbref_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        self._hooks = self._raised = self._levels = None
+
+    # ---- the detection half and detect() (oracle/orb_detect_ref.cpp).  cv::FAST, cv::resize and cv::GaussianBlur reach the test as
+    # callbacks; an exception inside one never crosses a C++ frame: it is kept, the callback returns empty, and the method that made
+    # the call raises it after the call has returned.
+    FAST_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                          C.POINTER(C.c_float))
+    RESIZE_CB = C.CFUNCTYPE(None, C.POINTER(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int64, C.c_int, C.c_int)
+    BLUR_CB = C.CFUNCTYPE(None, C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double)
+    KP = ("x", "y", "octave", "size", "response", "angle")  # the columns of a key-point row
+
+    @staticmethod
+    def _view(ptr, step, cols, rows):
+        """the rows x cols bytes at ptr with `step` bytes per row, as they lie"""
+        flat = np.ctypeslib.as_array(ptr, shape=((rows - 1) * step + cols,))
+        return np.lib.stride_tricks.as_strided(flat, (rows, cols), (step, 1))
+
+    def set_hooks(self, fast=None, resize=None, blur=None):
+        """fast(level, x0, y0, view, threshold, nonmax) -> [(x, y, response)] in the view's coordinates; resize(src, (rows, cols)) -> the
+        level; blur(src, ksize, sigma) -> the blurred level.  None: FAST finds nothing, the other two are "not provided"."""
+        assert self._detect_half, "oracle/_ref/liborb_ref.so was built without the detection half: run make -C oracle"
+
+        def kept(f, empty):
+            def call(*a):
+                try:
+                    return f(*a)
+                except BaseException as e:  # noqa: B902 (kept and raised by _done; nothing may cross the C++ frames)
+                    self._raised = self._raised or e
+                    return empty
+            return call
+
+        def c_fast(level, x0, y0, data, step, cols, rows, th, nonmax, cap, out):
+            keys = fast(level, x0, y0, self._view(data, step, cols, rows), th, bool(nonmax))
+            assert len(keys) <= cap
+            for i, (x, y, r) in enumerate(keys):
+                out[3 * i], out[3 * i + 1], out[3 * i + 2] = float(x), float(y), float(r)
+            return len(keys)
+
+        def c_resize(src, sstep, scols, srows, dst, dstep, dcols, drows):
+            self._view(dst, dstep, dcols, drows)[:] = resize(self._view(src, sstep, scols, srows), (drows, dcols))
+
+        def c_blur(src, sstep, dst, dstep, cols, rows, ksize, sigma):
+            self._view(dst, dstep, cols, rows)[:] = blur(self._view(src, sstep, cols, rows), ksize, sigma)
+
+        self._hooks = (self.FAST_CB(kept(c_fast, 0)) if fast else self.FAST_CB(), self.RESIZE_CB(kept(c_resize, None)) if resize else self.RESIZE_CB(),
+                       self.BLUR_CB(kept(c_blur, None)) if blur else self.BLUR_CB())
+        self.lib.orbref_set_hooks(*self._hooks)
+
+    def _done(self, n):
+        """after a call: the exception that a callback kept, the wrapper's own error, else the call's return value"""
+        raised, self._raised = self._raised, None
+        if raised is not None:
+            raise raised
+        if n < 0:
+            raise RuntimeError("liborb_ref: " + self.lib.orbref_last_error().decode())
+        return n
+
+    def fast_calls(self, reset=True):
+        """the FAST calls since the last reset, in order -> (n, 7) i32 {level, x0, y0, cols, rows, threshold, nonmax}"""
+        n = self.lib.orbref_fast_calls(None, 0)
+        out = np.zeros((n, 7), np.int32)
+        self.lib.orbref_fast_calls(_p(out), n)
+        if reset:
+            self.lib.orbref_fast_reset()
+        return out
+
+    def features_per_level(self, nfeatures):
+        """mnFeaturesPerLevel of ORBextractor(nfeatures) -> list"""
+        out = np.zeros(8, np.int32)
+        n = self._done(self.lib.orbref_features_per_level(int(nfeatures), _p(out)))
+        return out[:n].tolist()
+
+    def distribute(self, keys, min_x, max_x, min_y, max_y, N):
+        """DistributeOctTree: keys [(x, y, response)] relative to (min_x, min_y) -> vResultKeys in order, [(x, y, response)] as ints.
+        nIni >= 1 is the caller's to see to (deviation 2: the reference indexes an empty vector there)"""
+        k = np.ascontiguousarray(keys, dtype=np.float32).reshape(-1, 3)
+        assert int(np.floor(float(np.float32(max_x - min_x) / np.float32(max_y - min_y)) + 0.5)) >= 1 or len(k) == 0
+        cap = len(k) + 1
+        out = np.zeros((cap, 3), np.float32)
+        n = self._done(self.lib.orbref_distribute(_p(k), len(k), min_x, max_x, min_y, max_y, int(N), _p(out), cap))
+        assert n < cap and np.array_equal(out[:n], np.rint(out[:n]))
+        return [tuple(int(v) for v in row) for row in out[:n]]
+
+    def pyramid(self, image, nfeatures=1000):
+        """a new extractor and ComputePyramid(image) -> [dict(shape (rows, cols), step, offset, store, pixels (the view), whole (the
+        matrix the view was cut from, (rows + 38) x step as the reference made it))] per level"""
+        self._done(self.lib.orbref_pyramid(*self._level(image), int(nfeatures)))
+        return self.levels()
+
+    def levels(self):
+        info = np.zeros((8, 6), np.int32)
+        n = self._done(self.lib.orbref_pyramid_info(_p(info)))
+        out = []
+        for l in range(n):
+            rows, cols, step, offset, store = (int(v) for v in info[l, :5])
+            pixels, whole = np.zeros((rows, cols), np.uint8), np.zeros(store, np.uint8)
+            self._done(self.lib.orbref_level_pixels(l, 0, _p(pixels)))
+            if store:
+                self._done(self.lib.orbref_level_pixels(l, 1, _p(whole)))
+            out.append(dict(shape=(rows, cols), step=step, offset=offset, store=store, pixels=pixels, whole=whole))
+        return out
+
+    def overwrite_borders(self, seed):
+        """every byte of every level's matrix outside the level's view takes another value -> bytes written"""
+        return self._done(self.lib.orbref_overwrite_borders(int(seed)))
+
+    def set_levels(self, levels, per_level, ini_th=20, min_th=7, nfeatures=1000):
+        """a new extractor whose pyramid is `levels` (2-D uint8, rows may be strided), with the thresholds and mnFeaturesPerLevel given"""
+        self._levels = [l if l.flags["C_CONTIGUOUS"] or l.strides[1] == 1 else np.ascontiguousarray(l) for l in levels]  # (kept alive)
+        n = len(self._levels)
+        args = [self._level(l) for l in self._levels]
+        data = (C.c_void_p * n)(*[a[0] for a in args])
+        w, h = np.array([a[1] for a in args], np.int32), np.array([a[2] for a in args], np.int32)
+        st, per = np.array([a[3] for a in args], np.int64), np.ascontiguousarray(per_level, dtype=np.int32)
+        assert len(per) == n
+        self._done(self.lib.orbref_set_levels(int(nfeatures), n, data, _p(w), _p(h), _p(st), int(ini_th), int(min_th), _p(per)))
+
+    def key_points(self, cap=20000):
+        """ComputeKeyPointsOctTree on the pyramid of the last pyramid() / set_levels() / detect() -> (level_count (8,) i32, key-points
+        (n, 6) f32 with the columns KP, level by level)"""
+        count, kp = np.zeros(8, np.int32), np.zeros((cap, 6), np.float32)
+        n = self._done(self.lib.orbref_key_points(_p(count), _p(kp), cap))
+        assert n <= cap
+        return count, kp[:n].copy()
+
+    def detect(self, image, nfeatures, cap=20000):
+        """a new extractor and the whole detect(image) -> (_keypoints (n, 6) f32 with the columns KP, _descriptors (n, 32) u8)"""
+        kp, desc = np.zeros((cap, 6), np.float32), np.zeros((cap, 32), np.uint8)
+        n = self._done(self.lib.orbref_detect(*self._level(image), int(nfeatures), _p(kp), _p(desc), cap))
+        assert n <= cap
+        return kp[:n].copy(), desc[:n].copy()
 
     @staticmethod
     def _level(img):

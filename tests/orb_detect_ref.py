@@ -252,9 +252,33 @@ class List:
             n = n.next
 
 
-def distribute(keys, min_x, max_x, min_y, max_y, N, mut=()):
-    """DistributeOctTree (:529-737).  keys: [(x, y, response)] relative to (min_x, min_y), in vToDistributeKeys' order -> vResultKeys"""
+def nth_permutation(k, n):
+    """the k-th permutation of range(n) in lexicographic order (0: the identity)"""
+    items, out = list(range(n)), []
+    for i in range(n, 0, -1):
+        q, k = divmod(k, math.factorial(i - 1))
+        out.append(items.pop(q))
+    return out
+
+
+def distribute(keys, min_x, max_x, min_y, max_y, N, mut=(), info=None, tie_order=None):
+    """DistributeOctTree (:529-737).  keys: [(x, y, response)] relative to (min_x, min_y), in vToDistributeKeys' order -> vResultKeys
+    info: a dict that is filled with what happened -
+      tie         a phase-2 sort (:664) saw two entries of equal size: the reference's order there is the allocator's (deviation 4)
+      sorts       the phase-2 sorts that held two or more entries
+      walked      the most nodes that one phase-2 pass divided
+      end         "sweep N" (:649, size >= N), "sweep same" (:649, size == prevSize), "phase 2 N" / "phase 2 same" (:710)
+      sweeps      the sweeps of phase 1 that ran
+      phase1      the list's size when phase 1 ended: no result is shorter, whatever the order among equal sizes
+      n_ini       nIni
+      groups      the sizes of the equal-size groups of two or more that phase 2 REACHED, in the order it reached them
+    tie_order: None - the declared order among equal sizes; else a list of choices, one per reached group in that order: the group is
+      walked in the choice-th permutation (lexicographic) of its declared order; groups beyond the list take choice 0"""
+    if info is None:
+        info = {}
+    info.update(tie=False, sorts=0, walked=0, end=None, sweeps=0, phase1=0, n_ini=0, groups=[])
     n_ini = int(math.floor(float(f32(max_x - min_x) / f32(max_y - min_y)) + 0.5))  # :535, round() of a positive float
+    info["n_ini"] = n_ini
     if n_ini < 1:  # deviation 2
         return []
     h_x = f32(max_x - min_x) / f32(n_ini)
@@ -304,23 +328,48 @@ def distribute(keys, min_x, max_x, min_y, max_y, N, mut=()):
                     add(c, to_expand)
             n_to_expand += len(to_expand) - before
             n = nodes.erase(n)
+        info["sweeps"] += 1
+        info["phase1"] = nodes.size
         if nodes.size >= N or nodes.size == prev_size:  # :649
             finish = True
+            info["end"] = "sweep N" if nodes.size >= N else "sweep same"
         elif nodes.size + n_to_expand * 3 > N:  # :653
             while not finish:
                 prev_size = nodes.size
                 prev, to_expand = to_expand, []
                 # :664 sorts (size, pointer) and walks from the back.  Deviation 4: among equal sizes the node created last goes first
                 prev.sort(key=lambda n: (len(n.keys), -n.born if "tie_rev" in mut else n.born))
-                for n in reversed(prev):
-                    for c in n.divide(mut):
-                        if c.keys:
-                            add(c, to_expand)
-                    nodes.erase(n)
-                    if nodes.size >= N:  # :706
+                sizes = [len(n.keys) for n in prev]
+                info["sorts"] += len(prev) >= 2
+                info["tie"] = info["tie"] or len(set(sizes)) < len(sizes)
+                walk, walked = prev[::-1], 0
+                i = 0
+                while i < len(walk):
+                    j = i
+                    while j < len(walk) and len(walk[j].keys) == len(walk[i].keys):
+                        j += 1
+                    if j - i > 1:  # a group of equal sizes is reached: its order is the caller's choice, the declared one by default
+                        at = len(info["groups"])
+                        info["groups"].append(j - i)
+                        if tie_order is not None and at < len(tie_order):
+                            walk[i:j] = [walk[i + q] for q in nth_permutation(tie_order[at], j - i)]
+                    stop = False
+                    for n in walk[i:j]:
+                        walked += 1
+                        for c in n.divide(mut):
+                            if c.keys:
+                                add(c, to_expand)
+                        nodes.erase(n)
+                        if nodes.size >= N:  # :706
+                            stop = True
+                            break
+                    if stop:
                         break
+                    i = j
+                info["walked"] = max(info["walked"], walked)
                 if nodes.size >= N or nodes.size == prev_size:  # :710
                     finish = True
+                    info["end"] = "phase 2 N" if nodes.size >= N else "phase 2 same"
     out = []
     for n in nodes:  # :720-734
         best = n.keys[0]
@@ -342,9 +391,11 @@ def level_bound(width, height, n_level):
 
 def detect(levels, nfeatures, scale_factor=1.2, ini_th=20, min_th=7, cand_cap=None, mut=()):
     """gl_orb_detect for ONE image: levels - its pyramid, 2-D uint8 arrays.  -> dict(kp_xy n x 2, kp_oct n, kp_response n, level_count 8,
-    stat 4, cand [per level: m x 3 (x, y, score)], cand_count 8)"""
+    stat 4, cand [per level: m x 3 (x, y, score)], cand_count 8, tie [per level: a phase-2 sort saw two equal sizes, so the reference's
+    order on that level is its allocator's], sorts [per level: the phase-2 sorts of two or more entries])"""
     per_level = features_per_level(nfeatures, len(levels), scale_factor, mut)
     xy, octs, resp, level_count, cand, fell, mask = [], [], [], [0] * 8, [], 0, 0
+    tie, sorts = [False] * len(levels), [0] * len(levels)
     for l, img in enumerate(levels):
         h, w = img.shape
         keys, f = candidates(img, ini_th, min_th, mut)
@@ -354,7 +405,9 @@ def detect(levels, nfeatures, scale_factor=1.2, ini_th=20, min_th=7, cand_cap=No
             mask |= 1 << l
             continue
         rel = [(x - MIN_BORDER, y - MIN_BORDER, s) for x, y, s in keys]
-        res = distribute(rel, MIN_BORDER, w - MIN_BORDER, MIN_BORDER, h - MIN_BORDER, per_level[l], mut) if keys else []
+        info = {}
+        res = distribute(rel, MIN_BORDER, w - MIN_BORDER, MIN_BORDER, h - MIN_BORDER, per_level[l], mut, info) if keys else []
+        tie[l], sorts[l] = bool(info.get("tie")), int(info.get("sorts", 0))
         for x, y, s in res:  # :813-816
             xy.append((x + MIN_BORDER, y + MIN_BORDER))
             octs.append(l)
@@ -365,4 +418,4 @@ def detect(levels, nfeatures, scale_factor=1.2, ini_th=20, min_th=7, cand_cap=No
     cand_count = [len(c) for c in cand] + [0] * (8 - len(cand))
     return dict(kp_xy=np.array(xy, np.int32).reshape(-1, 2), kp_oct=np.array(octs, np.int32), kp_response=np.array(resp, np.float32),
                 level_count=np.array(level_count, np.int32), stat=np.array([sum(cand_count), fell, len(octs), mask], np.int32), cand=cand,
-                cand_count=np.array(cand_count, np.int32))
+                cand_count=np.array(cand_count, np.int32), tie=tie, sorts=sorts)
